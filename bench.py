@@ -1,15 +1,21 @@
 #!/usr/bin/env python3
 """Headline benchmark: B-scans/s of one TRAINING step of the 256x512x1, 3-class U-Net (fwd + Dice loss +
 bwd + gradient all-reduce + Adam), per-rank batch 32 (BASELINE.json configs[1]; configs[3] at N>1: weak
-scaling, global batch 32*N), fp32, synthetic scans, random-init weights.  Also reports inference ms/B-scan
-(hipGraph forward alone, and end to end with the host min-path post-process: BASELINE configs[4]).
+scaling, global batch 32*N), fp32, synthetic scans, random-init weights.  With ``--full`` also reports inference
+ms/B-scan (hipGraph forward alone, and end to end with the host min-path post-process: BASELINE configs[4]).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 With N>1 and no WORLD_SIZE in the environment the script starts its own N ranks (``torch.distributed.run``,
 one per GPU, RCCL) as a child process -- decided before anything touches the GPU -- and exits with its code.
 
-Prints ONE JSON line on rank 0 (contract in the task brief) with
+A plain run sets up, runs W untimed and K timed train steps and prints ONE JSON line on rank 0: the headline
+``value`` (B-scans/s), ``ms_per_step`` (wall time of the K timed steps / K), the per-step HIP-event median / minimum, the
+final loss and the whole-step roofline context computed from the timed steps (``step_vs_roofline``, no run of its own).
+``--dump-outputs DIR`` then writes what the last timed step handed its caller (``dump_outputs``); the inputs are
+seeded, so two builds run with the same arguments can be compared array for array.
+
+``--full`` adds every other leg to the record (each one runs after the timed steps and the dump):
   * ``roofline``: the dominant SOURCE kernel (template instantiations grouped), measured live with HIP events on
     the launch stream by the library's own per-launch profiler, plus ``step_frac`` (whole step vs the SURVEY A.3
     roofline of THIS run's shape/dtype) and ``traffic_ratio`` (PMC bytes / algorithmic bytes per step, from the
@@ -20,7 +26,10 @@ Prints ONE JSON line on rank 0 (contract in the task brief) with
     extra leg then creates a ONE-rank RCCL communicator and drives the same exchange step through it
     (``--no-collective-leg`` skips it, ``--force-collective`` puts it inside the timed region instead);
   * ``fit``: B-scans/s of ``Model.fit`` fed by ``DataGenerator`` from a uint8 array set (host gather -> pinned double
-    buffer -> H2D -> step), i.e. the real training loop beside the resident-input ``value``.
+    buffer -> H2D -> step), i.e. the real training loop beside the resident-input ``value``;
+  * ``inference_ms_per_scan`` (hipGraph forward, batch ``--infer-batch``) and the end-to-end inference fields of
+    ``evaluation.pipeline.bench_fields``.
+The ``--no-*`` options switch single legs off inside a ``--full`` run.
 """
 import argparse
 import glob
@@ -201,6 +210,25 @@ def family(kernel_name):
     return kernel_name.split("<")[0]
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(path, loss4, eng):
+    """What the timed path hands its caller after the last timed step, one float32 ``<name>.npy`` each: ``loss`` (the
+    step's [dice_loss_macro, dice_loss_micro, dice_coef_macro, dice_coef_micro]), ``grads`` (its all-reduced gradient),
+    ``params`` (after its Adam update) and ``state`` (BN moving statistics after its forward).  An array that would take
+    the files over 64 MB in all is replaced by a fixed, seeded sample of its entries (the same for every run)."""
+    import numpy as np
+    arrays = {"loss": loss4, "grads": eng.grads, "params": eng.params, "state": eng.state}
+    arrays = {k: v.detach().float().reshape(-1).cpu().numpy() for k, v in arrays.items()}
+    cap = DUMP_BUDGET_BYTES // (4 * len(arrays))
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        if a.size > cap:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))]
+        np.save(os.path.join(path, f"{name}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -227,7 +255,16 @@ def main():
     ap.add_argument("--no-fit", action="store_true", help="skip the Model.fit / DataGenerator throughput leg")
     ap.add_argument("--fit-scans", type=int, default=8192,
                     help="uint8 scans in the Model.fit leg's array set (one timed epoch; an epoch carries ~20 ms of fixed cost)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline figure: one-rank RCCL leg / all-reduce timing, inference, "
+                         "per-kernel profile and roofline, end-to-end inference, Model.fit, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, grads, params, BN state) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_profile and not args.full:
+        ap.error("--dump-profile needs --full (the per-launch profile is one of its legs)")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:      # (the rehearsal flag travels to the ranks in the environment)
         sys.exit(spawn_ranks(args.gpus))
@@ -254,6 +291,7 @@ def main():
     torch.cuda.set_device(dev)
     B, H, W, C, P = args.batch, args.height, args.width, args.classes, args.pool_layers
 
+    # (max_batch covers the inference batch in a plain run too: the timed steps run on the same handle either way)
     eng = UNetEngine(device=dev, input_channels=1, num_classes=C, image_height=H, image_width=W,
                      max_batch=max(B, 1 if args.no_inference else args.infer_batch), training=True,
                      seed=1000 + rank, init_seed=0, pool_layers=P,
@@ -267,7 +305,7 @@ def main():
     lab = torch.from_numpy(np.tile(labels[..., 0], (reps, 1, 1))[:B].copy()).to(dev)
     overlap = parallel.collective_active() and not args.no_overlap
     reducer = parallel.GradReducer(eng, overlap=overlap)
-    rccl = parallel.describe() if parallel.collective_active() else None
+    rccl = parallel.describe() if args.full and parallel.collective_active() else None
 
     def train_step():
         eng.forward(x, training=True, labels=lab, want_probs=False)
@@ -299,6 +337,8 @@ def main():
         cfg_label = "custom (not a BASELINE configuration)"
     final_loss = float(loss4[0])
     mm = eng.mfma_mode_name()
+    if args.dump_outputs and rank == 0:      # before any --full leg runs further steps on the same handle
+        dump_outputs(args.dump_outputs, loss4, eng)
 
     out = {
         "metric": f"B-scans/sec (train step), {H}x{W} {C}-class U-Net", "value": round(scans_per_s, 2),
@@ -334,7 +374,7 @@ def main():
         out["allreduce"] = dict(rccl, in_timed_region=True, overlap=bool(overlap), grad_floats=int(eng.grads.numel()),
                                 tail_offset=int(eng.grad_tail_offset()))
         out["allreduce"]["us_per_step"] = time_collectives(reducer, 10)
-    elif world == 1 and not args.no_collective_leg and not rehearsal:
+    elif args.full and world == 1 and not args.no_collective_leg and not rehearsal:
         try:
             import socket as _s
             with _s.socket() as sk:
@@ -365,7 +405,7 @@ def main():
                 pass
 
     # ---- inference: hipGraph-replayed forward (+argmax), batch 128, inputs resident ----
-    if not args.no_inference:
+    if args.full and not args.no_inference:
         IB = args.infer_batch
         xi = torch.from_numpy(np.tile(images, ((IB + nd - 1) // nd, 1, 1, 1))[:IB]).to(dev)
         eng.graph_capture(xi, want_probs=True, want_argmax=True)
@@ -384,7 +424,7 @@ def main():
     es = 4 if args.act_dtype == "f32" else 2
     cm = cost_model(H, W, C, 8, P, 2, es, PEAK_F32_TFLOPS if es == 4 else PEAK_BF16_TFLOPS)
     achieved_us = dt / args.steps / B * 1e6
-    if rank == 0 and not args.no_profile:
+    if args.full and rank == 0 and not args.no_profile:
         # per-launch HIP-event profile of 3 further (untimed) steps, on the launch stream
         eng.profile_begin()
         nprof = 3
@@ -481,18 +521,18 @@ def main():
                                "roofline_us_per_scan": round(cm["train_us"], 2),
                                "frac": round(cm["train_us"] / achieved_us, 4),
                                "inference_roofline_us_per_scan": round(cm["fwd_us"], 2)}
-    if rank == 0 and world == 1 and not args.no_inference and os.environ.get("OCT_BENCH_NO_E2E") != "1":
+    if args.full and rank == 0 and world == 1 and not args.no_inference and os.environ.get("OCT_BENCH_NO_E2E") != "1":
         try:
             from oct_image_segmentation_models_amd.evaluation import pipeline
             out.update(pipeline.bench_fields(eng, images, C, labels_u8=labels[..., 0]))
         except ImportError:
             pass
-    if rank == 0 and world == 1 and not args.no_fit and not args.no_inference and args.act_dtype == "f32":
+    if args.full and rank == 0 and world == 1 and not args.no_fit and not args.no_inference and args.act_dtype == "f32":
         try:
             out["fit"] = fit_throughput(eng, H, W, C, P, B, args.fit_scans, scans_per_s)
         except Exception as e:      # noqa: BLE001
             out["fit"] = {"error": f"{type(e).__name__}: {e}"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(H, W, C, P)
     if rank == 0:
         if rehearsal:

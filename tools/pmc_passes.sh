@@ -12,7 +12,7 @@ i=0
 for C in "$@"; do
   i=$((i+1))
   # hard per-pass limit: a counter set the hardware cannot collect makes rocprofv3 abort and then hang in its finalizer
-  timeout -k 10 ${PASS_TIMEOUT:-180} rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/pass$i -- python3 $ROOT/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-profile --infer-batch 32 ${BENCH_EXTRA:-} > $OUT/pass$i.log 2>&1 || { tail -5 $OUT/pass$i.log; exit 1; }
+  timeout -k 10 ${PASS_TIMEOUT:-180} rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/pass$i -- python3 $ROOT/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-profile --infer-batch 32 ${BENCH_EXTRA:-} > $OUT/pass$i.log 2>&1 || { tail -5 $OUT/pass$i.log; exit 1; }
   echo "pass $i done: $C"
   find $OUT/pass$i -name '*kernel_trace.csv' -delete
 done

@@ -9,7 +9,7 @@ OUT=$ROOT/gpurun_out/prof_$TAG
 rm -rf $OUT            # (gpurun merges gpurun_out/ back: without this, older runs' traces pile up beside the new ones)
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python3 $ROOT/bench.py --steps 20 --warmup 5 --dump-profile $OUT/launch_table.json "$@" > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
+python3 $ROOT/bench.py --full --steps 20 --warmup 5 --dump-profile $OUT/launch_table.json "$@" > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
 echo "bench: $(python3 -c "import json;d=json.load(open('$OUT/bench.json'));print(d['value'],d['unit'],d['ms_per_step'],'ms/step')")"
 # every profiler pass runs TRAIN STEPS ONLY, no host-side legs (no worker pools under the profiler's preload, no second
 # engine): the per-kernel averages of the trace are then in-step durations of the B = 32 training launches alone
