@@ -533,6 +533,7 @@ def backward(cfg: UNetConfig, params, cache, labels: np.ndarray, macro: bool = T
             if "drop" in c:
                 g = g * c["drop"]
             g = g * (c["y"] > 0)  # ReLU
+            c["gmask"] = g        # masked gradient g', kept for layer-wise checks of the device path
             n = g.shape[0] * g.shape[1] * g.shape[2]
             dbeta = g.sum(axis=(0, 1, 2))
             dgamma = (g * c["xhat"]).sum(axis=(0, 1, 2))

@@ -123,9 +123,10 @@ def test_bench_configuration_matches_the_fp64_oracle():
     element whose BN pre-activation is within fp32 rounding of zero flips its mask, is then wrong by its whole value, and
     the flip spreads (3x3 per conv, and through the BN-backward means to every element) as the gradient travels down.
     How much of that is inherent is MEASURED, not assumed: the same oracle run in fp32 (torch CPU, a different summation
-    order, same inputs) against its own fp64 run gives the yardstick; the HIP path must stay within 3x of it (plus a
+    order, same inputs) against its own fp64 run gives the yardstick; the HIP path must stay within 1.5x of it (plus a
     floor), layer by layer -- quantile (share of elements beyond 5e-4 of the tensor's scale) and relative L2 -- and every
-    kernel gradient within max(1e-3, 3x yardstick) relative L2."""
+    kernel gradient within max(1e-4, 1.5x yardstick) relative L2 (bias, gamma, beta: the same rule on the maximum error).
+    Per element and per layer, without the flips, these tensors are held by tests/test_gpu_layer_local.py."""
     from oct_image_segmentation_models_amd.engine import UNetEngine
     from oracle import unet_torch as ot
     B, P = 32, 4
@@ -193,20 +194,30 @@ def test_bench_configuration_matches_the_fp64_oracle():
     print("kernel gradients, relative L2 vs fp64 (HIP | fp32 torch):")
     for r in krows:
         print(f"   {r[0]:12s} {r[1]:9.2e} {r[2]:9.2e}")
-    for name, qh, qy, lh, ly in rows:
-        assert qh <= 3 * qy + 1e-4, f"{name}: {qh:.2e} of dz beyond 5e-4 of its scale (fp32 yardstick {qy:.2e})"
-        assert lh <= 3 * ly + 1e-3, f"{name}: dz relative L2 {lh:.2e} (fp32 yardstick {ly:.2e})"
-    for name, eh, ey in krows:
-        assert eh <= max(1e-3, 3 * ey), f"{name}.kernel: relative L2 {eh:.2e} (fp32 yardstick {ey:.2e})"
+    prows = []
     for li, L_ in enumerate(eng.layers):                    # bias / gamma / beta on the layer's kernel-gradient scale
         c = L_["cout"]
         kscale = np.abs(g64[li]["kernel"]).max()
         for key, off in [("bias", L_["bias_off"])] + ([("gamma", L_["gamma_off"]), ("beta", L_["beta_off"])] if L_["has_bn"] else []):
             rv = g64[li][key]
             scale = max(np.abs(rv).max(), kscale if key == "bias" else 0.0, 1e-12)
-            eh = np.abs(g[off:off + c] - rv).max() / scale
-            ey = np.abs(g32[li][key] - rv).max() / scale
-            assert eh <= max(1e-3, 3 * ey), f"{L_['name']}.{key}: {eh:.2e} of scale (fp32 yardstick {ey:.2e})"
+            prows.append((f"{L_['name']}.{key}", float(np.abs(g[off:off + c] - rv).max() / scale),
+                          float(np.abs(g32[li][key] - rv).max() / scale)))
+    print("bias / gamma / beta, max error on the tensor's scale vs fp64 (HIP | fp32 torch):")
+    for r in prows:
+        print(f"   {r[0]:18s} {r[1]:9.2e} {r[2]:9.2e}")
+    # gates: 1.5x the fp32 yardstick.  Largest measured HIP / torch ratios: dz relative L2 1.13 (dec3.conv1), kernel
+    # gradients 1.08 (enc0.conv1), bias / gamma / beta 1.40 (dec1.conv1.gamma, dec1.conv0.beta 1.38).  The last is the
+    # TIGHT gate (7 % headroom): deterministic, as both sides sum in a fixed order, but a change of the reduction order
+    # of the BN-backward partial rows will likely move it past 1.5x; then re-measure the yardstick ratio, and hold the
+    # per-channel values with the layer-local gamma / beta gates of tests/test_gpu_layer_local.py (>= 7x margin)
+    for name, qh, qy, lh, ly in rows:
+        assert qh <= 1.5 * qy + 1e-4, f"{name}: {qh:.2e} of dz beyond 5e-4 of its scale (fp32 yardstick {qy:.2e})"
+        assert lh <= 1.5 * ly + 1e-5, f"{name}: dz relative L2 {lh:.2e} (fp32 yardstick {ly:.2e})"
+    for name, eh, ey in krows:
+        assert eh <= max(1e-4, 1.5 * ey), f"{name}.kernel: relative L2 {eh:.2e} (fp32 yardstick {ey:.2e})"
+    for name, eh, ey in prows:
+        assert eh <= max(1e-4, 1.5 * ey), f"{name}: {eh:.2e} of scale (fp32 yardstick {ey:.2e})"
 
 
 def _bf16_round(a):

@@ -1,0 +1,232 @@
+"""Layer-local fp64 checks of every layer at the benched batch sizes (BASELINE configs[1], [2], [4]), default options.
+
+Each test runs one step of the production route, reads back what the engine stored (pre-BN outputs, BN records, gradient
+buffers, probabilities, gradients) and recomputes every layer in fp64 FROM THOSE STORED INPUTS with tests/layer_local.py:
+an element is held to the rounding of its own kernel, not to what an upstream mask flip made of it.  The kernel
+instantiations the step ran are asserted first, so a routing change cannot silently move what these checks cover.
+
+fp32 gates (tests/layer_local.py): z, g' and dz per element within GAMMA = 2^-17 of the same conv on absolute values
+(128 fp32 roundings of the largest possible accumulation; the 3-term split products of the bf16 pipe carry 2^-24 per
+product) and within 1e-6 relative L2 per tensor; dW, bias, gamma, beta within 2e-5 of the tensor's
+scale; record rows within 1e-5.  Measured margins: >= 7x on the per-element, parameter and record gates; 1.8x - 2.1x on
+the relative L2 gate at the widest layers, which is what fp32 accumulation predicts there (the arithmetic is at REL_L2
+in tests/layer_local.py).  Elements whose ReLU mask or pool route is decided within fp32 rounding are excluded and
+counted (<= 1e-5 of the elements).  bf16 gates: the one-rounding bounds of test_bf16_storage_layer_local_rounding_is_exact
+per layer and image.  Each test prints its per-layer table (worst err / bound per gate) and its wall time."""
+import time
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import unet_numpy as on
+from tests import layer_local as ll
+
+pytestmark = pytest.mark.gpu
+
+C = 3
+
+# kernel instantiations of one training step at configs[1] (B=32, 256x512, fp32) and configs[2] (B=64, 512x1024, P=5,
+# bf16) on the default route, and of the configs[4] inference forward (B=128) -- profiles/r03_*launch_table.json
+CONV_B32 = {
+    "conv_bt_k<2,1,0,16,3,float,2px>", "conv_bt_k<2,1,0,32,3,float>", "conv_bt_k<3,0,0,16,3,float,2px>",
+    "conv_bt_k<3,0,0,16,3,float>", "conv_bt_k<3,0,0,32,3,float>", "conv_bt_k<3,0,0,8,3,float,2px>",
+    "conv_bt_k<3,0,0,8,3,float>", "conv_bt_k<3,0,1,16,3,float,2px,gb>", "conv_bt_k<3,0,1,16,3,float,gb>",
+    "conv_bt_k<3,0,1,32,3,float>", "conv_bt_k<3,0,1,8,3,float,2px,gb,dw>", "conv_bt_k<3,0,2,16,3,float,gb>",
+    "conv_bt_k<3,0,2,8,3,float,2px,gb,dw>", "conv_bt_k<3,2,2,8,3,float,gb>", "conv_bx_k<2,1,0,8,32,3,4,float,1img>",
+    "conv_bx_k<2,1,0,8,64,3,8,float>", "conv_bx_k<3,0,0,4,64,3,4,float,1img>", "conv_bx_k<3,0,0,8,32,3,4,float,1img>",
+    "conv_bx_k<3,0,1,4,64,3,4,float,gb,1img>", "conv_bx_k<3,0,1,8,32,3,4,float,gb,1img>",
+    "conv_bx_k<3,0,2,4,64,3,4,float,gb,1img>", "conv_bx_k<3,0,2,8,32,3,4,float,gb,1img>",
+    "conv_bx_k<3,2,2,4,32,3,4,float,gb>", "conv_bx_k<3,2,2,4,64,3,4,float,gb>", "conv_dw16_k<2,16,true,float,gb,dz8>",
+    "conv_dw16_k<2,16,true,float,gb>", "conv_dw_first_k<float>", "conv_dwbt_k<3,false,16,16,3,float,gb>",
+    "conv_dwbt_k<3,false,16,32,3,float>", "conv_dwbt_k<3,false,32,16,3,float,gb>", "conv_dwbt_k<3,false,8,16,3,float,gb>",
+    "conv_dwbx_k<2,true,3,float,gb>", "conv_dwbx_k<3,false,3,float,gb>", "conv_first_fwd_k<float>",
+    "head_bwd_k<3,8,float>", "head_fwd_k<3,8,float>", "pool_bwd_flat_k<float>", "pool_fwd_k<float>",
+    "bn_bwd_apply_k<float>"}
+CONV_CFG2 = {
+    "conv_bt_k<2,1,0,16,1,unsigned short,2px>", "conv_bt_k<2,1,0,32,1,unsigned short>",
+    "conv_bt_k<3,0,0,16,1,unsigned short,2px>", "conv_bt_k<3,0,0,16,1,unsigned short>",
+    "conv_bt_k<3,0,0,32,1,unsigned short>", "conv_bt_k<3,0,0,8,1,unsigned short,2px>", "conv_bt_k<3,0,0,8,1,unsigned short>",
+    "conv_bt_k<3,0,1,16,1,unsigned short,2px,gb>", "conv_bt_k<3,0,1,16,1,unsigned short,gb>",
+    "conv_bt_k<3,0,1,32,1,unsigned short>", "conv_bt_k<3,0,1,8,1,unsigned short,2px,gb,dw>",
+    "conv_bt_k<3,0,2,16,1,unsigned short,gb>", "conv_bt_k<3,0,2,8,1,unsigned short,2px,gb,dw>",
+    "conv_bt_k<3,2,2,8,1,unsigned short,gb>", "conv_bx_k<2,1,0,4,64,1,4,unsigned short,1img>",
+    "conv_bx_k<2,1,0,8,32,1,4,unsigned short,1img>", "conv_bx_k<2,1,0,8,64,1,8,unsigned short>",
+    "conv_bx_k<3,0,0,4,64,1,4,unsigned short,1img>", "conv_bx_k<3,0,0,8,32,1,4,unsigned short,1img>",
+    "conv_bx_k<3,0,1,4,64,1,4,unsigned short,gb,1img>", "conv_bx_k<3,0,1,8,32,1,4,unsigned short,gb,1img>",
+    "conv_bx_k<3,0,2,4,64,1,4,unsigned short,gb,1img>", "conv_bx_k<3,0,2,8,32,1,4,unsigned short,gb,1img>",
+    "conv_bx_k<3,2,2,4,32,1,4,unsigned short,gb>", "conv_bx_k<3,2,2,4,64,1,4,unsigned short,gb>",
+    "conv_dw_first_k<unsigned short>", "conv_dwbt_k<2,true,16,8,1,unsigned short,gb>",
+    "conv_dwbt_k<2,true,32,16,1,unsigned short,gb>", "conv_dwbt_k<3,false,16,16,1,unsigned short,gb>",
+    "conv_dwbt_k<3,false,16,32,1,unsigned short>", "conv_dwbt_k<3,false,32,16,1,unsigned short,gb>",
+    "conv_dwbt_k<3,false,8,16,1,unsigned short,gb>", "conv_dwbx_k<2,true,1,unsigned short,gb>",
+    "conv_dwbx_k<3,false,1,unsigned short,gb>", "conv_first_fwd_k<unsigned short>", "head_bwd_k<3,8,unsigned short>",
+    "head_fwd_k<3,8,unsigned short>", "pool_bwd_flat_k<unsigned short,8>", "pool_fwd_k<unsigned short>",
+    "bn_bwd_apply8_bf16_k"}
+CONV_INFER = {"conv_bt_k<2,1,0,16,3,float,2px>", "conv_bt_k<2,1,0,32,3,float>", "conv_bt_k<3,0,0,16,3,float>",
+              "conv_bt_k<3,0,0,16,3,float,2px>", "conv_bt_k<3,0,0,32,3,float>", "conv_bt_k<3,0,0,8,3,float>",
+              "conv_bt_k<3,0,0,8,3,float,2px>", "conv_bx_k<2,1,0,4,64,3,4,float,1img>",
+              "conv_bx_k<2,1,0,8,32,3,4,float,1img>", "conv_bx_k<3,0,0,4,64,3,4,float,1img>",
+              "conv_bx_k<3,0,0,8,32,3,4,float,1img>", "conv_first_fwd_k<float>", "head_fwd_k<3,8,float>",
+              "pool_fwd_k<float>"}
+
+
+def _compute_kernels(ents):
+    return {e["kernel"] for e in ents if e["kernel"].startswith(("conv_", "head_", "pool_", "bn_bwd_apply"))}
+
+
+def _check_routing(ents, expected):
+    got = _compute_kernels(ents)
+    print("kernel instantiations:", sorted(got))
+    assert got == expected, ("missing", sorted(expected - got), "unexpected", sorted(got - expected))
+
+
+def _finish(rep, t0, title):
+    print(f"\n{title}: per-layer worst err / bound (fp32 and bf16 gates), share of elements not bit-identical "
+          f"(bf16 '!=0' columns), relative L2 ('.L2')")
+    print(rep.table())
+    print(f"{title}: wall time {time.time() - t0:.1f} s")
+    assert not rep.failures, "\n".join(rep.failures[:20])
+
+
+def _params_from_engine(eng):
+    """The engine's weights as oracle structures in fp64 (params, BN moving state)."""
+    wl, params, state, k = eng.get_weights(), [], [], 0
+    for L in eng.layers:
+        p = {"kernel": wl[k].astype(np.float64), "bias": wl[k + 1].astype(np.float64)}
+        k += 2
+        if L["has_bn"]:
+            p["gamma"], p["beta"] = wl[k].astype(np.float64), wl[k + 1].astype(np.float64)
+            state.append({"moving_mean": wl[k + 2].astype(np.float64), "moving_var": wl[k + 3].astype(np.float64)})
+            k += 4
+        params.append(p)
+    return params, state
+
+
+def test_configs1_fp32_batch_32_every_layer_every_element():
+    """configs[1] as bench.py times it: 256x512, P=4, fp32, batch 32 -- the inputs of
+    test_bench_configuration_matches_the_fp64_oracle (randomised BN parameters, 32 distinct scans, dropout step 3)."""
+    from oct_image_segmentation_models_amd.engine import UNetEngine
+    from tests.test_gpu_fullsize import scans
+    t0 = time.time()
+    B, H, W, P = 32, 256, 512, 4
+    cfg = on.UNetConfig(num_classes=C, start_neurons=8, pool_layers=P)
+    params, state = on.init_params(cfg, seed=7, dtype=np.float32, randomize_bn=True)
+    eng = UNetEngine(device="cuda:0", input_channels=1, num_classes=C, image_height=H, image_width=W, max_batch=B,
+                     training=True, seed=5, init_seed=1)
+    eng.set_weights(on.keras_weight_list(params, state))
+    img, lab = scans(B, 31)
+    for k in range(B):
+        img[k] = np.roll(img[k], 5 * k, axis=1); lab[k] = np.roll(lab[k], 5 * k, axis=1)
+    x = torch.from_numpy(img).cuda(); l = torch.from_numpy(lab[..., 0].copy()).cuda()
+    eng.set_dropout_step(3)
+    mask = eng.dropout_mask(B).double()
+    eng.profile_begin()
+    probs, _ = eng.forward(x, training=True, labels=l)
+    eng.loss_dice()
+    eng.backward(l, macro=True, loss_scale=1.0)
+    _check_routing(eng.profile_end(), CONV_B32)
+    p64, _ = _params_from_engine(eng)
+    S = ll.engine_stored(eng, B, probs)
+    rep = ll.LayerLocal(cfg, p64, S, img, labels=lab[..., 0], dropout_mask=mask, mode="f32", device="cuda:0").run()
+    _finish(rep, t0, "configs[1] fp32 B=32 256x512")
+
+
+def test_configs2_bf16_batch_64_every_layer_every_image():
+    """configs[2]: 512x1024, P=5, bf16 storage, batch 64, on the fused route (the BN-backward transform applied by the
+    consumers on load: dz of a fused layer is reconstructed from its stored g', z and record).  Then the existing
+    small-shape equality at size, on identical inputs: with the same backward-weights kernels on both routes
+    (fuse_dw_thin = 0, as test_bn_backward_on_load_equals_the_separate_pass), the two routes' gradients are equal bit for
+    bit against the stand-alone BN-backward route (fuse_first_apply = fuse_bn_apply = 0).  (With the default
+    fuse_dw_thin = 1 the fused route reduces three layers' dW inside their backward-data launches -- another summation
+    order -- and the last bits of the BN-backward means then move every gradient below.)"""
+    from oct_image_segmentation_models_amd import _hip
+    from oct_image_segmentation_models_amd.common.synthetic import make_scans
+    from oct_image_segmentation_models_amd.engine import UNetEngine
+    t0 = time.time()
+    B, H, W, P = 64, 512, 1024, 5
+    cfg = on.UNetConfig(num_classes=C, start_neurons=8, pool_layers=P)
+    params, state = on.init_params(cfg, seed=11, dtype=np.float32, randomize_bn=True)
+    kw = dict(device="cuda:0", input_channels=1, num_classes=C, image_height=H, image_width=W, max_batch=B,
+              training=True, seed=5, init_seed=2, pool_layers=P, dtype="bfloat16")
+    img8, lab8 = make_scans(8, H, W, C, seed=41)
+    img = np.concatenate([np.roll(img8, 9 * k, axis=2) for k in range(B // 8)])
+    lab = np.concatenate([np.roll(lab8, 9 * k, axis=2) for k in range(B // 8)])
+    x = torch.from_numpy(img).cuda(); l = torch.from_numpy(lab[..., 0].copy()).cuda()
+
+    def engine(fuse=1, fuse_dw_thin=1):
+        try:
+            _hip.set_option("fuse_first_apply", fuse); _hip.set_option("fuse_bn_apply", fuse)
+            _hip.set_option("fuse_dw_thin", fuse_dw_thin)
+            eng = UNetEngine(**kw)
+        finally:
+            _hip.set_option("fuse_first_apply", 1); _hip.set_option("fuse_bn_apply", 1); _hip.set_option("fuse_dw_thin", 1)
+        eng.set_weights(on.keras_weight_list(params, state))
+        eng.set_dropout_step(2)
+        eng.profile_begin()
+        probs, _ = eng.forward(x, training=True, labels=l)
+        eng.loss_dice()
+        eng.backward(l, macro=True)
+        return eng, probs, eng.profile_end()
+
+    def check(eng, probs):
+        p64, _ = _params_from_engine(eng)
+        S = ll.engine_stored(eng, B, probs)
+        return ll.LayerLocal(cfg, p64, S, img, labels=lab[..., 0], dropout_mask=eng.dropout_mask(B).double(), mode="bf16",
+                             mfma_mode=_hip.get_option("mfma_mode"), device="cuda:0").run()
+
+    eng, probs, ents = engine()
+    _check_routing(ents, CONV_CFG2)
+    assert {e["layer"] for e in ents if e["kernel"] == "conv_dwbt_k<2,true,16,8,1,unsigned short,gb>"} == {"dec4.up"}
+    assert {e["layer"] for e in ents if e["kernel"] == "bn_bwd_apply8_bf16_k"} == {"enc2.conv0"}
+    assert {e["layer"] for e in ents if e["kernel"].endswith(",dw>")} == {"enc0.conv1", f"dec{P - 1}.conv0", f"dec{P - 1}.conv1"}
+    nb = len(eng.layers) - 1
+    assert sum(eng.debug_layer_fused(li) for li in range(nb)) >= nb - 4
+    rep = check(eng, probs)
+    del eng
+    eng1, _, ents1 = engine(fuse=0, fuse_dw_thin=0)
+    assert not any(eng1.debug_layer_fused(li) for li in range(nb))
+    assert not any(",gb" in e["kernel"] for e in ents1)
+    g_sep = eng1.grads.clone()
+    del eng1
+    eng2, _, ents2 = engine(fuse=1, fuse_dw_thin=0)
+    assert not any(e["kernel"].endswith(",dw>") for e in ents2) and any(",gb" in e["kernel"] for e in ents2)
+    differ = [L["name"] for L in eng2.layers if not torch.equal(eng2.grads[L["kernel_off"]:L["beta_off" if L["has_bn"] else "bias_off"] + L["cout"]],
+                                                                  g_sep[L["kernel_off"]:L["beta_off" if L["has_bn"] else "bias_off"] + L["cout"]])]
+    _finish(rep, t0, "configs[2] bf16 B=64 512x1024 P=5")
+    assert not differ, f"fused and stand-alone BN-backward routes differ at configs[2] in {differ}"
+
+
+def test_configs4_inference_batch_128_every_layer():
+    """configs[4]: inference, fp32, batch 128, randomised moving statistics (those of
+    test_inference_at_batch_128_graph_replay_equals_chunked_forwards): every layer's z with the BN coefficients taken
+    from the parameters, the probabilities from the stored head input, the arg-max away from ties."""
+    from oct_image_segmentation_models_amd.engine import UNetEngine
+    from tests.test_gpu_fullsize import scans
+    t0 = time.time()
+    B, H, W = 128, 256, 512
+    cfg = on.UNetConfig(num_classes=C, start_neurons=8, pool_layers=4)
+    eng = UNetEngine(device="cuda:0", input_channels=1, num_classes=C, image_height=H, image_width=W, max_batch=B,
+                     training=False, seed=5, init_seed=1)
+    rng = np.random.default_rng(0)
+    wl = eng.get_weights()
+    i = 0
+    for L in eng.layers:
+        i += 2
+        if L["has_bn"]:
+            c = L["cout"]
+            wl[i] = rng.uniform(0.5, 1.5, c).astype(np.float32); wl[i + 1] = rng.normal(0, 0.1, c).astype(np.float32)
+            wl[i + 2] = rng.normal(0, 0.1, c).astype(np.float32); wl[i + 3] = rng.uniform(0.5, 1.5, c).astype(np.float32)
+            i += 4
+    eng.set_weights(wl)
+    img, _ = scans(B, 21)
+    for k in range(B):
+        img[k] = np.roll(img[k], 3 * k, axis=1)
+    x = torch.from_numpy(img).cuda()
+    eng.profile_begin()
+    probs, am = eng.forward(x, training=False, want_argmax=True)
+    _check_routing(eng.profile_end(), CONV_INFER)
+    p64, s64 = _params_from_engine(eng)
+    S = ll.engine_stored(eng, B, probs, training=False, argmax=am)
+    rep = ll.LayerLocal(cfg, p64, S, img, training=False, state=s64, mode="f32", device="cuda:0").run()
+    _finish(rep, t0, "configs[4] fp32 inference B=128 256x512")

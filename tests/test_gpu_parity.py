@@ -10,6 +10,9 @@ import torch
 
 from oracle import unet_numpy as on
 from tests.helpers import dropout_keep_mask, relu_margin
+# the bf16-mode rounding rules are shared with the full-size layer-local checks
+from tests.layer_local import (bf16_dw_operands, bf16_dx_weights, bf16_fwd_operands, bf16_round, bf16_ulp,  # noqa: F401
+                               upconv_dx_effective)
 
 pytestmark = pytest.mark.gpu
 
@@ -672,78 +675,6 @@ def make_bf16(B, H, W, C, sn, P, L=2, in_ch=1, seed=0):
     p64 = [{k: v.astype(np.float64) for k, v in p.items()} for p in params]
     s64 = [{k: v.astype(np.float64) for k, v in s.items()} for s in state]
     return cfg, eng, p64, s64
-
-
-def bf16_round(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(torch.bfloat16).double().numpy()
-
-
-def bf16_ulp(a):
-    """Spacing of bf16 numbers at |a| (8 significant bits)."""
-    return 2.0 ** (np.floor(np.log2(np.maximum(np.abs(a), 1e-30))) - 7)
-
-
-# ---- which arithmetic a layer runs in bf16 mode (dtype=1): mirror of the host rules in csrc/oct_unet.hip (bx_fwd_ok /
-# bt_fwd_ok / bx_bwd_ok / bt_bwd_ok / dw_plan).  On the bf16 MFMA pipe (mfma_mode 1, the default) BOTH operands of a
-# product are bf16: the activation is rounded once more after BN + ReLU (dz operands are stored bf16 already: exact)
-# and the weights are rounded per step; accumulation stays fp32.  Layers outside those rules (first layer, head,
-# channel counts that are not multiples of 8, mfma_mode 0) multiply the stored bf16 values with fp32 weights. ----
-def _bt_k(k):
-    return k in (8, 16, 32)
-
-
-def bf16_fwd_operands(plan, li, cfg, mfma_mode):
-    sp = plan[li]
-    if not mfma_mode or sp.src == "input" or not sp.has_bn:
-        return False
-    drop = sp.name == "dec0.up" and cfg.dropout_rate > 0
-    two_ok = sp.src != "concat" or plan[li - 1].cout % 8 == 0
-    thin = sp.cout <= 16 and sp.cout % 4 == 0 and _bt_k(sp.cin) and not drop and two_ok
-    wide = sp.cout % 32 == 0 and sp.cin % 8 == 0 and sp.cin <= 512 and two_ok
-    return thin or wide
-
-
-def bf16_dx_weights(plan, li, mfma_mode):
-    sp = plan[li]
-    if not mfma_mode or sp.src == "input" or not sp.has_bn:
-        return False
-    cg = sp.cin // 2 if sp.src == "concat" else sp.cin
-    wide = cg % 32 == 0 and sp.cout % 8 == 0 and sp.cout <= 512
-    thin = cg <= 16 and cg % 4 == 0 and (sp.cout == 8 if sp.src == "up" else _bt_k(sp.cout))
-    return wide or thin
-
-
-def bf16_dw_operands(plan, li, mfma_mode):
-    sp = plan[li]
-    if not mfma_mode or sp.src == "input" or sp.kh == 1 or not sp.has_bn:
-        return False
-    if sp.cin % 32 == 0 and sp.cout % 32 == 0:                               # conv_dwbx_k
-        return True
-    pair = (sp.cin, sp.cout)                                                  # conv_dwbt_k's instantiated shapes
-    if sp.src == "up":
-        return pair in ((16, 8), (32, 16))
-    if sp.src == "concat" and (sp.cin // 2) % 8:
-        return False
-    return pair in ((8, 8), (8, 16), (16, 8), (16, 16), (16, 32), (32, 16))
-
-
-def upconv_dx_effective(dz, kernel, round_w):
-    """Backward-data of UpSampling2D(2) -> Conv2D(2x2, same) as the engine forms it (prep_wt_k mode 1 + A_DOWN2): a 3x3
-    stride-2 gather over dz with effective weights Weff[a][b] = sum of the 2x2 taps that reach that offset; the
-    EFFECTIVE weights are what the bf16 pipe rounds."""
-    B, H2, W2, Co = dz.shape
-    Ci = kernel.shape[2]
-    Hl, Wl = H2 // 2, W2 // 2
-    sel = {0: (1,), 1: (0, 1), 2: (0,)}
-    dzp = np.zeros((B, H2 + 2, W2 + 2, Co)); dzp[:, 1:H2 + 1, 1:W2 + 1] = dz      # index 2y - 1 + a  ->  2y + a
-    out = np.zeros((B, Hl, Wl, Ci))
-    for a in range(3):
-        for b in range(3):
-            weff = sum(kernel[ky, kx] for ky in sel[a] for kx in sel[b])         # (Ci, Co)
-            if round_w:
-                weff = bf16_round(weff.astype(np.float32))                         # prep_wt_k sums in fp32, prep_wb*_k rounds
-            out += np.einsum("bhwo,io->bhwi", dzp[:, a:a + 2 * Hl:2, b:b + 2 * Wl:2], weff)
-    return out
 
 
 @pytest.mark.parametrize("case", BF16_CASES)

@@ -1,0 +1,303 @@
+"""CPU tests of the layer-local fp64 model (tests/layer_local.py), no GPU.
+
+(a) Fed the tensors of a perfect engine -- the numpy oracle itself in fp32 mode, the oracle's primitives with the bf16
+    rounding rules in bf16 mode -- the model reproduces every recomputed tensor (inputs, z, probabilities, records, g',
+    dz, dW, bias, gamma, beta) to 1e-12 and reports nothing, for every spec kind of ``build_plan``.
+    In bf16 mode the reference shares the model's bf16 operand rules (ll.bf16_*_operands, the mirror of the host rules
+    in csrc/oct_unet.hip): this checks the model's arithmetic under those rules, not the rules themselves -- those are
+    held against the hardware by the GPU tests (tests/test_gpu_parity.py, tests/test_gpu_layer_local.py).
+(b) The gates bite: one planted defect at a time, each named by layer, image and first coordinates."""
+import re
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import unet_numpy as on
+from tests import layer_local as ll
+
+C = 3
+
+
+def setup(B=3, H=16, W=32, sn=8, P=2, L=2, seed=0):
+    cfg = on.UNetConfig(num_classes=C, start_neurons=sn, pool_layers=P, conv_layers=L)
+    params, state = on.init_params(cfg, seed=seed, dtype=np.float32, randomize_bn=True)
+    p64 = [{k: v.astype(np.float64) for k, v in p.items()} for p in params]
+    s64 = [{k: v.astype(np.float64) for k, v in s.items()} for s in state]
+    images, labels = on.synth_scans(B, H, W, C, seed=seed + 5)
+    rng = np.random.default_rng(seed)
+    mask = (rng.random((B, H >> P, W >> P, sn << P)) < 0.5).astype(np.float64)
+    return cfg, p64, s64, images, labels[..., 0], mask
+
+
+def perfect_engine(cfg, p64, images, labels, mask, mode, fused, macro=True, mm=1):
+    """The stored tensors of an engine without any defect, built from the oracle's primitives: activations formed from
+    the stored z and the record, one bf16 rounding per stored tensor and per MFMA operand in bf16 mode (the rules of
+    tests/layer_local.py), every BN-backward transform as the fused consumers form it where ``fused[li]``.  Returns
+    (Stored, unrounded z per layer, true dz per layer)."""
+    R = ll.bf16_round if mode == "bf16" else (lambda a: a)
+    bf = mode == "bf16"
+    plan = on.build_plan(cfg)
+    nb, L = len(plan) - 1, cfg.conv_layers
+    z, zpre, rec = {}, {}, {}
+
+    def act(li, drop=True):
+        y = on.relu(rec[li][0] * z[li] + rec[li][1])
+        if drop and plan[li].name == f"mid.conv{L - 1}":
+            y = y * mask / (1.0 - cfg.dropout_rate)
+        return y
+
+    inps = {}
+    for li, sp in enumerate(plan):
+        if sp.src == "input":
+            inp = on.preprocess_u8(images, np.float64)
+        elif sp.src in ("prev", "head"):
+            inp = act(li - 1)
+        elif sp.src == "pool":
+            inp = R(on.maxpool2x2(act(li - 1)))
+        elif sp.src == "up":
+            inp = on.upsample2x(act(li - 1))
+        else:
+            inp = np.concatenate([act(li - 1), act(sp.skip_from)], axis=-1)
+        inps[li] = inp
+        p = p64[li]
+        rnd = bf and ll.bf16_fwd_operands(plan, li, cfg, mm)
+        zz = on.conv2d_same(R(inp) if rnd else inp, R(p["kernel"]) if rnd else p["kernel"], p["bias"])
+        if sp.has_bn:
+            zpre[li], z[li] = zz, R(zz)
+            _, mean, var, rstd, _ = on.batchnorm_train(zz, p["gamma"], p["beta"], cfg.bn_eps)
+            a = p["gamma"] * rstd
+            rec[li] = np.zeros((9, sp.cout)); rec[li][:4] = a, p["beta"] - a * mean, mean, rstd
+        else:
+            probs = on.softmax(zz)
+    y1 = on.one_hot(labels, C, np.float64)
+    dp = on.dice_loss_grad(y1, probs, macro)
+    dzr = {nb: probs * (dp - (probs * dp).sum(-1, keepdims=True))}
+    contrib, skipraw, gbuf, gq_of, dz_true = {}, {}, {}, {}, {}
+    grads = [dict() for _ in plan]
+    for li in range(nb, -1, -1):
+        sp, p = plan[li], p64[li]
+        if li < nb:
+            alive = (rec[li][0] * z[li] + rec[li][1]) > 0
+            gq = R(alive * (contrib.pop(li) + skipraw.get(li, 0.0)))
+            mean, rstd = rec[li][2], rec[li][3]
+            xhat = (z[li] - mean) * rstd
+            c1, c2 = gq.mean(axis=(0, 1, 2)), (gq * xhat).mean(axis=(0, 1, 2))
+            ga = p["gamma"] * rstd; gb = -ga * rstd * c2; gd = -ga * c1 - gb * mean
+            rec[li][4:] = c1, c2, ga, gb, gd
+            dz_true[li] = ga * (gq - c1 - xhat * c2)
+            gbuf[li] = gq if fused[li] else R(dz_true[li])
+            dzr[li] = R(ga * gq + gb * z[li] + gd) if fused[li] else gbuf[li]
+            gq_of[li] = gq
+            grads[li]["gamma"], grads[li]["beta"] = (gq * xhat).sum(axis=(0, 1, 2)), gq.sum(axis=(0, 1, 2))
+        dz = dzr[li]
+        rdw = bf and ll.bf16_dw_operands(plan, li, mm)
+        _, dk, db = on._conv_backward(R(inps[li]) if rdw else inps[li], p["kernel"], dz)
+        grads[li]["kernel"], grads[li]["bias"] = dk, db
+        if sp.src == "input":
+            continue
+        wq = bf and ll.bf16_dx_weights(plan, li, mm)
+        k = R(p["kernel"]) if wq else p["kernel"]
+        pi = li - 1
+        if sp.src == "up":
+            gy = ll.upconv_dx_effective(dz, p["kernel"], wq)
+            if plan[pi].name == f"mid.conv{L - 1}":
+                gy = gy * mask / (1.0 - cfg.dropout_rate)
+            contrib[pi] = gy
+            continue
+        gx, _, _ = on._conv_backward(inps[li], k, dz)
+        if sp.src in ("prev", "head"):
+            contrib[pi] = gx
+        elif sp.src == "concat":
+            C0 = plan[pi].cout
+            contrib[pi] = gx[..., :C0]
+            skipraw[sp.skip_from] = R(gx[..., C0:])
+        else:
+            contrib[pi] = on._maxpool_backward(act(pi, drop=False), R(gx))
+    S = ll.Stored(z=[torch.from_numpy(z[li]) for li in range(nb)], probs=torch.from_numpy(probs),
+                  rec=[torch.from_numpy(rec[li]) for li in range(nb)], gbuf=[torch.from_numpy(gbuf[li]) for li in range(nb)],
+                  fused=list(fused), grads=grads)
+    return S, zpre, dz_true, gq_of
+
+
+def rel(a, b):
+    return np.abs(np.asarray(a) - np.asarray(b)).max() / max(np.abs(b).max(), 1e-300)
+
+
+def run(cfg, p64, S, images, labels, mask, mode, keep=False, chunk=2, macro=True):
+    m = ll.LayerLocal(cfg, p64, S, images, labels=labels, dropout_mask=mask, mode=mode, macro=macro, chunk=chunk, keep=keep)
+    return m, m.run()
+
+
+GEOS = [dict(), dict(P=1, L=1, sn=8, H=8, W=16)]
+
+
+@pytest.mark.parametrize("macro", [True, False])
+@pytest.mark.parametrize("geo", GEOS)
+def test_model_matches_the_numpy_oracle_in_f32_mode(geo, macro):
+    cfg, p64, s64, images, labels, mask = setup(**geo)
+    plan = on.build_plan(cfg)
+    kinds = {sp.src for sp in plan}
+    assert kinds == {"input", "prev", "pool", "up", "concat", "head"} or geo.get("L") == 1
+    fused = [li % 2 == 0 for li in range(len(plan) - 1)]          # both routes: g' stored / dz stored
+    S, _, dz_true, _ = perfect_engine(cfg, p64, images, labels, mask, "f32", fused, macro=macro)
+    probs, cache = on.forward(cfg, p64, s64, on.preprocess_u8(images, np.float64), training=True, dropout_mask=mask)
+    _, grads = on.backward(cfg, p64, cache, labels, macro=macro)
+    m, rep = run(cfg, p64, S, images, labels, mask, "f32", keep=True, macro=macro)
+    assert not rep.failures, rep.failures
+    assert rep.excluded == 0
+    for li, sp in enumerate(plan):
+        assert rel(m.kept_tensor(sp.name, "x"), cache[li]["x"]) <= 1e-12, sp.name
+        assert rel(m.kept_tensor(sp.name, "z"), cache[li]["z"]) <= 1e-12, sp.name
+        assert rel(m.kept[sp.name]["grads"][0]["kernel"], grads[li]["kernel"]) <= 1e-12, sp.name
+        if not sp.has_bn:
+            assert rel(m.kept_tensor(sp.name, "probs"), probs) <= 1e-12
+            assert rel(m.kept[sp.name]["grads"][0]["bias"], grads[li]["bias"]) <= 1e-12
+            continue
+        st = m.kept[sp.name]["stats"][0]
+        assert rel(st[0], cache[li]["mean"]) <= 1e-12 and rel(st[1], cache[li]["var"]) <= 1e-12, sp.name
+        assert rel(m.kept_tensor(sp.name, "gmask"), cache[li]["gmask"]) <= 1e-12, sp.name
+        if not fused[li]:
+            assert rel(m.kept_tensor(sp.name, "dz"), cache[li]["dz"]) <= 1e-12, sp.name
+        n = cache[li]["z"][..., 0].size
+        c12 = m.kept[sp.name]["c12"][0]
+        assert rel(c12[0] * n, grads[li]["beta"]) <= 1e-12 and rel(c12[1] * n, grads[li]["gamma"]) <= 1e-12, sp.name
+    # (dropout after the bottleneck really was in play)
+    assert any(sp.name == f"mid.conv{cfg.conv_layers - 1}" for sp in plan) and 0 < mask.mean() < 1
+
+
+@pytest.mark.parametrize("geo", GEOS)
+def test_model_matches_the_bf16_rounding_rules(geo):
+    cfg, p64, s64, images, labels, mask = setup(**geo)
+    plan = on.build_plan(cfg)
+    fused = [li % 2 == 1 for li in range(len(plan) - 1)]
+    S, zpre, dz_true, gq = perfect_engine(cfg, p64, images, labels, mask, "bf16", fused)
+    m, rep = run(cfg, p64, S, images, labels, mask, "bf16", keep=True)
+    assert not rep.failures, rep.failures
+    assert any(ll.bf16_fwd_operands(plan, li, cfg, 1) for li in range(len(plan)))      # the rounding rules are in play
+    for li, sp in enumerate(plan[:-1]):
+        assert rel(m.kept_tensor(sp.name, "z"), zpre[li]) <= 1e-12, sp.name
+        assert rel(m.kept_tensor(sp.name, "gmask"), gq[li]) <= 1e-12, sp.name
+        if not fused[li]:
+            assert rel(m.kept_tensor(sp.name, "dz"), dz_true[li]) <= 1e-12, sp.name
+        assert rel(m.kept[sp.name]["grads"][0]["kernel"], S.grads[li]["kernel"]) <= 1e-12, sp.name
+
+
+def test_inference_model_matches_the_oracle():
+    cfg, p64, s64, images, _, _ = setup()
+    probs, cache = on.forward(cfg, p64, s64, on.preprocess_u8(images, np.float64), training=False)
+    plan = on.build_plan(cfg)
+    S = ll.Stored(z=[torch.from_numpy(cache[li]["z"]) for li in range(len(plan) - 1)], probs=torch.from_numpy(probs),
+                  argmax=torch.from_numpy(probs.argmax(-1)))
+    m = ll.LayerLocal(cfg, p64, S, images, training=False, state=s64, chunk=2, keep=True)
+    rep = m.run()
+    assert not rep.failures, rep.failures
+    assert rel(m.kept_tensor("head", "probs"), probs) <= 1e-12
+    S.probs = torch.from_numpy(probs.copy()); S.probs[1, 3, 5, 0] *= 1 + 1e-4
+    S.argmax = torch.from_numpy(probs.argmax(-1)); S.argmax[2, 7, 9] = (S.argmax[2, 7, 9] + 1) % C
+    fails = ll.LayerLocal(cfg, p64, S, images, training=False, state=s64, chunk=2).run().failures
+    assert any(f.startswith("head probs: image 1 at (y=3, x=5, c=0)") for f in fails), fails
+    assert any(f.startswith("head argmax: image 2 at (y=7, x=9)") for f in fails), fails
+
+
+# ---- (b) planted defects ---------------------------------------------------------------------------------------------
+
+def _layer(cfg, name):
+    return [sp.name for sp in on.build_plan(cfg)].index(name)
+
+
+def _one(fails, prefix):
+    hits = [f for f in fails if f.startswith(prefix)]
+    assert hits, (prefix, fails)
+    return hits[0]
+
+
+@pytest.fixture(scope="module")
+def clean():
+    cfg, p64, s64, images, labels, mask = setup()
+    fused = [True] * (len(on.build_plan(cfg)) - 1)
+    S, _, _, _ = perfect_engine(cfg, p64, images, labels, mask, "f32", fused)
+    return cfg, p64, images, labels, mask, S
+
+
+def _copy(S):
+    return ll.Stored(z=[t.clone() for t in S.z], probs=S.probs.clone(), rec=[t.clone() for t in S.rec],
+                     gbuf=[t.clone() for t in S.gbuf], fused=list(S.fused),
+                     grads=[{k: v.copy() for k, v in g.items()} for g in S.grads])
+
+
+def test_defect_one_element_of_z(clean):
+    cfg, p64, images, labels, mask, S0 = clean
+    S = _copy(S0)
+    li = _layer(cfg, "enc1.conv0")
+    b = 1
+    y, x, c = np.unravel_index(int(S.z[li][b].abs().argmax()), S.z[li][b].shape)
+    S.z[li][b, y, x, c] *= 1 + 1e-4
+    fails = run(cfg, p64, S, images, labels, mask, "f32")[1].failures
+    _one(fails, f"enc1.conv0 z: image {b} at (y={y}, x={x}, c={c})")
+
+
+def test_defect_one_dw_tap(clean):
+    cfg, p64, images, labels, mask, S0 = clean
+    S = _copy(S0)
+    li = _layer(cfg, "dec0.conv0")
+    k = S.grads[li]["kernel"]
+    i = np.unravel_index(int(np.abs(k).argmax()), k.shape)
+    k[i] *= 1 + 1e-4
+    fails = run(cfg, p64, S, images, labels, mask, "f32")[1].failures
+    _one(fails, "dec0.conv0 dW at (ky={}, kx={}, ci={}, co={})".format(*i))
+
+
+def test_defect_one_channel_of_c1(clean):
+    cfg, p64, images, labels, mask, S0 = clean
+    S = _copy(S0)
+    li = _layer(cfg, "mid.conv1")
+    c = 2
+    S.rec[li][4, c] += 1e-4 * float(S.gbuf[li][..., c].abs().mean())
+    fails = run(cfg, p64, S, images, labels, mask, "f32")[1].failures
+    _one(fails, f"mid.conv1 rec.c1 at (c={c})")
+
+
+def test_defect_pool_gradient_to_the_second_maximum(clean):
+    cfg, p64, images, labels, mask, S0 = clean
+    S = _copy(S0)
+    li = _layer(cfg, "enc0.conv1")
+    assert on.build_plan(cfg)[li + 1].src == "pool"
+    a, bb = S.rec[li][0].numpy(), S.rec[li][1].numpy()
+    img = 2
+    act = np.maximum(a * S.z[li][img].numpy() + bb, 0)                        # (H, W, C)
+    m = ll.LayerLocal(cfg, p64, S, images, labels=labels, dropout_mask=mask, chunk=2)
+    m.check_records()
+    gx = m._consumer_dx(li + 1, img, img + 1)[0]
+    gpool = gx[0].numpy()
+    Hh, Wh, Cc = gpool.shape
+    for (y, x, c) in np.ndindex(Hh, Wh, Cc):                                  # a window with two distinct positive values
+        win = act[2 * y:2 * y + 2, 2 * x:2 * x + 2, c].ravel()
+        order = np.argsort(-win, kind="stable")
+        if win[order[1]] > 0 and win[order[0]] - win[order[1]] > 1e-3 and abs(gpool[y, x, c]) > 1e-8:
+            break
+    else:
+        pytest.fail("no suitable window")
+    first, second = [(2 * y + o // 2, 2 * x + o % 2) for o in order[:2]]
+    g = S.gbuf[li]
+    g[img, first[0], first[1], c] -= gpool[y, x, c]
+    g[img, second[0], second[1], c] += gpool[y, x, c]
+    fails = run(cfg, p64, S, images, labels, mask, "f32")[1].failures
+    msg = _one(fails, f"enc0.conv1 g': image {img} at ")
+    yx = tuple(int(v) for v in re.search(r"\(y=(\d+), x=(\d+), c=(\d+)\)", msg).groups())
+    assert yx in ((*first, c), (*second, c)), (msg, first, second, c)
+
+
+def test_defect_truncating_bf16_store():
+    cfg, p64, s64, images, labels, mask = setup()
+    plan = on.build_plan(cfg)
+    S, zpre, _, _ = perfect_engine(cfg, p64, images, labels, mask, "bf16", [True] * (len(plan) - 1))
+    assert not run(cfg, p64, S, images, labels, mask, "bf16")[1].failures
+    li = _layer(cfg, "enc0.conv1")
+    f32 = np.ascontiguousarray(zpre[li], dtype=np.float32)
+    trunc = (f32.view(np.uint32) & np.uint32(0xFFFF0000)).view(np.float32).astype(np.float64)
+    assert (trunc != S.z[li].numpy()).mean() > 0.3
+    S.z[li] = torch.from_numpy(trunc)
+    fails = run(cfg, p64, S, images, labels, mask, "bf16")[1].failures
+    msg = _one(fails, "enc0.conv1 z: image 0")
+    assert re.search(r"identical to the fp64 value rounded once; first different at \(y=\d+, x=\d+, c=\d+\)", msg), msg
