@@ -164,6 +164,24 @@ int oct_unet_profile_end(oct_unet* h, oct_profile_entry* out, int max_entries, i
 int oct_boundary_maps(const unsigned char* labels_dev, int B, int H, int W, int n_cls, int bg_ilm, int bg_csi,
                       unsigned char* maps_dev, oct_stream_t stream);
 
+/* ---- evaluation metrics on device: average surface distance and robust Hausdorff distance of every foreground class
+ * (reference evaluation/evaluation.py:207-262 -> common/custom_metrics.py:103-119 -> google-deepmind/surface-distance
+ * compute_surface_distances / compute_average_surface_distance / compute_robust_hausdorff, 2D; results stored at
+ * evaluation.py:573-597 and averaged at :783-803, :870-882).  A restatement of the un-vendored package: PARITY UNPINNED.
+ * pred_dev, gt_dev: (B,H,W) u8 class maps; class c in 1..n_cls-1 is the mask (map == c).  Per (b, c) the 2x2-cell border
+ * elements of both masks, their contour lengths, the exact Euclidean distance (spacing_row, spacing_col: physical size of
+ * a pixel) of each to the nearest border element of the other mask, then out_dev (B, n_cls-1, 6) doubles:
+ *   {asd_gt_to_pred, asd_pred_to_gt, perc_gt_to_pred, perc_pred_to_gt, n_surfels_gt, n_surfels_pred}
+ * asd = length-weighted mean distance (NaN without border elements, +inf when the other mask has none); perc = the
+ * length-weighted `percent` percentile (+inf without border elements).  Hausdorff = max(perc_gt_to_pred, perc_pred_to_gt).
+ * Deterministic (fixed-order sums, integer-count selection).  workspace_dev: oct_surface_workspace_bytes(B, H, W, n_cls)
+ * bytes (0 = unsupported shape), caller-owned.  Rejected with an error: labels >= n_cls (checked on the device; the call
+ * then waits for `stream` once), percent outside [0, 100], non-positive spacings, a workspace that is too small. */
+size_t oct_surface_workspace_bytes(int B, int H, int W, int n_cls);
+int oct_surface_distances(const unsigned char* pred_dev, const unsigned char* gt_dev, int B, int H, int W, int n_cls,
+                          double spacing_row, double spacing_col, double percent,
+                          void* workspace_dev, size_t workspace_bytes, double* out_dev, oct_stream_t stream);
+
 /* ---- options ----
  * oct_set_option edits the PROCESS-WIDE DEFAULTS; a handle copies them when it is created (oct_unet_create) and every
  * launch of that handle reads its own copy: changing an option never affects a live handle, and two handles created

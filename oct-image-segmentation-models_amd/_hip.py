@@ -76,6 +76,9 @@ SYMBOLS = [
     ("oct_unet_profile_begin", C.c_int, [C.c_void_p]),
     ("oct_unet_profile_end", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _P(C.c_int)]),
     ("oct_boundary_maps", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    ("oct_surface_workspace_bytes", C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    ("oct_surface_distances", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
+                                        C.c_double, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     ("oct_set_option", C.c_int, [C.c_char_p, C.c_int]),
     ("oct_get_option", C.c_int, [C.c_char_p, _P(C.c_int)]),
     ("oct_unet_get_option", C.c_int, [C.c_void_p, C.c_char_p, _P(C.c_int)]),

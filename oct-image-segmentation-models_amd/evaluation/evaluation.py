@@ -4,8 +4,9 @@
 The forward pass is batched on the GPU (device arg-max, 1 B/px back to the host) instead of one
 ``predict`` call per image; everything after it -- one-hot, boundary maps, Dice
 metrics, optional graph search, per-image result files, dataset aggregates -- is the reference's host logic
-re-stated.  Under ``torchrun`` the test set is sharded by contiguous index range (no collective); rank 0
-aggregates.  PNG plots and surface-distance metrics are out of scope."""
+re-stated.  The surface-distance metrics (average surface distance, Hausdorff-95; :207-262) are computed on the
+device from the arg-max maps and the uploaded ground truth (``evaluation/surface.py``).  Under ``torchrun`` the test
+set is sharded by contiguous index range (no collective); rank 0 aggregates.  PNG plots are out of scope."""
 from __future__ import annotations
 
 import logging as log
@@ -27,6 +28,7 @@ from ..models import get_model_class
 from ..min_path_processing.pool import SegmentPool
 from .evaluation_parameters import EvaluationParameters
 from .pipeline import BatchedPredictor
+from .surface import SurfaceDistances, datasets as surface_datasets
 
 EVALUATION_RESULTS_FILENAME = "evaluation_results.hdf5"
 GS_EVALUATION_RESULTS_FILENAME = "gs_evaluation_results.hdf5"
@@ -37,7 +39,9 @@ OVERALL_EVALUATION_RESULTS_FILENAME_CSV = "overall_evaluation_results.csv"
 class EvaluationOutput:
     def __init__(self, image, image_name, image_segments, image_output_dir, predicted_labels, categorical_pred,
                  boundary_maps, gs_pred_segs, errors, mean_abs_err, mean_err, abs_err_sd, err_sd,
-                 dice_classes=None, dice_macro=None, dice_micro=None) -> None:
+                 dice_classes=None, dice_macro=None, dice_micro=None, average_surface_distances=None,
+                 average_surface_distances_gt_to_pred=None, average_surface_distances_pred_to_gt=None,
+                 hausdorff_distances=None) -> None:
         self.image = image
         self.image_name = image_name
         self.image_segments = image_segments
@@ -52,6 +56,10 @@ class EvaluationOutput:
         self.abs_err_sd = abs_err_sd
         self.err_sd = err_sd
         self.dice_classes, self.dice_macro, self.dice_micro = dice_classes, dice_macro, dice_micro
+        self.average_surface_distances = average_surface_distances
+        self.average_surface_distances_gt_to_pred = average_surface_distances_gt_to_pred
+        self.average_surface_distances_pred_to_gt = average_surface_distances_pred_to_gt
+        self.hausdorff_distances = hausdorff_distances
 
 
 def _dice_metrics(metrics, num_classes, label_onehot_hw, categorical_pred, transposed=False):
@@ -72,11 +80,21 @@ def _dice_metrics(metrics, num_classes, label_onehot_hw, categorical_pred, trans
     return dc, dm, dmi
 
 
+def _surface_metrics(metrics, rows):
+    """Per-image surface-distance datasets (evaluation.py:207-262) from one (C-1, 6) row block of the device, restricted
+    to the metrics asked for."""
+    if rows is None:
+        return {}
+    d = surface_datasets(rows)
+    keep = []
+    if EVALUATION_METRIC_AVERAGE_SURFACE_DISTANCE in metrics:
+        keep += ["average_surface_distances", "average_surface_distances_gt_to_pred", "average_surface_distances_pred_to_gt"]
+    if EVALUATION_METRIC_HAUSDORFF_DISTANCE in metrics:
+        keep.append("hausdorff_distances")
+    return {k: d[k] for k in keep}
+
+
 def evaluate_model(eval_params: EvaluationParameters) -> List[EvaluationOutput]:
-    for m in (EVALUATION_METRIC_AVERAGE_SURFACE_DISTANCE, EVALUATION_METRIC_HAUSDORFF_DISTANCE):
-        if m in eval_params.metrics:
-            log.error(f"Metric '{m}' needs the un-vendored surface-distance package and is outside the accelerated path.")
-            exit(1)
     rank, _, _ = parallel.init()
     world = parallel.world_size()
 
@@ -111,19 +129,40 @@ def evaluate_model(eval_params: EvaluationParameters) -> List[EvaluationOutput]:
     if eval_params.graph_search and hi > lo:
         pool = SegmentPool(eval_images.shape[1:3], eval_params.gsgrad, getattr(eval_params, "gs_workers", None))
     batches = ()
+    # surface distances (evaluation.py:207-262) run on the device next to the forward: arg-max maps against the uploaded
+    # ground-truth class maps, spacing (0.01111111, 0.01111111), percent 95
+    want_surface = any(m in eval_params.metrics for m in (EVALUATION_METRIC_AVERAGE_SURFACE_DISTANCE,
+                                                           EVALUATION_METRIC_HAUSDORFF_DISTANCE))
+    gt_u8 = surface = None
+    if want_surface and hi > lo:
+        gt = np.squeeze(eval_labels[lo:hi], axis=3)
+        if gt.min() < 0 or gt.max() >= num_classes:
+            raise ValueError(f"ground-truth labels outside 0..{num_classes - 1}")
+        gt_u8 = np.ascontiguousarray(gt.astype(np.uint8))
+        surface = SurfaceDistances(bs, eval_images.shape[1], eval_images.shape[2], num_classes,
+                                   eval_params.loaded_model._dev())
     if hi > lo and eval_images.dtype == np.uint8:
         engine = eval_params.loaded_model._ensure_engine(bs, False)
-        batches = BatchedPredictor(engine, bs, want_maps=True, bg_ilm=True, bg_csi=False).run(eval_images[lo:hi])
+        batches = BatchedPredictor(engine, bs, want_maps=True, bg_ilm=True, bg_csi=False,
+                                   surface=surface).run(eval_images[lo:hi], gt_u8)
     elif hi > lo:      # non-uint8 datasets: x / 255 on the host (Model.predict_labels), same outputs, no overlap
         def _plain():
+            import torch
             for r0 in range(0, hi - lo, bs):
                 r1 = min(r0 + bs, hi - lo)
                 lm, dm = eval_params.loaded_model.predict_labels(eval_images[lo + r0:lo + r1], batch_size=bs, want_maps=True,
                                                                  bg_ilm=True, bg_csi=False)
-                yield r0, r1, lm, dm
+                rows = None
+                if surface is not None:
+                    pred_dev = torch.from_numpy(np.ascontiguousarray(lm.astype(np.uint8))).to(surface.device)
+                    gt_dev = torch.from_numpy(gt_u8[r0:r1]).to(surface.device)
+                    rows = surface(pred_dev, gt_dev).cpu().numpy()
+                yield r0, r1, lm, dm, rows
         batches = _plain()
     t_prev = time.time()
-    for rb0, rb1, label_maps, dev_maps in batches:
+    for batch in batches:
+        rb0, rb1, label_maps, dev_maps = batch[:4]
+        surf_rows = batch[4] if len(batch) > 4 else None
         b0, b1 = lo + rb0, lo + rb1
         predict_time = (time.time() - t_prev) / (b1 - b0)
         gs_batch = pool.segment(dev_maps, eval_segments[b0:b1]) if pool is not None else None
@@ -136,13 +175,14 @@ def evaluate_model(eval_params: EvaluationParameters) -> List[EvaluationOutput]:
             categorical_pred = common_utils.labels_to_categorical(predicted_labels, num_classes)
             boundary_maps = dev_maps[ind - b0:ind - b0 + 1]   # == convert_predictions_to_maps_semantic(categorical_pred), on device
             dice_classes, dice_macro, dice_micro = _dice_metrics(eval_params.metrics, num_classes, eval_label, categorical_pred)
+            surface_ds = _surface_metrics(eval_params.metrics, None if surf_rows is None else surf_rows[ind - b0])
 
             predicted_labels = np.squeeze(predicted_labels, axis=0)
             categorical_pred = np.squeeze(categorical_pred, axis=0)
             boundary_maps = np.squeeze(boundary_maps, axis=0)
             _save_image_evaluation_results(eval_params, eval_image, eval_image_name, predicted_labels, categorical_pred,
                                            eval_label, eval_seg, dice_classes, dice_macro, dice_micro, predict_time,
-                                           eval_image_output_dir)
+                                           eval_image_output_dir, surface_ds)
 
             gs_pred_segs = errors = mean_abs_err = mean_err = abs_err_sd = err_sd = None
             if eval_params.graph_search:
@@ -165,7 +205,7 @@ def evaluate_model(eval_params: EvaluationParameters) -> List[EvaluationOutput]:
                 image_output_dir=eval_image_output_dir, predicted_labels=predicted_labels,
                 categorical_pred=categorical_pred, boundary_maps=boundary_maps, gs_pred_segs=gs_pred_segs, errors=errors,
                 mean_abs_err=mean_abs_err, mean_err=mean_err, abs_err_sd=abs_err_sd, err_sd=err_sd,
-                dice_classes=dice_classes, dice_macro=dice_macro, dice_micro=dice_micro))
+                dice_classes=dice_classes, dice_macro=dice_macro, dice_micro=dice_micro, **surface_ds))
         t_prev = time.time()
     if pool is not None:
         pool.close()
@@ -176,7 +216,8 @@ def evaluate_model(eval_params: EvaluationParameters) -> List[EvaluationOutput]:
 
 
 def _save_image_evaluation_results(eval_params, eval_image, image_name, predicted_labels, categorical_pred, eval_labels,
-                                   eval_segs, dice_classes, dice_macro, dice_micro, predict_time, output_dir):
+                                   eval_segs, dice_classes, dice_macro, dice_micro, predict_time, output_dir,
+                                   surface_ds=None):
     with open(output_dir / "input_image_name.txt", "w") as f:
         f.write(str(image_name))
     np.savetxt(output_dir / Path("predicted_segmentation_map.csv"), predicted_labels, fmt="%d", delimiter=",")
@@ -196,6 +237,8 @@ def _save_image_evaluation_results(eval_params, eval_image, image_name, predicte
         ds[EVALUATION_METRIC_DICE_MACRO] = np.expand_dims(dice_macro, axis=0).astype("float64")
     if dice_micro is not None:
         ds[EVALUATION_METRIC_DICE_MICRO] = np.expand_dims(dice_micro, axis=0).astype("float64")
+    for k, v in (surface_ds or {}).items():          # evaluation.py:573-597
+        ds[k] = np.asarray(v, dtype="float64")
     attrs = {"model_filename": np.array(str(eval_params.model_path), dtype="S1000"),
              "image_name": np.array(str(image_name), dtype="S1000"),
              "timestamp": np.array(common_utils.get_timestamp(), dtype="S1000"),
@@ -264,6 +307,12 @@ def _calc_overall_dataset_errors(eval_params: EvaluationParameters, eval_image_n
     for m in (EVALUATION_METRIC_DICE_CLASSES, EVALUATION_METRIC_DICE_MACRO, EVALUATION_METRIC_DICE_MICRO):
         if m in metrics:
             save_metric(m, stack(files, m))
+    if EVALUATION_METRIC_AVERAGE_SURFACE_DISTANCE in metrics:          # evaluation.py:870-880
+        for name in ("average_surface_distances", "average_surface_distances_gt_to_pred",
+                     "average_surface_distances_pred_to_gt"):
+            save_metric(name, stack(files, name))
+    if EVALUATION_METRIC_HAUSDORFF_DISTANCE in metrics:
+        save_metric("hausdorff_distances", stack(files, "hausdorff_distances"))
     if eval_params.graph_search:
         for m in (EVALUATION_METRIC_DICE_CLASSES, EVALUATION_METRIC_DICE_MACRO, EVALUATION_METRIC_DICE_MICRO):
             if m in metrics:

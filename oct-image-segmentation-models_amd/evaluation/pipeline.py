@@ -20,9 +20,14 @@ from ..min_path_processing.pool import SegmentPool, default_workers
 
 class BatchedPredictor:
     """Fixed-batch graph replay with overlapped transfers.  ``run(images_u8)`` yields
-    ``(lo, hi, labels (n,H,W) uint8, maps (n,C-1,H,W) uint8 | None)`` per device batch, in order."""
+    ``(lo, hi, labels (n,H,W) uint8, maps (n,C-1,H,W) uint8 | None)`` per device batch, in order.
 
-    def __init__(self, engine, batch: int, want_maps: bool = True, bg_ilm: bool = True, bg_csi: bool = False):
+    With ``surface`` (an ``evaluation.surface.SurfaceDistances`` for this batch and shape), ``run(images_u8, gt_u8)``
+    also uploads the ground-truth class maps (n,H,W) double-buffered like the images, runs the surface-distance kernels on
+    the arg-max maps behind their copy, and yields a fifth element: the (n, C-1, 6) float64 rows."""
+
+    def __init__(self, engine, batch: int, want_maps: bool = True, bg_ilm: bool = True, bg_csi: bool = False,
+                 surface=None):
         if not 1 <= batch <= engine.cfg.max_batch:
             raise ValueError(f"batch {batch} outside 1..max_batch={engine.cfg.max_batch}")
         self.eng, self.B, self.want_maps, self.bg = engine, int(batch), want_maps, (bg_ilm, bg_csi)
@@ -35,14 +40,29 @@ class BatchedPredictor:
         self.map_pin = [torch.empty((self.B, C - 1, H, W), dtype=torch.uint8).pin_memory() for _ in range(2)] if want_maps else None
         self.lab_dev = [torch.empty((self.B, H, W), dtype=torch.uint8, device=dev) for _ in range(2)]
         self.map_dev = [torch.empty((self.B, C - 1, H, W), dtype=torch.uint8, device=dev) for _ in range(2)] if want_maps else None
+        self.surf = surface
+        if surface is not None:
+            if (surface.B, surface.H, surface.W, surface.C) != (self.B, H, W, C):
+                raise ValueError("surface: SurfaceDistances built for another batch / shape")
+            self.gt_pin = [torch.empty((self.B, H, W), dtype=torch.uint8).pin_memory() for _ in range(2)]
+            self.gt_dev = [torch.empty((self.B, H, W), dtype=torch.uint8, device=dev) for _ in range(2)]
+            self.sd_dev = [torch.empty((self.B, C - 1, 6), dtype=torch.float64, device=dev) for _ in range(2)]
+            self.sd_pin = [torch.empty((self.B, C - 1, 6), dtype=torch.float64).pin_memory() for _ in range(2)]
         self.copy_in = torch.cuda.Stream(device=dev)
         self.copy_out = torch.cuda.Stream(device=dev)
         _, self.am = engine.graph_capture(self.x_dev, want_probs=False, want_argmax=True)
 
-    def run(self, images_u8: np.ndarray) -> Iterator[Tuple[int, int, np.ndarray, Optional[np.ndarray]]]:
+    def run(self, images_u8: np.ndarray, gt_u8: Optional[np.ndarray] = None) -> Iterator[tuple]:
         images_u8 = np.ascontiguousarray(images_u8)
         if images_u8.dtype != np.uint8:
             raise TypeError("the batched pipeline takes raw uint8 images (the /255 happens on the device)")
+        surf = gt_u8 is not None
+        if surf:
+            if self.surf is None:
+                raise ValueError("ground-truth maps given to a BatchedPredictor built without surface=")
+            gt_u8 = np.ascontiguousarray(gt_u8)
+            if gt_u8.dtype != np.uint8 or gt_u8.shape != images_u8.shape[:3]:
+                raise TypeError(f"gt_u8 must be uint8 class maps of shape {images_u8.shape[:3]}")
         n, B, eng = images_u8.shape[0], self.B, self.eng
         main = torch.cuda.current_stream(eng.device)
         nb = (n + B - 1) // B
@@ -50,6 +70,7 @@ class BatchedPredictor:
         x_free = [torch.cuda.Event() for _ in range(2)]
         out_done = [torch.cuda.Event() for _ in range(2)]
         out_ready = [torch.cuda.Event() for _ in range(2)]
+        gt_free = [torch.cuda.Event() for _ in range(2)]
 
         def upload(i):
             lo, hi, s = i * B, min(n, (i + 1) * B), i & 1
@@ -58,10 +79,16 @@ class BatchedPredictor:
                 # run (the device-side wait below only protects the staging buffer; no other host sync orders copy_in)
                 up_done[s].synchronize()
             self.x_pin[s][:hi - lo].copy_(torch.from_numpy(images_u8[lo:hi]))       # host gather into pinned memory
+            if surf:
+                self.gt_pin[s][:hi - lo].copy_(torch.from_numpy(gt_u8[lo:hi]))
             with torch.cuda.stream(self.copy_in):
                 if i >= 2:
                     self.copy_in.wait_event(x_free[s])                                  # staging buffer consumed by batch i-2
+                    if surf:
+                        self.copy_in.wait_event(gt_free[s])                             # gt maps of batch i-2 consumed
                 self.x_stage[s][:hi - lo].copy_(self.x_pin[s][:hi - lo], non_blocking=True)
+                if surf:
+                    self.gt_dev[s][:hi - lo].copy_(self.gt_pin[s][:hi - lo], non_blocking=True)
                 up_done[s].record(self.copy_in)
 
         pending = None
@@ -78,6 +105,10 @@ class BatchedPredictor:
             if i >= 2:
                 main.wait_event(out_done[s])                                            # device out buffers of batch i-2 downloaded
             self.lab_dev[s].copy_(self.am)
+            if surf:
+                # (the call waits for this stream once: it checks the labels on the device before the distance passes)
+                self.surf(self.lab_dev[s][:hi - lo], self.gt_dev[s][:hi - lo], out=self.sd_dev[s][:hi - lo])
+                gt_free[s].record(main)
             if self.want_maps:
                 self.map_dev[s].copy_(eng.boundary_maps(self.am, bg_ilm=self.bg[0], bg_csi=self.bg[1]))
             out_ready[s].record(main)
@@ -86,17 +117,21 @@ class BatchedPredictor:
                 self.lab_pin[s].copy_(self.lab_dev[s], non_blocking=True)
                 if self.want_maps:
                     self.map_pin[s].copy_(self.map_dev[s], non_blocking=True)
+                if surf:
+                    self.sd_pin[s].copy_(self.sd_dev[s], non_blocking=True)
                 out_done[s].record(self.copy_out)
             if pending is not None:
-                yield self._collect(*pending)
+                yield self._collect(*pending, surf)
             pending = (lo, hi, s, out_done[s])
         if pending is not None:
-            yield self._collect(*pending)
+            yield self._collect(*pending, surf)
 
-    def _collect(self, lo, hi, s, ev):
+    def _collect(self, lo, hi, s, ev, surf=False):
         ev.synchronize()
         labels = self.lab_pin[s][:hi - lo].numpy().copy()
         maps = self.map_pin[s][:hi - lo].numpy().copy() if self.want_maps else None
+        if surf:
+            return lo, hi, labels, maps, self.sd_pin[s][:hi - lo].numpy().copy()
         return lo, hi, labels, maps
 
 
