@@ -1,5 +1,5 @@
 """Shared test helpers (CPU side): numpy replica of the engine's counter-based dropout stream and a
-ReLU-boundary margin check that justifies tight fp32-vs-fp64 tolerances."""
+ReLU-boundary margin check that justifies tight fp32-vs-fp64 tolerances; a writable view of an engine's stored tensors."""
 import numpy as np
 
 from oracle import unet_numpy as on
@@ -31,3 +31,20 @@ def relu_margin(cfg, params, cache) -> float:
             yb = params[li]["gamma"] * cache[li]["xhat"] + params[li]["beta"]
             m = min(m, float(np.abs(yb).min()))
     return m
+
+
+def stored_activation_view(eng, layer: int, which: int = 0):
+    """A layer's saved pre-BN output (which=0) or gradient buffer (which=1) as a WRITABLE (max_batch, H, W, cout) view
+    of the engine's workspace in its storage type (float32, or bfloat16 where ``debug_activation`` returns a copy)."""
+    import torch
+    L = eng.layers[layer]
+    shape = (eng.cfg.max_batch, L["out_h"], L["out_w"], L["cout"])
+    n = shape[0] * shape[1] * shape[2] * shape[3]
+    bf = eng.cfg.dtype == 1
+    ref = eng.debug_activation(layer, which)          # (raises for a layer without such a buffer)
+    if not bf:
+        return ref
+    # bf16 storage: find the buffer's offset the way debug_activation does
+    from oct_image_segmentation_models_amd import _hip
+    off = _hip.lib().oct_unet_debug_activation(eng._h, layer, which) - eng.workspace.data_ptr()
+    return eng.workspace[off:off + 2 * n].view(torch.bfloat16).view(shape)

@@ -12,7 +12,11 @@ scale; record rows within 1e-5.  Measured margins: >= 7x on the per-element, par
 the relative L2 gate at the widest layers, which is what fp32 accumulation predicts there (the arithmetic is at REL_L2
 in tests/layer_local.py).  Elements whose ReLU mask or pool route is decided within fp32 rounding are excluded and
 counted (<= 1e-5 of the elements).  bf16 gates: the one-rounding bounds of test_bf16_storage_layer_local_rounding_is_exact
-per layer and image.  Each test prints its per-layer table (worst err / bound per gate) and its wall time."""
+per layer and image.  Each test prints its per-layer table (worst err / bound per gate) and its wall time.
+
+Two tests run a batch SMALLER than max_batch on an engine that has already run a full one (the ragged last batch of an
+epoch on the engine Model._ensure_engine reuses): the workspace is carved for max_batch and still holds the larger step,
+while every launch sizes its grid, its statistic rows and its kernel family by the call's B."""
 import time
 
 import numpy as np
@@ -69,6 +73,13 @@ CONV_INFER = {"conv_bt_k<2,1,0,16,3,float,2px>", "conv_bt_k<2,1,0,32,3,float>", 
               "conv_bx_k<2,1,0,8,32,3,4,float,1img>", "conv_bx_k<3,0,0,4,64,3,4,float,1img>",
               "conv_bx_k<3,0,0,8,32,3,4,float,1img>", "conv_first_fwd_k<float>", "head_fwd_k<3,8,float>",
               "pool_fwd_k<float>"}
+
+
+# the partial steps on used engines: fp32 B = 7 on a max_batch-32 engine, bf16 B = 5 on a max_batch-8 engine (512x1024, P=5)
+# (routing depends on the call's B: at these batch sizes the up-conv forward of the widest level leaves the 8-wave
+# double-buffered blocks for the 4-wave two-image ones; everything else is the full-batch set)
+CONV_B7_OF_32 = (CONV_B32 - {"conv_bx_k<2,1,0,8,64,3,8,float>"}) | {"conv_bx_k<2,1,0,4,64,3,4,float>"}
+CONV_B5_OF_8 = (CONV_CFG2 - {"conv_bx_k<2,1,0,8,64,1,8,unsigned short>"}) | {"conv_bx_k<2,1,0,4,64,1,4,unsigned short>"}
 
 
 def _compute_kernels(ents):
@@ -195,6 +206,75 @@ def test_configs2_bf16_batch_64_every_layer_every_image():
                                                                   g_sep[L["kernel_off"]:L["beta_off" if L["has_bn"] else "bias_off"] + L["cout"]])]
     _finish(rep, t0, "configs[2] bf16 B=64 512x1024 P=5")
     assert not differ, f"fused and stand-alone BN-backward routes differ at configs[2] in {differ}"
+
+
+def _used_engine_partial_step(eng, cfg, img_full, lab_full, img, lab, mode):
+    """One full step at max_batch on ``img_full``, then the step under test on the B < max_batch scans ``img``: returns
+    the layer-local report of the partial step and the profile entries of its launches."""
+    from oct_image_segmentation_models_amd import _hip
+    weights = eng.get_weights()
+    x = torch.from_numpy(img_full).cuda(); l = torch.from_numpy(lab_full[..., 0].copy()).cuda()
+    eng.set_dropout_step(2)
+    eng.forward(x, training=True, labels=l, want_probs=False)
+    eng.loss_dice()
+    eng.backward(l, macro=True, loss_scale=1.0)
+    eng.set_weights(weights)                      # (the moving statistics of the full step are not part of the check)
+    B = img.shape[0]
+    assert B < eng.cfg.max_batch
+    x = torch.from_numpy(img).cuda(); l = torch.from_numpy(lab[..., 0].copy()).cuda()
+    eng.set_dropout_step(3)
+    mask = eng.dropout_mask(B).double()
+    eng.profile_begin()
+    probs, _ = eng.forward(x, training=True, labels=l)
+    eng.loss_dice()
+    eng.backward(l, macro=True, loss_scale=1.0)
+    ents = eng.profile_end()
+    p64, _ = _params_from_engine(eng)
+    S = ll.engine_stored(eng, B, probs)
+    rep = ll.LayerLocal(cfg, p64, S, img, labels=lab[..., 0], dropout_mask=mask, mode=mode,
+                        mfma_mode=_hip.get_option("mfma_mode"), device="cuda:0").run()
+    return rep, ents
+
+
+def test_configs1_fp32_batch_7_on_an_engine_used_at_32():
+    """configs[1] geometry, fp32, max_batch 32: one full B = 32 step, then B = 7 on other scans (the ragged last batch of
+    an epoch on the reused engine).  The workspace still holds the larger step; routing depends on the call's B."""
+    from oct_image_segmentation_models_amd.engine import UNetEngine
+    from tests.test_gpu_fullsize import scans
+    t0 = time.time()
+    MB, B, H, W, P = 32, 7, 256, 512, 4
+    cfg = on.UNetConfig(num_classes=C, start_neurons=8, pool_layers=P)
+    params, state = on.init_params(cfg, seed=7, dtype=np.float32, randomize_bn=True)
+    eng = UNetEngine(device="cuda:0", input_channels=1, num_classes=C, image_height=H, image_width=W, max_batch=MB,
+                     training=True, seed=5, init_seed=1)
+    eng.set_weights(on.keras_weight_list(params, state))
+    img, lab = scans(MB, 31)
+    for k in range(MB):
+        img[k] = np.roll(img[k], 5 * k, axis=1); lab[k] = np.roll(lab[k], 5 * k, axis=1)
+    img7, lab7 = scans(B, 57)
+    for k in range(B):
+        img7[k] = np.roll(img7[k], 11 * k + 3, axis=1); lab7[k] = np.roll(lab7[k], 11 * k + 3, axis=1)
+    rep, ents = _used_engine_partial_step(eng, cfg, img, lab, img7, lab7, "f32")
+    _check_routing(ents, CONV_B7_OF_32)
+    _finish(rep, t0, "configs[1] fp32 B=7 of max_batch 32, 256x512")
+
+
+def test_configs2_bf16_batch_5_on_an_engine_used_at_8():
+    """configs[2] geometry (512x1024, P=5), bf16 storage, max_batch 8: one full step, then B = 5 on other scans."""
+    from oct_image_segmentation_models_amd.common.synthetic import make_scans
+    from oct_image_segmentation_models_amd.engine import UNetEngine
+    t0 = time.time()
+    MB, B, H, W, P = 8, 5, 512, 1024, 5
+    cfg = on.UNetConfig(num_classes=C, start_neurons=8, pool_layers=P)
+    params, state = on.init_params(cfg, seed=11, dtype=np.float32, randomize_bn=True)
+    eng = UNetEngine(device="cuda:0", input_channels=1, num_classes=C, image_height=H, image_width=W, max_batch=MB,
+                     training=True, seed=5, init_seed=2, pool_layers=P, dtype="bfloat16")
+    eng.set_weights(on.keras_weight_list(params, state))
+    img, lab = make_scans(MB, H, W, C, seed=41)
+    img5, lab5 = make_scans(B, H, W, C, seed=67)
+    rep, ents = _used_engine_partial_step(eng, cfg, img, lab, img5, lab5, "bf16")
+    _check_routing(ents, CONV_B5_OF_8)
+    _finish(rep, t0, "configs[2] bf16 B=5 of max_batch 8, 512x1024 P=5")
 
 
 def test_configs4_inference_batch_128_every_layer():

@@ -9,7 +9,7 @@ import pytest
 import torch
 
 from oracle import unet_numpy as on
-from tests.helpers import dropout_keep_mask, relu_margin
+from tests.helpers import dropout_keep_mask, relu_margin, stored_activation_view
 # the bf16-mode rounding rules are shared with the full-size layer-local checks
 from tests.layer_local import (bf16_dw_operands, bf16_dx_weights, bf16_fwd_operands, bf16_round, bf16_ulp,  # noqa: F401
                                upconv_dx_effective)
@@ -140,12 +140,12 @@ def test_inference_forward_matches_oracle(case, variant):
     assert torch.equal(probs_f, probs)
 
 
-@pytest.mark.parametrize("macro", [True, False])
-@pytest.mark.parametrize("case", CASES)
-def test_training_step_matches_oracle(case, macro, variant):
+def training_step_vs_oracle(cfg, eng, p64, s64, case, images, labels, macro, variant):
+    """One training step of ``eng`` on the case's own B images (the engine's max_batch may be larger) against the fp64
+    oracle: layer-wise z, probabilities, the four loss values, layer-wise dz, every gradient piece, the moving
+    statistics.  Returns (probabilities, loss vector) of the step."""
     B, H, W, C, sn, P, L, ic = case
-    cfg, eng, p64, s64 = make(B, H, W, C, sn, P, L, ic, training=True)
-    images, labels = data(B, H, W, C, ic, seed=MARGIN_SEED[case])
+    assert images.shape[0] == B
     x = torch.from_numpy(images).cuda()
     lab = torch.from_numpy(labels[..., 0].copy()).cuda()
     eng.set_dropout_step(DROP_STEP)
@@ -155,7 +155,8 @@ def test_training_step_matches_oracle(case, macro, variant):
     mask = mask.astype(np.float64)
     assert 0.3 < mask.mean() < 0.7
     probs, _ = eng.forward(x, training=True, labels=lab)
-    loss4 = eng.loss_dice().cpu().numpy()
+    loss4_dev = eng.loss_dice()
+    loss4 = loss4_dev.cpu().numpy()
     eng.backward(lab, macro=macro, loss_scale=0.5)
     torch.cuda.synchronize()
 
@@ -163,10 +164,13 @@ def test_training_step_matches_oracle(case, macro, variant):
     ref, cache = on.forward(cfg, p64, s64, xin, training=True, dropout_mask=mask)
     assert relu_margin(cfg, p64, cache) > 2e-5, "test input lost its ReLU margin; re-run the seed search"
     plan = on.build_plan(cfg)
+    worst = {"z": 0.0, "dz": 0.0}                       # worst err / bound per gate, printed at the end
     for li, spec in enumerate(plan[:-1]):
         z = eng.debug_activation(li, 0)[:B].cpu().numpy()
         scale = max(1.0, np.abs(cache[li]["z"]).max())
+        worst["z"] = max(worst["z"], np.abs(z - cache[li]["z"]).max() / scale / 1e-4)
         assert np.abs(z - cache[li]["z"]).max() / scale < 1e-4, f"layer {li} {spec.name} pre-BN output differs"
+    worst["probs"] = np.abs(probs.cpu().numpy() - ref).max() / PROB_TOL
     assert np.abs(probs.cpu().numpy() - ref).max() < PROB_TOL
 
     y = on.one_hot(labels, C, np.float64)
@@ -186,6 +190,7 @@ def test_training_step_matches_oracle(case, macro, variant):
         dz = eng.debug_dz(li)[:B].cpu().numpy()
         ref_dz = cache[li]["dz"]
         scale = np.abs(ref_dz).max()
+        worst["dz"] = max(worst["dz"], np.abs(dz - ref_dz).max() / scale / 5e-4)
         assert np.abs(dz - ref_dz).max() / scale < 5e-4, f"layer {li} {plan[li].name} dz differs"
     if variant == "bn_apply_separate":
         assert n_fused == 0
@@ -194,7 +199,22 @@ def test_training_step_matches_oracle(case, macro, variant):
     elif sn == 8 and ic == 1:
         # (every block but those behind the thin kernel's instantiations that would spill: 32 K channels, 16 K with 16 outputs)
         assert n_fused >= 4, n_fused
+    worst["grads"] = check_grads_vs_oracle(eng, grads) / GRAD_RTOL
+
+    # moving statistics (Bessel-corrected variance, momentum 0.99)
+    new_state = on.flatten_state(on.updated_moving_stats(cfg, s64, cache))
+    worst["state"] = np.abs(eng.state.cpu().numpy() - new_state).max() / 1e-5
+    assert np.abs(eng.state.cpu().numpy() - new_state).max() < 1e-5
+    worst["loss"] = max(abs(loss4[0] - on.dice_loss_macro(y, ref)), abs(loss4[1] - on.dice_loss_micro(y, ref))) / 1e-5
+    print("worst err / bound:", ", ".join(f"{k} {v:.3f}" for k, v in worst.items()))
+    return probs, loss4_dev
+
+
+def check_grads_vs_oracle(eng, grads):
+    """Every gradient piece of every layer within GRAD_RTOL of the oracle's, on the scale of the piece; returns the
+    worst relative error."""
     g = eng.grads.cpu().numpy()
+    worst = 0.0
     for L_, gr in zip(eng.layers, grads):
         n = L_["kh"] * L_["kw"] * L_["cin"] * L_["cout"]; c = L_["cout"]
         pieces = [("kernel", L_["kernel_off"], n), ("bias", L_["bias_off"], c)]
@@ -206,11 +226,115 @@ def test_training_step_matches_oracle(case, macro, variant):
             # a conv bias ahead of a BN has an analytically zero gradient: judge it on the kernel's scale
             scale = max(np.abs(refv).max(), kscale if key == "bias" else 0.0, 1e-12)
             err = np.abs(g[off:off + cnt] - refv).max() / scale
+            worst = max(worst, err)
             assert err < GRAD_RTOL, f"{L_['name']}.{key}: rel err {err}"
+    return worst
 
-    # moving statistics (Bessel-corrected variance, momentum 0.99)
-    new_state = on.flatten_state(on.updated_moving_stats(cfg, s64, cache))
-    assert np.abs(eng.state.cpu().numpy() - new_state).max() < 1e-5
+
+@pytest.mark.parametrize("macro", [True, False])
+@pytest.mark.parametrize("case", CASES)
+def test_training_step_matches_oracle(case, macro, variant):
+    B, H, W, C, sn, P, L, ic = case
+    cfg, eng, p64, s64 = make(B, H, W, C, sn, P, L, ic, training=True)
+    images, labels = data(B, H, W, C, ic, seed=MARGIN_SEED[case])
+    training_step_vs_oracle(cfg, eng, p64, s64, case, images, labels, macro, variant)
+
+
+GRAD_SENTINEL = 1e30
+
+
+def dirty_engine(eng, B, seed, scale=64.0):
+    """Make ``eng`` a USED engine before a step at B < max_batch: one full training step at max_batch on other scans
+    (fed as float32, scaled up so that every stale row is large), then NaN in the tail rows [B:max_batch] of every
+    layer's z and gradient buffer and a large finite sentinel in every gradient float.  The caller restores the weights
+    (set_weights: parameters and moving statistics) afterwards."""
+    mb, H, W, ic, C = eng.cfg.max_batch, eng.cfg.H, eng.cfg.W, eng.cfg.in_ch, eng.cfg.n_cls
+    assert B < mb
+    images, labels = data(mb, H, W, C, ic, seed=seed)
+    x = torch.from_numpy(on.preprocess_u8(images, np.float32) * np.float32(scale)).cuda()
+    lab = torch.from_numpy(labels[..., 0].copy()).cuda()
+    eng.set_dropout_step(DROP_STEP + 1)
+    eng.forward(x, training=True, labels=lab, want_probs=False)
+    eng.loss_dice()
+    eng.backward(lab, macro=True)
+    torch.cuda.synchronize()
+    nb = len(eng.layers) - 1
+    for li in range(nb):
+        for which in (0, 1):
+            v = stored_activation_view(eng, li, which)
+            assert bool((v[B:].float() != 0).any()), (li, which)     # the full step really left something behind
+            v[B:] = float("nan")
+    eng.grads.fill_(GRAD_SENTINEL)
+
+
+def assert_tails_untouched(eng, B):
+    """The NaN tails written by dirty_engine are still NaN everywhere (nothing wrote past image B - 1) and backward filled
+    the whole gradient buffer."""
+    for li in range(len(eng.layers) - 1):
+        for which in (0, 1):
+            assert bool(torch.isnan(stored_activation_view(eng, li, which)[B:]).all()), \
+                f"{eng.layers[li]['name']} {'zg'[which]} buffer: rows past image {B - 1} were written"
+    g = eng.grads
+    assert bool(torch.isfinite(g).all())
+    assert not bool((g.abs() >= 1e-3 * GRAD_SENTINEL).any()), "a gradient float still holds (part of) the sentinel"
+
+
+def assert_same_as_fresh_engine(eng, fresh, B, probs, probs_f, loss4, loss4_f):
+    """The partial step on the used engine against the same step on an engine created with max_batch = B: bit for bit."""
+    for li, L_ in enumerate(eng.layers[:-1]):
+        assert torch.equal(stored_activation_view(eng, li, 0)[:B], stored_activation_view(fresh, li, 0)[:B]), f"{L_['name']} z"
+        assert torch.equal(eng.debug_bn_record(li), fresh.debug_bn_record(li)), f"{L_['name']} BN record"
+    assert torch.equal(probs, probs_f) and torch.equal(loss4, loss4_f) and torch.equal(eng.state, fresh.state)
+    # the backward-weights plan of a launch (kernel family, channel chunks, number of partial slabs) is a function of the
+    # call's B; the slab count is only clamped by the rows allocated for max_batch, which are never fewer: same launches,
+    # same summation order, equal gradients
+    for L_ in eng.layers:
+        lo, hi = L_["kernel_off"], (L_["beta_off"] if L_["has_bn"] else L_["bias_off"]) + L_["cout"]
+        assert torch.equal(eng.grads[lo:hi], fresh.grads[lo:hi]), f"{L_['name']} gradients"
+
+
+# (case, macro, max_batch): max_batch = B + 1 with the macro loss, 4 B with the micro loss, and one B = 1 step on an
+# engine for 3 -- the committed margin seeds stay valid (the margin is a property of the B images and the (B, ...)
+# dropout mask, not of max_batch)
+PARTIAL = [(c, True, c[0] + 1) for c in CASES] + [(c, False, 4 * c[0]) for c in CASES] + [(CASES[5], True, 3)]
+
+
+@pytest.mark.parametrize("case,macro,max_batch", PARTIAL)
+def test_partial_training_step_on_a_used_engine(case, macro, max_batch, variant):
+    """A batch smaller than max_batch on an engine that has already run a full one (the ragged last batch of an epoch,
+    a smaller validation batch, predict after fit: Model._ensure_engine reuses the engine).  The workspace is carved for
+    max_batch and still holds the larger step; every launch must size itself by the call's B."""
+    B, H, W, C, sn, P, L, ic = case
+    cfg, eng, p64, s64 = make(B, H, W, C, sn, P, L, ic, training=True, max_batch=max_batch)
+    weights = eng.get_weights()
+    dirty_engine(eng, B, seed=MARGIN_SEED[case] + 1000)
+    eng.set_weights(weights)
+    images, labels = data(B, H, W, C, ic, seed=MARGIN_SEED[case])
+    probs, loss4 = training_step_vs_oracle(cfg, eng, p64, s64, case, images, labels, macro, variant)
+    assert bool(torch.isfinite(probs).all()) and bool(torch.isfinite(loss4).all()) and bool(torch.isfinite(eng.state).all())
+    assert_tails_untouched(eng, B)
+
+    # the same step on a fresh engine created with max_batch = B
+    _, fresh, _, _ = make(B, H, W, C, sn, P, L, ic, training=True)
+    x = torch.from_numpy(images).cuda(); lab = torch.from_numpy(labels[..., 0].copy()).cuda()
+    fresh.set_dropout_step(DROP_STEP)
+    probs_f, _ = fresh.forward(x, training=True, labels=lab)
+    loss4_f = fresh.loss_dice()
+    fresh.backward(lab, macro=macro, loss_scale=0.5)
+    torch.cuda.synchronize()
+    assert_same_as_fresh_engine(eng, fresh, B, probs, probs_f, loss4, loss4_f)
+
+    # the validation path of Model._run_epoch on the same used training engine: inference forward with labels + Dice
+    pv, _ = eng.forward(x, training=False, labels=lab)
+    lv = eng.loss_dice().cpu().numpy()
+    s_new = on.unflatten_state(cfg, eng.state.cpu().numpy().astype(np.float64))
+    ref_v, _ = on.forward(cfg, p64, s_new, on.preprocess_u8(images, np.float64), training=False)
+    assert np.abs(pv.cpu().numpy() - ref_v).max() < PROB_TOL
+    y = on.one_hot(labels, C, np.float64)
+    assert abs(lv[0] - on.dice_loss_macro(y, ref_v)) < 1e-5 and abs(lv[1] - on.dice_loss_micro(y, ref_v)) < 1e-5
+    assert abs(lv[2] - on.dice_coef_macro(y, ref_v)) < DICE_TOL and abs(lv[3] - on.dice_coef_micro(y, ref_v)) < DICE_TOL
+    for li in range(len(eng.layers) - 1):
+        assert bool(torch.isnan(stored_activation_view(eng, li, 0)[B:]).all()), f"{eng.layers[li]['name']}: validation forward wrote past image {B - 1}"
 
 
 def test_adam_and_sgd_steps_match_keras_formulas():
@@ -664,12 +788,12 @@ BF16_CASES = [(2, 32, 64, 3, 8, 2, 2, 1), (1, 48, 80, 3, 8, 3, 1, 3), (1, 32, 64
               (1, 32, 64, 3, 12, 2, 2, 1)]
 
 
-def make_bf16(B, H, W, C, sn, P, L=2, in_ch=1, seed=0):
+def make_bf16(B, H, W, C, sn, P, L=2, in_ch=1, seed=0, max_batch=None):
     from oct_image_segmentation_models_amd.engine import UNetEngine
     cfg = on.UNetConfig(input_channels=in_ch, num_classes=C, start_neurons=sn, pool_layers=P, conv_layers=L)
     params, state = on.init_params(cfg, seed=seed, dtype=np.float32, randomize_bn=True)
     eng = UNetEngine(device="cuda:0", input_channels=in_ch, num_classes=C, image_height=H, image_width=W,
-                     start_neurons=sn, pool_layers=P, conv_layers=L, max_batch=B, training=True, seed=seed + 100,
+                     start_neurons=sn, pool_layers=P, conv_layers=L, max_batch=max_batch or B, training=True, seed=seed + 100,
                      dtype="bfloat16")
     eng.set_weights(on.keras_weight_list(params, state))
     p64 = [{k: v.astype(np.float64) for k, v in p.items()} for p in params]
@@ -685,6 +809,14 @@ def test_bf16_storage_layer_local_rounding_is_exact(case, variant):
     cfg, eng, p64, s64 = make_bf16(B, H, W, C, sn, P, L, ic)
     assert eng.workspace.numel() < 0.8 * make(B, H, W, C, sn, P, L, ic)[1].workspace.numel()   # partials stay fp32
     images, labels = data(B, H, W, C, ic, seed=MARGIN_SEED.get(case, 5))
+    bf16_step_layer_local(cfg, eng, p64, case, images, labels)
+
+
+def bf16_step_layer_local(cfg, eng, p64, case, images, labels):
+    """One training step of a bf16-storage engine on the case's own B images (max_batch may be larger), stand-alone
+    BN-backward route: every stored tensor and every gradient against the fp64 recomputation from the engine's own stored
+    inputs, one rounding each."""
+    B, H, W, C, sn, P, L, ic = case
     x = torch.from_numpy(images).cuda(); lab = torch.from_numpy(labels[..., 0].copy()).cuda()
     eng.set_dropout_step(DROP_STEP)
     mask = eng.dropout_mask(B).cpu().numpy().astype(np.float64)
@@ -785,6 +917,27 @@ def test_bf16_storage_layer_local_rounding_is_exact(case, variant):
         assert (err <= bound).mean() > 0.999, (plan[pi].name, (err <= bound).mean())
         assert (err <= 4 * bound).all(), (plan[pi].name, (err / bound).max())
         assert (err == 0).mean() > 0.99, (plan[pi].name, (err == 0).mean())
+    return probs
+
+
+@pytest.mark.parametrize("case,max_batch", [(BF16_CASES[0], 3), (BF16_CASES[1], 4)])
+def test_bf16_partial_training_step_on_a_used_engine(case, max_batch):
+    """test_partial_training_step_on_a_used_engine in bf16 storage, default kernel selection: the partial step after a
+    full one, held to the one-rounding checks of test_bf16_storage_layer_local_rounding_is_exact."""
+    from oct_image_segmentation_models_amd import _hip
+    B, H, W, C, sn, P, L, ic = case
+    try:
+        _hip.set_option("fuse_first_apply", 0); _hip.set_option("fuse_bn_apply", 0)     # (every block's dz is stored)
+        cfg, eng, p64, s64 = make_bf16(B, H, W, C, sn, P, L, ic, max_batch=max_batch)
+    finally:
+        _hip.set_option("fuse_first_apply", 1); _hip.set_option("fuse_bn_apply", 1)
+    weights = eng.get_weights()
+    dirty_engine(eng, B, seed=MARGIN_SEED.get(case, 5) + 1000)
+    eng.set_weights(weights)
+    images, labels = data(B, H, W, C, ic, seed=MARGIN_SEED.get(case, 5))
+    probs = bf16_step_layer_local(cfg, eng, p64, case, images, labels)
+    assert bool(torch.isfinite(probs).all()) and bool(torch.isfinite(eng.state).all())
+    assert_tails_untouched(eng, B)
 
 
 @pytest.mark.parametrize("case", BF16_CASES[:2])     # (the 4-channel case feeds uniform noise images: its gradient is dominated

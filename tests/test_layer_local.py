@@ -79,17 +79,18 @@ def perfect_engine(cfg, p64, images, labels, mask, mode, fused, macro=True, mm=1
         sp, p = plan[li], p64[li]
         if li < nb:
             alive = (rec[li][0] * z[li] + rec[li][1]) > 0
-            gq = R(alive * (contrib.pop(li) + skipraw.get(li, 0.0)))
+            gun = alive * (contrib.pop(li) + skipraw.get(li, 0.0))     # fp32 accumulators: the statistics are taken of these ...
+            gq = R(gun)                                                # ... and the store rounds
             mean, rstd = rec[li][2], rec[li][3]
             xhat = (z[li] - mean) * rstd
-            c1, c2 = gq.mean(axis=(0, 1, 2)), (gq * xhat).mean(axis=(0, 1, 2))
+            c1, c2 = gun.mean(axis=(0, 1, 2)), (gun * xhat).mean(axis=(0, 1, 2))
             ga = p["gamma"] * rstd; gb = -ga * rstd * c2; gd = -ga * c1 - gb * mean
             rec[li][4:] = c1, c2, ga, gb, gd
             dz_true[li] = ga * (gq - c1 - xhat * c2)
             gbuf[li] = gq if fused[li] else R(dz_true[li])
             dzr[li] = R(ga * gq + gb * z[li] + gd) if fused[li] else gbuf[li]
             gq_of[li] = gq
-            grads[li]["gamma"], grads[li]["beta"] = (gq * xhat).sum(axis=(0, 1, 2)), gq.sum(axis=(0, 1, 2))
+            grads[li]["gamma"], grads[li]["beta"] = (gun * xhat).sum(axis=(0, 1, 2)), gun.sum(axis=(0, 1, 2))
         dz = dzr[li]
         rdw = bf and ll.bf16_dw_operands(plan, li, mm)
         _, dk, db = on._conv_backward(R(inps[li]) if rdw else inps[li], p["kernel"], dz)
