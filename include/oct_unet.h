@@ -27,6 +27,8 @@
  *   oct_adam_step / oct_sgd_step       optimizer.apply_gradients      training/training.py:190-193
  *   gradient buffer (caller-owned)     MirroredStrategy all-reduce    training/training.py:185-188,243
  *   oct_unet_graph_capture/_launch     (none: replaces per-call Keras dispatch overhead, evaluation.py:108-135)
+ *   oct_augment_batch                  BatchGenerator.get_aug_fly/_nofly common/data_generator.py:140-283,
+ *                                      flip_aug / add_noise_aug       common/augmentation.py:43-103
  */
 #ifndef OCT_UNET_H
 #define OCT_UNET_H
@@ -181,6 +183,35 @@ size_t oct_surface_workspace_bytes(int B, int H, int W, int n_cls);
 int oct_surface_distances(const unsigned char* pred_dev, const unsigned char* gt_dev, int B, int H, int W, int n_cls,
                           double spacing_row, double spacing_col, double percent,
                           void* workspace_dev, size_t workspace_bytes, double* out_dev, oct_stream_t stream);
+
+/* ---- training augmentations on device: (B,H,W,C) u8 images -> f32 in [0,1], flipped or with noise added; (B,H,W) u8 labels
+ * flipped alongside (reference common/data_generator.py:140-283 chooses an augmentation per sample, common/augmentation.py:
+ * 43-103 applies it; its noise is skimage.util.random_noise, whose RNG stream is unpinned: the stream here is the library's
+ * own, defined below and restated in numpy by common/augmentation.py device_aug_reference).  Stand-alone: no handle, no
+ * allocation, one asynchronous launch on `stream`, graph-capturable.  Per sample b, op = ops_dev[b]:
+ *   img = float32(x / 255.0), the u8 input definition of oct_unet_forward.
+ *   kind 0 none, 1 flip up-down, 2 flip left-right: out = img at the (mirrored) position, labels mirrored the same way.
+ *   Every other kind copies the labels.  A kind outside 0..5 is only visible on the device and is TREATED AS 0 (no
+ *   device-side flag, no stream wait: validate before upload).  labels_dev == NULL or labels_out_dev == NULL: no labels written.
+ *   Random words: Philox4x32-10 (Salmon et al., SC'11 / Random123), key = (seed low, seed high), counter =
+ *   (e >> 1, 0, noise_id low, noise_id high) with e = (y*W + x)*C + c the element's index inside its sample (output
+ *   position); element e owns words w0 = out[2(e&1)], w1 = out[2(e&1)+1].  Nothing depends on b, B or the launch geometry.
+ *   u1 = ((w0 >> 8) + 1) 2^-24 in (0,1], u2 = (w1 >> 8) 2^-24 in [0,1); z = sqrt(-2 ln u1) cos(2 pi u2) (fp32).
+ *   kind 3 gaussian: out = clip(img + (p0 + p1 z), 0, 1); kind 4 speckle: out = clip(img + img (p0 + p1 z), 0, 1);
+ *     p0 = mean, p1 = sigma = sqrt(variance).
+ *   kind 5 salt-and-pepper: flipped = ((w1 >> 8) 2^-24 <= p0), salted = ((w0 >> 8) 2^-24 <= p1); out = flipped ?
+ *     (salted ? 1 : 0) : img; p0 = amount, p1 = salt_vs_pepper ("salt" = 1, "pepper" = 0).
+ * Errors (negative, nothing launched): null x_u8_dev / ops_dev / x_out_dev, non-positive sizes, B > 65535 or
+ * H*W*C >= 2^31, labels_out_dev without labels_dev, an output range overlapping an input range or the other output. */
+typedef struct oct_aug_op {      /* one per sample of the batch, 32 bytes, in DEVICE memory */
+    int   kind;
+    float p0, p1, p2;
+    unsigned long long noise_id; /* selects the sample's random stream */
+    unsigned long long reserved;
+} oct_aug_op;
+int oct_augment_batch(const unsigned char* x_u8_dev, const unsigned char* labels_dev, const oct_aug_op* ops_dev,
+                      int B, int H, int W, int C, unsigned long long seed,
+                      float* x_out_dev, unsigned char* labels_out_dev, oct_stream_t stream);
 
 /* ---- options ----
  * oct_set_option edits the PROCESS-WIDE DEFAULTS; a handle copies them when it is created (oct_unet_create) and every

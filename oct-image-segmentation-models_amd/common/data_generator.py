@@ -16,10 +16,16 @@ every image -- a defect not reproduced here).  Augmented batches take the float3
 
 Without augmentation, batches are assembled with one fancy-indexing gather instead of the reference's per-sample Python loop
 (SURVEY 3.1 hot loop ii).  ``next_batch_u8`` is the engine's fast path: uint8 images + uint8 sparse labels,
-so the /255 happens on the GPU while the first conv loads the image."""
+so the /255 happens on the GPU while the first conv loads the image.
+
+``device_aug=True`` (off by default) moves the augmentations of ``common.augmentation.augmentation_map`` to the device:
+``next_batch_aug`` walks the generator's state exactly as ``get_batch_list`` does but returns the raw uint8 samples and one
+``oct_aug_op`` descriptor per sample; the engine's ``oct_augment_batch`` applies them (flips exactly; noise from its own
+documented Philox stream, not from numpy's).  Nothing is pre-computed or kept in float on the host in that mode."""
 from __future__ import annotations
 
 import logging as log
+import os
 from math import floor
 from typing import Callable, List, Optional, Tuple
 
@@ -29,7 +35,7 @@ import numpy as np
 class BatchGenerator:
     def __init__(self, images: np.ndarray, labels: np.ndarray, batch_size: int, aug_fn_args: List[Tuple],
                  aug_mode: str, aug_probs: Tuple, aug_fly: bool, preprocess_input_fn: Callable,
-                 seed: Optional[int] = None):
+                 seed: Optional[int] = None, device_aug: bool = False):
         if aug_mode not in ("none", "one", "all"):
             log.error(f"Unrecognized augmentation mode: {aug_mode}. Allowed values: 'none', 'one', 'all'. Exiting...")
             exit(1)
@@ -54,10 +60,21 @@ class BatchGenerator:
         self._rng = np.random.default_rng(seed)  # seed=None: OS entropy, as the reference's np.random.seed()
         self._sparse_cache = None
         self.batch_counter = self.full_counter = self.aug_counter = 0
-        self.images = None if aug_mode == "none" else self.images_u8.astype(np.float32) / np.float32(255.0)
-        if self.aug_fly is False and self.aug_mode != "none":
-            self.aug_images, self.aug_labels = self.setup_augnofly_data()
+        self.images = None
+        self.aug_ops = None         # descriptor templates of aug_fn_args (device path)
+        self.samples_drawn = 0      # GLOBAL-batch samples handed out by next_batch_aug since construction
+        if aug_mode != "none" and device_aug:
+            from . import augmentation
+            self.aug_ops = augmentation.aug_ops_from(aug_fn_args)
+        if aug_mode != "none" and self.aug_ops is None:
+            self._setup_host_aug()
         self.handle_epoch_end()
+
+    def _setup_host_aug(self):
+        """Host path: the float32 copy of the dataset and, with ``aug_fly=False``, the pre-computed augmented set."""
+        self.images = self.images_u8.astype(np.float32) / np.float32(255.0)
+        if self.aug_fly is False:
+            self.aug_images, self.aug_labels = self.setup_augnofly_data()
 
     def setup_augnofly_data(self):
         """Pre-computed augmentations: (N, n_augs, H, W, C) float32 images and (N, n_augs, ...) labels."""
@@ -103,6 +120,8 @@ class BatchGenerator:
 
     def get_batch_list(self):
         if self.aug_mode != "none":
+            if self.images is None:     # a device-augmentation generator asked for host batches after all
+                self._setup_host_aug()
             batch_images = np.zeros((self.batch_size,) + self.images.shape[1:], dtype="float32")
             batch_labels = np.zeros(self.batch_labels_shape)
             for k in range(self.batch_size):
@@ -139,6 +158,41 @@ class BatchGenerator:
             idx = idx[shard[0]:shard[1]]
         return self.images_u8[idx], self.sparse_labels()[idx]
 
+    def next_batch_aug(self, shard: Optional[Tuple[int, int]] = None):
+        """The next GLOBAL batch for the device augmentation: ``(images uint8, labels uint8 (B,H,W), ops)`` with one
+        ``augmentation.AUG_OP_DTYPE`` descriptor per sample.  The generator's state (shuffle walk, ``aug_counter`` /
+        ``full_counter`` wraps, one draw of ``self._rng`` per sample in mode "one") advances exactly as in
+        ``get_batch_list``, so one seed gives one sequence of (image, augmentation) pairs through either path.
+        ``noise_id``: with ``aug_fly`` a running count of the samples drawn since construction (fresh noise every epoch); without,
+        ``image_index * n_augs + j`` (the same noise for a pair in every epoch: what the pre-computed set means).  With
+        ``shard = (lo, hi)`` only samples lo..hi-1 are gathered; their descriptors are those of the one-rank run."""
+        if self.aug_ops is None:
+            raise TypeError("next_batch_aug needs device_aug=True, an augmentation mode and augmentations the device "
+                            "implements (augmentation.aug_ops_from)")
+        if self.images_u8.dtype != np.uint8:
+            raise TypeError(f"next_batch_aug needs a uint8 image array, the dataset holds {self.images_u8.dtype}")
+        B, N, A = self.batch_size, self.total_full_images, self.total_augs
+        if self.aug_mode == "all":
+            t = self.full_counter * A + self.aug_counter + np.arange(B)
+            idx, j = self.sample_shuffle[(t // A) % N], t % A
+            self.full_counter, self.aug_counter = int((t[-1] + 1) // A % N), int((t[-1] + 1) % A)
+        else:  # "one": Generator.choice(size=B) consumes the stream like B single draws
+            idx = self.sample_shuffle[(self.full_counter + np.arange(B)) % N]
+            j = self._rng.choice(A, size=B, p=self.aug_probs)
+            self.full_counter = (self.full_counter + B) % N
+        self.batch_counter += 1
+        if self.batch_counter == self.num_batches:
+            self.batch_counter = 0
+        ops = self.aug_ops[j]
+        if self.aug_fly:
+            ops["noise_id"] = self.samples_drawn + np.arange(B, dtype=np.uint64)
+        else:
+            ops["noise_id"] = idx.astype(np.uint64) * np.uint64(A) + j.astype(np.uint64)
+        self.samples_drawn += B
+        if shard is not None:
+            idx, ops = idx[shard[0]:shard[1]], ops[shard[0]:shard[1]]
+        return self.images_u8[idx], self.sparse_labels()[idx], ops
+
     def handle_epoch_end(self):
         self.batch_counter = 0
         self.full_counter = 0
@@ -152,14 +206,26 @@ class DataGenerator:
 
     def __init__(self, images: np.ndarray, labels: np.ndarray, batch_size: int, aug_fn_args: List[Tuple],
                  aug_mode: str, aug_probs: Tuple, aug_fly: bool, preprocess_input_fn: Callable,
-                 seed: Optional[int] = None):
+                 seed: Optional[int] = None, device_aug: bool = False):
         # uint8 fast path (the /255 happens on the GPU) only without augmentation AND only for uint8 storage: the
         # reference divides by 255 whatever the dataset's dtype (data_generator.py:76), so any other dtype goes through
         # get_batch_list(), which computes float32(images) / 255 on the host
         self.oct_fast_path = aug_mode == "none" and np.asarray(images).dtype == np.uint8
+        is_u8 = np.asarray(images).dtype == np.uint8
         self.batch_gen = BatchGenerator(images=images, labels=labels, batch_size=batch_size, aug_fn_args=aug_fn_args,
                                         aug_mode=aug_mode, aug_probs=aug_probs, aug_fly=aug_fly,
-                                        preprocess_input_fn=preprocess_input_fn, seed=seed)
+                                        preprocess_input_fn=preprocess_input_fn, seed=seed, device_aug=device_aug and is_u8)
+        # augmentation on the device (Model.fit: uint8 upload + oct_augment_batch) where it was asked for and is possible
+        self.oct_device_aug = self.batch_gen.aug_ops is not None
+        if device_aug and aug_mode != "none" and not self.oct_device_aug:
+            why = ("an augmentation is not one of augmentation_map's functions with arguments the device implements" if is_u8
+                   else f"the dataset holds {np.asarray(images).dtype}, not uint8")
+            log.warning(f"device_aug: augmenting on the host ({why})")
+        # Philox key of the device noise: the generator's seed (shared by all DP ranks), or OS entropy drawn once
+        self.oct_aug_seed = (int(seed) if seed is not None else int.from_bytes(os.urandom(8), "little")) & 0xFFFFFFFFFFFFFFFF
+
+    def next_batch_aug(self, shard: Optional[Tuple[int, int]] = None):
+        return self.batch_gen.next_batch_aug(shard)
 
     def __len__(self):
         return self.batch_gen.num_batches

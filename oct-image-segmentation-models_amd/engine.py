@@ -305,6 +305,44 @@ class UNetEngine:
                                                     out.data_ptr(), self._stream()), "oct_boundary_maps")
         return out
 
+    def augment(self, x_u8: torch.Tensor, labels: Optional[torch.Tensor], ops, seed: int, out=None):
+        """The training augmentations on the device (``oct_augment_batch``): (B,H,W,C) uint8 images, (B,H,W[,1]) uint8
+        labels or ``None`` and one ``common.augmentation.AUG_OP_DTYPE`` descriptor per sample -> ``(x float32 in [0,1],
+        labels uint8)`` (flipped alongside; ``None`` without labels).  ``ops``: a numpy descriptor array (validated, then
+        uploaded) or a uint8 device tensor of B*32 bytes that already holds validated descriptors.  ``out``: optional
+        ``(x_out, labels_out)`` tensors to write into.  Asynchronous on the current stream."""
+        from .common.augmentation import AUG_OP_DTYPE, AUG_SP
+        if x_u8.device != self.device or x_u8.dtype != torch.uint8 or not x_u8.is_contiguous() or x_u8.dim() != 4:
+            raise OctError("augment: images must be a contiguous uint8 (B,H,W,C) tensor on the engine's device")
+        B, H, W, Cn = x_u8.shape
+        if labels is not None and (labels.device != self.device or labels.dtype != torch.uint8 or not labels.is_contiguous()
+                                   or labels.numel() != B * H * W):
+            raise OctError("augment: labels must be a contiguous uint8 (B,H,W[,1]) tensor on the engine's device")
+        if isinstance(ops, np.ndarray):
+            if ops.dtype != AUG_OP_DTYPE or ops.shape != (B,):
+                raise OctError("augment: ops must hold one AUG_OP_DTYPE descriptor per sample")
+            if ops["kind"].min() < 0 or ops["kind"].max() > AUG_SP:
+                raise OctError("augment: descriptor kind outside 0..5")
+            ops = torch.from_numpy(np.ascontiguousarray(ops).view(np.uint8).copy()).to(self.device)
+        if ops.device != self.device or ops.dtype != torch.uint8 or not ops.is_contiguous() or ops.numel() != B * AUG_OP_DTYPE.itemsize:
+            raise OctError("augment: ops must be B*32 descriptor bytes on the engine's device")
+        x_out, lab_out = out if out is not None else (None, None)
+        if x_out is None:
+            x_out = torch.empty(x_u8.shape, dtype=torch.float32, device=self.device)
+        if labels is not None and lab_out is None:
+            lab_out = torch.empty(labels.shape, dtype=torch.uint8, device=self.device)
+        if x_out.device != self.device or x_out.dtype != torch.float32 or not x_out.is_contiguous() or x_out.shape != x_u8.shape:
+            raise OctError("augment: out[0] must be a contiguous float32 tensor of the images' shape on the engine's device")
+        if labels is not None and (lab_out.device != self.device or lab_out.dtype != torch.uint8 or not lab_out.is_contiguous()
+                                   or lab_out.numel() != labels.numel()):
+            raise OctError("augment: out[1] must be a contiguous uint8 tensor of the labels' size on the engine's device")
+        with torch.cuda.device(self.device):
+            _hip.check(_hip.lib().oct_augment_batch(
+                x_u8.data_ptr(), labels.data_ptr() if labels is not None else None, ops.data_ptr(), B, H, W, Cn,
+                int(seed) & 0xFFFFFFFFFFFFFFFF, x_out.data_ptr(), lab_out.data_ptr() if labels is not None else None,
+                self._stream()), "oct_augment_batch")
+        return x_out, (lab_out if labels is not None else None)
+
     # ---- weights exchange --------------------------------------------------------------------------
     def get_weights(self) -> List[np.ndarray]:
         """Keras ``get_weights()`` order: Conv2D [kernel HWIO, bias]; BN [gamma, beta, moving_mean, moving_var]."""

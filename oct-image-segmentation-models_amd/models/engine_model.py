@@ -239,7 +239,10 @@ class Model:
 
     # ---- training -------------------------------------------------------------------------------------
     def _host_batch(self, seq, index, rank, world):
-        """One GLOBAL batch from the Sequence -> this rank's (x, sparse uint8 labels) host arrays."""
+        """One GLOBAL batch from the Sequence -> this rank's (x, sparse uint8 labels) host arrays; for a Sequence that
+        augments on the device (``oct_device_aug``) the raw uint8 images and a third array, the per-sample descriptors."""
+        if getattr(seq, "oct_device_aug", False):
+            return seq.next_batch_aug(parallel.shard_batch(seq.batch_size, rank, world) if world > 1 else None)
         if getattr(seq, "oct_fast_path", False):
             if world > 1:      # gather this rank's slice only (8 ranks: 1/8 of the host work per step and rank)
                 return seq.next_batch_u8(parallel.shard_batch(seq.batch_size, rank, world))
@@ -252,18 +255,20 @@ class Model:
         lo, hi = parallel.shard_batch(X.shape[0], rank, world)
         return X[lo:hi], lab[lo:hi]
 
-    def _upload(self, X: np.ndarray, lab: np.ndarray, slot: int):
+    def _upload(self, X: np.ndarray, lab: np.ndarray, slot: int, ops: Optional[np.ndarray] = None):
         """Queue the upload of one batch into device slot ``slot`` on the COPY stream (never on the compute stream: 8 MB of
         uint8 per 32-scan batch would otherwise sit in front of every step).  Pinned staging buffers and device buffers come
         in THREE slots: slot s is refilled only after the step that last read its device tensors has finished -- a HOST
         wait on that step's event, two steps back, which also keeps this thread at most two steps ahead of the GPU.  (With two
         slots the copy had to wait for the previous step on the copy stream; the H2D call then held the host until that
         step was over and every step started with the launch latency exposed: 0.91 of the resident-input rate.)
-        Returns (x, labels, ready event)."""
+        ``ops`` (device augmentation: one 32-byte descriptor per sample) travels through the same slot as raw bytes.
+        Returns (x, labels, ready event, descriptor bytes or None)."""
         dev = self._engine.device if self._engine is not None else self._dev()
         st = self.__dict__.setdefault("_up", {"copy": None, "ev": {}, "done": {}, "dev": {}})
         if dev.type != "cuda":
-            return torch.from_numpy(np.ascontiguousarray(X)), torch.from_numpy(np.ascontiguousarray(lab)), None
+            return (torch.from_numpy(np.ascontiguousarray(X)), torch.from_numpy(np.ascontiguousarray(lab)), None,
+                    None if ops is None else torch.from_numpy(np.ascontiguousarray(ops).view(np.uint8).copy()))
         if st["copy"] is None:
             st["copy"] = torch.cuda.Stream(device=dev)
         if slot in st["done"]:
@@ -271,14 +276,31 @@ class Model:
         if slot in st["ev"]:
             st["ev"][slot].synchronize()          # host: the H2D copies that last read this slot's pinned buffers have executed
         xp, lp = self._staged(("x", slot), X), self._staged(("l", slot), lab)
+        op = None if ops is None else self._staged(("o", slot), np.ascontiguousarray(ops).view(np.uint8))
         bufs = st["dev"].get(slot)
         if bufs is None or bufs[0].shape != xp.shape or bufs[0].dtype != xp.dtype or bufs[1].shape != lp.shape:
             bufs = st["dev"][slot] = (torch.empty(xp.shape, dtype=xp.dtype, device=dev), torch.empty(lp.shape, dtype=lp.dtype, device=dev))
+        obuf = None
+        if op is not None:
+            obuf = st.setdefault("ops", {}).get(slot)
+            if obuf is None or obuf.shape != op.shape:
+                obuf = st["ops"][slot] = torch.empty(op.shape, dtype=torch.uint8, device=dev)
         with torch.cuda.stream(st["copy"]):
             bufs[0].copy_(xp, non_blocking=True); bufs[1].copy_(lp, non_blocking=True)
+            if op is not None:
+                obuf.copy_(op, non_blocking=True)
             ev = torch.cuda.Event(); ev.record(st["copy"])
         st["ev"][slot] = ev
-        return bufs[0], bufs[1], ev
+        return bufs[0], bufs[1], ev, obuf
+
+    def _augment(self, eng, seq, x, lab, ops):
+        """Device augmentation of one uploaded batch on the compute stream (behind the slot's ready event) into ONE
+        model-owned pair of buffers: the next step's augment is queued on the same stream behind this step's backward, the
+        last reader of the pair, so one pair is enough."""
+        buf = self.__dict__.get("_aug_out")
+        if buf is None or buf[0].shape != x.shape or buf[1].shape != lab.shape or buf[0].device != x.device:
+            buf = self._aug_out = (torch.empty(x.shape, dtype=torch.float32, device=x.device), torch.empty_like(lab))
+        return eng.augment(x, lab, ops, seq.oct_aug_seed, out=buf)
 
     def _release(self, slot: int):
         """The compute stream is done reading device slot ``slot`` (recorded behind the step that used it)."""
@@ -306,14 +328,19 @@ class Model:
         n = len(seq)
         # the upload of batch i+1 (host gather -> pinned buffers -> H2D on the copy stream) is queued before step i is
         # launched, so it runs under that step
-        nxt = self._upload(*self._host_batch(seq, 0, rank, world), 0) if n else None
+        def queue(index):       # (x, labels[, descriptors]) of batch `index` into slot index % 3
+            hb = self._host_batch(seq, index, rank, world)
+            return self._upload(hb[0], hb[1], index % 3, *hb[2:])
+        nxt = queue(0) if n else None
         for i in range(n):
-            x, lab, ready = nxt
+            x, lab, ready, ops = nxt
             if ready is not None:
                 torch.cuda.current_stream(x.device).wait_event(ready)
             if i + 1 < n:
-                nxt = self._upload(*self._host_batch(seq, i + 1, rank, world), (i + 1) % 3)
+                nxt = queue(i + 1)
             eng = self._ensure_engine(x.shape[0], training)
+            if ops is not None:
+                x, lab = self._augment(eng, seq, x, lab, ops)
             if focal:      # (re)selected per batch: _ensure_engine may have built a new engine
                 eng.set_focal_dice(focal["focal_loss_weight"], focal["gamma"], focal["class_weight"])
             elif getattr(eng, "_focal_active", False):

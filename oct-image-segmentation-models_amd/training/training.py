@@ -42,6 +42,7 @@ def save_training_params_file(save_foldername: Path, model_summary: str, model_c
         "batch_size": train_params.batch_size,
         "shuffle": train_params.shuffle,
         "aug_mode": np.array(train_params.aug_mode, dtype="S100"),
+        "aug_device": bool(train_params.aug_device),
         "optimizer": np.array(train_params.opt_con.__name__, dtype="S100"),
     }
     for key, val in opt.get_config().items():
@@ -160,13 +161,14 @@ def train_model(training_params: TrainingParams, mlflow_params=None):
     seed = parallel.shared_seed(training_params.seed) if parallel.world_size() > 1 else training_params.seed
     train_gen = data_gen.DataGenerator(train_images, train_labels, batch_size, training_params.aug_fn_args, training_params.aug_mode,
                                        training_params.aug_probs, training_params.aug_fly,
-                                       model_container.get_preprocess_input_fn(), seed=seed)
+                                       model_container.get_preprocess_input_fn(), seed=seed,
+                                       device_aug=training_params.aug_device)
     val_gen = data_gen.DataGenerator(val_images, val_labels, batch_size,
                                      training_params.aug_fn_args if aug_val_mode != "none" else [], aug_val_mode,
                                      training_params.aug_probs if aug_val_mode != "none" else (),
                                      training_params.aug_fly if aug_val_mode != "none" else False,
                                      model_container.get_preprocess_input_fn(),
-                                     seed=None if seed is None else seed + 1)
+                                     seed=None if seed is None else seed + 1, device_aug=training_params.aug_device)
 
     for name, gen in (("training", train_gen), ("validation", val_gen)):
         if batch_size > gen.get_total_samples():

@@ -19,7 +19,7 @@ class TrainingParams:
                  model_save_best: bool = True, model_save_monitor=("val_acc", "max"),
                  class_weight: Union[list, str, None] = None, channels_last: bool = True,
                  early_stopping: bool = True, restore_best_weights: bool = True, patience: int = 50,
-                 seed: Union[int, None] = None):
+                 seed: Union[int, None] = None, aug_device: bool = False):
         if (model_architecture is None and initial_model is None) or (
                 model_architecture is not None and initial_model is not None):
             log.error("Either 'model_architecture' or 'initial_model' need to be provided in the `config.json`.")
@@ -51,6 +51,9 @@ class TrainingParams:
         self.aug_probs = aug_probs
         self.aug_fly = aug_fly
         self.aug_val = aug_val
+        # extension: apply the augmentations on the GPU (oct_augment_batch; the noise then comes from its Philox stream,
+        # not from numpy's).  Off by default.
+        self.aug_device = bool(aug_device)
         self.shuffle = shuffle
         self.model_save_best = model_save_best
         self.model_save_monitor = model_save_monitor
