@@ -1,7 +1,8 @@
 // Host-side plumbing shared by the translation units of liboct_unet_hip.so: error channel, tuning options, the per-launch
 // HIP-event profiler and the signatures of the conv launchers.  The library is built from several .hip files compiled in
-// parallel (build.sh): oct_unet.hip holds the plan, the C ABI and the streaming kernels; tu_*.hip each instantiate one
-// family of the MFMA conv kernels behind the launcher declared here.
+// parallel (build.sh): oct_unet.hip holds the plan (build_plan / carve at creation, plan_backward per backward call), the
+// C ABI and the streaming kernels; tu_*.hip each instantiate one family of the MFMA conv kernels behind the launcher
+// declared here.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -100,8 +101,10 @@ inline bool bt_k_ok(int k) { return k == 8 || k == 16 || k == 32; }
 // what a conv launch needs besides its argument block
 struct LaunchCtx { const Options* o; int B; hipStream_t s; const char* layer; double flops, bytes; };
 
-// kernel family a conv launch is routed to (launch_conv.hpp::route): the host plan asks before it launches, because only
-// the bf16-pipe kernels can apply the BN-backward transform on load and finalize statistics in the launch
+// kernel family a conv launch is routed to (oct_unet.hip::conv_route, launch_igemm's dispatch).  The host asks the same
+// function about the argument block it is going to launch -- conv_forward for one launch, plan_backward once per
+// backward-data launch of a block, kept in its BwdRoute -- because only the bf16-pipe kernels can apply the BN-backward
+// transform on load and finalize statistics in the launch
 enum ConvRoute { ROUTE_BT = 0, ROUTE_BX = 1, ROUTE_F32 = 2 };
 ConvRoute conv_route(const oct::IgemmArgs& a, int amode, const Options& o);
 
@@ -110,8 +113,16 @@ ConvRoute conv_route(const oct::IgemmArgs& a, int amode, const Options& o);
 template <int KH, int AMODE, int EPI>
 int launch_igemm(const oct::IgemmArgs& a, const LaunchCtx& c, int* rows);
 
-// MFMA backward-weights launchers (launch_dw.hpp; tu_dw_*.hip).  `kind` as in DwPlan.
-struct DwPlan { int kind;  /* 0 = VALU (1-channel input / head), 16, 32 = fp32 pipe, 33 = conv_dwbx_k, 34 = conv_dwbt_k */ int cic, coc, th, chunks, npb, tiles; };
+// Backward-weights plan of a layer (oct_unet.hip::dw_plan): the kernel family, its channel chunking, pixel-tile height,
+// pixel-block count.  MFMA launchers: launch_dw.hpp, instantiated in tu_dw_*.hip.
+enum DwKind {
+    DW_VALU,      // VALU kernels of oct_unet.hip (image input / head)
+    DW_F32_16,    // fp32 pipe, thin (conv_dw16_k, conv_dwpair8_k)
+    DW_F32_32,    // fp32 pipe, wide (conv_dw32_k)
+    DW_BX,        // bf16 pipe, wide (conv_dwbx_k)
+    DW_BT,        // bf16 pipe, thin (conv_dwbt_k)
+};
+struct DwPlan { DwKind kind; int cic, coc, th, chunks, npb, tiles; };
 int launch_dw_bf16pipe(const oct::ConvBwdWArgs& a, const DwPlan& p, int kh, bool up, const LaunchCtx& c);
 int launch_dw_f32pipe(const oct::ConvBwdWArgs& a, const DwPlan& p, int kh, bool up, const LaunchCtx& c);
 

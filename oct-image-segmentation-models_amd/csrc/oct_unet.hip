@@ -66,7 +66,6 @@ struct Layer {
     bf16_t* wbx_f = nullptr; bf16_t* wbx_b = nullptr;   // split weights for the bf16-pipe kernels (forward / backward-data)
     bool bt_m2_f = false, bt_m2_b = false;                // thin kernel: this layer's forward / backward-data launches use the two-pixel form
     bf16_t* wbt_f = nullptr; bf16_t* wbt_b = nullptr;   // ... for the thin bf16-pipe kernel (16-row slices; backward: cin / Cg slices)
-    bool g_masked = false;   // last backward: the BN-backward transform was applied on load, `g` still holds the masked gradient g'
 };
 
 struct Plan {
@@ -180,7 +179,7 @@ DwPlan dw_plan(const Layer& l, int B, int mfma_mode, int bf16, const Options& o)
     DwPlan p{};
     if (mfma_mode && o.dwbx_enable && l.src != SRC_INPUT && l.kh != 1 && l.cin % 32 == 0 && l.cout % 32 == 0) {
         // wide layers on the bf16 pipe: one block per (32 ci, 32 co) pair and pixel slice, ~1 block per CU in total
-        p.kind = 33; p.cic = 32; p.coc = 32; p.th = 4;
+        p.kind = DW_BX; p.cic = 32; p.coc = 32; p.th = 4;
         p.chunks = (l.cin / 32) * (l.cout / 32);
         p.tiles = cdiv(l.H, p.th) * cdiv(l.W, kTileX);
         p.npb = std::max(1, std::min(B * p.tiles, cdiv(o.dwbx_blocks, p.chunks)));
@@ -191,7 +190,7 @@ DwPlan dw_plan(const Layer& l, int B, int mfma_mode, int bf16, const Options& o)
     // 143, 32->16 103 / 92, 8->16 39 / 35, 16->16 59 / 48, 16->32 come here.  bf16 mode (one rounding, one product): all.
     if (mfma_mode && dwbt_ok(l) && (bf16 || o.dwbt_f32_all || (l.src != SRC_UP && !(l.cin == 8 && l.cout == 8)))) {
         // thin layers on the bf16 pipe (conv_dwbt_k): one block holds all channels; 1 or 2 blocks per CU (LDS images)
-        p.kind = 34; p.cic = l.cin; p.coc = l.cout; p.th = 4; p.chunks = 1;
+        p.kind = DW_BT; p.cic = l.cin; p.coc = l.cout; p.th = 4; p.chunks = 1;
         p.tiles = cdiv(l.H, p.th) * cdiv(l.W, kTileX);
         p.npb = std::max(1, std::min(B * p.tiles, 256 * (l.cin + l.cout >= 48 ? 1 : 2)));
         return p;
@@ -199,22 +198,43 @@ DwPlan dw_plan(const Layer& l, int B, int mfma_mode, int bf16, const Options& o)
     if (l.src == SRC_INPUT || l.cin % 4 || l.cout % 4 || l.kh == 1) {
         // first layer (ANY in_ch: its source is the caller's image, uint8 or f32 -- only the VALU kernel's fetch_x reads
         // that; the MFMA stagers assume an activation-typed tensor) and the 1x1 n_cls-wide head
-        p.kind = 0; p.cic = (l.src == SRC_INPUT || l.cin % 4) ? 1 : chunk_of(l.cin); p.coc = l.cout % 4 ? (l.cout <= 4 ? 4 : 8) : chunk_of(l.cout); p.th = kTileY;
+        p.kind = DW_VALU; p.cic = (l.src == SRC_INPUT || l.cin % 4) ? 1 : chunk_of(l.cin); p.coc = l.cout % 4 ? (l.cout <= 4 ? 4 : 8) : chunk_of(l.cout); p.th = kTileY;
     } else if (l.cin >= 32 && l.cout >= 32) {
-        p.kind = 32; p.cic = l.cin % 64 == 0 ? 64 : 32; p.coc = 32; p.th = p.cic == 64 ? 2 : 4;
+        p.kind = DW_F32_32; p.cic = l.cin % 64 == 0 ? 64 : 32; p.coc = 32; p.th = p.cic == 64 ? 2 : 4;
     } else {
-        p.kind = 16; p.cic = l.cin >= 16 ? 16 : 8; p.coc = 16; p.th = 8;
+        p.kind = DW_F32_16; p.cic = l.cin >= 16 ? 16 : 8; p.coc = 16; p.th = 8;
     }
     p.chunks = cdiv(l.cin, p.cic) * cdiv(l.cout, p.coc);
     p.tiles = cdiv(l.H, p.th) * cdiv(l.W, kTileX);
     const int total = B * p.tiles;
     // one full round of resident blocks (no half-empty tail round): the wide kernel fits 2 blocks per CU (registers),
     // for the thin one 768 blocks measured best
-    int target = p.kind == 32 ? o.dw32_blocks : o.dw16_blocks;
-    if (p.kind == 16 && l.src == SRC_UP && p.cic == 16 && l.cout == 8) target = target * 4 / 3;   // (dz staged 8 wide: 4 blocks per CU)
+    int target = p.kind == DW_F32_32 ? o.dw32_blocks : o.dw16_blocks;
+    if (p.kind == DW_F32_16 && l.src == SRC_UP && p.cic == 16 && l.cout == 8) target = target * 4 / 3;   // (dz staged 8 wide: 4 blocks per CU)
     p.npb = std::max(1, std::min(total, cdiv(target, p.chunks)));
     return p;
 }
+
+// ---- what one block's backward launches (plan_backward decides, backward_impl walks) ----
+// One backward-data launch: dz of the block x its transposed / effective weights.  `a` is the argument block the route
+// was asked about and the one that is launched: a.out / a.Mout / a.m_off are the output buffer, its channel count Cg and
+// the offset ci_off of those channels in the conv's input.
+struct DxLaunch {
+    IgemmArgs a;
+    const Layer* prod;     // the block whose mask the launch applies and whose statistics it emits (nullptr: raw gradient)
+    bool up;               // up-conv: stride-2 gather of dz
+    const Layer* dw_x;     // with fdw: the block whose output is this launch's slice of the conv input ...
+    bool dw_bias;          // ... and whether this launch also sums the bias gradient (one launch per block does)
+    ConvRoute route;
+};
+struct BwdRoute {
+    DwPlan dw;             // backward-weights plan, npb clipped to the slabs the layer owns
+    bool fuse = false;     // dz = BN-backward transform of the masked gradient g', applied on load by every consumer of dz
+                           // (the g buffer keeps g'); false: the stand-alone pass turns g into dz in place
+    bool fdw = false;      // the backward-data launches reduce the backward-weights too (conv_bt_k FDW): no dW launch
+    int n_dx = 0;
+    DxLaunch dx[2];        // a concat: the skip half, then the up-path half
+};
 
 }  // namespace
 
@@ -224,6 +244,7 @@ struct oct_unet {
     Plan plan;
     float* params; float* grads; float* state;
     std::vector<void*> pooled, gpooled;    // per encoder level (activation storage type)
+    std::vector<BwdRoute> route;           // per layer: refilled at the top of every backward (options and B may change between calls)
     float* stat_part = nullptr;            // BN statistic partials (fwd and bwd share it: stream-ordered)
     unsigned* fin_counters = nullptr;      // [2 * layers] arrival counters of the in-launch finalizes (kernels_fin.hpp): zero between launches
     ReduceAllArgs red{};                   // filled while backward runs; one reduce launch at the end
@@ -250,7 +271,7 @@ size_t carve(const oct_unet_cfg& c, Plan& pl, oct_unet* h, char* base, const Opt
     size_t off = 0;
     auto take = [&](size_t bytes) -> char* { char* p = base ? base + off : nullptr; off += align256(bytes); return p; };
     const size_t B = (size_t)c.max_batch, esz = c.dtype ? 2 : 4;   // bytes per stored activation element
-    size_t stat_max = 0, dw_max = 0;
+    size_t stat_max = 0;
     for (auto& l : pl.L) {
         const size_t n = B * l.H * l.W * l.cout;
         void* z = l.has_bn ? (void*)take(n * esz) : nullptr;   // the head writes straight to the caller's buffers
@@ -273,7 +294,6 @@ size_t carve(const oct_unet_cfg& c, Plan& pl, oct_unet* h, char* base, const Opt
                                                   : (size_t)std::max(dw_plan(l, c.max_batch, 0, 0, o).npb, std::max(dw_plan(l, c.max_batch, 1, 1, o).npb, dw_plan(l, c.max_batch, 1, 0, o).npb));
             float* dwp = (float*)take(rows * wsz * 4);
             if (base) { l.dwp = dwp; l.dw_rows = (int)rows; }
-            dw_max = 0;
         }
     }
     for (int i = 0; i < pl.P; ++i) {
@@ -485,6 +505,27 @@ int head_nblk(int HW, int B) { return std::max(1, std::min(cdiv(HW, kBlock), cdi
 
 int dice_n(int C) { return 5 * C <= 16 ? 16 : (5 * C <= 32 ? 32 : 64); }
 
+// this step's weights in the operand layouts of the bf16-pipe conv kernels (split in fp32 mode, rounded in bf16 mode):
+// one launch per kernel family, over the forward descriptors or the backward-data ones (which read the prep_wt_k output)
+int prep_split_weights(oct_unet* h, bool bwd, hipStream_t s) {
+    if (!h->opt.mfma_mode) return 0;
+    const int item_bytes = 8 * (4 + 2 * (h->cfg.dtype ? 1 : 3));
+    auto grid = [](unsigned total) { return std::min<unsigned>((total + kBlock - 1) / kBlock, 2048u); };
+    if (const int n = bwd ? h->n_wbx_b : h->n_wbx_f) {
+        const unsigned total = bwd ? h->wbx_b_total : h->wbx_f_total;
+        ProfScope ps(s, "prep_wbx_k", "all", 0, (double)total * item_bytes);
+        prep_wbx_k<<<grid(total), kBlock, 0, s>>>(h->wbx_descs + (bwd ? h->n_wbx_f : 0), n, total);
+        HIP_OK(hipGetLastError());
+    }
+    if (const int n = bwd ? h->n_wbt_b : h->n_wbt_f) {
+        const unsigned total = bwd ? h->wbt_b_total : h->wbt_f_total;
+        ProfScope ps(s, "prep_wbt_k", "all", 0, (double)total * item_bytes);
+        prep_wbt_k<<<grid(total), kBlock, 0, s>>>(h->wbt_descs + (bwd ? h->n_wbt_f : 0), n, total);
+        HIP_OK(hipGetLastError());
+    }
+    return 0;
+}
+
 int forward_impl(oct_unet* h, const void* x, int x_is_u8, int B, int training, const oct_unet_io* io, hipStream_t s) {
     Plan& pl = h->plan;
     const int nl = (int)pl.L.size();
@@ -493,16 +534,7 @@ int forward_impl(oct_unet* h, const void* x, int x_is_u8, int B, int training, c
     const bool fside = training && h->opt.dw_side_stream && h->side && !(t_prof && t_prof->on);
     hipStream_t ps_ = fside ? h->side : s;
     if (fside) { HIP_OK(hipEventRecord(h->fork_ev[0], s)); HIP_OK(hipStreamWaitEvent(h->side, h->fork_ev[0], 0)); }
-    if (h->opt.mfma_mode && h->n_wbx_f) {
-        ProfScope ps(ps_, "prep_wbx_k", "all", 0, (double)h->wbx_f_total * 8 * (4 + 2 * (h->cfg.dtype ? 1 : 3)));
-        prep_wbx_k<<<std::min<unsigned>((h->wbx_f_total + kBlock - 1) / kBlock, 2048u), kBlock, 0, ps_>>>(h->wbx_descs, h->n_wbx_f, h->wbx_f_total);
-        HIP_OK(hipGetLastError());
-    }
-    if (h->opt.mfma_mode && h->n_wbt_f) {
-        ProfScope ps(ps_, "prep_wbt_k", "all", 0, (double)h->wbt_f_total * 8 * (4 + 2 * (h->cfg.dtype ? 1 : 3)));
-        prep_wbt_k<<<std::min<unsigned>((h->wbt_f_total + kBlock - 1) / kBlock, 2048u), kBlock, 0, ps_>>>(h->wbt_descs, h->n_wbt_f, h->wbt_f_total);
-        HIP_OK(hipGetLastError());
-    }
+    if (int rc = prep_split_weights(h, false, ps_)) return rc;
     if (fside) HIP_OK(hipEventRecord(h->prep_ev, h->side));
     if (!training) {  // (a, b) of every block from the moving statistics: one launch
         ProfScope ps(s, "bn_infer_all_k", "all", 0, (double)pl.n_state * 4 * 3);
@@ -588,47 +620,111 @@ int flush_reduce(oct_unet* h, hipStream_t s) {
 }
 
 // the real first layer (1 -> 8 channels, 3x3, image input): streaming backward-weights kernel; it can apply the layer's
-// BN-backward transform itself (nothing else reads that dz)
-inline bool first_dw_streams(const Layer& l) {
-    return l.src == SRC_INPUT && l.cin == 1 && l.cout == 8 && l.kh == 3 && l.has_bn && !l.drop_in;
+// BN-backward transform itself (nothing else reads that dz).  The one predicate of the plan and of the launch: the image
+// layer is always DW_VALU, carries BN, is never behind the dropout, and its source flags are F_U8 or none.
+inline bool first_dw_streams(const Layer& l) { return l.src == SRC_INPUT && l.cin == 1 && l.cout == 8 && l.kh == 3; }
+
+// Decide what every block's backward launches for this call's B and the handle's current options: h->route.  Host
+// arithmetic only -- nothing is launched here, and everything below that launches reads the record instead of deciding again.
+int plan_backward(oct_unet* h, int B) {
+    const Plan& pl = h->plan;
+    const Options& o = h->opt;
+    for (int li = 0; li + 1 < (int)pl.L.size(); ++li) {
+        const Layer& l = pl.L[li];
+        BwdRoute& r = h->route[li];
+        r = BwdRoute{};
+        r.dw = dw_plan(l, B, o.mfma_mode, h->cfg.dtype, o);
+        r.dw.npb = std::min(r.dw.npb, l.dw_rows);
+        // The block's BN-backward transform dz = ga g' + gb z + gd is applied by the consumers of dz while they stage it --
+        // the backward-weights kernel and the backward-data launches -- whenever all of them can (the bf16-pipe conv kernels
+        // and every MFMA backward-weights kernel); otherwise by the stand-alone pass, in place.
+        if (l.src == SRC_INPUT) {      // its dz has ONE consumer, the streaming backward-weights kernel
+            r.fuse = o.fuse_first_apply && first_dw_streams(l);
+            continue;
+        }
+        // a backward-data launch: dz x transposed / effective weights through the MFMA implicit-GEMM kernels, into the Cg
+        // channels at ci_off of the conv's input
+        auto add = [&](void* gout, int Cg, int ci_off, const Layer* prod, bool up, const Layer* dw_x, bool dw_bias) {
+            DxLaunch& d = r.dx[r.n_dx++];
+            d.prod = prod; d.up = up; d.dw_x = dw_x; d.dw_bias = dw_bias;
+            IgemmArgs& g = d.a;
+            g.x0 = l.g; g.C0 = l.cout; g.flags = 0; g.Cin = l.cout;
+            g.w = l.wt; g.w_ld = l.cin; g.m_off = ci_off; g.out = gout; g.Mout = Cg;
+            g.Hi = l.H; g.Wi = l.W; g.Ho = up ? l.H / 2 : l.H; g.Wo = up ? l.W / 2 : l.W;
+            g.part = prod ? h->stat_part : nullptr; g.zin = prod ? prod->z : nullptr; g.bnin = prod ? prod->bn : nullptr;
+            g.drop_out = (up && l.drop_in) ? 1 : 0; g.drop = make_drop(h); g.act_bf16 = h->cfg.dtype;
+            g.wbx = l.wbx_b; g.wbx_M = l.cin;
+            g.wbt = l.wbt_b ? l.wbt_b + (size_t)(ci_off / Cg) * (wbt_bytes(3, l.cout, h->cfg.dtype ? 1 : 3, l.bt_m2_b) / 2) : nullptr;
+            g.bt_m2 = l.bt_m2_b;
+            d.route = conv_route(d.a, up ? A_DOWN2 : A_NORMAL, o);
+        };
+        const Layer& p = pl.L[li - 1];
+        switch (l.src) {
+            case SRC_PREV: add(p.g, p.cout, 0, &p, false, &p, true); break;
+            case SRC_POOL: add(h->gpooled[l.level - 1], l.cin, 0, nullptr, false, nullptr, false); break;   // raw: the pool backward routes it into block li-1
+            case SRC_UP: add(p.g, p.cout, 0, &p, true, nullptr, false); break;
+            case SRC_CONCAT: {
+                const Layer& k = pl.L[l.skip_from];
+                add(k.g, k.cout, p.cout, nullptr, false, &k, false);   // skip half first (raw, merged later by the pool backward of that encoder level) ...
+                add(p.g, p.cout, 0, &p, false, &p, true);              // ... then the up-path half, whose statistics must be the ones pending for block li-1
+                break;
+            }
+            default: return fail(-3, "backward: bad src");
+        }
+        bool all_bf16 = true, all_bt = true;
+        for (int i = 0; i < r.n_dx; ++i) { all_bf16 = all_bf16 && r.dx[i].route != ROUTE_F32; all_bt = all_bt && r.dx[i].route == ROUTE_BT; }
+        const ConvRoute r0 = r.dx[r.n_dx - 1].route;      // the launch at channel offset 0 (a concat's halves have the same K and Cg)
+        const bool up = l.src == SRC_UP;
+        const int cg = bx_bwd_cg(l);
+        // (three bf16-pipe instantiations stay out: the stride-2 gather beyond the coefficient rows its LDS holds; the
+        //  thin kernel at 32 K channels, whose staging registers for g' AND z no longer fit; and the thin kernel at 16 K
+        //  channels with 16 output channels, where the second raw register set spills under the 256-register budget of two
+        //  blocks per CU: 87 us against 45 + 33 for the separate pass at B = 32, 128 x 256)
+        r.fuse = o.fuse_bn_apply && r.dw.kind != DW_VALU && all_bf16 && !(up && r0 == ROUTE_BX && l.cout > kBxGbDown2MaxC) &&
+                 !(r0 == ROUTE_BT && l.cout == 32) && !(r0 == ROUTE_BT && l.cout == 16 && cg == 16 && !o.fuse_bn_apply16);
+        // 3x3 layers with 8 output channels on the thin kernel (the full-resolution convs): their backward-data launches
+        // reduce the backward-weights too (conv_bt_k FDW) -- g', z and the producer's z are read once for both
+        r.fdw = r.fuse && o.fuse_dw_thin && l.kh == 3 && l.cout == 8 && !l.drop_in && (l.src == SRC_PREV || l.src == SRC_CONCAT) &&
+                cg == 8 && l.dw_rows >= std::min(B * cdiv(l.W, 32) * cdiv(l.H, 8), 512) &&      // (one slab per block of that launch)
+                all_bt;
+    }
+    return 0;
 }
 
-// backward-weights of block li.  fused_apply: `dz` is the masked gradient g' and the kernel applies the BN-backward
-// transform of the block on load (every kernel but the generic VALU one of odd first layers can)
-int conv_backward_w(oct_unet* h, int li, const void* x_in, int x_is_u8, const void* dz, int B, hipStream_t s, bool fused_apply) {
+// backward-weights of block li, as routed by r.  With r.fuse its g buffer is the masked gradient g' and the kernel applies
+// the BN-backward transform of the block on load (every kernel but the generic VALU one of odd first layers can)
+int conv_backward_w(oct_unet* h, int li, const BwdRoute& r, const void* x_in, int x_is_u8, int B, hipStream_t s) {
     const Layer& l = h->plan.L[li];
-    const Options& o = h->opt;
     const SrcDesc sd = src_of(h, li, x_in, x_is_u8);
-    DwPlan p = dw_plan(l, B, o.mfma_mode, h->cfg.dtype, o);
-    p.npb = std::min(p.npb, l.dw_rows);
+    const DwPlan& p = r.dw;
     ConvBwdWArgs a{};
     a.x0 = sd.x0; a.ab0 = sd.ab0; a.C0 = sd.C0; a.x1 = sd.x1; a.ab1 = sd.ab1; a.C1 = sd.C1;
     a.flags = sd.flags | (l.drop_in ? F_DROP : 0);
-    a.dz = dz; a.part = l.dwp;
+    a.dz = l.g; a.part = l.dwp;
     a.B = B; a.H = l.H; a.W = l.W; a.Cin = l.cin; a.Cout = l.cout;
     a.tiles_x = cdiv(l.W, kTileX); a.tiles = p.tiles; a.total_tiles = B * a.tiles; a.npb = p.npb;
     a.drop = make_drop(h); a.act_bf16 = h->cfg.dtype;
-    if (fused_apply) { a.zf = l.z; a.bnf = l.bn; }
+    if (r.fuse) { a.zf = l.z; a.bnf = l.bn; }
     const double px = (double)B * l.H * l.W, fl = 2.0 * l.kh * l.kw * l.cin * l.cout * px;
     const int es = h->cfg.dtype ? 2 : 4;
-    const double by = in_bytes(l, B, x_is_u8, es) + px * l.cout * es * (fused_apply ? 2 : 1);   // conv input once + dz once (fused: g' and z)
+    const double by = in_bytes(l, B, x_is_u8, es) + px * l.cout * es * (r.fuse ? 2 : 1);   // conv input once + dz once (fused: g' and z)
     const bool up = l.src == SRC_UP;
-    const LaunchCtx lc{&o, B, s, l.name, fl, by};
+    const LaunchCtx lc{&h->opt, B, s, l.name, fl, by};
     int rc = 0;
-    if (p.kind == 0 && l.cin == 1 && l.cout == 8 && l.kh == 3 && !(a.flags & (F_AFF | F_DROP | F_TWO | F_UP))) {
-        // the real first layer: streaming reduction kernel (kernels_bwd.hpp)
+    if (p.kind == DW_VALU && first_dw_streams(l)) {
+        // streaming reduction kernel (kernels_bwd.hpp)
         const int tx = cdiv(l.W, 128), tiles = tx * cdiv(l.H, 8), total = B * tiles;
         const int grid = std::min(total, a.npb);
         a.npb = grid;
         const int bf = a.act_bf16;
         ProfScope ps(s, bf ? "conv_dw_first_k<unsigned short>" : "conv_dw_first_k<float>", l.name, fl, by);
-        if (fused_apply) AT_DISPATCH(bf, (conv_dw_first_k<AT, true><<<grid, kBlock, 0, s>>>(a, tx, tiles, total)));
+        if (r.fuse) AT_DISPATCH(bf, (conv_dw_first_k<AT, true><<<grid, kBlock, 0, s>>>(a, tx, tiles, total)));
         else AT_DISPATCH(bf, (conv_dw_first_k<AT, false><<<grid, kBlock, 0, s>>>(a, tx, tiles, total)));
         HIP_OK(hipGetLastError());
-    } else if (p.kind == 0) {
-        if (fused_apply) return fail(-3, "conv_backward_w: the generic first-layer kernel does not apply the BN-backward transform");
+    } else if (p.kind == DW_VALU) {
+        if (r.fuse) return fail(-3, "conv_backward_w: the generic first-layer kernel does not apply the BN-backward transform");
         rc = launch_dw<3>(a, p.cic, p.coc, s, l.name, fl, by);   // other 1-channel / odd-channel first layers
-    } else if (p.kind == 33 || p.kind == 34) {
+    } else if (p.kind == DW_BX || p.kind == DW_BT) {
         rc = launch_dw_bf16pipe(a, p, l.kh, up, lc);
     } else {
         rc = launch_dw_f32pipe(a, p, l.kh, up, lc);
@@ -638,13 +734,21 @@ int conv_backward_w(oct_unet* h, int li, const void* x_in, int x_is_u8, const vo
     return 0;
 }
 
+// Launch a kernel; `done`, when given, is bound to the dispatch as its own completion signal (hipExtLaunchKernelGGL's
+// stopEvent).  Without one this is the plain launch.
+template <typename... KA, typename... A>
+void launch_signalling(void (*kernel)(KA...), dim3 grid, hipStream_t s, hipEvent_t done, A... args) {
+    if (done) hipExtLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, s, nullptr, done, 0, static_cast<KA>(args)...);
+    else kernel<<<grid, kBlock, 0, s>>>(static_cast<KA>(args)...);
+}
+
 // finalize (and, unless the consumers apply it on load, apply) BN backward for block li: its g buffer holds masked
 // gradients, stat_part the partials
 // `done` (optional): an event that must complete when the block's dz inputs are final.  It is bound to the LAST kernel
-// launched here as that dispatch's own completion signal (hipExtLaunchKernelGGL's stopEvent) instead of being recorded
-// behind it: a recorded event is a marker packet of its own in the stream, and the next backward-data launch waits
-// ~6 us for the command processor to retire it -- on every block that forks a backward-weights kernel.  *bound = false
-// when nothing was launched (the caller then records the event the ordinary way).
+// launched here as that dispatch's own completion signal instead of being recorded behind it: a recorded event is a marker
+// packet of its own in the stream, and the next backward-data launch waits ~6 us for the command processor to retire it --
+// on every block that forks a backward-weights kernel.  *bound = false when nothing was launched (the caller then records
+// the event the ordinary way).
 int bn_backward(oct_unet* h, int li, int nblk, int B, hipStream_t s, bool finalize_only, bool finalized_in_launch,
                 hipEvent_t done = nullptr, bool* bound = nullptr) {
     const Layer& l = h->plan.L[li];
@@ -654,58 +758,119 @@ int bn_backward(oct_unet* h, int li, int nblk, int B, hipStream_t s, bool finali
         f.part = h->stat_part; f.nblk = nblk; f.C = l.cout; f.count = (double)B * l.H * l.W;
         f.bn = l.bn; f.gamma = h->params + l.gamma_off; f.dgamma = h->grads + l.gamma_off; f.dbeta = h->grads + l.beta_off;
         ProfScope ps(s, "bn_bwd_finalize_k", l.name, 0, (double)nblk * 2 * l.cout * 4);
-        if (done && finalize_only) {
-            hipExtLaunchKernelGGL(bn_bwd_finalize_k, dim3(l.cout), dim3(kBlock), 0, s, nullptr, done, 0, f);
-            if (bound) *bound = true;
-        } else {
-            bn_bwd_finalize_k<<<l.cout, kBlock, 0, s>>>(f);
-        }
+        launch_signalling(bn_bwd_finalize_k, dim3(l.cout), s, finalize_only ? done : nullptr, f);
+        if (bound && done && finalize_only) *bound = true;
         HIP_OK(hipGetLastError());
     }
     if (finalize_only) return 0;      // the consumers apply the transform themselves
     const size_t n4 = (size_t)B * l.H * l.W * l.cout / 4;
-    const int grid = (int)std::min<size_t>((n4 + kBlock - 1) / kBlock, 8192);
     const int bf = h->cfg.dtype;
     if (bf && l.cout % 8 == 0) {           // 16-byte accesses in bf16 mode
         const size_t n8 = n4 / 2;
         const int grid8 = (int)std::min<size_t>((n8 + kBlock - 1) / kBlock, 8192);
         ProfScope ps(s, "bn_bwd_apply8_bf16_k", l.name, 0, (double)n4 * 8 * 3);
-        if (done) {
-            hipExtLaunchKernelGGL(bn_bwd_apply8_bf16_k, dim3(grid8), dim3(kBlock), 0, s, nullptr, done, 0,
-                                  (bf16_t*)l.g, (const bf16_t*)l.z, (const float*)l.bn, n8, l.cout);
-            if (bound) *bound = true;
-        } else {
-            bn_bwd_apply8_bf16_k<<<grid8, kBlock, 0, s>>>((bf16_t*)l.g, (const bf16_t*)l.z, l.bn, n8, l.cout);
-        }
-        HIP_OK(hipGetLastError());
-        return 0;
-    }
-    ProfScope ps(s, bf ? "bn_bwd_apply_k<unsigned short>" : "bn_bwd_apply_k<float>", l.name, 0, (double)n4 * (bf ? 8 : 16) * 3);
-    if (done) {
-        AT_DISPATCH(bf, hipExtLaunchKernelGGL(bn_bwd_apply_k<AT>, dim3(grid), dim3(kBlock), 0, s, nullptr, done, 0,
-                                              (AT*)l.g, (const AT*)l.z, (const float*)l.bn, n4, l.cout));
-        if (bound) *bound = true;
+        launch_signalling(bn_bwd_apply8_bf16_k, dim3(grid8), s, done, l.g, l.z, l.bn, n8, l.cout);
     } else {
-        AT_DISPATCH(bf, bn_bwd_apply_k<AT><<<grid, kBlock, 0, s>>>((AT*)l.g, (const AT*)l.z, l.bn, n4, l.cout));
+        const int grid = (int)std::min<size_t>((n4 + kBlock - 1) / kBlock, 8192);
+        ProfScope ps(s, bf ? "bn_bwd_apply_k<unsigned short>" : "bn_bwd_apply_k<float>", l.name, 0, (double)n4 * (bf ? 8 : 16) * 3);
+        AT_DISPATCH(bf, launch_signalling(bn_bwd_apply_k<AT>, dim3(grid), s, done, l.g, l.z, l.bn, n4, l.cout));
     }
+    if (bound && done) *bound = true;
     HIP_OK(hipGetLastError());
     return 0;
 }
 
-int backward_impl(oct_unet* h, const void* x_in, int x_is_u8, const unsigned char* labels, int macro, float loss_scale, hipStream_t s) {
-    Plan& pl = h->plan;
-    const int nl = (int)pl.L.size(), B = h->last_B;
-    const Layer& hd = pl.L[nl - 1]; const Layer& last = pl.L[nl - 2];
-    // head: dlogits, masked gradient of the last block + its statistics
+// head backward: dlogits, the head's kernel / bias gradient rows, the masked gradient of the last block and its
+// statistics.  *rows = statistic partial rows it wrote; *fin = true if it finalized those statistics itself
+int head_backward(oct_unet* h, const unsigned char* labels, int macro, float loss_scale, int B, hipStream_t s, int* rows, bool* fin) {
+    const int nl = (int)h->plan.L.size();
+    const Layer& hd = h->plan.L[nl - 1]; const Layer& last = h->plan.L[nl - 2];
     HeadBwdArgs hb{};
     hb.z = last.z; hb.bn = last.bn; hb.w = h->params + hd.w_off; hb.bias = h->params + hd.b_off;
     hb.labels = labels; hb.bc = h->dice_bc; hb.g = last.g; hb.part = h->stat_part; hb.wpart = hd.dwp;
     hb.HW = hd.H * hd.W; hb.nblk = head_nblk(hb.HW, B); hb.B = B; hb.macro = macro; hb.loss_scale = loss_scale; hb.act_bf16 = h->cfg.dtype;
     hb.focal_w = h->focal_w; hb.focal_gamma = h->focal_gamma; hb.focal_cw = h->focal_cw; hb.focal_clip_mod = h->opt.focal_clip_mod; hb.inv_count = 1.f / ((float)B * hb.HW);
+    if (fin_ok(h, last)) { hb.fin = fin_desc(h, nl - 2, 1, B); *fin = true; }
+    *rows = B * hb.nblk;
+    return DISPATCH_C(launch_head_bwd, h->cfg.n_cls, hb, hd.cin, B, s);
+}
+
+// one backward-data launch of block li.  *rows = statistic partial rows it wrote; *fin = true if it finalized the
+// producer's statistics itself
+int launch_dx(oct_unet* h, int li, const DxLaunch& d, int B, hipStream_t s, int* rows, bool* fin) {
+    const Layer& l = h->plan.L[li];
+    const BwdRoute& r = h->route[li];
+    IgemmArgs g = d.a;
+    if (r.fuse) { g.gb_z = l.z; g.gb_bn = l.bn; }
+    const int Cg = g.Mout;
+    const double px = (double)B * l.H * l.W, pxg = (double)B * g.Ho * g.Wo;
+    double fl = 2.0 * l.kh * l.kw * Cg * l.cout * px;                // algorithmic flops of the original conv's dX
+    const int es = h->cfg.dtype ? 2 : 4;
+    double by = px * l.cout * es * (r.fuse ? 2 : 1) + pxg * Cg * es * (d.prod ? 2 : 1);
+    if (r.fdw) {
+        g.dw_x = d.dw_x->z; g.dw_ab = d.dw_x->bn; g.dw_part = l.dwp; g.dw_Cin = l.cin; g.dw_ci_off = g.m_off; g.dw_bias = d.dw_bias ? 1 : 0;
+        fl *= 2; if (!d.prod) by += pxg * Cg * es;                    // + the dW flops; + the X read where no mask reads it
+    }
+    const LaunchCtx lc{&h->opt, B, s, l.name, fl, by};
+    if (d.prod && fin_ok(h, *d.prod) && d.route == ROUTE_BT) {
+        g.fin = fin_desc(h, (int)(d.prod - h->plan.L.data()), 1, B); *fin = true;
+    }
+    if (d.up) return launch_igemm<3, A_DOWN2, EPI_MASK>(g, lc, rows);
+    return d.prod ? launch_igemm<3, A_NORMAL, EPI_MASK>(g, lc, rows)
+                  : launch_igemm<3, A_NORMAL, EPI_RAW>(g, lc, rows);
+}
+
+// max-pool backward in front of block li: routes the raw gradient wrt the pooled tensor into block li-1, masked, and emits
+// that block's statistics.  *rows / *fin as launch_dx
+int pool_backward(oct_unet* h, int li, int B, hipStream_t s, int* rows, bool* fin) {
+    const Layer& l = h->plan.L[li]; const Layer& p = h->plan.L[li - 1];
+    PoolBwdArgs pb{};
+    pb.gp = h->gpooled[l.level - 1]; pb.z = p.z; pb.bn = p.bn; pb.g = p.g; pb.part = h->stat_part;
+    pb.act_bf16 = h->cfg.dtype; pb.H = p.H; pb.W = p.W; pb.C = p.cout; pb.tiles_x = cdiv(p.W / 2, kTileX); pb.tiles = tiles_of(p.H / 2, p.W / 2);
+    const int bf = h->cfg.dtype, c4 = p.cout / 4;
+    const double pbytes = (double)B * p.H * p.W * p.cout * (bf ? 2 : 4) * 3.25;
+    if (c4 >= 1 && c4 <= 64 && (c4 & (c4 - 1)) == 0) {     // flat, channel-contiguous mapping
+        const bool v8 = bf && p.cout % 8 == 0;                               // bf16 storage: 8 channels (16 bytes) per thread
+        const size_t items = (size_t)B * (p.H / 2) * (p.W / 2) * (v8 ? c4 / 2 : c4);
+        const size_t cap = (size_t)B * cdiv(p.H, 2) * cdiv(p.W, kTileX);     // statistic rows carve() guarantees
+        const int grid = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(cdiv((int)items, kBlock), 2048), cap));
+        if (fin_ok(h, p)) { pb.fin = fin_desc(h, li - 1, 1, B); *fin = true; }
+        ProfScope ps(s, bf ? (v8 ? "pool_bwd_flat_k<unsigned short,8>" : "pool_bwd_flat_k<unsigned short>") : "pool_bwd_flat_k<float>", p.name, 0, pbytes);
+        if (v8) pool_bwd_flat_k<bf16_t, 8><<<grid, kBlock, 0, s>>>(pb, B);
+        else AT_DISPATCH(bf, pool_bwd_flat_k<AT><<<grid, kBlock, 0, s>>>(pb, B));
+        *rows = grid;
+    } else {
+        dim3 grid(pb.tiles, p.cout / 4, B);
+        ProfScope ps(s, bf ? "pool_bwd_k<4,unsigned short>" : "pool_bwd_k<4,float>", p.name, 0, pbytes);
+        AT_DISPATCH(bf, pool_bwd_k<4, AT><<<grid, kBlock, 0, s>>>(pb));
+        *rows = B * pb.tiles;
+    }
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// Fork the backward-weights launches of the blocks in `pend` to the side stream: it waits for `fe` -- dz of every pending
+// block is final there; recorded on s here unless a launch already carries it -- and takes the launches.
+int fork_pending_dw(oct_unet* h, std::vector<int>& pend, hipEvent_t fe, bool fe_bound, const void* x_in, int x_is_u8, int B, hipStream_t s) {
+    if (!fe_bound) HIP_OK(hipEventRecord(fe, s));
+    HIP_OK(hipStreamWaitEvent(h->side, fe, 0));
+    for (int li : pend)
+        if (int rc = conv_backward_w(h, li, h->route[li], x_in, x_is_u8, B, h->side)) return rc;
+    pend.clear();
+    return 0;
+}
+
+int backward_impl(oct_unet* h, const void* x_in, int x_is_u8, const unsigned char* labels, int macro, float loss_scale, hipStream_t s) {
+    const Plan& pl = h->plan;
+    const Options& o = h->opt;
+    const int nl = (int)pl.L.size(), B = h->last_B;
+    int rc = plan_backward(h, B);
+    if (rc) return rc;
     // backward-data weights of every block for this step's parameters: transposed / effective fp32 kernels, then their
     // bf16 operand layouts.  Nothing needs them before the first backward-data launch, so they run on the side stream
     // under the head backward and the last block's BN backward.
-    const bool side_ok = h->opt.dw_side_stream && h->side && !(t_prof && t_prof->on);
+    // (the per-launch profiler wants serial launches)
+    const bool side_ok = o.dw_side_stream && h->side && !(t_prof && t_prof->on);
     hipStream_t ps_ = side_ok ? h->side : s;
     if (side_ok) { HIP_OK(hipEventRecord(h->fork_ev[0], s)); HIP_OK(hipStreamWaitEvent(h->side, h->fork_ev[0], 0)); }
     {
@@ -713,207 +878,64 @@ int backward_impl(oct_unet* h, const void* x_in, int x_is_u8, const unsigned cha
         prep_wt_k<<<std::min<unsigned>((h->wt_total + kBlock - 1) / kBlock, 2048u), kBlock, 0, ps_>>>(h->wt_descs, h->n_wt, h->wt_total);
         HIP_OK(hipGetLastError());
     }
-    if (h->opt.mfma_mode && h->n_wbx_b) {
-        ProfScope ps(ps_, "prep_wbx_k", "all", 0, (double)h->wbx_b_total * 8 * (4 + 2 * (h->cfg.dtype ? 1 : 3)));
-        prep_wbx_k<<<std::min<unsigned>((h->wbx_b_total + kBlock - 1) / kBlock, 2048u), kBlock, 0, ps_>>>(h->wbx_descs + h->n_wbx_f, h->n_wbx_b, h->wbx_b_total);
-        HIP_OK(hipGetLastError());
-    }
-    if (h->opt.mfma_mode && h->n_wbt_b) {
-        ProfScope ps(ps_, "prep_wbt_k", "all", 0, (double)h->wbt_b_total * 8 * (4 + 2 * (h->cfg.dtype ? 1 : 3)));
-        prep_wbt_k<<<std::min<unsigned>((h->wbt_b_total + kBlock - 1) / kBlock, 2048u), kBlock, 0, ps_>>>(h->wbt_descs + h->n_wbt_f, h->n_wbt_b, h->wbt_b_total);
-        HIP_OK(hipGetLastError());
-    }
+    if ((rc = prep_split_weights(h, true, ps_))) return rc;
     if (side_ok) HIP_OK(hipEventRecord(h->prep_ev, h->side));
     bool prep_pending = side_ok;
+    int pending_nblk = 0;                     // number of stat partial rows waiting for block (li-1)
     bool pending_fin = false;                 // the pending statistics were finalized by the launch that emitted them
-    if (fin_ok(h, last)) { hb.fin = fin_desc(h, nl - 2, 1, B); pending_fin = true; }
-    int rc = DISPATCH_C(launch_head_bwd, h->cfg.n_cls, hb, hd.cin, B, s);
-    if (rc) return rc;
-    int pending_nblk = B * hb.nblk;           // number of stat partial rows waiting for block (li-1)
-    bool forked = false;
-    struct PendingDw { int li; bool fuse; };
-    std::vector<PendingDw> pend;          // forked backward-weights launches not yet issued
-    unsigned n_forks = 0;
+    if ((rc = head_backward(h, labels, macro, loss_scale, B, s, &pending_nblk, &pending_fin))) return rc;
+    std::vector<int> pend;                    // blocks whose forked backward-weights launch is not yet issued
+    unsigned n_forks = 0;                     // forks so far: they rotate through the handle's events
     h->red.n = 0;
-    queue_reduce(h, hd, pending_nblk);   // head kernel/bias gradient rows written by head_bwd_k
+    queue_reduce(h, pl.L[nl - 1], pending_nblk);   // head kernel/bias gradient rows written by head_bwd_k
 
     for (int li = nl - 2; li >= 0; --li) {
-        Layer& l = pl.L[li];
-        const Options& o = h->opt;
-        // backward-data launches of this block: dz x transposed / effective weights through the MFMA implicit-GEMM kernels
-        auto dx_args = [&](void* gout, int Cg, int ci_off, const Layer* prod, bool up) {
-            IgemmArgs g{};
-            g.x0 = l.g; g.C0 = l.cout; g.flags = 0; g.Cin = l.cout;
-            g.w = l.wt; g.w_ld = l.cin; g.m_off = ci_off; g.out = gout; g.Mout = Cg;
-            g.Hi = l.H; g.Wi = l.W; g.Ho = up ? l.H / 2 : l.H; g.Wo = up ? l.W / 2 : l.W;
-            g.part = prod ? h->stat_part : nullptr; g.zin = prod ? prod->z : nullptr; g.bnin = prod ? prod->bn : nullptr;
-            g.drop_out = (up && l.drop_in) ? 1 : 0; g.drop = make_drop(h); g.act_bf16 = h->cfg.dtype;
-            g.wbx = l.wbx_b; g.wbx_M = l.cin;
-            g.wbt = l.wbt_b ? l.wbt_b + (size_t)(ci_off / Cg) * (wbt_bytes(3, l.cout, h->cfg.dtype ? 1 : 3, l.bt_m2_b) / 2) : nullptr;
-            g.bt_m2 = l.bt_m2_b;
-            return g;
-        };
-        // g buffer of block li is complete (+ partials in stat_part).  Its BN-backward transform dz = ga g' + gb z + gd is
-        // applied by the consumers of dz while they stage it -- the backward-weights kernel and the backward-data launches --
-        // whenever all of them can (the bf16-pipe conv kernels and every MFMA backward-weights kernel); otherwise by the
-        // stand-alone pass, in place.  First layer: its dz has ONE consumer, the streaming backward-weights kernel.
-        const int dwkind = dw_plan(l, B, o.mfma_mode, h->cfg.dtype, o).kind;
-        bool fuse;
-        if (l.src == SRC_INPUT) {
-            fuse = o.fuse_first_apply && li == 0 && first_dw_streams(l) && dwkind == 0 &&
-                   !(src_of(h, li, x_in, x_is_u8).flags & (F_AFF | F_DROP | F_TWO | F_UP));
-        } else {
-            const int cg = bx_bwd_cg(l);
-            const bool up = l.src == SRC_UP;
-            const ConvRoute r0 = conv_route(dx_args(nullptr, cg, 0, nullptr, up), up ? A_DOWN2 : A_NORMAL, o);
-            // (three bf16-pipe instantiations stay out: the stride-2 gather beyond the coefficient rows its LDS holds; the
-            //  thin kernel at 32 K channels, whose staging registers for g' AND z no longer fit; and the thin kernel at 16 K
-            //  channels with 16 output channels, where the second raw register set spills under the 256-register budget of two
-            //  blocks per CU: 87 us against 45 + 33 for the separate pass at B = 32, 128 x 256)
-            fuse = o.fuse_bn_apply && dwkind != 0 && r0 != ROUTE_F32 && !(up && r0 == ROUTE_BX && l.cout > kBxGbDown2MaxC) &&
-                   !(r0 == ROUTE_BT && l.cout == 32) && !(r0 == ROUTE_BT && l.cout == 16 && cg == 16 && !o.fuse_bn_apply16) &&
-                   (l.src != SRC_CONCAT || conv_route(dx_args(nullptr, cg, cg, nullptr, false), A_NORMAL, o) != ROUTE_F32);
-        }
-        l.g_masked = fuse;
-        // 3x3 layers with 8 output channels on the thin kernel (the full-resolution convs): their backward-data launches
-        // reduce the backward-weights too (conv_bt_k FDW) -- g', z and the producer's z are read once for both
-        bool fdw = false;
-        if (fuse && o.fuse_dw_thin && l.kh == 3 && l.cout == 8 && !l.drop_in && (l.src == SRC_PREV || l.src == SRC_CONCAT) &&
-            bx_bwd_cg(l) == 8 && l.dw_rows >= std::min(B * cdiv(l.W, 32) * cdiv(l.H, 8), 512) &&      // (one slab per block of that launch)
-            conv_route(dx_args(nullptr, 8, 0, nullptr, false), A_NORMAL, o) == ROUTE_BT &&
-            (l.src != SRC_CONCAT || conv_route(dx_args(nullptr, 8, 8, nullptr, false), A_NORMAL, o) == ROUTE_BT))
-            fdw = true;
-        // (the per-launch profiler wants serial launches; the input layer has no backward-data launch to run beside, so its
-        //  backward-weights kernel stays on the caller's stream: no fork, no join wait in front of the slab reduce)
-        const bool fork = side_ok && !fdw && l.src != SRC_INPUT;
-        // Forked backward-weights launches go to the side stream in GROUPS (dw_fork_group blocks per fork): every event the
-        // side stream waits for costs the caller's stream ~6 us in front of its next launch (the dispatch that carries the
-        // completion signal has to be retired by the command processor first), and a block's dz, z and record stay valid
-        // until the end of the backward pass, so its backward-weights kernel may start a block or two late.
+        const Layer& l = pl.L[li];
+        const BwdRoute& r = h->route[li];
+        // g buffer of block li is complete (+ partials in stat_part).  Its backward-weights launch goes to the side stream
+        // unless the backward-data launches carry it; the input layer has no backward-data launch to run beside, so its
+        // kernel stays on the caller's stream: no fork, no join wait in front of the slab reduce
+        const bool fork = side_ok && !r.fdw && l.src != SRC_INPUT;
         const bool tail_here = li == first_mid_layer(pl);      // every gradient from the first bottleneck conv on is queued here
-        if (fork) pend.push_back({li, fuse});
+        // Forked launches go to the side stream in GROUPS (dw_fork_group blocks per fork): every event the side stream waits
+        // for costs the caller's stream ~6 us in front of its next launch (the dispatch that carries the completion signal
+        // has to be retired by the command processor first), and a block's dz, z and record stay valid until the end of
+        // the backward pass, so its backward-weights kernel may start a block or two late.
+        if (fork) pend.push_back(li);
         const bool flush = !pend.empty() && (!fork || (int)pend.size() >= o.dw_fork_group || tail_here);
         hipEvent_t fe = flush ? h->fork_ev[1 + n_forks++ % (h->fork_ev.size() - 1)] : nullptr;
         bool fe_bound = false;
-        rc = bn_backward(h, li, pending_nblk, B, s, fuse, pending_fin, (flush && o.fork_on_launch) ? fe : nullptr, &fe_bound);
+        rc = bn_backward(h, li, pending_nblk, B, s, r.fuse, pending_fin, (flush && o.fork_on_launch) ? fe : nullptr, &fe_bound);
         if (rc) return rc;
         pending_fin = false;
-        if (flush) {
-            if (!fe_bound) HIP_OK(hipEventRecord(fe, s));        // dz of every pending block is final here
-            HIP_OK(hipStreamWaitEvent(h->side, fe, 0));
-            for (const PendingDw& p : pend) {
-                rc = conv_backward_w(h, p.li, x_in, x_is_u8, pl.L[p.li].g, B, h->side, p.fuse);
-                if (rc) return rc;
-            }
-            pend.clear();
-            forked = true;
-        }
-        if (!fdw && !fork) {
-            rc = conv_backward_w(h, li, x_in, x_is_u8, l.g, B, s, fuse);
-            if (rc) return rc;
-        }
-        if (tail_here && (forked || h->tail_event)) {
+        if (flush && (rc = fork_pending_dw(h, pend, fe, fe_bound, x_in, x_is_u8, B, s))) return rc;
+        if (!r.fdw && !fork && (rc = conv_backward_w(h, li, r, x_in, x_is_u8, B, s))) return rc;
+        if (tail_here && (n_forks || h->tail_event)) {
             // every parameter gradient at offsets >= L[li].w_off (bottleneck, decoder, head: Keras creation order) is
             // final once the queued slabs are summed: the DP launcher all-reduces that segment on a side stream while
             // the encoder backward runs.  The sum runs on the handle's side stream, behind the backward-weights
             // kernels that write those slabs (the slabs written by launches of the caller's stream -- head, fused dX+dW --
             // are older than the fork event that stream last waited for): the caller's stream neither waits for the side
             // stream here nor carries the reduce, and the end-of-backward reduce is left with the encoder's slabs.
-            hipStream_t rs = forked ? h->side : s;
-            rc = flush_reduce(h, rs);
-            if (rc) return rc;
+            hipStream_t rs = n_forks ? h->side : s;
+            if ((rc = flush_reduce(h, rs))) return rc;
             if (h->tail_event) HIP_OK(hipEventRecord(h->tail_event, rs));
         }
         if (l.src == SRC_INPUT) break;
         if (prep_pending) { HIP_OK(hipStreamWaitEvent(s, h->prep_ev, 0)); prep_pending = false; }   // first backward-data launch
-        int rows = 0;
-        // (xsrc: with fdw, the layer whose output is this launch's slice of the conv input -- `prod` when the launch masks)
-        auto dx = [&](void* gout, int Cg, int ci_off, const Layer* prod, bool up, const Layer* xsrc = nullptr, bool first = true) -> int {
-            IgemmArgs g = dx_args(gout, Cg, ci_off, prod, up);
-            if (fuse) { g.gb_z = l.z; g.gb_bn = l.bn; }
-            const double px = (double)B * l.H * l.W, pxg = (double)B * g.Ho * g.Wo;
-            double fl = 2.0 * l.kh * l.kw * Cg * l.cout * px;                // algorithmic flops of the original conv's dX
-            const int es = h->cfg.dtype ? 2 : 4;
-            double by = px * l.cout * es * (fuse ? 2 : 1) + pxg * Cg * es * (prod ? 2 : 1);
-            if (fdw) {
-                g.dw_x = xsrc->z; g.dw_ab = xsrc->bn; g.dw_part = l.dwp; g.dw_Cin = l.cin; g.dw_ci_off = ci_off; g.dw_bias = first ? 1 : 0;
-                fl *= 2; if (!prod) by += pxg * Cg * es;                      // + the dW flops; + the X read where no mask reads it
-            }
-            const LaunchCtx lc{&o, B, s, l.name, fl, by};
-            if (prod && fin_ok(h, *prod) && conv_route(g, up ? A_DOWN2 : A_NORMAL, o) == ROUTE_BT) {
-                g.fin = fin_desc(h, (int)(prod - pl.L.data()), 1, B); pending_fin = true;
-            }
-            if (up) return launch_igemm<3, A_DOWN2, EPI_MASK>(g, lc, &rows);
-            return prod ? launch_igemm<3, A_NORMAL, EPI_MASK>(g, lc, &rows)
-                        : launch_igemm<3, A_NORMAL, EPI_RAW>(g, lc, &rows);
-        };
-        switch (l.src) {
-            case SRC_PREV: {
-                Layer& p = pl.L[li - 1];
-                rc = dx(p.g, p.cout, 0, &p, false, &p, true);
-                if (rc) return rc;
-                pending_nblk = rows;
-                if (fdw) queue_reduce(h, l, rows);
-                break;
-            }
-            case SRC_POOL: {  // gradient wrt the pooled tensor (raw), then route through the pool into block li-1
-                Layer& p = pl.L[li - 1];
-                rc = dx(h->gpooled[l.level - 1], l.cin, 0, nullptr, false);
-                if (rc) return rc;
-                PoolBwdArgs pb{};
-                pb.gp = h->gpooled[l.level - 1]; pb.z = p.z; pb.bn = p.bn; pb.g = p.g; pb.part = h->stat_part;
-                pb.act_bf16 = h->cfg.dtype; pb.H = p.H; pb.W = p.W; pb.C = p.cout; pb.tiles_x = cdiv(p.W / 2, kTileX); pb.tiles = tiles_of(p.H / 2, p.W / 2);
-                const int bf = h->cfg.dtype, c4 = p.cout / 4;
-                const double pbytes = (double)B * p.H * p.W * p.cout * (bf ? 2 : 4) * 3.25;
-                if (c4 >= 1 && c4 <= 64 && (c4 & (c4 - 1)) == 0) {     // flat, channel-contiguous mapping
-                    const bool v8 = bf && p.cout % 8 == 0;                               // bf16 storage: 8 channels (16 bytes) per thread
-                    const size_t items = (size_t)B * (p.H / 2) * (p.W / 2) * (v8 ? c4 / 2 : c4);
-                    const size_t cap = (size_t)B * cdiv(p.H, 2) * cdiv(p.W, kTileX);     // statistic rows carve() guarantees
-                    const int grid = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(cdiv((int)items, kBlock), 2048), cap));
-                    if (fin_ok(h, p)) { pb.fin = fin_desc(h, li - 1, 1, B); pending_fin = true; }
-                    ProfScope ps(s, bf ? (v8 ? "pool_bwd_flat_k<unsigned short,8>" : "pool_bwd_flat_k<unsigned short>") : "pool_bwd_flat_k<float>", p.name, 0, pbytes);
-                    if (v8) pool_bwd_flat_k<bf16_t, 8><<<grid, kBlock, 0, s>>>(pb, B);
-                    else AT_DISPATCH(bf, pool_bwd_flat_k<AT><<<grid, kBlock, 0, s>>>(pb, B));
-                    HIP_OK(hipGetLastError());
-                    pending_nblk = grid;
-                    break;
-                }
-                const int c_t = 4;
-                dim3 grid(pb.tiles, p.cout / c_t, B);
-                ProfScope ps(s, bf ? "pool_bwd_k<4,unsigned short>" : "pool_bwd_k<4,float>", p.name, 0, pbytes);
-                AT_DISPATCH(bf, pool_bwd_k<4, AT><<<grid, kBlock, 0, s>>>(pb));
-                HIP_OK(hipGetLastError());
-                pending_nblk = B * pb.tiles;
-                break;
-            }
-            case SRC_UP: {
-                Layer& p = pl.L[li - 1];
-                rc = dx(p.g, p.cout, 0, &p, true);
-                if (rc) return rc;
-                pending_nblk = rows;
-                break;
-            }
-            case SRC_CONCAT: {
-                Layer& p = pl.L[li - 1]; Layer& k = pl.L[l.skip_from];
-                // skip half first (raw, merged later by pool_bwd of that encoder level) ...
-                rc = dx(k.g, k.cout, p.cout, nullptr, false, &k, false);
-                if (rc) return rc;
-                const int rows_skip = rows;
-                // ... then the up-path half, whose statistics must be the ones pending for block li-1
-                rc = dx(p.g, p.cout, 0, &p, false, &p, true);
-                if (rc) return rc;
-                pending_nblk = rows;
-                if (fdw) {
-                    if (rows != rows_skip) return fail(-3, "fused backward-weights: the two halves ran different grids");
-                    queue_reduce(h, l, rows);
-                }
-                break;
-            }
-            default: return fail(-3, "backward: bad src");
+        int rows = 0, rows_before = 0;
+        for (int i = 0; i < r.n_dx; ++i) {
+            rows_before = rows;
+            if ((rc = launch_dx(h, li, r.dx[i], B, s, &rows, &pending_fin))) return rc;
         }
-        if (rc) return rc;
+        pending_nblk = rows;                  // of the last launch: the one that emits block li-1's statistics, if any does
+        if (r.fdw) {
+            if (r.n_dx == 2 && rows != rows_before) return fail(-3, "fused backward-weights: the two halves ran different grids");
+            queue_reduce(h, l, rows);
+        }
+        if (l.src == SRC_POOL && (rc = pool_backward(h, li, B, s, &pending_nblk, &pending_fin))) return rc;
     }
-    if (forked) { HIP_OK(hipEventRecord(h->join_ev, h->side)); HIP_OK(hipStreamWaitEvent(s, h->join_ev, 0)); }
+    if (n_forks) { HIP_OK(hipEventRecord(h->join_ev, h->side)); HIP_OK(hipStreamWaitEvent(s, h->join_ev, 0)); }
     return flush_reduce(h, s);
 }
 
@@ -977,6 +999,7 @@ int oct_unet_create(const oct_unet_cfg* c, float* params, float* grads, float* s
         delete h; return fail(-1, "buffers must be aligned (workspace 256 B, params/grads/state 16 B)");
     }
     carve(*c, h->plan, h, (char*)ws, h->opt);
+    h->route.resize(h->plan.L.size());
     if (c->training) {
         std::vector<WtDesc> d;
         unsigned off = 0;
@@ -1072,6 +1095,7 @@ int oct_unet_create(const oct_unet_cfg* c, float* params, float* grads, float* s
 
 void oct_unet_destroy(oct_unet* h) {
     if (!h) return;
+    if (t_prof == &h->prof) t_prof = nullptr;     // the handle-less entry points (oct_augment_batch, ...) consult t_prof too
     if (h->side) {
         (void)hipStreamSynchronize(h->side);
         for (auto e : h->fork_ev) if (e) (void)hipEventDestroy(e);
@@ -1309,7 +1333,7 @@ int oct_unet_set_option(oct_unet* h, const char* name, int value) {
 
 int oct_unet_debug_layer_fused(const oct_unet* h, int layer) {
     if (!h || layer < 0 || layer >= (int)h->plan.L.size()) return -1;
-    return h->plan.L[layer].g_masked ? 1 : 0;
+    return h->route[layer].fuse ? 1 : 0;
 }
 
 const void* oct_unet_debug_activation(oct_unet* h, int layer, int which) {
