@@ -310,3 +310,162 @@ def test_configs4_inference_batch_128_every_layer():
     S = ll.engine_stored(eng, B, probs, training=False, argmax=am)
     rep = ll.LayerLocal(cfg, p64, S, img, training=False, state=s64, mode="f32", device="cuda:0").run()
     _finish(rep, t0, "configs[4] fp32 inference B=128 256x512")
+
+
+# ---- production routing at real, non-power-of-two sizes ---------------------------------------------------------------
+# OCT B-scans are 496 rows high.  Every conv kernel tiles pixels 32 wide and 4, 8 or 16 rows high and the thin persistent
+# kernel walks B * cdiv(W, 32) * cdiv(H, 8) tiles with at most 256 * per_cu blocks: at the sizes below blocks loop over
+# many tiles of which some are ragged (the last tile row at 496 = 62 x 8 is full, at 124 and 62 it is not; 432 and 48 are
+# no multiples of 32), levels have odd heights (31, 17, 15) and odd widths (27, 23), and the statistic rows of a launch
+# count cdiv(H, 2) * cdiv(W, 32) per image.  Same model, gates and default options as the tests above.  Their printed tables:
+# profiles/r05_layer_local_ragged.txt.
+
+# Scan seeds.  EXCLUDE_MAX (1e-5 of the elements) caps what the fp32 mask / route exclusions may remove; that the inputs alone
+# stay inside it is checked on the CPU by tools/check_exclusions.py: the same LayerLocal on the tensors of a defect-free
+# engine (tests/test_layer_local.perfect_engine: the oracle's primitives, same weights, scans, rolls and dropout bits) at
+# the tests' own batches reports no failure and excludes 46 of 4.72e8 elements at 496x768 (B = 8), 9 of 1.46e8 at 272x432
+# (B = 8), 2 of 5.5e7 for the partial step's scans (B = 3); bf16 480x736 (B = 8): no failure (that mode has no exclusions).
+# The inference check excludes nothing by construction.
+SCAN_SEED = {(496, 768): 31, (272, 432): 43, (272, 432, "partial"): 57, (480, 736): 41, (496, 768, "infer"): 21}
+
+
+# Kernel instantiations of these steps (from their first passing run; a tripwire for routing changes, not a correctness
+# gate).  At batch 8 / 3 every one is the set of the partial steps above: the routing depends on the kernel shapes and the
+# call's B, not on whether the image divides the tiles.
+CONV_496x768 = CONV_272x432 = CONV_272x432_B3_OF_8 = CONV_B7_OF_32
+CONV_480x736_BF16 = CONV_B5_OF_8
+CONV_INFER_496x768 = CONV_INFER
+
+
+def ragged_scans(n, H, W, seed, step):
+    """n synthetic scans at H x W (8 distinct ones, tiled), image k rolled by step * k columns -- labels alongside."""
+    from oct_image_segmentation_models_amd.common.synthetic import make_scans
+    img8, lab8 = make_scans(8, H, W, C, seed=seed)
+    reps = (n + 7) // 8
+    img, lab = np.tile(img8, (reps, 1, 1, 1))[:n], np.tile(lab8, (reps, 1, 1, 1))[:n]
+    for k in range(n):
+        img[k] = np.roll(img[k], step * k, axis=1); lab[k] = np.roll(lab[k], step * k, axis=1)
+    return img, lab
+
+
+def _cdiv(a, b):
+    return (a + b - 1) // b
+
+
+def _check_routing_rules(ents, P, B, H, W):
+    """What the routing rules predict at any size (the pinned sets above and below are tripwires, these are the claims):
+    the full-resolution 8 -> 8 layers reduce their backward-weights inside their conv_bt_k backward-data launches, and the
+    wide kernel and both bf16-pipe backward-weights kernels ran.  That the persistent thin kernel's blocks loop is not
+    observable (a profile entry carries no grid): the last line is arithmetic on the test's own constants, a comment that
+    the size was chosen so, not a check."""
+    dw = {e["layer"] for e in ents if e["kernel"].startswith("conv_bt_k<") and e["kernel"].endswith(",dw>")}
+    assert dw == {"enc0.conv1", f"dec{P - 1}.conv0", f"dec{P - 1}.conv1"}, dw
+    fams = {e["kernel"].split("<")[0] for e in ents}
+    assert {"conv_bt_k", "conv_bx_k", "conv_dwbx_k", "conv_dwbt_k"} <= fams, fams
+    # launch_bt: grid = min(B * tiles, 256 * per_cu), per_cu <= 3
+    assert B * _cdiv(W, 32) * _cdiv(H, 8) > 256 * 3
+
+
+def _train_step_layer_local(H, W, P, B, mode, scan_seed, expected, title):
+    """One default-route training step at batch B of H x W against the layer-local fp64 model."""
+    from oct_image_segmentation_models_amd import _hip
+    from oct_image_segmentation_models_amd.engine import UNetEngine
+    t0 = time.time()
+    cfg = on.UNetConfig(num_classes=C, start_neurons=8, pool_layers=P)
+    params, state = on.init_params(cfg, seed=7, dtype=np.float32, randomize_bn=True)
+    eng = UNetEngine(device="cuda:0", input_channels=1, num_classes=C, image_height=H, image_width=W, max_batch=B,
+                     training=True, seed=5, init_seed=1, pool_layers=P, dtype="bfloat16" if mode == "bf16" else "float32")
+    eng.set_weights(on.keras_weight_list(params, state))
+    img, lab = ragged_scans(B, H, W, scan_seed, 5)
+    x = torch.from_numpy(img).cuda(); l = torch.from_numpy(lab[..., 0].copy()).cuda()
+    eng.set_dropout_step(3)
+    mask = eng.dropout_mask(B).double()
+    eng.profile_begin()
+    probs, _ = eng.forward(x, training=True, labels=l)
+    eng.loss_dice()
+    eng.backward(l, macro=True, loss_scale=1.0)
+    ents = eng.profile_end()
+    _check_routing(ents, expected)
+    _check_routing_rules(ents, P, B, H, W)
+    p64, _ = _params_from_engine(eng)
+    S = ll.engine_stored(eng, B, probs)
+    rep = ll.LayerLocal(cfg, p64, S, img, labels=lab[..., 0], dropout_mask=mask, mode=mode,
+                        mfma_mode=_hip.get_option("mfma_mode"), device="cuda:0").run()
+    _finish(rep, t0, title)
+
+
+def test_fp32_batch_8_at_496x768():
+    """496x768 (a real B-scan height), P=4, fp32, batch 8: levels 496x768, 248x384, 124x192, 62x96, bottleneck 31x48 --
+    rows ragged from 124 down, the width ragged at 48, the bottleneck height odd."""
+    _train_step_layer_local(496, 768, 4, 8, "f32", SCAN_SEED[496, 768], CONV_496x768, "fp32 B=8 496x768")
+
+
+def test_fp32_batch_8_at_272x432():
+    """272x432, P=4, fp32, batch 8: bottleneck 17x27; 432 = 13.5 x 32, so every persistent conv_bt_k block walks ragged
+    tiles at full resolution, and every level below has a ragged width too (216, 108, 54, 27)."""
+    _train_step_layer_local(272, 432, 4, 8, "f32", SCAN_SEED[272, 432], CONV_272x432, "fp32 B=8 272x432")
+
+
+def test_fp32_batch_3_at_272x432_on_an_engine_used_at_8():
+    """272x432, fp32, max_batch 8: one full step, then B = 3 on other scans; the workspace rows were carved for 8."""
+    from oct_image_segmentation_models_amd.engine import UNetEngine
+    t0 = time.time()
+    MB, B, H, W, P = 8, 3, 272, 432, 4
+    cfg = on.UNetConfig(num_classes=C, start_neurons=8, pool_layers=P)
+    params, state = on.init_params(cfg, seed=7, dtype=np.float32, randomize_bn=True)
+    eng = UNetEngine(device="cuda:0", input_channels=1, num_classes=C, image_height=H, image_width=W, max_batch=MB,
+                     training=True, seed=5, init_seed=1)
+    eng.set_weights(on.keras_weight_list(params, state))
+    img, lab = ragged_scans(MB, H, W, SCAN_SEED[272, 432], 5)
+    img3, lab3 = ragged_scans(B, H, W, SCAN_SEED[272, 432, "partial"], 11)
+    rep, ents = _used_engine_partial_step(eng, cfg, img, lab, img3, lab3, "f32")
+    _check_routing(ents, CONV_272x432_B3_OF_8)
+    _check_routing_rules(ents, P, B, H, W)
+    _finish(rep, t0, "fp32 B=3 of max_batch 8, 272x432")
+
+
+def test_bf16_batch_8_at_480x736():
+    """480x736, P=5, bf16 storage, batch 8, on the fused route (the default): levels down to a 15x23 bottleneck, odd
+    heights and widths from 30x46 down."""
+    _train_step_layer_local(480, 736, 5, 8, "bf16", SCAN_SEED[480, 736], CONV_480x736_BF16, "bf16 B=8 480x736 P=5")
+
+
+def test_inference_batch_16_at_496x768_and_graph_replay():
+    """Inference, fp32, batch 16 at 496x768, randomised moving statistics: every layer's z, the probabilities, the
+    arg-max away from ties; then the same forward captured into a hipGraph and replayed, bit-equal to the direct call."""
+    from oct_image_segmentation_models_amd.engine import UNetEngine
+    t0 = time.time()
+    B, H, W = 16, 496, 768
+    cfg = on.UNetConfig(num_classes=C, start_neurons=8, pool_layers=4)
+    eng = UNetEngine(device="cuda:0", input_channels=1, num_classes=C, image_height=H, image_width=W, max_batch=B,
+                     training=False, seed=5, init_seed=1)
+    rng = np.random.default_rng(0)
+    wl = eng.get_weights()
+    i = 0
+    for L in eng.layers:
+        i += 2
+        if L["has_bn"]:
+            c = L["cout"]
+            wl[i] = rng.uniform(0.5, 1.5, c).astype(np.float32); wl[i + 1] = rng.normal(0, 0.1, c).astype(np.float32)
+            wl[i + 2] = rng.normal(0, 0.1, c).astype(np.float32); wl[i + 3] = rng.uniform(0.5, 1.5, c).astype(np.float32)
+            i += 4
+    eng.set_weights(wl)
+    img, _ = ragged_scans(B, H, W, SCAN_SEED[496, 768, "infer"], 3)
+    x = torch.from_numpy(img).cuda()
+    eng.profile_begin()
+    probs, am = eng.forward(x, training=False, want_argmax=True)
+    ents = eng.profile_end()
+    _check_routing(ents, CONV_INFER_496x768)
+    assert {"conv_bt_k", "conv_bx_k"} <= {e["kernel"].split("<")[0] for e in ents}
+    assert B * _cdiv(W, 32) * _cdiv(H, 8) > 256 * 3          # (a comment, as in _check_routing_rules: the size makes the thin kernel's blocks loop)
+    probs, am = probs.clone(), am.clone()
+    p64, s64 = _params_from_engine(eng)
+    S = ll.engine_stored(eng, B, probs, training=False, argmax=am)
+    rep = ll.LayerLocal(cfg, p64, S, img, training=False, state=s64, mode="f32", device="cuda:0").run()
+    xb = x.clone()
+    gp, gam = eng.graph_capture(xb, want_probs=True, want_argmax=True)
+    for _ in range(2):
+        gp.zero_(); gam.zero_()
+        eng.graph_launch(); torch.cuda.synchronize()
+        assert torch.equal(gp, probs) and torch.equal(gam, am)
+    _finish(rep, t0, "fp32 inference B=16 496x768")

@@ -51,11 +51,23 @@ CASES = [
     (1, 32, 64, 3, 8, 2, 2, 4),     # 4 input channels: the first layer's dW must take the image-typed (uint8 / f32) VALU path
     (1, 32, 64, 3, 32, 1, 2, 1),    # start_neurons 32: every conv but the first on the wide kernels, 32-channel head
     (1, 32, 64, 3, 12, 2, 2, 1),    # start_neurons 12 (12/24/48 channels): nothing divides by 8 or 32 -> the generic kernels
+    # ragged geometries with conv_layers = 2: every kernel tiles pixels 32 wide and 4 / 8 / 16 rows high (8 x 64 for the
+    # pixel-pair and VALU thin kernels); none of the sizes below divides them at any level
+    (2, 36, 68, 3, 8, 2, 2, 1),     # 36x68, 18x34, 9x17: ragged 8 -> 8 layers (fused backward-weights, two-pixel form), odd bottleneck
+    (1, 48, 80, 3, 8, 4, 2, 1),     # default depth: the 64- and 128-channel wide kernels on 6x10 and 3x5 images, up-conv backward from 3x5
+    (3, 16, 16, 3, 8, 4, 2, 1),     # smallest legal image: 1x1 bottleneck (BN statistics over 3 values), W < 32 at every level
+    (1, 80, 24, 3, 16, 2, 2, 1),    # tall and narrow: widths 24, 12, 6; start_neurons 16
+    (2, 20, 34, 3, 4, 1, 2, 1),     # 8 -> 8 bottleneck 17 wide: the two-pixel form meets an odd width; 4-channel layers on the generic kernels
 ]
+RAGGED = CASES[7:]
 # Data seeds (found offline with the oracle alone) for which every BN pre-activation of the training
 # forward stays > 2e-5 away from the ReLU kink: fp32-vs-fp64 rounding then cannot flip a ReLU mask, so the
 # gradient comparison can use tight tolerances.  The margin is re-asserted inside the test.
-MARGIN_SEED = {CASES[0]: 97, CASES[1]: 13, CASES[2]: 28, CASES[3]: 75, CASES[4]: 3, CASES[5]: 72, CASES[6]: 58}   # tools/find_margin_seed.py
+# Margins of the ragged cases: 2.13e-5, 4.06e-5, 3.7e-5, 2.56e-5, 6.1e-5 (CASES[8]: tools/find_margin_seed.py over seeds 1 .. 12000).
+# 2e-5 is not a guarantee for every variant: at |a z| of about 9 the "bt_one_px" summation order flipped the ReLU of an
+# element 2.33e-5 from the kink (48x80 P=4, dec3.up), so prefer a seed with a wider margin where the search finds one.
+MARGIN_SEED = {CASES[0]: 97, CASES[1]: 13, CASES[2]: 28, CASES[3]: 75, CASES[4]: 3, CASES[5]: 72, CASES[6]: 58,
+               CASES[7]: 308, CASES[8]: 2743, CASES[9]: 2, CASES[10]: 38, CASES[11]: 2}   # tools/find_margin_seed.py
 DROP_STEP = 3
 
 
@@ -114,13 +126,38 @@ def variant(request):
     _hip.set_option("pair8_geometry", 221)
 
 
+# the variants under which the ragged cases assert, from the profile of the step itself, that the intricate edge code ran on
+# them: the default routing at these grid sizes, and one variant that forces the thin-layer choices
+PROFILED = ("tile_per_block", "thin8_valu")
+
+
+def check_ragged_routing(case, variant, ents, training):
+    """The ragged geometries reach what they were added for (asserted, not assumed): a conv_bt_k instantiation that also
+    reduces the backward-weights (",dw>") on the 8 -> 8 3x3 layers of the start_neurons-8 cases, and the two-pixel form
+    (",2px") on the 17-wide 8 -> 8 bottleneck of the last case, in its forward and its backward-data launch."""
+    B, H, W, C, sn, P, L, ic = case
+    bt = [(e["kernel"], e["layer"]) for e in ents if e["kernel"].startswith("conv_bt_k<")]
+    if training and sn == 8:
+        fused = {l for k, l in bt if k.endswith(",dw>")}
+        assert {"enc0.conv1", f"dec{P - 1}.conv0", f"dec{P - 1}.conv1"} <= fused, (fused, bt)
+    if case == CASES[11]:
+        two = [k for k, l in bt if ",2px" in k and l == "mid.conv1"]              # conv_bt_k<KH,AMODE,EPI,...>: EPI 0 is the forward
+        assert any(k.split(",")[2] == "0" for k in two), bt
+        assert not training or any(k.split(",")[2] != "0" for k in two), bt
+
+
 @pytest.mark.parametrize("case", CASES)
 def test_inference_forward_matches_oracle(case, variant):
     B, H, W, C, sn, P, L, ic = case
     cfg, eng, p64, s64 = make(B, H, W, C, sn, P, L, ic, training=False)
     images, labels = data(B, H, W, C, ic)
     x = torch.from_numpy(images).cuda()
+    profiled = case in RAGGED and variant in PROFILED
+    if profiled:
+        eng.profile_begin()
     probs, am = eng.forward(x, training=False, want_argmax=True)
+    if profiled:
+        check_ragged_routing(case, variant, eng.profile_end(), training=False)
     ref, cache = on.forward(cfg, p64, s64, on.preprocess_u8(images, np.float64), training=False)
     # layer-wise first: names the first diverging layer
     for li, spec in enumerate(on.build_plan(cfg)[:-1]):
@@ -154,11 +191,16 @@ def training_step_vs_oracle(cfg, eng, p64, s64, case, images, labels, macro, var
     assert np.array_equal(mask, dropout_keep_mask(100, DROP_STEP, mask.shape).astype(np.uint8))
     mask = mask.astype(np.float64)
     assert 0.3 < mask.mean() < 0.7
+    profiled = case in RAGGED and variant in PROFILED
+    if profiled:
+        eng.profile_begin()
     probs, _ = eng.forward(x, training=True, labels=lab)
     loss4_dev = eng.loss_dice()
     loss4 = loss4_dev.cpu().numpy()
     eng.backward(lab, macro=macro, loss_scale=0.5)
     torch.cuda.synchronize()
+    if profiled:
+        check_ragged_routing(case, variant, eng.profile_end(), training=True)
 
     xin = on.preprocess_u8(images, np.float64)
     ref, cache = on.forward(cfg, p64, s64, xin, training=True, dropout_mask=mask)
@@ -296,7 +338,8 @@ def assert_same_as_fresh_engine(eng, fresh, B, probs, probs_f, loss4, loss4_f):
 # (case, macro, max_batch): max_batch = B + 1 with the macro loss, 4 B with the micro loss, and one B = 1 step on an
 # engine for 3 -- the committed margin seeds stay valid (the margin is a property of the B images and the (B, ...)
 # dropout mask, not of max_batch)
-PARTIAL = [(c, True, c[0] + 1) for c in CASES] + [(c, False, 4 * c[0]) for c in CASES] + [(CASES[5], True, 3)]
+PARTIAL = [(c, True, c[0] + 1) for c in CASES[:7]] + [(c, False, 4 * c[0]) for c in CASES[:7]] + [(CASES[5], True, 3)]
+PARTIAL += [(c, True, c[0] + 1) for c in RAGGED] + [(c, False, 4 * c[0]) for c in RAGGED]     # (appended: the ids above stay)
 
 
 @pytest.mark.parametrize("case,macro,max_batch", PARTIAL)
@@ -478,6 +521,26 @@ def test_device_boundary_maps_match_reference_definition():
             assert np.array_equal(got, ref), kw
 
 
+@pytest.mark.parametrize("shape", [(3, 36, 68), (2, 496, 768)])
+def test_device_boundary_maps_at_sizes_off_the_launch_grid(shape):
+    """oct_boundary_maps at 36x68 and at the height of a real B-scan, 496x768 (B H W is no multiple of the block, and at
+    the second size the grid-stride loop wraps), bit-exact against the same numpy definition: smooth layered maps, random
+    maps, and steps at the first / last row and column."""
+    B, H, W = shape
+    cfg, eng, _, _ = make(1, 32, 64, 4, 8, 2, training=False)          # (the maps' size is the call's, not the engine's)
+    rng = np.random.default_rng(1)
+    _, smooth = on.synth_scans(B, H, W, 4, seed=8)
+    edge = np.zeros((B, H, W), np.uint8); edge[0, 1:, :] = 1; edge[1, :-1, :] = 2; edge[1, -1, :] = 3
+    edge[-1, :, 0] = 3; edge[-1, :, -1] = 1
+    for lab in (smooth[..., 0], rng.integers(0, 4, (B, H, W)).astype(np.uint8), edge):
+        cat = np.transpose(np.eye(4, dtype=np.float32)[lab], (0, 3, 1, 2))
+        for kw in (dict(bg_ilm=True, bg_csi=False), dict(bg_ilm=False, bg_csi=True), dict(bg_ilm=True, bg_csi=True)):
+            with np.errstate(invalid="ignore"):
+                ref = on.convert_predictions_to_maps_semantic(cat, **kw)
+            got = eng.boundary_maps(torch.from_numpy(np.ascontiguousarray(lab)).cuda(), **kw).cpu().numpy()
+            assert got.shape == (B, 3, H, W) and np.array_equal(got, ref), kw
+
+
 def test_hip_path_matches_committed_golden():
     """HIP path vs the COMMITTED fixture tests/golden/unet_golden.npz (fp64 oracle outputs; generating script
     committed next to it).  Tolerances as in the live-oracle tests."""
@@ -607,7 +670,7 @@ def test_focal_dice_loss_and_gradients_match_oracle(macro, cw):
 
 
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
-@pytest.mark.parametrize("geo", [(3, 40, 96, 3, 8, 3), (2, 32, 64, 4, 16, 2)])
+@pytest.mark.parametrize("geo", [(3, 40, 96, 3, 8, 3), (2, 32, 64, 4, 16, 2), (2, 36, 68, 3, 8, 2)])   # last: ragged at every level
 def test_bn_backward_on_load_equals_the_separate_pass(dtype, geo):
     """By default no block's dz is ever stored: the BN-backward transform dz = ga g' + gb z + gd is applied by the
     consumers of dz while they stage g' and z -- block 0 inside conv_dw_first_k (its only consumer; the image has no
@@ -656,9 +719,20 @@ def test_backward_weights_inside_the_backward_data_launch(dtype):
     products, another summation order: every gradient equals the separate-kernel route to fp32 accumulation accuracy (and
     both are checked against the oracle by the variant tests), the dW kernels of those layers are really gone, and
     everything else (backward-data results, BN statistics) is bit-identical."""
+    backward_weights_fused_vs_separate(dtype, 3, 40, 96)          # ragged against the 8 x 32 tile
+
+
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+def test_backward_weights_inside_the_backward_data_launch_at_36x68(dtype):
+    """The same at 36 x 68, pool_layers 2: neither the rows nor the width of any level (36x68, 18x34, 9x17) divide the
+    8 x 32 tile, so every block of the fused launches clamps its X loads into the image and masks its own pixels."""
+    backward_weights_fused_vs_separate(dtype, 2, 36, 68)
+
+
+def backward_weights_fused_vs_separate(dtype, B, H, W):
     from oct_image_segmentation_models_amd import _hip
     from oct_image_segmentation_models_amd.engine import UNetEngine
-    B, H, W, C = 3, 40, 96, 3                        # ragged against the 8 x 32 tile
+    C = 3
     images, labels = data(B, H, W, C, 1, seed=23)
     x = torch.from_numpy(images).cuda(); lab = torch.from_numpy(labels[..., 0].copy()).cuda()
     got, gbuf = {}, {}
@@ -785,7 +859,9 @@ def test_config3_shape_in_its_own_dtype_bf16():
 #      ReLU masks that the forward noise flips, cosine > 0.9 per kernel tensor and > 0.97 over the whole gradient
 #      (the layer-local test above is the one that pins every backward kernel to one rounding).
 BF16_CASES = [(2, 32, 64, 3, 8, 2, 2, 1), (1, 48, 80, 3, 8, 3, 1, 3), (1, 32, 64, 3, 8, 2, 2, 4), (1, 32, 64, 3, 32, 1, 2, 1),
-              (1, 32, 64, 3, 12, 2, 2, 1)]
+              (1, 32, 64, 3, 12, 2, 2, 1),
+              # the ragged geometries of CASES whose channel counts are multiples of 8 (bf16 MFMA operands on every layer but the first)
+              (2, 36, 68, 3, 8, 2, 2, 1), (1, 48, 80, 3, 8, 4, 2, 1), (1, 80, 24, 3, 16, 2, 2, 1)]
 
 
 def make_bf16(B, H, W, C, sn, P, L=2, in_ch=1, seed=0, max_batch=None):
@@ -807,7 +883,14 @@ def test_bf16_storage_layer_local_rounding_is_exact(case, variant):
     _hip.set_option("fuse_first_apply", 0); _hip.set_option("fuse_bn_apply", 0)   # this test reads EVERY block's STORED dz (the fused
     B, H, W, C, sn, P, L, ic = case               # route is pinned bit for bit against this one by the test below)
     cfg, eng, p64, s64 = make_bf16(B, H, W, C, sn, P, L, ic)
-    assert eng.workspace.numel() < 0.8 * make(B, H, W, C, sn, P, L, ic)[1].workspace.numel()   # partials stay fp32
+    # the stored z and gradient tensor of every block are 2 bytes per element smaller; partial slabs, records and prepared
+    # weights stay fp32
+    ws16, ws32 = eng.workspace.numel(), make(B, H, W, C, sn, P, L, ic)[1].workspace.numel()
+    act = sum(B * L_["out_h"] * L_["out_w"] * L_["cout"] for L_ in eng.layers[:-1])
+    assert ws32 - ws16 >= 4 * act
+    # (one geometry by name: on the 80 x 24 image with start_neurons 16 the stored activations are 4 act = 0.095 of an fp32
+    #  workspace of 64-channel dW slabs and prepared weights; the ratio there is 0.805 and only the exact saving is asserted)
+    assert ws16 < 0.8 * ws32 or case == (1, 80, 24, 3, 16, 2, 2, 1)
     images, labels = data(B, H, W, C, ic, seed=MARGIN_SEED.get(case, 5))
     bf16_step_layer_local(cfg, eng, p64, case, images, labels)
 
@@ -825,9 +908,7 @@ def bf16_step_layer_local(cfg, eng, p64, case, images, labels):
     zh = [eng.debug_activation(li, 0)[:B].cpu().numpy().astype(np.float64) for li in range(len(plan) - 1)]
 
     rec = [eng.debug_bn_record(li).cpu().numpy().astype(np.float64) for li in range(len(plan) - 1)]
-    for li in range(len(plan) - 1):      # the record itself: a = gamma*rstd, b = beta - a*mean, batch statistics of z
-        _, mean, var, rstd, _ = on.batchnorm_train(zh[li], p64[li]["gamma"], p64[li]["beta"], cfg.bn_eps)
-        assert np.allclose(rec[li][2], mean, atol=2e-4 * np.abs(zh[li]).max()) and np.allclose(rec[li][3], rstd, rtol=2e-3)
+    for li in range(len(plan) - 1):      # the record itself: a = gamma*rstd, b = beta - a*mean (its batch statistics: below)
         assert np.allclose(rec[li][0], p64[li]["gamma"] * rec[li][3], rtol=1e-5, atol=1e-7)
         assert np.allclose(rec[li][1], p64[li]["beta"] - rec[li][0] * rec[li][2], rtol=1e-5, atol=1e-6)
 
@@ -857,6 +938,12 @@ def bf16_step_layer_local(cfg, eng, p64, case, images, labels):
         else:
             z = on.conv2d_same(inp, p64[li]["kernel"], p64[li]["bias"])
         if spec.has_bn:
+            # the record's batch statistics: the engine takes them of its fp32 accumulators BEFORE it rounds z for the store,
+            # so they are those of this unrounded recomputation, not of the stored roundings (the two differ by the mean of
+            # N rounding errors: nothing at a full-size layer, 2x this bound over the 15 pixels of a 3 x 5 bottleneck, where
+            # a defect-free model of the engine misses it too -- tests/layer_local.py has the same rule)
+            _, mean, var, rstd, _ = on.batchnorm_train(z, p64[li]["gamma"], p64[li]["beta"], cfg.bn_eps)
+            assert np.allclose(rec[li][2], mean, atol=2e-4 * np.abs(zh[li]).max()) and np.allclose(rec[li][3], rstd, rtol=2e-3), spec.name
             err = np.abs(zh[li] - bf16_round(z))
             # + an absolute floor for cancelling sums near zero (the statistics differ by ~1e-5 relative)
             bound = 1.001 * bf16_ulp(z) + 5e-5 * np.abs(z).max()
@@ -920,7 +1007,8 @@ def bf16_step_layer_local(cfg, eng, p64, case, images, labels):
     return probs
 
 
-@pytest.mark.parametrize("case,max_batch", [(BF16_CASES[0], 3), (BF16_CASES[1], 4)])
+@pytest.mark.parametrize("case,max_batch", [(BF16_CASES[0], 3), (BF16_CASES[1], 4), (BF16_CASES[5], 3), (BF16_CASES[6], 4),
+                                            (BF16_CASES[7], 2)])
 def test_bf16_partial_training_step_on_a_used_engine(case, max_batch):
     """test_partial_training_step_on_a_used_engine in bf16 storage, default kernel selection: the partial step after a
     full one, held to the one-rounding checks of test_bf16_storage_layer_local_rounding_is_exact."""
