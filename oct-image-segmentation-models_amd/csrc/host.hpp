@@ -1,8 +1,8 @@
 // Host-side plumbing shared by the translation units of liboct_unet_hip.so: error channel, tuning options, the per-launch
-// HIP-event profiler and the signatures of the conv launchers.  The library is built from several .hip files compiled in
-// parallel (build.sh): oct_unet.hip holds the plan (build_plan / carve at creation, plan_backward per backward call), the
-// C ABI and the streaming kernels; tu_*.hip each instantiate one family of the MFMA conv kernels behind the launcher
-// declared here.
+// HIP-event profiler, the ONE shape rule that says which bf16-pipe kernel family can serve a conv launch (pipe_fit) and the
+// signatures of the conv launchers.  The library is built from several .hip files compiled in parallel (build.sh):
+// oct_unet.hip holds the plan (build_plan / carve at creation, plan_backward per backward call), the C ABI and the
+// streaming kernels; tu_*.hip each instantiate one family of the MFMA conv kernels behind the launcher declared here.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -101,17 +101,36 @@ inline bool bt_k_ok(int k) { return k == 8 || k == 16 || k == 32; }
 // what a conv launch needs besides its argument block
 struct LaunchCtx { const Options* o; int B; hipStream_t s; const char* layer; double flops, bytes; };
 
-// kernel family a conv launch is routed to (oct_unet.hip::conv_route, launch_igemm's dispatch).  The host asks the same
-// function about the argument block it is going to launch -- conv_forward for one launch, plan_backward once per
-// backward-data launch of a block, kept in its BwdRoute -- because only the bf16-pipe kernels can apply the BN-backward
-// transform on load and finalize statistics in the launch
+// kernel family a conv launch runs on
 enum ConvRoute { ROUTE_BT = 0, ROUTE_BX = 1, ROUTE_F32 = 2 };
+
+// THE shape rule: which bf16-pipe family can serve a conv launch of K channels into M output channels at channel offset
+// m_off of the weights' output dimension -- the thin kernel (ROUTE_BT: conv_bt_k, and whether its two-pixel form applies),
+// the wide one (ROUTE_BX: conv_bx_k) or neither (ROUTE_F32).  `two`: the input is a concat of two tensors, the first C0
+// channels wide.  Everything that needs the answer asks here: carve() about a layer's forward and backward-data launches
+// (which prepared weights exist), conv_route about an argument block (which kernel runs), launch_bt about the two-pixel form.
+struct PipeFit { ConvRoute fam; bool m2; };
+inline PipeFit pipe_fit(int K, int M, int m_off, bool two, int C0, int amode) {
+    const bool down2 = amode == oct::A_DOWN2;
+    if (two && C0 % 8) return {ROUTE_F32, false};          // staging moves 8-channel octets: one source tensor each
+    // thin: <= 16 output channels per launch, K exactly 8, 16 or 32 (the 2x-strided input tile only fits LDS at 8);
+    // two-pixel form: exactly 8 output channels, 8 or 16 K channels, not the stride-2 gather
+    if (M <= 16 && M % 4 == 0 && bt_k_ok(K) && (!down2 || K == 8)) return {ROUTE_BT, M == 8 && !down2 && K <= 16};
+    // wide: 32-channel output blocks, K in octets up to the affine rows the kernel caches in LDS
+    if (M % 32 == 0 && K % 8 == 0 && K <= (down2 ? 256 : 512) && m_off % bx_mb(M) == 0) return {ROUTE_BX, false};
+    return {ROUTE_F32, false};
+}
+
+// The route of one launch: the family pipe_fit names, if mfma_mode is on, its prepared weights exist and the input carries
+// no dropout the family cannot apply; else the fp32 pipe.  Asked ONCE per launch -- by conv_forward, and by plan_backward
+// for each backward-data launch of a block (DxLaunch::route) -- because only the bf16-pipe kernels can apply the
+// BN-backward transform on load and finalize statistics in the launch; launch_igemm is handed the answer.
 ConvRoute conv_route(const oct::IgemmArgs& a, int amode, const Options& o);
 
 // MFMA conv launchers (forward and backward-data); *rows = statistic partial rows the launch writes.
 // Defined in launch_conv.hpp, instantiated one per tu_conv_*.hip.
 template <int KH, int AMODE, int EPI>
-int launch_igemm(const oct::IgemmArgs& a, const LaunchCtx& c, int* rows);
+int launch_igemm(const oct::IgemmArgs& a, ConvRoute r, const LaunchCtx& c, int* rows);
 
 // Backward-weights plan of a layer (oct_unet.hip::dw_plan): the kernel family, its channel chunking, pixel-tile height,
 // pixel-block count.  MFMA launchers: launch_dw.hpp, instantiated in tu_dw_*.hip.

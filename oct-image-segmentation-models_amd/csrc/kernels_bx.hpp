@@ -958,6 +958,10 @@ static __global__ __launch_bounds__(kBlock) void prep_wbt_k(const WbtDesc* __res
 __host__ inline int wbt_groups(int KH, int CT, bool m2 = false) { const int tpm = 32 / CT; return (KH * (m2 ? KH + 1 : KH) + tpm - 1) / tpm; }
 __host__ inline size_t wbt_bytes(int KH, int CT, int NS, bool m2 = false) { return (size_t)wbt_groups(KH, CT, m2) * NS * 16 * 32 * 2; }
 
+// Blocks per CU of conv_bt_k: what the LDS images and registers of the (CT, FDW) instantiation allow -- the kernel's launch bounds and
+// the persistent grid of its launcher (launch_bt).
+constexpr int bt_per_cu(int CT, bool FDW) { return FDW ? 2 : (CT == 32 ? 1 : (CT == 16 ? 2 : 3)); }
+
 // GB (backward-data launches): x0 is the masked gradient g' of the layer; dz = ga g' + gb z + gd is formed while the tile is
 // staged (A.gb_z, A.gb_bn; common.hpp) -- the stand-alone bn_bwd_apply pass over g' is gone.
 //
@@ -971,7 +975,7 @@ __host__ inline size_t wbt_bytes(int KH, int CT, int NS, bool m2 = false) { retu
 // backward-weights kernel of these layers (3 more tensor passes over the largest tensors of the net) is gone.
 // One partial slab per block, like conv_dwbt_k (A.dw_part; reduce_all_k sums them); two blocks per CU.
 template <int KH, int AMODE, int EPI, int CT, int NS, typename AT, bool M2 = false, bool GB = false, bool FDW = false>
-__global__ __launch_bounds__(kBlock, FDW ? 2 : (CT == 32 ? 1 : (CT == 16 ? 2 : 3))) void conv_bt_k(const IgemmArgs A) {
+__global__ __launch_bounds__(kBlock, bt_per_cu(CT, FDW)) void conv_bt_k(const IgemmArgs A) {
     static_assert(!GB || EPI != EPI_FWD, "the BN-backward transform on load belongs to backward-data launches");
     static_assert(!FDW || (GB && CT == 8 && KH == 3 && AMODE == A_NORMAL), "fused backward-weights: 3x3, 8 K channels, transform on load");
     static_assert(!M2 || ((CT == 8 || CT == 16) && AMODE != A_DOWN2), "two-pixel form: 8 or 16 K channels, unit-stride or upsampled input");

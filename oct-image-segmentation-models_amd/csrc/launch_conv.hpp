@@ -1,5 +1,5 @@
-// Launchers of the MFMA conv kernels (forward and backward-data): pick the kernel family from the channel counts and the
-// pixel tile from the grid size.  Included by the tu_conv_*.hip files, each of which instantiates launch_igemm for one
+// Launchers of the MFMA conv kernels (forward and backward-data): launch_igemm runs the kernel family its caller routed
+// the launch to (host.hpp: conv_route) and picks the pixel tile from the grid size.  Included by the tu_conv_*.hip files, each of which instantiates launch_igemm for one
 // (kernel size, addressing mode, epilogue) triple -- the device code of those instantiations is most of the library's
 // compile time, so they are built in parallel.
 #pragma once
@@ -156,11 +156,11 @@ template <int KH, int AMODE, int EPI>
 int launch_bt(IgemmArgs a, const LaunchCtx& c, int* rows) {
     a.tiles_x = cdiv(a.Wo, 32); a.tiles = a.tiles_x * cdiv(a.Ho, 8); a.total_tiles = c.B * a.tiles;
     const bool fdw = a.dw_part != nullptr;                          // the launch also reduces the layer's backward-weights (FDW)
-    const int per_cu = fdw ? 2 : (a.Cin == 32 ? 1 : (a.Cin == 16 ? 2 : 3));     // what the LDS images and registers of the instantiation allow
+    const int per_cu = bt_per_cu(a.Cin, fdw);                       // the instantiation's __launch_bounds__
     const int want = c.o->bt_blocks_per_cu;
     const int nblk = std::min(a.total_tiles, want > 0 ? 256 * std::min(want, per_cu) : 256 * per_cu);
     const int bf = a.act_bf16 ? 1 : 0;
-    const bool m2 = a.bt_m2 && a.Mout == 8 && AMODE != A_DOWN2 && (a.Cin == 8 || a.Cin == 16);
+    const bool m2 = a.bt_m2 && pipe_fit(a.Cin, a.Mout, a.m_off, a.flags & F_TWO, a.C0, AMODE).m2;
     const bool gb = a.gb_z != nullptr;
     char nm[72]; snprintf(nm, sizeof nm, "conv_bt_k<%d,%d,%d,%d,%d,%s%s%s%s>", KH, AMODE, EPI, a.Cin, bf ? 1 : 3, AT_NAME(bf), m2 ? ",2px" : "", gb ? ",gb" : "", fdw ? ",dw" : "");
     ProfScope ps(c.s, nm, c.layer, c.flops, c.bytes);
@@ -208,8 +208,7 @@ int launch_bt(IgemmArgs a, const LaunchCtx& c, int* rows) {
 }
 
 template <int KH, int AMODE, int EPI>
-int launch_igemm(const IgemmArgs& a, const LaunchCtx& c, int* rows) {
-    const ConvRoute r = conv_route(a, AMODE, *c.o);
+int launch_igemm(const IgemmArgs& a, ConvRoute r, const LaunchCtx& c, int* rows) {
     if (r == ROUTE_BT) return launch_bt<KH, AMODE, EPI>(a, c, rows);
     if (r == ROUTE_BX) return launch_bx<KH, AMODE, EPI>(a, c, rows);
     if (a.gb_z) return fail(-3, "fp32-pipe conv kernels do not apply the BN-backward transform on load");

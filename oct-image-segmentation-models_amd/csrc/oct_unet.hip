@@ -6,7 +6,9 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/oct_unet.h"
@@ -30,21 +32,17 @@ namespace { thread_local std::string g_err; }
 int fail(int code, const std::string& msg) { g_err = msg; return code; }
 
 // the conv launchers live in their own translation units (tu_conv_*.hip): one explicit instantiation each
-extern template int launch_igemm<3, A_NORMAL, EPI_FWD>(const IgemmArgs&, const LaunchCtx&, int*);
-extern template int launch_igemm<2, A_UPF, EPI_FWD>(const IgemmArgs&, const LaunchCtx&, int*);
-extern template int launch_igemm<3, A_NORMAL, EPI_MASK>(const IgemmArgs&, const LaunchCtx&, int*);
-extern template int launch_igemm<3, A_NORMAL, EPI_RAW>(const IgemmArgs&, const LaunchCtx&, int*);
-extern template int launch_igemm<3, A_DOWN2, EPI_MASK>(const IgemmArgs&, const LaunchCtx&, int*);
+extern template int launch_igemm<3, A_NORMAL, EPI_FWD>(const IgemmArgs&, ConvRoute, const LaunchCtx&, int*);
+extern template int launch_igemm<2, A_UPF, EPI_FWD>(const IgemmArgs&, ConvRoute, const LaunchCtx&, int*);
+extern template int launch_igemm<3, A_NORMAL, EPI_MASK>(const IgemmArgs&, ConvRoute, const LaunchCtx&, int*);
+extern template int launch_igemm<3, A_NORMAL, EPI_RAW>(const IgemmArgs&, ConvRoute, const LaunchCtx&, int*);
+extern template int launch_igemm<3, A_DOWN2, EPI_MASK>(const IgemmArgs&, ConvRoute, const LaunchCtx&, int*);
 
-// which kernel family launch_igemm (launch_conv.hpp) hands a launch to
+// which kernel family runs a launch (host.hpp)
 ConvRoute conv_route(const IgemmArgs& a, int amode, const Options& o) {
-    const bool octets_ok = !(a.flags & F_TWO) || a.C0 % 8 == 0;    // staging moves 8-channel octets: one source tensor each
-    if (o.mfma_mode && a.wbt && a.Mout <= 16 && a.Mout % 4 == 0 && bt_k_ok(a.Cin) && !(a.flags & F_DROP) && octets_ok &&
-        (amode != A_DOWN2 || a.Cin == 8))
-        return ROUTE_BT;
-    if (o.mfma_mode && a.wbx && a.Mout % 32 == 0 && a.Cin % 8 == 0 && a.m_off % bx_mb(a.Mout) == 0 && octets_ok &&
-        a.Cin <= (amode == A_DOWN2 ? 256 : 512))       // the kernel caches the affine rows of its K channels in LDS
-        return ROUTE_BX;
+    const ConvRoute f = pipe_fit(a.Cin, a.Mout, a.m_off, a.flags & F_TWO, a.C0, amode).fam;
+    if (o.mfma_mode && f == ROUTE_BT && a.wbt && !(a.flags & F_DROP)) return ROUTE_BT;    // (conv_bt_k applies no dropout)
+    if (o.mfma_mode && f == ROUTE_BX && a.wbx) return ROUTE_BX;
     return ROUTE_F32;
 }
 }  // namespace octh
@@ -150,19 +148,22 @@ inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 inline int tiles_of(int H, int W) { return cdiv(H, kTileY) * cdiv(W, kTileX); }
 inline int chunk_of(int c) { return c % 16 == 0 ? 16 : (c % 8 == 0 ? 8 : 4); }   // channel chunk per thread
 
-// ---- bf16-pipe kernel eligibility (kernels_bx.hpp): forward needs >= 32 output channels, backward-data >= 32 channels
-// per launch (a concat's dX is two launches of cin/2 channels each); K channels in multiples of 8, <= 512 ----
-inline bool bx_fwd_ok(const Layer& l) { return l.src != SRC_INPUT && l.has_bn && l.cin % 8 == 0 && l.cin <= 512 && l.cout % 32 == 0; }
-inline int bx_bwd_cg(const Layer& l) { return l.src == SRC_CONCAT ? l.cin / 2 : l.cin; }
-inline bool bx_bwd_ok(const Layer& l) { return l.src != SRC_INPUT && l.has_bn && l.cout % 8 == 0 && l.cout <= 512 && bx_bwd_cg(l) % 32 == 0; }
-
-// thin bf16-pipe kernel (conv_bt_k): <= 16 output channels per launch, K channels exactly 8, 16 or 32
-inline bool bt_fwd_ok(const Layer& l) { return l.src != SRC_INPUT && l.has_bn && l.cout <= 16 && l.cout % 4 == 0 && bt_k_ok(l.cin); }
-inline bool bt_bwd_ok(const Layer& l) { const int cg = bx_bwd_cg(l); return l.src != SRC_INPUT && l.has_bn && cg <= 16 && cg % 4 == 0 && bt_k_ok(l.cout); }
-
-// two-pixel form of the thin kernel: exactly 8 output channels per launch, 8 or 16 K channels, not the stride-2 gather
-inline bool bt_m2_fwd(const Layer& l, const Options& o) { return o.bt_m2 && bt_fwd_ok(l) && l.cout == 8 && (l.cin == 8 || l.cin == 16); }
-inline bool bt_m2_bwd(const Layer& l, const Options& o) { return o.bt_m2 && bt_bwd_ok(l) && l.src != SRC_UP && bx_bwd_cg(l) == 8 && (l.cout == 8 || l.cout == 16); }
+// ---- the shape rule (host.hpp: pipe_fit) asked about a layer's own conv launches: which prepared bf16 weights can be read.
+// Forward: one launch of cin -> cout channels.  Backward-data: cout -> Cg channels at a time -- a concat's dX is two
+// launches of cin / 2 channels each (the skip half at offset cin / 2, the up-path half at 0), an up-conv's the stride-2 gather ----
+inline bool mfma_conv(const Layer& l) { return l.src != SRC_INPUT && l.has_bn; }   // not the image layer, not the head
+inline int bwd_cg(const Layer& l) { return l.src == SRC_CONCAT ? l.cin / 2 : l.cin; }
+inline PipeFit fit_fwd(const Layer& l) {
+    if (!mfma_conv(l)) return {ROUTE_F32, false};
+    return pipe_fit(l.cin, l.cout, 0, l.src == SRC_CONCAT, l.cin / 2, l.src == SRC_UP ? A_UPF : A_NORMAL);
+}
+inline PipeFit fit_bwd(const Layer& l) {
+    PipeFit f{ROUTE_F32, false};
+    if (!mfma_conv(l)) return f;
+    for (int off = 0; off < l.cin && f.fam == ROUTE_F32; off += bwd_cg(l))      // (prepared if any of the launches can read them)
+        f = pipe_fit(l.cout, bwd_cg(l), off, false, 0, l.src == SRC_UP ? A_DOWN2 : A_NORMAL);
+    return f;
+}
 
 // thin backward-weights on the bf16 pipe (conv_dwbt_k): the instantiated (cin, cout) pairs
 inline bool dwbt_ok(const Layer& l) {
@@ -279,11 +280,13 @@ size_t carve(const oct_unet_cfg& c, Plan& pl, oct_unet* h, char* base, const Opt
         float* bn = l.has_bn ? (float*)take((size_t)BN_ARRAYS * l.cout * 4) : nullptr;
         float* wt = (c.training && l.has_bn && l.src != SRC_INPUT) ? (float*)take((size_t)9 * l.cin * l.cout * 4) : nullptr;
         const int ns = c.dtype ? 1 : 3;
-        bf16_t* wf = bx_fwd_ok(l) ? (bf16_t*)take(wbx_bytes(l.kh, l.cin, l.cout, bx_mb(l.cout), ns)) : nullptr;
-        bf16_t* wb = (c.training && bx_bwd_ok(l)) ? (bf16_t*)take(wbx_bytes(3, l.cout, l.cin, bx_mb(bx_bwd_cg(l)), ns)) : nullptr;
-        const bool m2f = bt_m2_fwd(l, o), m2b = bt_m2_bwd(l, o);
-        bf16_t* tf = bt_fwd_ok(l) ? (bf16_t*)take(wbt_bytes(l.kh, l.cin, ns, m2f)) : nullptr;
-        bf16_t* tb = (c.training && bt_bwd_ok(l)) ? (bf16_t*)take(wbt_bytes(3, l.cout, ns, m2b) * (l.cin / bx_bwd_cg(l))) : nullptr;
+        // prepared bf16 weights: exactly those a launch of this layer can be routed to
+        const PipeFit ff = fit_fwd(l), fb = c.training ? fit_bwd(l) : PipeFit{ROUTE_F32, false};
+        const bool m2f = o.bt_m2 && ff.m2, m2b = o.bt_m2 && fb.m2;
+        bf16_t* wf = ff.fam == ROUTE_BX ? (bf16_t*)take(wbx_bytes(l.kh, l.cin, l.cout, bx_mb(l.cout), ns)) : nullptr;
+        bf16_t* wb = fb.fam == ROUTE_BX ? (bf16_t*)take(wbx_bytes(3, l.cout, l.cin, bx_mb(bwd_cg(l)), ns)) : nullptr;
+        bf16_t* tf = ff.fam == ROUTE_BT ? (bf16_t*)take(wbt_bytes(l.kh, l.cin, ns, m2f)) : nullptr;
+        bf16_t* tb = fb.fam == ROUTE_BT ? (bf16_t*)take(wbt_bytes(3, l.cout, ns, m2b) * (l.cin / bwd_cg(l))) : nullptr;
         if (base) { l.bt_m2_f = m2f; l.bt_m2_b = m2b; }
         if (base) { l.z = z; l.g = g; l.bn = bn; l.wt = wt; l.wbx_f = wf; l.wbx_b = wb; l.wbt_f = tf; l.wbt_b = tb; }
         // statistic partial rows: one per pixel tile; the MFMA kernels may use tiles as small as 2 x 32 pixels
@@ -413,9 +416,10 @@ int conv_forward(oct_unet* h, int li, const void* x_in, int x_is_u8, int B, int 
         g.part = a.part; g.drop = a.drop; g.act_bf16 = h->cfg.dtype;
         g.wbx = l.wbx_f; g.wbx_M = l.cout; g.wbt = l.wbt_f; g.bt_m2 = l.bt_m2_f;
         const LaunchCtx lc{&h->opt, B, s, l.name, fl, by};
-        if (training && fin_ok(h, l) && conv_route(g, l.src == SRC_UP ? A_UPF : A_NORMAL, h->opt) == ROUTE_BT) { g.fin = fin_desc(h, li, 0, B); fin_in_launch = true; }
-        rc = l.src == SRC_UP ? launch_igemm<2, A_UPF, EPI_FWD>(g, lc, &stat_rows)
-                             : launch_igemm<3, A_NORMAL, EPI_FWD>(g, lc, &stat_rows);
+        const ConvRoute rt = conv_route(g, l.src == SRC_UP ? A_UPF : A_NORMAL, h->opt);
+        if (training && fin_ok(h, l) && rt == ROUTE_BT) { g.fin = fin_desc(h, li, 0, B); fin_in_launch = true; }
+        rc = l.src == SRC_UP ? launch_igemm<2, A_UPF, EPI_FWD>(g, rt, lc, &stat_rows)
+                             : launch_igemm<3, A_NORMAL, EPI_FWD>(g, rt, lc, &stat_rows);
     } else if (l.src == SRC_INPUT && l.cin == 1 && l.cout == 8 && l.kh == 3) {   // the real first layer: persistent streaming kernel
         const int tx = cdiv(l.W, 128), tiles = tx * cdiv(l.H, 8), total = B * tiles;
         const int grid = std::min(total, 2048);      // <= B*ceil(H/2)*ceil(W/32) statistic rows guaranteed by carve()
@@ -444,23 +448,24 @@ int conv_forward(oct_unet* h, int li, const void* x_in, int x_is_u8, int B, int 
     return 0;
 }
 
+// the head kernels are instantiated for every start_neurons (= the head's input channels): run f(constant cin)
+template <typename F>
+int head_cin_dispatch(int cin, F f) {
+    switch (cin) {
+#define HEAD_CIN(N) case N: f(std::integral_constant<int, N>{}); return 0;
+        HEAD_CIN(4) HEAD_CIN(8) HEAD_CIN(16) HEAD_CIN(12) HEAD_CIN(20) HEAD_CIN(24) HEAD_CIN(28) HEAD_CIN(32)
+#undef HEAD_CIN
+        default: return fail(-3, "head: unsupported start_neurons");
+    }
+}
+
 template <int C>
 int launch_head_fwd(const HeadFwdArgs& a, int cin, int B, hipStream_t s) {
     dim3 grid(a.nblk, B), block(kBlock);
     const double px = (double)B * a.HW;
     char nm[64]; snprintf(nm, sizeof nm, "head_fwd_k<%d,%d,%s>", C, cin, AT_NAME(a.act_bf16));
     ProfScope ps(s, nm, "head", 2.0 * cin * C * px, px * (cin * 4 + (a.probs ? C * 4 : 0) + (a.argmax ? 1 : 0) + (a.labels ? 1 : 0)));
-    switch (cin) {
-        case 4: AT_DISPATCH(a.act_bf16, head_fwd_k<C, 4, AT><<<grid, block, 0, s>>>(a)); break;
-        case 8: AT_DISPATCH(a.act_bf16, head_fwd_k<C, 8, AT><<<grid, block, 0, s>>>(a)); break;
-        case 16: AT_DISPATCH(a.act_bf16, head_fwd_k<C, 16, AT><<<grid, block, 0, s>>>(a)); break;
-        case 12: AT_DISPATCH(a.act_bf16, head_fwd_k<C, 12, AT><<<grid, block, 0, s>>>(a)); break;
-        case 20: AT_DISPATCH(a.act_bf16, head_fwd_k<C, 20, AT><<<grid, block, 0, s>>>(a)); break;
-        case 24: AT_DISPATCH(a.act_bf16, head_fwd_k<C, 24, AT><<<grid, block, 0, s>>>(a)); break;
-        case 28: AT_DISPATCH(a.act_bf16, head_fwd_k<C, 28, AT><<<grid, block, 0, s>>>(a)); break;
-        case 32: AT_DISPATCH(a.act_bf16, head_fwd_k<C, 32, AT><<<grid, block, 0, s>>>(a)); break;
-        default: return fail(-3, "head: unsupported start_neurons");
-    }
+    if (int rc = head_cin_dispatch(cin, [&](auto ci) { AT_DISPATCH(a.act_bf16, head_fwd_k<C, decltype(ci)::value, AT><<<grid, block, 0, s>>>(a)); })) return rc;
     HIP_OK(hipGetLastError());
     return 0;
 }
@@ -471,17 +476,7 @@ int launch_head_bwd(const HeadBwdArgs& a, int cin, int B, hipStream_t s) {
     const double px = (double)B * a.HW;
     char nm[64]; snprintf(nm, sizeof nm, "head_bwd_k<%d,%d,%s>", C, cin, AT_NAME(a.act_bf16));
     ProfScope ps(s, nm, "head", 6.0 * cin * C * px, px * (cin * 4 * 2 + 1));
-    switch (cin) {
-        case 4: AT_DISPATCH(a.act_bf16, head_bwd_k<C, 4, AT><<<grid, block, 0, s>>>(a)); break;
-        case 8: AT_DISPATCH(a.act_bf16, head_bwd_k<C, 8, AT><<<grid, block, 0, s>>>(a)); break;
-        case 16: AT_DISPATCH(a.act_bf16, head_bwd_k<C, 16, AT><<<grid, block, 0, s>>>(a)); break;
-        case 12: AT_DISPATCH(a.act_bf16, head_bwd_k<C, 12, AT><<<grid, block, 0, s>>>(a)); break;
-        case 20: AT_DISPATCH(a.act_bf16, head_bwd_k<C, 20, AT><<<grid, block, 0, s>>>(a)); break;
-        case 24: AT_DISPATCH(a.act_bf16, head_bwd_k<C, 24, AT><<<grid, block, 0, s>>>(a)); break;
-        case 28: AT_DISPATCH(a.act_bf16, head_bwd_k<C, 28, AT><<<grid, block, 0, s>>>(a)); break;
-        case 32: AT_DISPATCH(a.act_bf16, head_bwd_k<C, 32, AT><<<grid, block, 0, s>>>(a)); break;
-        default: return fail(-3, "head: unsupported start_neurons");
-    }
+    if (int rc = head_cin_dispatch(cin, [&](auto ci) { AT_DISPATCH(a.act_bf16, head_bwd_k<C, decltype(ci)::value, AT><<<grid, block, 0, s>>>(a)); })) return rc;
     HIP_OK(hipGetLastError());
     return 0;
 }
@@ -675,7 +670,7 @@ int plan_backward(oct_unet* h, int B) {
         for (int i = 0; i < r.n_dx; ++i) { all_bf16 = all_bf16 && r.dx[i].route != ROUTE_F32; all_bt = all_bt && r.dx[i].route == ROUTE_BT; }
         const ConvRoute r0 = r.dx[r.n_dx - 1].route;      // the launch at channel offset 0 (a concat's halves have the same K and Cg)
         const bool up = l.src == SRC_UP;
-        const int cg = bx_bwd_cg(l);
+        const int cg = bwd_cg(l);
         // (three bf16-pipe instantiations stay out: the stride-2 gather beyond the coefficient rows its LDS holds; the
         //  thin kernel at 32 K channels, whose staging registers for g' AND z no longer fit; and the thin kernel at 16 K
         //  channels with 16 output channels, where the second raw register set spills under the 256-register budget of two
@@ -815,9 +810,9 @@ int launch_dx(oct_unet* h, int li, const DxLaunch& d, int B, hipStream_t s, int*
     if (d.prod && fin_ok(h, *d.prod) && d.route == ROUTE_BT) {
         g.fin = fin_desc(h, (int)(d.prod - h->plan.L.data()), 1, B); *fin = true;
     }
-    if (d.up) return launch_igemm<3, A_DOWN2, EPI_MASK>(g, lc, rows);
-    return d.prod ? launch_igemm<3, A_NORMAL, EPI_MASK>(g, lc, rows)
-                  : launch_igemm<3, A_NORMAL, EPI_RAW>(g, lc, rows);
+    if (d.up) return launch_igemm<3, A_DOWN2, EPI_MASK>(g, d.route, lc, rows);
+    return d.prod ? launch_igemm<3, A_NORMAL, EPI_MASK>(g, d.route, lc, rows)
+                  : launch_igemm<3, A_NORMAL, EPI_RAW>(g, d.route, lc, rows);
 }
 
 // max-pool backward in front of block li: routes the raw gradient wrt the pooled tensor into block li-1, masked, and emits
@@ -939,6 +934,68 @@ int backward_impl(oct_unet* h, const void* x_in, int x_is_u8, const unsigned cha
     return flush_reduce(h, s);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// creation: the descriptor lists of the weight-preparation kernels, one entry per prepared buffer carve() handed out
+// ---------------------------------------------------------------------------------------------------------------
+template <typename T>
+int upload(T* dst, const std::vector<T>& v, const char* what) {
+    if (v.empty()) return 0;
+    const hipError_t e = hipMemcpy(dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+    return e == hipSuccess ? 0 : fail(-5, std::string("hipMemcpy(") + what + "): " + hipGetErrorString(e));
+}
+
+// transposed / effective fp32 backward-data weights (prep_wt_k)
+int build_wt_descs(oct_unet* h) {
+    std::vector<WtDesc> d;
+    unsigned off = 0;
+    for (auto& l : h->plan.L) {
+        if (!l.wt) continue;
+        WtDesc w{}; w.w = h->params + l.w_off; w.wt = l.wt; w.kh = l.kh; w.cin = l.cin; w.cout = l.cout;
+        w.mode = l.kh == 3 ? 0 : 1; w.start = off; w.count = 9u * l.cin * l.cout;
+        off += w.count; d.push_back(w);
+    }
+    h->n_wt = (int)d.size(); h->wt_total = off;
+    return upload(h->wt_descs, d, "wt_descs");
+}
+
+// split weights of the wide bf16-pipe kernel (prep_wbx_k): forward entries first, then backward-data entries
+int build_wbx_descs(oct_unet* h) {
+    std::vector<WbxDesc> d;
+    const int ns = h->cfg.dtype ? 1 : 3;
+    auto add = [&](const float* src, bf16_t* dst, int KH, int Kc, int M, int MB, unsigned* off) {
+        WbxDesc w{}; w.src = src; w.dst = dst; w.KH = KH; w.Kc = Kc; w.M = M; w.ld = M; w.MB = MB; w.NS = ns; w.start = *off;
+        w.count = (unsigned)(((Kc + 15) / 16) * ((M + MB - 1) / MB) * KH * KH * MB * 2);
+        *off += w.count; d.push_back(w);
+    };
+    for (auto& l : h->plan.L) if (l.wbx_f) add(h->params + l.w_off, l.wbx_f, l.kh, l.cin, l.cout, bx_mb(l.cout), &h->wbx_f_total);
+    h->n_wbx_f = (int)d.size();
+    for (auto& l : h->plan.L) if (l.wbx_b) add(l.wt, l.wbx_b, 3, l.cout, l.cin, bx_mb(bwd_cg(l)), &h->wbx_b_total);
+    h->n_wbx_b = (int)d.size() - h->n_wbx_f;
+    return upload(h->wbx_descs, d, "wbx_descs");
+}
+
+// weight slices of the thin bf16-pipe kernel (prep_wbt_k): forward entries first, then backward-data entries (one per
+// launch: Cg output channels at offset m_off)
+int build_wbt_descs(oct_unet* h) {
+    std::vector<WbtDesc> d;
+    const int ns = h->cfg.dtype ? 1 : 3;
+    auto add = [&](const float* src, bf16_t* dst, int KH, int Kc, int M, int m_off, bool m2, unsigned* off) {
+        WbtDesc w{}; w.src = src; w.dst = dst; w.KH = KH; w.Kc = Kc; w.M = M; w.ld = M; w.m_off = m_off; w.CT = Kc; w.NS = ns; w.m2 = m2;
+        w.start = *off; w.count = (unsigned)wbt_groups(KH, Kc, m2) * 64;
+        *off += w.count; d.push_back(w);
+    };
+    for (auto& l : h->plan.L) if (l.wbt_f) add(h->params + l.w_off, l.wbt_f, l.kh, l.cin, l.cout, 0, l.bt_m2_f, &h->wbt_f_total);
+    h->n_wbt_f = (int)d.size();
+    for (auto& l : h->plan.L) {
+        if (!l.wbt_b) continue;
+        const int cg = bwd_cg(l);
+        for (int sl = 0; sl < l.cin / cg; ++sl)
+            add(l.wt, l.wbt_b + (size_t)sl * (wbt_bytes(3, l.cout, ns, l.bt_m2_b) / 2), 3, l.cout, l.cin, sl * cg, l.bt_m2_b, &h->wbt_b_total);
+    }
+    h->n_wbt_b = (int)d.size() - h->n_wbt_f;
+    return upload(h->wbt_descs, d, "wbt_descs");
+}
+
 }  // namespace
 
 // =================================================================================================================
@@ -990,90 +1047,25 @@ int oct_unet_create(const oct_unet_cfg* c, float* params, float* grads, float* s
     if (int rc = check_cfg(c)) return rc;
     if (!out || !params || !state || !ws) return fail(-1, "null pointer argument");
     if (c->training && !grads) return fail(-1, "training handle needs a grads buffer");
-    oct_unet* h = new oct_unet();
+    std::unique_ptr<oct_unet, void (*)(oct_unet*)> own(new oct_unet(), oct_unet_destroy);   // every error path below frees it
+    oct_unet* h = own.get();
     h->cfg = *c; h->plan = build_plan(*c); h->opt = g_opt;
     h->params = params; h->grads = grads; h->state = state;
     const size_t need = carve(*c, h->plan, nullptr, nullptr, h->opt);
-    if (ws_bytes < need) { delete h; return fail(-4, "workspace too small: need " + std::to_string(need) + " bytes"); }
-    if (((uintptr_t)ws & 255) || ((uintptr_t)params & 15) || ((uintptr_t)state & 15) || (grads && ((uintptr_t)grads & 15))) {
-        delete h; return fail(-1, "buffers must be aligned (workspace 256 B, params/grads/state 16 B)");
-    }
+    if (ws_bytes < need) return fail(-4, "workspace too small: need " + std::to_string(need) + " bytes");
+    if (((uintptr_t)ws & 255) || ((uintptr_t)params & 15) || ((uintptr_t)state & 15) || (grads && ((uintptr_t)grads & 15)))
+        return fail(-1, "buffers must be aligned (workspace 256 B, params/grads/state 16 B)");
     carve(*c, h->plan, h, (char*)ws, h->opt);
     h->route.resize(h->plan.L.size());
-    if (c->training) {
-        std::vector<WtDesc> d;
-        unsigned off = 0;
-        for (auto& l : h->plan.L) {
-            if (!l.wt) continue;
-            WtDesc w{}; w.w = params + l.w_off; w.wt = l.wt; w.kh = l.kh; w.cin = l.cin; w.cout = l.cout;
-            w.mode = l.kh == 3 ? 0 : 1; w.start = off; w.count = 9u * l.cin * l.cout;
-            off += w.count; d.push_back(w);
-        }
-        h->n_wt = (int)d.size(); h->wt_total = off;
-        hipError_t e = hipMemcpy(h->wt_descs, d.data(), d.size() * sizeof(WtDesc), hipMemcpyHostToDevice);
-        if (e != hipSuccess) { delete h; return fail(-5, std::string("hipMemcpy(wt_descs): ") + hipGetErrorString(e)); }
-    }
-    {   // split-weight descriptors: forward entries first, then backward-data entries
-        std::vector<WbxDesc> d;
-        const int ns = c->dtype ? 1 : 3;
-        auto items = [](int KH, int Kc, int M, int MB) { return (unsigned)(((Kc + 15) / 16) * ((M + MB - 1) / MB) * KH * KH * MB * 2); };
-        unsigned off = 0;
-        for (auto& l : h->plan.L) {
-            if (!l.wbx_f) continue;
-            WbxDesc w{}; w.src = params + l.w_off; w.dst = l.wbx_f; w.KH = l.kh; w.Kc = l.cin; w.M = l.cout; w.ld = l.cout;
-            w.MB = bx_mb(l.cout); w.NS = ns; w.start = off; w.count = items(w.KH, w.Kc, w.M, w.MB);
-            off += w.count; d.push_back(w);
-        }
-        h->n_wbx_f = (int)d.size(); h->wbx_f_total = off;
-        off = 0;
-        for (auto& l : h->plan.L) {
-            if (!l.wbx_b) continue;
-            WbxDesc w{}; w.src = l.wt; w.dst = l.wbx_b; w.KH = 3; w.Kc = l.cout; w.M = l.cin; w.ld = l.cin;
-            w.MB = bx_mb(bx_bwd_cg(l)); w.NS = ns; w.start = off; w.count = items(3, w.Kc, w.M, w.MB);
-            off += w.count; d.push_back(w);
-        }
-        h->n_wbx_b = (int)d.size() - h->n_wbx_f; h->wbx_b_total = off;
-        if (!d.empty()) {
-            hipError_t e = hipMemcpy(h->wbx_descs, d.data(), d.size() * sizeof(WbxDesc), hipMemcpyHostToDevice);
-            if (e != hipSuccess) { delete h; return fail(-5, std::string("hipMemcpy(wbx_descs): ") + hipGetErrorString(e)); }
-        }
-    }
-    {   // thin-kernel weight slices: forward entries first, then backward-data entries (one per 16-row slice)
-        std::vector<WbtDesc> d;
-        const int ns = c->dtype ? 1 : 3;
-        unsigned off = 0;
-        for (auto& l : h->plan.L) {
-            if (!l.wbt_f) continue;
-            WbtDesc w{}; w.src = params + l.w_off; w.dst = l.wbt_f; w.KH = l.kh; w.Kc = l.cin; w.M = l.cout; w.ld = l.cout;
-            w.m_off = 0; w.CT = l.cin; w.NS = ns; w.m2 = l.bt_m2_f; w.start = off; w.count = (unsigned)wbt_groups(l.kh, l.cin, l.bt_m2_f) * 64;
-            off += w.count; d.push_back(w);
-        }
-        h->n_wbt_f = (int)d.size(); h->wbt_f_total = off;
-        off = 0;
-        for (auto& l : h->plan.L) {
-            if (!l.wbt_b) continue;
-            const int cg = bx_bwd_cg(l);
-            for (int sl = 0; sl < l.cin / cg; ++sl) {
-                WbtDesc w{}; w.src = l.wt; w.dst = l.wbt_b + (size_t)sl * (wbt_bytes(3, l.cout, ns, l.bt_m2_b) / 2); w.KH = 3; w.Kc = l.cout;
-                w.M = l.cin; w.ld = l.cin; w.m_off = sl * cg; w.CT = l.cout; w.NS = ns; w.m2 = l.bt_m2_b; w.start = off;
-                w.count = (unsigned)wbt_groups(3, l.cout, l.bt_m2_b) * 64;
-                off += w.count; d.push_back(w);
-            }
-        }
-        h->n_wbt_b = (int)d.size() - h->n_wbt_f; h->wbt_b_total = off;
-        if (!d.empty()) {
-            hipError_t e = hipMemcpy(h->wbt_descs, d.data(), d.size() * sizeof(WbtDesc), hipMemcpyHostToDevice);
-            if (e != hipSuccess) { delete h; return fail(-5, std::string("hipMemcpy(wbt_descs): ") + hipGetErrorString(e)); }
-        }
-    }
-    {
-        hipError_t e0 = hipMemset(h->fin_counters, 0, 2 * h->plan.L.size() * sizeof(unsigned));
-        if (e0 != hipSuccess) { delete h; return fail(-5, std::string("hipMemset(fin_counters): ") + hipGetErrorString(e0)); }
-    }
+    if (c->training) if (int rc = build_wt_descs(h)) return rc;
+    if (int rc = build_wbx_descs(h)) return rc;
+    if (int rc = build_wbt_descs(h)) return rc;
+    hipError_t e = hipMemset(h->fin_counters, 0, 2 * h->plan.L.size() * sizeof(unsigned));
+    if (e != hipSuccess) return fail(-5, std::string("hipMemset(fin_counters): ") + hipGetErrorString(e));
     float lut[256];
     for (int i = 0; i < 256; ++i) lut[i] = (float)((double)i / 255.0);
-    hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(c_u8_lut), lut, sizeof lut);
-    if (e != hipSuccess) { delete h; return fail(-5, std::string("hipMemcpyToSymbol: ") + hipGetErrorString(e)); }
+    e = hipMemcpyToSymbol(HIP_SYMBOL(c_u8_lut), lut, sizeof lut);
+    if (e != hipSuccess) return fail(-5, std::string("hipMemcpyToSymbol: ") + hipGetErrorString(e));
     if (c->training) {
         int lo = 0, hi = 0;
         (void)hipDeviceGetStreamPriorityRange(&lo, &hi);         // lo = numerically largest = least urgent
@@ -1089,7 +1081,7 @@ int oct_unet_create(const oct_unet_cfg* c, float* params, float* grads, float* s
             if (!ok) { (void)hipStreamDestroy(h->side); h->side = nullptr; }
         }
     }
-    *out = h;
+    *out = own.release();
     return 0;
 }
 
@@ -1123,36 +1115,27 @@ int oct_unet_forward(oct_unet* h, const void* x, int x_is_u8, int B, int trainin
     return 0;
 }
 
-int oct_unet_loss_dice(oct_unet* h, float smooth, float* out4, oct_stream_t stream) {
+// Dice (and focal) loss of the last forward: out holds n_user floats
+static int loss_finalize(oct_unet* h, const char* what, float smooth, float* out, int n_user, oct_stream_t stream) {
     if (!h) return fail(-1, "null handle");
-    if (!h->have_dice) return fail(-1, "loss_dice needs a preceding forward with io.labels");
+    if (!h->have_dice) return fail(-1, std::string(what) + " needs a preceding forward with io.labels");
     DiceFinArgs a{};
     a.part = h->dice_part; a.B = h->last_B; a.C = h->cfg.n_cls; a.nblk = head_nblk(h->cfg.H * h->cfg.W, h->last_B);
-    a.N = dice_n(a.C); a.smooth = smooth; a.out4 = h->loss4; a.out4_user = out4; a.bc = h->dice_bc;
-    a.n_user = 4; a.inv_count = 1.0 / ((double)h->last_B * h->cfg.H * h->cfg.W); a.focal_w = h->focal_w;
+    a.N = dice_n(a.C); a.smooth = smooth; a.out4 = h->loss4; a.out4_user = out; a.bc = h->dice_bc;
+    a.n_user = n_user; a.inv_count = 1.0 / ((double)h->last_B * h->cfg.H * h->cfg.W); a.focal_w = h->focal_w;
     dice_finalize_k<<<1, kBlock, 0, (hipStream_t)stream>>>(a);
     HIP_OK(hipGetLastError());
     h->dice_final = 1;
     return 0;
 }
+
+int oct_unet_loss_dice(oct_unet* h, float smooth, float* out4, oct_stream_t stream) { return loss_finalize(h, "loss_dice", smooth, out4, 4, stream); }
+int oct_unet_loss_focal_dice(oct_unet* h, float smooth, float* out8, oct_stream_t stream) { return loss_finalize(h, "loss_focal_dice", smooth, out8, 8, stream); }
 
 int oct_unet_set_focal_dice(oct_unet* h, float focal_loss_weight, float gamma, const float* class_weight_dev) {
     if (!h) return fail(-1, "null handle");
     if (!(focal_loss_weight >= 0.f && focal_loss_weight <= 1.f) || !(gamma >= 0.f)) return fail(-1, "focal_dice: weight must be in [0,1], gamma >= 0");
     h->focal_w = focal_loss_weight; h->focal_gamma = gamma; h->focal_cw = class_weight_dev;
-    return 0;
-}
-
-int oct_unet_loss_focal_dice(oct_unet* h, float smooth, float* out8, oct_stream_t stream) {
-    if (!h) return fail(-1, "null handle");
-    if (!h->have_dice) return fail(-1, "loss_focal_dice needs a preceding forward with io.labels");
-    DiceFinArgs a{};
-    a.part = h->dice_part; a.B = h->last_B; a.C = h->cfg.n_cls; a.nblk = head_nblk(h->cfg.H * h->cfg.W, h->last_B);
-    a.N = dice_n(a.C); a.smooth = smooth; a.out4 = h->loss4; a.out4_user = out8; a.bc = h->dice_bc;
-    a.n_user = 8; a.inv_count = 1.0 / ((double)h->last_B * h->cfg.H * h->cfg.W); a.focal_w = h->focal_w;
-    dice_finalize_k<<<1, kBlock, 0, (hipStream_t)stream>>>(a);
-    HIP_OK(hipGetLastError());
-    h->dice_final = 1;
     return 0;
 }
 
@@ -1298,37 +1281,48 @@ const Opt k_opts[] = {
     {"bx_two_blocks", &Options::bx_two_blocks, 0, 1}, {"fork_on_launch", &Options::fork_on_launch, 0, 1},
     {"event_sysfence", &Options::event_sysfence, 0, 1}, {"dw_fork_group", &Options::dw_fork_group, 1, 8}, {"fuse_bn_apply16", &Options::fuse_bn_apply16, 0, 1},
 };
+const Opt* find_opt(const char* name) {
+    for (const Opt& o : k_opts) if (!strcmp(name, o.name)) return &o;
+    fail(-1, std::string("unknown option: ") + name);
+    return nullptr;
+}
+int check_opt(const char* name, int value) {     // the two options whose valid values are not a range
+    if (!strcmp(name, "pair8_geometry") && value != 221 && value != 111) return fail(-1, "pair8_geometry must be 221 or 111");
+    if (!strcmp(name, "bx_waves") && value != 4 && value != 8) return fail(-1, "bx_waves must be 4 or 8");
+    return 0;
+}
+int get_opt(const Options& from, const char* name, int* value) {
+    const Opt* o = find_opt(name);
+    if (o) *value = from.*o->var;
+    return o ? 0 : -1;
+}
+int set_opt(Options& to, const char* name, int value) {
+    if (int rc = check_opt(name, value)) return rc;
+    const Opt* o = find_opt(name);
+    if (o) to.*o->var = value < o->lo ? o->lo : (value > o->hi ? o->hi : value);
+    return o ? 0 : -1;
+}
 }  // namespace
 
 int oct_get_option(const char* name, int* value) {
     if (!name || !value) return fail(-1, "null argument");
-    for (const Opt& o : k_opts) if (!strcmp(name, o.name)) { *value = g_opt.*o.var; return 0; }
-    return fail(-1, std::string("unknown option: ") + name);
+    return get_opt(g_opt, name, value);
 }
 
 int oct_set_option(const char* name, int value) {
     if (!name) return fail(-1, "null option name");
-    if (!strcmp(name, "pair8_geometry") && value != 221 && value != 111) return fail(-1, "pair8_geometry must be 221 or 111");
-    if (!strcmp(name, "bx_waves") && value != 4 && value != 8) return fail(-1, "bx_waves must be 4 or 8");
-    for (const Opt& o : k_opts)
-        if (!strcmp(name, o.name)) { g_opt.*o.var = value < o.lo ? o.lo : (value > o.hi ? o.hi : value); return 0; }
-    return fail(-1, std::string("unknown option: ") + name);
+    return set_opt(g_opt, name, value);
 }
 
 int oct_unet_get_option(const oct_unet* h, const char* name, int* value) {
     if (!h || !name || !value) return fail(-1, "null argument");
-    for (const Opt& o : k_opts) if (!strcmp(name, o.name)) { *value = h->opt.*o.var; return 0; }
-    return fail(-1, std::string("unknown option: ") + name);
+    return get_opt(h->opt, name, value);
 }
 
 int oct_unet_set_option(oct_unet* h, const char* name, int value) {
     if (!h || !name) return fail(-1, "null argument");
     if (!strcmp(name, "bt_m2")) return fail(-1, "bt_m2 shapes the prepared weights: set the default before oct_unet_create");
-    if (!strcmp(name, "pair8_geometry") && value != 221 && value != 111) return fail(-1, "pair8_geometry must be 221 or 111");
-    if (!strcmp(name, "bx_waves") && value != 4 && value != 8) return fail(-1, "bx_waves must be 4 or 8");
-    for (const Opt& o : k_opts)
-        if (!strcmp(name, o.name)) { h->opt.*o.var = value < o.lo ? o.lo : (value > o.hi ? o.hi : value); return 0; }
-    return fail(-1, std::string("unknown option: ") + name);
+    return set_opt(h->opt, name, value);
 }
 
 int oct_unet_debug_layer_fused(const oct_unet* h, int layer) {

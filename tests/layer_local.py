@@ -69,8 +69,8 @@ def bf16_ulp(a):
     return 2.0 ** (np.floor(np.log2(np.maximum(np.abs(a), 1e-30))) - 7)
 
 
-# ---- which arithmetic a layer runs in bf16 mode (dtype=1): mirror of the host rules in csrc/oct_unet.hip (bx_fwd_ok /
-# bt_fwd_ok / bx_bwd_ok / bt_bwd_ok / dw_plan).  On the bf16 MFMA pipe (mfma_mode 1, the default) BOTH operands of a
+# ---- which arithmetic a layer runs in bf16 mode (dtype=1): mirror of the host rules (csrc/host.hpp: pipe_fit;
+# csrc/oct_unet.hip: conv_route, dw_plan).  On the bf16 MFMA pipe (mfma_mode 1, the default) BOTH operands of a
 # product are bf16: the activation is rounded once more after BN + ReLU (dz operands are stored bf16 already: exact)
 # and the weights are rounded per step; accumulation stays fp32.  Layers outside those rules (first layer, head,
 # channel counts that are not multiples of 8, mfma_mode 0) multiply the stored bf16 values with fp32 weights. ----
