@@ -25,6 +25,7 @@
  *                                      dice_coef_micro/_macro         common/custom_metrics.py:18-77
  *   oct_unet_backward                  Keras autodiff of the above    training/training.py:262-266,401-407
  *   oct_adam_step / oct_sgd_step       optimizer.apply_gradients      training/training.py:190-193
+ *   oct_opt_step                       ... of any other opt_con, and the clipnorm / clipvalue / global_clipnorm options
  *   gradient buffer (caller-owned)     MirroredStrategy all-reduce    training/training.py:185-188,243
  *   oct_unet_graph_capture/_launch     (none: replaces per-call Keras dispatch overhead, evaluation.py:108-135)
  *   oct_augment_batch                  BatchGenerator.get_aug_fly/_nofly common/data_generator.py:140-283,
@@ -137,6 +138,45 @@ int oct_adam_step(float* params_dev, const float* grads_dev, float* m_dev, float
                   float lr, float beta1, float beta2, float eps, long step /*1-based*/, oct_stream_t stream);
 int oct_sgd_step(float* params_dev, const float* grads_dev, float* momentum_buf_dev /*or NULL*/, size_t n,
                  float lr, float momentum, oct_stream_t stream);
+
+/* ---- the Keras optimizer family with gradient clipping, on flat buffers (formulas: DESIGN.md section 13) ----
+ * One streaming launch per step; clipping is applied on the fly and grads_dev is never written.  Stand-alone like the
+ * two entry points above: no handle, no allocation, no host synchronisation, asynchronous on `stream`. */
+enum { OCT_OPT_SGD = 0, OCT_OPT_ADAM = 1, OCT_OPT_ADAMAX = 2, OCT_OPT_RMSPROP = 3, OCT_OPT_ADAGRAD = 4, OCT_OPT_ADADELTA = 5 };
+enum { OCT_OPT_NESTEROV = 1, OCT_OPT_AMSGRAD = 2, OCT_OPT_CENTERED = 4 };                 /* oct_opt_desc.flags */
+enum { OCT_CLIP_NONE = 0, OCT_CLIP_VALUE = 1, OCT_CLIP_NORM = 2, OCT_CLIP_GLOBAL_NORM = 3 };  /* oct_opt_desc.clip_mode */
+
+typedef struct oct_opt_desc {
+    int kind;             /* OCT_OPT_*                                                                            */
+    int flags;            /* OCT_OPT_NESTEROV (SGD with momentum), OCT_OPT_AMSGRAD (Adam), OCT_OPT_CENTERED (RMSprop) */
+    int clip_mode;        /* OCT_CLIP_*: at most one kind of clipping per step                                     */
+    float clip;           /* its threshold: > 0 for the norm modes, >= 0 for OCT_CLIP_VALUE                        */
+    float lr;             /* learning rate of THIS step (decay / schedule already applied by the caller)          */
+    float beta1, beta2;   /* Adam, Adamax                                                                          */
+    float rho;            /* RMSprop, Adadelta                                                                     */
+    float momentum;       /* SGD, RMSprop (0 = none)                                                               */
+    float eps;            /* all but SGD                                                                           */
+} oct_opt_desc;
+
+/* State buffers of n floats each the optimizer needs (0..3), in the order the step takes them, or -1 for a bad descriptor:
+ *   SGD       momentum != 0: [v]                           Adam      [m, v] (+ [vhat] with OCT_OPT_AMSGRAD)
+ *   Adamax    [m, u]                                       RMSprop   [rms] (+ [mom] if momentum != 0) (+ [mg] if OCT_OPT_CENTERED)
+ *   Adagrad   [a]  (the caller fills it with initial_accumulator_value)      Adadelta  [a, b]
+ * Every other buffer starts at zero. */
+int oct_opt_slot_count(const oct_opt_desc* desc);
+
+/* Bytes of scratch a clipped step over n floats in n_vars variables needs (norm partials in double + one scale per variable). */
+size_t oct_opt_scratch_bytes(size_t n_vars, size_t n);
+
+/* One optimizer step (`step` is 1-based).  slots: HOST array of 3 device pointers, the state buffers above in that order
+ * (entries past the slot count are ignored).
+ * var_off_dev: the variable table for OCT_CLIP_NORM -- n_vars + 1 ascending offsets ON THE DEVICE, variable k being
+ * [var_off[k], var_off[k+1]), var_off[0] = 0 and var_off[n_vars] = n (the pieces oct_unet_layer_info describes: kernel,
+ * bias, gamma, beta of each conv); unused (may be NULL) in the other modes.  scratch_dev: oct_opt_scratch_bytes() bytes,
+ * 16-byte aligned, for the two norm modes (else may be NULL).  The norm modes add two launches: per-variable partial sums of
+ * squares in a fixed order, then their sum in double and scale = clip / max(norm, clip) -- no atomics, no host read. */
+int oct_opt_step(const oct_opt_desc* desc, float* params_dev, const float* grads_dev, float* const* slots, size_t n,
+                 long step, const unsigned long long* var_off_dev, size_t n_vars, void* scratch_dev, oct_stream_t stream);
 
 /* ---- dropout stream control (parity tests replay the mask) ---- */
 int oct_unet_set_dropout_step(oct_unet* h, unsigned long long step);

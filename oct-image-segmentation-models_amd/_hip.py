@@ -42,6 +42,17 @@ class ProfileEntry(C.Structure):
                 ("total_ms", C.c_double), ("flops", C.c_double), ("bytes", C.c_double)]
 
 
+class OptDesc(C.Structure):
+    _fields_ = [("kind", C.c_int), ("flags", C.c_int), ("clip_mode", C.c_int), ("clip", C.c_float), ("lr", C.c_float),
+                ("beta1", C.c_float), ("beta2", C.c_float), ("rho", C.c_float), ("momentum", C.c_float), ("eps", C.c_float)]
+
+
+# oct_opt_desc.kind / .flags / .clip_mode (include/oct_unet.h)
+OPT_SGD, OPT_ADAM, OPT_ADAMAX, OPT_RMSPROP, OPT_ADAGRAD, OPT_ADADELTA = range(6)
+OPT_NESTEROV, OPT_AMSGRAD, OPT_CENTERED = 1, 2, 4
+CLIP_NONE, CLIP_VALUE, CLIP_NORM, CLIP_GLOBAL_NORM = range(4)
+
+
 class UNetIO(C.Structure):
     _fields_ = [("probs", C.c_void_p), ("argmax", C.c_void_p), ("labels", C.c_void_p)]
 
@@ -69,6 +80,10 @@ SYMBOLS = [
     ("oct_adam_step", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_float,
                                 C.c_float, C.c_float, C.c_long, C.c_void_p]),
     ("oct_sgd_step", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_float, C.c_void_p]),
+    ("oct_opt_slot_count", C.c_int, [_P(OptDesc)]),
+    ("oct_opt_scratch_bytes", C.c_size_t, [C.c_size_t, C.c_size_t]),
+    ("oct_opt_step", C.c_int, [_P(OptDesc), C.c_void_p, C.c_void_p, _P(C.c_void_p), C.c_size_t, C.c_long, C.c_void_p,
+                               C.c_size_t, C.c_void_p, C.c_void_p]),
     ("oct_unet_set_dropout_step", C.c_int, [C.c_void_p, C.c_ulonglong]),
     ("oct_unet_dropout_mask", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     ("oct_unet_graph_capture", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _P(UNetIO), C.c_void_p]),

@@ -219,6 +219,51 @@ class UNetEngine:
             _hip.check(_hip.lib().oct_sgd_step(self.params.data_ptr(), self.grads.data_ptr(), mom, self.n_params, lr,
                                                momentum, self._stream()), "oct_sgd_step")
 
+    # state buffers of oct_opt_step by kind, in the ABI's slot order (Adam and SGD share theirs with adam_step / sgd_step)
+    _OPT_SLOTS = {_hip.OPT_SGD: ("mom",), _hip.OPT_ADAM: ("m", "v", "vhat"), _hip.OPT_ADAMAX: ("adamax.m", "adamax.u"),
+                  _hip.OPT_RMSPROP: ("rmsprop.rms", "rmsprop.mom", "rmsprop.mg"), _hip.OPT_ADAGRAD: ("adagrad.a",),
+                  _hip.OPT_ADADELTA: ("adadelta.a", "adadelta.b")}
+
+    def var_offsets(self) -> np.ndarray:
+        """The variable table of the flat parameter buffer: n_vars + 1 ascending offsets, variable k being
+        [off[k], off[k+1]) -- kernel, bias and (with BN) gamma, beta of every conv, in buffer order."""
+        offs = sorted(L[k] for L in self.layers for k in (("kernel_off", "bias_off", "gamma_off", "beta_off") if L["has_bn"]
+                                                          else ("kernel_off", "bias_off")))
+        return np.asarray(offs + [self.n_params], np.uint64)
+
+    def optimizer_step(self, kind: int, *, lr: float, beta_1: float = 0.9, beta_2: float = 0.999, rho: float = 0.9,
+                       momentum: float = 0.0, epsilon: float = 1e-7, flags: int = 0, clip_mode: int = _hip.CLIP_NONE,
+                       clip: float = 0.0, initial_accumulator_value: float = 0.1):
+        """One step of any optimizer of the family on params / grads (``oct_opt_step``); state buffers, the variable table
+        and the clipping scratch are created at the first step that needs them and then live in ``_opt``."""
+        l = _hip.lib()
+        desc = _hip.OptDesc(kind, flags, clip_mode, clip, lr, beta_1, beta_2, rho, momentum, epsilon)
+        ns = l.oct_opt_slot_count(C.byref(desc))
+        if ns < 0:
+            raise OctError(f"oct_opt_slot_count: {l.oct_last_error().decode()}")
+        names = self._OPT_SLOTS[kind]
+        if kind == _hip.OPT_RMSPROP:
+            names = tuple(n for n, on in zip(names, (True, momentum != 0.0, bool(flags & _hip.OPT_CENTERED))) if on)
+        slots = (C.c_void_p * 3)()
+        for k, name in enumerate(names[:ns]):
+            if name not in self._opt:
+                self._opt[name] = torch.full_like(self.params, initial_accumulator_value if kind == _hip.OPT_ADAGRAD else 0.0)
+            slots[k] = self._opt[name].data_ptr()
+        var_off = scratch = None
+        n_vars = 0
+        if clip_mode in (_hip.CLIP_NORM, _hip.CLIP_GLOBAL_NORM):
+            if "clip.var_off" not in self._opt:
+                off = self.var_offsets()
+                self._opt["clip.var_off"] = torch.from_numpy(off.astype(np.int64)).to(self.device)
+                self._opt["clip.scratch"] = torch.empty(int(l.oct_opt_scratch_bytes(len(off) - 1, self.n_params)),
+                                                        dtype=torch.uint8, device=self.device)
+            var_off, scratch = self._opt["clip.var_off"].data_ptr(), self._opt["clip.scratch"].data_ptr()
+            n_vars = self._opt["clip.var_off"].numel() - 1
+        self.opt_step += 1
+        with torch.cuda.device(self.device):
+            _hip.check(l.oct_opt_step(C.byref(desc), self.params.data_ptr(), self.grads.data_ptr(), slots, self.n_params,
+                                      self.opt_step, var_off, n_vars, scratch, self._stream()), "oct_opt_step")
+
     # ---- data-parallel overlap hook (SURVEY 8e) ---------------------------------------------------
     def grad_tail_offset(self) -> int:
         """First float of the gradient segment (bottleneck + decoder + head) that is final at the tail event."""

@@ -166,7 +166,8 @@ class Model:
             if metric_name not in ("dice_coef_macro", "dice_coef_micro"):
                 raise OctError("compile(metrics=...): only dice_coef_macro / dice_coef_micro are implemented")
         if optimizer is not None and not hasattr(optimizer, "apply"):
-            raise OctError("compile(optimizer=...): pass an optimizers.Adam / optimizers.SGD instance")
+            raise OctError("compile(optimizer=...): pass an instance of one of the optimizers.Optimizer classes "
+                           "(SGD, Adam, Adamax, RMSprop, Adagrad, Adadelta)")
         self.optimizer, self._loss_name, self._metric_name = optimizer, loss_name, metric_name
 
     def count_params(self) -> int:
