@@ -253,6 +253,40 @@ int oct_augment_batch(const unsigned char* x_u8_dev, const unsigned char* labels
                       int B, int H, int W, int C, unsigned long long seed,
                       float* x_out_dev, unsigned char* labels_out_dev, oct_stream_t stream);
 
+/* ---- min-path boundary search on the device ----
+ * The boundary delineation of min_path_processing/graph_search.py for (B, M, H, W) uint8 boundary maps as
+ * oct_boundary_maps leaves them (M = classes - 1; no transpose), one workgroup per map.  The grid graph of the host
+ * search is a DAG by columns -- interior vertices have edges only to the next column (right, max_grad up, max_grad
+ * down), the zero-cost "down" edges exist only inside the two appended columns of ones -- so its shortest distances obey
+ * a column recurrence, stated here and restated in numpy by min_path_processing/device_search.py::delineate_dp:
+ *   p = k / 255 in fp64 (numpy's maps / 255; a 256-entry table divided on the host).  Graph column 0 and W + 1 are
+ *   ones, graph column j + 1 is image column j.  D[0][r] = 0.  For j = 0..W-1 and every row r,
+ *     D[j+1][r] = min over r' in {r, r+1..r+max_grad, r-1..r-max_grad} within [0, H) of
+ *                 D[j][r'] + (2.0 - (P[j][r'] + P[j+1][r])),            all fp64, no contraction.
+ *   Every edge weight is >= 0 and fp64 addition is monotone: D equals, bit for bit, Dijkstra's final distances.
+ *   Equal predecessors: the FIRST that attains the minimum in the order right (r), below nearest first (r+1, r+2, ..),
+ *   above nearest first (r-1, ..) is chosen; the vertex carries a tie bit if more than one attains it and j >= 1 (the
+ *   predecessors in the appended column 0 are all equal and change no delineation).
+ *   End: cost = min over r' of D[W][r'] + (2.0 - (P[W][r'] + 1.0)), the smallest such r'; tied if more than one attains it.
+ *   Back-trace from (W, r') to graph column 1: rows_out[image column] = row; the map's tie flag is the OR of the end
+ *   tie and the tie bits of the vertices on the chosen path (a tie bit off the path cannot change it; another optimal
+ *   delineation shows as a tie bit where the two paths merge).
+ * tied_out = 0: the minimum-cost delineation is unique and rows_out is what the host search returns.  tied_out = 1: the
+ * host search resolves the tie by the push order of its heap, which no column rule reproduces -- send that map to the
+ * host, or accept the rule above.  cost_out equals the host search's distance of the end vertex for every map.
+ * oct_minpath_workspace_bytes: bytes of workspace for up to B images, 0 for an unsupported shape (H or W beyond the
+ * uint16 rows, max_grad outside 1..16, or H beyond what one workgroup's LDS holds: two fp64 column pairs and a map tile,
+ * about 1600 rows).  The predecessor bytes (W x H per map) stay in LDS when they fit (256 x 512 does) and use the
+ * workspace otherwise.  oct_minpath_device: stand-alone, no handle, no allocation, no host synchronisation, one
+ * asynchronous launch on `stream`, graph-capturable (call once outside a capture first when W * H exceeds 32 KiB: the
+ * first launch per device raises the kernel's dynamic LDS limit).  Errors (negative, nothing launched): null pointers,
+ * max_grad outside 1..16, an unsupported shape, a workspace smaller than oct_minpath_workspace_bytes. */
+size_t oct_minpath_workspace_bytes(int B, int M, int H, int W, int max_grad);
+int oct_minpath_device(const unsigned char* maps_dev, int B, int M, int H, int W, int max_grad,
+                       void* workspace_dev, size_t workspace_bytes,
+                       unsigned short* rows_out_dev /* (B, M, W) */, double* cost_out_dev /* (B, M) */,
+                       unsigned char* tied_out_dev /* (B, M) */, oct_stream_t stream);
+
 /* ---- options ----
  * oct_set_option edits the PROCESS-WIDE DEFAULTS; a handle copies them when it is created (oct_unet_create) and every
  * launch of that handle reads its own copy: changing an option never affects a live handle, and two handles created

@@ -25,6 +25,7 @@ from ..common import (EVALUATION_METRIC_AVERAGE_SURFACE_DISTANCE, EVALUATION_MET
 from ..common import utils as common_utils
 from ..min_path_processing import graph_search, utils
 from ..models import get_model_class
+from ..min_path_processing.device_search import DeviceMinPath, LazyPool, merge_ties
 from ..min_path_processing.pool import SegmentPool
 from .evaluation_parameters import EvaluationParameters
 from .pipeline import BatchedPredictor
@@ -125,8 +126,14 @@ def evaluate_model(eval_params: EvaluationParameters) -> List[EvaluationOutput]:
     # BASELINE configs[4] path (evaluation/pipeline.py): the worker pool for the host min-path post-process is started
     # BEFORE the first GPU call of this process; the forward is a hipGraph replay at the configured batch with pinned,
     # double-buffered uint8 upload / download; a batch's graph search runs on the pool, not image by image on one core
-    pool = None
-    if eval_params.graph_search and hi > lo:
+    # gs_device: the search runs on the device behind the boundary maps (min_path_processing/device_search.py); the host
+    # pool is then only started if a map's minimum-cost path is not unique and gs_device_ties == "host"
+    pool = minpath = host_ties = None
+    if eval_params.graph_search and hi > lo and getattr(eval_params, "gs_device", False):
+        minpath = DeviceMinPath(bs, num_classes - 1, eval_images.shape[1], eval_images.shape[2], eval_params.gsgrad,
+                                eval_params.loaded_model._dev())
+        host_ties = LazyPool(eval_images.shape[1:3], eval_params.gsgrad, getattr(eval_params, "gs_workers", None))
+    elif eval_params.graph_search and hi > lo:
         pool = SegmentPool(eval_images.shape[1:3], eval_params.gsgrad, getattr(eval_params, "gs_workers", None))
     batches = ()
     # surface distances (evaluation.py:207-262) run on the device next to the forward: arg-max maps against the uploaded
@@ -144,7 +151,7 @@ def evaluate_model(eval_params: EvaluationParameters) -> List[EvaluationOutput]:
     if hi > lo and eval_images.dtype == np.uint8:
         engine = eval_params.loaded_model._ensure_engine(bs, False)
         batches = BatchedPredictor(engine, bs, want_maps=True, bg_ilm=True, bg_csi=False,
-                                   surface=surface).run(eval_images[lo:hi], gt_u8)
+                                   surface=surface, minpath=minpath).run(eval_images[lo:hi], gt_u8)
     elif hi > lo:      # non-uint8 datasets: x / 255 on the host (Model.predict_labels), same outputs, no overlap
         def _plain():
             import torch
@@ -157,15 +164,22 @@ def evaluate_model(eval_params: EvaluationParameters) -> List[EvaluationOutput]:
                     pred_dev = torch.from_numpy(np.ascontiguousarray(lm.astype(np.uint8))).to(surface.device)
                     gt_dev = torch.from_numpy(gt_u8[r0:r1]).to(surface.device)
                     rows = surface(pred_dev, gt_dev).cpu().numpy()
-                yield r0, r1, lm, dm, rows
+                if minpath is None:
+                    yield r0, r1, lm, dm, rows
+                else:
+                    yield r0, r1, lm, dm, rows, minpath.to_host(*minpath(torch.from_numpy(np.ascontiguousarray(dm)).to(minpath.device)))
         batches = _plain()
     t_prev = time.time()
     for batch in batches:
         rb0, rb1, label_maps, dev_maps = batch[:4]
-        surf_rows = batch[4] if len(batch) > 4 else None
+        extra = list(batch[4:])
+        mp = extra.pop() if minpath is not None else None            # (rows, cost, tied) of the device search
+        surf_rows = extra[0] if extra else None
         b0, b1 = lo + rb0, lo + rb1
         predict_time = (time.time() - t_prev) / (b1 - b0)
         gs_batch = pool.segment(dev_maps, eval_segments[b0:b1]) if pool is not None else None
+        if mp is not None:
+            gs_batch = merge_ties(dev_maps, mp[0], mp[2], eval_segments[b0:b1], host_ties, eval_params.gs_device_ties)
         for ind in range(b0, b1):
             eval_image, eval_image_name = eval_images[ind], eval_image_names[ind]
             eval_seg, eval_image_output_dir = eval_segments[ind], eval_image_output_dirs[ind]
@@ -209,6 +223,8 @@ def evaluate_model(eval_params: EvaluationParameters) -> List[EvaluationOutput]:
         t_prev = time.time()
     if pool is not None:
         pool.close()
+    if host_ties is not None:
+        host_ties.close()
     parallel.barrier()
     if rank == 0:
         _calc_overall_dataset_errors(eval_params, eval_image_names)

@@ -23,7 +23,8 @@ class EvaluationParameters:
     def __init__(self, model_path: Path, mlflow_tracking_uri: Optional[str], mlflow_run_uuid: Optional[str],
                  test_dataset_path: Path, save_foldername: Path, save_params: EvaluationSaveParams,
                  graph_search: bool, metrics: List[str], gsgrad=1, dice_errors: bool = True, binarize: bool = True,
-                 bg_ilm: bool = True, bg_csi: bool = False, batch_size: int = 32):
+                 bg_ilm: bool = True, bg_csi: bool = False, batch_size: int = 32, gs_device: bool = False,
+                 gs_device_ties: str = "host"):
         self.model_path = Path(model_path)
         self.mlflow_tracking_uri = mlflow_tracking_uri
         self.mlflow_run_uuid = mlflow_run_uuid
@@ -41,6 +42,13 @@ class EvaluationParameters:
         self.bg_csi = bg_csi
         self.save_foldername = Path(save_foldername)
         self.batch_size = batch_size   # extension: device batch (the reference predicts one image per call)
+        # extension: the min-path search on the device (min_path_processing/device_search.py).  "host" ties: maps whose
+        # minimum-cost path is not unique go back to the host search (outputs identical to gs_device=False); "device"
+        # ties: they keep the device's documented rule and no host search runs
+        if gs_device_ties not in ("host", "device"):
+            raise ValueError('gs_device_ties must be "host" or "device"')
+        self.gs_device = bool(gs_device)
+        self.gs_device_ties = gs_device_ties
         self.loaded_model, self.model_config = utils.load_model_and_config(
             self.model_path, mlflow_tracking_uri=mlflow_tracking_uri, mlflow_run_uuid=mlflow_run_uuid)
         self.num_classes = self.loaded_model.output.shape[-1]

@@ -24,10 +24,15 @@ class BatchedPredictor:
 
     With ``surface`` (an ``evaluation.surface.SurfaceDistances`` for this batch and shape), ``run(images_u8, gt_u8)``
     also uploads the ground-truth class maps (n,H,W) double-buffered like the images, runs the surface-distance kernels on
-    the arg-max maps behind their copy, and yields a fifth element: the (n, C-1, 6) float64 rows."""
+    the arg-max maps behind their copy, and yields a fifth element: the (n, C-1, 6) float64 rows.
+
+    With ``minpath`` (a ``min_path_processing.device_search.DeviceMinPath`` for this batch, C-1 maps and shape) the min-path
+    search runs on the boundary maps behind ``boundary_maps`` on the main stream, and ``run`` yields one more, last
+    element: ``(rows (n,C-1,W) uint16, cost (n,C-1) float64, tied (n,C-1) bool)``, downloaded through pinned double
+    buffers next to the labels and maps."""
 
     def __init__(self, engine, batch: int, want_maps: bool = True, bg_ilm: bool = True, bg_csi: bool = False,
-                 surface=None):
+                 surface=None, minpath=None):
         if not 1 <= batch <= engine.cfg.max_batch:
             raise ValueError(f"batch {batch} outside 1..max_batch={engine.cfg.max_batch}")
         self.eng, self.B, self.want_maps, self.bg = engine, int(batch), want_maps, (bg_ilm, bg_csi)
@@ -48,6 +53,16 @@ class BatchedPredictor:
             self.gt_dev = [torch.empty((self.B, H, W), dtype=torch.uint8, device=dev) for _ in range(2)]
             self.sd_dev = [torch.empty((self.B, C - 1, 6), dtype=torch.float64, device=dev) for _ in range(2)]
             self.sd_pin = [torch.empty((self.B, C - 1, 6), dtype=torch.float64).pin_memory() for _ in range(2)]
+        self.minpath = minpath
+        if minpath is not None:
+            if not want_maps:
+                raise ValueError("minpath: needs want_maps=True")
+            if (minpath.B, minpath.M, minpath.H, minpath.W) != (self.B, C - 1, H, W):
+                raise ValueError("minpath: DeviceMinPath built for another batch / shape")
+            self.mp_dev = [(torch.empty((self.B, C - 1, W), dtype=torch.int16, device=dev),
+                            torch.empty((self.B, C - 1), dtype=torch.float64, device=dev),
+                            torch.empty((self.B, C - 1), dtype=torch.uint8, device=dev)) for _ in range(2)]
+            self.mp_pin = [tuple(torch.empty(t.shape, dtype=t.dtype).pin_memory() for t in self.mp_dev[0]) for _ in range(2)]
         self.copy_in = torch.cuda.Stream(device=dev)
         self.copy_out = torch.cuda.Stream(device=dev)
         _, self.am = engine.graph_capture(self.x_dev, want_probs=False, want_argmax=True)
@@ -111,6 +126,8 @@ class BatchedPredictor:
                 gt_free[s].record(main)
             if self.want_maps:
                 self.map_dev[s].copy_(eng.boundary_maps(self.am, bg_ilm=self.bg[0], bg_csi=self.bg[1]))
+                if self.minpath is not None:
+                    self.minpath(self.map_dev[s][:hi - lo], *(t[:hi - lo] for t in self.mp_dev[s]))
             out_ready[s].record(main)
             with torch.cuda.stream(self.copy_out):
                 self.copy_out.wait_event(out_ready[s])
@@ -119,6 +136,9 @@ class BatchedPredictor:
                     self.map_pin[s].copy_(self.map_dev[s], non_blocking=True)
                 if surf:
                     self.sd_pin[s].copy_(self.sd_dev[s], non_blocking=True)
+                if self.minpath is not None:
+                    for t_pin, t_dev in zip(self.mp_pin[s], self.mp_dev[s]):
+                        t_pin.copy_(t_dev, non_blocking=True)
                 out_done[s].record(self.copy_out)
             if pending is not None:
                 yield self._collect(*pending, surf)
@@ -130,9 +150,13 @@ class BatchedPredictor:
         ev.synchronize()
         labels = self.lab_pin[s][:hi - lo].numpy().copy()
         maps = self.map_pin[s][:hi - lo].numpy().copy() if self.want_maps else None
+        out = (lo, hi, labels, maps)
         if surf:
-            return lo, hi, labels, maps, self.sd_pin[s][:hi - lo].numpy().copy()
-        return lo, hi, labels, maps
+            out += (self.sd_pin[s][:hi - lo].numpy().copy(),)
+        if self.minpath is not None:
+            rows, cost, tied = (t[:hi - lo].numpy() for t in self.mp_pin[s])
+            out += ((rows.view(np.uint16).copy(), cost.copy(), tied.astype(bool)),)
+        return out
 
 
 def bench_fields(engine, images_u8: np.ndarray, num_classes: int, batch: Optional[int] = None, n_batches: int = 6,

@@ -15,6 +15,7 @@ from .. import parallel
 from ..common import h5io, utils
 from ..evaluation.pipeline import BatchedPredictor
 from ..min_path_processing import graph_search  # noqa: F401  (re-exported: callers build graph structures through it)
+from ..min_path_processing.device_search import DeviceMinPath, LazyPool, merge_ties
 from ..min_path_processing.pool import SegmentPool
 from ..models import get_model_class
 from .prediction_parameters import PredictionParams
@@ -53,25 +54,36 @@ def predict(predict_params: PredictionParams) -> List[PredictionOutput]:
     bs = max(1, min(int(predict_params.batch_size), max(hi - lo, 1)))
     # same device pipeline as evaluate_model (evaluation/pipeline.py): worker pool first, then the hipGraph replay with
     # pinned double-buffered uint8 transfers; non-uint8 images take the host x / 255 path of Model.predict_labels
-    pool = None
-    if predict_params.graph_search and hi > lo:
+    # gs_device: the search runs on the device; the host pool only starts for maps whose minimum-cost path is not unique
+    pool = minpath = host_ties = None
+    if predict_params.graph_search and hi > lo and getattr(predict_params, "gs_device", False):
+        minpath = DeviceMinPath(bs, num_classes - 1, images.shape[1], images.shape[2], 1, predict_params.loaded_model._dev())
+        host_ties = LazyPool(images.shape[1:3], 1, getattr(predict_params, "gs_workers", None))
+    elif predict_params.graph_search and hi > lo:
         pool = SegmentPool(images.shape[1:3], 1, getattr(predict_params, "gs_workers", None))
     if hi > lo and images.dtype == np.uint8:
         engine = predict_params.loaded_model._ensure_engine(bs, False)
-        batches = BatchedPredictor(engine, bs, want_maps=True, bg_ilm=True, bg_csi=False).run(images[lo:hi])
+        batches = BatchedPredictor(engine, bs, want_maps=True, bg_ilm=True, bg_csi=False, minpath=minpath).run(images[lo:hi])
     else:
         def _plain():
             for r0 in range(0, hi - lo, bs):
                 r1 = min(r0 + bs, hi - lo)
                 lm, dm = predict_params.loaded_model.predict_labels(images[lo + r0:lo + r1], batch_size=bs, want_maps=True,
                                                                     bg_ilm=True, bg_csi=False)
-                yield r0, r1, lm, dm
+                if minpath is None:
+                    yield r0, r1, lm, dm
+                else:
+                    import torch
+                    yield r0, r1, lm, dm, minpath.to_host(*minpath(torch.from_numpy(np.ascontiguousarray(dm)).to(minpath.device)))
         batches = _plain()
     t0 = time.time()
-    for rb0, rb1, label_maps, dev_maps in batches:
+    for batch in batches:
+        rb0, rb1, label_maps, dev_maps = batch[:4]
         b0, b1 = lo + rb0, lo + rb1
         predict_time = (time.time() - t0) / (b1 - b0)
         gs_batch = pool.segment(dev_maps, None) if pool is not None else None
+        if minpath is not None:
+            gs_batch = merge_ties(dev_maps, batch[4][0], batch[4][2], None, host_ties, predict_params.gs_device_ties)
         for i in range(b0, b1):
             predict_image, image_name, image_output_dir = images[i], dataset.image_names[i], Path(dataset.image_output_dirs[i])
             os.makedirs(image_output_dir, exist_ok=True)
@@ -104,6 +116,8 @@ def predict(predict_params: PredictionParams) -> List[PredictionOutput]:
         t0 = time.time()
     if pool is not None:
         pool.close()
+    if host_ties is not None:
+        host_ties.close()
     parallel.barrier()
     return outputs
 

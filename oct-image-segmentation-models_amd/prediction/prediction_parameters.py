@@ -22,7 +22,8 @@ class PredictionParams:
     def __init__(self, model_path: Path, mlflow_tracking_uri: Union[str, None], mlflow_run_uuid: Union[str, None],
                  dataset: Dataset, config_output_dir: Path, save_params: PredictionSaveParams,
                  graph_search: bool = False, trim_maps: bool = False, trim_ref_ind: int = 0,
-                 trim_window: tuple = (0, 0), col_error_range: tuple = None, batch_size: int = 32) -> None:
+                 trim_window: tuple = (0, 0), col_error_range: tuple = None, batch_size: int = 32, gs_device: bool = False,
+                 gs_device_ties: str = "host") -> None:
         self.model_path = Path(model_path)
         self.mlflow_tracking_uri = mlflow_tracking_uri
         self.mlflow_run_uuid = mlflow_run_uuid
@@ -37,6 +38,11 @@ class PredictionParams:
         self.trim_ref_ind = trim_ref_ind
         self.trim_window = trim_window
         self.batch_size = batch_size
+        # extension: the min-path search on the device (see EvaluationParameters)
+        if gs_device_ties not in ("host", "device"):
+            raise ValueError('gs_device_ties must be "host" or "device"')
+        self.gs_device = bool(gs_device)
+        self.gs_device_ties = gs_device_ties
         self.col_error_range = col_error_range
         if col_error_range is None:
             self.col_error_range = range(dataset.images[0].shape[1])  # image_width
