@@ -24,6 +24,13 @@ def md5(file_path: Path) -> str:
     return h.hexdigest()
 
 
+def result_attrs(model_path, image_name, **times) -> dict:
+    """File attributes every per-image result file of ``evaluate_model`` / ``predict`` carries, then the caller's timings."""
+    return {"model_filename": np.array(str(model_path), dtype="S1000"),
+            "image_name": np.array(str(image_name), dtype="S1000"),
+            "timestamp": np.array(get_timestamp(), dtype="S1000"), **times}
+
+
 def to_categorical(y, num_classes: int) -> np.ndarray:
     """keras.utils.to_categorical: a trailing axis of size 1 is dropped, result float32 (Appendix B.8)."""
     y = np.asarray(y, dtype="int64")
@@ -119,3 +126,12 @@ def create_area_mask(image_shape: tuple, segs) -> np.ndarray:
                 mask[col, segs[seg_ind - 1, col]:cur_seg] = seg_ind
         mask[col, segs[len(segs) - 1, col]:] = len(segs)
     return mask
+
+
+def labels_from_delineations(image_shape_t: tuple, segs, num_classes: int) -> Tuple[np.ndarray, np.ndarray]:
+    """Graph-search delineations (C-1, W) -> the class map they enclose, (H, W), and its categorical form
+    (1, C, W, H) in the transposed frame the search works in (evaluation.py:317-333, prediction.py:145-158).
+    ``image_shape_t`` is the shape of the TRANSPOSED image, as for ``create_area_mask``."""
+    mask = create_area_mask(image_shape_t, segs)
+    labels_t, categorical = perform_argmax(np.expand_dims(to_categorical(mask, num_classes), axis=0))
+    return np.transpose(np.squeeze(labels_t)), categorical

@@ -14,7 +14,7 @@ import os
 import time
 import warnings
 from pathlib import Path
-from typing import List, Optional
+from typing import List
 
 import numpy as np
 
@@ -25,11 +25,9 @@ from ..common import (EVALUATION_METRIC_AVERAGE_SURFACE_DISTANCE, EVALUATION_MET
 from ..common import utils as common_utils
 from ..min_path_processing import graph_search, utils
 from ..models import get_model_class
-from ..min_path_processing.device_search import DeviceMinPath, LazyPool, merge_ties
-from ..min_path_processing.pool import SegmentPool
 from .evaluation_parameters import EvaluationParameters
-from .pipeline import BatchedPredictor
-from .surface import SurfaceDistances, datasets as surface_datasets
+from .pipeline import InferenceRun
+from .surface import datasets as surface_datasets
 
 EVALUATION_RESULTS_FILENAME = "evaluation_results.hdf5"
 GS_EVALUATION_RESULTS_FILENAME = "gs_evaluation_results.hdf5"
@@ -122,109 +120,59 @@ def evaluate_model(eval_params: EvaluationParameters) -> List[EvaluationOutput]:
 
     lo, hi = parallel.shard_range(n_images, rank, world)
     eval_outputs: List[EvaluationOutput] = []
-    bs = max(1, min(int(eval_params.batch_size), max(hi - lo, 1)))
-    # BASELINE configs[4] path (evaluation/pipeline.py): the worker pool for the host min-path post-process is started
-    # BEFORE the first GPU call of this process; the forward is a hipGraph replay at the configured batch with pinned,
-    # double-buffered uint8 upload / download; a batch's graph search runs on the pool, not image by image on one core
-    # gs_device: the search runs on the device behind the boundary maps (min_path_processing/device_search.py); the host
-    # pool is then only started if a map's minimum-cost path is not unique and gs_device_ties == "host"
-    pool = minpath = host_ties = None
-    if eval_params.graph_search and hi > lo and getattr(eval_params, "gs_device", False):
-        minpath = DeviceMinPath(bs, num_classes - 1, eval_images.shape[1], eval_images.shape[2], eval_params.gsgrad,
-                                eval_params.loaded_model._dev())
-        host_ties = LazyPool(eval_images.shape[1:3], eval_params.gsgrad, getattr(eval_params, "gs_workers", None))
-    elif eval_params.graph_search and hi > lo:
-        pool = SegmentPool(eval_images.shape[1:3], eval_params.gsgrad, getattr(eval_params, "gs_workers", None))
-    batches = ()
     # surface distances (evaluation.py:207-262) run on the device next to the forward: arg-max maps against the uploaded
     # ground-truth class maps, spacing (0.01111111, 0.01111111), percent 95
     want_surface = any(m in eval_params.metrics for m in (EVALUATION_METRIC_AVERAGE_SURFACE_DISTANCE,
                                                            EVALUATION_METRIC_HAUSDORFF_DISTANCE))
-    gt_u8 = surface = None
-    if want_surface and hi > lo:
-        gt = np.squeeze(eval_labels[lo:hi], axis=3)
-        if gt.min() < 0 or gt.max() >= num_classes:
-            raise ValueError(f"ground-truth labels outside 0..{num_classes - 1}")
-        gt_u8 = np.ascontiguousarray(gt.astype(np.uint8))
-        surface = SurfaceDistances(bs, eval_images.shape[1], eval_images.shape[2], num_classes,
-                                   eval_params.loaded_model._dev())
-    if hi > lo and eval_images.dtype == np.uint8:
-        engine = eval_params.loaded_model._ensure_engine(bs, False)
-        batches = BatchedPredictor(engine, bs, want_maps=True, bg_ilm=True, bg_csi=False,
-                                   surface=surface, minpath=minpath).run(eval_images[lo:hi], gt_u8)
-    elif hi > lo:      # non-uint8 datasets: x / 255 on the host (Model.predict_labels), same outputs, no overlap
-        def _plain():
-            import torch
-            for r0 in range(0, hi - lo, bs):
-                r1 = min(r0 + bs, hi - lo)
-                lm, dm = eval_params.loaded_model.predict_labels(eval_images[lo + r0:lo + r1], batch_size=bs, want_maps=True,
-                                                                 bg_ilm=True, bg_csi=False)
-                rows = None
-                if surface is not None:
-                    pred_dev = torch.from_numpy(np.ascontiguousarray(lm.astype(np.uint8))).to(surface.device)
-                    gt_dev = torch.from_numpy(gt_u8[r0:r1]).to(surface.device)
-                    rows = surface(pred_dev, gt_dev).cpu().numpy()
-                if minpath is None:
-                    yield r0, r1, lm, dm, rows
-                else:
-                    yield r0, r1, lm, dm, rows, minpath.to_host(*minpath(torch.from_numpy(np.ascontiguousarray(dm)).to(minpath.device)))
-        batches = _plain()
-    t_prev = time.time()
-    for batch in batches:
-        rb0, rb1, label_maps, dev_maps = batch[:4]
-        extra = list(batch[4:])
-        mp = extra.pop() if minpath is not None else None            # (rows, cost, tied) of the device search
-        surf_rows = extra[0] if extra else None
-        b0, b1 = lo + rb0, lo + rb1
-        predict_time = (time.time() - t_prev) / (b1 - b0)
-        gs_batch = pool.segment(dev_maps, eval_segments[b0:b1]) if pool is not None else None
-        if mp is not None:
-            gs_batch = merge_ties(dev_maps, mp[0], mp[2], eval_segments[b0:b1], host_ties, eval_params.gs_device_ties)
-        for ind in range(b0, b1):
-            eval_image, eval_image_name = eval_images[ind], eval_image_names[ind]
-            eval_seg, eval_image_output_dir = eval_segments[ind], eval_image_output_dirs[ind]
-            eval_label = common_utils.to_categorical(eval_labels[ind], num_classes)        # (H,W,C)
-            os.makedirs(eval_image_output_dir, exist_ok=True)
-            predicted_labels = label_maps[ind - b0:ind - b0 + 1].astype(np.int64)          # (1,H,W)
-            categorical_pred = common_utils.labels_to_categorical(predicted_labels, num_classes)
-            boundary_maps = dev_maps[ind - b0:ind - b0 + 1]   # == convert_predictions_to_maps_semantic(categorical_pred), on device
-            dice_classes, dice_macro, dice_micro = _dice_metrics(eval_params.metrics, num_classes, eval_label, categorical_pred)
-            surface_ds = _surface_metrics(eval_params.metrics, None if surf_rows is None else surf_rows[ind - b0])
-
-            predicted_labels = np.squeeze(predicted_labels, axis=0)
-            categorical_pred = np.squeeze(categorical_pred, axis=0)
-            boundary_maps = np.squeeze(boundary_maps, axis=0)
-            _save_image_evaluation_results(eval_params, eval_image, eval_image_name, predicted_labels, categorical_pred,
-                                           eval_label, eval_seg, dice_classes, dice_macro, dice_micro, predict_time,
-                                           eval_image_output_dir, surface_ds)
-
-            gs_pred_segs = errors = mean_abs_err = mean_err = abs_err_sd = err_sd = None
-            if eval_params.graph_search:
-                eval_image_t = np.transpose(eval_image, axes=[1, 0, 2])
-                start_graph_time = time.time()
-                gs_pred_segs, errors = gs_batch[ind - b0]          # == graph_search.segment_maps(boundary_maps_t, eval_seg, grid)
-                reconstructed_maps = common_utils.create_area_mask(eval_image_t.shape, gs_pred_segs)
-                reconstructed_maps = np.expand_dims(common_utils.to_categorical(reconstructed_maps, num_classes), axis=0)
-                [gs_eval_label, reconstructed_maps] = common_utils.perform_argmax(reconstructed_maps)
-                gs_dc, gs_dm, gs_dmi = _dice_metrics(eval_params.metrics, num_classes, eval_label, reconstructed_maps,
-                                                     transposed=True)
-                gs_eval_label = np.transpose(np.squeeze(gs_eval_label))
-                graph_time = time.time() - start_graph_time
-                mean_abs_err, mean_err, abs_err_sd, err_sd = graph_search.calculate_overall_errors(errors)
-                _save_graph_based_evaluation_results(eval_params, eval_image_name, gs_eval_label, gs_pred_segs, gs_dc,
-                                                     gs_dm, gs_dmi, errors, mean_abs_err, mean_err, abs_err_sd, err_sd,
-                                                     graph_time, eval_image_output_dir)
-            eval_outputs.append(EvaluationOutput(
-                image=eval_image, image_name=eval_image_name, image_segments=eval_seg,
-                image_output_dir=eval_image_output_dir, predicted_labels=predicted_labels,
-                categorical_pred=categorical_pred, boundary_maps=boundary_maps, gs_pred_segs=gs_pred_segs, errors=errors,
-                mean_abs_err=mean_abs_err, mean_err=mean_err, abs_err_sd=abs_err_sd, err_sd=err_sd,
-                dice_classes=dice_classes, dice_macro=dice_macro, dice_micro=dice_micro, **surface_ds))
+    # BASELINE configs[4] path (evaluation/pipeline.py::InferenceRun): search mode, batch source and worker pools
+    with InferenceRun(eval_params.loaded_model, eval_images[lo:hi], eval_params.batch_size, num_classes,
+                      gt=np.squeeze(eval_labels[lo:hi], axis=3) if want_surface else None,
+                      graph_search=eval_params.graph_search, gsgrad=eval_params.gsgrad, gs_device=eval_params.gs_device,
+                      gs_device_ties=eval_params.gs_device_ties, gs_workers=eval_params.gs_workers) as run:
         t_prev = time.time()
-    if pool is not None:
-        pool.close()
-    if host_ties is not None:
-        host_ties.close()
+        for batch in run:
+            b0, b1 = lo + batch.lo, lo + batch.hi
+            predict_time = (time.time() - t_prev) / (b1 - b0)
+            gs_found = run.graph_search(batch, eval_segments[b0:b1])
+            for ind in range(b0, b1):
+                eval_image, eval_image_name = eval_images[ind], eval_image_names[ind]
+                eval_seg, eval_image_output_dir = eval_segments[ind], eval_image_output_dirs[ind]
+                eval_label = common_utils.to_categorical(eval_labels[ind], num_classes)        # (H,W,C)
+                os.makedirs(eval_image_output_dir, exist_ok=True)
+                predicted_labels = batch.labels[ind - b0:ind - b0 + 1].astype(np.int64)        # (1,H,W)
+                categorical_pred = common_utils.labels_to_categorical(predicted_labels, num_classes)
+                boundary_maps = batch.maps[ind - b0:ind - b0 + 1]   # == convert_predictions_to_maps_semantic(categorical_pred), on device
+                dice_classes, dice_macro, dice_micro = _dice_metrics(eval_params.metrics, num_classes, eval_label, categorical_pred)
+                surface_ds = _surface_metrics(eval_params.metrics, None if batch.surface is None else batch.surface[ind - b0])
+
+                predicted_labels = np.squeeze(predicted_labels, axis=0)
+                categorical_pred = np.squeeze(categorical_pred, axis=0)
+                boundary_maps = np.squeeze(boundary_maps, axis=0)
+                _save_image_evaluation_results(eval_params, eval_image, eval_image_name, predicted_labels, categorical_pred,
+                                               eval_label, eval_seg, dice_classes, dice_macro, dice_micro, predict_time,
+                                               eval_image_output_dir, surface_ds)
+
+                gs_pred_segs = errors = mean_abs_err = mean_err = abs_err_sd = err_sd = None
+                if eval_params.graph_search:
+                    eval_image_t = np.transpose(eval_image, axes=[1, 0, 2])
+                    start_graph_time = time.time()
+                    gs_pred_segs, errors = gs_found[ind - b0]      # == graph_search.segment_maps(boundary_maps_t, eval_seg, grid)
+                    gs_eval_label, reconstructed_maps = common_utils.labels_from_delineations(eval_image_t.shape, gs_pred_segs,
+                                                                                             num_classes)
+                    gs_dc, gs_dm, gs_dmi = _dice_metrics(eval_params.metrics, num_classes, eval_label, reconstructed_maps,
+                                                         transposed=True)
+                    graph_time = time.time() - start_graph_time
+                    mean_abs_err, mean_err, abs_err_sd, err_sd = graph_search.calculate_overall_errors(errors)
+                    _save_graph_based_evaluation_results(eval_params, eval_image_name, gs_eval_label, gs_pred_segs, gs_dc,
+                                                         gs_dm, gs_dmi, errors, mean_abs_err, mean_err, abs_err_sd, err_sd,
+                                                         graph_time, eval_image_output_dir)
+                eval_outputs.append(EvaluationOutput(
+                    image=eval_image, image_name=eval_image_name, image_segments=eval_seg,
+                    image_output_dir=eval_image_output_dir, predicted_labels=predicted_labels,
+                    categorical_pred=categorical_pred, boundary_maps=boundary_maps, gs_pred_segs=gs_pred_segs, errors=errors,
+                    mean_abs_err=mean_abs_err, mean_err=mean_err, abs_err_sd=abs_err_sd, err_sd=err_sd,
+                    dice_classes=dice_classes, dice_macro=dice_macro, dice_micro=dice_micro, **surface_ds))
+            t_prev = time.time()
     parallel.barrier()
     if rank == 0:
         _calc_overall_dataset_errors(eval_params, eval_image_names)
@@ -255,10 +203,7 @@ def _save_image_evaluation_results(eval_params, eval_image, image_name, predicte
         ds[EVALUATION_METRIC_DICE_MICRO] = np.expand_dims(dice_micro, axis=0).astype("float64")
     for k, v in (surface_ds or {}).items():          # evaluation.py:573-597
         ds[k] = np.asarray(v, dtype="float64")
-    attrs = {"model_filename": np.array(str(eval_params.model_path), dtype="S1000"),
-             "image_name": np.array(str(image_name), dtype="S1000"),
-             "timestamp": np.array(common_utils.get_timestamp(), dtype="S1000"),
-             "predict_time": np.array(predict_time)}
+    attrs = common_utils.result_attrs(eval_params.model_path, image_name, predict_time=np.array(predict_time))
     h5io.save(output_dir / Path(EVALUATION_RESULTS_FILENAME), ds, attrs)
 
 
@@ -277,10 +222,7 @@ def _save_graph_based_evaluation_results(eval_params, image_name, gs_eval_label,
         ds[EVALUATION_METRIC_DICE_MACRO] = np.expand_dims(gs_dice_macro, axis=0).astype("float64")
     if gs_dice_micro is not None:
         ds[EVALUATION_METRIC_DICE_MICRO] = np.expand_dims(gs_dice_micro, axis=0).astype("float64")
-    attrs = {"model_filename": np.array(str(eval_params.model_path), dtype="S1000"),
-             "image_name": np.array(str(image_name), dtype="S1000"),
-             "timestamp": np.array(common_utils.get_timestamp(), dtype="S1000"),
-             "graph_time": np.array(graph_time)}
+    attrs = common_utils.result_attrs(eval_params.model_path, image_name, graph_time=np.array(graph_time))
     h5io.save(output_dir / Path(GS_EVALUATION_RESULTS_FILENAME), ds, attrs)
 
 

@@ -24,7 +24,7 @@ class EvaluationParameters:
                  test_dataset_path: Path, save_foldername: Path, save_params: EvaluationSaveParams,
                  graph_search: bool, metrics: List[str], gsgrad=1, dice_errors: bool = True, binarize: bool = True,
                  bg_ilm: bool = True, bg_csi: bool = False, batch_size: int = 32, gs_device: bool = False,
-                 gs_device_ties: str = "host"):
+                 gs_device_ties: str = "host", gs_workers: Optional[int] = None):
         self.model_path = Path(model_path)
         self.mlflow_tracking_uri = mlflow_tracking_uri
         self.mlflow_run_uuid = mlflow_run_uuid
@@ -49,6 +49,7 @@ class EvaluationParameters:
             raise ValueError('gs_device_ties must be "host" or "device"')
         self.gs_device = bool(gs_device)
         self.gs_device_ties = gs_device_ties
+        self.gs_workers = gs_workers   # extension: host-search worker processes (None: the CPU share, 1: inline)
         self.loaded_model, self.model_config = utils.load_model_and_config(
             self.model_path, mlflow_tracking_uri=mlflow_tracking_uri, mlflow_run_uuid=mlflow_run_uuid)
         self.num_classes = self.loaded_model.output.shape[-1]

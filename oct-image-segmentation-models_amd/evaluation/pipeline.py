@@ -10,26 +10,38 @@ composition (tests/test_gpu_workflow.py::test_batched_pipeline_equals_per_image_
 from __future__ import annotations
 
 import time
-from typing import Iterator, Optional, Tuple
+from typing import Iterable, Iterator, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
 
+from ..min_path_processing.device_search import DeviceMinPath, LazyPool, merge_ties
 from ..min_path_processing.pool import SegmentPool, default_workers
+from .surface import SurfaceDistances
+
+
+class Batch(NamedTuple):
+    """What the device yields for images ``lo:hi`` of a run.  A new device-side post-process is one more field here,
+    filled by ``BatchedPredictor`` and by ``host_batches``, and nowhere else."""
+    lo: int
+    hi: int
+    labels: np.ndarray                             # (n, H, W) uint8 arg-max class maps
+    maps: Optional[np.ndarray] = None              # (n, C-1, H, W) uint8 boundary maps
+    surface: Optional[np.ndarray] = None           # (n, C-1, 6) float64 surface-distance rows
+    minpath: Optional[Tuple[np.ndarray, ...]] = None   # rows (n, C-1, W) uint16, cost (n, C-1) float64, tied (n, C-1) bool
 
 
 class BatchedPredictor:
-    """Fixed-batch graph replay with overlapped transfers.  ``run(images_u8)`` yields
-    ``(lo, hi, labels (n,H,W) uint8, maps (n,C-1,H,W) uint8 | None)`` per device batch, in order.
+    """Fixed-batch graph replay with overlapped transfers.  ``run(images_u8)`` yields one ``Batch`` per device batch, in
+    order; ``maps`` is None without ``want_maps``.
 
     With ``surface`` (an ``evaluation.surface.SurfaceDistances`` for this batch and shape), ``run(images_u8, gt_u8)``
     also uploads the ground-truth class maps (n,H,W) double-buffered like the images, runs the surface-distance kernels on
-    the arg-max maps behind their copy, and yields a fifth element: the (n, C-1, 6) float64 rows.
+    the arg-max maps behind their copy, and fills ``Batch.surface``.
 
     With ``minpath`` (a ``min_path_processing.device_search.DeviceMinPath`` for this batch, C-1 maps and shape) the min-path
-    search runs on the boundary maps behind ``boundary_maps`` on the main stream, and ``run`` yields one more, last
-    element: ``(rows (n,C-1,W) uint16, cost (n,C-1) float64, tied (n,C-1) bool)``, downloaded through pinned double
-    buffers next to the labels and maps."""
+    search runs on the boundary maps behind ``boundary_maps`` on the main stream and fills ``Batch.minpath``, downloaded
+    through pinned double buffers next to the labels and maps."""
 
     def __init__(self, engine, batch: int, want_maps: bool = True, bg_ilm: bool = True, bg_csi: bool = False,
                  surface=None, minpath=None):
@@ -67,7 +79,7 @@ class BatchedPredictor:
         self.copy_out = torch.cuda.Stream(device=dev)
         _, self.am = engine.graph_capture(self.x_dev, want_probs=False, want_argmax=True)
 
-    def run(self, images_u8: np.ndarray, gt_u8: Optional[np.ndarray] = None) -> Iterator[tuple]:
+    def run(self, images_u8: np.ndarray, gt_u8: Optional[np.ndarray] = None) -> Iterator[Batch]:
         images_u8 = np.ascontiguousarray(images_u8)
         if images_u8.dtype != np.uint8:
             raise TypeError("the batched pipeline takes raw uint8 images (the /255 happens on the device)")
@@ -150,13 +162,102 @@ class BatchedPredictor:
         ev.synchronize()
         labels = self.lab_pin[s][:hi - lo].numpy().copy()
         maps = self.map_pin[s][:hi - lo].numpy().copy() if self.want_maps else None
-        out = (lo, hi, labels, maps)
-        if surf:
-            out += (self.sd_pin[s][:hi - lo].numpy().copy(),)
+        surface = self.sd_pin[s][:hi - lo].numpy().copy() if surf else None
+        minpath = None
         if self.minpath is not None:
             rows, cost, tied = (t[:hi - lo].numpy() for t in self.mp_pin[s])
-            out += ((rows.view(np.uint16).copy(), cost.copy(), tied.astype(bool)),)
-        return out
+            minpath = (rows.view(np.uint16).copy(), cost.copy(), tied.astype(bool))
+        return Batch(lo, hi, labels, maps, surface, minpath)
+
+
+def host_batches(model, images: np.ndarray, batch: int, *, gt_u8: Optional[np.ndarray] = None, surface=None,
+                 minpath=None) -> Iterator[Batch]:
+    """The same records for images that are not uint8: x / 255 on the host (``Model.predict_labels``), one synchronous
+    forward per batch, no overlap.  ``surface`` / ``minpath`` as in ``BatchedPredictor``."""
+    for lo in range(0, images.shape[0], batch):
+        hi = min(lo + batch, images.shape[0])
+        labels, maps = model.predict_labels(images[lo:hi], batch_size=batch, want_maps=True, bg_ilm=True, bg_csi=False)
+        rows = found = None
+        if surface is not None:
+            pred_dev = torch.from_numpy(np.ascontiguousarray(labels.astype(np.uint8))).to(surface.device)
+            rows = surface(pred_dev, torch.from_numpy(gt_u8[lo:hi]).to(surface.device)).cpu().numpy()
+        if minpath is not None:
+            found = minpath.to_host(*minpath(torch.from_numpy(np.ascontiguousarray(maps)).to(minpath.device)))
+        yield Batch(lo, hi, labels, maps, rows, found)
+
+
+class InferenceRun:
+    """One pass of a loaded model over ``images`` (a rank's slice) for ``evaluate_model`` / ``predict``: iterating it
+    yields the ``Batch`` records, ``graph_search(batch, truths)`` gives a batch's delineations, and leaving the ``with``
+    block closes the worker pools on every path.  It picks
+
+    * the search: none, the host ``SegmentPool`` (started here, BEFORE the first GPU call of the run), or with
+      ``gs_device`` a ``DeviceMinPath`` behind the boundary maps plus a ``LazyPool`` that only starts when a tied map
+      arrives and ``gs_device_ties == "host"``;
+    * ``SurfaceDistances`` when ground-truth class maps ``gt`` (n,H,W) are given: arg-max maps against them on the device;
+    * the source: ``BatchedPredictor`` (hipGraph replay, pinned double-buffered transfers) for uint8 images,
+      ``host_batches`` for every other dtype.
+
+    ``batches`` replaces the model by a ready source of records (tests of the host side: no device is touched)."""
+
+    def __init__(self, model, images: np.ndarray, batch: int, num_classes: int, *, gt: Optional[np.ndarray] = None,
+                 graph_search: bool = False, gsgrad: int = 1, gs_device: bool = False, gs_device_ties: str = "host",
+                 gs_workers: Optional[int] = None, batches: Optional[Iterable[Batch]] = None):
+        n, (H, W), C = images.shape[0], images.shape[1:3], int(num_classes)
+        self.pool = self.host_ties = None
+        self.ties, self._batches = gs_device_ties, (() if batches is None else batches)
+        if n == 0:
+            return
+        gt_u8 = None
+        if gt is not None:
+            if gt.min() < 0 or gt.max() >= C:
+                raise ValueError(f"ground-truth labels outside 0..{C - 1}")
+            gt_u8 = np.ascontiguousarray(gt.astype(np.uint8))
+        if graph_search and gs_device:
+            self.host_ties = LazyPool((H, W), gsgrad, gs_workers)
+        elif graph_search:
+            self.pool = SegmentPool((H, W), gsgrad, gs_workers)
+        if batches is not None:
+            return
+        try:
+            bs, dev = max(1, min(int(batch), n)), model._dev()
+            minpath = DeviceMinPath(bs, C - 1, H, W, gsgrad, dev) if self.host_ties is not None else None
+            surface = SurfaceDistances(bs, H, W, C, dev) if gt_u8 is not None else None
+            if images.dtype == np.uint8:
+                predictor = BatchedPredictor(model._ensure_engine(bs, False), bs, want_maps=True, bg_ilm=True, bg_csi=False,
+                                             surface=surface, minpath=minpath)
+                self._batches = predictor.run(images, gt_u8)
+            else:
+                self._batches = host_batches(model, images, bs, gt_u8=gt_u8, surface=surface, minpath=minpath)
+        except BaseException:
+            self.close()
+            raise
+
+    def __iter__(self) -> Iterator[Batch]:
+        return iter(self._batches)
+
+    def graph_search(self, batch: Batch, truths: Optional[np.ndarray] = None) -> Optional[list]:
+        """[(gs_pred_segs uint16 (C-1, W), errors float64 (C-1, W)), ...] per image of the batch -- every entry equals
+        ``graph_search.segment_maps`` of the image's maps, but for the tied maps under ``gs_device_ties == "device"`` --
+        or None without graph search.  The host part of the search runs in this call, not while the batch is fetched."""
+        if self.pool is not None:
+            return self.pool.segment(batch.maps, truths)
+        if self.host_ties is not None:
+            rows, _, tied = batch.minpath
+            return merge_ties(batch.maps, rows, tied, truths, self.host_ties, self.ties)
+        return None
+
+    def close(self) -> None:
+        for p in (self.pool, self.host_ties):
+            if p is not None:
+                p.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
 
 
 def bench_fields(engine, images_u8: np.ndarray, num_classes: int, batch: Optional[int] = None, n_batches: int = 6,
@@ -184,7 +285,7 @@ def bench_fields(engine, images_u8: np.ndarray, num_classes: int, batch: Optiona
     out = {}
     with SegmentPool((H, W), gsgrad=1, workers=workers) as pool, SegmentPool((H, W), gsgrad=1, workers=1) as solo:
         first = next(iter(pred.run(imgs[:B])))                      # warm-up: graph, pinned buffers, worker start-up
-        maps0 = first[3]
+        maps0 = first.maps
         pool.segment(maps0[:min(B, 2 * workers)])
         ns = min(B, 8)
 
@@ -198,8 +299,8 @@ def bench_fields(engine, images_u8: np.ndarray, num_classes: int, batch: Optiona
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             jobs = []
-            for lo, hi, labels, maps in pred.run(imgs):
-                jobs.append(pool.segment_async(maps if maps_for_pool is None else maps_for_pool[:hi - lo]))
+            for b in pred.run(imgs):
+                jobs.append(pool.segment_async(b.maps if maps_for_pool is None else maps_for_pool[:b.hi - b.lo]))
             for j in jobs:
                 j.get()
             return round((time.perf_counter() - t0) / imgs.shape[0] * 1e3, 4)

@@ -13,10 +13,8 @@ import numpy as np
 
 from .. import parallel
 from ..common import h5io, utils
-from ..evaluation.pipeline import BatchedPredictor
+from ..evaluation.pipeline import InferenceRun
 from ..min_path_processing import graph_search  # noqa: F401  (re-exported: callers build graph structures through it)
-from ..min_path_processing.device_search import DeviceMinPath, LazyPool, merge_ties
-from ..min_path_processing.pool import SegmentPool
 from ..models import get_model_class
 from .prediction_parameters import PredictionParams
 
@@ -51,73 +49,42 @@ def predict(predict_params: PredictionParams) -> List[PredictionOutput]:
 
     outputs: List[PredictionOutput] = []
     lo, hi = parallel.shard_range(len(images), rank, world)
-    bs = max(1, min(int(predict_params.batch_size), max(hi - lo, 1)))
-    # same device pipeline as evaluate_model (evaluation/pipeline.py): worker pool first, then the hipGraph replay with
-    # pinned double-buffered uint8 transfers; non-uint8 images take the host x / 255 path of Model.predict_labels
-    # gs_device: the search runs on the device; the host pool only starts for maps whose minimum-cost path is not unique
-    pool = minpath = host_ties = None
-    if predict_params.graph_search and hi > lo and getattr(predict_params, "gs_device", False):
-        minpath = DeviceMinPath(bs, num_classes - 1, images.shape[1], images.shape[2], 1, predict_params.loaded_model._dev())
-        host_ties = LazyPool(images.shape[1:3], 1, getattr(predict_params, "gs_workers", None))
-    elif predict_params.graph_search and hi > lo:
-        pool = SegmentPool(images.shape[1:3], 1, getattr(predict_params, "gs_workers", None))
-    if hi > lo and images.dtype == np.uint8:
-        engine = predict_params.loaded_model._ensure_engine(bs, False)
-        batches = BatchedPredictor(engine, bs, want_maps=True, bg_ilm=True, bg_csi=False, minpath=minpath).run(images[lo:hi])
-    else:
-        def _plain():
-            for r0 in range(0, hi - lo, bs):
-                r1 = min(r0 + bs, hi - lo)
-                lm, dm = predict_params.loaded_model.predict_labels(images[lo + r0:lo + r1], batch_size=bs, want_maps=True,
-                                                                    bg_ilm=True, bg_csi=False)
-                if minpath is None:
-                    yield r0, r1, lm, dm
-                else:
-                    import torch
-                    yield r0, r1, lm, dm, minpath.to_host(*minpath(torch.from_numpy(np.ascontiguousarray(dm)).to(minpath.device)))
-        batches = _plain()
-    t0 = time.time()
-    for batch in batches:
-        rb0, rb1, label_maps, dev_maps = batch[:4]
-        b0, b1 = lo + rb0, lo + rb1
-        predict_time = (time.time() - t0) / (b1 - b0)
-        gs_batch = pool.segment(dev_maps, None) if pool is not None else None
-        if minpath is not None:
-            gs_batch = merge_ties(dev_maps, batch[4][0], batch[4][2], None, host_ties, predict_params.gs_device_ties)
-        for i in range(b0, b1):
-            predict_image, image_name, image_output_dir = images[i], dataset.image_names[i], Path(dataset.image_output_dirs[i])
-            os.makedirs(image_output_dir, exist_ok=True)
-            log.info(f"Inferring image {i}: {image_name}")
-            start_convert_time = time.time()
-            predicted_labels = label_maps[i - b0:i - b0 + 1].astype(np.int64)
-            categorical_pred = utils.labels_to_categorical(predicted_labels, num_classes)
-            boundary_maps = dev_maps[i - b0:i - b0 + 1]   # == convert_predictions_to_maps_semantic(categorical_pred), on device
-            convert_time = time.time() - start_convert_time
-            predicted_labels = np.squeeze(predicted_labels, axis=0)
-            categorical_pred = np.squeeze(categorical_pred, axis=0)
-            boundary_maps = np.squeeze(boundary_maps, axis=0)
-            save_image_prediction_results(predict_params, predict_image, image_name, predicted_labels, categorical_pred,
-                                          boundary_maps, predict_time, convert_time, image_output_dir)
-            gs_pred_segs = None
-            if predict_params.graph_search:
-                predict_image_t = np.transpose(predict_image, axes=[1, 0, 2])
-                start_graph_time = time.time()
-                gs_pred_segs = gs_batch[i - b0][0]               # == graph_search.segment_maps(boundary_maps_t, None, grid)
-                reconstructed_maps = utils.create_area_mask(predict_image_t.shape, gs_pred_segs)
-                reconstructed_maps = np.expand_dims(utils.to_categorical(reconstructed_maps, num_classes), axis=0)
-                [gs_prediction_label, reconstructed_maps] = utils.perform_argmax(reconstructed_maps)
-                gs_prediction_label = np.transpose(np.squeeze(gs_prediction_label))
-                graph_time = time.time() - start_graph_time
-                save_graph_based_prediction_results(predict_params, image_name, gs_prediction_label, gs_pred_segs,
-                                                    graph_time, image_output_dir)
-            outputs.append(PredictionOutput(image=predict_image, image_name=image_name, image_output_dir=image_output_dir,
-                                            predicted_labels=predicted_labels, categorical_pred=categorical_pred,
-                                            boundary_maps=boundary_maps, gs_pred_segs=gs_pred_segs))
+    # the device pipeline of evaluate_model (evaluation/pipeline.py::InferenceRun), without ground truth
+    with InferenceRun(predict_params.loaded_model, images[lo:hi], predict_params.batch_size, num_classes,
+                      graph_search=predict_params.graph_search, gs_device=predict_params.gs_device,
+                      gs_device_ties=predict_params.gs_device_ties, gs_workers=predict_params.gs_workers) as run:
         t0 = time.time()
-    if pool is not None:
-        pool.close()
-    if host_ties is not None:
-        host_ties.close()
+        for batch in run:
+            b0, b1 = lo + batch.lo, lo + batch.hi
+            predict_time = (time.time() - t0) / (b1 - b0)
+            gs_found = run.graph_search(batch)
+            for i in range(b0, b1):
+                predict_image, image_name, image_output_dir = images[i], dataset.image_names[i], Path(dataset.image_output_dirs[i])
+                os.makedirs(image_output_dir, exist_ok=True)
+                log.info(f"Inferring image {i}: {image_name}")
+                start_convert_time = time.time()
+                predicted_labels = batch.labels[i - b0:i - b0 + 1].astype(np.int64)
+                categorical_pred = utils.labels_to_categorical(predicted_labels, num_classes)
+                boundary_maps = batch.maps[i - b0:i - b0 + 1]   # == convert_predictions_to_maps_semantic(categorical_pred), on device
+                convert_time = time.time() - start_convert_time
+                predicted_labels = np.squeeze(predicted_labels, axis=0)
+                categorical_pred = np.squeeze(categorical_pred, axis=0)
+                boundary_maps = np.squeeze(boundary_maps, axis=0)
+                save_image_prediction_results(predict_params, predict_image, image_name, predicted_labels, categorical_pred,
+                                              boundary_maps, predict_time, convert_time, image_output_dir)
+                gs_pred_segs = None
+                if predict_params.graph_search:
+                    predict_image_t = np.transpose(predict_image, axes=[1, 0, 2])
+                    start_graph_time = time.time()
+                    gs_pred_segs = gs_found[i - b0][0]           # == graph_search.segment_maps(boundary_maps_t, None, grid)
+                    gs_prediction_label, _ = utils.labels_from_delineations(predict_image_t.shape, gs_pred_segs, num_classes)
+                    graph_time = time.time() - start_graph_time
+                    save_graph_based_prediction_results(predict_params, image_name, gs_prediction_label, gs_pred_segs,
+                                                        graph_time, image_output_dir)
+                outputs.append(PredictionOutput(image=predict_image, image_name=image_name, image_output_dir=image_output_dir,
+                                                predicted_labels=predicted_labels, categorical_pred=categorical_pred,
+                                                boundary_maps=boundary_maps, gs_pred_segs=gs_pred_segs))
+            t0 = time.time()
     parallel.barrier()
     return outputs
 
@@ -139,10 +106,7 @@ def save_image_prediction_results(pred_params, predict_image, image_name, predic
     if pred_params.save_params.boundary_maps is True:
         ds["boundary_maps"] = boundary_maps.astype("uint8")
     ds["raw_image"] = predict_image.astype("uint8")
-    attrs = {"model_filename": np.array(str(pred_params.model_path), dtype="S1000"),
-             "image_name": np.array(str(image_name), dtype="S1000"),
-             "timestamp": np.array(utils.get_timestamp(), dtype="S1000"),
-             "predict_time": np.array(predict_time), "convert_time": convert_time}
+    attrs = utils.result_attrs(pred_params.model_path, image_name, predict_time=np.array(predict_time), convert_time=convert_time)
     h5io.save(output_dir / Path("prediction_info.hdf5"), ds, attrs)
 
 
@@ -151,7 +115,5 @@ def save_graph_based_prediction_results(predict_params, image_name, gs_predictio
     np.savetxt(output_dir / Path("gs_boundaries.csv"), gs_pred_segs, delimiter=",", fmt="%d")
     np.savetxt(output_dir / Path("gs_segmentation_map.csv"), gs_prediction_label, fmt="%d", delimiter=",")
     ds = {"gs_pred_segs": gs_pred_segs.astype("uint16"), "gs_predicted_labels": gs_prediction_label.astype("uint8")}
-    attrs = {"model_filename": np.array(str(predict_params.model_path), dtype="S1000"),
-             "image_name": np.array(str(image_name), dtype="S1000"),
-             "timestamp": np.array(utils.get_timestamp(), dtype="S1000"), "graph_time": np.array(graph_time)}
+    attrs = utils.result_attrs(predict_params.model_path, image_name, graph_time=np.array(graph_time))
     h5io.save(output_dir / Path("graph_search_prediction_info.hdf5"), ds, attrs)

@@ -23,7 +23,7 @@ class PredictionParams:
                  dataset: Dataset, config_output_dir: Path, save_params: PredictionSaveParams,
                  graph_search: bool = False, trim_maps: bool = False, trim_ref_ind: int = 0,
                  trim_window: tuple = (0, 0), col_error_range: tuple = None, batch_size: int = 32, gs_device: bool = False,
-                 gs_device_ties: str = "host") -> None:
+                 gs_device_ties: str = "host", gs_workers: Union[int, None] = None) -> None:
         self.model_path = Path(model_path)
         self.mlflow_tracking_uri = mlflow_tracking_uri
         self.mlflow_run_uuid = mlflow_run_uuid
@@ -43,6 +43,7 @@ class PredictionParams:
             raise ValueError('gs_device_ties must be "host" or "device"')
         self.gs_device = bool(gs_device)
         self.gs_device_ties = gs_device_ties
+        self.gs_workers = gs_workers   # extension: host-search worker processes (None: the CPU share, 1: inline)
         self.col_error_range = col_error_range
         if col_error_range is None:
             self.col_error_range = range(dataset.images[0].shape[1])  # image_width

@@ -163,7 +163,7 @@ def test_abi_errors_launch_nothing():
 
 def test_batched_predictor_minpath_double_buffers():
     """2 1/2 batches, then 5 batches (each pinned / device buffer pair is reused): rows, costs and tie flags per image equal
-    a direct DeviceMinPath call on the maps the predictor yields; without minpath the tuples are what they were."""
+    a direct DeviceMinPath call on the maps the predictor yields; without minpath the records are what they were."""
     from oct_image_segmentation_models_amd.engine import UNetEngine
     from oct_image_segmentation_models_amd.evaluation.pipeline import BatchedPredictor
     from oct_image_segmentation_models_amd.min_path_processing.device_search import DeviceMinPath
@@ -175,12 +175,13 @@ def test_batched_predictor_minpath_double_buffers():
     direct = DeviceMinPath(B, Cc - 1, H, W, 1, "cuda:0")
     # (a predictor captures the engine's one forward graph over its own input buffer: the plain one runs first)
     plain = list(BatchedPredictor(eng, B, want_maps=True).run(images[:10]))
-    assert all(len(b) == 4 for b in plain)
+    assert all(b.surface is None and b.minpath is None for b in plain)
     pred = BatchedPredictor(eng, B, want_maps=True, minpath=mp)
     for n, spans in ((10, [(0, 4), (4, 8), (8, 10)]), (20, [(4 * i, 4 * i + 4) for i in range(5)])):
         got = list(pred.run(images[:n]))
         assert [(b[0], b[1]) for b in got] == spans
-        for lo, hi, labels, maps, (rows, cost, tied) in got:
+        for b in got:
+            lo, hi, maps, (rows, cost, tied) = b.lo, b.hi, b.maps, b.minpath
             assert rows.dtype == np.uint16 and rows.shape == (hi - lo, Cc - 1, W) and tied.dtype == bool
             e = direct.to_host(*direct(torch.from_numpy(maps).cuda()))
             assert np.array_equal(rows, e[0]) and np.array_equal(cost, e[1]) and np.array_equal(tied, e[2]), (n, lo)

@@ -226,4 +226,4 @@ def test_evaluate_model_all_five_metrics(tmp_path):
         assert lines.index("Mean dice_coef_micro") < lines.index("Mean average_surface_distances") \
             < lines.index("Mean hausdorff_distances")
         per_path[tag] = np.array(got)
-    np.testing.assert_array_equal(per_path["u8"], per_path["f32"])       # batched uint8 path == float _plain() path
+    np.testing.assert_array_equal(per_path["u8"], per_path["f32"])       # batched uint8 path == float host_batches path

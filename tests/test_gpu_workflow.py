@@ -157,7 +157,8 @@ def test_batched_pipeline_equals_per_image_path_at_batch_128():
         pred = BatchedPredictor(eng, B, want_maps=True)
         got_lab = np.empty((N, Hh, Ww), np.uint8); got_map = np.empty((N, Cc - 1, Hh, Ww), np.uint8)
         spans = []
-        for lo, hi, lab, maps in pred.run(imgs):
+        for b in pred.run(imgs):
+            lo, hi, lab, maps = b.lo, b.hi, b.labels, b.maps
             spans.append((lo, hi)); got_lab[lo:hi] = lab; got_map[lo:hi] = maps
         assert spans == [(0, 128), (128, 160)]
         for i in (0, 1, 77, 127, 128, 159):                            # per-image reference path

@@ -41,7 +41,7 @@ def main():
         clean_dev = eng.boundary_maps(torch.from_numpy(lab).to(eng.device))
         mp = DeviceMinPath(B, C - 1, H, W, 1, eng.device)
         pred = BatchedPredictor(eng, B, want_maps=True, minpath=mp)
-        noise = next(iter(pred.run(imgs[:B])))[3]                   # warm-up: graph, pinned buffers, the kernel's LDS limit
+        noise = next(iter(pred.run(imgs[:B]))).maps                 # warm-up: graph, pinned buffers, the kernel's LDS limit
         noise_dev = torch.from_numpy(noise).to(eng.device)
         pool.segment(noise[:min(B, 2 * workers)])                   # worker start-up
         res = {"what": f"oct_minpath_device, B={B}, {H}x{W}, {C} classes ({C - 1} maps per scan), max_grad 1",
@@ -58,8 +58,8 @@ def main():
             pred.minpath = mp
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            jobs = [merge_ties_async(maps, rows, tied, None, pool.segment_async, ties)
-                    for lo, hi, _, maps, (rows, cost, tied) in pred.run(imgs)]
+            jobs = [merge_ties_async(b.maps, b.minpath[0], b.minpath[2], None, pool.segment_async, ties)
+                    for b in pred.run(imgs)]
             for j in jobs:
                 j.get()
             return (time.perf_counter() - t0) / imgs.shape[0] * 1e3
@@ -68,7 +68,7 @@ def main():
             pred.minpath = None
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            jobs = [pool.segment_async(maps) for lo, hi, _, maps in pred.run(imgs)]
+            jobs = [pool.segment_async(b.maps) for b in pred.run(imgs)]
             for j in jobs:
                 j.get()
             return (time.perf_counter() - t0) / imgs.shape[0] * 1e3
