@@ -23,6 +23,7 @@
  *     io.argmax                        perform_argmax                 common/utils.py:80-112
  *   oct_unet_loss_dice                 dice_loss_micro/_macro         common/custom_losses.py:47-81
  *                                      dice_coef_micro/_macro         common/custom_metrics.py:18-77
+ *   oct_unet_set_bce_dice / _loss_bce_dice  bce_dice_loss             common/custom_losses.py:84-91
  *   oct_unet_backward                  Keras autodiff of the above    training/training.py:262-266,401-407
  *   oct_adam_step / oct_sgd_step       optimizer.apply_gradients      training/training.py:190-193
  *   oct_opt_step                       ... of any other opt_con, and the clipnorm / clipvalue / global_clipnorm options
@@ -116,6 +117,22 @@ int oct_unet_loss_dice(oct_unet* h, float smooth, float* out4_dev, oct_stream_t 
  * test_focal_clip_modulation_switch pins both against the oracle on a saturated head). */
 int oct_unet_set_focal_dice(oct_unet* h, float focal_loss_weight, float gamma, const float* class_weight_dev);
 int oct_unet_loss_focal_dice(oct_unet* h, float smooth, float* out8_dev, oct_stream_t stream);
+/* bce_dice_loss (reference common/custom_losses.py:84-91): keras.losses.binary_crossentropy(y, p) + dice_loss_micro, i.e.
+ *   L = (1 / (B H W C)) sum_{b,h,w,c} -( y ln(pc + e) + (1 - y) ln(qc + e) ) + dice_loss_micro
+ * with p the softmax output, y the one-hot label, pc = clip(p, 1e-7, 1 - 1e-7), qc = clip(1 - p, 1e-7, 1 - 1e-7).  The
+ * mean over B*H*W*C is Keras's mean over the class axis followed by SUM_OVER_BATCH_SIZE; under data-parallel training
+ * oct_unet_backward's loss_scale carries the division by the number of replicas.  This restates Keras 2.9
+ * (backend.binary_crossentropy, from_logits=False) from its definition: TensorFlow is not available to this project, so
+ * parity with it is NOT pinned by a test (as for the focal loss); the tests compare with a torch-fp64 restatement.
+ * oct_unet_set_bce_dice(h, 1) selects the loss for the following forward / loss / backward calls and clears a selected
+ * focal_dice_loss; (h, 0), or oct_unet_set_focal_dice with weight > 0, clears it.  oct_unet_loss_bce_dice is
+ * oct_unet_loss_dice with 8 outputs: out8_dev = out4 + {bce mean, 0, bce + dice_loss_micro, 0}.  oct_unet_backward
+ * differentiates bce + dice_loss_micro (macro = 0); macro = 1 while the loss is selected is an argument error.
+ * Unverifiable detail, isolated as a switch: whether the backend adds its epsilon once more inside the logarithms after
+ * the clip.  oct_set_option("bce_inner_eps", 1) [default]: e = 1e-7; 0: e = 0.  Both are tested against the same
+ * restatement under the same setting. */
+int oct_unet_set_bce_dice(oct_unet* h, int on);
+int oct_unet_loss_bce_dice(oct_unet* h, float smooth, float* out8_dev, oct_stream_t stream);
 /* After training forward + loss_dice: fills the grads buffer with d(loss_scale*loss)/dparams. */
 int oct_unet_backward(oct_unet* h, const unsigned char* labels_dev, int macro, float loss_scale,
                       oct_stream_t stream);
@@ -292,12 +309,13 @@ int oct_minpath_device(const unsigned char* maps_dev, int B, int M, int H, int W
  * launch of that handle reads its own copy: changing an option never affects a live handle, and two handles created
  * under different settings coexist in one process.  oct_unet_workspace_bytes uses the defaults current at the call, so
  * size and create a handle under the same settings.  oct_unet_get_option reads a handle's copy.
- * Two select ARITHMETIC (documented alternatives, each tested against the oracle):
+ * Three select ARITHMETIC (documented alternatives, each tested against the oracle):
  *   "mfma_mode" (default 1): 1 = convolutions on the bf16 matrix pipe -- in fp32 mode (cfg.dtype 0) every fp32 operand is
  *   split exactly into three bf16 terms and a product is six bf16 MFMAs accumulated in fp32 (fp32-equivalent results,
  *   DESIGN.md section 4); in bf16 mode (cfg.dtype 1) activations and weights are rounded once and multiplied directly.
  *   0 = the fp32-pipe kernels (v_mfma_f32_*_f32), fp32 math on whatever the storage type is.
  *   "focal_clip_modulation" (default 0): see oct_unet_set_focal_dice.
+ *   "bce_inner_eps" (default 1): see oct_unet_set_bce_dice.
  * The rest are tuning knobs (results do not depend on them beyond fp32 rounding, only which kernel variant runs):
  *   "bx_min_blocks" (256): a wide bf16-pipe launch takes the taller pixel tile only if that still yields this many blocks.
  *   "bx_two_blocks" (1): wide bf16-pipe launches (3x3 and 2x2-over-upsample) run as 4-wave blocks with ONE input image in LDS,

@@ -4,8 +4,9 @@
 On the accelerated path the Dice sums are fused into the HIP head kernel, so ``Model.compile`` selects the
 loss by the ``oct_loss`` tag of the callable; the callables themselves are numpy restatements usable on host
 arrays (e.g. for evaluation code).  ``focal_dice_loss`` (reference :98-178, built on the third-party ``focal-loss``
-package: published formula restated, parity unpinned) is implemented the same way; the BCE mixes and the plain
-focal loss are out of scope and raise."""
+package: published formula restated, parity unpinned) and ``bce_dice_loss`` (reference :84-91, Keras 2.9's
+``binary_crossentropy`` restated, parity unpinned) are implemented the same way; ``bce_focal_loss`` and the plain
+focal loss raise."""
 from __future__ import annotations
 
 import numpy as np
@@ -74,18 +75,43 @@ def focal_dice_loss(*, num_classes: int, gamma: float = 2, class_weight=None, fo
     return _focal_dice_loss
 
 
-def _out_of_scope(name):
+def bce_dice_loss(*, num_classes: int, bce_inner_eps: bool = True, **kwargs):
+    """``bce_dice_loss`` (reference custom_losses.py:84-91): ``keras.losses.binary_crossentropy(y, p) + dice_loss_micro``.
+    The cross-entropy restates Keras 2.9's ``backend.binary_crossentropy`` (``from_logits=False``) on the clipped
+    probabilities, ``-(y ln(pc + e) + (1 - y) ln(1 - pc + e))``, averaged over the class axis and then over the batch
+    (one mean over every element).  ``bce_inner_eps=False`` drops the inner ``+ e`` (engine option "bce_inner_eps").
+    Sparse ``y_true`` (labels) is accepted as well as the dense one-hot the reference feeds it."""
+    dice_fn = dice_loss_micro(is_y_true_sparse=False, num_classes=num_classes)
+    e = FOCAL_EPS if bce_inner_eps else 0.0
+
+    def _bce_dice_loss(y_true, y_pred):
+        p = np.asarray(y_pred, np.float64)
+        y = np.asarray(y_true)
+        y = np.asarray(y, np.float64) if y.shape == p.shape else _one_hot(y, num_classes)
+        pc = np.clip(p, FOCAL_EPS, 1.0 - FOCAL_EPS)
+        qc = np.clip(1.0 - p, FOCAL_EPS, 1.0 - FOCAL_EPS)
+        bce = -(y * np.log(pc + e) + (1.0 - y) * np.log(qc + e))
+        return np.mean(bce) + dice_fn(y, p)
+
+    _bce_dice_loss.oct_loss = "bce_dice_loss"
+    return _bce_dice_loss
+
+
+def _out_of_scope(name, why=None):
     def factory(**kwargs):
-        raise NotImplementedError(f"loss '{name}' is outside the accelerated path (only the Dice losses and "
-                                  "focal_dice_loss are implemented; see DESIGN.md section 7)")
+        raise NotImplementedError(why or f"loss '{name}' is outside the accelerated path (only the Dice losses, "
+                                  "focal_dice_loss and bce_dice_loss are implemented; see DESIGN.md section 11)")
     return factory
 
 
 custom_loss_objects = {
-    "bce_dice_loss": {"function": _out_of_scope("bce_dice_loss"), "takes_sparse": False},
+    "bce_dice_loss": {"function": bce_dice_loss, "takes_sparse": False},
     "dice_loss_micro": {"function": dice_loss_micro, "takes_sparse": False},
     "dice_loss_macro": {"function": dice_loss_macro, "takes_sparse": False},
     "focal_loss": {"function": _out_of_scope("focal_loss"), "takes_sparse": True},
-    "bce_focal_loss": {"function": _out_of_scope("bce_focal_loss"), "takes_sparse": False},
+    "bce_focal_loss": {"function": _out_of_scope(
+        "bce_focal_loss", "loss 'bce_focal_loss': the reference's own registry entry cannot be called through the registry "
+        "(its function takes (y_true, y_pred), the registry passes num_classes= / is_y_true_sparse=), so there is "
+        "nothing to mirror; see DESIGN.md section 11"), "takes_sparse": False},
     "focal_dice_loss": {"function": focal_dice_loss, "takes_sparse": True},
 }

@@ -47,6 +47,7 @@ struct Options {
     int bx_min_blocks = 256;        // a bf16-pipe launch takes the taller pixel tile only if that still yields this many blocks
     int mfma_mode = 1;              // 1: bf16 MFMA pipe (split products in fp32 mode); 0: the fp32-pipe kernels everywhere
     int focal_clip_mod = 0;         // focal loss: 1 = the (1-p)^gamma modulation sees the clipped p too
+    int bce_inner_eps = 1;          // bce_dice_loss: 1 = ln(clip(p) + 1e-7) (Keras backend restated from memory), 0 = ln(clip(p))
     int fork_on_launch = 1;         // the event a forked backward-weights kernel waits for is the completion signal of the preceding
                                     // launch itself (0: a recorded marker behind it -- ~6 us in front of every backward-data launch)
     int dw_fork_group = 1;          // blocks whose backward-weights launches share one fork to the side stream.  Measured: 2-4 halve the

@@ -250,6 +250,8 @@ struct HeadBwdArgs {
     // focal_dice_loss: L = w * focal + (1 - w) * dice  (focal_w = 0: plain Dice)
     float focal_w, focal_gamma; const float* focal_cw; float inv_count;   // inv_count = 1 / (B*H*W)
     int focal_clip_mod;                // see HeadFwdArgs
+    // bce_dice_loss: L = bce + dice_micro (focal_w = 0, macro = 0); bce_scale = loss_scale / (B*H*W*C)
+    int bce_on; float bce_inner, bce_scale;
     FinDesc fin;                       // BN-backward sums of the last conv block finalized by the last block (kernels_fin.hpp)
 };
 
@@ -313,9 +315,36 @@ __global__ __launch_bounds__(kBlock) void head_bwd_k(const HeadBwdArgs A) {
             }
             dot = fmaf(p[c], dp[c], dot);
         }
+        // BCE half of bce_dice_loss.  The branch sits HERE, at the join behind the focal branch of the last class, and its
+        // result is added below unconditionally (x + 0 = x: the Dice and focal paths stay bit-identical): a branch between
+        // dl and the 1x1 backward costs <3, 8, float> 8 VGPRs (126 -> 134) and with them the fourth wave per SIMD
+        float dlb[C];
+#pragma unroll
+        for (int c = 0; c < C; ++c) dlb[c] = 0.f;
+        if (A.bce_on) {
+            // dBCE/dp_c = s ( -y/(pc + e) + (1 - y)/(qc + e) ) where neither clip is active.  With q = 1 - p and the usual
+            // p (dp - dot) the result is lost where p saturates: 1/q blows up exactly where 1 - p and dp - dot cancel
+            // (DESIGN.md section 11).  So q comes from the other classes' probabilities, and the Jacobian is applied as
+            //   dl_c = p_c ( q_c dp_c - sum_{k != c} p_k dp_k )
+            float q[C], db[C];
+            softmax_complement<C>(p, q);
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                const bool inr = valid && p[c] >= kFocalEps && q[c] >= kFocalEps;
+                const float r = A.bce_scale / ((lab == c ? p[c] : q[c]) + A.bce_inner);      // y picks the term
+                db[c] = inr ? (lab == c ? -r : r) : 0.f;
+            }
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                float o = 0.f;
+#pragma unroll
+                for (int k = 0; k < C; ++k) if (k != c) o = fmaf(p[k], db[k], o);
+                dlb[c] = p[c] * (q[c] * db[c] - o);
+            }
+        }
         float dl[C];
 #pragma unroll
-        for (int c = 0; c < C; ++c) { dl[c] = valid ? p[c] * (dp[c] - dot) : 0.f; wv[CIN * C + c] += dl[c]; }
+        for (int c = 0; c < C; ++c) { dl[c] = (valid ? p[c] * (dp[c] - dot) : 0.f) + dlb[c]; wv[CIN * C + c] += dl[c]; }
         float g[CIN];
 #pragma unroll
         for (int i = 0; i < CIN; ++i) {

@@ -272,13 +272,30 @@ struct HeadFwdArgs {
     const void* z; const float* ab;    // last conv's raw output (activation storage type) + BN record
     const float* w; const float* bias; // (CIN, C), (C)
     float* probs; unsigned char* argmax; const unsigned char* labels;
-    float* dice_part;                  // [B][nblk][DiceN]; slot 5*C (always spare: 5*C < DiceN) = focal-loss sum
+    float* dice_part;                  // [B][nblk][DiceN]; slot 5*C (always spare: 5*C < DiceN) = focal-loss sum, or the BCE sum
     int HW, nblk, act_bf16;
     // focal half of focal_dice_loss (custom_losses.py:98-178): cw[y] * (1 - p_y)^gamma * (-log p_y), p clipped to [1e-7, 1-1e-7]
     int focal_on; float focal_gamma; const float* focal_cw;   // class weights (C) or nullptr
     int focal_clip_mod;                // 1: the (1 - p)^gamma modulation also sees the clipped p; 0: only the logarithm does
+    // BCE half of bce_dice_loss (custom_losses.py:84-91; Keras 2.9 backend.binary_crossentropy restated, parity unpinned):
+    //   sum_c -( y ln(pc + e) + (1 - y) ln(qc + e) ),  pc = clip(p, eps, 1-eps), qc = clip(1 - p, eps, 1-eps),  e = eps or 0
+    // Never together with focal_on: the two share slot 5*C.
+    int bce_on; float bce_inner;       // bce_inner = e (option bce_inner_eps)
 };
 constexpr float kFocalEps = 1e-7f;
+
+// q_c = 1 - p_c of a softmax row, taken as the sum of the other classes: `1.f - p` has an absolute error of one ulp of p,
+// which is all of q where p saturates (and 1/q is what the BCE gradient multiplies by)
+template <int C>
+__device__ inline void softmax_complement(const float (&p)[C], float (&q)[C]) {
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        float s = 0.f;
+#pragma unroll
+        for (int k = 0; k < C; ++k) if (k != c) s += p[k];
+        q[c] = s;
+    }
+}
 
 // raw z of one pixel (CIN values) -> registers; split from the arithmetic so that the head kernels can request the next
 // chunk's pixel before they work on the current one (one chunk of software prefetch)
@@ -356,6 +373,16 @@ __global__ __launch_bounds__(kBlock) void head_fwd_k(const HeadFwdArgs A) {
                     const float cw = A.focal_cw ? A.focal_cw[lab < C ? lab : 0] : 1.f;
                     v[C * kDiceVals] += cw * powf(1.f - (A.focal_clip_mod ? pc : py), A.focal_gamma) * -logf(pc);
                 }
+                if (A.bce_on) {
+                    float q[C], t = 0.f;
+                    softmax_complement<C>(p, q);
+#pragma unroll
+                    for (int c = 0; c < C; ++c) {
+                        const float u = lab == c ? p[c] : q[c];        // y picks one of the two logarithms
+                        t -= logf(fminf(fmaxf(u, kFocalEps), 1.f - kFocalEps) + A.bce_inner);
+                    }
+                    v[C * kDiceVals] += t;
+                }
             }
         }
     }
@@ -366,12 +393,14 @@ __global__ __launch_bounds__(kBlock) void head_fwd_k(const HeadFwdArgs A) {
 //   out4 = {dice_loss_macro, dice_loss_micro, dice_coef_macro, dice_coef_micro}
 //   bc   = per (b,c): {Num = 2I+s, Den = T+P+s}; then the micro pair at [2*B*C], [2*B*C+1]
 //   out8 = out4 + {focal mean, w*focal + (1-w)*dice_macro, w*focal + (1-w)*dice_micro, 0}   (focal_dice_loss)
+//   out8 = out4 + {bce mean, 0, bce + dice_micro, 0}                                        (bce_dice_loss, bce_on)
 struct DiceFinArgs {
     const float* part; int B, C, nblk, N;
     float smooth; float* out4; float* out4_user; double* bc;
     int n_user;            // floats copied to out4_user: 4 (loss_dice) or 8 (loss_focal_dice)
     double inv_count;      // 1 / (B*H*W)
     float focal_w;
+    int bce_on;            // slot 5*C holds the BCE sum: its mean is over B*H*W*C
 };
 
 static __global__ __launch_bounds__(kBlock) void dice_finalize_k(const DiceFinArgs A) {
@@ -425,6 +454,10 @@ static __global__ __launch_bounds__(kBlock) void dice_finalize_k(const DiceFinAr
         o4[5] = (float)(w * focal + (1.0 - w) * (1.0 - sh[0][0] / n));
         o4[6] = (float)(w * focal + (1.0 - w) * (1.0 - num / den));
         o4[7] = 0.f;
+        if (A.bce_on) {
+            const double bce = sh[7][0] * (A.inv_count / A.C);
+            o4[4] = (float)bce; o4[5] = 0.f; o4[6] = (float)(bce + (1.0 - num / den));
+        }
         for (int j = 0; j < 8; ++j) { A.out4[j] = o4[j]; if (A.out4_user && j < A.n_user) A.out4_user[j] = o4[j]; }
     }
 }

@@ -251,6 +251,7 @@ struct oct_unet {
     ReduceAllArgs red{};                   // filled while backward runs; one reduce launch at the end
     float* dice_part = nullptr; double* dice_bc = nullptr; float* loss4 = nullptr;   // loss4: 8 floats (dice_finalize_k)
     float focal_w = 0.f, focal_gamma = 2.f; const float* focal_cw = nullptr;           // focal_dice_loss (0 = plain Dice)
+    int bce_on = 0;                                                                    // bce_dice_loss (never with focal_w > 0)
     WtDesc* wt_descs = nullptr; int n_wt = 0; unsigned wt_total = 0;
     WbxDesc* wbx_descs = nullptr; int n_wbx_f = 0, n_wbx_b = 0; unsigned wbx_f_total = 0, wbx_b_total = 0;   // [fwd..., bwd...]
     WbtDesc* wbt_descs = nullptr; int n_wbt_f = 0, n_wbt_b = 0; unsigned wbt_f_total = 0, wbt_b_total = 0;   // [fwd..., bwd...]
@@ -566,6 +567,7 @@ int forward_impl(oct_unet* h, const void* x, int x_is_u8, int B, int training, c
     a.probs = io ? io->probs : nullptr; a.argmax = io ? io->argmax : nullptr; a.labels = io ? io->labels : nullptr;
     a.dice_part = h->dice_part; a.HW = hd.H * hd.W; a.nblk = head_nblk(a.HW, B); a.act_bf16 = h->cfg.dtype;
     a.focal_on = h->focal_w > 0.f; a.focal_gamma = h->focal_gamma; a.focal_cw = h->focal_cw; a.focal_clip_mod = h->opt.focal_clip_mod;
+    a.bce_on = h->bce_on; a.bce_inner = h->opt.bce_inner_eps ? kFocalEps : 0.f;
     const int rc = DISPATCH_C(launch_head_fwd, h->cfg.n_cls, a, hd.cin, B, s);
     if (rc) return rc;
     h->last_B = B; h->last_training = training; h->have_dice = a.labels != nullptr;
@@ -785,6 +787,7 @@ int head_backward(oct_unet* h, const unsigned char* labels, int macro, float los
     hb.labels = labels; hb.bc = h->dice_bc; hb.g = last.g; hb.part = h->stat_part; hb.wpart = hd.dwp;
     hb.HW = hd.H * hd.W; hb.nblk = head_nblk(hb.HW, B); hb.B = B; hb.macro = macro; hb.loss_scale = loss_scale; hb.act_bf16 = h->cfg.dtype;
     hb.focal_w = h->focal_w; hb.focal_gamma = h->focal_gamma; hb.focal_cw = h->focal_cw; hb.focal_clip_mod = h->opt.focal_clip_mod; hb.inv_count = 1.f / ((float)B * hb.HW);
+    hb.bce_on = h->bce_on; hb.bce_inner = h->opt.bce_inner_eps ? kFocalEps : 0.f; hb.bce_scale = loss_scale * hb.inv_count / (float)h->cfg.n_cls;
     if (fin_ok(h, last)) { hb.fin = fin_desc(h, nl - 2, 1, B); *fin = true; }
     *rows = B * hb.nblk;
     return DISPATCH_C(launch_head_bwd, h->cfg.n_cls, hb, hd.cin, B, s);
@@ -1122,7 +1125,7 @@ static int loss_finalize(oct_unet* h, const char* what, float smooth, float* out
     DiceFinArgs a{};
     a.part = h->dice_part; a.B = h->last_B; a.C = h->cfg.n_cls; a.nblk = head_nblk(h->cfg.H * h->cfg.W, h->last_B);
     a.N = dice_n(a.C); a.smooth = smooth; a.out4 = h->loss4; a.out4_user = out; a.bc = h->dice_bc;
-    a.n_user = n_user; a.inv_count = 1.0 / ((double)h->last_B * h->cfg.H * h->cfg.W); a.focal_w = h->focal_w;
+    a.n_user = n_user; a.inv_count = 1.0 / ((double)h->last_B * h->cfg.H * h->cfg.W); a.focal_w = h->focal_w; a.bce_on = h->bce_on;
     dice_finalize_k<<<1, kBlock, 0, (hipStream_t)stream>>>(a);
     HIP_OK(hipGetLastError());
     h->dice_final = 1;
@@ -1131,11 +1134,20 @@ static int loss_finalize(oct_unet* h, const char* what, float smooth, float* out
 
 int oct_unet_loss_dice(oct_unet* h, float smooth, float* out4, oct_stream_t stream) { return loss_finalize(h, "loss_dice", smooth, out4, 4, stream); }
 int oct_unet_loss_focal_dice(oct_unet* h, float smooth, float* out8, oct_stream_t stream) { return loss_finalize(h, "loss_focal_dice", smooth, out8, 8, stream); }
+int oct_unet_loss_bce_dice(oct_unet* h, float smooth, float* out8, oct_stream_t stream) { return loss_finalize(h, "loss_bce_dice", smooth, out8, 8, stream); }
 
 int oct_unet_set_focal_dice(oct_unet* h, float focal_loss_weight, float gamma, const float* class_weight_dev) {
     if (!h) return fail(-1, "null handle");
     if (!(focal_loss_weight >= 0.f && focal_loss_weight <= 1.f) || !(gamma >= 0.f)) return fail(-1, "focal_dice: weight must be in [0,1], gamma >= 0");
     h->focal_w = focal_loss_weight; h->focal_gamma = gamma; h->focal_cw = class_weight_dev;
+    if (focal_loss_weight > 0.f) h->bce_on = 0;     // the two share one slot of the Dice partial rows
+    return 0;
+}
+
+int oct_unet_set_bce_dice(oct_unet* h, int on) {
+    if (!h) return fail(-1, "null handle");
+    h->bce_on = on != 0;
+    if (h->bce_on) h->focal_w = 0.f;
     return 0;
 }
 
@@ -1143,6 +1155,7 @@ int oct_unet_backward(oct_unet* h, const unsigned char* labels, int macro, float
     if (!h || !labels) return fail(-1, "null handle or labels");
     if (!h->last_training || !h->have_dice || !h->dice_final)
         return fail(-1, "backward needs a training forward with io.labels followed by oct_unet_loss_dice");
+    if (h->bce_on && macro) return fail(-1, "bce_dice_loss is defined with dice_loss_micro only: macro must be 0");
     t_prof = &h->prof;
     const int rc = backward_impl(h, h->last_x, h->last_u8, labels, macro, loss_scale, (hipStream_t)stream);
     if (rc && h->side && h->join_ev) {
@@ -1271,6 +1284,7 @@ const Opt k_opts[] = {
     {"igemm_min_blocks", &Options::igemm_min_blocks, 1, 1 << 30}, {"dwpair8_enable", &Options::dwpair8, 0, 1},
     {"pair8_geometry", &Options::pair_geo, 111, 221}, {"pair8_min_tiles", &Options::pair_min_tiles, 1, 1 << 30},
     {"thin8_min_tiles", &Options::thin_min_tiles, 1, 1 << 30}, {"focal_clip_modulation", &Options::focal_clip_mod, 0, 1},
+    {"bce_inner_eps", &Options::bce_inner_eps, 0, 1},
     {"mfma_mode", &Options::mfma_mode, 0, 1}, {"bx_min_blocks", &Options::bx_min_blocks, 1, 1 << 30},
     {"dwbx_blocks", &Options::dwbx_blocks, 8, 1 << 20}, {"bt_blocks_per_cu", &Options::bt_blocks_per_cu, 0, 8},
     {"dwbt_f32_all", &Options::dwbt_f32_all, 0, 1}, {"bt_m2", &Options::bt_m2, 0, 1},

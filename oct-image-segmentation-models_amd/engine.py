@@ -182,6 +182,8 @@ class UNetEngine:
                 raise OctError(f"class_weight must have {self.cfg.n_cls} entries")
         self._focal_cw = cw          # keep the device buffer alive: the library only stores the pointer
         self._focal_active = float(focal_loss_weight) > 0.0
+        if self._focal_active:
+            self._bce_active = False     # the library clears it too: the two losses share one slot of the Dice rows
         with torch.cuda.device(self.device):
             _hip.check(_hip.lib().oct_unet_set_focal_dice(self._h, float(focal_loss_weight), float(gamma),
                                                           cw.data_ptr() if cw is not None else None), "oct_unet_set_focal_dice")
@@ -191,6 +193,23 @@ class UNetEngine:
         out = torch.empty(8, dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
             _hip.check(_hip.lib().oct_unet_loss_focal_dice(self._h, smooth, out.data_ptr(), self._stream()), "oct_unet_loss_focal_dice")
+        return out
+
+    def set_bce_dice(self, on: bool = True) -> None:
+        """Select ``bce_dice_loss`` (reference custom_losses.py:84-91) for the following forward / loss / backward calls:
+        L = mean over (B,H,W,C) of the binary cross-entropy + dice_loss_micro.  Clears a selected focal_dice_loss;
+        ``on=False`` restores the plain Dice losses.  ``backward`` then takes ``macro=False`` only."""
+        self._bce_active = bool(on)
+        if self._bce_active:
+            self._focal_active = False
+        with torch.cuda.device(self.device):
+            _hip.check(_hip.lib().oct_unet_set_bce_dice(self._h, int(bool(on))), "oct_unet_set_bce_dice")
+
+    def loss_bce_dice(self, smooth: float = 1e-5) -> torch.Tensor:
+        """loss_dice() + [bce mean, 0, bce + dice_loss_micro, 0] (device tensor, 8 floats)."""
+        out = torch.empty(8, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _hip.check(_hip.lib().oct_unet_loss_bce_dice(self._h, smooth, out.data_ptr(), self._stream()), "oct_unet_loss_bce_dice")
         return out
 
     def backward(self, labels: torch.Tensor, macro: bool = True, loss_scale: float = 1.0):

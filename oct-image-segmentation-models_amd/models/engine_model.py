@@ -156,8 +156,8 @@ class Model:
     # ---- keras.Model surface -------------------------------------------------------------------------
     def compile(self, optimizer=None, loss=None, metrics=None, **kwargs):
         loss_name = getattr(loss, "oct_loss", None) if loss is not None else None
-        if loss is not None and loss_name not in ("dice_loss_macro", "dice_loss_micro", "focal_dice_loss"):
-            raise OctError("compile(loss=...): only the Dice losses and focal_dice_loss from common.custom_losses are "
+        if loss is not None and loss_name not in ("dice_loss_macro", "dice_loss_micro", "focal_dice_loss", "bce_dice_loss"):
+            raise OctError("compile(loss=...): only the Dice losses, focal_dice_loss and bce_dice_loss from common.custom_losses are "
                            "implemented by the HIP engine (the loss arithmetic is fused into the head kernels)")
         self._focal = dict(getattr(loss, "oct_focal", None) or {}) if loss_name == "focal_dice_loss" else None
         metric_name = None
@@ -324,7 +324,8 @@ class Model:
 
     def _run_epoch(self, seq, training: bool, rank: int, world: int):
         focal = getattr(self, "_focal", None)
-        macro = focal["dice_macro"] if focal else self._loss_name != "dice_loss_micro"
+        bce = self._loss_name == "bce_dice_loss"        # bce + dice_loss_micro: the micro combination only
+        macro = focal["dice_macro"] if focal else self._loss_name not in ("dice_loss_micro", "bce_dice_loss")
         acc = None
         n = len(seq)
         # the upload of batch i+1 (host gather -> pinned buffers -> H2D on the copy stream) is queued before step i is
@@ -346,8 +347,12 @@ class Model:
                 eng.set_focal_dice(focal["focal_loss_weight"], focal["gamma"], focal["class_weight"])
             elif getattr(eng, "_focal_active", False):
                 eng.set_focal_dice(0.0)     # an engine last used by a focal model goes back to the plain Dice losses
+            if bce:
+                eng.set_bce_dice(True)
+            elif getattr(eng, "_bce_active", False):
+                eng.set_bce_dice(False)     # ... and one last used by a BCE model too
             eng.forward(x, training=training, labels=lab, want_probs=False)
-            loss4 = eng.loss_focal_dice() if focal else eng.loss_dice()
+            loss4 = eng.loss_focal_dice() if focal else (eng.loss_bce_dice() if bce else eng.loss_dice())
             if training:
                 red = getattr(self, "_reducer", None)
                 if red is None or red.engine is not eng:       # _ensure_engine may have built a new engine
@@ -363,7 +368,7 @@ class Model:
         if world > 1:
             torch.distributed.all_reduce(acc); acc /= world
         v = acc.cpu().numpy()
-        out = {"loss": float((v[5] if macro else v[6]) if focal else (v[0] if macro else v[1]))}
+        out = {"loss": float((v[5] if macro else v[6]) if (focal or bce) else (v[0] if macro else v[1]))}
         if self._metric_name:
             out[self._metric_name] = float(v[2] if self._metric_name == "dice_coef_macro" else v[3])
         return out
