@@ -366,7 +366,10 @@ int oct_minpath_device(const unsigned char* maps_dev, int B, int M, int H, int W
  *   "dwpair8_enable" (default 1): backward-weights of 3x3 layers with 8 output channels on the pixel-pair kernel
  *   (0 = the padded 16-column kernel).
  *   "pair8_geometry" (NWY*100 + NWX*10 + RPW in {221, 111}, default 221): waves per block (rows x columns)
- *   and 4-row groups per wave of that kernel; its tile is (4*RPW*NWY) x (32*NWX) pixels. */
+ *   and 4-row groups per wave of that kernel; its tile is (4*RPW*NWY) x (32*NWX) pixels.
+ *   "persistent_max_blocks" (default 0 = no cap; 0 .. 1 << 20, anything else is an error): for tests: caps the grid of
+ *   every persistent launch so that small images make blocks walk several tiles.  The statistic rows and backward-weights
+ *   slabs of a launch follow the capped grid.  May be set on a live handle. */
 int oct_set_option(const char* name, int value);
 int oct_get_option(const char* name, int* value);
 int oct_unet_get_option(const oct_unet* h, const char* name, int* value);

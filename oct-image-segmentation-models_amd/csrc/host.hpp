@@ -6,6 +6,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -55,6 +56,8 @@ struct Options {
                                     // pair with backward-data launches of the next level, which they slow down more
     int event_sysfence = 0;         // 1: the handle's fork/join events carry a system-scope fence (set before oct_unet_create)
     int persist_min_tiles = 2048;   // pixel tiles from which thin single-chunk convs use the persistent pipelined kernel
+    int max_blocks = 0;             // FOR TESTS ("persistent_max_blocks"): > 0 caps the grid of every persistent launch, so that
+                                    // small images make blocks walk several tiles (cap_grid below); 0 = the launches' own grids
 };
 extern Options g_opt;
 
@@ -96,6 +99,9 @@ struct ProfScope {
 #define AT_NAME(bf) ((bf) ? "unsigned short" : "float")
 
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+// the grid of a persistent launch (blocks that walk pixel tiles; one statistic row / dW slab per block) under the
+// "persistent_max_blocks" test cap: every such launch sizes its grid, its rows and its slabs through here
+inline int cap_grid(int grid, const Options& o) { return o.max_blocks > 0 ? std::min(grid, o.max_blocks) : grid; }
 inline int bx_mb(int M) { return M % 64 == 0 ? 64 : 32; }
 inline bool bt_k_ok(int k) { return k == 8 || k == 16 || k == 32; }
 

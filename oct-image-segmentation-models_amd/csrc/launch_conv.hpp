@@ -32,7 +32,7 @@ int launch_igemm_geo(IgemmArgs a, const LaunchCtx& c, int* rows) {
 template <int SHAPE, int KH, int AMODE, int EPI, int TH, int MB, int WN, int KCP>
 int launch_igemm_p(IgemmArgs a, const LaunchCtx& c, int* rows) {
     a.tiles_x = cdiv(a.Wo, 32); a.tiles = a.tiles_x * cdiv(a.Ho, TH); a.total_tiles = c.B * a.tiles;
-    const int nblk = std::min(a.total_tiles, c.o->igemm_p_blocks);    // ~5 resident blocks per CU
+    const int nblk = cap_grid(std::min(a.total_tiles, c.o->igemm_p_blocks), *c.o);    // ~5 resident blocks per CU
     dim3 grid(nblk, cdiv(a.Mout, MB), 1), block(kBlock);
     char nm[64]; snprintf(nm, sizeof nm, "conv_igemm_p_k<%d,%d,%d,%d,%d,%d,%d,%d,%s>", SHAPE, KH, AMODE, EPI, TH, MB, WN, KCP, AT_NAME(a.act_bf16));
     ProfScope ps(c.s, nm, c.layer, c.flops, c.bytes);
@@ -57,7 +57,7 @@ int launch_pair8_geo(IgemmArgs a, const LaunchCtx& c, int* rows) {
         AT_DISPATCH(bf, if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, conv_pair8_k<EPI, CMAX, DEPTH, NWY, NWX, RPW, AT>, NT, 0) != hipSuccess) nb = 0);
         occ[bf] = nb < 1 ? 2 : nb;
     }
-    const int nblk = std::min(a.total_tiles, occ[bf] * 256);
+    const int nblk = cap_grid(std::min(a.total_tiles, occ[bf] * 256), *c.o);
     char nm[80]; snprintf(nm, sizeof nm, "conv_pair8_k<%d,%d,%d,%d,%d,%d,%s>", EPI, CMAX, DEPTH, NWY, NWX, RPW, AT_NAME(a.act_bf16));
     ProfScope ps(c.s, nm, c.layer, c.flops, c.bytes);
     AT_DISPATCH(bf, conv_pair8_k<EPI, CMAX, DEPTH, NWY, NWX, RPW, AT><<<nblk, NT, 0, c.s>>>(a, a.w, reinterpret_cast<AT*>(a.out)));
@@ -80,7 +80,7 @@ int launch_pair8(const IgemmArgs& a, const LaunchCtx& c, int* rows) {
 template <int KH, int AMODE, int EPI>
 int launch_thin8(IgemmArgs a, const LaunchCtx& c, int* rows) {
     a.tiles_x = cdiv(a.Wo, 64); a.tiles = a.tiles_x * cdiv(a.Ho, 8); a.total_tiles = c.B * a.tiles;
-    const int nblk = std::min(a.total_tiles, 1536);
+    const int nblk = cap_grid(std::min(a.total_tiles, 1536), *c.o);
     char nm[64]; snprintf(nm, sizeof nm, "conv_thin8_k<%d,%d,%d,%d,%s>", KH, AMODE, EPI, a.Cin <= 8 ? 8 : 16, AT_NAME(a.act_bf16));
     ProfScope ps(c.s, nm, c.layer, c.flops, c.bytes);
     if (a.Cin <= 8) AT_DISPATCH(a.act_bf16, conv_thin8_k<KH, AMODE, EPI, 8, AT><<<nblk, kBlock, 0, c.s>>>(a, a.w, reinterpret_cast<AT*>(a.out)));
@@ -158,7 +158,7 @@ int launch_bt(IgemmArgs a, const LaunchCtx& c, int* rows) {
     const bool fdw = a.dw_part != nullptr;                          // the launch also reduces the layer's backward-weights (FDW)
     const int per_cu = bt_per_cu(a.Cin, fdw);                       // the instantiation's __launch_bounds__
     const int want = c.o->bt_blocks_per_cu;
-    const int nblk = std::min(a.total_tiles, want > 0 ? 256 * std::min(want, per_cu) : 256 * per_cu);
+    const int nblk = cap_grid(std::min(a.total_tiles, want > 0 ? 256 * std::min(want, per_cu) : 256 * per_cu), *c.o);
     const int bf = a.act_bf16 ? 1 : 0;
     const bool m2 = a.bt_m2 && pipe_fit(a.Cin, a.Mout, a.m_off, a.flags & F_TWO, a.C0, AMODE).m2;
     const bool gb = a.gb_z != nullptr;

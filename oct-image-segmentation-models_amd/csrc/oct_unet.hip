@@ -423,7 +423,7 @@ int conv_forward(oct_unet* h, int li, const void* x_in, int x_is_u8, int B, int 
                              : launch_igemm<3, A_NORMAL, EPI_FWD>(g, rt, lc, &stat_rows);
     } else if (l.src == SRC_INPUT && l.cin == 1 && l.cout == 8 && l.kh == 3) {   // the real first layer: persistent streaming kernel
         const int tx = cdiv(l.W, 128), tiles = tx * cdiv(l.H, 8), total = B * tiles;
-        const int grid = std::min(total, 2048);      // <= B*ceil(H/2)*ceil(W/32) statistic rows guaranteed by carve()
+        const int grid = cap_grid(std::min(total, 2048), h->opt);      // <= B*ceil(H/2)*ceil(W/32) statistic rows guaranteed by carve()
         const int bf = h->cfg.dtype;
         if (training && fin_ok(h, l)) { a.fin = fin_desc(h, li, 0, B); fin_in_launch = true; }
         ProfScope ps(s, bf ? "conv_first_fwd_k<unsigned short>" : "conv_first_fwd_k<float>", l.name, fl, by);
@@ -631,7 +631,7 @@ int plan_backward(oct_unet* h, int B) {
         BwdRoute& r = h->route[li];
         r = BwdRoute{};
         r.dw = dw_plan(l, B, o.mfma_mode, h->cfg.dtype, o);
-        r.dw.npb = std::min(r.dw.npb, l.dw_rows);
+        r.dw.npb = cap_grid(std::min(r.dw.npb, l.dw_rows), o);
         // The block's BN-backward transform dz = ga g' + gb z + gd is applied by the consumers of dz while they stage it --
         // the backward-weights kernel and the backward-data launches -- whenever all of them can (the bf16-pipe conv kernels
         // and every MFMA backward-weights kernel); otherwise by the stand-alone pass, in place.
@@ -682,7 +682,7 @@ int plan_backward(oct_unet* h, int B) {
         // 3x3 layers with 8 output channels on the thin kernel (the full-resolution convs): their backward-data launches
         // reduce the backward-weights too (conv_bt_k FDW) -- g', z and the producer's z are read once for both
         r.fdw = r.fuse && o.fuse_dw_thin && l.kh == 3 && l.cout == 8 && !l.drop_in && (l.src == SRC_PREV || l.src == SRC_CONCAT) &&
-                cg == 8 && l.dw_rows >= std::min(B * cdiv(l.W, 32) * cdiv(l.H, 8), 512) &&      // (one slab per block of that launch)
+                cg == 8 && l.dw_rows >= cap_grid(std::min(B * cdiv(l.W, 32) * cdiv(l.H, 8), 512), o) &&      // (one slab per block of that launch)
                 all_bt;
     }
     return 0;
@@ -1291,7 +1291,7 @@ const Opt k_opts[] = {
     {"fuse_first_apply", &Options::fuse_first_apply, 0, 1}, {"fuse_bn_apply", &Options::fuse_bn_apply, 0, 1},
     {"fuse_bn_finalize", &Options::fuse_bn_finalize, 0, 1}, {"bx_waves", &Options::bx_waves, 4, 8},
     {"dw_side_stream", &Options::dw_side_stream, 0, 1}, {"timing_skip", &Options::timing_skip, 0, 255}, {"fuse_dw_thin", &Options::fuse_dw_thin, 0, 1},
-    {"dwbx_enable", &Options::dwbx_enable, 0, 1},
+    {"dwbx_enable", &Options::dwbx_enable, 0, 1}, {"persistent_max_blocks", &Options::max_blocks, 0, 1 << 20},
     {"bx_two_blocks", &Options::bx_two_blocks, 0, 1}, {"fork_on_launch", &Options::fork_on_launch, 0, 1},
     {"event_sysfence", &Options::event_sysfence, 0, 1}, {"dw_fork_group", &Options::dw_fork_group, 1, 8}, {"fuse_bn_apply16", &Options::fuse_bn_apply16, 0, 1},
 };
@@ -1300,9 +1300,10 @@ const Opt* find_opt(const char* name) {
     fail(-1, std::string("unknown option: ") + name);
     return nullptr;
 }
-int check_opt(const char* name, int value) {     // the two options whose valid values are not a range
+int check_opt(const char* name, int value) {     // the options whose valid values are not a clamped range
     if (!strcmp(name, "pair8_geometry") && value != 221 && value != 111) return fail(-1, "pair8_geometry must be 221 or 111");
     if (!strcmp(name, "bx_waves") && value != 4 && value != 8) return fail(-1, "bx_waves must be 4 or 8");
+    if (!strcmp(name, "persistent_max_blocks") && (value < 0 || value > (1 << 20))) return fail(-1, "persistent_max_blocks must be 0 (no cap) .. 1048576");
     return 0;
 }
 int get_opt(const Options& from, const char* name, int* value) {

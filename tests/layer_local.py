@@ -78,11 +78,11 @@ def _bt_k(k):
     return k in (8, 16, 32)
 
 
-def bf16_fwd_operands(plan, li, cfg, mfma_mode):
+def bf16_fwd_operands(plan, li, cfg, mfma_mode, training=True):
     sp = plan[li]
     if not mfma_mode or sp.src == "input" or not sp.has_bn:
         return False
-    drop = sp.name == "dec0.up" and cfg.dropout_rate > 0
+    drop = training and sp.name == "dec0.up" and cfg.dropout_rate > 0      # (conv_forward: dropout only in a training forward)
     two_ok = sp.src != "concat" or plan[li - 1].cout % 8 == 0
     thin = sp.cout <= 16 and sp.cout % 4 == 0 and _bt_k(sp.cin) and not drop and two_ok
     wide = sp.cout % 32 == 0 and sp.cin % 8 == 0 and sp.cin <= 512 and two_ok
@@ -519,7 +519,7 @@ class LayerLocal:
         self._zsums = {}
         for li, sp in enumerate(self.plan):
             p = self.P[li]
-            rnd = bf and bf16_fwd_operands(self.plan, li, self.cfg, self.mm)
+            rnd = bf and bf16_fwd_operands(self.plan, li, self.cfg, self.mm, self.training)
             w = t_bf16(p["kernel"]) if rnd else p["kernel"]
             if sp.has_bn:
                 gate = ElementGate(self.rep, sp.name, "z", self.mode, rel_l2=self._rel_l2(li, False))

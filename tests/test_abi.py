@@ -103,3 +103,22 @@ def test_glorot_init_statistics(hip):
     assert abs(k.max() - lim) < 1e-3 * lim + 1e-4 and abs(k.std() - lim / np.sqrt(3)) < 0.01 * lim
     assert np.all(p[L["gamma_off"]:L["gamma_off"] + 128] == 1) and np.all(p[L["bias_off"]:L["bias_off"] + 128] == 0)
     assert np.all(s[L["moving_var_off"]:L["moving_var_off"] + 128] == 1)
+
+
+def test_persistent_max_blocks_round_trip_and_range(hip):
+    """The grid cap for tests: default 0 (no cap), any value in 0 .. 1 << 20 reads back as set, anything else is an error
+    that leaves the value alone (unlike the tuning knobs, which clamp: a clamped cap would silently test another grid)."""
+    from oct_image_segmentation_models_amd._hip import OctError
+    assert hip.get_option("persistent_max_blocks") == 0
+    try:
+        for v in (8, 12, 1, 1 << 20, 0, 16):
+            hip.set_option("persistent_max_blocks", v)
+            assert hip.get_option("persistent_max_blocks") == v
+        for bad in (-1, (1 << 20) + 1, -(1 << 31)):
+            with pytest.raises(OctError, match="persistent_max_blocks"):
+                hip.set_option("persistent_max_blocks", bad)
+            assert hip.get_option("persistent_max_blocks") == 16
+    finally:
+        hip.set_option("persistent_max_blocks", 0)
+    with pytest.raises(OctError, match="unknown option"):
+        hip.get_option("persistent_max_block")

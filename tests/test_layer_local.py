@@ -188,6 +188,37 @@ def test_model_matches_the_bf16_rounding_rules(geo):
         assert rel(m.kept[sp.name]["grads"][0]["kernel"], S.grads[li]["kernel"]) <= 1e-12, sp.name
 
 
+def test_bf16_operand_rule_of_the_up_conv_behind_the_dropout_follows_the_forward():
+    """dec0.up reads the dropped tensor.  In a TRAINING forward the thin bf16-pipe kernel cannot apply the dropout, so the
+    32 -> 16 up-conv of start_neurons 8, pool_layers 2 runs on the fp32 pipe (stored activations x fp32 weights); in
+    inference there is no dropout and it runs on the bf16 pipe with both operands rounded (conv_forward: drop = training &&
+    drop_in).  The wide kernel applies the dropout itself: 64 -> 32 rounds in both."""
+    for P, thin in ((2, True), (3, False)):
+        cfg = on.UNetConfig(num_classes=C, start_neurons=8, pool_layers=P)
+        plan = on.build_plan(cfg)
+        li = [sp.name for sp in plan].index("dec0.up")
+        assert (plan[li].cin, plan[li].cout) == ((32, 16) if thin else (64, 32))
+        assert ll.bf16_fwd_operands(plan, li, cfg, 1, training=True) == (not thin)
+        assert ll.bf16_fwd_operands(plan, li, cfg, 1) == (not thin)                  # (the default is the training forward)
+        assert ll.bf16_fwd_operands(plan, li, cfg, 1, training=False)
+        assert not ll.bf16_fwd_operands(plan, li, cfg, 0, training=False)            # fp32 pipe everywhere
+        others = [k for k in range(len(plan)) if k != li]
+        assert all(ll.bf16_fwd_operands(plan, k, cfg, 1, True) == ll.bf16_fwd_operands(plan, k, cfg, 1, False) for k in others)
+    # and the inference model applies it: with the weights of dec0.up rounded its z differs from the unrounded product
+    cfg, p64, s64, images, _, _ = setup(P=2)
+    plan = on.build_plan(cfg)
+    li = [sp.name for sp in plan].index("dec0.up")
+    _, cache = on.forward(cfg, p64, s64, on.preprocess_u8(images, np.float64), training=False)
+    S = ll.Stored(z=[torch.from_numpy(ll.bf16_round(cache[k]["z"])) for k in range(len(plan) - 1)], probs=torch.from_numpy(cache[-1]["z"] * 0))
+    m = ll.LayerLocal(cfg, p64, S, images, training=False, state=s64, mode="bf16", chunk=2, keep=True)
+    m.check_forward()
+    x = m.kept_tensor("dec0.up", "x")
+    unrounded = on.conv2d_same(np.asarray(x), p64[li]["kernel"], p64[li]["bias"])
+    rounded = on.conv2d_same(ll.bf16_round(np.asarray(x)), ll.bf16_round(p64[li]["kernel"]), p64[li]["bias"])
+    z = np.asarray(m.kept_tensor("dec0.up", "z"))
+    assert rel(z, rounded) <= 1e-12 and rel(z, unrounded) > 1e-4
+
+
 def test_inference_model_matches_the_oracle():
     cfg, p64, s64, images, _, _ = setup()
     probs, cache = on.forward(cfg, p64, s64, on.preprocess_u8(images, np.float64), training=False)
