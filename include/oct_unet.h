@@ -304,6 +304,24 @@ int oct_minpath_device(const unsigned char* maps_dev, int B, int M, int H, int W
                        unsigned short* rows_out_dev /* (B, M, W) */, double* cost_out_dev /* (B, M) */,
                        unsigned char* tied_out_dev /* (B, M) */, oct_stream_t stream);
 
+/* ---- evaluation Dice on the device (csrc/kernels_dice.hpp; host restatements: evaluation/dice_device.py) ----
+ * Both calls are stand-alone (no handle), allocate nothing, are asynchronous on `stream`, never wait for it and record
+ * into a stream capture.  Argument errors return a negative code with oct_last_error() and launch nothing.
+ *
+ * oct_confusion_counts: counts[b][g * n_cls + p] = number of pixels of image b with gt == g and pred == p, for (B,H,W)
+ * uint8 class maps; the last word of a row counts the pixels where either label is >= n_cls, which appear nowhere else
+ * in the row.  The call overwrites counts_dev (zeroing is part of it).  1 <= B <= 65535, H*W < 2^32, 2 <= n_cls <= 32.
+ * Every Dice metric of the evaluation is a function of one row (dice_from_counts).
+ *
+ * oct_area_labels: the class map, in the (H,W) frame, that graph-search delineations enclose -- exactly
+ * common/utils.py::labels_from_delineations.  Per column, with M = n_cls - 1 and s_i = segs[b][i][col]: going up in i,
+ * s_i == 0 becomes the first non-zero s_j with j > i, or H; row r then gets M if r >= s_{M-1}, else the largest k in
+ * 1..M-1 with s_{k-1} <= r < s_k, else 0.  Boundaries may cross; values >= H reach no row.  H <= 65535, else as above. */
+int oct_confusion_counts(const unsigned char* pred_dev, const unsigned char* gt_dev, int B, int H, int W, int n_cls,
+                         unsigned int* counts_dev /* (B, n_cls*n_cls + 1) */, oct_stream_t stream);
+int oct_area_labels(const unsigned short* segs_dev /* (B, n_cls-1, W) */, int B, int H, int W, int n_cls,
+                    unsigned char* labels_dev /* (B, H, W) */, oct_stream_t stream);
+
 /* ---- options ----
  * oct_set_option edits the PROCESS-WIDE DEFAULTS; a handle copies them when it is created (oct_unet_create) and every
  * launch of that handle reads its own copy: changing an option never affects a live handle, and two handles created

@@ -101,6 +101,8 @@ SYMBOLS = [
     ("oct_minpath_workspace_bytes", C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     ("oct_minpath_device", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("oct_confusion_counts", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    ("oct_area_labels", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     ("oct_set_option", C.c_int, [C.c_char_p, C.c_int]),
     ("oct_get_option", C.c_int, [C.c_char_p, _P(C.c_int)]),
     ("oct_unet_get_option", C.c_int, [C.c_void_p, C.c_char_p, _P(C.c_int)]),

@@ -1,0 +1,192 @@
+"""The evaluation's Dice metrics and graph-search class maps from the device.
+
+Every Dice metric ``evaluate_model`` writes (``dice_coef_classes`` / ``_macro`` / ``_micro``, reference
+evaluation/evaluation.py:175-208 and :335-375) is a function of the per-image confusion matrix ``n[g][p]`` -- the number
+of pixels with ground truth ``g`` and prediction ``p`` -- and the class map that graph-search delineations enclose
+(``common.utils.labels_from_delineations``) has a closed form per pixel.  ``ConfusionCounts`` and ``AreaLabels`` run the
+two kernels (``oct_confusion_counts`` / ``oct_area_labels``, include/oct_unet.h) on the current stream;
+``confusion_counts_reference`` and ``area_labels_reference`` are the numpy restatements they are tested against, and
+``dice_from_counts`` turns one matrix into exactly what ``evaluation._dice_metrics`` returns for the image."""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional, Tuple
+
+import numpy as np
+import torch
+
+from .. import _hip
+from ..common import (EVALUATION_METRIC_DICE_CLASSES, EVALUATION_METRIC_DICE_MACRO, EVALUATION_METRIC_DICE_MICRO)
+
+DICE_METRICS = (EVALUATION_METRIC_DICE_CLASSES, EVALUATION_METRIC_DICE_MACRO, EVALUATION_METRIC_DICE_MICRO)
+MAX_CLASSES = 32
+# The host sums one-hot float32 arrays: such a sum is exact while it stays <= 2^24.  soft_dice_class sums pred + true
+# elementwise, up to 2 H W per class, so the host's own values are order-independent (and dice_from_counts equals them bit
+# for bit) while H * W <= 2^23; above that the workflows keep the host path.
+MAX_EXACT_PIXELS = 1 << 23
+
+
+def confusion_counts_reference(pred: np.ndarray, gt: np.ndarray, num_classes: int) -> np.ndarray:
+    """(n,H,W) class maps -> (n, C*C + 1) uint32: word ``g*C + p`` counts the pixels with gt == g and pred == p, the last
+    word those where either label is >= C (they appear nowhere else in the row)."""
+    pred, gt, Cc = np.asarray(pred).astype(np.int64), np.asarray(gt).astype(np.int64), int(num_classes)
+    if pred.shape != gt.shape or pred.ndim != 3:
+        raise ValueError("pred and gt must be (n,H,W) class maps of one shape")
+    bad = (pred < 0) | (pred >= Cc) | (gt < 0) | (gt >= Cc)
+    key = np.where(bad, Cc * Cc, gt * Cc + pred).reshape(pred.shape[0], -1)
+    return np.stack([np.bincount(k, minlength=Cc * Cc + 1) for k in key]).astype(np.uint32)
+
+
+def area_labels_reference(segs: np.ndarray, H: int, W: int) -> np.ndarray:
+    """Delineations (n, M, W) or (M, W) -> the class maps (n,H,W) / (H,W) uint8 that ``labels_from_delineations`` gives,
+    in the (H,W) frame.  Per column: going up in i, a zero s_i becomes the first non-zero s_j with j > i, or H; row r gets
+    M if r >= s_{M-1}, else the largest k in 1..M-1 with s_{k-1} <= r < s_k (the host loop's sequential overwrites), else 0."""
+    s = np.asarray(segs).astype(np.int64)
+    single = s.ndim == 2
+    if single:
+        s = s[None]
+    n, M = s.shape[:2]
+    if s.shape[2] != W:
+        raise ValueError(f"segs must have {W} columns")
+    nxt = np.full((n, W), H, np.int64)
+    for i in range(M - 1, -1, -1):
+        nxt = np.where(s[:, i] == 0, nxt, s[:, i])
+        s[:, i] = nxt
+    r = np.arange(H, dtype=np.int64)[None, :, None]
+    lab = np.zeros((n, H, W), np.uint8)
+    for k in range(1, M):
+        lab[(s[:, k - 1, None, :] <= r) & (r < s[:, k, None, :])] = k
+    lab[r >= s[:, M - 1, None, :]] = M
+    return lab[0] if single else lab
+
+
+def counts_matrix(rows: np.ndarray, num_classes: int, first_image: int = 0) -> np.ndarray:
+    """(n, C*C + 1) rows of the device -> (n, C, C) uint32; a non-zero out-of-range word raises with the image index."""
+    rows = np.asarray(rows).view(np.uint32) if np.asarray(rows).dtype == np.int32 else np.asarray(rows, np.uint32)
+    Cc = int(num_classes)
+    bad = np.nonzero(rows[:, Cc * Cc])[0]
+    if bad.size:
+        i = int(bad[0])
+        raise ValueError(f"image {first_image + i}: {int(rows[i, Cc * Cc])} pixels carry a label outside 0..{Cc - 1}")
+    return rows[:, :Cc * Cc].reshape(-1, Cc, Cc).copy()
+
+
+def dice_from_counts(counts: np.ndarray, metrics) -> Tuple[Optional[np.ndarray], Optional[np.ndarray], Optional[np.ndarray]]:
+    """One image's confusion matrix (C, C) (rows: ground truth, columns: prediction) -> (dice_classes (1, C) float32,
+    dice_macro, dice_micro 0-d float32; None for a metric not in ``metrics``): the values, dtypes and shapes of
+    ``evaluation._dice_metrics`` for that image, in its plain and its transposed form alike.  The host works in float32 on
+    one-hot arrays; its sums are the integers below (exact in float32 up to ``MAX_EXACT_PIXELS``), and the expressions
+    that follow them are repeated here operation by operation."""
+    n = np.asarray(counts).astype(np.int64)
+    if n.ndim != 2 or n.shape[0] != n.shape[1]:
+        raise ValueError("counts must be one (C, C) confusion matrix")
+    inter = np.diagonal(n).astype(np.float32)[None, :]                 # sum(true * pred) per class
+    true, pred = n.sum(axis=1).astype(np.float32)[None, :], n.sum(axis=0).astype(np.float32)[None, :]
+    dc = dm = dmi = None
+    if EVALUATION_METRIC_DICE_CLASSES in metrics:                      # custom_metrics.soft_dice_class
+        dc = ((2.0 * inter) + 1e-5) / ((pred + true) + 1e-5)
+    if EVALUATION_METRIC_DICE_MACRO in metrics:                        # custom_metrics.dice_coef_macro
+        dm = np.array(np.mean((2.0 * inter + 1e-05) / ((true + pred) + 1e-05)))
+    if EVALUATION_METRIC_DICE_MICRO in metrics:                        # custom_metrics.dice_coef_micro
+        total = np.float32(n.sum())
+        with np.errstate(invalid="ignore", divide="ignore"):
+            dmi = np.array(np.float32(2.0) * np.float32(np.trace(n)) / (total + total))
+    return dc, dm, dmi
+
+
+def _check_maps(device, H, W, *maps):
+    for t in maps:
+        if t.device != device or t.dtype != torch.uint8 or not t.is_contiguous() or t.dim() != 3 \
+                or tuple(t.shape[1:]) != (H, W):
+            raise _hip.OctError(f"class maps must be contiguous uint8 (n,{H},{W}) tensors on {device}")
+
+
+class ConfusionCounts:
+    """``oct_confusion_counts`` for up to ``batch`` images of one shape: ``(pred, gt)`` -> (n, C*C + 1) int32 rows on the
+    device (the bits are the uint32 counts), queued on the current stream."""
+
+    def __init__(self, batch: int, H: int, W: int, num_classes: int, device):
+        self.B, self.H, self.W, self.C = int(batch), int(H), int(W), int(num_classes)
+        if not (1 <= self.B <= 65535 and self.H >= 1 and self.W >= 1 and self.H * self.W < 1 << 32
+                and 2 <= self.C <= MAX_CLASSES):
+            raise _hip.OctError(f"oct_confusion_counts does not support B={batch}, {H}x{W}, {num_classes} classes")
+        self.device = torch.device(device)
+        self.out = torch.empty((self.B, self.C * self.C + 1), dtype=torch.int32, device=self.device)
+
+    def __call__(self, pred: torch.Tensor, gt: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        _check_maps(self.device, self.H, self.W, pred, gt)
+        n = pred.shape[0]
+        if gt.shape[0] != n or not 1 <= n <= self.B:
+            raise _hip.OctError(f"pred and gt need the same count n in 1..{self.B}")
+        if out is None:
+            out = self.out[:n]
+        elif out.device != self.device or out.dtype != torch.int32 or not out.is_contiguous() \
+                or tuple(out.shape) != (n, self.C * self.C + 1):
+            raise _hip.OctError(f"out must be a contiguous int32 ({n},{self.C * self.C + 1}) tensor on {self.device}")
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        with torch.cuda.device(self.device):
+            _hip.check(_hip.lib().oct_confusion_counts(pred.data_ptr(), gt.data_ptr(), n, self.H, self.W, self.C,
+                                                       out.data_ptr(), stream), "oct_confusion_counts")
+        return out
+
+    def to_host(self, rows: torch.Tensor, first_image: int = 0) -> np.ndarray:
+        """Device rows -> (n, C, C) uint32 on the host (waits for the stream); out-of-range labels raise."""
+        return counts_matrix(rows.cpu().numpy(), self.C, first_image)
+
+
+class AreaLabels:
+    """``oct_area_labels`` for up to ``batch`` images: delineations (n, C-1, W) int16 / uint16 on the device (the bits
+    are uint16 rows, as the searches emit them) -> (n,H,W) uint8 class maps on the device, queued on the current stream."""
+
+    def __init__(self, batch: int, H: int, W: int, num_classes: int, device):
+        self.B, self.H, self.W, self.C = int(batch), int(H), int(W), int(num_classes)
+        if not (1 <= self.B <= 65535 and 1 <= self.H <= 65535 and self.W >= 1 and self.H * self.W < 1 << 32
+                and 2 <= self.C <= MAX_CLASSES):
+            raise _hip.OctError(f"oct_area_labels does not support B={batch}, {H}x{W}, {num_classes} classes")
+        self.device = torch.device(device)
+        self.out = torch.empty((self.B, self.H, self.W), dtype=torch.uint8, device=self.device)
+
+    def __call__(self, segs: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if segs.device != self.device or segs.element_size() != 2 or segs.is_floating_point() or not segs.is_contiguous() \
+                or segs.dim() != 3 or tuple(segs.shape[1:]) != (self.C - 1, self.W):
+            raise _hip.OctError(f"segs must be a contiguous 16-bit integer (n,{self.C - 1},{self.W}) tensor on {self.device}")
+        n = segs.shape[0]
+        if not 1 <= n <= self.B:
+            raise _hip.OctError(f"segs needs a count n in 1..{self.B}")
+        if out is None:
+            out = self.out[:n]
+        else:
+            _check_maps(self.device, self.H, self.W, out)
+            if out.shape[0] != n:
+                raise _hip.OctError(f"out must hold {n} class maps")
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        with torch.cuda.device(self.device):
+            _hip.check(_hip.lib().oct_area_labels(segs.data_ptr(), n, self.H, self.W, self.C, out.data_ptr(), stream),
+                       "oct_area_labels")
+        return out
+
+
+class DelineationLabels:
+    """The stage behind ``InferenceRun.gs_labels``: a batch's final delineations (n, C-1, W) uint16 on the host -> the
+    class maps they enclose, (n,H,W) uint8 on the host, and with the batch's ground-truth class maps (n,H,W) the
+    (n, C, C) uint32 confusion counts of those maps against it (else None).  It owns its device buffers and uploads
+    both inputs itself; the call waits for the device."""
+
+    def __init__(self, batch: int, H: int, W: int, num_classes: int, device):
+        self.area = AreaLabels(batch, H, W, num_classes, device)
+        self.counts = ConfusionCounts(batch, H, W, num_classes, device)
+
+    def __call__(self, segs: np.ndarray, gt: Optional[np.ndarray] = None,
+                 first_image: int = 0) -> Tuple[np.ndarray, Optional[np.ndarray]]:
+        a, dev = self.area, self.area.device
+        segs = np.ascontiguousarray(segs)
+        if segs.dtype != np.uint16 or segs.ndim != 3 or segs.shape[1:] != (a.C - 1, a.W):
+            raise ValueError(f"delineations must be uint16 (n,{a.C - 1},{a.W}), not {segs.dtype} {segs.shape}")
+        labels_dev = a(torch.from_numpy(segs.view(np.int16)).to(dev))
+        counts = None
+        if gt is not None:
+            gt_u8 = np.ascontiguousarray(gt, dtype=np.uint8)
+            if gt_u8.shape != (segs.shape[0], a.H, a.W):
+                raise ValueError(f"ground truth of shape {gt_u8.shape}, expected {(segs.shape[0], a.H, a.W)}")
+            counts = self.counts.to_host(self.counts(labels_dev, torch.from_numpy(gt_u8).to(dev)), first_image)
+        return labels_dev.cpu().numpy(), counts

@@ -5,7 +5,9 @@ The forward pass is batched on the GPU (device arg-max, 1 B/px back to the host)
 ``predict`` call per image; everything after it -- one-hot, boundary maps, Dice
 metrics, optional graph search, per-image result files, dataset aggregates -- is the reference's host logic
 re-stated.  The surface-distance metrics (average surface distance, Hausdorff-95; :207-262) are computed on the
-device from the arg-max maps and the uploaded ground truth (``evaluation/surface.py``).  Under ``torchrun`` the test
+device from the arg-max maps and the uploaded ground truth (``evaluation/surface.py``).  With
+``EvaluationParameters(metrics_device=True)`` the Dice metrics come from confusion counts made on the device and the
+graph-search class maps from ``oct_area_labels`` (``evaluation/dice_device.py``): the same files, byte for byte.  Under ``torchrun`` the test
 set is sharded by contiguous index range (no collective); rank 0 aggregates.  PNG plots are out of scope."""
 from __future__ import annotations
 
@@ -25,6 +27,7 @@ from ..common import (EVALUATION_METRIC_AVERAGE_SURFACE_DISTANCE, EVALUATION_MET
 from ..common import utils as common_utils
 from ..min_path_processing import graph_search, utils
 from ..models import get_model_class
+from .dice_device import DICE_METRICS, MAX_EXACT_PIXELS, dice_from_counts
 from .evaluation_parameters import EvaluationParameters
 from .pipeline import InferenceRun
 from .surface import datasets as surface_datasets
@@ -79,6 +82,14 @@ def _dice_metrics(metrics, num_classes, label_onehot_hw, categorical_pred, trans
     return dc, dm, dmi
 
 
+def _batch_dice(metrics, num_classes, batch, k, label_onehot_hw, categorical_pred):
+    """Dice classes / macro / micro of image ``k`` of a batch: from the device's confusion counts where the batch carries
+    them (``Batch.confusion``), else from the one-hot arrays on the host.  The same values, dtypes and shapes either way."""
+    if batch.confusion is not None:
+        return dice_from_counts(batch.confusion[k], metrics)
+    return _dice_metrics(metrics, num_classes, label_onehot_hw, categorical_pred)
+
+
 def _surface_metrics(metrics, rows):
     """Per-image surface-distance datasets (evaluation.py:207-262) from one (C-1, 6) row block of the device, restricted
     to the metrics asked for."""
@@ -94,6 +105,9 @@ def _surface_metrics(metrics, rows):
 
 
 def evaluate_model(eval_params: EvaluationParameters) -> List[EvaluationOutput]:
+    """With ``eval_params.metrics_device`` the ``graph_time`` attribute of gs_evaluation_results.hdf5 is the time of the
+    batch's device stage (class maps of the delineations and their confusion counts) divided by the batch's image count,
+    not a per-image host time; it stays an attribute, and every dataset and CSV file equals the host path's."""
     rank, _, _ = parallel.init()
     world = parallel.world_size()
 
@@ -124,9 +138,18 @@ def evaluate_model(eval_params: EvaluationParameters) -> List[EvaluationOutput]:
     # ground-truth class maps, spacing (0.01111111, 0.01111111), percent 95
     want_surface = any(m in eval_params.metrics for m in (EVALUATION_METRIC_AVERAGE_SURFACE_DISTANCE,
                                                            EVALUATION_METRIC_HAUSDORFF_DISTANCE))
+    want_dice = any(m in eval_params.metrics for m in DICE_METRICS)
+    # metrics_device: Dice from device confusion counts, graph-search class maps from the device.  The host's float32 sums
+    # are exact (hence order-free, hence reproduced bit for bit) only up to MAX_EXACT_PIXELS: larger images keep the host path
+    metrics_device = bool(getattr(eval_params, "metrics_device", False))
+    if metrics_device and eval_images.shape[1] * eval_images.shape[2] > MAX_EXACT_PIXELS:
+        log.info(f"metrics_device: images above {MAX_EXACT_PIXELS} pixels keep the host metrics")
+        metrics_device = False
+    need_gt = want_surface or (metrics_device and want_dice)
+    gt_maps = np.squeeze(eval_labels[lo:hi], axis=3) if need_gt else None
     # BASELINE configs[4] path (evaluation/pipeline.py::InferenceRun): search mode, batch source and worker pools
     with InferenceRun(eval_params.loaded_model, eval_images[lo:hi], eval_params.batch_size, num_classes,
-                      gt=np.squeeze(eval_labels[lo:hi], axis=3) if want_surface else None,
+                      gt=gt_maps, surface=want_surface, confusion=metrics_device and want_dice,
                       graph_search=eval_params.graph_search, gsgrad=eval_params.gsgrad, gs_device=eval_params.gs_device,
                       gs_device_ties=eval_params.gs_device_ties, gs_workers=eval_params.gs_workers) as run:
         t_prev = time.time()
@@ -134,6 +157,11 @@ def evaluate_model(eval_params: EvaluationParameters) -> List[EvaluationOutput]:
             b0, b1 = lo + batch.lo, lo + batch.hi
             predict_time = (time.time() - t_prev) / (b1 - b0)
             gs_found = run.graph_search(batch, eval_segments[b0:b1])
+            gs_labels = gs_counts = None
+            if metrics_device and eval_params.graph_search:
+                start_stage_time = time.time()
+                gs_labels, gs_counts = run.gs_labels(batch, gs_found, gt_maps[batch.lo:batch.hi] if want_dice else None)
+                gs_stage_time = (time.time() - start_stage_time) / (b1 - b0)
             for ind in range(b0, b1):
                 eval_image, eval_image_name = eval_images[ind], eval_image_names[ind]
                 eval_seg, eval_image_output_dir = eval_segments[ind], eval_image_output_dirs[ind]
@@ -142,7 +170,8 @@ def evaluate_model(eval_params: EvaluationParameters) -> List[EvaluationOutput]:
                 predicted_labels = batch.labels[ind - b0:ind - b0 + 1].astype(np.int64)        # (1,H,W)
                 categorical_pred = common_utils.labels_to_categorical(predicted_labels, num_classes)
                 boundary_maps = batch.maps[ind - b0:ind - b0 + 1]   # == convert_predictions_to_maps_semantic(categorical_pred), on device
-                dice_classes, dice_macro, dice_micro = _dice_metrics(eval_params.metrics, num_classes, eval_label, categorical_pred)
+                dice_classes, dice_macro, dice_micro = _batch_dice(eval_params.metrics, num_classes, batch, ind - b0,
+                                                                   eval_label, categorical_pred)
                 surface_ds = _surface_metrics(eval_params.metrics, None if batch.surface is None else batch.surface[ind - b0])
 
                 predicted_labels = np.squeeze(predicted_labels, axis=0)
@@ -157,11 +186,17 @@ def evaluate_model(eval_params: EvaluationParameters) -> List[EvaluationOutput]:
                     eval_image_t = np.transpose(eval_image, axes=[1, 0, 2])
                     start_graph_time = time.time()
                     gs_pred_segs, errors = gs_found[ind - b0]      # == graph_search.segment_maps(boundary_maps_t, eval_seg, grid)
-                    gs_eval_label, reconstructed_maps = common_utils.labels_from_delineations(eval_image_t.shape, gs_pred_segs,
-                                                                                             num_classes)
-                    gs_dc, gs_dm, gs_dmi = _dice_metrics(eval_params.metrics, num_classes, eval_label, reconstructed_maps,
-                                                         transposed=True)
-                    graph_time = time.time() - start_graph_time
+                    if gs_labels is not None:
+                        gs_eval_label = gs_labels[ind - b0]
+                        gs_dc, gs_dm, gs_dmi = (dice_from_counts(gs_counts[ind - b0], eval_params.metrics) if want_dice
+                                                else (None, None, None))
+                        graph_time = gs_stage_time
+                    else:
+                        gs_eval_label, reconstructed_maps = common_utils.labels_from_delineations(eval_image_t.shape,
+                                                                                                 gs_pred_segs, num_classes)
+                        gs_dc, gs_dm, gs_dmi = _dice_metrics(eval_params.metrics, num_classes, eval_label,
+                                                             reconstructed_maps, transposed=True)
+                        graph_time = time.time() - start_graph_time
                     mean_abs_err, mean_err, abs_err_sd, err_sd = graph_search.calculate_overall_errors(errors)
                     _save_graph_based_evaluation_results(eval_params, eval_image_name, gs_eval_label, gs_pred_segs, gs_dc,
                                                          gs_dm, gs_dmi, errors, mean_abs_err, mean_err, abs_err_sd, err_sd,

@@ -24,7 +24,7 @@ class EvaluationParameters:
                  test_dataset_path: Path, save_foldername: Path, save_params: EvaluationSaveParams,
                  graph_search: bool, metrics: List[str], gsgrad=1, dice_errors: bool = True, binarize: bool = True,
                  bg_ilm: bool = True, bg_csi: bool = False, batch_size: int = 32, gs_device: bool = False,
-                 gs_device_ties: str = "host", gs_workers: Optional[int] = None):
+                 gs_device_ties: str = "host", gs_workers: Optional[int] = None, metrics_device: bool = False):
         self.model_path = Path(model_path)
         self.mlflow_tracking_uri = mlflow_tracking_uri
         self.mlflow_run_uuid = mlflow_run_uuid
@@ -50,6 +50,10 @@ class EvaluationParameters:
         self.gs_device = bool(gs_device)
         self.gs_device_ties = gs_device_ties
         self.gs_workers = gs_workers   # extension: host-search worker processes (None: the CPU share, 1: inline)
+        # extension: the Dice metrics from confusion counts made on the device and the graph-search class maps from
+        # oct_area_labels (evaluation/dice_device.py).  Every dataset and CSV file equals the host path's; the graph_time
+        # attribute becomes the batch's stage time divided by its image count
+        self.metrics_device = bool(metrics_device)
         self.loaded_model, self.model_config = utils.load_model_and_config(
             self.model_path, mlflow_tracking_uri=mlflow_tracking_uri, mlflow_run_uuid=mlflow_run_uuid)
         self.num_classes = self.loaded_model.output.shape[-1]

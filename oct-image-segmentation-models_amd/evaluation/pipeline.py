@@ -17,6 +17,7 @@ import torch
 
 from ..min_path_processing.device_search import DeviceMinPath, LazyPool, merge_ties
 from ..min_path_processing.pool import SegmentPool, default_workers
+from .dice_device import ConfusionCounts, DelineationLabels, counts_matrix
 from .surface import SurfaceDistances
 
 
@@ -29,6 +30,7 @@ class Batch(NamedTuple):
     maps: Optional[np.ndarray] = None              # (n, C-1, H, W) uint8 boundary maps
     surface: Optional[np.ndarray] = None           # (n, C-1, 6) float64 surface-distance rows
     minpath: Optional[Tuple[np.ndarray, ...]] = None   # rows (n, C-1, W) uint16, cost (n, C-1) float64, tied (n, C-1) bool
+    confusion: Optional[np.ndarray] = None         # (n, C, C) uint32 confusion counts [gt][pred] of labels against the ground truth
 
 
 class BatchedPredictor:
@@ -41,10 +43,14 @@ class BatchedPredictor:
 
     With ``minpath`` (a ``min_path_processing.device_search.DeviceMinPath`` for this batch, C-1 maps and shape) the min-path
     search runs on the boundary maps behind ``boundary_maps`` on the main stream and fills ``Batch.minpath``, downloaded
-    through pinned double buffers next to the labels and maps."""
+    through pinned double buffers next to the labels and maps.
+
+    With ``confusion`` (an ``evaluation.dice_device.ConfusionCounts`` for this batch and shape) the ground truth is
+    uploaded in the same way and ``oct_confusion_counts`` runs on the arg-max maps next to the surface distances;
+    ``Batch.confusion`` holds the matrices, and a label outside 0..C-1 raises when the batch is collected."""
 
     def __init__(self, engine, batch: int, want_maps: bool = True, bg_ilm: bool = True, bg_csi: bool = False,
-                 surface=None, minpath=None):
+                 surface=None, minpath=None, confusion=None):
         if not 1 <= batch <= engine.cfg.max_batch:
             raise ValueError(f"batch {batch} outside 1..max_batch={engine.cfg.max_batch}")
         self.eng, self.B, self.want_maps, self.bg = engine, int(batch), want_maps, (bg_ilm, bg_csi)
@@ -61,10 +67,17 @@ class BatchedPredictor:
         if surface is not None:
             if (surface.B, surface.H, surface.W, surface.C) != (self.B, H, W, C):
                 raise ValueError("surface: SurfaceDistances built for another batch / shape")
-            self.gt_pin = [torch.empty((self.B, H, W), dtype=torch.uint8).pin_memory() for _ in range(2)]
-            self.gt_dev = [torch.empty((self.B, H, W), dtype=torch.uint8, device=dev) for _ in range(2)]
             self.sd_dev = [torch.empty((self.B, C - 1, 6), dtype=torch.float64, device=dev) for _ in range(2)]
             self.sd_pin = [torch.empty((self.B, C - 1, 6), dtype=torch.float64).pin_memory() for _ in range(2)]
+        self.conf = confusion
+        if confusion is not None:
+            if (confusion.B, confusion.H, confusion.W, confusion.C) != (self.B, H, W, C):
+                raise ValueError("confusion: ConfusionCounts built for another batch / shape")
+            self.cf_dev = [torch.empty((self.B, C * C + 1), dtype=torch.int32, device=dev) for _ in range(2)]
+            self.cf_pin = [torch.empty((self.B, C * C + 1), dtype=torch.int32).pin_memory() for _ in range(2)]
+        if surface is not None or confusion is not None:
+            self.gt_pin = [torch.empty((self.B, H, W), dtype=torch.uint8).pin_memory() for _ in range(2)]
+            self.gt_dev = [torch.empty((self.B, H, W), dtype=torch.uint8, device=dev) for _ in range(2)]
         self.minpath = minpath
         if minpath is not None:
             if not want_maps:
@@ -83,10 +96,11 @@ class BatchedPredictor:
         images_u8 = np.ascontiguousarray(images_u8)
         if images_u8.dtype != np.uint8:
             raise TypeError("the batched pipeline takes raw uint8 images (the /255 happens on the device)")
-        surf = gt_u8 is not None
-        if surf:
-            if self.surf is None:
-                raise ValueError("ground-truth maps given to a BatchedPredictor built without surface=")
+        have_gt = gt_u8 is not None
+        surf, conf = have_gt and self.surf is not None, have_gt and self.conf is not None
+        if have_gt:
+            if not (surf or conf):
+                raise ValueError("ground-truth maps given to a BatchedPredictor built without surface= or confusion=")
             gt_u8 = np.ascontiguousarray(gt_u8)
             if gt_u8.dtype != np.uint8 or gt_u8.shape != images_u8.shape[:3]:
                 raise TypeError(f"gt_u8 must be uint8 class maps of shape {images_u8.shape[:3]}")
@@ -106,15 +120,15 @@ class BatchedPredictor:
                 # run (the device-side wait below only protects the staging buffer; no other host sync orders copy_in)
                 up_done[s].synchronize()
             self.x_pin[s][:hi - lo].copy_(torch.from_numpy(images_u8[lo:hi]))       # host gather into pinned memory
-            if surf:
+            if have_gt:
                 self.gt_pin[s][:hi - lo].copy_(torch.from_numpy(gt_u8[lo:hi]))
             with torch.cuda.stream(self.copy_in):
                 if i >= 2:
                     self.copy_in.wait_event(x_free[s])                                  # staging buffer consumed by batch i-2
-                    if surf:
+                    if have_gt:
                         self.copy_in.wait_event(gt_free[s])                             # gt maps of batch i-2 consumed
                 self.x_stage[s][:hi - lo].copy_(self.x_pin[s][:hi - lo], non_blocking=True)
-                if surf:
+                if have_gt:
                     self.gt_dev[s][:hi - lo].copy_(self.gt_pin[s][:hi - lo], non_blocking=True)
                 up_done[s].record(self.copy_in)
 
@@ -135,6 +149,9 @@ class BatchedPredictor:
             if surf:
                 # (the call waits for this stream once: it checks the labels on the device before the distance passes)
                 self.surf(self.lab_dev[s][:hi - lo], self.gt_dev[s][:hi - lo], out=self.sd_dev[s][:hi - lo])
+            if conf:
+                self.conf(self.lab_dev[s][:hi - lo], self.gt_dev[s][:hi - lo], out=self.cf_dev[s][:hi - lo])
+            if have_gt:
                 gt_free[s].record(main)
             if self.want_maps:
                 self.map_dev[s].copy_(eng.boundary_maps(self.am, bg_ilm=self.bg[0], bg_csi=self.bg[1]))
@@ -148,17 +165,19 @@ class BatchedPredictor:
                     self.map_pin[s].copy_(self.map_dev[s], non_blocking=True)
                 if surf:
                     self.sd_pin[s].copy_(self.sd_dev[s], non_blocking=True)
+                if conf:
+                    self.cf_pin[s].copy_(self.cf_dev[s], non_blocking=True)
                 if self.minpath is not None:
                     for t_pin, t_dev in zip(self.mp_pin[s], self.mp_dev[s]):
                         t_pin.copy_(t_dev, non_blocking=True)
                 out_done[s].record(self.copy_out)
             if pending is not None:
-                yield self._collect(*pending, surf)
+                yield self._collect(*pending, surf, conf)
             pending = (lo, hi, s, out_done[s])
         if pending is not None:
-            yield self._collect(*pending, surf)
+            yield self._collect(*pending, surf, conf)
 
-    def _collect(self, lo, hi, s, ev, surf=False):
+    def _collect(self, lo, hi, s, ev, surf=False, conf=False):
         ev.synchronize()
         labels = self.lab_pin[s][:hi - lo].numpy().copy()
         maps = self.map_pin[s][:hi - lo].numpy().copy() if self.want_maps else None
@@ -167,23 +186,29 @@ class BatchedPredictor:
         if self.minpath is not None:
             rows, cost, tied = (t[:hi - lo].numpy() for t in self.mp_pin[s])
             minpath = (rows.view(np.uint16).copy(), cost.copy(), tied.astype(bool))
-        return Batch(lo, hi, labels, maps, surface, minpath)
+        confusion = counts_matrix(self.cf_pin[s][:hi - lo].numpy(), self.eng.cfg.n_cls, lo) if conf else None
+        return Batch(lo, hi, labels, maps, surface, minpath, confusion)
 
 
 def host_batches(model, images: np.ndarray, batch: int, *, gt_u8: Optional[np.ndarray] = None, surface=None,
-                 minpath=None) -> Iterator[Batch]:
+                 minpath=None, confusion=None) -> Iterator[Batch]:
     """The same records for images that are not uint8: x / 255 on the host (``Model.predict_labels``), one synchronous
-    forward per batch, no overlap.  ``surface`` / ``minpath`` as in ``BatchedPredictor``."""
+    forward per batch, no overlap.  ``surface`` / ``minpath`` / ``confusion`` as in ``BatchedPredictor``."""
     for lo in range(0, images.shape[0], batch):
         hi = min(lo + batch, images.shape[0])
         labels, maps = model.predict_labels(images[lo:hi], batch_size=batch, want_maps=True, bg_ilm=True, bg_csi=False)
-        rows = found = None
+        rows = found = counts = None
+        if surface is not None or confusion is not None:
+            dev = (surface if surface is not None else confusion).device
+            pred_dev = torch.from_numpy(np.ascontiguousarray(labels.astype(np.uint8))).to(dev)
+            gt_dev = torch.from_numpy(gt_u8[lo:hi]).to(dev)
         if surface is not None:
-            pred_dev = torch.from_numpy(np.ascontiguousarray(labels.astype(np.uint8))).to(surface.device)
-            rows = surface(pred_dev, torch.from_numpy(gt_u8[lo:hi]).to(surface.device)).cpu().numpy()
+            rows = surface(pred_dev, gt_dev).cpu().numpy()
+        if confusion is not None:
+            counts = confusion.to_host(confusion(pred_dev, gt_dev), lo)
         if minpath is not None:
             found = minpath.to_host(*minpath(torch.from_numpy(np.ascontiguousarray(maps)).to(minpath.device)))
-        yield Batch(lo, hi, labels, maps, rows, found)
+        yield Batch(lo, hi, labels, maps, rows, found, counts)
 
 
 class InferenceRun:
@@ -194,7 +219,8 @@ class InferenceRun:
     * the search: none, the host ``SegmentPool`` (started here, BEFORE the first GPU call of the run), or with
       ``gs_device`` a ``DeviceMinPath`` behind the boundary maps plus a ``LazyPool`` that only starts when a tied map
       arrives and ``gs_device_ties == "host"``;
-    * ``SurfaceDistances`` when ground-truth class maps ``gt`` (n,H,W) are given: arg-max maps against them on the device;
+    * ``SurfaceDistances`` when ground-truth class maps ``gt`` (n,H,W) are given and ``surface`` is left on, and
+      ``ConfusionCounts`` when they are given and ``confusion`` is set: arg-max maps against them on the device;
     * the source: ``BatchedPredictor`` (hipGraph replay, pinned double-buffered transfers) for uint8 images,
       ``host_batches`` for every other dtype.
 
@@ -202,9 +228,11 @@ class InferenceRun:
 
     def __init__(self, model, images: np.ndarray, batch: int, num_classes: int, *, gt: Optional[np.ndarray] = None,
                  graph_search: bool = False, gsgrad: int = 1, gs_device: bool = False, gs_device_ties: str = "host",
-                 gs_workers: Optional[int] = None, batches: Optional[Iterable[Batch]] = None):
+                 gs_workers: Optional[int] = None, batches: Optional[Iterable[Batch]] = None, surface: bool = True,
+                 confusion: bool = False):
         n, (H, W), C = images.shape[0], images.shape[1:3], int(num_classes)
         self.pool = self.host_ties = None
+        self._gs = self._gs_geom = None                   # gs_labels' own device buffers: made by its first call
         self.ties, self._batches = gs_device_ties, (() if batches is None else batches)
         if n == 0:
             return
@@ -221,14 +249,19 @@ class InferenceRun:
             return
         try:
             bs, dev = max(1, min(int(batch), n)), model._dev()
+            self._gs_geom = (bs, H, W, C, dev)
             minpath = DeviceMinPath(bs, C - 1, H, W, gsgrad, dev) if self.host_ties is not None else None
-            surface = SurfaceDistances(bs, H, W, C, dev) if gt_u8 is not None else None
+            surface = SurfaceDistances(bs, H, W, C, dev) if gt_u8 is not None and surface else None
+            confusion = ConfusionCounts(bs, H, W, C, dev) if gt_u8 is not None and confusion else None
+            if surface is None and confusion is None:
+                gt_u8 = None
             if images.dtype == np.uint8:
                 predictor = BatchedPredictor(model._ensure_engine(bs, False), bs, want_maps=True, bg_ilm=True, bg_csi=False,
-                                             surface=surface, minpath=minpath)
+                                             surface=surface, minpath=minpath, confusion=confusion)
                 self._batches = predictor.run(images, gt_u8)
             else:
-                self._batches = host_batches(model, images, bs, gt_u8=gt_u8, surface=surface, minpath=minpath)
+                self._batches = host_batches(model, images, bs, gt_u8=gt_u8, surface=surface, minpath=minpath,
+                                             confusion=confusion)
         except BaseException:
             self.close()
             raise
@@ -246,6 +279,21 @@ class InferenceRun:
             rows, _, tied = batch.minpath
             return merge_ties(batch.maps, rows, tied, truths, self.host_ties, self.ties)
         return None
+
+    def gs_labels(self, batch: Batch, found: list, gt: Optional[np.ndarray] = None) -> Tuple[np.ndarray, Optional[np.ndarray]]:
+        """The class maps the batch's final delineations enclose -- ``found`` is what ``graph_search`` returned for the
+        batch, so every search mode feeds it -- as (n,H,W) uint8, each equal to ``labels_from_delineations`` of the image;
+        with the batch's ground-truth class maps ``gt`` (n,H,W) also their (n, C, C) uint32 confusion counts against it
+        (else None).  The delineations and the ground truth are uploaded here, into buffers of this method: the
+        predictor's own ground-truth buffers are recycled by the upload two batches ahead, while the host may still be
+        searching this batch.  Waits for the device."""
+        if self._gs_geom is None:
+            raise RuntimeError("gs_labels needs the device: this run was built over injected batches")
+        if self._gs is None:
+            self._gs = DelineationLabels(*self._gs_geom)
+        if len(found) != batch.hi - batch.lo:
+            raise ValueError(f"gs_labels: {len(found)} delineations for a batch of {batch.hi - batch.lo} images")
+        return self._gs(np.stack([f[0] for f in found]), gt, first_image=batch.lo)
 
     def close(self) -> None:
         for p in (self.pool, self.host_ties):

@@ -32,6 +32,9 @@ class PredictionOutput:
 
 
 def predict(predict_params: PredictionParams) -> List[PredictionOutput]:
+    """With ``predict_params.gs_labels_device`` the graph-search class maps come from the device, a batch at a time, and
+    the ``graph_time`` attribute of graph_search_prediction_info.hdf5 is that stage's time divided by the batch's image
+    count; every dataset and CSV file equals the host path's."""
     rank, _, _ = parallel.init()
     world = parallel.world_size()
     dataset = predict_params.dataset
@@ -58,6 +61,11 @@ def predict(predict_params: PredictionParams) -> List[PredictionOutput]:
             b0, b1 = lo + batch.lo, lo + batch.hi
             predict_time = (time.time() - t0) / (b1 - b0)
             gs_found = run.graph_search(batch)
+            gs_labels = None
+            if predict_params.graph_search and getattr(predict_params, "gs_labels_device", False):
+                start_stage_time = time.time()
+                gs_labels, _ = run.gs_labels(batch, gs_found)
+                gs_stage_time = (time.time() - start_stage_time) / (b1 - b0)
             for i in range(b0, b1):
                 predict_image, image_name, image_output_dir = images[i], dataset.image_names[i], Path(dataset.image_output_dirs[i])
                 os.makedirs(image_output_dir, exist_ok=True)
@@ -77,8 +85,11 @@ def predict(predict_params: PredictionParams) -> List[PredictionOutput]:
                     predict_image_t = np.transpose(predict_image, axes=[1, 0, 2])
                     start_graph_time = time.time()
                     gs_pred_segs = gs_found[i - b0][0]           # == graph_search.segment_maps(boundary_maps_t, None, grid)
-                    gs_prediction_label, _ = utils.labels_from_delineations(predict_image_t.shape, gs_pred_segs, num_classes)
-                    graph_time = time.time() - start_graph_time
+                    if gs_labels is not None:
+                        gs_prediction_label, graph_time = gs_labels[i - b0], gs_stage_time
+                    else:
+                        gs_prediction_label, _ = utils.labels_from_delineations(predict_image_t.shape, gs_pred_segs, num_classes)
+                        graph_time = time.time() - start_graph_time
                     save_graph_based_prediction_results(predict_params, image_name, gs_prediction_label, gs_pred_segs,
                                                         graph_time, image_output_dir)
                 outputs.append(PredictionOutput(image=predict_image, image_name=image_name, image_output_dir=image_output_dir,
