@@ -21,6 +21,7 @@
  *   oct_unet_forward (training=1)      Model.fit train step (fwd)     training/training.py:401-407
  *     x_is_u8 preprocessing            get_preprocess_input_fn x/255  models/unet.py:87-91
  *     io.argmax                        perform_argmax                 common/utils.py:80-112
+ *   oct_boundary_maps_soft             perform_argmax(bin=False) -> convert_predictions_to_maps_semantic  common/utils.py:80-168
  *   oct_unet_loss_dice                 dice_loss_micro/_macro         common/custom_losses.py:47-81
  *                                      dice_coef_micro/_macro         common/custom_metrics.py:18-77
  *   oct_unet_set_bce_dice / _loss_bce_dice  bce_dice_loss             common/custom_losses.py:84-91
@@ -222,6 +223,28 @@ int oct_unet_profile_end(oct_unet* h, oct_profile_entry* out, int max_entries, i
  * convert_predictions_to_maps_semantic(one_hot(argmax)) of the reference (common/utils.py:115-168) ---- */
 int oct_boundary_maps(const unsigned char* labels_dev, int B, int H, int W, int n_cls, int bg_ilm, int bg_csi,
                       unsigned char* maps_dev, oct_stream_t stream);
+
+/* ---- soft boundary maps on device: (B,H,W,n_cls) f32 class probabilities -> (B, n_cls-1, H, W) u8 boundary maps, exactly
+ * convert_predictions_to_maps_semantic of the probabilities themselves, which is what perform_argmax(bin=False) hands it
+ * (common/utils.py:80-168); oct_boundary_maps is the same function of the arg-max's one-hot.  Restated in numpy, element
+ * by element, by common/utils.py::soft_boundary_maps_reference.  For map m in 1..n_cls-1:
+ *   flip = (m == 1 && bg_ilm) || (m == n_cls-1 && bg_csi);  k = flip ? m-1 : m;  f[r] = probability of class k in the
+ *   pixel's column at row r.  In fp32, one IEEE operation per step:
+ *     d[r] = 0 if H == 1;  f[1] - f[0] at r == 0;  f[H-1] - f[H-2] at r == H-1;  (f[r+1] - f[r-1]) / 2 otherwise
+ *     (np.gradient along the rows);  d = -d if flip;  g[r] = 2 * max(d[r], 0);
+ *     v = max(g[r] - g[(r+1) mod H], 0)        (the roll wraps: the last row subtracts row 0's g);
+ *     out = (unsigned char)((int)(v * 255.0f) & 255)   (numpy's float32 -> uint8 cast: truncate, then wrap -- the rule
+ *     oct_boundary_maps follows for 510 -> 254; with probabilities in [0,1] only rows 0 and H-1 can exceed 255).
+ *   All steps but the two subtractions and the product with 255 are exact, and none is contracted with another, so the
+ *   result equals numpy's bit for bit.
+ * The inputs are finite floats, and the values are defined for [0,1], what the softmax delivers: NaN and infinity are
+ * outside the contract (no fault, unspecified bytes).  Stand-alone like oct_boundary_maps: no handle, no allocation, one
+ * asynchronous launch on `stream`, never waits, records into a stream capture.  probs_dev needs only its natural 4-byte
+ * alignment, maps_dev none.  Errors (negative, oct_last_error(), nothing launched): null pointers, non-positive sizes,
+ * n_cls outside 2..32, an output range overlapping the input. */
+int oct_boundary_maps_soft(const float* probs_dev /* (B,H,W,n_cls) f32, the layout of oct_unet_io.probs */,
+                           int B, int H, int W, int n_cls, int bg_ilm, int bg_csi,
+                           unsigned char* maps_dev /* (B, n_cls-1, H, W) */, oct_stream_t stream);
 
 /* ---- evaluation metrics on device: average surface distance and robust Hausdorff distance of every foreground class
  * (reference evaluation/evaluation.py:207-262 -> common/custom_metrics.py:103-119 -> google-deepmind/surface-distance

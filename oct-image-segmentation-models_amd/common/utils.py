@@ -95,6 +95,32 @@ def convert_predictions_to_maps_semantic(categorical_pred, bg_ilm=True, bg_csi=F
     return boundary_maps
 
 
+def soft_boundary_maps_reference(probs_nhwc, bg_ilm=True, bg_csi=False) -> np.ndarray:
+    """``oct_boundary_maps_soft`` (include/oct_unet.h) restated element by element: (n,H,W,C) float32 class
+    probabilities -> uint8 (n, C-1, H, W), equal to ``convert_predictions_to_maps_semantic(perform_argmax(probs,
+    bin=False)[1])``.  Every step is one float32 operation, in the order of the header's definition; a single row
+    (where ``np.gradient`` refuses the input) has gradient 0."""
+    p = np.asarray(probs_nhwc, dtype=np.float32)
+    n, H, W, C = p.shape
+    two, zero = np.float32(2.0), np.float32(0.0)
+    out = np.zeros((n, C - 1, H, W), dtype=np.uint8)
+    rows = np.arange(H)
+    lo, hi = np.maximum(rows - 1, 0), np.minimum(rows + 1, H - 1)
+    interior = (rows > 0) & (rows < H - 1)
+    for m in range(1, C):
+        flip = (m == 1 and bool(bg_ilm)) or (m == C - 1 and bool(bg_csi))
+        f = p[:, :, :, m - 1 if flip else m]                       # (n,H,W)
+        d = f[:, hi, :] - f[:, lo, :]                              # one-sided at the edge rows, 0 where H == 1
+        d[:, interior, :] = d[:, interior, :] / two
+        if flip:
+            d = -d
+        g = two * np.maximum(d, zero)
+        v = np.maximum(g - g[:, (rows + 1) % H, :], zero)          # the roll wraps: the last row subtracts row 0's g
+        # numpy's float32 -> uint8 cast on the hosts the goldens come from: truncate, then wrap (510 -> 254)
+        out[:, m - 1] = ((v * np.float32(255.0)).astype(np.int32) & 255).astype(np.uint8)
+    return out
+
+
 def create_area_mask(image_shape: tuple, segs) -> np.ndarray:
     """Boundaries -> stacked-region mask (dataset_construction.py:654-708, channels_last).  ``image_shape`` is
     (width, height[, channels]) of the TRANSPOSED image the graph search works on; regions do not include the

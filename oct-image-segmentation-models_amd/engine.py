@@ -369,6 +369,20 @@ class UNetEngine:
                                                     out.data_ptr(), self._stream()), "oct_boundary_maps")
         return out
 
+    def boundary_maps_soft(self, probs: torch.Tensor, bg_ilm: bool = True, bg_csi: bool = False) -> torch.Tensor:
+        """(B,H,W,num_classes) float32 class probabilities (the forward's ``probs``) -> (B, num_classes-1, H, W) uint8
+        soft boundary maps: ``convert_predictions_to_maps_semantic`` of the probabilities themselves
+        (``oct_boundary_maps_soft``; ``common.utils.soft_boundary_maps_reference`` restates it)."""
+        if probs.device != self.device or probs.dtype != torch.float32 or not probs.is_contiguous() or probs.dim() != 4 \
+                or probs.shape[3] != self.cfg.n_cls:
+            raise OctError(f"probs must be a contiguous float32 (B,H,W,{self.cfg.n_cls}) tensor on the engine's device")
+        B, H, W, _ = probs.shape
+        out = torch.empty((B, self.cfg.n_cls - 1, H, W), dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            _hip.check(_hip.lib().oct_boundary_maps_soft(probs.data_ptr(), B, H, W, self.cfg.n_cls, int(bg_ilm), int(bg_csi),
+                                                         out.data_ptr(), self._stream()), "oct_boundary_maps_soft")
+        return out
+
     def augment(self, x_u8: torch.Tensor, labels: Optional[torch.Tensor], ops, seed: int, out=None):
         """The training augmentations on the device (``oct_augment_batch``): (B,H,W,C) uint8 images, (B,H,W[,1]) uint8
         labels or ``None`` and one ``common.augmentation.AUG_OP_DTYPE`` descriptor per sample -> ``(x float32 in [0,1],

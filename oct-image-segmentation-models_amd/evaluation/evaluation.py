@@ -151,7 +151,8 @@ def evaluate_model(eval_params: EvaluationParameters) -> List[EvaluationOutput]:
     with InferenceRun(eval_params.loaded_model, eval_images[lo:hi], eval_params.batch_size, num_classes,
                       gt=gt_maps, surface=want_surface, confusion=metrics_device and want_dice,
                       graph_search=eval_params.graph_search, gsgrad=eval_params.gsgrad, gs_device=eval_params.gs_device,
-                      gs_device_ties=eval_params.gs_device_ties, gs_workers=eval_params.gs_workers) as run:
+                      gs_device_ties=eval_params.gs_device_ties, gs_workers=eval_params.gs_workers,
+                      soft_maps=not getattr(eval_params, "binarize", True)) as run:
         t_prev = time.time()
         for batch in run:
             b0, b1 = lo + batch.lo, lo + batch.hi
@@ -169,7 +170,8 @@ def evaluate_model(eval_params: EvaluationParameters) -> List[EvaluationOutput]:
                 os.makedirs(eval_image_output_dir, exist_ok=True)
                 predicted_labels = batch.labels[ind - b0:ind - b0 + 1].astype(np.int64)        # (1,H,W)
                 categorical_pred = common_utils.labels_to_categorical(predicted_labels, num_classes)
-                boundary_maps = batch.maps[ind - b0:ind - b0 + 1]   # == convert_predictions_to_maps_semantic(categorical_pred), on device
+                # on device: == convert_predictions_to_maps_semantic(categorical_pred); with binarize=False, of the probabilities
+                boundary_maps = batch.maps[ind - b0:ind - b0 + 1]
                 dice_classes, dice_macro, dice_micro = _batch_dice(eval_params.metrics, num_classes, batch, ind - b0,
                                                                    eval_label, categorical_pred)
                 surface_ds = _surface_metrics(eval_params.metrics, None if batch.surface is None else batch.surface[ind - b0])
@@ -269,6 +271,8 @@ def save_eval_config_file(eval_params: EvaluationParameters):
              "test_dataset_path": np.array(str(eval_params.test_dataset_path), dtype="S1000"),
              "test_dataset_md5": np.array(common_utils.md5(md5_path), dtype="S1000"),
              "gsgrad": np.array(eval_params.gsgrad)}
+    if not getattr(eval_params, "binarize", True):
+        attrs["binarize"] = np.array(False)      # recorded only when it departs from the default: binarize=True files stay as they were
     h5io.save(eval_params.save_foldername / Path("eval_params.hdf5"), {}, attrs)
 
 

@@ -29,7 +29,12 @@ class EvaluationParameters:
         self.mlflow_tracking_uri = mlflow_tracking_uri
         self.mlflow_run_uuid = mlflow_run_uuid
         self.test_dataset_path = Path(test_dataset_path)
-        self.binarize = binarize
+        # binarize=False (the reference's perform_argmax(bin=False)): the boundary maps are
+        # convert_predictions_to_maps_semantic of the class PROBABILITIES, built on the device (oct_boundary_maps_soft), and
+        # everything behind the graph search follows them: gs_pred_segs, errors, the graph-search class maps, their Dice,
+        # the CSV files.  predicted_labels, the arg-max Dice and the surface distances do not change, and categorical_pred
+        # stays the one-hot of the arg-max: the files store it as uint8, for which truncated probabilities mean nothing
+        self.binarize = bool(binarize)
         self.save_params = save_params
         self.graph_search = graph_search
         if not set(metrics).issubset(EVALUATION_METRICS):

@@ -47,10 +47,17 @@ class BatchedPredictor:
 
     With ``confusion`` (an ``evaluation.dice_device.ConfusionCounts`` for this batch and shape) the ground truth is
     uploaded in the same way and ``oct_confusion_counts`` runs on the arg-max maps next to the surface distances;
-    ``Batch.confusion`` holds the matrices, and a label outside 0..C-1 raises when the batch is collected."""
+    ``Batch.confusion`` holds the matrices, and a label outside 0..C-1 raises when the batch is collected.
+
+    With ``soft_maps`` the graph also writes the class probabilities, into a buffer that never leaves the device, and
+    ``maps`` are the soft boundary maps of those (``oct_boundary_maps_soft``) instead of the binary maps of the arg-max.
+    Labels, surface distances, confusion counts, the min-path stage behind the maps and every transfer are the same."""
 
     def __init__(self, engine, batch: int, want_maps: bool = True, bg_ilm: bool = True, bg_csi: bool = False,
-                 surface=None, minpath=None, confusion=None):
+                 surface=None, minpath=None, confusion=None, soft_maps: bool = False):
+        if soft_maps and not want_maps:
+            raise ValueError("soft_maps: needs want_maps=True")
+        self.soft_maps = bool(soft_maps)
         if not 1 <= batch <= engine.cfg.max_batch:
             raise ValueError(f"batch {batch} outside 1..max_batch={engine.cfg.max_batch}")
         self.eng, self.B, self.want_maps, self.bg = engine, int(batch), want_maps, (bg_ilm, bg_csi)
@@ -90,7 +97,7 @@ class BatchedPredictor:
             self.mp_pin = [tuple(torch.empty(t.shape, dtype=t.dtype).pin_memory() for t in self.mp_dev[0]) for _ in range(2)]
         self.copy_in = torch.cuda.Stream(device=dev)
         self.copy_out = torch.cuda.Stream(device=dev)
-        _, self.am = engine.graph_capture(self.x_dev, want_probs=False, want_argmax=True)
+        self.probs, self.am = engine.graph_capture(self.x_dev, want_probs=self.soft_maps, want_argmax=True)
 
     def run(self, images_u8: np.ndarray, gt_u8: Optional[np.ndarray] = None) -> Iterator[Batch]:
         images_u8 = np.ascontiguousarray(images_u8)
@@ -154,7 +161,10 @@ class BatchedPredictor:
             if have_gt:
                 gt_free[s].record(main)
             if self.want_maps:
-                self.map_dev[s].copy_(eng.boundary_maps(self.am, bg_ilm=self.bg[0], bg_csi=self.bg[1]))
+                if self.soft_maps:
+                    self.map_dev[s].copy_(eng.boundary_maps_soft(self.probs, bg_ilm=self.bg[0], bg_csi=self.bg[1]))
+                else:
+                    self.map_dev[s].copy_(eng.boundary_maps(self.am, bg_ilm=self.bg[0], bg_csi=self.bg[1]))
                 if self.minpath is not None:
                     self.minpath(self.map_dev[s][:hi - lo], *(t[:hi - lo] for t in self.mp_dev[s]))
             out_ready[s].record(main)
@@ -191,12 +201,13 @@ class BatchedPredictor:
 
 
 def host_batches(model, images: np.ndarray, batch: int, *, gt_u8: Optional[np.ndarray] = None, surface=None,
-                 minpath=None, confusion=None) -> Iterator[Batch]:
+                 minpath=None, confusion=None, soft_maps: bool = False) -> Iterator[Batch]:
     """The same records for images that are not uint8: x / 255 on the host (``Model.predict_labels``), one synchronous
-    forward per batch, no overlap.  ``surface`` / ``minpath`` / ``confusion`` as in ``BatchedPredictor``."""
+    forward per batch, no overlap.  ``surface`` / ``minpath`` / ``confusion`` / ``soft_maps`` as in ``BatchedPredictor``."""
     for lo in range(0, images.shape[0], batch):
         hi = min(lo + batch, images.shape[0])
-        labels, maps = model.predict_labels(images[lo:hi], batch_size=batch, want_maps=True, bg_ilm=True, bg_csi=False)
+        labels, maps = model.predict_labels(images[lo:hi], batch_size=batch, want_maps=True, bg_ilm=True, bg_csi=False,
+                                            soft_maps=soft_maps)
         rows = found = counts = None
         if surface is not None or confusion is not None:
             dev = (surface if surface is not None else confusion).device
@@ -224,12 +235,15 @@ class InferenceRun:
     * the source: ``BatchedPredictor`` (hipGraph replay, pinned double-buffered transfers) for uint8 images,
       ``host_batches`` for every other dtype.
 
+    ``soft_maps`` is passed to whichever source is built: ``Batch.maps`` are then the soft boundary maps of the class
+    probabilities, and everything behind them (either search, ``gs_labels``) works on those.
+
     ``batches`` replaces the model by a ready source of records (tests of the host side: no device is touched)."""
 
     def __init__(self, model, images: np.ndarray, batch: int, num_classes: int, *, gt: Optional[np.ndarray] = None,
                  graph_search: bool = False, gsgrad: int = 1, gs_device: bool = False, gs_device_ties: str = "host",
                  gs_workers: Optional[int] = None, batches: Optional[Iterable[Batch]] = None, surface: bool = True,
-                 confusion: bool = False):
+                 confusion: bool = False, soft_maps: bool = False):
         n, (H, W), C = images.shape[0], images.shape[1:3], int(num_classes)
         self.pool = self.host_ties = None
         self._gs = self._gs_geom = None                   # gs_labels' own device buffers: made by its first call
@@ -257,11 +271,12 @@ class InferenceRun:
                 gt_u8 = None
             if images.dtype == np.uint8:
                 predictor = BatchedPredictor(model._ensure_engine(bs, False), bs, want_maps=True, bg_ilm=True, bg_csi=False,
-                                             surface=surface, minpath=minpath, confusion=confusion)
+                                             surface=surface, minpath=minpath, confusion=confusion,
+                                             soft_maps=soft_maps)
                 self._batches = predictor.run(images, gt_u8)
             else:
                 self._batches = host_batches(model, images, bs, gt_u8=gt_u8, surface=surface, minpath=minpath,
-                                             confusion=confusion)
+                                             confusion=confusion, soft_maps=soft_maps)
         except BaseException:
             self.close()
             raise

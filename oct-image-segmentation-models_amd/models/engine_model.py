@@ -433,10 +433,13 @@ class Model:
         return out
 
     def predict_labels(self, x_u8: np.ndarray, batch_size: int = 32, want_maps: bool = False, bg_ilm: bool = True,
-                       bg_csi: bool = False):
+                       bg_csi: bool = False, soft_maps: bool = False):
         """Raw uint8 images -> uint8 arg-max class maps (n,H,W), computed on the device (1 B/px back instead of
         4*C B/px).  With ``want_maps`` also the (n, C-1, H, W) uint8 boundary maps of
-        ``convert_predictions_to_maps_semantic``, computed on the device from the class maps."""
+        ``convert_predictions_to_maps_semantic``, computed on the device from the class maps -- or, with ``soft_maps``,
+        from the class probabilities, which stay on the device (``UNetEngine.boundary_maps_soft``)."""
+        if soft_maps and not want_maps:
+            raise ValueError("soft_maps: needs want_maps=True")
         x_u8 = np.ascontiguousarray(x_u8)
         if x_u8.dtype != np.uint8:
             # the reference normalises x / 255 whatever the dtype (models/unet.py:87-91); the engine's float32 input
@@ -448,10 +451,12 @@ class Model:
         maps = np.empty((n, self.config["num_classes"] - 1) + tuple(x_u8.shape[1:3]), np.uint8) if want_maps else None
         for lo in range(0, n, batch_size):
             xb = torch.from_numpy(x_u8[lo:lo + batch_size]).to(eng.device)
-            _, am = eng.forward(xb, training=False, want_probs=False, want_argmax=True)
+            probs, am = eng.forward(xb, training=False, want_probs=soft_maps, want_argmax=True)
             out[lo:lo + batch_size] = am.cpu().numpy()
             if want_maps:
-                maps[lo:lo + batch_size] = eng.boundary_maps(am, bg_ilm=bg_ilm, bg_csi=bg_csi).cpu().numpy()
+                dev_maps = (eng.boundary_maps_soft(probs, bg_ilm=bg_ilm, bg_csi=bg_csi) if soft_maps
+                            else eng.boundary_maps(am, bg_ilm=bg_ilm, bg_csi=bg_csi))
+                maps[lo:lo + batch_size] = dev_maps.cpu().numpy()
         return (out, maps) if want_maps else out
 
 

@@ -55,7 +55,8 @@ def predict(predict_params: PredictionParams) -> List[PredictionOutput]:
     # the device pipeline of evaluate_model (evaluation/pipeline.py::InferenceRun), without ground truth
     with InferenceRun(predict_params.loaded_model, images[lo:hi], predict_params.batch_size, num_classes,
                       graph_search=predict_params.graph_search, gs_device=predict_params.gs_device,
-                      gs_device_ties=predict_params.gs_device_ties, gs_workers=predict_params.gs_workers) as run:
+                      gs_device_ties=predict_params.gs_device_ties, gs_workers=predict_params.gs_workers,
+                      soft_maps=not getattr(predict_params, "binarize", True)) as run:
         t0 = time.time()
         for batch in run:
             b0, b1 = lo + batch.lo, lo + batch.hi
@@ -73,7 +74,8 @@ def predict(predict_params: PredictionParams) -> List[PredictionOutput]:
                 start_convert_time = time.time()
                 predicted_labels = batch.labels[i - b0:i - b0 + 1].astype(np.int64)
                 categorical_pred = utils.labels_to_categorical(predicted_labels, num_classes)
-                boundary_maps = batch.maps[i - b0:i - b0 + 1]   # == convert_predictions_to_maps_semantic(categorical_pred), on device
+                # on device: == convert_predictions_to_maps_semantic(categorical_pred); with binarize=False, of the probabilities
+                boundary_maps = batch.maps[i - b0:i - b0 + 1]
                 convert_time = time.time() - start_convert_time
                 predicted_labels = np.squeeze(predicted_labels, axis=0)
                 categorical_pred = np.squeeze(categorical_pred, axis=0)
@@ -103,6 +105,8 @@ def predict(predict_params: PredictionParams) -> List[PredictionOutput]:
 def save_predict_config_file(predict_params: PredictionParams):
     attrs = {"model_filename": np.array(str(predict_params.model_path), dtype="S1000"),
              "error_col_inc_range": np.array((predict_params.col_error_range[0], predict_params.col_error_range[-1]))}
+    if not getattr(predict_params, "binarize", True):
+        attrs["binarize"] = np.array(False)      # recorded only when it departs from the default: binarize=True files stay as they were
     h5io.save(predict_params.config_output_dir / Path("prediction_params.hdf5"), {}, attrs)
 
 

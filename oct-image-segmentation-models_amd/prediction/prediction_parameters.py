@@ -23,7 +23,8 @@ class PredictionParams:
                  dataset: Dataset, config_output_dir: Path, save_params: PredictionSaveParams,
                  graph_search: bool = False, trim_maps: bool = False, trim_ref_ind: int = 0,
                  trim_window: tuple = (0, 0), col_error_range: tuple = None, batch_size: int = 32, gs_device: bool = False,
-                 gs_device_ties: str = "host", gs_workers: Union[int, None] = None, gs_labels_device: bool = False) -> None:
+                 gs_device_ties: str = "host", gs_workers: Union[int, None] = None, gs_labels_device: bool = False,
+                 binarize: bool = True) -> None:
         self.model_path = Path(model_path)
         self.mlflow_tracking_uri = mlflow_tracking_uri
         self.mlflow_run_uuid = mlflow_run_uuid
@@ -47,6 +48,8 @@ class PredictionParams:
         # extension: gs_prediction_label from oct_area_labels (evaluation/dice_device.py) instead of the host loop; the
         # same files, and the graph_time attribute becomes the batch's stage time divided by its image count
         self.gs_labels_device = bool(gs_labels_device)
+        # extension, as EvaluationParameters.binarize: False = soft boundary maps of the class probabilities
+        self.binarize = bool(binarize)
         self.col_error_range = col_error_range
         if col_error_range is None:
             self.col_error_range = range(dataset.images[0].shape[1])  # image_width
