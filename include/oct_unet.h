@@ -22,6 +22,7 @@
  *     x_is_u8 preprocessing            get_preprocess_input_fn x/255  models/unet.py:87-91
  *     io.argmax                        perform_argmax                 common/utils.py:80-112
  *   oct_boundary_maps_soft             perform_argmax(bin=False) -> convert_predictions_to_maps_semantic  common/utils.py:80-168
+ *   oct_render_rgba                    save_image_plot / save_segmentation_plot (own line rule)  common/plotting.py:169-278
  *   oct_unet_loss_dice                 dice_loss_micro/_macro         common/custom_losses.py:47-81
  *                                      dice_coef_micro/_macro         common/custom_metrics.py:18-77
  *   oct_unet_set_bce_dice / _loss_bce_dice  bce_dice_loss             common/custom_losses.py:84-91
@@ -344,6 +345,54 @@ int oct_confusion_counts(const unsigned char* pred_dev, const unsigned char* gt_
                          unsigned int* counts_dev /* (B, n_cls*n_cls + 1) */, oct_stream_t stream);
 int oct_area_labels(const unsigned short* segs_dev /* (B, n_cls-1, W) */, int B, int H, int W, int n_cls,
                     unsigned char* labels_dev /* (B, H, W) */, oct_stream_t stream);
+
+/* ---- PNG pictures on the device (csrc/kernels_render.hpp; numpy restatement: common/plotting.py::render_reference) ----
+ * oct_render_rgba renders B images of H x W into out_dev (B, H, W, 4) uint8 RGBA with A = 255: a base layer, then
+ * K >= 0 polylines over it.  Integers only; the restatement and the kernel agree bit for bit.
+ *
+ * Base layer.  OCT_RENDER_BASE_IMAGE: base_dev is (B, H, W, ic) uint8; ic == 3 gives R, G, B, any other ic gives
+ * R = G = B = channel 0.  OCT_RENDER_BASE_LABELS: base_dev is (B, H, W) uint8 (ic is ignored) and a pixel gets
+ * style->palette[label], a label >= style->n_cls gives (0, 0, 0).
+ *
+ * Lines.  rows_dev is (B, K, W) uint16, K = style->n_lines (rows_dev may be NULL when K == 0); line k has the colour
+ * style->line_rgb[3k..3k+2] and the style style->line_style[k], 0 solid or 1 dotted.  Lines are drawn in index order.
+ * One inclusive column range [col_lo, col_hi] and one half_width R in eighths of a pixel (1..64; 22 = a 5.5 px line)
+ * hold for the whole call.  In eighths of a pixel, the centre of pixel (r, c) at (x, y) = (8c, 8r):
+ *   vertex    column c of a line has a vertex at (8c, 8 rows[c]) iff col_lo <= c <= col_hi and 0 < rows[c] < H
+ *             (0 is the searches' "nothing here"; a row >= H counts as missing too).
+ *   segment   columns c and c+1 form a segment iff both have a vertex; an isolated vertex draws nothing.
+ *   samples   a pixel has 16 samples s = (8c + ox, 8r + oy), ox, oy in {-3, -1, 1, 3}.
+ *   on        for the segment P0 -> P1, d = P1 - P0 = (8, 8 (rows[c+1] - rows[c])), w = s - P0, t = w.d, den = d.d:
+ *             t <= 0: |w|^2 <= R^2;  t >= den: |s - P1|^2 <= R^2;  otherwise |w|^2 den - t^2 <= R^2 den
+ *             (round caps and joins).  All of it fits int64 for H <= 4096.
+ *   dotted    a sample counts only when floor_mod(sx - 8 col_lo, 120) < 48: 6 px on in a period of 15, phased by column.
+ *   coverage  the number of the pixel's samples, 0..16, that are on ANY segment of the line (joins do not count twice).
+ *   blend     per channel out = (cov * colour + (16 - cov) * out + 8) >> 4, line after line.
+ * So an interior flat solid line of R = 22 at row y covers rows y-2..y+2 fully and rows y-3, y+3 with coverage 4, and a gap
+ * narrower than the line closes under the round caps.
+ *
+ * The palette, the line colours and the line styles travel BY VALUE: `style` is a host struct that the call copies into the
+ * kernel's arguments before it returns (nothing of it is read later, no device buffer is involved).  Stand-alone like
+ * oct_area_labels: no handle, no allocation, one asynchronous launch on `stream`, never waits, records into a stream
+ * capture.  Errors (negative, oct_last_error(), nothing launched): null pointers, non-positive sizes, B > 65535, an unknown
+ * base mode, n_cls outside 1..32 in label mode, K outside 0..16, H > 4096, half_width outside 1..64, col_lo > col_hi or a
+ * range outside 0..W-1, an output range overlapping an input. */
+#define OCT_RENDER_BASE_IMAGE 0
+#define OCT_RENDER_BASE_LABELS 1
+#define OCT_RENDER_MAX_CLASSES 32
+#define OCT_RENDER_MAX_LINES 16
+typedef struct oct_render_style {
+    int n_cls;                                              /* label mode: entries of palette in use */
+    int n_lines;                                            /* K */
+    int col_lo, col_hi;                                     /* inclusive column range of every line */
+    int half_width;                                         /* R, eighths of a pixel */
+    unsigned char palette[3 * OCT_RENDER_MAX_CLASSES];      /* RGB per class */
+    unsigned char line_rgb[3 * OCT_RENDER_MAX_LINES];       /* RGB per line */
+    unsigned char line_style[OCT_RENDER_MAX_LINES];         /* 0 solid, 1 dotted */
+} oct_render_style;
+int oct_render_rgba(int base_mode, const unsigned char* base_dev, int ic, const unsigned short* rows_dev /* (B, K, W) */,
+                    const oct_render_style* style /* host */, int B, int H, int W,
+                    unsigned char* out_dev /* (B, H, W, 4) */, oct_stream_t stream);
 
 /* ---- options ----
  * oct_set_option edits the PROCESS-WIDE DEFAULTS; a handle copies them when it is created (oct_unet_create) and every

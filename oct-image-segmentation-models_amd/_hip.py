@@ -53,6 +53,16 @@ OPT_NESTEROV, OPT_AMSGRAD, OPT_CENTERED = 1, 2, 4
 CLIP_NONE, CLIP_VALUE, CLIP_NORM, CLIP_GLOBAL_NORM = range(4)
 
 
+class RenderStyle(C.Structure):
+    """``oct_render_style``: palette, line colours and styles of one ``oct_render_rgba`` call, passed by value."""
+    _fields_ = [("n_cls", C.c_int), ("n_lines", C.c_int), ("col_lo", C.c_int), ("col_hi", C.c_int), ("half_width", C.c_int),
+                ("palette", C.c_ubyte * 96), ("line_rgb", C.c_ubyte * 48), ("line_style", C.c_ubyte * 16)]
+
+
+RENDER_BASE_IMAGE, RENDER_BASE_LABELS = 0, 1
+RENDER_MAX_CLASSES, RENDER_MAX_LINES = 32, 16
+
+
 class UNetIO(C.Structure):
     _fields_ = [("probs", C.c_void_p), ("argmax", C.c_void_p), ("labels", C.c_void_p)]
 
@@ -104,6 +114,8 @@ SYMBOLS = [
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("oct_confusion_counts", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     ("oct_area_labels", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    ("oct_render_rgba", C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, _P(RenderStyle), C.c_int, C.c_int, C.c_int,
+                                  C.c_void_p, C.c_void_p]),
     ("oct_set_option", C.c_int, [C.c_char_p, C.c_int]),
     ("oct_get_option", C.c_int, [C.c_char_p, _P(C.c_int)]),
     ("oct_unet_get_option", C.c_int, [C.c_void_p, C.c_char_p, _P(C.c_int)]),

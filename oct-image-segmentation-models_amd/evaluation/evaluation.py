@@ -8,7 +8,10 @@ re-stated.  The surface-distance metrics (average surface distance, Hausdorff-95
 device from the arg-max maps and the uploaded ground truth (``evaluation/surface.py``).  With
 ``EvaluationParameters(metrics_device=True)`` the Dice metrics come from confusion counts made on the device and the
 graph-search class maps from ``oct_area_labels`` (``evaluation/dice_device.py``): the same files, byte for byte.  Under ``torchrun`` the test
-set is sharded by contiguous index range (no collective); rank 0 aggregates.  PNG plots are out of scope."""
+set is sharded by contiguous index range (no collective); rank 0 aggregates.  With ``EvaluationParameters(png_plots=True)``
+the reference's PNG pictures of every image are rasterised on the device (``oct_render_rgba``, ``evaluation/render.py``) and
+written by ``common/png.py``; each rank writes those of its own shard.  ``performance_plot.png`` and
+``categorical_pred_N.png`` are out of scope."""
 from __future__ import annotations
 
 import logging as log
@@ -30,6 +33,7 @@ from ..models import get_model_class
 from .dice_device import DICE_METRICS, MAX_EXACT_PIXELS, dice_from_counts
 from .evaluation_parameters import EvaluationParameters
 from .pipeline import InferenceRun
+from .render import EVALUATION_PNG_NAMES, write_pictures
 from .surface import datasets as surface_datasets
 
 EVALUATION_RESULTS_FILENAME = "evaluation_results.hdf5"
@@ -148,6 +152,8 @@ def evaluate_model(eval_params: EvaluationParameters) -> List[EvaluationOutput]:
     need_gt = want_surface or (metrics_device and want_dice)
     gt_maps = np.squeeze(eval_labels[lo:hi], axis=3) if need_gt else None
     # BASELINE configs[4] path (evaluation/pipeline.py::InferenceRun): search mode, batch source and worker pools
+    # png_plots: the pictures of evaluation.py:488-548 and :673-695 of the reference, under its save_params conditions
+    png_plots = bool(getattr(eval_params, "png_plots", False)) and eval_params.save_params.png_images is True
     with InferenceRun(eval_params.loaded_model, eval_images[lo:hi], eval_params.batch_size, num_classes,
                       gt=gt_maps, surface=want_surface, confusion=metrics_device and want_dice,
                       graph_search=eval_params.graph_search, gsgrad=eval_params.gsgrad, gs_device=eval_params.gs_device,
@@ -163,6 +169,11 @@ def evaluate_model(eval_params: EvaluationParameters) -> List[EvaluationOutput]:
                 start_stage_time = time.time()
                 gs_labels, gs_counts = run.gs_labels(batch, gs_found, gt_maps[batch.lo:batch.hi] if want_dice else None)
                 gs_stage_time = (time.time() - start_stage_time) / (b1 - b0)
+            pictures = None
+            if png_plots:
+                pictures = run.render_pngs(batch, eval_images[b0:b1], gs_found, gt=np.squeeze(eval_labels[b0:b1], axis=3),
+                                           truths=eval_segments[b0:b1], gs_labels=gs_labels,
+                                           pred_map=eval_params.save_params.predicted_labels is True)
             for ind in range(b0, b1):
                 eval_image, eval_image_name = eval_images[ind], eval_image_names[ind]
                 eval_seg, eval_image_output_dir = eval_segments[ind], eval_image_output_dirs[ind]
@@ -203,6 +214,8 @@ def evaluate_model(eval_params: EvaluationParameters) -> List[EvaluationOutput]:
                     _save_graph_based_evaluation_results(eval_params, eval_image_name, gs_eval_label, gs_pred_segs, gs_dc,
                                                          gs_dm, gs_dmi, errors, mean_abs_err, mean_err, abs_err_sd, err_sd,
                                                          graph_time, eval_image_output_dir)
+                if pictures is not None:
+                    write_pictures(eval_image_output_dir, pictures, ind - b0, EVALUATION_PNG_NAMES)
                 eval_outputs.append(EvaluationOutput(
                     image=eval_image, image_name=eval_image_name, image_segments=eval_seg,
                     image_output_dir=eval_image_output_dir, predicted_labels=predicted_labels,
@@ -273,6 +286,8 @@ def save_eval_config_file(eval_params: EvaluationParameters):
              "gsgrad": np.array(eval_params.gsgrad)}
     if not getattr(eval_params, "binarize", True):
         attrs["binarize"] = np.array(False)      # recorded only when it departs from the default: binarize=True files stay as they were
+    if getattr(eval_params, "png_plots", False):
+        attrs["png_plots"] = np.array(True)      # likewise
     h5io.save(eval_params.save_foldername / Path("eval_params.hdf5"), {}, attrs)
 
 

@@ -15,7 +15,8 @@ class EvaluationSaveParams:
                  boundary_maps: bool = True) -> None:
         self.predicted_labels = predicted_labels
         self.categorical_pred = categorical_pred
-        self.png_images = png_images      # accepted for compatibility; PNG plotting is out of scope
+        # takes effect with EvaluationParameters(png_plots=True): False keeps every PNG picture from being written
+        self.png_images = png_images
         self.boundary_maps = boundary_maps
 
 
@@ -24,7 +25,8 @@ class EvaluationParameters:
                  test_dataset_path: Path, save_foldername: Path, save_params: EvaluationSaveParams,
                  graph_search: bool, metrics: List[str], gsgrad=1, dice_errors: bool = True, binarize: bool = True,
                  bg_ilm: bool = True, bg_csi: bool = False, batch_size: int = 32, gs_device: bool = False,
-                 gs_device_ties: str = "host", gs_workers: Optional[int] = None, metrics_device: bool = False):
+                 gs_device_ties: str = "host", gs_workers: Optional[int] = None, metrics_device: bool = False,
+                 png_plots: bool = False):
         self.model_path = Path(model_path)
         self.mlflow_tracking_uri = mlflow_tracking_uri
         self.mlflow_run_uuid = mlflow_run_uuid
@@ -59,6 +61,11 @@ class EvaluationParameters:
         # oct_area_labels (evaluation/dice_device.py).  Every dataset and CSV file equals the host path's; the graph_time
         # attribute becomes the batch's stage time divided by its image count
         self.metrics_device = bool(metrics_device)
+        # extension: write the reference's PNG pictures of every image (raw_image, predicted / ground-truth / graph-search
+        # segmentation maps, truth_plot and the two graph-search overlays), rasterised on the device by oct_render_rgba and
+        # encoded by common/png.py, under the reference's save_params conditions (png_images; predicted_labels for the
+        # prediction map).  Off by default like every device post-process: no other output changes either way
+        self.png_plots = bool(png_plots)
         self.loaded_model, self.model_config = utils.load_model_and_config(
             self.model_path, mlflow_tracking_uri=mlflow_tracking_uri, mlflow_run_uuid=mlflow_run_uuid)
         self.num_classes = self.loaded_model.output.shape[-1]

@@ -18,6 +18,7 @@ import torch
 from ..min_path_processing.device_search import DeviceMinPath, LazyPool, merge_ties
 from ..min_path_processing.pool import SegmentPool, default_workers
 from .dice_device import ConfusionCounts, DelineationLabels, counts_matrix
+from .render import PngRenderer, batch_pictures
 from .surface import SurfaceDistances
 
 
@@ -247,6 +248,7 @@ class InferenceRun:
         n, (H, W), C = images.shape[0], images.shape[1:3], int(num_classes)
         self.pool = self.host_ties = None
         self._gs = self._gs_geom = None                   # gs_labels' own device buffers: made by its first call
+        self._png = None                                  # render_pngs' own device and pinned buffers, likewise
         self.ties, self._batches = gs_device_ties, (() if batches is None else batches)
         if n == 0:
             return
@@ -309,6 +311,37 @@ class InferenceRun:
         if len(found) != batch.hi - batch.lo:
             raise ValueError(f"gs_labels: {len(found)} delineations for a batch of {batch.hi - batch.lo} images")
         return self._gs(np.stack([f[0] for f in found]), gt, first_image=batch.lo)
+
+    def render_pngs(self, batch: Batch, images: np.ndarray, found: Optional[list] = None, *,
+                    gt: Optional[np.ndarray] = None, truths: Optional[np.ndarray] = None, gs_labels: Optional[np.ndarray] = None,
+                    pred_map: bool = True, col_range=None) -> dict:
+        """The PNG pictures of a batch as host RGBA arrays (n,H,W,4) uint8, rasterised on the device by
+        ``oct_render_rgba`` (``evaluation.render.batch_pictures`` names the keys): ``raw`` of the batch's ``images``
+        (n,H,W,ic), ``pred`` of the arg-max maps (unless ``pred_map`` is off), with the ground-truth class maps ``gt``
+        (n,H,W) ``gt``, with the ground-truth boundaries ``truths`` (n,M,W) ``truth``, and with ``found`` -- what
+        ``graph_search`` returned for the batch -- ``gs_map``, ``gs_bounds`` (columns ``col_range``) and, where ``truths``
+        are given, ``gs_both``.  ``gs_labels`` are the class maps of the delineations where the caller has them
+        (``gs_labels()``); otherwise ``oct_area_labels`` makes them here, on the device.  Everything is uploaded here,
+        into buffers of this method -- the predictor's double buffers are recycled two batches ahead -- and nothing of
+        the batch is referenced once the call returns.  Waits for the device."""
+        if self._gs_geom is None:
+            raise RuntimeError("render_pngs needs the device: this run was built over injected batches")
+        bs, H, W, C, dev = self._gs_geom
+        n = batch.hi - batch.lo
+        if images.shape[0] != n or (found is not None and len(found) != n):
+            raise ValueError(f"render_pngs: a batch of {n} images needs {n} scans and delineations")
+        if self._png is None:
+            self._png = PngRenderer(bs, H, W, dev)
+        gs_segs = None
+        if found is not None:
+            gs_segs = np.stack([f[0] for f in found]).astype(np.uint16)
+            if gs_labels is None:
+                if self._gs is None:
+                    self._gs = DelineationLabels(*self._gs_geom)
+                gs_labels = self._gs.area(torch.from_numpy(np.ascontiguousarray(gs_segs).view(np.int16)).to(dev))
+        return batch_pictures(self._png, C, images, pred_labels=batch.labels if pred_map else None, gt_labels=gt,
+                              truths=truths, gs_segs=gs_segs, gs_labels=gs_labels,
+                              both_overlay=truths is not None and gs_segs is not None, col_range=col_range)
 
     def close(self) -> None:
         for p in (self.pool, self.host_ties):

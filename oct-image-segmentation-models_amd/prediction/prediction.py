@@ -1,6 +1,8 @@
 """``predict``: the reference's prediction workflow
 (oct_image_segmentation_models/prediction/prediction.py:48-186, savers :189-329) -- the evaluation stack
-without labels/metrics.  Batched device forward with device arg-max; host tail re-stated; PNGs out of scope."""
+without labels/metrics.  Batched device forward with device arg-max; host tail re-stated.  With
+``PredictionParams(png_plots=True)`` the reference's PNG pictures (prediction.py:243-263, :307-320) are rasterised on the
+device (``oct_render_rgba``, ``evaluation/render.py``); ``categorical_pred_N.png`` is out of scope."""
 from __future__ import annotations
 
 import logging as log
@@ -14,6 +16,7 @@ import numpy as np
 from .. import parallel
 from ..common import h5io, utils
 from ..evaluation.pipeline import InferenceRun
+from ..evaluation.render import PREDICTION_PNG_NAMES, write_pictures
 from ..min_path_processing import graph_search  # noqa: F401  (re-exported: callers build graph structures through it)
 from ..models import get_model_class
 from .prediction_parameters import PredictionParams
@@ -52,6 +55,7 @@ def predict(predict_params: PredictionParams) -> List[PredictionOutput]:
 
     outputs: List[PredictionOutput] = []
     lo, hi = parallel.shard_range(len(images), rank, world)
+    png_plots = bool(getattr(predict_params, "png_plots", False)) and predict_params.save_params.png_images is True
     # the device pipeline of evaluate_model (evaluation/pipeline.py::InferenceRun), without ground truth
     with InferenceRun(predict_params.loaded_model, images[lo:hi], predict_params.batch_size, num_classes,
                       graph_search=predict_params.graph_search, gs_device=predict_params.gs_device,
@@ -67,6 +71,11 @@ def predict(predict_params: PredictionParams) -> List[PredictionOutput]:
                 start_stage_time = time.time()
                 gs_labels, _ = run.gs_labels(batch, gs_found)
                 gs_stage_time = (time.time() - start_stage_time) / (b1 - b0)
+            pictures = None
+            if png_plots:
+                pictures = run.render_pngs(batch, images[b0:b1], gs_found, gs_labels=gs_labels,
+                                           pred_map=predict_params.save_params.predicted_labels is True,
+                                           col_range=(predict_params.col_error_range[0], predict_params.col_error_range[-1]))
             for i in range(b0, b1):
                 predict_image, image_name, image_output_dir = images[i], dataset.image_names[i], Path(dataset.image_output_dirs[i])
                 os.makedirs(image_output_dir, exist_ok=True)
@@ -94,6 +103,8 @@ def predict(predict_params: PredictionParams) -> List[PredictionOutput]:
                         graph_time = time.time() - start_graph_time
                     save_graph_based_prediction_results(predict_params, image_name, gs_prediction_label, gs_pred_segs,
                                                         graph_time, image_output_dir)
+                if pictures is not None:
+                    write_pictures(image_output_dir, pictures, i - b0, PREDICTION_PNG_NAMES)
                 outputs.append(PredictionOutput(image=predict_image, image_name=image_name, image_output_dir=image_output_dir,
                                                 predicted_labels=predicted_labels, categorical_pred=categorical_pred,
                                                 boundary_maps=boundary_maps, gs_pred_segs=gs_pred_segs))
@@ -107,6 +118,8 @@ def save_predict_config_file(predict_params: PredictionParams):
              "error_col_inc_range": np.array((predict_params.col_error_range[0], predict_params.col_error_range[-1]))}
     if not getattr(predict_params, "binarize", True):
         attrs["binarize"] = np.array(False)      # recorded only when it departs from the default: binarize=True files stay as they were
+    if getattr(predict_params, "png_plots", False):
+        attrs["png_plots"] = np.array(True)      # likewise
     h5io.save(predict_params.config_output_dir / Path("prediction_params.hdf5"), {}, attrs)
 
 

@@ -14,7 +14,8 @@ class PredictionSaveParams:
                  boundary_maps: bool = True) -> None:
         self.predicted_labels = predicted_labels
         self.categorical_pred = categorical_pred
-        self.png_images = png_images      # accepted for compatibility; PNG plotting is out of scope
+        # takes effect with PredictionParams(png_plots=True): False keeps every PNG picture from being written
+        self.png_images = png_images
         self.boundary_maps = boundary_maps
 
 
@@ -24,7 +25,7 @@ class PredictionParams:
                  graph_search: bool = False, trim_maps: bool = False, trim_ref_ind: int = 0,
                  trim_window: tuple = (0, 0), col_error_range: tuple = None, batch_size: int = 32, gs_device: bool = False,
                  gs_device_ties: str = "host", gs_workers: Union[int, None] = None, gs_labels_device: bool = False,
-                 binarize: bool = True) -> None:
+                 binarize: bool = True, png_plots: bool = False) -> None:
         self.model_path = Path(model_path)
         self.mlflow_tracking_uri = mlflow_tracking_uri
         self.mlflow_run_uuid = mlflow_run_uuid
@@ -50,6 +51,9 @@ class PredictionParams:
         self.gs_labels_device = bool(gs_labels_device)
         # extension, as EvaluationParameters.binarize: False = soft boundary maps of the class probabilities
         self.binarize = bool(binarize)
+        # extension, as EvaluationParameters.png_plots: segmentation_map.png, raw_image.png and, with graph search,
+        # gs_predicted_segmentation_map.png and gs_predicted_boundaries_ovelay_plot.png (columns col_error_range)
+        self.png_plots = bool(png_plots)
         self.col_error_range = col_error_range
         if col_error_range is None:
             self.col_error_range = range(dataset.images[0].shape[1])  # image_width
