@@ -191,3 +191,52 @@ def get_option(name: str) -> int:
 def check(rc: int, what: str = "") -> None:
     if rc != 0:
         raise OctError(f"{what} failed (rc={rc}): {lib().oct_last_error().decode()}")
+
+
+def stream_ptr(device) -> C.c_void_p:
+    """The current HIP stream of ``device``, as the ABI's ``stream`` argument."""
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def call(name: str, device, *args) -> None:
+    """Call the library's ``name(*args)`` with ``device`` current; a non-zero return code raises ``OctError``."""
+    import torch
+    with torch.cuda.device(device):
+        check(getattr(lib(), name)(*args), name)
+
+
+def expect(t, what: str, *, device, dtype, shape=None, numel=None) -> None:
+    """Raise ``OctError`` unless tensor ``t`` may be handed to a kernel as ``what``: on ``device`` (a ``torch.device``),
+    of ``dtype`` (one, or a tuple of allowed ones), contiguous, and of ``shape`` -- a tuple in which ``None`` matches
+    any extent -- and / or of ``numel`` elements, for the (B,H,W[,1]) arguments that are compared by size."""
+    dtypes = dtype if isinstance(dtype, tuple) else (dtype,)
+    ok = t.device == device and t.dtype in dtypes and t.is_contiguous() and (numel is None or t.numel() == numel)
+    if ok and shape is not None:
+        ok = t.dim() == len(shape) and all(e is None or e == s for e, s in zip(shape, t.shape))
+    if not ok:
+        want = f"{numel} elements" if shape is None else "shape (" + ",".join("n" if e is None else str(e) for e in shape) + ")"
+        raise OctError(f"{what} must be a contiguous {' / '.join(map(str, dtypes))} tensor of {want} on {device}, not "
+                       f"{'a' if t.is_contiguous() else 'a non-contiguous'} {t.dtype} {tuple(t.shape)} one on {t.device}")
+
+
+def expect_map_pair(pred, gt, *, device, batch: int, H: int, W: int) -> int:
+    """The two arguments of the kernels that compare class maps: uint8 (n,H,W) predictions and ground truth on ``device``
+    with one count n in 1..batch, which is returned."""
+    import torch
+    expect(pred, "pred", device=device, dtype=torch.uint8, shape=(None, H, W))
+    n = pred.shape[0]
+    expect(gt, "gt", device=device, dtype=torch.uint8, shape=(n, H, W))
+    if not 1 <= n <= batch:
+        raise OctError(f"pred and gt need a count n in 1..{batch}, not {n}")
+    return n
+
+
+def out_view(out, own, n: int, what: str = "out"):
+    """The output of a call over ``n`` images: ``own[:n]``, a view of the wrapper's buffer, unless the caller passes
+    ``out``, which must then look exactly like that view."""
+    view = own[:n]
+    if out is None:
+        return view
+    expect(out, what, device=own.device, dtype=own.dtype, shape=tuple(view.shape))
+    return out

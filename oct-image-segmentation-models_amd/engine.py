@@ -122,22 +122,21 @@ class UNetEngine:
     def num_classes(self): return self.cfg.n_cls
 
     def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return _hip.stream_ptr(self.device)
+
+    def _call(self, name: str, *args) -> None:
+        """``name(handle, *args)`` of the library, on the engine's device."""
+        _hip.call(name, self.device, self._h, *args)
 
     def _check_x(self, x: torch.Tensor):
-        if x.device != self.device or not x.is_contiguous():
-            raise OctError("input must be a contiguous tensor on the engine's device")
-        if x.dim() != 4 or tuple(x.shape[1:]) != (self.cfg.H, self.cfg.W, self.cfg.in_ch):
-            raise OctError(f"input must be (B,{self.cfg.H},{self.cfg.W},{self.cfg.in_ch}), got {tuple(x.shape)}")
-        if x.dtype not in (torch.uint8, torch.float32):
-            raise OctError("input must be uint8 (raw) or float32 (already /255)")
+        # uint8: raw scans; float32: already / 255
+        _hip.expect(x, "input", device=self.device, dtype=(torch.uint8, torch.float32),
+                    shape=(None, self.cfg.H, self.cfg.W, self.cfg.in_ch))
         if not 1 <= x.shape[0] <= self.cfg.max_batch:
             raise OctError(f"batch {x.shape[0]} outside 1..max_batch={self.cfg.max_batch}")
 
     def _check_labels(self, labels: torch.Tensor, B: int):
-        if labels.device != self.device or labels.dtype != torch.uint8 or not labels.is_contiguous() \
-                or labels.numel() != B * self.cfg.H * self.cfg.W:
-            raise OctError("labels must be a contiguous uint8 (B,H,W[,1]) tensor on the engine's device")
+        _hip.expect(labels, "labels (B,H,W[,1])", device=self.device, dtype=torch.uint8, numel=B * self.cfg.H * self.cfg.W)
 
     def _io(self, B, labels, want_probs, want_argmax, probs_out=None, argmax_out=None):
         probs = am = None
@@ -159,18 +158,18 @@ class UNetEngine:
         if labels is not None:
             self._check_labels(labels, B)
         io, probs, am = self._io(B, labels, want_probs, want_argmax, probs_out, argmax_out)
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.lib().oct_unet_forward(self._h, x.data_ptr(), int(x.dtype == torch.uint8), B,
-                                                   int(training), C.byref(io), self._stream()), "oct_unet_forward")
+        self._call("oct_unet_forward", x.data_ptr(), int(x.dtype == torch.uint8), B, int(training), C.byref(io), self._stream())
         self._keep = [x, labels, probs, am]
         return probs, am
 
+    def _loss(self, name: str, n: int, smooth: float) -> torch.Tensor:
+        out = torch.empty(n, dtype=torch.float32, device=self.device)
+        self._call(name, smooth, out.data_ptr(), self._stream())
+        return out
+
     def loss_dice(self, smooth: float = 1e-5) -> torch.Tensor:
         """[dice_loss_macro, dice_loss_micro, dice_coef_macro, dice_coef_micro] of the last forward (device tensor)."""
-        out = torch.empty(4, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.lib().oct_unet_loss_dice(self._h, smooth, out.data_ptr(), self._stream()), "oct_unet_loss_dice")
-        return out
+        return self._loss("oct_unet_loss_dice", 4, smooth)
 
     def set_focal_dice(self, focal_loss_weight: float = 0.5, gamma: float = 2.0, class_weight=None) -> None:
         """Select ``focal_dice_loss`` (reference custom_losses.py:98-178) for the following forward / loss / backward
@@ -184,16 +183,11 @@ class UNetEngine:
         self._focal_active = float(focal_loss_weight) > 0.0
         if self._focal_active:
             self._bce_active = False     # the library clears it too: the two losses share one slot of the Dice rows
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.lib().oct_unet_set_focal_dice(self._h, float(focal_loss_weight), float(gamma),
-                                                          cw.data_ptr() if cw is not None else None), "oct_unet_set_focal_dice")
+        self._call("oct_unet_set_focal_dice", float(focal_loss_weight), float(gamma), cw.data_ptr() if cw is not None else None)
 
     def loss_focal_dice(self, smooth: float = 1e-5) -> torch.Tensor:
         """loss_dice() + [focal term, w*focal+(1-w)*dice_macro, w*focal+(1-w)*dice_micro, 0] (device tensor, 8 floats)."""
-        out = torch.empty(8, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.lib().oct_unet_loss_focal_dice(self._h, smooth, out.data_ptr(), self._stream()), "oct_unet_loss_focal_dice")
-        return out
+        return self._loss("oct_unet_loss_focal_dice", 8, smooth)
 
     def set_bce_dice(self, on: bool = True) -> None:
         """Select ``bce_dice_loss`` (reference custom_losses.py:84-91) for the following forward / loss / backward calls:
@@ -202,30 +196,22 @@ class UNetEngine:
         self._bce_active = bool(on)
         if self._bce_active:
             self._focal_active = False
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.lib().oct_unet_set_bce_dice(self._h, int(bool(on))), "oct_unet_set_bce_dice")
+        self._call("oct_unet_set_bce_dice", int(bool(on)))
 
     def loss_bce_dice(self, smooth: float = 1e-5) -> torch.Tensor:
         """loss_dice() + [bce mean, 0, bce + dice_loss_micro, 0] (device tensor, 8 floats)."""
-        out = torch.empty(8, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.lib().oct_unet_loss_bce_dice(self._h, smooth, out.data_ptr(), self._stream()), "oct_unet_loss_bce_dice")
-        return out
+        return self._loss("oct_unet_loss_bce_dice", 8, smooth)
 
     def backward(self, labels: torch.Tensor, macro: bool = True, loss_scale: float = 1.0):
         self._check_labels(labels, labels.shape[0])
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.lib().oct_unet_backward(self._h, labels.data_ptr(), int(macro), loss_scale, self._stream()),
-                       "oct_unet_backward")
+        self._call("oct_unet_backward", labels.data_ptr(), int(macro), loss_scale, self._stream())
 
     def adam_step(self, lr=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7):
         if "m" not in self._opt:
             self._opt["m"] = torch.zeros_like(self.params); self._opt["v"] = torch.zeros_like(self.params)
         self.opt_step += 1
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.lib().oct_adam_step(self.params.data_ptr(), self.grads.data_ptr(), self._opt["m"].data_ptr(),
-                                                self._opt["v"].data_ptr(), self.n_params, lr, beta_1, beta_2, epsilon,
-                                                self.opt_step, self._stream()), "oct_adam_step")
+        _hip.call("oct_adam_step", self.device, self.params.data_ptr(), self.grads.data_ptr(), self._opt["m"].data_ptr(),
+                  self._opt["v"].data_ptr(), self.n_params, lr, beta_1, beta_2, epsilon, self.opt_step, self._stream())
 
     def sgd_step(self, lr=1e-2, momentum=0.0):
         mom = None
@@ -234,9 +220,8 @@ class UNetEngine:
                 self._opt["mom"] = torch.zeros_like(self.params)
             mom = self._opt["mom"].data_ptr()
         self.opt_step += 1
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.lib().oct_sgd_step(self.params.data_ptr(), self.grads.data_ptr(), mom, self.n_params, lr,
-                                               momentum, self._stream()), "oct_sgd_step")
+        _hip.call("oct_sgd_step", self.device, self.params.data_ptr(), self.grads.data_ptr(), mom, self.n_params, lr, momentum,
+                  self._stream())
 
     # state buffers of oct_opt_step by kind, in the ABI's slot order (Adam and SGD share theirs with adam_step / sgd_step)
     _OPT_SLOTS = {_hip.OPT_SGD: ("mom",), _hip.OPT_ADAM: ("m", "v", "vhat"), _hip.OPT_ADAMAX: ("adamax.m", "adamax.u"),
@@ -279,9 +264,8 @@ class UNetEngine:
             var_off, scratch = self._opt["clip.var_off"].data_ptr(), self._opt["clip.scratch"].data_ptr()
             n_vars = self._opt["clip.var_off"].numel() - 1
         self.opt_step += 1
-        with torch.cuda.device(self.device):
-            _hip.check(l.oct_opt_step(C.byref(desc), self.params.data_ptr(), self.grads.data_ptr(), slots, self.n_params,
-                                      self.opt_step, var_off, n_vars, scratch, self._stream()), "oct_opt_step")
+        _hip.call("oct_opt_step", self.device, C.byref(desc), self.params.data_ptr(), self.grads.data_ptr(), slots, self.n_params,
+                  self.opt_step, var_off, n_vars, scratch, self._stream())
 
     # ---- data-parallel overlap hook ---------------------------------------------------
     def grad_tail_offset(self) -> int:
@@ -294,8 +278,7 @@ class UNetEngine:
             with torch.cuda.device(self.device):
                 event.record()          # torch creates the HIP event lazily, at its first record
         self._tail_event = event        # keep the handle alive
-        _hip.check(_hip.lib().oct_unet_set_tail_event(self._h, C.c_void_p(event.cuda_event) if event is not None else None),
-                   "oct_unet_set_tail_event")
+        self._call("oct_unet_set_tail_event", C.c_void_p(event.cuda_event) if event is not None else None)
 
     # ---- arithmetic mode of the convolution kernels (reported by bench.py) --------------------------
     def mfma_products(self) -> int:
@@ -316,26 +299,24 @@ class UNetEngine:
 
     # ---- per-launch profiler ---------------------------------------------------------------------
     def profile_begin(self):
-        _hip.check(_hip.lib().oct_unet_profile_begin(self._h), "oct_unet_profile_begin")
+        self._call("oct_unet_profile_begin")
 
     def profile_end(self) -> List[dict]:
         """One dict per (kernel instantiation, layer): launches, total_ms, algorithmic flops and bytes."""
         n = C.c_int(0)
         buf = (_hip.ProfileEntry * 1024)()
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.lib().oct_unet_profile_end(self._h, buf, 1024, C.byref(n)), "oct_unet_profile_end")
+        self._call("oct_unet_profile_end", buf, 1024, C.byref(n))
         return [dict(kernel=buf[i].kernel.decode(), layer=buf[i].layer.decode(), launches=buf[i].launches,
                      total_ms=buf[i].total_ms, flops=buf[i].flops, bytes=buf[i].bytes) for i in range(min(n.value, 1024))]
 
     # ---- dropout replay (tests) -------------------------------------------------------------------
     def set_dropout_step(self, step: int):
-        _hip.check(_hip.lib().oct_unet_set_dropout_step(self._h, step), "oct_unet_set_dropout_step")
+        self._call("oct_unet_set_dropout_step", step)
 
     def dropout_mask(self, B: int) -> torch.Tensor:
         P = self.cfg.pool_layers
         m = torch.empty((B, self.cfg.H >> P, self.cfg.W >> P, self.cfg.start_neurons << P), dtype=torch.uint8, device=self.device)
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.lib().oct_unet_dropout_mask(self._h, B, m.data_ptr(), self._stream()), "oct_unet_dropout_mask")
+        self._call("oct_unet_dropout_mask", B, m.data_ptr(), self._stream())
         return m
 
     # ---- inference hipGraph ------------------------------------------------------------------------
@@ -347,40 +328,32 @@ class UNetEngine:
         self._graph_keep = [x, probs, am]
         s = torch.cuda.Stream(self.device)
         s.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.lib().oct_unet_graph_capture(self._h, x.data_ptr(), int(x.dtype == torch.uint8), x.shape[0],
-                                                         C.byref(io), C.c_void_p(s.cuda_stream)), "oct_unet_graph_capture")
+        self._call("oct_unet_graph_capture", x.data_ptr(), int(x.dtype == torch.uint8), x.shape[0], C.byref(io),
+                   C.c_void_p(s.cuda_stream))
         torch.cuda.current_stream(self.device).wait_stream(s)
         return probs, am
 
     def graph_launch(self):
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.lib().oct_unet_graph_launch(self._h, self._stream()), "oct_unet_graph_launch")
+        self._call("oct_unet_graph_launch", self._stream())
 
     # ---- post-step on device ---------------------------------------------------------------------
     def boundary_maps(self, labels: torch.Tensor, bg_ilm: bool = True, bg_csi: bool = False) -> torch.Tensor:
         """(B,H,W) uint8 class maps (e.g. the arg-max output) -> (B, num_classes-1, H, W) uint8 boundary maps."""
-        if labels.device != self.device or labels.dtype != torch.uint8 or not labels.is_contiguous() or labels.dim() != 3:
-            raise OctError("labels must be a contiguous uint8 (B,H,W) tensor on the engine's device")
-        B, H, W = labels.shape
-        out = torch.empty((B, self.cfg.n_cls - 1, H, W), dtype=torch.uint8, device=self.device)
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.lib().oct_boundary_maps(labels.data_ptr(), B, H, W, self.cfg.n_cls, int(bg_ilm), int(bg_csi),
-                                                    out.data_ptr(), self._stream()), "oct_boundary_maps")
-        return out
+        _hip.expect(labels, "labels (B,H,W)", device=self.device, dtype=torch.uint8, shape=(None, None, None))
+        return self._maps("oct_boundary_maps", labels, bg_ilm, bg_csi)
 
     def boundary_maps_soft(self, probs: torch.Tensor, bg_ilm: bool = True, bg_csi: bool = False) -> torch.Tensor:
         """(B,H,W,num_classes) float32 class probabilities (the forward's ``probs``) -> (B, num_classes-1, H, W) uint8
         soft boundary maps: ``convert_predictions_to_maps_semantic`` of the probabilities themselves
         (``oct_boundary_maps_soft``; ``common.utils.soft_boundary_maps_reference`` restates it)."""
-        if probs.device != self.device or probs.dtype != torch.float32 or not probs.is_contiguous() or probs.dim() != 4 \
-                or probs.shape[3] != self.cfg.n_cls:
-            raise OctError(f"probs must be a contiguous float32 (B,H,W,{self.cfg.n_cls}) tensor on the engine's device")
-        B, H, W, _ = probs.shape
+        _hip.expect(probs, "probs (B,H,W,C)", device=self.device, dtype=torch.float32, shape=(None, None, None, self.cfg.n_cls))
+        return self._maps("oct_boundary_maps_soft", probs, bg_ilm, bg_csi)
+
+    def _maps(self, name: str, src: torch.Tensor, bg_ilm: bool, bg_csi: bool) -> torch.Tensor:
+        B, H, W = src.shape[:3]
         out = torch.empty((B, self.cfg.n_cls - 1, H, W), dtype=torch.uint8, device=self.device)
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.lib().oct_boundary_maps_soft(probs.data_ptr(), B, H, W, self.cfg.n_cls, int(bg_ilm), int(bg_csi),
-                                                         out.data_ptr(), self._stream()), "oct_boundary_maps_soft")
+        _hip.call(name, self.device, src.data_ptr(), B, H, W, self.cfg.n_cls, int(bg_ilm), int(bg_csi), out.data_ptr(),
+                  self._stream())
         return out
 
     def augment(self, x_u8: torch.Tensor, labels: Optional[torch.Tensor], ops, seed: int, out=None):
@@ -390,35 +363,29 @@ class UNetEngine:
         uploaded) or a uint8 device tensor of B*32 bytes that already holds validated descriptors.  ``out``: optional
         ``(x_out, labels_out)`` tensors to write into.  Asynchronous on the current stream."""
         from .common.augmentation import AUG_OP_DTYPE, AUG_SP
-        if x_u8.device != self.device or x_u8.dtype != torch.uint8 or not x_u8.is_contiguous() or x_u8.dim() != 4:
-            raise OctError("augment: images must be a contiguous uint8 (B,H,W,C) tensor on the engine's device")
+        u8 = dict(device=self.device, dtype=torch.uint8)
+        _hip.expect(x_u8, "augment: images (B,H,W,C)", shape=(None, None, None, None), **u8)
         B, H, W, Cn = x_u8.shape
-        if labels is not None and (labels.device != self.device or labels.dtype != torch.uint8 or not labels.is_contiguous()
-                                   or labels.numel() != B * H * W):
-            raise OctError("augment: labels must be a contiguous uint8 (B,H,W[,1]) tensor on the engine's device")
+        if labels is not None:
+            _hip.expect(labels, "augment: labels (B,H,W[,1])", numel=B * H * W, **u8)
         if isinstance(ops, np.ndarray):
             if ops.dtype != AUG_OP_DTYPE or ops.shape != (B,):
                 raise OctError("augment: ops must hold one AUG_OP_DTYPE descriptor per sample")
             if ops["kind"].min() < 0 or ops["kind"].max() > AUG_SP:
                 raise OctError("augment: descriptor kind outside 0..5")
             ops = torch.from_numpy(np.ascontiguousarray(ops).view(np.uint8).copy()).to(self.device)
-        if ops.device != self.device or ops.dtype != torch.uint8 or not ops.is_contiguous() or ops.numel() != B * AUG_OP_DTYPE.itemsize:
-            raise OctError("augment: ops must be B*32 descriptor bytes on the engine's device")
+        _hip.expect(ops, "augment: ops (B*32 descriptor bytes)", numel=B * AUG_OP_DTYPE.itemsize, **u8)
         x_out, lab_out = out if out is not None else (None, None)
         if x_out is None:
             x_out = torch.empty(x_u8.shape, dtype=torch.float32, device=self.device)
         if labels is not None and lab_out is None:
             lab_out = torch.empty(labels.shape, dtype=torch.uint8, device=self.device)
-        if x_out.device != self.device or x_out.dtype != torch.float32 or not x_out.is_contiguous() or x_out.shape != x_u8.shape:
-            raise OctError("augment: out[0] must be a contiguous float32 tensor of the images' shape on the engine's device")
-        if labels is not None and (lab_out.device != self.device or lab_out.dtype != torch.uint8 or not lab_out.is_contiguous()
-                                   or lab_out.numel() != labels.numel()):
-            raise OctError("augment: out[1] must be a contiguous uint8 tensor of the labels' size on the engine's device")
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.lib().oct_augment_batch(
-                x_u8.data_ptr(), labels.data_ptr() if labels is not None else None, ops.data_ptr(), B, H, W, Cn,
-                int(seed) & 0xFFFFFFFFFFFFFFFF, x_out.data_ptr(), lab_out.data_ptr() if labels is not None else None,
-                self._stream()), "oct_augment_batch")
+        _hip.expect(x_out, "augment: out[0]", device=self.device, dtype=torch.float32, shape=tuple(x_u8.shape))
+        if labels is not None:
+            _hip.expect(lab_out, "augment: out[1]", numel=labels.numel(), **u8)
+        _hip.call("oct_augment_batch", self.device, x_u8.data_ptr(), labels.data_ptr() if labels is not None else None,
+                  ops.data_ptr(), B, H, W, Cn, int(seed) & 0xFFFFFFFFFFFFFFFF, x_out.data_ptr(),
+                  lab_out.data_ptr() if labels is not None else None, self._stream())
         return x_out, (lab_out if labels is not None else None)
 
     # ---- weights exchange --------------------------------------------------------------------------

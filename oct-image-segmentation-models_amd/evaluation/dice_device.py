@@ -9,7 +9,6 @@ two kernels (``oct_confusion_counts`` / ``oct_area_labels``, include/oct_unet.h)
 ``dice_from_counts`` turns one matrix into exactly what ``evaluation._dice_metrics`` returns for the image."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional, Tuple
 
 import numpy as np
@@ -94,13 +93,6 @@ def dice_from_counts(counts: np.ndarray, metrics) -> Tuple[Optional[np.ndarray],
     return dc, dm, dmi
 
 
-def _check_maps(device, H, W, *maps):
-    for t in maps:
-        if t.device != device or t.dtype != torch.uint8 or not t.is_contiguous() or t.dim() != 3 \
-                or tuple(t.shape[1:]) != (H, W):
-            raise _hip.OctError(f"class maps must be contiguous uint8 (n,{H},{W}) tensors on {device}")
-
-
 class ConfusionCounts:
     """``oct_confusion_counts`` for up to ``batch`` images of one shape: ``(pred, gt)`` -> (n, C*C + 1) int32 rows on the
     device (the bits are the uint32 counts), queued on the current stream."""
@@ -112,21 +104,13 @@ class ConfusionCounts:
             raise _hip.OctError(f"oct_confusion_counts does not support B={batch}, {H}x{W}, {num_classes} classes")
         self.device = torch.device(device)
         self.out = torch.empty((self.B, self.C * self.C + 1), dtype=torch.int32, device=self.device)
+        self.outs, self.geometry = (self.out,), (self.B, self.H, self.W, self.C)
 
     def __call__(self, pred: torch.Tensor, gt: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        _check_maps(self.device, self.H, self.W, pred, gt)
-        n = pred.shape[0]
-        if gt.shape[0] != n or not 1 <= n <= self.B:
-            raise _hip.OctError(f"pred and gt need the same count n in 1..{self.B}")
-        if out is None:
-            out = self.out[:n]
-        elif out.device != self.device or out.dtype != torch.int32 or not out.is_contiguous() \
-                or tuple(out.shape) != (n, self.C * self.C + 1):
-            raise _hip.OctError(f"out must be a contiguous int32 ({n},{self.C * self.C + 1}) tensor on {self.device}")
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.lib().oct_confusion_counts(pred.data_ptr(), gt.data_ptr(), n, self.H, self.W, self.C,
-                                                       out.data_ptr(), stream), "oct_confusion_counts")
+        n = _hip.expect_map_pair(pred, gt, device=self.device, batch=self.B, H=self.H, W=self.W)
+        out = _hip.out_view(out, self.out, n)
+        _hip.call("oct_confusion_counts", self.device, pred.data_ptr(), gt.data_ptr(), n, self.H, self.W, self.C,
+                  out.data_ptr(), _hip.stream_ptr(self.device))
         return out
 
     def to_host(self, rows: torch.Tensor, first_image: int = 0) -> np.ndarray:
@@ -147,22 +131,13 @@ class AreaLabels:
         self.out = torch.empty((self.B, self.H, self.W), dtype=torch.uint8, device=self.device)
 
     def __call__(self, segs: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        if segs.device != self.device or segs.element_size() != 2 or segs.is_floating_point() or not segs.is_contiguous() \
-                or segs.dim() != 3 or tuple(segs.shape[1:]) != (self.C - 1, self.W):
-            raise _hip.OctError(f"segs must be a contiguous 16-bit integer (n,{self.C - 1},{self.W}) tensor on {self.device}")
+        _hip.expect(segs, "segs", device=self.device, dtype=(torch.int16, torch.uint16), shape=(None, self.C - 1, self.W))
         n = segs.shape[0]
         if not 1 <= n <= self.B:
             raise _hip.OctError(f"segs needs a count n in 1..{self.B}")
-        if out is None:
-            out = self.out[:n]
-        else:
-            _check_maps(self.device, self.H, self.W, out)
-            if out.shape[0] != n:
-                raise _hip.OctError(f"out must hold {n} class maps")
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.lib().oct_area_labels(segs.data_ptr(), n, self.H, self.W, self.C, out.data_ptr(), stream),
-                       "oct_area_labels")
+        out = _hip.out_view(out, self.out, n)
+        _hip.call("oct_area_labels", self.device, segs.data_ptr(), n, self.H, self.W, self.C, out.data_ptr(),
+                  _hip.stream_ptr(self.device))
         return out
 
 

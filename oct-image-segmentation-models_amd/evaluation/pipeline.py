@@ -17,14 +17,14 @@ import torch
 
 from ..min_path_processing.device_search import DeviceMinPath, LazyPool, merge_ties
 from ..min_path_processing.pool import SegmentPool, default_workers
-from .dice_device import ConfusionCounts, DelineationLabels, counts_matrix
+from .dice_device import ConfusionCounts, DelineationLabels
 from .render import PngRenderer, batch_pictures
 from .surface import SurfaceDistances
 
 
 class Batch(NamedTuple):
-    """What the device yields for images ``lo:hi`` of a run.  A new device-side post-process is one more field here,
-    filled by ``BatchedPredictor`` and by ``host_batches``, and nowhere else."""
+    """What the device yields for images ``lo:hi`` of a run.  A new device-side post-process is one more field here and
+    one more entry of ``_stages``, and nothing else: ``BatchedPredictor`` and ``host_batches`` walk that list."""
     lo: int
     hi: int
     labels: np.ndarray                             # (n, H, W) uint8 arg-max class maps
@@ -32,6 +32,29 @@ class Batch(NamedTuple):
     surface: Optional[np.ndarray] = None           # (n, C-1, 6) float64 surface-distance rows
     minpath: Optional[Tuple[np.ndarray, ...]] = None   # rows (n, C-1, W) uint16, cost (n, C-1) float64, tied (n, C-1) bool
     confusion: Optional[np.ndarray] = None         # (n, C, C) uint32 confusion counts [gt][pred] of labels against the ground truth
+
+
+class _Stage(NamedTuple):
+    """One per-batch device post-process: the ``Batch`` field it fills, the wrapper that runs it -- ``run(*inputs, *outs)``
+    queues it on the current stream, ``run.outs`` are its own output buffers for a full batch, ``run.to_host`` turns
+    output rows into the field's value -- and what it reads: the boundary maps, or else the arg-max maps and the ground
+    truth."""
+    field: str
+    run: object
+    on_maps: bool
+
+    def launch(self, n: int, outs, labels, gt, maps) -> None:
+        inputs = (maps[:n],) if self.on_maps else (labels[:n], gt[:n])
+        self.run(*inputs, *(t[:n] for t in outs))
+
+    def to_host(self, n: int, outs, first_image: int):
+        return self.run.to_host(*(t[:n] for t in outs), first_image=first_image)
+
+
+def _stages(surface, confusion, minpath, have_gt: bool = True) -> list:
+    """The stages to run, in their order on the stream; those that read the ground truth only when there is one."""
+    every = (_Stage("surface", surface, False), _Stage("confusion", confusion, False), _Stage("minpath", minpath, True))
+    return [st for st in every if st.run is not None and (st.on_maps or have_gt)]
 
 
 class BatchedPredictor:
@@ -71,31 +94,20 @@ class BatchedPredictor:
         self.map_pin = [torch.empty((self.B, C - 1, H, W), dtype=torch.uint8).pin_memory() for _ in range(2)] if want_maps else None
         self.lab_dev = [torch.empty((self.B, H, W), dtype=torch.uint8, device=dev) for _ in range(2)]
         self.map_dev = [torch.empty((self.B, C - 1, H, W), dtype=torch.uint8, device=dev) for _ in range(2)] if want_maps else None
-        self.surf = surface
-        if surface is not None:
-            if (surface.B, surface.H, surface.W, surface.C) != (self.B, H, W, C):
-                raise ValueError("surface: SurfaceDistances built for another batch / shape")
-            self.sd_dev = [torch.empty((self.B, C - 1, 6), dtype=torch.float64, device=dev) for _ in range(2)]
-            self.sd_pin = [torch.empty((self.B, C - 1, 6), dtype=torch.float64).pin_memory() for _ in range(2)]
-        self.conf = confusion
-        if confusion is not None:
-            if (confusion.B, confusion.H, confusion.W, confusion.C) != (self.B, H, W, C):
-                raise ValueError("confusion: ConfusionCounts built for another batch / shape")
-            self.cf_dev = [torch.empty((self.B, C * C + 1), dtype=torch.int32, device=dev) for _ in range(2)]
-            self.cf_pin = [torch.empty((self.B, C * C + 1), dtype=torch.int32).pin_memory() for _ in range(2)]
-        if surface is not None or confusion is not None:
+        self.wrappers = (surface, confusion, minpath)
+        self.out_dev, self.out_pin = {}, {}                 # per stage field: device and pinned double buffers
+        every = _stages(*self.wrappers)
+        for st in every:
+            if st.on_maps and not want_maps:
+                raise ValueError(f"{st.field}: needs want_maps=True")
+            if st.run.geometry != ((self.B, C - 1, H, W) if st.on_maps else (self.B, H, W, C)):
+                raise ValueError(f"{st.field}: {type(st.run).__name__} built for another batch / shape")
+            self.out_dev[st.field] = [tuple(torch.empty_like(t) for t in st.run.outs) for _ in range(2)]
+            self.out_pin[st.field] = [tuple(torch.empty(t.shape, dtype=t.dtype).pin_memory() for t in st.run.outs) for _ in range(2)]
+        self.gt_pin = self.gt_dev = (None, None)
+        if not all(st.on_maps for st in every):
             self.gt_pin = [torch.empty((self.B, H, W), dtype=torch.uint8).pin_memory() for _ in range(2)]
             self.gt_dev = [torch.empty((self.B, H, W), dtype=torch.uint8, device=dev) for _ in range(2)]
-        self.minpath = minpath
-        if minpath is not None:
-            if not want_maps:
-                raise ValueError("minpath: needs want_maps=True")
-            if (minpath.B, minpath.M, minpath.H, minpath.W) != (self.B, C - 1, H, W):
-                raise ValueError("minpath: DeviceMinPath built for another batch / shape")
-            self.mp_dev = [(torch.empty((self.B, C - 1, W), dtype=torch.int16, device=dev),
-                            torch.empty((self.B, C - 1), dtype=torch.float64, device=dev),
-                            torch.empty((self.B, C - 1), dtype=torch.uint8, device=dev)) for _ in range(2)]
-            self.mp_pin = [tuple(torch.empty(t.shape, dtype=t.dtype).pin_memory() for t in self.mp_dev[0]) for _ in range(2)]
         self.copy_in = torch.cuda.Stream(device=dev)
         self.copy_out = torch.cuda.Stream(device=dev)
         self.probs, self.am = engine.graph_capture(self.x_dev, want_probs=self.soft_maps, want_argmax=True)
@@ -105,9 +117,9 @@ class BatchedPredictor:
         if images_u8.dtype != np.uint8:
             raise TypeError("the batched pipeline takes raw uint8 images (the /255 happens on the device)")
         have_gt = gt_u8 is not None
-        surf, conf = have_gt and self.surf is not None, have_gt and self.conf is not None
+        stages = _stages(*self.wrappers, have_gt=have_gt)
         if have_gt:
-            if not (surf or conf):
+            if all(st.on_maps for st in stages):
                 raise ValueError("ground-truth maps given to a BatchedPredictor built without surface= or confusion=")
             gt_u8 = np.ascontiguousarray(gt_u8)
             if gt_u8.dtype != np.uint8 or gt_u8.shape != images_u8.shape[:3]:
@@ -154,11 +166,11 @@ class BatchedPredictor:
             if i >= 2:
                 main.wait_event(out_done[s])                                            # device out buffers of batch i-2 downloaded
             self.lab_dev[s].copy_(self.am)
-            if surf:
-                # (the call waits for this stream once: it checks the labels on the device before the distance passes)
-                self.surf(self.lab_dev[s][:hi - lo], self.gt_dev[s][:hi - lo], out=self.sd_dev[s][:hi - lo])
-            if conf:
-                self.conf(self.lab_dev[s][:hi - lo], self.gt_dev[s][:hi - lo], out=self.cf_dev[s][:hi - lo])
+            outs = [self.out_dev[st.field][s] for st in stages]
+            srcs = (self.lab_dev[s], self.gt_dev[s], self.map_dev[s] if self.want_maps else None)
+            for st, o in zip(stages, outs):
+                if not st.on_maps:
+                    st.launch(hi - lo, o, *srcs)
             if have_gt:
                 gt_free[s].record(main)
             if self.want_maps:
@@ -166,61 +178,54 @@ class BatchedPredictor:
                     self.map_dev[s].copy_(eng.boundary_maps_soft(self.probs, bg_ilm=self.bg[0], bg_csi=self.bg[1]))
                 else:
                     self.map_dev[s].copy_(eng.boundary_maps(self.am, bg_ilm=self.bg[0], bg_csi=self.bg[1]))
-                if self.minpath is not None:
-                    self.minpath(self.map_dev[s][:hi - lo], *(t[:hi - lo] for t in self.mp_dev[s]))
+            for st, o in zip(stages, outs):
+                if st.on_maps:
+                    st.launch(hi - lo, o, *srcs)
             out_ready[s].record(main)
             with torch.cuda.stream(self.copy_out):
                 self.copy_out.wait_event(out_ready[s])
                 self.lab_pin[s].copy_(self.lab_dev[s], non_blocking=True)
                 if self.want_maps:
                     self.map_pin[s].copy_(self.map_dev[s], non_blocking=True)
-                if surf:
-                    self.sd_pin[s].copy_(self.sd_dev[s], non_blocking=True)
-                if conf:
-                    self.cf_pin[s].copy_(self.cf_dev[s], non_blocking=True)
-                if self.minpath is not None:
-                    for t_pin, t_dev in zip(self.mp_pin[s], self.mp_dev[s]):
+                for st, o in zip(stages, outs):
+                    for t_pin, t_dev in zip(self.out_pin[st.field][s], o):
                         t_pin.copy_(t_dev, non_blocking=True)
                 out_done[s].record(self.copy_out)
             if pending is not None:
-                yield self._collect(*pending, surf, conf)
+                yield self._collect(*pending, stages)
             pending = (lo, hi, s, out_done[s])
         if pending is not None:
-            yield self._collect(*pending, surf, conf)
+            yield self._collect(*pending, stages)
 
-    def _collect(self, lo, hi, s, ev, surf=False, conf=False):
+    def _collect(self, lo, hi, s, ev, stages=()):
         ev.synchronize()
         labels = self.lab_pin[s][:hi - lo].numpy().copy()
         maps = self.map_pin[s][:hi - lo].numpy().copy() if self.want_maps else None
-        surface = self.sd_pin[s][:hi - lo].numpy().copy() if surf else None
-        minpath = None
-        if self.minpath is not None:
-            rows, cost, tied = (t[:hi - lo].numpy() for t in self.mp_pin[s])
-            minpath = (rows.view(np.uint16).copy(), cost.copy(), tied.astype(bool))
-        confusion = counts_matrix(self.cf_pin[s][:hi - lo].numpy(), self.eng.cfg.n_cls, lo) if conf else None
-        return Batch(lo, hi, labels, maps, surface, minpath, confusion)
+        return Batch(lo, hi, labels, maps, **{st.field: st.to_host(hi - lo, self.out_pin[st.field][s], lo) for st in stages})
 
 
 def host_batches(model, images: np.ndarray, batch: int, *, gt_u8: Optional[np.ndarray] = None, surface=None,
                  minpath=None, confusion=None, soft_maps: bool = False) -> Iterator[Batch]:
     """The same records for images that are not uint8: x / 255 on the host (``Model.predict_labels``), one synchronous
-    forward per batch, no overlap.  ``surface`` / ``minpath`` / ``confusion`` / ``soft_maps`` as in ``BatchedPredictor``."""
+    forward per batch, no overlap.  ``surface`` / ``minpath`` / ``confusion`` / ``soft_maps`` as in ``BatchedPredictor``;
+    each stage writes its own output buffers."""
+    stages = _stages(surface, confusion, minpath, have_gt=gt_u8 is not None)
+    on_labels, on_maps = any(not st.on_maps for st in stages), any(st.on_maps for st in stages)
+
+    def upload(a):
+        return torch.from_numpy(np.ascontiguousarray(a)).to(stages[0].run.device)
+
     for lo in range(0, images.shape[0], batch):
         hi = min(lo + batch, images.shape[0])
         labels, maps = model.predict_labels(images[lo:hi], batch_size=batch, want_maps=True, bg_ilm=True, bg_csi=False,
                                             soft_maps=soft_maps)
-        rows = found = counts = None
-        if surface is not None or confusion is not None:
-            dev = (surface if surface is not None else confusion).device
-            pred_dev = torch.from_numpy(np.ascontiguousarray(labels.astype(np.uint8))).to(dev)
-            gt_dev = torch.from_numpy(gt_u8[lo:hi]).to(dev)
-        if surface is not None:
-            rows = surface(pred_dev, gt_dev).cpu().numpy()
-        if confusion is not None:
-            counts = confusion.to_host(confusion(pred_dev, gt_dev), lo)
-        if minpath is not None:
-            found = minpath.to_host(*minpath(torch.from_numpy(np.ascontiguousarray(maps)).to(minpath.device)))
-        yield Batch(lo, hi, labels, maps, rows, found, counts)
+        lab_dev, gt_dev = (upload(labels.astype(np.uint8)), upload(gt_u8[lo:hi])) if on_labels else (None, None)
+        maps_dev = upload(maps) if on_maps else None
+        fields = {}
+        for st in stages:
+            st.launch(hi - lo, st.run.outs, lab_dev, gt_dev, maps_dev)
+            fields[st.field] = st.to_host(hi - lo, st.run.outs, lo)
+        yield Batch(lo, hi, labels, maps, **fields)
 
 
 class InferenceRun:
@@ -297,6 +302,11 @@ class InferenceRun:
             return merge_ties(batch.maps, rows, tied, truths, self.host_ties, self.ties)
         return None
 
+    def _delineation_labels(self) -> DelineationLabels:
+        if self._gs is None:
+            self._gs = DelineationLabels(*self._gs_geom)
+        return self._gs
+
     def gs_labels(self, batch: Batch, found: list, gt: Optional[np.ndarray] = None) -> Tuple[np.ndarray, Optional[np.ndarray]]:
         """The class maps the batch's final delineations enclose -- ``found`` is what ``graph_search`` returned for the
         batch, so every search mode feeds it -- as (n,H,W) uint8, each equal to ``labels_from_delineations`` of the image;
@@ -306,11 +316,9 @@ class InferenceRun:
         searching this batch.  Waits for the device."""
         if self._gs_geom is None:
             raise RuntimeError("gs_labels needs the device: this run was built over injected batches")
-        if self._gs is None:
-            self._gs = DelineationLabels(*self._gs_geom)
         if len(found) != batch.hi - batch.lo:
             raise ValueError(f"gs_labels: {len(found)} delineations for a batch of {batch.hi - batch.lo} images")
-        return self._gs(np.stack([f[0] for f in found]), gt, first_image=batch.lo)
+        return self._delineation_labels()(np.stack([f[0] for f in found]), gt, first_image=batch.lo)
 
     def render_pngs(self, batch: Batch, images: np.ndarray, found: Optional[list] = None, *,
                     gt: Optional[np.ndarray] = None, truths: Optional[np.ndarray] = None, gs_labels: Optional[np.ndarray] = None,
@@ -336,9 +344,7 @@ class InferenceRun:
         if found is not None:
             gs_segs = np.stack([f[0] for f in found]).astype(np.uint16)
             if gs_labels is None:
-                if self._gs is None:
-                    self._gs = DelineationLabels(*self._gs_geom)
-                gs_labels = self._gs.area(torch.from_numpy(np.ascontiguousarray(gs_segs).view(np.int16)).to(dev))
+                gs_labels = self._delineation_labels().area(torch.from_numpy(np.ascontiguousarray(gs_segs).view(np.int16)).to(dev))
         return batch_pictures(self._png, C, images, pred_labels=batch.labels if pred_map else None, gt_labels=gt,
                               truths=truths, gs_segs=gs_segs, gs_labels=gs_labels,
                               both_overlay=truths is not None and gs_segs is not None, col_range=col_range)

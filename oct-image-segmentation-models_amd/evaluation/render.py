@@ -58,8 +58,8 @@ class PngRenderer:
         if (base.dtype != (torch.uint8 if on_dev else np.uint8)) or base.ndim not in (3, 4) or (labels and base.ndim != 3) \
                 or tuple(base.shape[1:3]) != (self.H, self.W):
             raise _hip.OctError(f"the base layer must be uint8 (n,{self.H},{self.W}[,ic]), class maps without a channel axis")
-        if on_dev and (base.device != self.device or not base.is_contiguous()):
-            raise _hip.OctError(f"a device base layer must be contiguous on {self.device}")
+        if on_dev:
+            _hip.expect(base, "a device base layer", device=self.device, dtype=torch.uint8, shape=(None,) * base.ndim)
         n = int(base.shape[0])
         ic = 1 if base.ndim == 3 else int(base.shape[3])
         K = 0
@@ -71,8 +71,8 @@ class PngRenderer:
             K = int(lines.shape[1])
             if not lines_dev:
                 lines = np.ascontiguousarray(lines).view(np.int16)
-            elif lines.device != self.device or not lines.is_contiguous():
-                raise _hip.OctError(f"device lines must be contiguous on {self.device}")
+            else:
+                _hip.expect(lines, "device lines", device=self.device, dtype=(torch.int16, torch.uint16), shape=(n, K, self.W))
         col_lo, col_hi = (0, self.W - 1) if col_range is None else (int(col_range[0]), int(col_range[-1]))
         styles = [plotting.SOLID] * K if styles is None else [int(s) for s in styles]
         colours = np.zeros((0, 3), np.int64) if colours is None else np.asarray(colours, np.int64).reshape(-1, 3)
@@ -92,26 +92,23 @@ class PngRenderer:
             st.line_style[i] = int(v) & 255
         mode = _hip.RENDER_BASE_LABELS if labels else _hip.RENDER_BASE_IMAGE
         out = np.empty((n, self.H, self.W, 4), np.uint8)
-        lib = _hip.lib()
-        stream = torch.cuda.current_stream(self.device)
-        with torch.cuda.device(self.device):
-            for lo in range(0, n, self.chunk):
-                hi = min(n, lo + self.chunk)
-                m = hi - lo
-                b_dev = base[lo:hi] if on_dev else self._upload_base(base[lo:hi])
-                r_ptr = None
-                if K:
-                    if isinstance(lines, torch.Tensor):
-                        r_dev = lines[lo:hi]
-                    else:
-                        r_dev = self.rows_dev.view(-1)[:m * K * self.W].view(m, K, self.W)
-                        r_dev.copy_(torch.from_numpy(lines[lo:hi]))
-                    r_ptr = r_dev.data_ptr()
-                _hip.check(lib.oct_render_rgba(mode, b_dev.data_ptr(), ic, r_ptr, C.byref(st), m, self.H, self.W,
-                                               self.out_dev.data_ptr(), C.c_void_p(stream.cuda_stream)), "oct_render_rgba")
-                self.out_pin[:m].copy_(self.out_dev[:m], non_blocking=True)
-                stream.synchronize()
-                out[lo:hi] = self.out_pin[:m].numpy()
+        for lo in range(0, n, self.chunk):
+            hi = min(n, lo + self.chunk)
+            m = hi - lo
+            b_dev = base[lo:hi] if on_dev else self._upload_base(base[lo:hi])
+            r_ptr = None
+            if K:
+                if isinstance(lines, torch.Tensor):
+                    r_dev = lines[lo:hi]
+                else:
+                    r_dev = self.rows_dev.view(-1)[:m * K * self.W].view(m, K, self.W)
+                    r_dev.copy_(torch.from_numpy(lines[lo:hi]))
+                r_ptr = r_dev.data_ptr()
+            _hip.call("oct_render_rgba", self.device, mode, b_dev.data_ptr(), ic, r_ptr, C.byref(st), m, self.H, self.W,
+                      self.out_dev.data_ptr(), _hip.stream_ptr(self.device))
+            self.out_pin[:m].copy_(self.out_dev[:m], non_blocking=True)
+            torch.cuda.current_stream(self.device).synchronize()
+            out[lo:hi] = self.out_pin[:m].numpy()
         return out
 
 

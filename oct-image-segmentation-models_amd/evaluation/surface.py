@@ -6,7 +6,6 @@ per-image result datasets the reference writes (:573-597).  The kernels restate 
 (PARITY UNPINNED); ``common.custom_metrics`` holds the host restatement they are tested against."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, Optional, Tuple
 
 import numpy as np
@@ -32,28 +31,24 @@ class SurfaceDistances:
             raise _hip.OctError(f"oct_surface_distances does not support B={batch}, {H}x{W}, {num_classes} classes")
         self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         self.out = torch.empty((self.B, self.C - 1, 6), dtype=torch.float64, device=self.device)
+        self.outs, self.geometry = (self.out,), (self.B, self.H, self.W, self.C)
 
     def __call__(self, pred: torch.Tensor, gt: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """(n,H,W) uint8 predicted and ground-truth class maps on the device, n <= batch -> (n, C-1, 6) float64 on the
-        device (``out`` or a view of an internal buffer that the next call overwrites), queued on the current stream."""
-        for t in (pred, gt):
-            if t.device != self.device or t.dtype != torch.uint8 or not t.is_contiguous() or t.dim() != 3 \
-                    or tuple(t.shape[1:]) != (self.H, self.W):
-                raise _hip.OctError(f"class maps must be contiguous uint8 (n,{self.H},{self.W}) tensors on {self.device}")
-        n = pred.shape[0]
-        if gt.shape[0] != n or not 1 <= n <= self.B:
-            raise _hip.OctError(f"pred and gt need the same count n in 1..{self.B}")
-        if out is None:
-            out = self.out[:n]
-        elif out.device != self.device or out.dtype != torch.float64 or not out.is_contiguous() \
-                or tuple(out.shape) != (n, self.C - 1, 6):
-            raise _hip.OctError(f"out must be a contiguous float64 ({n},{self.C - 1},6) tensor on {self.device}")
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.lib().oct_surface_distances(
-                pred.data_ptr(), gt.data_ptr(), n, self.H, self.W, self.C, self.spacing[0], self.spacing[1], self.percent,
-                self.workspace.data_ptr(), self.workspace.numel(), out.data_ptr(), stream), "oct_surface_distances")
+        device (``out`` or a view of an internal buffer that the next call overwrites), queued on the current stream.
+        The call waits for that stream once: it checks the labels on the device before the distance passes."""
+        n = _hip.expect_map_pair(pred, gt, device=self.device, batch=self.B, H=self.H, W=self.W)
+        out = _hip.out_view(out, self.out, n)
+        _hip.call("oct_surface_distances", self.device, pred.data_ptr(), gt.data_ptr(), n, self.H, self.W, self.C,
+                  self.spacing[0], self.spacing[1], self.percent, self.workspace.data_ptr(), self.workspace.numel(),
+                  out.data_ptr(), _hip.stream_ptr(self.device))
         return out
+
+    @staticmethod
+    def to_host(rows: torch.Tensor, first_image: int = 0) -> np.ndarray:
+        """Device or pinned rows -> a fresh (n, C-1, 6) float64 host array (waits for the stream).  ``first_image`` is
+        what the pipeline's stages take in common; nothing here can fail per image."""
+        return rows.cpu().numpy().copy()
 
 
 def datasets(rows: np.ndarray) -> Dict[str, np.ndarray]:

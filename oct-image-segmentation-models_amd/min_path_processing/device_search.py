@@ -11,7 +11,6 @@ resolves exact fp64 ties by the push order of its heap, which no column rule rep
 whose chosen path passes a tie (``tied``), and ``merge_ties`` sends exactly those maps back to the host search."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import Callable, List, Optional, Tuple
 
 import numpy as np
@@ -173,30 +172,20 @@ class DeviceMinPath:
         self.rows = torch.empty((self.B, self.M, self.W), dtype=torch.int16, device=self.device)
         self.cost = torch.empty((self.B, self.M), dtype=torch.float64, device=self.device)
         self.tied = torch.empty((self.B, self.M), dtype=torch.uint8, device=self.device)
+        self.outs, self.geometry = (self.rows, self.cost, self.tied), (self.B, self.M, self.H, self.W)
 
     def __call__(self, maps, rows=None, cost=None, tied=None):
         torch, _hip = self._torch, self._hip
-        if maps.device != self.device or maps.dtype != torch.uint8 or not maps.is_contiguous() or maps.dim() != 4 \
-                or tuple(maps.shape[1:]) != (self.M, self.H, self.W) or not 1 <= maps.shape[0] <= self.B:
-            raise _hip.OctError(f"maps must be a contiguous uint8 (n<={self.B},{self.M},{self.H},{self.W}) tensor on {self.device}")
+        _hip.expect(maps, "maps", device=self.device, dtype=torch.uint8, shape=(None, self.M, self.H, self.W))
         n = maps.shape[0]
-        outs = []
-        for t, own, shape, dt in ((rows, self.rows, (n, self.M, self.W), torch.int16),
-                                  (cost, self.cost, (n, self.M), torch.float64),
-                                  (tied, self.tied, (n, self.M), torch.uint8)):
-            if t is None:
-                t = own[:n]
-            elif t.device != self.device or t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != shape:
-                raise _hip.OctError(f"output must be a contiguous {dt} {shape} tensor on {self.device}")
-            outs.append(t)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.lib().oct_minpath_device(
-                maps.data_ptr(), n, self.M, self.H, self.W, self.max_grad, self.workspace.data_ptr(),
-                self.workspace.numel(), outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(), stream),
-                "oct_minpath_device")
-        return tuple(outs)
+        if not 1 <= n <= self.B:
+            raise _hip.OctError(f"maps needs a count n in 1..{self.B}, not {n}")
+        outs = tuple(_hip.out_view(t, own, n, what) for t, own, what in zip((rows, cost, tied), self.outs, ("rows", "cost", "tied")))
+        _hip.call("oct_minpath_device", self.device, maps.data_ptr(), n, self.M, self.H, self.W, self.max_grad,
+                  self.workspace.data_ptr(), self.workspace.numel(), *(t.data_ptr() for t in outs), _hip.stream_ptr(self.device))
+        return outs
 
     @staticmethod
-    def to_host(rows, cost, tied) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    def to_host(rows, cost, tied, first_image: int = 0) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        # (first_image: what the pipeline's stages take in common; nothing here can fail per image)
         return (rows.cpu().numpy().view(np.uint16).copy(), cost.cpu().numpy().copy(), tied.cpu().numpy().astype(bool))

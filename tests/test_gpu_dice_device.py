@@ -2,7 +2,6 @@
 numpy restatements -- exact equality everywhere -- the ``Batch.confusion`` field of both batch sources, and
 evaluate_model / predict with the ``metrics_device`` / ``gs_labels_device`` switches against the host path, file by file."""
 import ctypes as C
-import json
 from pathlib import Path
 
 import numpy as np
@@ -11,6 +10,7 @@ import torch
 
 from oracle import unet_numpy as on
 from tests.dice_cases import SEG_FAMILIES, host_area_labels, map_pairs, seg_family
+from tests.helpers import save_untrained_model, tree_equal
 
 pytestmark = pytest.mark.gpu
 
@@ -172,20 +172,6 @@ def _scans():
     return images, labels
 
 
-def _save_untrained_model(root):
-    from oct_image_segmentation_models_amd.models.engine_model import Model
-    config = dict(input_channels=1, num_classes=CC, image_height=H_, image_width=W_, start_neurons=SN, pool_layers=P_)
-    cfg = on.UNetConfig(num_classes=CC, start_neurons=SN, pool_layers=P_)
-    params, state = on.init_params(cfg, seed=3, dtype=np.float32, randomize_bn=True)
-    m = Model(name="unet", config=config)
-    m.set_weights(on.keras_weight_list(params, state))
-    (root / "model").mkdir()
-    path = m.save(root / "model" / "model.npz")
-    with open(root / "model" / "model_config.json", "w") as fh:
-        json.dump(config, fh)
-    return path
-
-
 def test_batch_confusion_from_both_sources(tmp_path):
     dd = _dd()
     from oct_image_segmentation_models_amd.engine import UNetEngine
@@ -209,37 +195,13 @@ def test_batch_confusion_from_both_sources(tmp_path):
     with pytest.raises(ValueError, match="image 5"):
         list(pred.run(images, bad))
     torch.cuda.synchronize()
-    model = load_model(_save_untrained_model(tmp_path))
+    model = load_model(save_untrained_model(tmp_path, H_, W_, CC, SN, P_))
     got = list(host_batches(model, images.astype(np.float32), BATCH, gt_u8=gt,
                             confusion=dd.ConfusionCounts(BATCH, H_, W_, CC, "cuda:0")))
     assert [(b.lo, b.hi) for b in got] == [(0, 4), (4, 6)]
     for b in got:
         want = dd.confusion_counts_reference(b.labels, gt[b.lo:b.hi], CC)
         assert b.confusion.dtype == np.uint32 and np.array_equal(b.confusion, want[:, :-1].reshape(-1, CC, CC))
-
-
-def _tree_equal(a: Path, b: Path, h5_names):
-    """Every file under ``a`` has its twin under ``b``: hdf5 datasets identical (attributes carry the times), CSV and text
-    files byte for byte."""
-    from oct_image_segmentation_models_amd.common import h5io
-    fa, fb = (sorted(p.relative_to(r) for p in r.rglob("*") if p.is_file()) for r in (a, b))
-    assert fa == fb and fa
-    seen = set()
-    for rel in fa:
-        if ".hdf5" in rel.suffixes:                                            # (foo.hdf5.npz without an HDF5 backend)
-            x, y = h5io.load(a / rel), h5io.load(b / rel)
-            keys = sorted(k for k in x if not k.startswith("attr:"))
-            assert keys == sorted(k for k in y if not k.startswith("attr:")), rel
-            for k in keys:
-                u, v = np.asarray(x[k]), np.asarray(y[k])
-                assert u.dtype == v.dtype and u.shape == v.shape, (rel, k)
-                assert np.array_equal(u, v, equal_nan=u.dtype.kind == "f"), (rel, k)
-            for k in set(x) - set(keys) - {"attr:graph_time", "attr:predict_time", "attr:convert_time", "attr:timestamp"}:
-                assert np.array_equal(np.asarray(x[k]), np.asarray(y[k])), (rel, k)
-            seen.add(rel.name.replace(".npz", ""))
-        else:
-            assert (a / rel).read_bytes() == (b / rel).read_bytes(), rel
-    assert set(h5_names) <= seen
 
 
 @pytest.mark.parametrize("mode", ["pool", "device_host_ties", "device_device_ties"])
@@ -253,7 +215,7 @@ def test_workflows_with_the_switches_equal_the_host_path(tmp_path, mode):
     images, labels = _scans()
     data = tmp_path / "test.hdf5"
     h5io.save(data, {"test_images": images, "test_labels": labels})
-    _save_untrained_model(tmp_path)
+    save_untrained_model(tmp_path, H_, W_, CC, SN, P_)
     search = {"pool": {}, "device_host_ties": dict(gs_device=True, gs_device_ties="host"),
               "device_device_ties": dict(gs_device=True, gs_device_ties="device")}[mode]
     calls = {"area": 0, "counts": 0}
@@ -294,9 +256,9 @@ def test_workflows_with_the_switches_equal_the_host_path(tmp_path, mode):
         assert calls == {"area": 4, "counts": 4}
     finally:
         dice_device.AreaLabels.__call__, dice_device.ConfusionCounts.__call__ = real_area, real_counts
-    _tree_equal(tmp_path / "eval_host", tmp_path / "eval_dev",
-                ["evaluation_results.hdf5", "gs_evaluation_results.hdf5", "overall_evaluation_results.hdf5"])
-    _tree_equal(tmp_path / "pred_host", tmp_path / "pred_dev", ["prediction_info.hdf5", "graph_search_prediction_info.hdf5"])
+    tree_equal(tmp_path / "eval_host", tmp_path / "eval_dev",
+               ["evaluation_results.hdf5", "gs_evaluation_results.hdf5", "overall_evaluation_results.hdf5"])
+    tree_equal(tmp_path / "pred_host", tmp_path / "pred_dev", ["prediction_info.hdf5", "graph_search_prediction_info.hdf5"])
     assert len(host) == len(dev) == len(p_host) == len(p_dev) == N_IMG
     for h, d in zip(host, dev):
         for field in ("predicted_labels", "categorical_pred", "boundary_maps", "gs_pred_segs", "errors", "mean_abs_err",

@@ -2,7 +2,6 @@
 against its numpy restatement ``delineate_dp`` (rows, tie flags and fp64 costs all exact), against the native host
 search on untied maps, through ``BatchedPredictor(minpath=...)`` and through ``evaluate_model`` / ``predict``."""
 import ctypes as C
-import json
 from pathlib import Path
 
 import numpy as np
@@ -10,6 +9,7 @@ import pytest
 import torch
 
 from oracle import unet_numpy as on
+from tests.helpers import datasets_equal, save_untrained_model
 
 pytestmark = pytest.mark.gpu
 
@@ -199,29 +199,6 @@ def _path_cost(map_hw, rows):
     return d + (2.0 - (prev + 1.0))
 
 
-def _save_untrained_model(root, H, W, C_):
-    from oct_image_segmentation_models_amd.models.engine_model import Model
-    config = dict(input_channels=1, num_classes=C_, image_height=H, image_width=W, start_neurons=8, pool_layers=2)
-    cfg = on.UNetConfig(num_classes=C_, start_neurons=8, pool_layers=2)
-    params, state = on.init_params(cfg, seed=3, dtype=np.float32, randomize_bn=True)
-    m = Model(name="unet", config=config)
-    m.set_weights(on.keras_weight_list(params, state))
-    (root / "model").mkdir()
-    path = m.save(root / "model" / "model.npz")
-    with open(root / "model" / "model_config.json", "w") as fh:
-        json.dump(config, fh)
-    return path
-
-
-def _datasets_equal(a: dict, b: dict):
-    keys = sorted(k for k in a if not k.startswith("attr:"))
-    assert keys == sorted(k for k in b if not k.startswith("attr:"))
-    for k in keys:
-        x, y = np.asarray(a[k]), np.asarray(b[k])
-        assert x.dtype == y.dtype and x.shape == y.shape, k
-        assert np.array_equal(x, y, equal_nan=x.dtype.kind == "f"), k
-
-
 @pytest.mark.parametrize("dtype", ["u8", "f32"])
 def test_evaluate_and_predict_with_gs_device(tmp_path, dtype):
     """The small golden dataset (noise images: an untrained net's maps, tied and untied) through evaluate_model and
@@ -242,7 +219,7 @@ def test_evaluate_and_predict_with_gs_device(tmp_path, dtype):
         data = tmp_path / "f32.hdf5"
         images = images.astype(np.float32)
         h5io.save(data, {"test_images": images, "test_labels": labels})
-    _save_untrained_model(tmp_path, H, W, Cc)
+    save_untrained_model(tmp_path, H, W, Cc, 8, 2)
     metrics = ["dice_coef_classes", "dice_coef_macro", "dice_coef_micro"]
 
     def evaluate(name, **kw):
@@ -272,8 +249,8 @@ def test_evaluate_and_predict_with_gs_device(tmp_path, dtype):
     for i in range(n):
         assert np.array_equal(host[i].gs_pred_segs, dev_host[i].gs_pred_segs)
         assert np.array_equal(host[i].errors, dev_host[i].errors, equal_nan=True)
-        _datasets_equal(h5io.load(host[i].image_output_dir / "gs_evaluation_results.hdf5"),
-                        h5io.load(dev_host[i].image_output_dir / "gs_evaluation_results.hdf5"))
+        datasets_equal(h5io.load(host[i].image_output_dir / "gs_evaluation_results.hdf5"),
+                       h5io.load(dev_host[i].image_output_dir / "gs_evaluation_results.hdf5"))
         maps = host[i].boundary_maps
         assert np.array_equal(maps, dev_dev[i].boundary_maps)
         _, _, tied = device_search.delineate_dp(maps[None], 1)
@@ -283,8 +260,8 @@ def test_evaluate_and_predict_with_gs_device(tmp_path, dtype):
                 assert np.array_equal(dev_dev[i].gs_pred_segs[m], host[i].gs_pred_segs[m]), (i, m)
             n_tied += int(tied[0, m])
     assert sum(started) == n_tied                                    # the tied maps, and only those, went to the host
-    _datasets_equal(h5io.load(tmp_path / "eval_host" / "overall_evaluation_results.hdf5"),
-                    h5io.load(tmp_path / "eval_dev_host" / "overall_evaluation_results.hdf5"))
+    datasets_equal(h5io.load(tmp_path / "eval_host" / "overall_evaluation_results.hdf5"),
+                   h5io.load(tmp_path / "eval_dev_host" / "overall_evaluation_results.hdf5"))
 
     def run_predict(name, **kw):
         ds = Dataset(images, [Path(f"volume_{i}.tiff") for i in range(n)], [tmp_path / name / f"image_{i}" for i in range(n)])
@@ -300,6 +277,6 @@ def test_evaluate_and_predict_with_gs_device(tmp_path, dtype):
     for i in range(n):
         assert np.array_equal(p_host[i].gs_pred_segs, host[i].gs_pred_segs)
         assert np.array_equal(p_dev[i].gs_pred_segs, p_host[i].gs_pred_segs)
-        _datasets_equal(h5io.load(p_host[i].image_output_dir / "graph_search_prediction_info.hdf5"),
-                        h5io.load(p_dev[i].image_output_dir / "graph_search_prediction_info.hdf5"))
+        datasets_equal(h5io.load(p_host[i].image_output_dir / "graph_search_prediction_info.hdf5"),
+                       h5io.load(p_dev[i].image_output_dir / "graph_search_prediction_info.hdf5"))
         assert np.array_equal(p_dd[i].gs_pred_segs, dev_dev[i].gs_pred_segs)

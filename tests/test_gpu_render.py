@@ -3,7 +3,6 @@ everywhere -- on the smallest shapes at which the kernel can go wrong (tile edge
 int64 bound), in a stream capture and on bad arguments; ``PngRenderer`` in chunks; ``evaluate_model`` / ``predict`` with
 ``png_plots=True`` in the three search / metric modes: the files they write, their pixels, and everything else unchanged."""
 import ctypes as C
-import json
 from pathlib import Path
 
 import numpy as np
@@ -12,6 +11,7 @@ import torch
 
 from oracle import unet_numpy as on
 from tests import render_cases as rc
+from tests.helpers import save_untrained_model
 
 pytestmark = pytest.mark.gpu
 
@@ -233,19 +233,6 @@ PRED_PNGS = {"segmentation_map.png", "raw_image.png", "gs_predicted_segmentation
 TIMES = {"attr:graph_time", "attr:predict_time", "attr:convert_time", "attr:timestamp"}
 
 
-def _save_untrained_model(root, H, W):
-    from oct_image_segmentation_models_amd.models.engine_model import Model
-    config = dict(input_channels=1, num_classes=CC, image_height=H, image_width=W, start_neurons=8, pool_layers=2)
-    cfg = on.UNetConfig(num_classes=CC, start_neurons=8, pool_layers=2)
-    params, state = on.init_params(cfg, seed=3, dtype=np.float32, randomize_bn=True)
-    m = Model(name="unet", config=config)
-    m.set_weights(on.keras_weight_list(params, state))
-    (root / "model").mkdir()
-    m.save(root / "model" / "model.npz")
-    with open(root / "model" / "model_config.json", "w") as fh:
-        json.dump(config, fh)
-
-
 class _Workflows:
     def __init__(self, tmp_path):
         from oct_image_segmentation_models_amd.common import dataset_loader as dl
@@ -253,7 +240,7 @@ class _Workflows:
         self.data = ROOT / "tests" / "golden" / "dataset_small.hdf5"
         self.images, self.labels, _ = dl.load_testing_data(dl.open_dataset(self.data))
         self.n, self.H, self.W = self.images.shape[:3]
-        _save_untrained_model(tmp_path, self.H, self.W)
+        save_untrained_model(tmp_path, self.H, self.W, CC, 8, 2)
         self.cols = range(3, self.W - 5)
 
     def evaluate(self, name, save=None, graph_search=True, **kw):

@@ -2,7 +2,6 @@
 exact equality everywhere -- on odd shapes, misaligned buffers, a strided grid and in a stream capture; the ``soft_maps``
 switch of both batch sources; ``evaluate_model`` / ``predict`` with ``binarize=False`` against a host composition
 (probabilities -> perform_argmax(bin=False) -> convert_predictions_to_maps_semantic -> the host search), file by file."""
-import json
 from pathlib import Path
 
 import numpy as np
@@ -10,6 +9,7 @@ import pytest
 import torch
 
 from oracle import unet_numpy as on
+from tests.helpers import save_untrained_model, tree_equal
 from tests.soft_maps_cases import BG, FAMILIES, class_map, family
 
 pytestmark = pytest.mark.gpu
@@ -169,20 +169,6 @@ def _engine(max_batch):
                       pool_layers=P_, max_batch=max_batch, training=False, seed=2, init_seed=4)
 
 
-def _save_untrained_model(root):
-    from oct_image_segmentation_models_amd.models.engine_model import Model
-    config = dict(input_channels=1, num_classes=CC, image_height=H_, image_width=W_, start_neurons=SN, pool_layers=P_)
-    cfg = on.UNetConfig(num_classes=CC, start_neurons=SN, pool_layers=P_)
-    params, state = on.init_params(cfg, seed=3, dtype=np.float32, randomize_bn=True)
-    m = Model(name="unet", config=config)
-    m.set_weights(on.keras_weight_list(params, state))
-    (root / "model").mkdir()
-    path = m.save(root / "model" / "model.npz")
-    with open(root / "model" / "model_config.json", "w") as fh:
-        json.dump(config, fh)
-    return path
-
-
 def test_batched_predictor_soft_maps_with_a_ragged_last_batch():
     from oct_image_segmentation_models_amd.evaluation.pipeline import BatchedPredictor
     images, _ = _scans()
@@ -211,7 +197,7 @@ def test_host_batches_soft_maps_with_float_images(tmp_path):
     from oct_image_segmentation_models_amd.evaluation.pipeline import host_batches
     from oct_image_segmentation_models_amd.models.engine_model import load_model
     images, _ = _scans()
-    model = load_model(_save_untrained_model(tmp_path))
+    model = load_model(save_untrained_model(tmp_path, H_, W_, CC, SN, P_))
     fimg = images.astype(np.float32)
     soft = list(host_batches(model, fimg, BATCH, soft_maps=True))
     hard = list(host_batches(model, fimg, BATCH))
@@ -224,30 +210,6 @@ def test_host_batches_soft_maps_with_float_images(tmp_path):
         assert np.array_equal(b.labels, h.labels) and not np.array_equal(b.maps, h.maps)
     with pytest.raises(ValueError, match="soft_maps"):
         model.predict_labels(images, batch_size=BATCH, want_maps=False, soft_maps=True)
-
-
-def _tree_equal(a: Path, b: Path, h5_names):
-    """Every file under ``a`` has its twin under ``b``: hdf5 datasets identical (attributes carry the times; ``b`` may
-    carry attributes ``a`` lacks), CSV and text files byte for byte."""
-    from oct_image_segmentation_models_amd.common import h5io
-    fa, fb = (sorted(p.relative_to(r) for p in r.rglob("*") if p.is_file()) for r in (a, b))
-    assert fa == fb and fa
-    seen = set()
-    for rel in fa:
-        if ".hdf5" in rel.suffixes:                                            # (foo.hdf5.npz without an HDF5 backend)
-            x, y = h5io.load(a / rel), h5io.load(b / rel)
-            keys = sorted(k for k in x if not k.startswith("attr:"))
-            assert keys == sorted(k for k in y if not k.startswith("attr:")), rel
-            for k in keys:
-                u, v = np.asarray(x[k]), np.asarray(y[k])
-                assert u.dtype == v.dtype and u.shape == v.shape, (rel, k)
-                assert np.array_equal(u, v, equal_nan=u.dtype.kind == "f"), (rel, k)
-            for k in set(x) - set(keys) - {"attr:graph_time", "attr:predict_time", "attr:convert_time", "attr:timestamp"}:
-                assert np.array_equal(np.asarray(x[k]), np.asarray(y[k])), (rel, k)
-            seen.add(rel.name.replace(".npz", ""))
-        else:
-            assert (a / rel).read_bytes() == (b / rel).read_bytes(), rel
-    assert set(h5_names) <= seen
 
 
 @pytest.mark.parametrize("mode", ["host", "device_host_ties", "metrics_device"])
@@ -267,7 +229,7 @@ def test_workflows_with_binarize_false_equal_a_host_composition(tmp_path, mode):
     images, labels = _scans()
     data = tmp_path / "test.hdf5"
     h5io.save(data, {"test_images": images, "test_labels": labels})
-    _save_untrained_model(tmp_path)
+    save_untrained_model(tmp_path, H_, W_, CC, SN, P_)
     switches = {"host": ({}, {}), "device_host_ties": (dict(gs_device=True, gs_device_ties="host"),) * 2,
                 "metrics_device": (dict(metrics_device=True), dict(gs_labels_device=True))}[mode]
 
@@ -313,9 +275,9 @@ def test_workflows_with_binarize_false_equal_a_host_composition(tmp_path, mode):
 
     got = evaluate("eval_got", binarize=False, **switches[0])
     p_got = run_predict("pred_got", binarize=False, **switches[1])
-    _tree_equal(tmp_path / "eval_want", tmp_path / "eval_got",
-                ["evaluation_results.hdf5", "gs_evaluation_results.hdf5", "overall_evaluation_results.hdf5"])
-    _tree_equal(tmp_path / "pred_want", tmp_path / "pred_got", ["prediction_info.hdf5", "graph_search_prediction_info.hdf5"])
+    tree_equal(tmp_path / "eval_want", tmp_path / "eval_got",
+               ["evaluation_results.hdf5", "gs_evaluation_results.hdf5", "overall_evaluation_results.hdf5"])
+    tree_equal(tmp_path / "pred_want", tmp_path / "pred_got", ["prediction_info.hdf5", "graph_search_prediction_info.hdf5"])
     assert not h5io.load(tmp_path / "eval_got" / "eval_params.hdf5")["attr:binarize"]
     assert not h5io.load(tmp_path / "pred_got" / "prediction_params.hdf5")["attr:binarize"]
     assert "attr:binarize" not in h5io.load(tmp_path / "eval_want" / "eval_params.hdf5")
@@ -342,8 +304,8 @@ def test_workflows_with_binarize_false_equal_a_host_composition(tmp_path, mode):
         hard = evaluate("eval_hard", binarize=True)
         p_hard = run_predict("pred_hard", binarize=True)
         plain = evaluate("eval_plain")
-        _tree_equal(tmp_path / "eval_plain", tmp_path / "eval_hard",
-                    ["evaluation_results.hdf5", "gs_evaluation_results.hdf5", "overall_evaluation_results.hdf5"])
+        tree_equal(tmp_path / "eval_plain", tmp_path / "eval_hard",
+                   ["evaluation_results.hdf5", "gs_evaluation_results.hdf5", "overall_evaluation_results.hdf5"])
         assert "attr:binarize" not in h5io.load(tmp_path / "eval_hard" / "eval_params.hdf5")
         assert "attr:binarize" not in h5io.load(tmp_path / "pred_hard" / "prediction_params.hdf5")
         for hd, ph, g in zip(hard, p_hard, got):

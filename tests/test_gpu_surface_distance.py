@@ -1,7 +1,6 @@
 """GPU tests of the device surface-distance metrics (oct_surface_distances, evaluation/surface.py) against the host
 restatement in common/custom_metrics.py, and of evaluate_model with all five metrics on both of its paths."""
 import ctypes as C
-import json
 from pathlib import Path
 
 import numpy as np
@@ -9,6 +8,7 @@ import pytest
 import torch
 
 from oracle import unet_numpy as on
+from tests.helpers import save_untrained_model
 
 pytestmark = pytest.mark.gpu
 
@@ -156,20 +156,6 @@ def test_bad_arguments_rejected_without_launch():
     assert (r[:, 1, 4:] == 0).all() and np.isnan(r[:, 1, :2]).all() and (r[:, 1, 2:4] == np.inf).all()  # class 2: absent
 
 
-def _save_untrained_model(root, H, W, C_):
-    from oct_image_segmentation_models_amd.models.engine_model import Model
-    config = dict(input_channels=1, num_classes=C_, image_height=H, image_width=W, start_neurons=8, pool_layers=2)
-    cfg = on.UNetConfig(num_classes=C_, start_neurons=8, pool_layers=2)
-    params, state = on.init_params(cfg, seed=3, dtype=np.float32, randomize_bn=True)
-    m = Model(name="unet", config=config)
-    m.set_weights(on.keras_weight_list(params, state))
-    (root / "model").mkdir()
-    path = m.save(root / "model" / "model.npz")
-    with open(root / "model" / "model_config.json", "w") as fh:
-        json.dump(config, fh)
-    return path
-
-
 def _evaluate(root, data, name, metrics):
     from oct_image_segmentation_models_amd.evaluation import eval_model
     from oct_image_segmentation_models_amd.evaluation.evaluation_parameters import EvaluationParameters, EvaluationSaveParams
@@ -182,7 +168,7 @@ def _evaluate(root, data, name, metrics):
 def test_evaluate_model_all_five_metrics(tmp_path):
     from oct_image_segmentation_models_amd.common import custom_metrics as cm, h5io
     H, W, C_, n = 64, 128, 3, 5
-    _save_untrained_model(tmp_path, H, W, C_)
+    save_untrained_model(tmp_path, H, W, C_, 8, 2)
     te_i, te_l = on.synth_scans(n, H, W, C_, seed=3)
     te_l[1][te_l[1] == 2] = 1                                  # a class absent from one ground truth
     h5io.save(tmp_path / "u8.hdf5", {"test_images": te_i, "test_labels": te_l})

@@ -175,6 +175,57 @@ def test_batched_pipeline_equals_per_image_path_at_batch_128():
             assert np.array_equal(res[i][0], p_inline) and np.array_equal(res[i][1], e_inline)
 
 
+def test_every_stage_at_once_through_one_predictor():
+    """``surface=``, ``confusion=`` and ``minpath=`` together: 14 scans at batch 4 are four batches, so both buffer slots
+    are recycled and the last batch is ragged; two runs over one predictor.  Every field of every batch equals, bit for
+    bit, the same wrapper called directly on that batch's labels / maps and ground truth (the wrappers' own tests pin them
+    to their numpy restatements; this pins the stage loop: the shared ground-truth upload, the slots, the order).  Without
+    ground truth the stages that read it yield None and the rest is unchanged."""
+    from oct_image_segmentation_models_amd.engine import UNetEngine
+    from oct_image_segmentation_models_amd.evaluation.dice_device import ConfusionCounts
+    from oct_image_segmentation_models_amd.evaluation.pipeline import BatchedPredictor
+    from oct_image_segmentation_models_amd.evaluation.surface import SurfaceDistances
+    from oct_image_segmentation_models_amd.min_path_processing.device_search import DeviceMinPath
+    Hs, Ws, Cs, B, N = 32, 64, 4, 4, 14
+    eng = UNetEngine(device="cuda:0", input_channels=1, num_classes=Cs, image_height=Hs, image_width=Ws, start_neurons=4,
+                     pool_layers=2, max_batch=B, training=False, seed=2, init_seed=4)
+    images, labels = on.synth_scans(N, Hs, Ws, Cs, seed=31)
+    gt = np.ascontiguousarray(labels[..., 0].astype(np.uint8))
+
+    def wrappers():
+        return (SurfaceDistances(B, Hs, Ws, Cs, "cuda:0"), ConfusionCounts(B, Hs, Ws, Cs, "cuda:0"),
+                DeviceMinPath(B, Cs - 1, Hs, Ws, 1, "cuda:0"))
+
+    def up(a):
+        return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+    def same_bits(a, b):                                      # array_equal on the bits: a NaN row equals only itself
+        return a.dtype == b.dtype == np.float64 and a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
+
+    surf, conf, mp = wrappers()
+    d_surf, d_conf, d_mp = wrappers()
+    pred = BatchedPredictor(eng, B, want_maps=True, surface=surf, confusion=conf, minpath=mp)
+    runs = [list(pred.run(images, gt)) for _ in range(2)]
+    for got in runs:
+        assert [(b.lo, b.hi) for b in got] == [(0, 4), (4, 8), (8, 12), (12, 14)]
+        for b in got:
+            n, lab, g = b.hi - b.lo, up(b.labels), up(gt[b.lo:b.hi])
+            assert b.labels.shape == (n, Hs, Ws) and b.maps.shape == (n, Cs - 1, Hs, Ws)
+            assert b.surface.shape == (n, Cs - 1, 6) and same_bits(b.surface, d_surf(lab, g).cpu().numpy()), b.lo
+            assert b.confusion.dtype == np.uint32 and np.array_equal(b.confusion, d_conf.to_host(d_conf(lab, g))), b.lo
+            rows, cost, tied = d_mp.to_host(*d_mp(up(b.maps)))
+            assert b.minpath[0].dtype == np.uint16 and b.minpath[2].dtype == bool
+            assert np.array_equal(b.minpath[0], rows) and same_bits(b.minpath[1], cost) and np.array_equal(b.minpath[2], tied), b.lo
+    for a, b in zip(*runs):
+        assert np.array_equal(a.labels, b.labels) and np.array_equal(a.maps, b.maps)
+    bare = list(pred.run(images))
+    assert len(bare) == 4
+    for a, b in zip(runs[0], bare):
+        assert b.surface is None and b.confusion is None
+        assert np.array_equal(a.labels, b.labels) and np.array_equal(a.maps, b.maps)
+        assert all(np.array_equal(x, y) for x, y in zip(a.minpath, b.minpath)) and len(b.minpath) == 3
+
+
 def test_config0_at_its_stated_size(tmp_path):
     """BASELINE configs[0] as written: 4 train (+ 4 validation) 256x512x1 scans in a real HDF5 file, 3 boundaries
     (= 4 classes), 1 epoch through ``train_model`` (reference training/training.py:135-408) -- the plumbing case,
