@@ -51,7 +51,11 @@ typedef struct oct_unet_cfg {
     int n_cls;            /* num_classes, 2..8                    (training.py:176)     */
     int H, W;             /* image_height, image_width; multiples of 2^pool_layers     */
     int max_batch;        /* largest per-rank batch any call will pass                  */
-    int start_neurons;    /* default 8; multiple of 4 in 4..32    (unet.py:69)          */
+    int start_neurons;    /* default 8; multiple of 4 in 4..64    (unet.py:69).  Widths  */
+                          /*     above 32 run the channel-streaming head kernels ("head_wide"). */
+                          /*     The 32-bit element index inside a layer bounds the size:      */
+                          /*     max_batch*H*W*2*start_neurons < 2^31 -- at 64 channels         */
+                          /*     max_batch*H*W*128 < 2^31, i.e. max_batch <= 127 at 256x512     */
     int pool_layers;      /* default 4                            (unet.py:70)          */
     int conv_layers;      /* default 2                            (unet.py:71)          */
     int enc_k;            /* 3  (enc_kernel (3,3))                (unet.py:72)          */
@@ -432,7 +436,15 @@ int oct_render_rgba(int base_mode, const unsigned char* base_dev, int ic, const 
  *   "fuse_bn_finalize" (0): 1 = the BN records of the thin layers (<= 32 channels) are written by the LAST block of the
  *   launch that produces the partial rows (arrival counter; write-through rows; csrc/kernels_fin.hpp) instead of by a
  *   bn_*_finalize launch.  Same results to fp32 rounding; measured 0.5-1 % slower per step than the launches it removes,
- *   hence off by default.
+ *   hence off by default.  (The channel-streaming head kernels never finalize in the launch: under "head_wide", and above
+ *   32 channels, the last block's statistics are finalized by the bn_bwd_finalize launch whatever this option says.)
+ *   "head_wide" (0; may be set on a live handle between steps): the head (BN + ReLU on load, 1x1 conv, softmax, loss
+ *   sums; backward: loss gradient, softmax Jacobian, 1x1 backward, mask, statistics) has two forms.  The register kernels
+ *   head_fwd_k / head_bwd_k<C, CIN> keep a pixel's CIN channels and CIN*C + C + 2*CIN partial sums in registers and exist
+ *   for start_neurons <= 32.  The channel-streaming kernels head_fwd_wide_k / head_bwd_wide_k<C> (csrc/kernels_head_wide.hpp)
+ *   take CIN at run time, stream z in 16-byte steps and form the sums over pixels on the fp32 matrix pipe; start_neurons
+ *   36..64 always run them.  1 = every start_neurons runs them (same buffers, same arithmetic per pixel, another -- fixed --
+ *   summation order), so that they can be tested and timed against the register kernels on equal inputs.
  *   "dwbt_f32_all" (0): 1 = fp32 mode takes conv_dwbt_k for every thin backward-weights shape (default: where it wins).
  *   "dw_side_stream" (1): backward-weights kernels and the per-step weight preparation run on a low-priority stream
  *   owned by the handle, beside the backward-data chain.  0 = everything on the caller's stream.

@@ -14,6 +14,8 @@
 #include "kernels_bwd.hpp"
 #include "kernels_igemm.hpp"
 
+namespace oct { struct HeadFwdArgs; }     // kernels_fwd.hpp
+
 namespace octh {
 
 // ---- tuning options.  oct_set_option edits the process-wide DEFAULTS (g_opt); a handle snapshots them when it is
@@ -56,6 +58,8 @@ struct Options {
                                     // pair with backward-data launches of the next level, which they slow down more
     int event_sysfence = 0;         // 1: the handle's fork/join events carry a system-scope fence (set before oct_unet_create)
     int persist_min_tiles = 2048;   // pixel tiles from which thin single-chunk convs use the persistent pipelined kernel
+    int head_wide = 0;              // 1: every start_neurons takes the channel-streaming head kernels (kernels_head_wide.hpp), which
+                                    // widths above 32 always take: holds them against the register kernels on equal inputs
     int max_blocks = 0;             // FOR TESTS ("persistent_max_blocks"): > 0 caps the grid of every persistent launch, so that
                                     // small images make blocks walk several tiles (cap_grid below); 0 = the launches' own grids
 };
@@ -151,5 +155,10 @@ enum DwKind {
 struct DwPlan { DwKind kind; int cic, coc, th, chunks, npb, tiles; };
 int launch_dw_bf16pipe(const oct::ConvBwdWArgs& a, const DwPlan& p, int kh, bool up, const LaunchCtx& c);
 int launch_dw_f32pipe(const oct::ConvBwdWArgs& a, const DwPlan& p, int kh, bool up, const LaunchCtx& c);
+
+// Channel-streaming head (kernels_head_wide.hpp, instantiated in tu_head_wide.hip): C classes, cin a runtime multiple of 4 in
+// 4..64.  Same argument blocks and output buffers as the register kernels of oct_unet.hip; a.fin must be empty.
+int launch_head_fwd_wide(const oct::HeadFwdArgs& a, int C, int cin, int B, hipStream_t s);
+int launch_head_bwd_wide(const oct::HeadBwdArgs& a, int C, int cin, int B, hipStream_t s);
 
 }  // namespace octh

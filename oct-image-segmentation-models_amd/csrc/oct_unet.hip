@@ -79,8 +79,8 @@ int check_cfg(const oct_unet_cfg* c) {
     if (c->n_cls < 2 || c->n_cls > 8) return fail(-1, "n_cls must be in 2..8");
     if (c->pool_layers < 1 || c->pool_layers > 6) return fail(-1, "pool_layers must be in 1..6");
     if (c->conv_layers < 1) return fail(-1, "conv_layers must be >= 1");
-    if (c->start_neurons < 4 || c->start_neurons > 32 || c->start_neurons % 4)
-        return fail(-1, "start_neurons must be a multiple of 4 in 4..32");
+    if (c->start_neurons < 4 || c->start_neurons > 64 || c->start_neurons % 4)
+        return fail(-1, "start_neurons must be a multiple of 4 in 4..64");
     if (c->enc_k != 3 || c->dec_k != 2) return fail(-1, "only enc_kernel (3,3) / dec_kernel (2,2) are implemented");
     const int m = 1 << c->pool_layers;
     if (c->H < m || c->W < m || c->H % m || c->W % m) return fail(-1, "H and W must be multiples of 2^pool_layers");
@@ -449,7 +449,10 @@ int conv_forward(oct_unet* h, int li, const void* x_in, int x_is_u8, int B, int 
     return 0;
 }
 
-// the head kernels are instantiated for every start_neurons (= the head's input channels): run f(constant cin)
+// the register head kernels are instantiated for every start_neurons (= the head's input channels) up to 32: run
+// f(constant cin).  Wider heads, and every head under option "head_wide", take the channel-streaming kernels
+// (kernels_head_wide.hpp), whose register use does not grow with cin
+inline bool head_is_wide(const Options& o, int cin) { return cin > 32 || o.head_wide; }
 template <typename F>
 int head_cin_dispatch(int cin, F f) {
     switch (cin) {
@@ -461,7 +464,8 @@ int head_cin_dispatch(int cin, F f) {
 }
 
 template <int C>
-int launch_head_fwd(const HeadFwdArgs& a, int cin, int B, hipStream_t s) {
+int launch_head_fwd(const HeadFwdArgs& a, int cin, int B, hipStream_t s, bool wide) {
+    if (wide) return launch_head_fwd_wide(a, C, cin, B, s);
     dim3 grid(a.nblk, B), block(kBlock);
     const double px = (double)B * a.HW;
     char nm[64]; snprintf(nm, sizeof nm, "head_fwd_k<%d,%d,%s>", C, cin, AT_NAME(a.act_bf16));
@@ -472,7 +476,8 @@ int launch_head_fwd(const HeadFwdArgs& a, int cin, int B, hipStream_t s) {
 }
 
 template <int C>
-int launch_head_bwd(const HeadBwdArgs& a, int cin, int B, hipStream_t s) {
+int launch_head_bwd(const HeadBwdArgs& a, int cin, int B, hipStream_t s, bool wide) {
+    if (wide) return launch_head_bwd_wide(a, C, cin, B, s);
     dim3 grid(a.nblk, B), block(kBlock);
     const double px = (double)B * a.HW;
     char nm[64]; snprintf(nm, sizeof nm, "head_bwd_k<%d,%d,%s>", C, cin, AT_NAME(a.act_bf16));
@@ -568,7 +573,7 @@ int forward_impl(oct_unet* h, const void* x, int x_is_u8, int B, int training, c
     a.dice_part = h->dice_part; a.HW = hd.H * hd.W; a.nblk = head_nblk(a.HW, B); a.act_bf16 = h->cfg.dtype;
     a.focal_on = h->focal_w > 0.f; a.focal_gamma = h->focal_gamma; a.focal_cw = h->focal_cw; a.focal_clip_mod = h->opt.focal_clip_mod;
     a.bce_on = h->bce_on; a.bce_inner = h->opt.bce_inner_eps ? kFocalEps : 0.f;
-    const int rc = DISPATCH_C(launch_head_fwd, h->cfg.n_cls, a, hd.cin, B, s);
+    const int rc = DISPATCH_C(launch_head_fwd, h->cfg.n_cls, a, hd.cin, B, s, head_is_wide(h->opt, hd.cin));
     if (rc) return rc;
     h->last_B = B; h->last_training = training; h->have_dice = a.labels != nullptr;
     return 0;
@@ -788,9 +793,10 @@ int head_backward(oct_unet* h, const unsigned char* labels, int macro, float los
     hb.HW = hd.H * hd.W; hb.nblk = head_nblk(hb.HW, B); hb.B = B; hb.macro = macro; hb.loss_scale = loss_scale; hb.act_bf16 = h->cfg.dtype;
     hb.focal_w = h->focal_w; hb.focal_gamma = h->focal_gamma; hb.focal_cw = h->focal_cw; hb.focal_clip_mod = h->opt.focal_clip_mod; hb.inv_count = 1.f / ((float)B * hb.HW);
     hb.bce_on = h->bce_on; hb.bce_inner = h->opt.bce_inner_eps ? kFocalEps : 0.f; hb.bce_scale = loss_scale * hb.inv_count / (float)h->cfg.n_cls;
-    if (fin_ok(h, last)) { hb.fin = fin_desc(h, nl - 2, 1, B); *fin = true; }
+    const bool wide = head_is_wide(h->opt, hd.cin);          // (only the register kernels finalize the statistics in the launch)
+    if (!wide && fin_ok(h, last)) { hb.fin = fin_desc(h, nl - 2, 1, B); *fin = true; }
     *rows = B * hb.nblk;
-    return DISPATCH_C(launch_head_bwd, h->cfg.n_cls, hb, hd.cin, B, s);
+    return DISPATCH_C(launch_head_bwd, h->cfg.n_cls, hb, hd.cin, B, s, wide);
 }
 
 // one backward-data launch of block li.  *rows = statistic partial rows it wrote; *fin = true if it finalized the
@@ -1284,7 +1290,7 @@ const Opt k_opts[] = {
     {"igemm_min_blocks", &Options::igemm_min_blocks, 1, 1 << 30}, {"dwpair8_enable", &Options::dwpair8, 0, 1},
     {"pair8_geometry", &Options::pair_geo, 111, 221}, {"pair8_min_tiles", &Options::pair_min_tiles, 1, 1 << 30},
     {"thin8_min_tiles", &Options::thin_min_tiles, 1, 1 << 30}, {"focal_clip_modulation", &Options::focal_clip_mod, 0, 1},
-    {"bce_inner_eps", &Options::bce_inner_eps, 0, 1},
+    {"bce_inner_eps", &Options::bce_inner_eps, 0, 1}, {"head_wide", &Options::head_wide, 0, 1},
     {"mfma_mode", &Options::mfma_mode, 0, 1}, {"bx_min_blocks", &Options::bx_min_blocks, 1, 1 << 30},
     {"dwbx_blocks", &Options::dwbx_blocks, 8, 1 << 20}, {"bt_blocks_per_cu", &Options::bt_blocks_per_cu, 0, 8},
     {"dwbt_f32_all", &Options::dwbt_f32_all, 0, 1}, {"bt_m2", &Options::bt_m2, 0, 1},
