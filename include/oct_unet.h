@@ -31,6 +31,7 @@
  *   oct_opt_step                       ... of any other opt_con, and the clipnorm / clipvalue / global_clipnorm options
  *   gradient buffer (caller-owned)     MirroredStrategy all-reduce    training/training.py:185-188,243
  *   oct_unet_graph_capture/_launch     (none: replaces per-call Keras dispatch overhead, evaluation.py:108-135)
+ *   oct_unet_forward_mc / oct_mc_update (none: Monte-Carlo dropout prediction; the Dropout(0.5) it keeps on is models/unet.py:130)
  *   oct_augment_batch                  BatchGenerator.get_aug_fly/_nofly common/data_generator.py:140-283,
  *                                      flip_aug / add_noise_aug       common/augmentation.py:43-103
  */
@@ -250,6 +251,56 @@ int oct_boundary_maps(const unsigned char* labels_dev, int B, int H, int W, int 
 int oct_boundary_maps_soft(const float* probs_dev /* (B,H,W,n_cls) f32, the layout of oct_unet_io.probs */,
                            int B, int H, int W, int n_cls, int bg_ilm, int bg_csi,
                            unsigned char* maps_dev /* (B, n_cls-1, H, W) */, oct_stream_t stream);
+
+/* ---- Monte-Carlo dropout on device (Gal & Ghahramani 2016; the reference has no counterpart: its Dropout(0.5) on the
+ * bottleneck, models/unet.py:130, is only active in Model.fit).  T stochastic softmax outputs p^(0..T-1) of one batch are
+ * folded, one call per sample, into running sums in a caller-owned workspace; the call for the last sample turns the sums
+ * into the maps of oct_mc_out.  Restated in numpy, step by step, by common/utils.py::mc_reduce_reference.  All arithmetic is
+ * fp32, one IEEE operation per step, none contracted with another:
+ *   plogp(p) = p > 0 ? p * logf(p) : 0                 (logf: the OCML library function, not the fast intrinsic)
+ *   h_t = -(plogp(p_0) + plogp(p_1) + ... )            (summed in class order) -- the entropy of sample t
+ *   workspace: S_c (B,H,W,n_cls) then E (B,H,W).  t == 0: S_c = p_c, E = h_0 (no memset needed);  t > 0: S_c += p_c, E += h_t
+ *   t == T-1:  m_c = S_c * float(1.0f / T)                                     -> mean_probs
+ *              argmax = the lowest index among equal maxima of m                -> argmax
+ *              entropy = -(plogp(m_0) + plogp(m_1) + ...)  (class order)         -> entropy      (predictive entropy, nats)
+ *              mutual_info = max(entropy - E * float(1.0f / T), 0)              -> mutual_info  (BALD)
+ *   mean_probs and argmax therefore equal the numpy restatement bit for bit; entropy and mutual_info agree with it to
+ *   the accuracy of logf (about 1 ulp per term; 2e-5 absolute against fp64 for n_cls <= 32, T <= 64).
+ * Calls are made with t in order 0..T-1 on one stream.  The call of the last sample does not write the sums back: the
+ * workspace contents are unspecified afterwards.  Inputs are probabilities: finite, in [0,1] (NaN: no fault, unspecified
+ * values).  Stand-alone like oct_boundary_maps_soft: no handle, no allocation, ONE asynchronous launch per call on `stream`
+ * (grid-stride over pixels, no atomics, deterministic), never waits, records into a stream capture.  Pointers need their
+ * natural alignment only; with 16-byte aligned buffers, n_cls <= 8 and B*H*W*n_cls % 4 == 0 the kernel moves float4s.
+ * Errors (negative, oct_last_error(), nothing launched): null probs / workspace, null `out` when t == T-1, non-positive
+ * sizes, n_cls outside 2..32, B*H*W >= 2^31, T outside 1..64, t outside 0..T-1, a workspace smaller than
+ * oct_mc_workspace_bytes, output ranges that overlap the input, the workspace or each other. */
+typedef struct oct_mc_out {
+    float* mean_probs;            /* (B,H,W,n_cls) f32, or NULL */
+    unsigned char* argmax;        /* (B,H,W) u8,        or NULL */
+    float* entropy;               /* (B,H,W) f32,       or NULL */
+    float* mutual_info;           /* (B,H,W) f32,       or NULL */
+} oct_mc_out;
+size_t oct_mc_workspace_bytes(int B, int H, int W, int n_cls);   /* B*H*W*(n_cls+1) floats; 0 = unsupported shape */
+int oct_mc_update(const float* probs_dev /* (B,H,W,n_cls) f32 */, int B, int H, int W, int n_cls, int t, int T,
+                  void* ws_dev, size_t ws_bytes, const oct_mc_out* out /* read when t == T-1 */, oct_stream_t stream);
+
+/* Inference forward with the bottleneck dropout ON, T times, reduced by oct_mc_update: per-pixel uncertainty of a batch.
+ * BN runs from the moving statistics (as training = 0) and the weights are prepared once; the encoder and the bottleneck
+ * sit in front of the dropout and are deterministic, so layers [0, k) run ONCE -- k = the up-convolution behind the
+ * bottleneck -- and for t = 0..T-1 layers [k, head] run with the dropout stream of step step0 + t on the input of layer k:
+ * exactly the keep-mask oct_unet_dropout_mask returns after oct_unet_set_dropout_step(step0 + t), kept values scaled by
+ * 1 / (1 - dropout_rate) as in training.  The head writes sample t to probs_scratch_dev and oct_mc_update(t, T) folds it
+ * into mc_ws_dev; `out` receives the maps of the T samples.  With dropout_rate == 0 the samples are identical.
+ * Works on training and inference handles, f32 and bf16 (cfg.dtype 1).  No statistic rows are written, the moving
+ * statistics and parameters are untouched, nothing is saved for a backward, the handle's dropout step is as before the
+ * call; a pending Dice sum is dropped (a following oct_unet_loss_dice needs a new forward with io.labels).  Allocates
+ * nothing and is asynchronous on `stream`.  NOT for graph capture: the dropout step travels by value in the kernel
+ * arguments, so a replay would repeat the captured steps -- which is also why each call is cheap to vary.
+ * Errors (negative, oct_last_error(), nothing launched): null handle, x, scratch, workspace or out; B outside
+ * 1..max_batch; T outside 1..64; mc_ws_bytes < oct_mc_workspace_bytes(B, H, W, n_cls); overlapping ranges as above. */
+int oct_unet_forward_mc(oct_unet* h, const void* x_dev, int x_is_u8, int B, int T, unsigned long long step0,
+                        float* probs_scratch_dev /* (B,H,W,n_cls) f32 */, void* mc_ws_dev, size_t mc_ws_bytes,
+                        const oct_mc_out* out, oct_stream_t stream);
 
 /* ---- evaluation metrics on device: average surface distance and robust Hausdorff distance of every foreground class
  * (reference evaluation/evaluation.py:207-262 -> common/custom_metrics.py:103-119 -> google-deepmind/surface-distance

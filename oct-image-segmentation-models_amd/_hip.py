@@ -67,6 +67,14 @@ class UNetIO(C.Structure):
     _fields_ = [("probs", C.c_void_p), ("argmax", C.c_void_p), ("labels", C.c_void_p)]
 
 
+class McOut(C.Structure):
+    """``oct_mc_out``: the maps the last ``oct_mc_update`` of a sequence writes (device pointers, ``None`` = not wanted)."""
+    _fields_ = [("mean_probs", C.c_void_p), ("argmax", C.c_void_p), ("entropy", C.c_void_p), ("mutual_info", C.c_void_p)]
+
+
+MC_MAX_SAMPLES = 64
+
+
 # every symbol include/oct_unet.h declares: (name, restype, argtypes)
 _P = C.POINTER
 SYMBOLS = [
@@ -104,6 +112,11 @@ SYMBOLS = [
     ("oct_unet_profile_end", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _P(C.c_int)]),
     ("oct_boundary_maps", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     ("oct_boundary_maps_soft", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    ("oct_mc_workspace_bytes", C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    ("oct_mc_update", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                _P(McOut), C.c_void_p]),
+    ("oct_unet_forward_mc", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_ulonglong, C.c_void_p, C.c_void_p,
+                                      C.c_size_t, _P(McOut), C.c_void_p]),
     ("oct_surface_workspace_bytes", C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     ("oct_surface_distances", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
                                         C.c_double, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),

@@ -121,6 +121,51 @@ def soft_boundary_maps_reference(probs_nhwc, bg_ilm=True, bg_csi=False) -> np.nd
     return out
 
 
+def mc_reduce_reference(probs_stack, dtype=np.float32) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """``oct_mc_update`` (include/oct_unet.h) restated step by step: a stack (T, n, H, W, C) of softmax outputs of T
+    Monte-Carlo dropout samples -> ``(mean_probs (n,H,W,C), argmax (n,H,W) uint8, entropy (n,H,W), mutual_info (n,H,W))``.
+    With ``dtype=np.float32`` every step is one float32 operation in the order of the header's definition, so
+    ``mean_probs`` and ``argmax`` equal the kernel's bit for bit (the entropies differ by the rounding of the logarithm);
+    ``dtype=np.float64`` runs the same steps in double precision on the same float32 inputs, for the entropy checks."""
+    p = np.asarray(probs_stack, dtype=np.float32)
+    if p.ndim != 5 or p.shape[0] < 1:
+        raise ValueError("mc_reduce_reference: need a (T, n, H, W, C) stack with T >= 1")
+    dt = np.dtype(dtype).type
+    T, C = p.shape[0], p.shape[-1]
+    inv_t = dt(dt(1.0) / dt(T))
+
+    def neg_sum_plogp(q):                      # -(plogp(q_0) + plogp(q_1) + ...), summed in class order
+        t = np.zeros_like(q)
+        pos = q > 0
+        t[pos] = q[pos] * np.log(q[pos])       # p > 0 ? p * log(p) : 0
+        acc = t[..., 0].copy()
+        for c in range(1, C):
+            acc = acc + t[..., c]
+        return -acc
+
+    S = E = None
+    for t in range(T):
+        pt = p[t].astype(dt)
+        h = neg_sum_plogp(pt)
+        S, E = (pt.copy(), h) if t == 0 else (S + pt, E + h)
+    m = S * inv_t
+    best, arg = m[..., 0].copy(), np.zeros(m.shape[:-1], np.uint8)
+    for c in range(1, C):                      # the lowest index among equal maxima
+        gt = m[..., c] > best
+        best[gt] = m[..., c][gt]
+        arg[gt] = c
+    entropy = neg_sum_plogp(m)
+    mutual_info = np.maximum(entropy - E * inv_t, dt(0.0))
+    return m, arg, entropy, mutual_info
+
+
+def entropy_to_u8(entropy, num_classes: int) -> np.ndarray:
+    """Predictive entropy (nats) -> uint8 gray levels for ``uncertainty_map.png``: floor(min(entropy / ln C, 1) * 255 + 0.5),
+    so 255 is the entropy of the uniform distribution over the ``num_classes`` classes."""
+    e = np.asarray(entropy, dtype=np.float64) / np.log(float(num_classes))
+    return np.floor(np.minimum(e, 1.0) * 255.0 + 0.5).astype(np.uint8)
+
+
 def create_area_mask(image_shape: tuple, segs) -> np.ndarray:
     """Boundaries -> stacked-region mask (dataset_construction.py:654-708, channels_last).  ``image_shape`` is
     (width, height[, channels]) of the TRANSPOSED image the graph search works on; regions do not include the

@@ -15,6 +15,7 @@
 #include "kernels_igemm.hpp"
 
 namespace oct { struct HeadFwdArgs; }     // kernels_fwd.hpp
+struct oct_mc_out;                        // include/oct_unet.h
 
 namespace octh {
 
@@ -160,5 +161,10 @@ int launch_dw_f32pipe(const oct::ConvBwdWArgs& a, const DwPlan& p, int kh, bool 
 // 4..64.  Same argument blocks and output buffers as the register kernels of oct_unet.hip; a.fin must be empty.
 int launch_head_fwd_wide(const oct::HeadFwdArgs& a, int C, int cin, int B, hipStream_t s);
 int launch_head_bwd_wide(const oct::HeadBwdArgs& a, int C, int cin, int B, hipStream_t s);
+
+// Monte-Carlo dropout reduction (tu_mc.hip): every argument error of oct_mc_update(probs, ..., t, T, ws, ws_bytes, out), with
+// nothing launched -- oct_unet_forward_mc asks about its last sample before its first launch
+int mc_validate(const float* probs, int B, int H, int W, int n_cls, int t, int T, const void* ws, size_t ws_bytes,
+                const oct_mc_out* out);
 
 }  // namespace octh

@@ -391,7 +391,10 @@ double in_bytes(const Layer& l, int B, int x_is_u8, int es = 4) {
     return px * l.cin * es;
 }
 
-int conv_forward(oct_unet* h, int li, const void* x_in, int x_is_u8, int B, int training, hipStream_t s) {
+// `dropout`: the layer's input passes through the dropout stream of the handle's current step, if the layer sits behind the
+// dropout at all -- a training forward, or a Monte-Carlo sample of an inference forward (training == 0: BN from the moving
+// statistics, no statistic rows)
+int conv_forward(oct_unet* h, int li, const void* x_in, int x_is_u8, int B, int training, bool dropout, hipStream_t s) {
     Layer& l = h->plan.L[li];
     const SrcDesc sd = src_of(h, li, x_in, x_is_u8);
     ConvFwdArgs a{};
@@ -401,7 +404,7 @@ int conv_forward(oct_unet* h, int li, const void* x_in, int x_is_u8, int B, int 
     a.H = l.H; a.W = l.W; a.Cin = l.cin; a.Cout = l.cout;
     a.tiles_x = cdiv(l.W, kTileX); a.tiles = tiles_of(l.H, l.W);
     a.drop = make_drop(h); a.act_bf16 = h->cfg.dtype;
-    const bool drop = training && l.drop_in;
+    const bool drop = dropout && l.drop_in;
     const double px = (double)B * l.H * l.W, fl = 2.0 * l.kh * l.kw * l.cin * l.cout * px;
     const int es = h->cfg.dtype ? 2 : 4;
     const double by = in_bytes(l, B, x_is_u8, es) + px * l.cout * es;   // logical input once + output once
@@ -527,12 +530,13 @@ int prep_split_weights(oct_unet* h, bool bwd, hipStream_t s) {
     return 0;
 }
 
-int forward_impl(oct_unet* h, const void* x, int x_is_u8, int B, int training, const oct_unet_io* io, hipStream_t s) {
+// The forward in three parts, so that a Monte-Carlo forward can run the first once and the other two per sample:
+// forward_prepare (this step's weights; the BN records from the moving statistics), forward_stages (the conv blocks
+// [li0, li1) with their pools) and forward_head.  fside: the weight preparation runs on the side stream under the first layer.
+int forward_prepare(oct_unet* h, int training, bool fside, hipStream_t s) {
     Plan& pl = h->plan;
-    const int nl = (int)pl.L.size();
     // this step's weights, split / rounded into bf16 MFMA operand order (one launch per kernel family).  In a training
     // step they run on the side stream under the first layer (which does not use them).
-    const bool fside = training && h->opt.dw_side_stream && h->side && !(t_prof && t_prof->on);
     hipStream_t ps_ = fside ? h->side : s;
     if (fside) { HIP_OK(hipEventRecord(h->fork_ev[0], s)); HIP_OK(hipStreamWaitEvent(h->side, h->fork_ev[0], 0)); }
     if (int rc = prep_split_weights(h, false, ps_)) return rc;
@@ -549,7 +553,13 @@ int forward_impl(oct_unet* h, const void* x, int x_is_u8, int B, int training, c
         bn_infer_all_k<<<ia.n, 128, 0, s>>>(ia, h->cfg.bn_eps);
         HIP_OK(hipGetLastError());
     }
-    for (int li = 0; li < nl - 1; ++li) {
+    return 0;
+}
+
+int forward_stages(oct_unet* h, const void* x, int x_is_u8, int B, int training, bool dropout, bool fside, int li0, int li1,
+                   hipStream_t s) {
+    Plan& pl = h->plan;
+    for (int li = li0; li < li1; ++li) {
         Layer& l = pl.L[li];
         if (l.src == SRC_POOL) {  // pool the previous block's output (BN+ReLU applied on load)
             const Layer& p = pl.L[li - 1];
@@ -561,11 +571,15 @@ int forward_impl(oct_unet* h, const void* x, int x_is_u8, int B, int training, c
             HIP_OK(hipGetLastError());
         }
         if (fside && li == 1) HIP_OK(hipStreamWaitEvent(s, h->prep_ev, 0));     // first layer that reads the split weights
-        const int rc = conv_forward(h, li, x, x_is_u8, B, training, s);
+        const int rc = conv_forward(h, li, x, x_is_u8, B, training, dropout, s);
         if (rc) return rc;
     }
-    if (fside && nl - 1 <= 1) HIP_OK(hipStreamWaitEvent(s, h->prep_ev, 0));
-    // head
+    return 0;
+}
+
+int forward_head(oct_unet* h, int B, const oct_unet_io* io, hipStream_t s) {
+    Plan& pl = h->plan;
+    const int nl = (int)pl.L.size();
     const Layer& hd = pl.L[nl - 1]; const Layer& last = pl.L[nl - 2];
     HeadFwdArgs a{};
     a.z = last.z; a.ab = last.bn; a.w = h->params + hd.w_off; a.bias = h->params + hd.b_off;
@@ -575,8 +589,25 @@ int forward_impl(oct_unet* h, const void* x, int x_is_u8, int B, int training, c
     a.bce_on = h->bce_on; a.bce_inner = h->opt.bce_inner_eps ? kFocalEps : 0.f;
     const int rc = DISPATCH_C(launch_head_fwd, h->cfg.n_cls, a, hd.cin, B, s, head_is_wide(h->opt, hd.cin));
     if (rc) return rc;
-    h->last_B = B; h->last_training = training; h->have_dice = a.labels != nullptr;
+    h->have_dice = a.labels != nullptr;
     return 0;
+}
+
+int forward_impl(oct_unet* h, const void* x, int x_is_u8, int B, int training, const oct_unet_io* io, hipStream_t s) {
+    const int nl = (int)h->plan.L.size();
+    const bool fside = training && h->opt.dw_side_stream && h->side && !(t_prof && t_prof->on);
+    if (int rc = forward_prepare(h, training, fside, s)) return rc;
+    if (int rc = forward_stages(h, x, x_is_u8, B, training, training != 0, fside, 0, nl - 1, s)) return rc;
+    if (fside && nl - 1 <= 1) HIP_OK(hipStreamWaitEvent(s, h->prep_ev, 0));
+    if (int rc = forward_head(h, B, io, s)) return rc;
+    h->last_B = B; h->last_training = training;
+    return 0;
+}
+
+// index of the first decoder layer (the up-convolution behind the bottleneck, whose input the dropout sits on)
+int first_dec_layer(const Plan& pl) {
+    for (int li = 0; li < (int)pl.L.size(); ++li) if (pl.L[li].src == SRC_UP) return li;
+    return (int)pl.L.size() - 1;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1122,6 +1153,33 @@ int oct_unet_forward(oct_unet* h, const void* x, int x_is_u8, int B, int trainin
     if (rc) return rc;
     h->last_x = x; h->last_u8 = x_is_u8; h->dice_final = 0;
     return 0;
+}
+
+int oct_unet_forward_mc(oct_unet* h, const void* x, int x_is_u8, int B, int T, unsigned long long step0, float* probs_scratch,
+                        void* mc_ws, size_t mc_ws_bytes, const oct_mc_out* out, oct_stream_t stream) {
+    if (!h || !x || !probs_scratch || !mc_ws || !out) return fail(-1, "forward_mc: null handle, input, scratch, workspace or out");
+    if (B < 1 || B > h->cfg.max_batch) return fail(-1, "B out of range (1..max_batch)");
+    if (T < 1 || T > 64) return fail(-1, "forward_mc: T out of range (1..64)");
+    const oct_unet_cfg& c = h->cfg;
+    // what the T reductions would refuse (the last one reads `out`), before anything is launched
+    if (int rc = mc_validate(probs_scratch, B, c.H, c.W, c.n_cls, T - 1, T, mc_ws, mc_ws_bytes, out)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    t_prof = &h->prof;
+    const int nl = (int)h->plan.L.size(), k = first_dec_layer(h->plan);
+    const unsigned long long step_saved = h->drop_step;
+    const int advance_saved = h->drop_advance;
+    oct_unet_io io{}; io.probs = probs_scratch;
+    int rc = forward_prepare(h, 0, false, s);
+    if (!rc) rc = forward_stages(h, x, x_is_u8, B, 0, false, false, 0, k, s);       // encoder + bottleneck: once
+    for (int t = 0; t < T && !rc; ++t) {
+        h->drop_step = step0 + (unsigned long long)t;                               // by value into layer k's kernel arguments
+        rc = forward_stages(h, x, x_is_u8, B, 0, true, false, k, nl - 1, s);
+        if (!rc) rc = forward_head(h, B, &io, s);
+        if (!rc) rc = oct_mc_update(probs_scratch, B, c.H, c.W, c.n_cls, t, T, mc_ws, mc_ws_bytes, out, stream);
+    }
+    h->drop_step = step_saved; h->drop_advance = advance_saved;
+    h->have_dice = 0; h->dice_final = 0;
+    return rc;
 }
 
 // Dice (and focal) loss of the last forward: out holds n_user floats

@@ -103,6 +103,7 @@ class UNetEngine:
         self._opt: Dict[str, torch.Tensor] = {}
         self.opt_step = 0
         self._keep = []  # tensors referenced by an in-flight / captured launch
+        self._mc: Dict[int, dict] = {}  # forward_mc's buffers per batch size
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -318,6 +319,56 @@ class UNetEngine:
         m = torch.empty((B, self.cfg.H >> P, self.cfg.W >> P, self.cfg.start_neurons << P), dtype=torch.uint8, device=self.device)
         self._call("oct_unet_dropout_mask", B, m.data_ptr(), self._stream())
         return m
+
+    # ---- Monte-Carlo dropout: per-pixel uncertainty ---------------------------------------------------
+    def _mc_buffers(self, B: int) -> dict:
+        """Scratch probabilities, reduction workspace and output maps of ``forward_mc`` for batch ``B``: made once, kept."""
+        bufs = self._mc
+        if B not in bufs:
+            H, W, Cn = self.cfg.H, self.cfg.W, self.cfg.n_cls
+            f32 = dict(dtype=torch.float32, device=self.device)
+            bufs[B] = dict(
+                scratch=torch.empty((B, H, W, Cn), **f32),
+                ws=torch.empty(int(_hip.lib().oct_mc_workspace_bytes(B, H, W, Cn)), dtype=torch.uint8, device=self.device),
+                mean_probs=torch.empty((B, H, W, Cn), **f32), argmax=torch.empty((B, H, W), dtype=torch.uint8, device=self.device),
+                entropy=torch.empty((B, H, W), **f32), mutual_info=torch.empty((B, H, W), **f32))
+        return bufs[B]
+
+    def forward_mc(self, x: torch.Tensor, samples: int, step0: int = 0, want_mean_probs: bool = False) -> Dict[str, torch.Tensor]:
+        """``samples`` inference forwards with the bottleneck dropout on (dropout steps ``step0 .. step0+samples-1``, the
+        encoder and bottleneck run once), reduced on the device (``oct_unet_forward_mc``): a dict of device tensors
+        ``argmax`` (B,H,W) uint8 -- of the mean probabilities --, ``entropy`` and ``mutual_info`` (B,H,W) float32 and, with
+        ``want_mean_probs``, ``mean_probs`` (B,H,W,C) float32.  The tensors are the engine's own buffers for this batch
+        size: the next ``forward_mc`` of the same batch size refills them.  Asynchronous on the current stream."""
+        self._check_x(x)
+        if not 1 <= int(samples) <= _hip.MC_MAX_SAMPLES:
+            raise OctError(f"forward_mc: samples must be in 1..{_hip.MC_MAX_SAMPLES}, not {samples}")
+        B = x.shape[0]
+        b = self._mc_buffers(B)
+        keys = ("argmax", "entropy", "mutual_info") + (("mean_probs",) if want_mean_probs else ())
+        out = _hip.McOut(**{k: b[k].data_ptr() for k in keys})
+        self._call("oct_unet_forward_mc", x.data_ptr(), int(x.dtype == torch.uint8), B, int(samples),
+                   int(step0) & 0xFFFFFFFFFFFFFFFF, b["scratch"].data_ptr(), b["ws"].data_ptr(), b["ws"].numel(), C.byref(out),
+                   self._stream())
+        self._keep = [x]
+        return {k: b[k] for k in keys}
+
+    def mc_update(self, probs: torch.Tensor, t: int, samples: int, ws: torch.Tensor, *, mean_probs=None, argmax=None,
+                  entropy=None, mutual_info=None) -> None:
+        """Fold softmax sample ``t`` of ``samples`` -- ``probs`` (B,H,W,C) float32, any C in 2..32 -- into the running sums
+        in ``ws`` (a uint8 tensor of ``oct_mc_workspace_bytes`` bytes); the call with ``t == samples - 1`` writes the maps
+        that are given (``oct_mc_update``; ``common.utils.mc_reduce_reference`` restates it).  Calls go in order of t."""
+        _hip.expect(probs, "probs (B,H,W,C)", device=self.device, dtype=torch.float32, shape=(None, None, None, None))
+        B, H, W, Cn = probs.shape
+        _hip.expect(ws, "mc workspace", device=self.device, dtype=torch.uint8, shape=(None,))
+        for t_, what, dt, shape in ((mean_probs, "mean_probs", torch.float32, (B, H, W, Cn)), (argmax, "argmax", torch.uint8, (B, H, W)),
+                                    (entropy, "entropy", torch.float32, (B, H, W)), (mutual_info, "mutual_info", torch.float32, (B, H, W))):
+            if t_ is not None:
+                _hip.expect(t_, what, device=self.device, dtype=dt, shape=shape)
+        ptr = lambda t_: t_.data_ptr() if t_ is not None else None
+        out = _hip.McOut(ptr(mean_probs), ptr(argmax), ptr(entropy), ptr(mutual_info))
+        _hip.call("oct_mc_update", self.device, probs.data_ptr(), B, H, W, Cn, int(t), int(samples), ws.data_ptr(), ws.numel(),
+                  C.byref(out), self._stream())
 
     # ---- inference hipGraph ------------------------------------------------------------------------
     def graph_capture(self, x: torch.Tensor, want_probs=True, want_argmax=False):

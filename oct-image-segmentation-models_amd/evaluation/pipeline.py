@@ -33,6 +33,22 @@ class Batch(NamedTuple):
     minpath: Optional[Tuple[np.ndarray, ...]] = None   # rows (n, C-1, W) uint16, cost (n, C-1) float64, tied (n, C-1) bool
     confusion: Optional[np.ndarray] = None         # (n, C, C) uint32 confusion counts [gt][pred] of labels against the ground truth
 
+    # Monte-Carlo dropout runs (mc_samples > 0) also carry two (n, H, W) float32 maps: the predictive entropy (nats) and the
+    # mutual information (BALD) of the samples.  They are ATTRIBUTES, not tuple fields -- the seven fields above are what
+    # every positional construction and unpacking of a record relies on -- and None on every other record.
+    entropy = None
+    mutual_info = None
+
+    def with_uncertainty(self, entropy: np.ndarray, mutual_info: np.ndarray) -> "Batch":
+        """This record with ``entropy`` / ``mutual_info`` set."""
+        b = _UncertainBatch(*self)
+        b.entropy, b.mutual_info = entropy, mutual_info
+        return b
+
+
+class _UncertainBatch(Batch):
+    """A ``Batch`` that can hold the two attributes (a NamedTuple instance has no dictionary; an instance of this has)."""
+
 
 class _Stage(NamedTuple):
     """One per-batch device post-process: the ``Batch`` field it fills, the wrapper that runs it -- ``run(*inputs, *outs)``
@@ -75,13 +91,23 @@ class BatchedPredictor:
 
     With ``soft_maps`` the graph also writes the class probabilities, into a buffer that never leaves the device, and
     ``maps`` are the soft boundary maps of those (``oct_boundary_maps_soft``) instead of the binary maps of the arg-max.
-    Labels, surface distances, confusion counts, the min-path stage behind the maps and every transfer are the same."""
+    Labels, surface distances, confusion counts, the min-path stage behind the maps and every transfer are the same.
+
+    With ``mc_samples`` > 0 every batch is a Monte-Carlo dropout prediction: no graph is captured, and the per-batch graph
+    launch is ``engine.forward_mc`` on the same fixed input buffer -- ``mc_samples`` forwards with the bottleneck dropout on,
+    dropout steps ``mc_step0 .. mc_step0+mc_samples-1`` for EVERY batch.  The arg-max maps and (with ``soft_maps``) the
+    probabilities are then those of the MEAN prediction, everything behind them is unchanged, and ``Batch.entropy`` /
+    ``Batch.mutual_info`` carry the two uncertainty maps, downloaded through pinned double buffers like the labels.  The
+    dropout stream is indexed by the position in the batch's bottleneck tensor and seeded per rank: an image's result
+    depends on its position in its batch and on the rank that predicts it."""
 
     def __init__(self, engine, batch: int, want_maps: bool = True, bg_ilm: bool = True, bg_csi: bool = False,
-                 surface=None, minpath=None, confusion=None, soft_maps: bool = False):
+                 surface=None, minpath=None, confusion=None, soft_maps: bool = False, mc_samples: int = 0, mc_step0: int = 0):
         if soft_maps and not want_maps:
             raise ValueError("soft_maps: needs want_maps=True")
-        self.soft_maps = bool(soft_maps)
+        if not 0 <= int(mc_samples) <= 64:
+            raise ValueError(f"mc_samples must be in 0..64, not {mc_samples}")
+        self.soft_maps, self.mc_samples, self.mc_step0 = bool(soft_maps), int(mc_samples), int(mc_step0)
         if not 1 <= batch <= engine.cfg.max_batch:
             raise ValueError(f"batch {batch} outside 1..max_batch={engine.cfg.max_batch}")
         self.eng, self.B, self.want_maps, self.bg = engine, int(batch), want_maps, (bg_ilm, bg_csi)
@@ -110,7 +136,13 @@ class BatchedPredictor:
             self.gt_dev = [torch.empty((self.B, H, W), dtype=torch.uint8, device=dev) for _ in range(2)]
         self.copy_in = torch.cuda.Stream(device=dev)
         self.copy_out = torch.cuda.Stream(device=dev)
-        self.probs, self.am = engine.graph_capture(self.x_dev, want_probs=self.soft_maps, want_argmax=True)
+        self.unc_dev = self.unc_pin = None                  # (entropy, mutual_info) double buffers
+        if self.mc_samples:
+            self.unc_dev = [tuple(torch.empty((self.B, H, W), dtype=torch.float32, device=dev) for _ in range(2)) for _ in range(2)]
+            self.unc_pin = [tuple(torch.empty((self.B, H, W), dtype=torch.float32).pin_memory() for _ in range(2)) for _ in range(2)]
+            self.probs = self.am = None                     # the engine's forward_mc buffers: set by every batch
+        else:
+            self.probs, self.am = engine.graph_capture(self.x_dev, want_probs=self.soft_maps, want_argmax=True)
 
     def run(self, images_u8: np.ndarray, gt_u8: Optional[np.ndarray] = None) -> Iterator[Batch]:
         images_u8 = np.ascontiguousarray(images_u8)
@@ -162,10 +194,17 @@ class BatchedPredictor:
             main.wait_event(up_done[s])
             self.x_dev.copy_(self.x_stage[s])                                           # D2D, then the staging buffer is free
             x_free[s].record(main)
-            eng.graph_launch()
+            mc = None
+            if self.mc_samples:
+                mc = eng.forward_mc(self.x_dev, self.mc_samples, step0=self.mc_step0, want_mean_probs=self.soft_maps)
+                self.am, self.probs = mc["argmax"], mc.get("mean_probs")
+            else:
+                eng.graph_launch()
             if i >= 2:
                 main.wait_event(out_done[s])                                            # device out buffers of batch i-2 downloaded
             self.lab_dev[s].copy_(self.am)
+            if mc is not None:
+                self.unc_dev[s][0].copy_(mc["entropy"]); self.unc_dev[s][1].copy_(mc["mutual_info"])
             outs = [self.out_dev[st.field][s] for st in stages]
             srcs = (self.lab_dev[s], self.gt_dev[s], self.map_dev[s] if self.want_maps else None)
             for st, o in zip(stages, outs):
@@ -187,6 +226,9 @@ class BatchedPredictor:
                 self.lab_pin[s].copy_(self.lab_dev[s], non_blocking=True)
                 if self.want_maps:
                     self.map_pin[s].copy_(self.map_dev[s], non_blocking=True)
+                if mc is not None:
+                    for t_pin, t_dev in zip(self.unc_pin[s], self.unc_dev[s]):
+                        t_pin.copy_(t_dev, non_blocking=True)
                 for st, o in zip(stages, outs):
                     for t_pin, t_dev in zip(self.out_pin[st.field][s], o):
                         t_pin.copy_(t_dev, non_blocking=True)
@@ -201,14 +243,17 @@ class BatchedPredictor:
         ev.synchronize()
         labels = self.lab_pin[s][:hi - lo].numpy().copy()
         maps = self.map_pin[s][:hi - lo].numpy().copy() if self.want_maps else None
-        return Batch(lo, hi, labels, maps, **{st.field: st.to_host(hi - lo, self.out_pin[st.field][s], lo) for st in stages})
+        batch = Batch(lo, hi, labels, maps, **{st.field: st.to_host(hi - lo, self.out_pin[st.field][s], lo) for st in stages})
+        if self.unc_pin is not None:
+            batch = batch.with_uncertainty(*(t[:hi - lo].numpy().copy() for t in self.unc_pin[s]))
+        return batch
 
 
 def host_batches(model, images: np.ndarray, batch: int, *, gt_u8: Optional[np.ndarray] = None, surface=None,
-                 minpath=None, confusion=None, soft_maps: bool = False) -> Iterator[Batch]:
+                 minpath=None, confusion=None, soft_maps: bool = False, mc_samples: int = 0, mc_step0: int = 0) -> Iterator[Batch]:
     """The same records for images that are not uint8: x / 255 on the host (``Model.predict_labels``), one synchronous
-    forward per batch, no overlap.  ``surface`` / ``minpath`` / ``confusion`` / ``soft_maps`` as in ``BatchedPredictor``;
-    each stage writes its own output buffers."""
+    forward per batch, no overlap.  ``surface`` / ``minpath`` / ``confusion`` / ``soft_maps`` / ``mc_samples`` /
+    ``mc_step0`` as in ``BatchedPredictor``; each stage writes its own output buffers."""
     stages = _stages(surface, confusion, minpath, have_gt=gt_u8 is not None)
     on_labels, on_maps = any(not st.on_maps for st in stages), any(st.on_maps for st in stages)
 
@@ -217,15 +262,16 @@ def host_batches(model, images: np.ndarray, batch: int, *, gt_u8: Optional[np.nd
 
     for lo in range(0, images.shape[0], batch):
         hi = min(lo + batch, images.shape[0])
-        labels, maps = model.predict_labels(images[lo:hi], batch_size=batch, want_maps=True, bg_ilm=True, bg_csi=False,
-                                            soft_maps=soft_maps)
+        labels, maps, *unc = model.predict_labels(images[lo:hi], batch_size=batch, want_maps=True, bg_ilm=True, bg_csi=False,
+                                                  soft_maps=soft_maps, mc_samples=mc_samples, mc_step0=mc_step0)
         lab_dev, gt_dev = (upload(labels.astype(np.uint8)), upload(gt_u8[lo:hi])) if on_labels else (None, None)
         maps_dev = upload(maps) if on_maps else None
         fields = {}
         for st in stages:
             st.launch(hi - lo, st.run.outs, lab_dev, gt_dev, maps_dev)
             fields[st.field] = st.to_host(hi - lo, st.run.outs, lo)
-        yield Batch(lo, hi, labels, maps, **fields)
+        record = Batch(lo, hi, labels, maps, **fields)
+        yield record.with_uncertainty(*unc) if unc else record
 
 
 class InferenceRun:
@@ -244,12 +290,16 @@ class InferenceRun:
     ``soft_maps`` is passed to whichever source is built: ``Batch.maps`` are then the soft boundary maps of the class
     probabilities, and everything behind them (either search, ``gs_labels``) works on those.
 
+    ``mc_samples`` > 0 (with ``mc_step0``) is passed on likewise: every batch is then a Monte-Carlo dropout prediction,
+    ``Batch.labels`` / ``Batch.maps`` are those of the mean prediction, and ``Batch.entropy`` / ``Batch.mutual_info`` are
+    filled (see ``BatchedPredictor`` for what the result depends on).
+
     ``batches`` replaces the model by a ready source of records (tests of the host side: no device is touched)."""
 
     def __init__(self, model, images: np.ndarray, batch: int, num_classes: int, *, gt: Optional[np.ndarray] = None,
                  graph_search: bool = False, gsgrad: int = 1, gs_device: bool = False, gs_device_ties: str = "host",
                  gs_workers: Optional[int] = None, batches: Optional[Iterable[Batch]] = None, surface: bool = True,
-                 confusion: bool = False, soft_maps: bool = False):
+                 confusion: bool = False, soft_maps: bool = False, mc_samples: int = 0, mc_step0: int = 0):
         n, (H, W), C = images.shape[0], images.shape[1:3], int(num_classes)
         self.pool = self.host_ties = None
         self._gs = self._gs_geom = None                   # gs_labels' own device buffers: made by its first call
@@ -279,11 +329,12 @@ class InferenceRun:
             if images.dtype == np.uint8:
                 predictor = BatchedPredictor(model._ensure_engine(bs, False), bs, want_maps=True, bg_ilm=True, bg_csi=False,
                                              surface=surface, minpath=minpath, confusion=confusion,
-                                             soft_maps=soft_maps)
+                                             soft_maps=soft_maps, mc_samples=mc_samples, mc_step0=mc_step0)
                 self._batches = predictor.run(images, gt_u8)
             else:
                 self._batches = host_batches(model, images, bs, gt_u8=gt_u8, surface=surface, minpath=minpath,
-                                             confusion=confusion, soft_maps=soft_maps)
+                                             confusion=confusion, soft_maps=soft_maps, mc_samples=mc_samples,
+                                             mc_step0=mc_step0)
         except BaseException:
             self.close()
             raise
@@ -348,6 +399,16 @@ class InferenceRun:
         return batch_pictures(self._png, C, images, pred_labels=batch.labels if pred_map else None, gt_labels=gt,
                               truths=truths, gs_segs=gs_segs, gs_labels=gs_labels,
                               both_overlay=truths is not None and gs_segs is not None, col_range=col_range)
+
+    def render_gray(self, gray_u8: np.ndarray) -> np.ndarray:
+        """(n,H,W) uint8 -> (n,H,W,4) RGBA on the host: the values as a gray scan with no lines, through the renderer of
+        ``render_pngs`` (``predict`` draws the quantised predictive entropy with it).  Waits for the device."""
+        if self._gs_geom is None:
+            raise RuntimeError("render_gray needs the device: this run was built over injected batches")
+        bs, H, W, _, dev = self._gs_geom
+        if self._png is None:
+            self._png = PngRenderer(bs, H, W, dev)
+        return self._png.render(np.ascontiguousarray(gray_u8, dtype=np.uint8)[..., None])
 
     def close(self) -> None:
         for p in (self.pool, self.host_ties):

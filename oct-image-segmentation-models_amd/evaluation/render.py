@@ -119,7 +119,8 @@ EVALUATION_PNG_NAMES = {"pred": "predicted_segmentation_map.png", "raw": "raw_im
                         "gs_bounds": "gs_predicted_boundaries_ovelay_plot.png"}
 PREDICTION_PNG_NAMES = {"pred": "segmentation_map.png", "raw": "raw_image.png",
                         "gs_map": "gs_predicted_segmentation_map.png",
-                        "gs_bounds": "gs_predicted_boundaries_ovelay_plot.png"}
+                        "gs_bounds": "gs_predicted_boundaries_ovelay_plot.png",
+                        "uncertainty": "uncertainty_map.png"}        # (no counterpart in the reference: Monte-Carlo dropout)
 
 
 def write_pictures(output_dir, pictures: Dict[str, np.ndarray], k: int, names: Dict[str, str]) -> None:

@@ -432,12 +432,35 @@ class Model:
             out[lo:lo + bs] = probs.cpu().numpy()
         return out
 
+    def predict_mc(self, x, samples: int, batch_size: Optional[int] = None, step0: int = 0):
+        """Monte-Carlo dropout prediction: ``samples`` stochastic forwards per batch with the bottleneck dropout on (dropout
+        steps ``step0 .. step0+samples-1``, the same for every batch; ``UNetEngine.forward_mc``), reduced on the device.
+        Input as for ``predict``; returns ``(mean_probs (n,H,W,num_classes), entropy (n,H,W), mutual_info (n,H,W))``
+        float32.  The dropout stream is indexed by the element's position in the bottleneck tensor of its BATCH and seeded
+        per rank, so an image's result depends on its position in its batch (hence on ``batch_size``) and on the rank."""
+        x = np.asarray(x)
+        if x.dtype != np.uint8:
+            x = np.ascontiguousarray(x, dtype=np.float32)
+        n = x.shape[0]
+        bs = int(batch_size or min(n, 32))
+        eng = self._ensure_engine(min(bs, n), False)
+        mean = np.empty((n,) + tuple(x.shape[1:3]) + (self.config["num_classes"],), np.float32)
+        ent, mi = np.empty(x.shape[:3], np.float32), np.empty(x.shape[:3], np.float32)
+        for lo in range(0, n, bs):
+            xb = torch.from_numpy(np.ascontiguousarray(x[lo:lo + bs])).to(eng.device)
+            out = eng.forward_mc(xb, samples, step0=step0, want_mean_probs=True)
+            mean[lo:lo + bs], ent[lo:lo + bs], mi[lo:lo + bs] = (out[k].cpu().numpy() for k in ("mean_probs", "entropy", "mutual_info"))
+        return mean, ent, mi
+
     def predict_labels(self, x_u8: np.ndarray, batch_size: int = 32, want_maps: bool = False, bg_ilm: bool = True,
-                       bg_csi: bool = False, soft_maps: bool = False):
+                       bg_csi: bool = False, soft_maps: bool = False, mc_samples: int = 0, mc_step0: int = 0):
         """Raw uint8 images -> uint8 arg-max class maps (n,H,W), computed on the device (1 B/px back instead of
         4*C B/px).  With ``want_maps`` also the (n, C-1, H, W) uint8 boundary maps of
         ``convert_predictions_to_maps_semantic``, computed on the device from the class maps -- or, with ``soft_maps``,
-        from the class probabilities, which stay on the device (``UNetEngine.boundary_maps_soft``)."""
+        from the class probabilities, which stay on the device (``UNetEngine.boundary_maps_soft``).
+        With ``mc_samples`` > 0 every batch is a Monte-Carlo dropout prediction (``predict_mc``): the class maps and
+        boundary maps are those of the mean prediction, and the (n,H,W) float32 predictive entropy and mutual information
+        are returned behind them -- ``(labels, entropy, mutual_info)`` or ``(labels, maps, entropy, mutual_info)``."""
         if soft_maps and not want_maps:
             raise ValueError("soft_maps: needs want_maps=True")
         x_u8 = np.ascontiguousarray(x_u8)
@@ -449,15 +472,21 @@ class Model:
         eng = self._ensure_engine(min(batch_size, n), False)
         out = np.empty(x_u8.shape[:3], np.uint8)
         maps = np.empty((n, self.config["num_classes"] - 1) + tuple(x_u8.shape[1:3]), np.uint8) if want_maps else None
+        unc = (np.empty(x_u8.shape[:3], np.float32), np.empty(x_u8.shape[:3], np.float32)) if mc_samples else ()
         for lo in range(0, n, batch_size):
             xb = torch.from_numpy(x_u8[lo:lo + batch_size]).to(eng.device)
-            probs, am = eng.forward(xb, training=False, want_probs=soft_maps, want_argmax=True)
+            if mc_samples:
+                mc = eng.forward_mc(xb, mc_samples, step0=mc_step0, want_mean_probs=soft_maps)
+                probs, am = mc.get("mean_probs"), mc["argmax"]
+                unc[0][lo:lo + batch_size], unc[1][lo:lo + batch_size] = mc["entropy"].cpu().numpy(), mc["mutual_info"].cpu().numpy()
+            else:
+                probs, am = eng.forward(xb, training=False, want_probs=soft_maps, want_argmax=True)
             out[lo:lo + batch_size] = am.cpu().numpy()
             if want_maps:
                 dev_maps = (eng.boundary_maps_soft(probs, bg_ilm=bg_ilm, bg_csi=bg_csi) if soft_maps
                             else eng.boundary_maps(am, bg_ilm=bg_ilm, bg_csi=bg_csi))
                 maps[lo:lo + batch_size] = dev_maps.cpu().numpy()
-        return (out, maps) if want_maps else out
+        return ((out, maps) if want_maps else out) if not mc_samples else ((out, maps) + unc if want_maps else (out,) + unc)
 
 
 def load_model(path) -> Model:

@@ -24,7 +24,8 @@ from .prediction_parameters import PredictionParams
 
 class PredictionOutput:
     def __init__(self, image: np.ndarray, image_name: Path, image_output_dir: Path, predicted_labels: np.ndarray,
-                 categorical_pred: np.ndarray, boundary_maps: np.ndarray, gs_pred_segs: Union[np.ndarray, None]) -> None:
+                 categorical_pred: np.ndarray, boundary_maps: np.ndarray, gs_pred_segs: Union[np.ndarray, None],
+                 predictive_entropy: Union[np.ndarray, None] = None, mutual_information: Union[np.ndarray, None] = None) -> None:
         self.image = image
         self.image_name = image_name
         self.image_output_dir = image_output_dir
@@ -32,12 +33,20 @@ class PredictionOutput:
         self.categorical_pred = categorical_pred
         self.boundary_maps = boundary_maps
         self.gs_pred_segs = gs_pred_segs
+        # (H,W) float32 maps of a Monte-Carlo dropout prediction (PredictionParams.mc_samples > 0), else None
+        self.predictive_entropy = predictive_entropy
+        self.mutual_information = mutual_information
 
 
 def predict(predict_params: PredictionParams) -> List[PredictionOutput]:
     """With ``predict_params.gs_labels_device`` the graph-search class maps come from the device, a batch at a time, and
     the ``graph_time`` attribute of graph_search_prediction_info.hdf5 is that stage's time divided by the batch's image
-    count; every dataset and CSV file equals the host path's."""
+    count; every dataset and CSV file equals the host path's.
+
+    With ``predict_params.mc_samples`` > 0 every batch is a Monte-Carlo dropout prediction (``InferenceRun(mc_samples=)``):
+    every file describes the MEAN prediction, prediction_info.hdf5 gains the float32 (H,W) datasets ``predictive_entropy``
+    and ``mutual_information`` and the attribute ``mc_samples``, and with the PNG pictures on ``uncertainty_map.png`` (the
+    entropy over ln C as a gray scan) is written too.  With 0 every file is byte for byte what it was."""
     rank, _, _ = parallel.init()
     world = parallel.world_size()
     dataset = predict_params.dataset
@@ -56,11 +65,13 @@ def predict(predict_params: PredictionParams) -> List[PredictionOutput]:
     outputs: List[PredictionOutput] = []
     lo, hi = parallel.shard_range(len(images), rank, world)
     png_plots = bool(getattr(predict_params, "png_plots", False)) and predict_params.save_params.png_images is True
+    mc_samples = int(getattr(predict_params, "mc_samples", 0))
     # the device pipeline of evaluate_model (evaluation/pipeline.py::InferenceRun), without ground truth
     with InferenceRun(predict_params.loaded_model, images[lo:hi], predict_params.batch_size, num_classes,
                       graph_search=predict_params.graph_search, gs_device=predict_params.gs_device,
                       gs_device_ties=predict_params.gs_device_ties, gs_workers=predict_params.gs_workers,
-                      soft_maps=not getattr(predict_params, "binarize", True)) as run:
+                      soft_maps=not getattr(predict_params, "binarize", True),
+                      mc_samples=mc_samples, mc_step0=getattr(predict_params, "mc_step0", 0)) as run:
         t0 = time.time()
         for batch in run:
             b0, b1 = lo + batch.lo, lo + batch.hi
@@ -76,6 +87,8 @@ def predict(predict_params: PredictionParams) -> List[PredictionOutput]:
                 pictures = run.render_pngs(batch, images[b0:b1], gs_found, gs_labels=gs_labels,
                                            pred_map=predict_params.save_params.predicted_labels is True,
                                            col_range=(predict_params.col_error_range[0], predict_params.col_error_range[-1]))
+                if batch.entropy is not None:
+                    pictures["uncertainty"] = run.render_gray(utils.entropy_to_u8(batch.entropy, num_classes))
             for i in range(b0, b1):
                 predict_image, image_name, image_output_dir = images[i], dataset.image_names[i], Path(dataset.image_output_dirs[i])
                 os.makedirs(image_output_dir, exist_ok=True)
@@ -89,8 +102,12 @@ def predict(predict_params: PredictionParams) -> List[PredictionOutput]:
                 predicted_labels = np.squeeze(predicted_labels, axis=0)
                 categorical_pred = np.squeeze(categorical_pred, axis=0)
                 boundary_maps = np.squeeze(boundary_maps, axis=0)
+                entropy = mutual_info = None
+                if batch.entropy is not None:
+                    entropy, mutual_info = batch.entropy[i - b0], batch.mutual_info[i - b0]
                 save_image_prediction_results(predict_params, predict_image, image_name, predicted_labels, categorical_pred,
-                                              boundary_maps, predict_time, convert_time, image_output_dir)
+                                              boundary_maps, predict_time, convert_time, image_output_dir,
+                                              entropy=entropy, mutual_info=mutual_info)
                 gs_pred_segs = None
                 if predict_params.graph_search:
                     predict_image_t = np.transpose(predict_image, axes=[1, 0, 2])
@@ -107,7 +124,8 @@ def predict(predict_params: PredictionParams) -> List[PredictionOutput]:
                     write_pictures(image_output_dir, pictures, i - b0, PREDICTION_PNG_NAMES)
                 outputs.append(PredictionOutput(image=predict_image, image_name=image_name, image_output_dir=image_output_dir,
                                                 predicted_labels=predicted_labels, categorical_pred=categorical_pred,
-                                                boundary_maps=boundary_maps, gs_pred_segs=gs_pred_segs))
+                                                boundary_maps=boundary_maps, gs_pred_segs=gs_pred_segs,
+                                                predictive_entropy=entropy, mutual_information=mutual_info))
             t0 = time.time()
     parallel.barrier()
     return outputs
@@ -120,11 +138,16 @@ def save_predict_config_file(predict_params: PredictionParams):
         attrs["binarize"] = np.array(False)      # recorded only when it departs from the default: binarize=True files stay as they were
     if getattr(predict_params, "png_plots", False):
         attrs["png_plots"] = np.array(True)      # likewise
+    if getattr(predict_params, "mc_samples", 0):
+        attrs["mc_samples"] = np.array(int(predict_params.mc_samples))      # likewise, with the first dropout step
+        attrs["mc_step0"] = np.array(int(getattr(predict_params, "mc_step0", 0)))
     h5io.save(predict_params.config_output_dir / Path("prediction_params.hdf5"), {}, attrs)
 
 
 def save_image_prediction_results(pred_params, predict_image, image_name, predicted_labels, categorical_pred,
-                                  boundary_maps, predict_time, convert_time, output_dir):
+                                  boundary_maps, predict_time, convert_time, output_dir, entropy=None, mutual_info=None):
+    """``entropy`` / ``mutual_info``: the (H,W) maps of a Monte-Carlo dropout prediction, stored (with the sample count)
+    only when given: without them the file is what it always was."""
     ds = {}
     if pred_params.save_params.categorical_pred is True:
         ds["categorical_pred"] = categorical_pred.astype("uint8")
@@ -135,6 +158,10 @@ def save_image_prediction_results(pred_params, predict_image, image_name, predic
         ds["boundary_maps"] = boundary_maps.astype("uint8")
     ds["raw_image"] = predict_image.astype("uint8")
     attrs = utils.result_attrs(pred_params.model_path, image_name, predict_time=np.array(predict_time), convert_time=convert_time)
+    if entropy is not None:
+        ds["predictive_entropy"] = np.asarray(entropy, np.float32)
+        ds["mutual_information"] = np.asarray(mutual_info, np.float32)
+        attrs["mc_samples"] = np.array(int(getattr(pred_params, "mc_samples", 0)))
     h5io.save(output_dir / Path("prediction_info.hdf5"), ds, attrs)
 
 

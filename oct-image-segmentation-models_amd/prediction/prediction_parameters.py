@@ -25,7 +25,9 @@ class PredictionParams:
                  graph_search: bool = False, trim_maps: bool = False, trim_ref_ind: int = 0,
                  trim_window: tuple = (0, 0), col_error_range: tuple = None, batch_size: int = 32, gs_device: bool = False,
                  gs_device_ties: str = "host", gs_workers: Union[int, None] = None, gs_labels_device: bool = False,
-                 binarize: bool = True, png_plots: bool = False) -> None:
+                 binarize: bool = True, png_plots: bool = False, mc_samples: int = 0, mc_step0: int = 0) -> None:
+        if not 0 <= int(mc_samples) <= 64:
+            raise ValueError(f"mc_samples must be in 0..64, not {mc_samples}")
         self.model_path = Path(model_path)
         self.mlflow_tracking_uri = mlflow_tracking_uri
         self.mlflow_run_uuid = mlflow_run_uuid
@@ -54,6 +56,12 @@ class PredictionParams:
         # extension, as EvaluationParameters.png_plots: segmentation_map.png, raw_image.png and, with graph search,
         # gs_predicted_segmentation_map.png and gs_predicted_boundaries_ovelay_plot.png (columns col_error_range)
         self.png_plots = bool(png_plots)
+        # extension: Monte-Carlo dropout prediction.  mc_samples > 0: every batch is predicted mc_samples times with the
+        # bottleneck dropout on (dropout steps mc_step0 .. mc_step0+mc_samples-1, the same for every batch); the class maps,
+        # boundary maps and everything behind them are those of the mean prediction, and prediction_info.hdf5 gains
+        # predictive_entropy / mutual_information.  A result depends on the image's position in its batch (batch_size) and
+        # on the rank that predicts it (the dropout stream is seeded per rank).  0: the deterministic prediction
+        self.mc_samples, self.mc_step0 = int(mc_samples), int(mc_step0)
         self.col_error_range = col_error_range
         if col_error_range is None:
             self.col_error_range = range(dataset.images[0].shape[1])  # image_width
