@@ -489,6 +489,14 @@ int oct_render_rgba(int base_mode, const unsigned char* base_dev, int ic, const 
  *   bn_*_finalize launch.  Same results to fp32 rounding; measured 0.5-1 % slower per step than the launches it removes,
  *   hence off by default.  (The channel-streaming head kernels never finalize in the launch: under "head_wide", and above
  *   32 channels, the last block's statistics are finalized by the bn_bwd_finalize launch whatever this option says.)
+ *   "pool_in_epilogue" (1; fp32 storage only; may be set on a live handle between steps): the bf16-pipe forward conv in
+ *   front of a max-pool also writes the pooled tensor, from its accumulators, as the RAW window extrema of z -- the maximum
+ *   where the layer's gamma >= 0 (+-0 included), the minimum where gamma < 0 -- and the pool's consumers (the next conv and
+ *   its backward-weights kernel) apply the producer's BN + ReLU on load.  relu(fma(a, z, b)) is monotone in z with the
+ *   direction of sign(gamma), so this is bit for bit what pool_fwd_k computes from relu(a z + b), without re-reading z.
+ *   conv_bt_k does it (8 and 16 K channels), and conv_bx_k where a wave holds two tile rows; the other producers (the wide form with
+ *   one tile row per wave, the fp32-pipe kernels, the image layer) and bf16 storage keep the pool_fwd_k pass.  0 = that
+ *   pass everywhere.
  *   "head_wide" (0; may be set on a live handle between steps): the head (BN + ReLU on load, 1x1 conv, softmax, loss
  *   sums; backward: loss gradient, softmax Jacobian, 1x1 backward, mask, statistics) has two forms.  The register kernels
  *   head_fwd_k / head_bwd_k<C, CIN> keep a pixel's CIN channels and CIN*C + C + 2*CIN partial sums in registers and exist

@@ -61,6 +61,8 @@ struct Options {
     int persist_min_tiles = 2048;   // pixel tiles from which thin single-chunk convs use the persistent pipelined kernel
     int head_wide = 0;              // 1: every start_neurons takes the channel-streaming head kernels (kernels_head_wide.hpp), which
                                     // widths above 32 always take: holds them against the register kernels on equal inputs
+    int pool_in_epilogue = 1;       // fp32 storage: the bf16-pipe forward convs in front of a max-pool write the pooled tensor from their
+                                    // accumulators (raw window extrema; consumers apply BN + ReLU on load) -- no pool_fwd_k pass
     int max_blocks = 0;             // FOR TESTS ("persistent_max_blocks"): > 0 caps the grid of every persistent launch, so that
                                     // small images make blocks walk several tiles (cap_grid below); 0 = the launches' own grids
 };
@@ -111,7 +113,10 @@ inline int bx_mb(int M) { return M % 64 == 0 ? 64 : 32; }
 inline bool bt_k_ok(int k) { return k == 8 || k == 16 || k == 32; }
 
 // what a conv launch needs besides its argument block
-struct LaunchCtx { const Options* o; int B; hipStream_t s; const char* layer; double flops, bytes; };
+struct LaunchCtx {
+    const Options* o; int B; hipStream_t s; const char* layer; double flops, bytes;
+    bool* pooled = nullptr;     // out (optional): the launch wrote IgemmArgs::pool_out (the kernel form it picked can)
+};
 
 // kernel family a conv launch runs on
 enum ConvRoute { ROUTE_BT = 0, ROUTE_BX = 1, ROUTE_F32 = 2 };

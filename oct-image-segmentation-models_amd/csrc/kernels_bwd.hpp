@@ -179,8 +179,11 @@ static __global__ __launch_bounds__(kBlock) void bn_bwd_finalize_k(const BnBwdFi
     __shared__ double sh[8];
     const int c = blockIdx.x;
     double s, q;
+    // gamma and the record's forward rows are requested in front of the column sums, not behind them
+    float ga = 0.f, mean = 0.f, rstd = 0.f;
+    if (threadIdx.x == 0) { ga = A.gamma[c]; mean = A.bn[BN_MEAN * A.C + c]; rstd = A.bn[BN_RSTD * A.C + c]; }
     column_sums_f64(A.part, A.nblk, A.C, c, sh, s, q);
-    if (threadIdx.x == 0) bn_bwd_finalize_write(s, q, A.count, A.C, c, A.bn, A.gamma, A.dgamma, A.dbeta);
+    if (threadIdx.x == 0) bn_bwd_finalize_write(s, q, A.count, A.C, c, A.bn, ga, mean, rstd, A.dgamma, A.dbeta);
 }
 
 // the BN-backward transform of one element: dz = ga g' + (gb z + gd) (record rows BN_GA / BN_GB / BN_GD), written as its

@@ -457,6 +457,11 @@ __global__ __launch_bounds__(64 * NW, NIMG == 1 ? (NW == 4 ? 2 : 1) : 1) void co
     // register until the weight slots they will be staged in are free
     constexpr int EPN = EPI == EPI_MASK ? 4 * MB : (EPI == EPI_FWD ? MB : 0), EPF = (EPN + NTHR - 1) / NTHR;
     float epi_pf[EPF > 0 ? EPF : 1];
+    // pooled output (IgemmArgs::pool_out; fp32 storage, two tile rows per wave: every 2x2 window lies in one wave).  The
+    // layer's gamma (its sign picks the window's max or min of z) travels with the bias: one value per thread, staged behind `red`
+    constexpr bool POOLS = EPI == EPI_FWD && AMODE == A_NORMAL && KH == 3 && NTW == 2 && sizeof(AT) == 4;
+    static_assert(!POOLS || (EPF == 1 && EPI_B + RED_B + MB * 4 <= SCRATCH_B), "the gamma row sits behind the reduction scratch");
+    float gam_pf = 0.f;
     auto load_epi = [&]() {
 #pragma unroll
         for (int i = 0; i < EPF; ++i) {
@@ -466,6 +471,7 @@ __global__ __launch_bounds__(64 * NW, NIMG == 1 ? (NW == 4 ? 2 : 1) : 1) void co
             else if constexpr (EPI == EPI_MASK) { if (e < 4 * MB && m0 + e % MB < A.Mout) v = A.bnin[(e / MB) * A.Mout + m0 + e % MB]; }
             epi_pf[i] = v;
         }
+        if constexpr (POOLS) { if (A.pool_out && tid < MB && m0 + tid < A.Mout) gam_pf = A.pool_gamma[A.m_off + m0 + tid]; }
     };
     int g = 0;
 #if defined(BX_DBG) && (BX_DBG == 6 || BX_DBG == 7)      // timing experiments: prologue + epilogue only (6), prologue only (7)
@@ -535,6 +541,8 @@ __global__ __launch_bounds__(64 * NW, NIMG == 1 ? (NW == 4 ? 2 : 1) : 1) void co
 #pragma unroll
         for (int i = 0; i < EPF; ++i) { const int e = tid + i * NTHR; if (e < EPN) epi[e] = epi_pf[i]; }     // (requested before the last tap row)
     }
+    float* const gam = reinterpret_cast<float*>(WTs + EPI_B + RED_B);                  // POOLS: [MB]
+    if constexpr (POOLS) { if (tid < MB) gam[tid] = gam_pf; }
     __syncthreads();
     float s1[MTW][ACC], s2[MTW][ACC];
 #pragma unroll
@@ -583,6 +591,33 @@ __global__ __launch_bounds__(64 * NW, NIMG == 1 ? (NW == 4 ? 2 : 1) : 1) void co
                 }
                 if (valid) sta4<AT>(reinterpret_cast<AT*>(A.out) + pix * A.Mout + m, make_float4(v[0], v[1], v[2], v[3]));
             }
+        }
+    }
+    if constexpr (POOLS) {
+        if (A.pool_out) {         // launch-uniform.  z = acc + bias: the same fp32 add as above, the values as stored
+            // vertical pair: rows 2 wave, 2 wave + 1 are this lane's two pixel rows; horizontal pair: pixel j in adjacent lanes
+            const int Hp = A.Ho >> 1, Wp = A.Wo >> 1, yo = (y0 >> 1) + wave, xo = (x0 >> 1) + (j >> 1);
+            // a pooled pixel inside (Hp, Wp) has all four sources inside the image
+            const bool pst = (j & 1) == 0 && yo < Hp && xo < Wp;
+#pragma unroll
+            for (int mt = 0; mt < MTW; ++mt)
+#pragma unroll
+                for (int q = 0; q < QUADS; ++q) {
+                    const int ml = mt * MT + 8 * q + 4 * h, m = m0 + ml;
+                    const float4 bs4 = ld4(epi + ml), gm4 = ld4(gam + ml);
+                    const float bs[4] = {bs4.x, bs4.y, bs4.z, bs4.w}, gm[4] = {gm4.x, gm4.y, gm4.z, gm4.w};
+                    float e[4];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const float t0 = acc[mt][0][4 * q + k] + bs[k], t1 = acc[mt][1][4 * q + k] + bs[k];
+                        const float ev = gm[k] < 0.f ? fminf(t0, t1) : fmaxf(t0, t1);
+                        const float eo = __shfl_xor(ev, 1, 64);
+                        e[k] = gm[k] < 0.f ? fminf(ev, eo) : fmaxf(ev, eo);
+                    }
+                    if (pst && m < A.Mout)
+                        sta4<AT>(reinterpret_cast<AT*>(A.pool_out) + (((size_t)b * Hp + yo) * Wp + xo) * A.Mout + m,
+                                 make_float4(e[0], e[1], e[2], e[3]));
+                }
         }
     }
     if constexpr (EPI != EPI_RAW) {
@@ -1031,6 +1066,19 @@ __global__ __launch_bounds__(kBlock, bt_per_cu(CT, FDW)) void conv_bt_k(const Ig
     const int m4 = M2 ? 4 * (kg & 1) : 4 * kg, dx = M2 ? kg >> 1 : 0;
     float4 bias = make_float4(0.f, 0.f, 0.f, 0.f);
     if (EPI == EPI_FWD && m4 < A.Mout) bias = ld4(A.bias + A.m_off + m4);
+    // pooled output (IgemmArgs::pool_out; fp32 storage): rows 2 wave, 2 wave + 1 of the tile are this wave's, so every 2x2
+    // window lies in one wave.  Bit k of pmin: channel m4 + k takes the window MINIMUM of z (gamma < 0; +-0 take the maximum).
+    // Not in the 32-K form: it has at most 16 output channels, and no block in front of a pool narrows (the launcher clears
+    // pool_out).  Carrying the dead code there changed which of that kernel's `s2 += u * u` hipcc contracts into fmas -- the
+    // layer's variance, and every number behind it, one ulp away from what the kernel computed before.
+    constexpr bool POOLS = EPI == EPI_FWD && AMODE == A_NORMAL && sizeof(AT) == 4 && CT != 32;
+    int pmin = 0;
+    if constexpr (POOLS) {
+        if (A.pool_out && m4 < A.Mout) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) pmin |= (A.pool_gamma[A.m_off + m4 + k] < 0.f ? 1 : 0) << k;
+        }
+    }
 
     // ---- staging set-up: thread serves channel octet o of pixels P_k ----
     const int o = tid % OCT, c8 = 8 * o;
@@ -1389,6 +1437,29 @@ __global__ __launch_bounds__(kBlock, bt_per_cu(CT, FDW)) void conv_bt_k(const Ig
                 }
             }
             if (valid) sta4<AT>(reinterpret_cast<AT*>(A.out) + tbase + ooff[nt], make_float4(v[0], v[1], v[2], v[3]));
+        }
+        if constexpr (POOLS) {
+            if (A.pool_out) {         // launch-uniform.  z = acc + bias: the same fp32 add as above, the values as stored
+                const int Hp = A.Ho >> 1, Wp = A.Wo >> 1, yo = (y0 >> 1) + wave;
+                const float bs[4] = {bias.x, bias.y, bias.z, bias.w};
+                auto ext = [&](float p, float q, int k) { return (pmin >> k) & 1 ? fminf(p, q) : fmaxf(p, q); };
+#pragma unroll
+                for (int hw = 0; hw < (M2 ? 1 : 2); ++hw) {
+                    // vertical pair: pixel groups (row 0, row 1) of this lane; horizontal pair: the two-pixel form keeps pixel
+                    // 2 px + dx in lanes l and l ^ 32, the one-pixel form pixel 16 hw + px in adjacent lanes
+                    const int n0 = M2 ? 0 : hw, n1 = M2 ? 1 : 2 + hw;
+                    float e[4];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) e[k] = ext(acc[n0][k] + bs[k], acc[n1][k] + bs[k], k);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) e[k] = ext(e[k], __shfl_xor(e[k], M2 ? 32 : 1, 64), k);
+                    const int xo = (x0 >> 1) + (M2 ? px : 8 * hw + (px >> 1));
+                    // a pooled pixel inside (Hp, Wp) has all four sources inside the image
+                    if ((M2 ? dx == 0 : (px & 1) == 0) && yo < Hp && xo < Wp && m4 < A.Mout)
+                        sta4<AT>(reinterpret_cast<AT*>(A.pool_out) + (((size_t)b * Hp + yo) * Wp + xo) * A.Mout + m4,
+                                 make_float4(e[0], e[1], e[2], e[3]));
+                }
+            }
         }
         cur = nxt;
         __syncthreads();

@@ -29,38 +29,51 @@ struct FinDesc {
     float* dgamma; float* dbeta;                                  // backward
 };
 
-// forward: column sums (s = sum z, q = sum z^2) of channel c -> (a, b, mean, rstd) and the moving-statistics update
+// forward: column sums (s = sum z, q = sum z^2) of channel c -> (a, b, mean, rstd) and the moving-statistics update.
+// The value form takes the channel's gamma / beta / moving statistics already loaded: the finalize LAUNCHES request them
+// before the column sums, so the tail of the kernel is arithmetic and stores only (one memory round trip, not two)
 __device__ __forceinline__ void bn_fwd_finalize_write(double s, double q, double count, int C, int c, float* __restrict__ bn,
-                                                      const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                      float gamma_c, float beta_c, float mm_c, float mv_c,
                                                       float* __restrict__ mm, float* __restrict__ mv, float eps, float momentum,
                                                       int unbiased) {
     const double mean = s / count;
     double var = q / count - mean * mean;
     if (var < 0) var = 0;
     const double rstd = 1.0 / sqrt(var + (double)eps);
-    const double a = (double)gamma[c] * rstd;
+    const double a = (double)gamma_c * rstd;
     bn[BN_A * C + c] = (float)a;
-    bn[BN_B * C + c] = (float)((double)beta[c] - mean * a);
+    bn[BN_B * C + c] = (float)((double)beta_c - mean * a);
     bn[BN_MEAN * C + c] = (float)mean;
     bn[BN_RSTD * C + c] = (float)rstd;
     const double m = momentum;
     const double uv = (unbiased && count > 1) ? var * (count / (count - 1.0)) : var;
-    mm[c] = (float)((double)mm[c] * m + mean * (1.0 - m));
-    mv[c] = (float)((double)mv[c] * m + uv * (1.0 - m));
+    mm[c] = (float)((double)mm_c * m + mean * (1.0 - m));
+    mv[c] = (float)((double)mv_c * m + uv * (1.0 - m));
+}
+__device__ __forceinline__ void bn_fwd_finalize_write(double s, double q, double count, int C, int c, float* __restrict__ bn,
+                                                      const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                      float* __restrict__ mm, float* __restrict__ mv, float eps, float momentum,
+                                                      int unbiased) {
+    bn_fwd_finalize_write(s, q, count, C, c, bn, gamma[c], beta[c], mm[c], mv[c], mm, mv, eps, momentum, unbiased);
 }
 
 // backward: partial sums (s = sum g', q = sum g' xhat) of channel c -> dbeta, dgamma, the record's c1, c2 and the two-fma
-// form of the BN-backward transform (common.hpp)
+// form of the BN-backward transform (common.hpp).  Value form: gamma and the record's mean / rstd already loaded (see above)
 __device__ __forceinline__ void bn_bwd_finalize_write(double s, double q, double count, int C, int c, float* __restrict__ bn,
-                                                      const float* __restrict__ gamma, float* __restrict__ dgamma,
+                                                      float gamma_c, float mean_c, float rstd_c, float* __restrict__ dgamma,
                                                       float* __restrict__ dbeta) {
     dbeta[c] = (float)s;
     dgamma[c] = (float)q;
     const double c1 = s / count, c2 = q / count;
-    const double rstd = (double)bn[BN_RSTD * C + c], mean = (double)bn[BN_MEAN * C + c];
-    const double ga = (double)gamma[c] * rstd, gb = -ga * rstd * c2, gd = -ga * c1 - gb * mean;
+    const double rstd = (double)rstd_c, mean = (double)mean_c;
+    const double ga = (double)gamma_c * rstd, gb = -ga * rstd * c2, gd = -ga * c1 - gb * mean;
     bn[BN_C1 * C + c] = (float)c1; bn[BN_C2 * C + c] = (float)c2;
     bn[BN_GA * C + c] = (float)ga; bn[BN_GB * C + c] = (float)gb; bn[BN_GD * C + c] = (float)gd;
+}
+__device__ __forceinline__ void bn_bwd_finalize_write(double s, double q, double count, int C, int c, float* __restrict__ bn,
+                                                      const float* __restrict__ gamma, float* __restrict__ dgamma,
+                                                      float* __restrict__ dbeta) {
+    bn_bwd_finalize_write(s, q, count, C, c, bn, gamma[c], bn[BN_MEAN * C + c], bn[BN_RSTD * C + c], dgamma, dbeta);
 }
 
 // a partial-row element that another block of the SAME launch may read: write-through

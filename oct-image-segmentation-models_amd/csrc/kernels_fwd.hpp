@@ -205,8 +205,11 @@ static __global__ __launch_bounds__(kBlock) void bn_fwd_finalize_k(const BnFinAr
     __shared__ double sh[8];
     const int c = blockIdx.x;
     double s, q;
+    // the writing thread's parameters and moving statistics are requested in front of the column sums, not behind them
+    float ga = 0.f, be = 0.f, mmc = 0.f, mvc = 0.f;
+    if (threadIdx.x == 0) { ga = A.gamma[c]; be = A.beta[c]; mmc = A.mm[c]; mvc = A.mv[c]; }
     column_sums_f64(A.part, A.nblk, A.C, c, sh, s, q);
-    if (threadIdx.x == 0) bn_fwd_finalize_write(s, q, A.count, A.C, c, A.bn, A.gamma, A.beta, A.mm, A.mv, A.eps, A.momentum, A.unbiased);
+    if (threadIdx.x == 0) bn_fwd_finalize_write(s, q, A.count, A.C, c, A.bn, ga, be, mmc, mvc, A.mm, A.mv, A.eps, A.momentum, A.unbiased);
 }
 
 // inference: (a, b) from the moving statistics, one thread per channel of one layer

@@ -57,7 +57,12 @@ struct IgemmArgs {
     // slice's first input channel, and whether this launch also writes the bias-gradient column sums
     const void* dw_x; const float* dw_ab; float* dw_part; int dw_Cin, dw_ci_off, dw_bias;
     FinDesc fin;                                 // conv_bt_k: the statistics this launch emits (EPI_FWD: of its own output;
-                                                 // EPI_MASK: the BN-backward sums of the producer) are finalized by its last block
+                                                 // EPI_MASK: the BN-backward sums of the producer) are finalized by its last block    // EPI_FWD, fp32 storage, bf16-pipe kernels whose waves hold both rows of a 2x2 window (conv_bt_k, 8 / 16 K; conv_bx_k with two
+    // rows per wave): the launch also writes the max-pooled tensor -- as RAW extrema of z.  y = relu(fma(a, z, b)) is monotone
+    // in z with the direction of sign(a) = sign(gamma), so max over the window of y == relu(fma(a, m, b)) bit for bit with
+    // m = the window's max of z where gamma >= 0 and its min where gamma < 0; the consumers apply (a, b) on load (F_AFF).
+    // pool_out: (B,Ho/2,Wo/2,Mout) or nullptr (the launchers clear it for a kernel form that cannot); pool_gamma: Mout floats
+    void* pool_out; const float* pool_gamma;
 };
 
 template <int SHAPE> struct MfmaShape;

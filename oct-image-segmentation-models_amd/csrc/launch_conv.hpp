@@ -90,6 +90,9 @@ int launch_thin8(IgemmArgs a, const LaunchCtx& c, int* rows) {
     return 0;
 }
 
+// bytes of the pooled tensor a forward launch writes beside z (IgemmArgs::pool_out; fp32 storage only)
+inline double pool_out_bytes(const IgemmArgs& a, int B) { return a.pool_out ? (double)B * (a.Ho / 2) * (a.Wo / 2) * a.Mout * 4 : 0.0; }
+
 // ---- bf16-pipe implicit GEMM (kernels_bx.hpp): NS = 3 split products in fp32 mode, 1 in bf16 mode ----
 // GB: the input is a masked gradient g' whose BN-backward transform is applied while it is staged (backward-data only)
 template <int KH, int AMODE, int EPI, int TH, int MB, int NW, int NIMG = 2>
@@ -97,8 +100,11 @@ int launch_bx_nw(IgemmArgs a, const LaunchCtx& c, int* rows) {
     a.tiles_x = cdiv(a.Wo, 32); a.tiles = a.tiles_x * cdiv(a.Ho, TH);
     dim3 grid(a.tiles, cdiv(a.Mout, MB), c.B), block(64 * NW);
     const bool gb = a.gb_z != nullptr;
+    // the pooled tensor from the epilogue: forward 3x3 launches with two tile rows per wave, fp32 storage (conv_bx_k POOLS)
+    if (!(EPI == EPI_FWD && AMODE == A_NORMAL && KH == 3 && TH / NW == 2) || a.act_bf16) a.pool_out = nullptr;
+    if (a.pool_out && c.pooled) *c.pooled = true;
     char nm[80]; snprintf(nm, sizeof nm, "conv_bx_k<%d,%d,%d,%d,%d,%d,%d,%s%s%s>", KH, AMODE, EPI, TH, MB, a.act_bf16 ? 1 : 3, NW, AT_NAME(a.act_bf16), gb ? ",gb" : "", NIMG == 1 ? ",1img" : "");
-    ProfScope ps(c.s, nm, c.layer, c.flops, c.bytes);
+    ProfScope ps(c.s, nm, c.layer, c.flops, c.bytes + pool_out_bytes(a, c.B));
     *rows = c.B * a.tiles;
     if constexpr (AMODE == A_UPF && EPI == EPI_FWD && NIMG == 2) {
         if (a.flags & F_DROP) {
@@ -162,8 +168,11 @@ int launch_bt(IgemmArgs a, const LaunchCtx& c, int* rows) {
     const int bf = a.act_bf16 ? 1 : 0;
     const bool m2 = a.bt_m2 && pipe_fit(a.Cin, a.Mout, a.m_off, a.flags & F_TWO, a.C0, AMODE).m2;
     const bool gb = a.gb_z != nullptr;
+    // the pooled tensor from the epilogue: the forward 3x3 forms with 8 or 16 K channels, fp32 storage (conv_bt_k POOLS)
+    if (!(EPI == EPI_FWD && AMODE == A_NORMAL) || bf || a.Cin == 32) a.pool_out = nullptr;
+    if (a.pool_out && c.pooled) *c.pooled = true;
     char nm[72]; snprintf(nm, sizeof nm, "conv_bt_k<%d,%d,%d,%d,%d,%s%s%s%s>", KH, AMODE, EPI, a.Cin, bf ? 1 : 3, AT_NAME(bf), m2 ? ",2px" : "", gb ? ",gb" : "", fdw ? ",dw" : "");
-    ProfScope ps(c.s, nm, c.layer, c.flops, c.bytes);
+    ProfScope ps(c.s, nm, c.layer, c.flops, c.bytes + pool_out_bytes(a, c.B));
     if (a.bt_m2 && !m2) return fail(-3, "conv_bt_k: weights were prepared in the two-pixel form for a launch that cannot use it");
     if (gb && EPI == EPI_FWD) return fail(-3, "conv_bt_k: the BN-backward transform on load is only built for backward-data launches");
     *rows = nblk;

@@ -245,6 +245,9 @@ struct oct_unet {
     Plan plan;
     float* params; float* grads; float* state;
     std::vector<void*> pooled, gpooled;    // per encoder level (activation storage type)
+    std::vector<char> pool_raw;            // per encoder level, set by every forward: pooled[level] holds the window extrema of the
+                                           // producer's RAW z (written by its conv launch; consumers apply its BN record on load)
+                                           // instead of pool_fwd_k's activated maxima
     std::vector<BwdRoute> route;           // per layer: refilled at the top of every backward (options and B may change between calls)
     float* stat_part = nullptr;            // BN statistic partials (fwd and bwd share it: stream-ordered)
     unsigned* fin_counters = nullptr;      // [2 * layers] arrival counters of the in-launch finalizes (kernels_fin.hpp): zero between launches
@@ -304,7 +307,7 @@ size_t carve(const oct_unet_cfg& c, Plan& pl, oct_unet* h, char* base, const Opt
         const size_t n = B * (c.H >> (i + 1)) * (c.W >> (i + 1)) * ((size_t)c.start_neurons << i);
         void* p = (void*)take(n * esz);
         void* gp = c.training ? (void*)take(n * esz) : nullptr;
-        if (h) { h->pooled.push_back(p); h->gpooled.push_back(gp); }
+        if (h) { h->pooled.push_back(p); h->gpooled.push_back(gp); h->pool_raw.push_back(0); }
     }
     const int nblk_head = cdiv(c.H * c.W, kBlock);
     stat_max = std::max(stat_max, B * nblk_head * 2 * (size_t)c.start_neurons);
@@ -372,7 +375,10 @@ SrcDesc src_of(const oct_unet* h, int li, const void* x_in, int x_is_u8) {
     switch (l.src) {
         case SRC_INPUT: d.x0 = x_in; d.ab0 = nullptr; d.C0 = l.cin; d.flags = x_is_u8 ? F_U8 : 0; break;
         case SRC_PREV: case SRC_HEAD: { const Layer& p = h->plan.L[li - 1]; d.x0 = p.z; d.ab0 = p.bn; d.C0 = p.cout; d.flags = F_AFF; break; }
-        case SRC_POOL: d.x0 = h->pooled[l.level - 1]; d.ab0 = nullptr; d.C0 = l.cin; d.flags = 0; break;
+        case SRC_POOL: {       // a raw level (pool_raw): extrema of the producer's z, activated on load like a SRC_PREV input
+            const bool raw = h->pool_raw[l.level - 1] != 0;
+            d.x0 = h->pooled[l.level - 1]; d.ab0 = raw ? h->plan.L[li - 1].bn : nullptr; d.C0 = l.cin; d.flags = raw ? F_AFF : 0; break;
+        }
         case SRC_UP: { const Layer& p = h->plan.L[li - 1]; d.x0 = p.z; d.ab0 = p.bn; d.C0 = p.cout; d.flags = F_AFF | F_UP; break; }
         case SRC_CONCAT: {
             const Layer& p = h->plan.L[li - 1]; const Layer& k = h->plan.L[l.skip_from];
@@ -419,11 +425,18 @@ int conv_forward(oct_unet* h, int li, const void* x_in, int x_is_u8, int B, int 
         g.Ho = l.H; g.Wo = l.W; g.Hi = l.src == SRC_UP ? l.H / 2 : l.H; g.Wi = l.src == SRC_UP ? l.W / 2 : l.W;
         g.part = a.part; g.drop = a.drop; g.act_bf16 = h->cfg.dtype;
         g.wbx = l.wbx_f; g.wbx_M = l.cout; g.wbt = l.wbt_f; g.bt_m2 = l.bt_m2_f;
-        const LaunchCtx lc{&h->opt, B, s, l.name, fl, by};
+        // the block in front of a max-pool: the launch writes the pooled tensor too where its kernel form can (fp32 storage)
+        const bool feeds_pool = li + 1 < (int)h->plan.L.size() && h->plan.L[li + 1].src == SRC_POOL;
+        bool pooled = false;
+        if (feeds_pool && h->opt.pool_in_epilogue && !h->cfg.dtype && l.has_bn) {
+            g.pool_out = h->pooled[h->plan.L[li + 1].level - 1]; g.pool_gamma = h->params + l.gamma_off;
+        }
+        const LaunchCtx lc{&h->opt, B, s, l.name, fl, by, &pooled};
         const ConvRoute rt = conv_route(g, l.src == SRC_UP ? A_UPF : A_NORMAL, h->opt);
         if (training && fin_ok(h, l) && rt == ROUTE_BT) { g.fin = fin_desc(h, li, 0, B); fin_in_launch = true; }
         rc = l.src == SRC_UP ? launch_igemm<2, A_UPF, EPI_FWD>(g, rt, lc, &stat_rows)
                              : launch_igemm<3, A_NORMAL, EPI_FWD>(g, rt, lc, &stat_rows);
+        if (feeds_pool) h->pool_raw[h->plan.L[li + 1].level - 1] = pooled ? 1 : 0;
     } else if (l.src == SRC_INPUT && l.cin == 1 && l.cout == 8 && l.kh == 3) {   // the real first layer: persistent streaming kernel
         const int tx = cdiv(l.W, 128), tiles = tx * cdiv(l.H, 8), total = B * tiles;
         const int grid = cap_grid(std::min(total, 2048), h->opt);      // <= B*ceil(H/2)*ceil(W/32) statistic rows guaranteed by carve()
@@ -561,7 +574,9 @@ int forward_stages(oct_unet* h, const void* x, int x_is_u8, int B, int training,
     Plan& pl = h->plan;
     for (int li = li0; li < li1; ++li) {
         Layer& l = pl.L[li];
-        if (l.src == SRC_POOL) {  // pool the previous block's output (BN+ReLU applied on load)
+        // pool the previous block's output (BN+ReLU applied on load) -- unless its conv launch has written the raw window
+        // extrema already (pool_raw: set by conv_forward of block li - 1 just before)
+        if (l.src == SRC_POOL && !h->pool_raw[l.level - 1]) {
             const Layer& p = pl.L[li - 1];
             const size_t n = (size_t)B * (p.H / 2) * (p.W / 2) * (p.cout / 4);
             const int grid = (int)std::min<size_t>((n + kBlock - 1) / kBlock, 8192);
@@ -1358,6 +1373,7 @@ const Opt k_opts[] = {
     {"dwbx_enable", &Options::dwbx_enable, 0, 1}, {"persistent_max_blocks", &Options::max_blocks, 0, 1 << 20},
     {"bx_two_blocks", &Options::bx_two_blocks, 0, 1}, {"fork_on_launch", &Options::fork_on_launch, 0, 1},
     {"event_sysfence", &Options::event_sysfence, 0, 1}, {"dw_fork_group", &Options::dw_fork_group, 1, 8}, {"fuse_bn_apply16", &Options::fuse_bn_apply16, 0, 1},
+    {"pool_in_epilogue", &Options::pool_in_epilogue, 0, 1},
 };
 const Opt* find_opt(const char* name) {
     for (const Opt& o : k_opts) if (!strcmp(name, o.name)) return &o;
