@@ -132,6 +132,11 @@ __device__ inline void column_sums_f64(const float* __restrict__ part, int rows,
 }
 
 __device__ inline float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+// A wave-uniform value that no kernel of the launch writes (a weight, a bias, a row of a BN record), read through the
+// constant address space.  A plain load of it from inside a loop that also stores to global memory cannot be hoisted or
+// given to the scalar unit -- the store might alias it -- so it becomes a per-lane global load in every iteration, and the
+// s_waitcnt vmcnt(0) in front of its first use also waits for every load the kernel had requested ahead on purpose.
+__device__ __forceinline__ float ldc(const float* p) { return *(const __attribute__((address_space(4))) float*)p; }
 __device__ inline void st4(float* p, const float4& v) { *reinterpret_cast<float4*>(p) = v; }
 
 // ---- activation storage type: float (dtype 0) or bfloat16 (dtype 1: bf16 STORAGE of activations and activation

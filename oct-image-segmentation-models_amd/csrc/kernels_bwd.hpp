@@ -278,28 +278,14 @@ __global__ __launch_bounds__(kBlock) void head_bwd_k(const HeadBwdArgs A) {
     const float scale = (1.f - A.focal_w) * (A.macro ? A.loss_scale / (float)(A.B * C) : A.loss_scale);
     const float fscale = A.focal_w * A.loss_scale * A.inv_count;
 
-    const AT* const zbase = reinterpret_cast<const AT*>(A.z) + (size_t)b * A.HW * CIN;
-    auto pix_of = [&](int chunk) { const int px = chunk * kBlock + threadIdx.x; return px < A.HW ? px : 0; };
-    float zn[CIN];
-    int labn = 0;
-    if ((int)blockIdx.x * kBlock < A.HW) {
-        const int q = pix_of(blockIdx.x);
-        head_load<CIN, AT>(zbase + (size_t)q * CIN, zn);
-        labn = A.labels[(size_t)b * A.HW + q];
-    }
+    HeadQueue<CIN, kHeadBwdAhead, AT> hq(reinterpret_cast<const AT*>(A.z) + (size_t)b * A.HW * CIN, A.labels + (size_t)b * A.HW, A.HW);
+    hq.fill(blockIdx.x, gridDim.x);
     for (int chunk = blockIdx.x; chunk * kBlock < A.HW; chunk += gridDim.x) {
         const int px = chunk * kBlock + threadIdx.x;
         const bool valid = px < A.HW;
         const size_t pix = (size_t)b * A.HW + (valid ? px : 0);
         float y[CIN], zr[CIN], p[C];
-#pragma unroll
-        for (int i = 0; i < CIN; ++i) zr[i] = zn[i];
-        const int lab = labn;
-        if ((chunk + (int)gridDim.x) * kBlock < A.HW) {          // the next chunk's pixel is requested before this one is used
-            const int q = pix_of(chunk + gridDim.x);
-            head_load<CIN, AT>(zbase + (size_t)q * CIN, zn);
-            labn = A.labels[(size_t)b * A.HW + q];
-        }
+        const int lab = hq.pop(zr, chunk + kHeadBwdAhead * (int)gridDim.x);     // later chunks' pixels are requested before this one is used
         head_logits<C, CIN>(A.bn, A.w, A.bias, y, zr, p);
         float dp[C], dot = 0.f;
 #pragma unroll
@@ -312,7 +298,7 @@ __global__ __launch_bounds__(kBlock) void head_bwd_k(const HeadBwdArgs A) {
                 const bool inr = p[c] >= kFocalEps && p[c] <= 1.f - kFocalEps;
                 if (inr || !A.focal_clip_mod) {
                     const float pc = fminf(fmaxf(p[c], kFocalEps), 1.f - kFocalEps);
-                    const float q = 1.f - p[c], cw = A.focal_cw ? A.focal_cw[c] : 1.f, qg1 = powf(q, A.focal_gamma - 1.f);
+                    const float q = 1.f - p[c], cw = A.focal_cw ? ldc(A.focal_cw + c) : 1.f, qg1 = powf(q, A.focal_gamma - 1.f);
                     dp[c] += fscale * cw * (A.focal_gamma * qg1 * logf(pc) - (inr ? qg1 * q / pc : 0.f));
                 }
             }
@@ -353,9 +339,9 @@ __global__ __launch_bounds__(kBlock) void head_bwd_k(const HeadBwdArgs A) {
         for (int i = 0; i < CIN; ++i) {
             float a = 0.f;
 #pragma unroll
-            for (int c = 0; c < C; ++c) { a = fmaf(A.w[i * C + c], dl[c], a); wv[i * C + c] = fmaf(y[i], dl[c], wv[i * C + c]); }
+            for (int c = 0; c < C; ++c) { a = fmaf(ldc(A.w + i * C + c), dl[c], a); wv[i * C + c] = fmaf(y[i], dl[c], wv[i * C + c]); }
             a = (valid && y[i] > 0.f) ? a : 0.f;
-            const float xh = (zr[i] - A.bn[BN_MEAN * CIN + i]) * A.bn[BN_RSTD * CIN + i];
+            const float xh = (zr[i] - ldc(A.bn + BN_MEAN * CIN + i)) * ldc(A.bn + BN_RSTD * CIN + i);
             g[i] = a; s1[i] += a; s2[i] += a * xh;
         }
         if (valid) {
@@ -484,9 +470,9 @@ __global__ __launch_bounds__(kBlock) void conv_bwd_w_k(const ConvBwdWArgs A) {
 // operation order): nothing else consumes this layer's dz -- the input image has no gradient -- so the 3-tensor pass
 // over the largest tensor of the net disappears from the backward-data chain (66 us of a 4.2 ms step).
 template <typename AT, bool FUSE>
-__global__ __launch_bounds__(kBlock) void conv_dw_first_k(const ConvBwdWArgs A, int tiles_x, int tiles, int total_tiles) {
-    constexpr int TH = 8, TW = 128, XH = TH + 2, XW = TW + 2;
-    __shared__ float Xs[XH * XW];
+__global__ __launch_bounds__(kBlock, 3) void conv_dw_first_k(const ConvBwdWArgs A, int tiles_x, int tiles, int total_tiles) {
+    constexpr int TH = FirstTileRaw::TH, TW = FirstTileRaw::TW, XH = FirstTileRaw::XH, XW = FirstTileRaw::XW, NG = TW / 32;
+    __shared__ float Xs2[2][XH * XW];     // two image tiles: the walk writes tile t+1 while tile t is still being read
     __shared__ float red[256];
     __shared__ float lut_s[256];          // the float32(i/255.0) table, copied once: lookups become LDS reads
     const int t = threadIdx.x, xl = t & 31, row = t >> 5;
@@ -497,44 +483,53 @@ __global__ __launch_bounds__(kBlock) void conv_dw_first_k(const ConvBwdWArgs A, 
 #pragma unroll
     for (int k = 0; k < 16; ++k) acc1[k] = 0.f;
     const bool u8 = (A.flags & F_U8) != 0;
-    for (int tl = blockIdx.x; tl < total_tiles; tl += gridDim.x) {
+    // the image tile is requested one tile ahead and parked in registers over the previous tile's sums (FirstTileRaw); one
+    // barrier per tile; a block without a tile requests nothing
+    FirstTileRaw nx;
+    const bool any = (int)blockIdx.x < total_tiles;
+    if (any) nx.request(A.x0, u8, blockIdx.x, tiles, tiles_x, A.H, A.W);
+    __syncthreads();                      // lut_s
+    if (any) nx.store(Xs2[0], lut_s, u8);
+    __syncthreads();
+    int cur = 0;
+    for (int tl = blockIdx.x; tl < total_tiles; tl += gridDim.x, cur ^= 1) {
         const int b = tl / tiles, tile = tl % tiles;
         const int x0 = (tile % tiles_x) * TW, y0 = (tile / tiles_x) * TH;
-        __syncthreads();
-        {   // all image loads of the tile are issued before any is used (the /255 table lookup is a dependent access)
-            constexpr int NS = (XH * XW + kBlock - 1) / kBlock;
-            unsigned int rb[NS]; float rf[NS]; bool in[NS];
-#pragma unroll
-            for (int k = 0; k < NS; ++k) {
-                const int i = t + k * kBlock, cy = i / XW, cx = i % XW, iy = y0 + cy - 1, ix = x0 + cx - 1;
-                in[k] = i < XH * XW && iy >= 0 && iy < A.H && ix >= 0 && ix < A.W;
-                const size_t pix = in[k] ? ((size_t)b * A.H + iy) * A.W + ix : 0;
-                rb[k] = 0; rf[k] = 0.f;
-                if (in[k]) { if (u8) rb[k] = reinterpret_cast<const unsigned char*>(A.x0)[pix]; else rf[k] = reinterpret_cast<const float*>(A.x0)[pix]; }
-            }
-#pragma unroll
-            for (int k = 0; k < NS; ++k) {
-                const int i = t + k * kBlock;
-                if (i < XH * XW) Xs[i] = in[k] ? (u8 ? lut_s[rb[k]] : rf[k]) : 0.f;
-            }
-        }
-        __syncthreads();
+        const float* __restrict__ Xs = Xs2[cur];
+        const bool more = tl + (int)gridDim.x < total_tiles;
+        if (more) nx.request(A.x0, u8, tl + gridDim.x, tiles, tiles_x, A.H, A.W);
         const int y = y0 + row;
+        // a thread's NG pixels: the dz (and z) quads of pixel k + AH are requested before pixel k's sums, so AH pixels' loads
+        // are in flight beside the arithmetic (all NG at once would take 174 registers and with them the third block per
+        // CU).  The loads are unconditional -- a pixel outside the image reads element 0 and is not used -- so that no
+        // branch stands between them.
+        constexpr int AH = 2;
+        float4 dq[NG][2]; [[maybe_unused]] float4 zq[NG][2];
+        bool ok[NG];
+        auto request = [&](int k) {
+            const int x = x0 + xl + 32 * k;
+            ok[k] = y < A.H && x < A.W;
+            const size_t e8 = ok[k] ? (((size_t)b * A.H + y) * A.W + x) * 8 : 0;
+            const AT* dp = reinterpret_cast<const AT*>(A.dz) + e8;
+            dq[k][0] = lda4<AT>(dp); dq[k][1] = lda4<AT>(dp + 4);
+            if constexpr (FUSE) {
+                const AT* zp = reinterpret_cast<const AT*>(A.zf) + e8;
+                zq[k][0] = lda4<AT>(zp); zq[k][1] = lda4<AT>(zp + 4);
+            }
+        };
 #pragma unroll
-        for (int k = 0; k < TW / 32; ++k) {
-            const int xx = xl + 32 * k, x = x0 + xx;
-            if (y < A.H && x < A.W) {
-                const size_t e8 = (((size_t)b * A.H + y) * A.W + x) * 8;
-                const AT* dp = reinterpret_cast<const AT*>(A.dz) + e8;
-                const float4 d0 = lda4<AT>(dp), d1 = lda4<AT>(dp + 4);
-                float d[8] = {d0.x, d0.y, d0.z, d0.w, d1.x, d1.y, d1.z, d1.w};
+        for (int k = 0; k < AH; ++k) request(k);
+#pragma unroll
+        for (int k = 0; k < NG; ++k) {
+            if (k + AH < NG) request(k + AH);
+            const int xx = xl + 32 * k;
+            if (ok[k]) {
+                float d[8] = {dq[k][0].x, dq[k][0].y, dq[k][0].z, dq[k][0].w, dq[k][1].x, dq[k][1].y, dq[k][1].z, dq[k][1].w};
                 if constexpr (FUSE) {
-                    const AT* zp = reinterpret_cast<const AT*>(A.zf) + e8;
-                    const float4 z0 = lda4<AT>(zp), z1 = lda4<AT>(zp + 4);
-                    const float zv[8] = {z0.x, z0.y, z0.z, z0.w, z1.x, z1.y, z1.z, z1.w};
+                    const float zv[8] = {zq[k][0].x, zq[k][0].y, zq[k][0].z, zq[k][0].w, zq[k][1].x, zq[k][1].y, zq[k][1].z, zq[k][1].w};
 #pragma unroll
                     for (int co = 0; co < 8; ++co) {      // bn_bwd_apply_k's expression; bf16 storage: dz is rounded as it would be stored
-                        const float o = bn_bwd_apply1(A.bnf[BN_GA * 8 + co], A.bnf[BN_GB * 8 + co], A.bnf[BN_GD * 8 + co], d[co], zv[co]);
+                        const float o = bn_bwd_apply1(ldc(A.bnf + BN_GA * 8 + co), ldc(A.bnf + BN_GB * 8 + co), ldc(A.bnf + BN_GD * 8 + co), d[co], zv[co]);
                         d[co] = dz_as_stored<AT>(o);
                         asm volatile("" : "+v"(d[co]));      // dz is a ROUNDED value (as if stored): its last product must not be
                                                              // contracted into the sums below
@@ -553,6 +548,8 @@ __global__ __launch_bounds__(kBlock) void conv_dw_first_k(const ConvBwdWArgs A, 
                 for (int co = 0; co < 8; ++co) acc1[8 + co] += d[co];
             }
         }
+        if (more) nx.store(Xs2[cur ^ 1], lut_s, u8);
+        __syncthreads();                  // tile t+1 is in place, and nobody reads tile t any more
     }
     float* out = A.part + (size_t)blockIdx.x * 80;
     block_reduce_store<64>(acc0, red, out, 64);

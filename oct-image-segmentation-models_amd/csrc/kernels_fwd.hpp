@@ -121,6 +121,39 @@ __global__ __launch_bounds__(kBlock) void conv_fwd_k(const ConvFwdArgs A) {
     }
 }
 
+// An image tile of the first layer (8 x 128 pixels and a one-pixel halo) on its way from global memory to LDS: request()
+// puts a thread's share of tile tl into registers, store() turns it into floats in an LDS buffer (the /255 table lookup is
+// a dependent access, so it happens here, behind the wait).  Between the two conv_dw_first_k (kernels_bwd.hpp) works on
+// the tile in front of it; conv_first_fwd_k below, two tiles per block at the benched shape, gains nothing from it
+//  and stages its tile in place.
+struct FirstTileRaw {
+    static constexpr int TH = 8, TW = 128, XH = TH + 2, XW = TW + 2, NS = (XH * XW + kBlock - 1) / kBlock;
+    unsigned int raw[NS];       // the byte, or the float's bits
+    unsigned int inm;           // bit k: element k lies inside the image
+    __device__ __forceinline__ void request(const void* __restrict__ x, bool u8, int tl, int tiles, int tiles_x, int H, int W) {
+        const int b = tl / tiles, tile = tl % tiles, x0 = (tile % tiles_x) * TW, y0 = (tile / tiles_x) * TH;
+        inm = 0;
+#pragma unroll
+        for (int k = 0; k < NS; ++k) {
+            const int i = (int)threadIdx.x + k * kBlock, cy = i / XW, cx = i % XW, iy = y0 + cy - 1, ix = x0 + cx - 1;
+            const bool in = i < XH * XW && iy >= 0 && iy < H && ix >= 0 && ix < W;
+            const size_t pix = in ? ((size_t)b * H + iy) * W + ix : 0;
+            raw[k] = 0;
+            if (in) {
+                if (u8) raw[k] = reinterpret_cast<const unsigned char*>(x)[pix]; else raw[k] = __float_as_uint(reinterpret_cast<const float*>(x)[pix]);
+                inm |= 1u << k;
+            }
+        }
+    }
+    __device__ __forceinline__ void store(float* __restrict__ Xs, const float* __restrict__ lut_s, bool u8) const {
+#pragma unroll
+        for (int k = 0; k < NS; ++k) {
+            const int i = (int)threadIdx.x + k * kBlock;
+            if (i < XH * XW) Xs[i] = (inm >> k & 1u) ? (u8 ? lut_s[raw[k]] : __uint_as_float(raw[k])) : 0.f;
+        }
+    }
+};
+
 // ---- first layer, the real configuration (1 input channel -- uint8 through the /255 table, or f32 --, 8 output
 // channels, 3x3).  Output-write bound (32 B/pixel): a PERSISTENT block walks 8 x 128 tiles, image tile in LDS, the 72
 // weights wave-uniform, 4 pixels per thread with fully coalesced 32 B stores; BN statistics stay in registers across
@@ -300,8 +333,8 @@ __device__ inline void softmax_complement(const float (&p)[C], float (&q)[C]) {
     }
 }
 
-// raw z of one pixel (CIN values) -> registers; split from the arithmetic so that the head kernels can request the next
-// chunk's pixel before they work on the current one (one chunk of software prefetch)
+// raw z of one pixel (CIN values) -> registers; split from the arithmetic so that the head kernels can request later
+// chunks' pixels before they work on the current one (HeadQueue)
 template <int CIN, typename AT>
 __device__ inline void head_load(const AT* __restrict__ zp, float (&zr)[CIN]) {
 #pragma unroll
@@ -311,17 +344,53 @@ __device__ inline void head_load(const AT* __restrict__ zp, float (&zr)[CIN]) {
     }
 }
 
+// The head kernels' chunk walk keeps D chunks requested ahead of the one in work: a thread's pixel (CIN raw values) and its
+// label byte sit in registers from D chunks before they are used, so a block has D x 256 x (CIN x 4 + 1) bytes in flight
+// while it computes.  pop() hands out the oldest entry and requests chunk `next` into the freed slot (nothing once the
+// walk runs past the image: the slot then keeps stale values that are never handed out).
+constexpr int kHeadFwdAhead = 1, kHeadBwdAhead = 1;
+template <int CIN, int D, typename AT>
+struct HeadQueue {
+    const AT* zb; const unsigned char* lb; int HW;
+    float zq[D][CIN]; int lq[D];
+    __device__ HeadQueue(const AT* z, const unsigned char* l, int hw) : zb(z), lb(l), HW(hw) {}
+    __device__ __forceinline__ void request(int d, int chunk) {
+        if (chunk * kBlock < HW) {
+            const int px = chunk * kBlock + (int)threadIdx.x, q = px < HW ? px : 0;
+            head_load<CIN, AT>(zb + (size_t)q * CIN, zq[d]);
+            if (lb) lq[d] = lb[q];
+        }
+    }
+    __device__ __forceinline__ void fill(int first, int stride) {
+#pragma unroll
+        for (int d = 0; d < D; ++d) { lq[d] = 0; request(d, first + d * stride); }
+    }
+    __device__ __forceinline__ int pop(float (&zr)[CIN], int next) {
+        const int lab = lq[0];
+#pragma unroll
+        for (int i = 0; i < CIN; ++i) zr[i] = zq[0][i];
+#pragma unroll
+        for (int d = 0; d + 1 < D; ++d) {
+            lq[d] = lq[d + 1];
+#pragma unroll
+            for (int i = 0; i < CIN; ++i) zq[d][i] = zq[d + 1][i];
+        }
+        request(D - 1, next);
+        return lab;
+    }
+};
+
 template <int C, int CIN>
 __device__ inline void head_logits(const float* __restrict__ ab, const float* __restrict__ w, const float* __restrict__ bias,
                                    float (&y)[CIN], const float (&zr)[CIN], float (&p)[C]) {
 #pragma unroll
-    for (int i = 0; i < CIN; ++i) y[i] = fmaxf(fmaf(ab[i], zr[i], ab[CIN + i]), 0.f);
+    for (int i = 0; i < CIN; ++i) y[i] = fmaxf(fmaf(ldc(ab + i), zr[i], ldc(ab + CIN + i)), 0.f);
     float mx = -3.4e38f;
 #pragma unroll
     for (int c = 0; c < C; ++c) {
-        float l = bias[c];
+        float l = ldc(bias + c);
 #pragma unroll
-        for (int i = 0; i < CIN; ++i) l = fmaf(y[i], w[i * C + c], l);
+        for (int i = 0; i < CIN; ++i) l = fmaf(y[i], ldc(w + i * C + c), l);
         p[c] = l; mx = fmaxf(mx, l);
     }
     float sum = 0.f;
@@ -342,12 +411,15 @@ __global__ __launch_bounds__(kBlock) void head_fwd_k(const HeadFwdArgs A) {
     float v[N];
 #pragma unroll
     for (int i = 0; i < N; ++i) v[i] = 0.f;
+    HeadQueue<CIN, kHeadFwdAhead, AT> hq(reinterpret_cast<const AT*>(A.z) + (size_t)b * A.HW * CIN,
+                                         A.labels ? A.labels + (size_t)b * A.HW : nullptr, A.HW);
+    hq.fill(blockIdx.x, gridDim.x);
     for (int chunk = blockIdx.x; chunk * kBlock < A.HW; chunk += gridDim.x) {
         const int px = chunk * kBlock + threadIdx.x;
         const bool valid = px < A.HW;
         const size_t pix = (size_t)b * A.HW + (valid ? px : 0);
         float y[CIN], zr[CIN], p[C];
-        head_load<CIN, AT>(reinterpret_cast<const AT*>(A.z) + pix * CIN, zr);   // (a chunk of prefetch was measured here: slower)
+        const int lab = hq.pop(zr, chunk + kHeadFwdAhead * (int)gridDim.x);     // this chunk's pixel; the one kHeadFwdAhead chunks on is requested
         head_logits<C, CIN>(A.ab, A.w, A.bias, y, zr, p);
         if (valid) {
             if (A.probs) {
@@ -361,7 +433,6 @@ __global__ __launch_bounds__(kBlock) void head_fwd_k(const HeadFwdArgs A) {
                 A.argmax[pix] = (unsigned char)am;
             }
             if (A.labels) {
-                const int lab = A.labels[pix];
 #pragma unroll
                 for (int c = 0; c < C; ++c) {
                     const float yv = lab == c ? 1.f : 0.f, ph = p[c] > 0.5f ? 1.f : 0.f;
@@ -406,38 +477,62 @@ struct DiceFinArgs {
     int bce_on;            // slot 5*C holds the BCE sum: its mean is over B*H*W*C
 };
 
+// v[j] += row k's J values at p0 for k = k0 .. in groups of R rows: the R x J loads of a group are independent and issued
+// together (one memory round trip), the additions stay in row order.  Returns the first row not taken.
+template <int R, int J>
+__device__ __forceinline__ int dice_rows(const float* __restrict__ p0, int N, int k, int nblk, double (&v)[J]) {
+    for (; k + R <= nblk; k += R) {
+        float t[R][J];
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+#pragma unroll
+            for (int j = 0; j < J; ++j) t[r][j] = p0[(size_t)(k + r) * N + j];
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+#pragma unroll
+            for (int j = 0; j < J; ++j) v[j] += t[r][j];
+    }
+    return k;
+}
+template <int J>
+__device__ __forceinline__ void dice_rows_all(const float* __restrict__ p0, int N, int nblk, double (&v)[J]) {
+    int k = dice_rows<32, J>(p0, N, 0, nblk, v);      // the benched step has 64 rows per image: two round trips
+    k = dice_rows<8, J>(p0, N, k, nblk, v);
+    dice_rows<1, J>(p0, N, k, nblk, v);
+}
+
+// One block.  Thread i % 256 owns pair i = (b, c).  The slot-5C sum (focal / BCE) of image b belongs to the owner of (b, 0)
+// and is a chain over the image's rows as long as the five Dice chains together are wide; while pairs leave threads idle
+// (B*C + b < 256) thread 255 - b -- the far end of the block, another wave -- forms it beside the owners and hands it over
+// through sh[7].  Every sum keeps its order of additions, so the outputs do not depend on who formed them.
 static __global__ __launch_bounds__(kBlock) void dice_finalize_k(const DiceFinArgs A) {
     __shared__ double sh[8][kBlock];
     double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // score_macro, coef_macro, I, T, P, Ih, Ph (micro sums), focal sum
     const int n = A.B * A.C;
+    const int hb = kBlock - 1 - (int)threadIdx.x;          // the image whose slot-5C sum this thread forms as a helper ...
+    const bool helper = hb < A.B && n + hb < kBlock;       // ... if it owns no pair (then n < 256: one pair per owner at most)
+    double hs[1] = {0};
+    if (helper) dice_rows_all<1>(A.part + (size_t)hb * A.nblk * A.N + A.C * kDiceVals, A.N, A.nblk, hs);
     for (int i = threadIdx.x; i < n; i += kBlock) {
         const int b = i / A.C, c = i % A.C;
         double v[kDiceVals] = {0, 0, 0, 0, 0};
         const float* p0 = A.part + (size_t)b * A.nblk * A.N + c * kDiceVals;
-        int k = 0;
-        for (; k + 8 <= A.nblk; k += 8) {          // 8 rows' loads issued together (one memory round trip), fixed order
-            float t[8][kDiceVals];
-#pragma unroll
-            for (int r = 0; r < 8; ++r)
-#pragma unroll
-                for (int j = 0; j < kDiceVals; ++j) t[r][j] = p0[(size_t)(k + r) * A.N + j];
-#pragma unroll
-            for (int r = 0; r < 8; ++r)
-#pragma unroll
-                for (int j = 0; j < kDiceVals; ++j) v[j] += t[r][j];
-        }
-        for (; k < A.nblk; ++k)
-            for (int j = 0; j < kDiceVals; ++j) v[j] += p0[(size_t)k * A.N + j];
+        dice_rows_all<kDiceVals>(p0, A.N, A.nblk, v);
         const double s = A.smooth;
         const double num = 2.0 * v[0] + s, den = v[1] + v[2] + s;
         A.bc[2 * i] = num; A.bc[2 * i + 1] = den;
         acc[0] += num / den;
         acc[1] += (2.0 * v[3] + 1e-5) / (v[1] + v[4] + 1e-5);   // dice_coef_macro eps (custom_metrics.py:50)
         acc[2] += v[0]; acc[3] += v[1]; acc[4] += v[2]; acc[5] += v[3]; acc[6] += v[4];
-        if (c == 0)
-            for (int k = 0; k < A.nblk; ++k) acc[7] += A.part[((size_t)b * A.nblk + k) * A.N + A.C * kDiceVals];
+        if (c == 0 && n + b >= kBlock) {                        // no idle thread for this image: the owner's own chain, as ever
+            double f[1] = {acc[7]};
+            dice_rows_all<1>(A.part + (size_t)b * A.nblk * A.N + A.C * kDiceVals, A.N, A.nblk, f);
+            acc[7] = f[0];
+        }
     }
     for (int j = 0; j < 8; ++j) sh[j][threadIdx.x] = acc[j];
+    __syncthreads();
+    if (helper) sh[7][hb * A.C] = hs[0];
     __syncthreads();
     for (int o = kBlock / 2; o > 0; o >>= 1) {
         if ((int)threadIdx.x < o) for (int j = 0; j < 8; ++j) sh[j][threadIdx.x] += sh[j][threadIdx.x + o];
