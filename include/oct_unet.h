@@ -497,6 +497,11 @@ int oct_render_rgba(int base_mode, const unsigned char* base_dev, int ic, const 
  *   conv_bt_k does it (8 and 16 K channels), and conv_bx_k where a wave holds two tile rows; the other producers (the wide form with
  *   one tile row per wave, the fp32-pipe kernels, the image layer) and bf16 storage keep the pool_fwd_k pass.  0 = that
  *   pass everywhere.
+ *   "bx_down2_ring" (1; may be set on a live handle between steps): the stride-2 forms of conv_bx_k (backward-data of the
+ *   up-convolutions) run as many blocks as are resident at once; a block walks a strided list of (image, tile) items and
+ *   requests, converts and copies the first K chunk of its next item while the last tap row of the current one is
+ *   multiplied ("persistent_max_blocks" caps that grid).  0 = one block per item.  Every item keeps its own accumulators,
+ *   epilogue and statistic row: results are bit for bit the same either way.
  *   "head_wide" (0; may be set on a live handle between steps): the head (BN + ReLU on load, 1x1 conv, softmax, loss
  *   sums; backward: loss gradient, softmax Jacobian, 1x1 backward, mask, statistics) has two forms.  The register kernels
  *   head_fwd_k / head_bwd_k<C, CIN> keep a pixel's CIN channels and CIN*C + C + 2*CIN partial sums in registers and exist

@@ -63,6 +63,8 @@ struct Options {
                                     // widths above 32 always take: holds them against the register kernels on equal inputs
     int pool_in_epilogue = 1;       // fp32 storage: the bf16-pipe forward convs in front of a max-pool write the pooled tensor from their
                                     // accumulators (raw window extrema; consumers apply BN + ReLU on load) -- no pool_fwd_k pass
+    int bx_down2_ring = 1;          // conv_bx_k, stride-2 forms: a resident grid of blocks walks the (image, tile) items and stages the next
+                                    // item's first tile under the current item's last tap row (0: one block per item)
     int max_blocks = 0;             // FOR TESTS ("persistent_max_blocks"): > 0 caps the grid of every persistent launch, so that
                                     // small images make blocks walk several tiles (cap_grid below); 0 = the launches' own grids
 };

@@ -40,6 +40,21 @@ __device__ __forceinline__ uint32_t pk_bf16(float a, float b) {      // v_cvt_pk
 __device__ __forceinline__ void touch_raw(float4& v) { asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w)); }
 __device__ __forceinline__ void touch_raw(uint2& v) { asm volatile("" : "+v"(v.x), "+v"(v.y)); }
 
+// A barrier inside the pipeline of conv_bx_k: s_waitcnt lgkmcnt(0) with vmcnt(0) (DRAIN) or without, then a RAW s_barrier.
+// __syncthreads() would put a fence in front of the barrier, and while an LDS-DMA is pending that fence drains the whole
+// vector-memory counter whether the caller wants that or not.  The wait is the builtin, not inline assembly: hipcc's own
+// wait insertion sees it and keeps its books by it.  The empty assembly statements keep memory operations on their side.
+template <bool DRAIN>
+__device__ __forceinline__ void bx_wait_barrier() {
+    constexpr int vm = DRAIN ? 0 : 63;
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_s_waitcnt((vm & 15) | ((vm >> 4) << 14) | (7 << 4));      // gfx9 encoding: expcnt 7 = no wait, lgkmcnt 0
+#if !(defined(BX_DBG) && BX_DBG == 1)      // (1: timing experiment without the per-step barrier)
+    __builtin_amdgcn_s_barrier();
+#endif
+    asm volatile("" ::: "memory");
+}
+
 // consumer-side transform of 8 staged values: y = max(fa * v + fb, lo) inside the image, exactly 0 outside (zero padding
 // is applied AFTER the activation).  The affine goes as v_pk_fma_f32 (two channels per instruction), ReLU and padding as
 // ONE v_med3_f32 per element: clamp to [lo, +big) inside, to [0, 0] outside.
@@ -140,7 +155,8 @@ __host__ inline size_t wbx_bytes(int KH, int Kc, int M, int MB, int NS) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// grid (tiles, ceil(Mout/MB), B), block 256.  A.wbx = split weights of this layer direction (prep_wbx_k layout for MB),
+// grid (tiles, ceil(Mout/MB), B), block 256 -- the stride-2 forms: (blocks, ceil(Mout/MB), 1), see WALK.
+// A.wbx = split weights of this layer direction (prep_wbx_k layout for MB),
 // A.m_off must be a multiple of MB.  DROP: the input passes through dropout (the bottleneck output feeding dec0.up).
 //
 // LDS bank conflicts: a ds_read_b128 is served in groups of 16 lanes over 64 banks; with a 32-byte row pitch rows r and
@@ -185,20 +201,22 @@ __global__ __launch_bounds__(64 * NW, NIMG == 1 ? (NW == 4 ? 2 : 1) : 1) void co
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int j = lane & 31, h = lane >> 5;
-    const int tile = blockIdx.x, b = blockIdx.z, m0 = blockIdx.y * MB;
-    const int x0 = (tile % A.tiles_x) * TW, y0 = (tile / A.tiles_x) * TH;
-    const int iy0 = AMODE == A_NORMAL ? y0 - (KH - 1) / 2 : (AMODE == A_UPF ? y0 / 2 : 2 * y0 - 1);
-    const int ix0 = AMODE == A_NORMAL ? x0 - (KH - 1) / 2 : (AMODE == A_UPF ? x0 / 2 : 2 * x0 - 1);
+    // WALK (the stride-2 forms): the block walks the (image, tile) items blockIdx.x, blockIdx.x + gridDim.x, ... < A.total_tiles
+    // (grid (blocks, ceil(Mout/MB), 1)); every other form is launched with one block per item.  The OUTPUT geometry
+    // (tile, b, x0, y0: epilogue, statistic row) and the STAGING geometry (goff, img: loads and conversion) are separate:
+    // staging moves on to the next item while the last K chunk of the current one is still being multiplied.
+    constexpr bool WALK = AMODE == A_DOWN2;
+    static_assert(!WALK || (NIMG == 2 && !DROP), "the tile ring needs both input images");
+    const int m0 = blockIdx.y * MB;
+    int tile, b, x0, y0;
+    auto item_of = [&](int it, int& t, int& bb) {
+        if constexpr (WALK) { bb = it / A.tiles; t = it - bb * A.tiles; } else { t = blockIdx.x; bb = blockIdx.z; }
+    };
+    auto set_out = [&](int it) { item_of(it, tile, b); x0 = (tile % A.tiles_x) * TW; y0 = (tile / A.tiles_x) * TH; };
     const int nch = (A.Cin + 15) / 16;
     const int nmb = (A.wbx_M + MB - 1) / MB, mblk = (A.m_off + m0) / MB;
 
     f32x16 acc[MTW][NTW];
-#pragma unroll
-    for (int mt = 0; mt < MTW; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < NTW; ++nt)
-#pragma unroll
-            for (int r = 0; r < ACC; ++r) acc[mt][nt][r] = 0.f;
 
     // ---- weight slabs by LDS-DMA: slab (chunk, ky) -> slot; wave w copies pieces w, w+4, ... ----
     const char* const wsrc = reinterpret_cast<const char*>(A.wbx);
@@ -214,39 +232,59 @@ __global__ __launch_bounds__(64 * NW, NIMG == 1 ? (NW == 4 ? 2 : 1) : 1) void co
         }
     };
 
-    // ---- input staging: item = (tile pixel P, channel half hh); geometry computed once ----
+    // ---- input staging: item = (tile pixel P, channel half hh); geometry computed once per (image, tile) ----
     int goff[NSLOT], ldst[NSLOT];          // source pixel offset in the image (-1: zero); LDS byte offset of the item
     const int hh = tid & 1;
+    size_t img = 0;
+    auto set_stage = [&](int it) {
+        int st, sb;
+        item_of(it, st, sb);
+        const int sx0 = (st % A.tiles_x) * TW, sy0 = (st / A.tiles_x) * TH;
+        const int iy0 = AMODE == A_NORMAL ? sy0 - (KH - 1) / 2 : (AMODE == A_UPF ? sy0 / 2 : 2 * sy0 - 1);
+        const int ix0 = AMODE == A_NORMAL ? sx0 - (KH - 1) / 2 : (AMODE == A_UPF ? sx0 / 2 : 2 * sx0 - 1);
+#pragma unroll
+        for (int k = 0; k < NSLOT; ++k) {
+            const int P = (tid >> 1) + k * (NTHR / 2), lx = P % IW, ly = P / IW, gy = iy0 + ly, gx = ix0 + lx;
+            const bool in = P < NPIX && gy >= 0 && gy < A.Hi && gx >= 0 && gx < A.Wi;
+            goff[k] = in ? gy * A.Wi + gx : -1;
+        }
+        img = (size_t)sb * A.Hi * A.Wi;
+    };
 #pragma unroll
     for (int k = 0; k < NSLOT; ++k) {
-        const int P = (tid >> 1) + k * (NTHR / 2), lx = P % IW, ly = P / IW, gy = iy0 + ly, gx = ix0 + lx;
-        const bool in = P < NPIX && gy >= 0 && gy < A.Hi && gx >= 0 && gx < A.Wi;
-        goff[k] = in ? gy * A.Wi + gx : -1;
+        const int P = (tid >> 1) + k * (NTHR / 2);
         const int Pd = P < NPIX ? P : NPIX + (P & 63);            // items past the tile: spread over the dump strip
         ldst[k] = Pd * 32 + ((hh ^ ((Pd >> 3) & 1)) * 16);
     }
-    const size_t img = (size_t)b * A.Hi * A.Wi;
+    int item = WALK ? (int)blockIdx.x : 0;
+    const int n_items = WALK ? A.total_tiles : 1, istep = WALK ? (int)gridDim.x : 1;
+    set_out(item);
+    set_stage(item);
     // affine rows of the (possibly concatenated) input, once per block: (a, b) of y = max(a*z + b, lo); identity without BN
     const bool aff = (A.flags & F_AFF) != 0;
     const float lo = aff ? 0.f : -3.0e38f;
     // (the rows themselves are fetched in the pipeline prologue, BEHIND the first tile's loads: one latency, not two)
     typename Raw4<AT>::type pin[NSLOT][2], pz[GB ? NSLOT : 1][2];
+    // Every staging load is UNCONDITIONAL: an item outside the image or past the channels reads pixel 0 / channel octet 0
+    // of its own image (always inside the tensor) and store_slot discards the value (`in`).  No exec-mask branch around a
+    // load: the requests of a tile issue back to back instead of one s_and_saveexec block each.
+    static_assert(KH >= 2, "the tile is requested a tap row ahead of its use");
     auto load_in = [&](int c0) {
-        const int c = c0 + 8 * hh;
+        const int cr = c0 + 8 * hh;
+        const int c = cr < A.Cin ? cr : 0;    // channel counts are multiples of 8 on this path
         const bool two = (A.flags & F_TWO) && c >= A.C0;
         const int C = two ? A.C1 : A.C0;
         const AT* __restrict__ src = (two ? reinterpret_cast<const AT*>(A.x1) + (c - A.C0) : reinterpret_cast<const AT*>(A.x0) + c) + img * C;
-        const bool cok = c < A.Cin;           // channel counts are multiples of 8 on this path
 #pragma unroll
         for (int k = 0; k < NSLOT; ++k) {
-            const bool ok = cok && goff[k] >= 0;
-            const AT* p = src + (size_t)(ok ? goff[k] : 0) * C;
-            pin[k][0] = ok ? ldraw4<AT>(p) : raw_zero4<AT>();
-            pin[k][1] = ok ? ldraw4<AT>(p + 4) : raw_zero4<AT>();
+            const size_t po = (size_t)(goff[k] >= 0 ? goff[k] : 0) * C;
+            const AT* p = src + po;
+            pin[k][0] = ldraw4<AT>(p);
+            pin[k][1] = ldraw4<AT>(p + 4);
             if constexpr (GB) {      // same element of the layer's z (same shape as g': one source, no concat)
-                const AT* q = reinterpret_cast<const AT*>(A.gb_z) + c + img * C + (size_t)(ok ? goff[k] : 0) * C;
-                pz[k][0] = ok ? ldraw4<AT>(q) : raw_zero4<AT>();
-                pz[k][1] = ok ? ldraw4<AT>(q + 4) : raw_zero4<AT>();
+                const AT* q = reinterpret_cast<const AT*>(A.gb_z) + c + img * C + po;
+                pz[k][0] = ldraw4<AT>(q);
+                pz[k][1] = ldraw4<AT>(q + 4);
             }
         }
     };
@@ -411,23 +449,41 @@ __global__ __launch_bounds__(64 * NW, NIMG == 1 ? (NW == 4 ? 2 : 1) : 1) void co
     };
 
     // ---- pipeline over (chunk, tap row) ----
+    // ONE round trip in the prologue: the slab DMA, the first tile's loads and the affine rows are all requested before the
+    // first wait.  The row loads are unconditional too (a channel past Cin, or a launch without BN rows, reads element 0 of
+    // a row that exists -- without BN: of the split weights -- and the value is replaced below), MAXC / NTHR of them per row.
     dma_slab(0, 0, 0);
     load_in(0);
-    for (int c = tid; c < nch * 16; c += NTHR) {
-        float av = 1.f, bv = 0.f;
-        if (aff && c < A.Cin) {
-            const bool two = (A.flags & F_TWO) && c >= A.C0;
-            const float* ab = two ? A.ab1 : A.ab0; const int C = two ? A.C1 : A.C0, cc = two ? c - A.C0 : c;
-            av = ab[cc]; bv = ab[C + cc];
-        }
+    constexpr int RIT = (MAXC + NTHR - 1) / NTHR;
+    float rav[RIT], rbv[RIT], rgv[GB ? RIT : 1];
+#pragma unroll
+    for (int i = 0; i < RIT; ++i) {
+        const int c = tid + i * NTHR;
+        const bool ok = c < A.Cin;
         if constexpr (GB) {
-            const bool ok = c < A.Cin;
-            av = ok ? A.gb_bn[BN_GA * A.Cin + c] : 0.f; bv = ok ? A.gb_bn[BN_GD * A.Cin + c] : 0.f;
-            ABs[2 * MAXC + c] = ok ? A.gb_bn[BN_GB * A.Cin + c] : 0.f;
+            const int cc = ok ? c : 0;
+            rav[i] = A.gb_bn[BN_GA * A.Cin + cc]; rbv[i] = A.gb_bn[BN_GD * A.Cin + cc]; rgv[i] = A.gb_bn[BN_GB * A.Cin + cc];
+        } else {
+            const bool two = (A.flags & F_TWO) && c >= A.C0;
+            const float* ab = !aff ? reinterpret_cast<const float*>(A.wbx) : (two ? A.ab1 : A.ab0);
+            const int C = two ? A.C1 : A.C0, cc = two ? c - A.C0 : c;
+            const bool ld = aff && ok;
+            rav[i] = ab[ld ? cc : 0]; rbv[i] = ab[ld ? C + cc : 0];
         }
-        ABs[c] = av; ABs[MAXC + c] = bv;
     }
-    __syncthreads();                 // ABs visible
+#pragma unroll
+    for (int i = 0; i < RIT; ++i) {
+        const int c = tid + i * NTHR;
+        const bool ok = c < A.Cin;
+        if (c < nch * 16) {
+            if constexpr (GB) {
+                ABs[c] = ok ? rav[i] : 0.f; ABs[MAXC + c] = ok ? rbv[i] : 0.f; ABs[2 * MAXC + c] = ok ? rgv[i] : 0.f;
+            } else {
+                ABs[c] = (aff && ok) ? rav[i] : 1.f; ABs[MAXC + c] = (aff && ok) ? rbv[i] : 0.f;
+            }
+        }
+    }
+    __syncthreads();                 // ABs visible (the rows were the youngest loads: everything has landed)
     begin_store(0);
 #pragma unroll
     for (int k = 0; k < NSLOT; ++k) store_slot(k, 0);
@@ -473,7 +529,7 @@ __global__ __launch_bounds__(64 * NW, NIMG == 1 ? (NW == 4 ? 2 : 1) : 1) void co
         }
         if constexpr (POOLS) { if (A.pool_out && tid < MB && m0 + tid < A.Mout) gam_pf = A.pool_gamma[A.m_off + m0 + tid]; }
     };
-    int g = 0;
+    int g = 0, q = 0;          // running tap-row and K-chunk counts over the block's items: slab slot g & 1, input image q & 1
 #if defined(BX_DBG) && (BX_DBG == 6 || BX_DBG == 7)      // timing experiments: prologue + epilogue only (6), prologue only (7)
     const int nch_run = 0;
     if constexpr (NW == 4) load_zraw();
@@ -484,14 +540,22 @@ __global__ __launch_bounds__(64 * NW, NIMG == 1 ? (NW == 4 ? 2 : 1) : 1) void co
 #else
     const int nch_run = nch;
 #endif
-    for (int c = 0; c < nch_run; ++c) {
+    // ---- the block's items (WALK; one item otherwise).  The (chunk, tap row) pipeline runs on ACROSS items: the first chunk
+    // of the next item is requested in tap row 0 of this item's last chunk and converted into the free image under its last
+    // tap row, the next item's first slab is copied during that row too -- the epilogue is the only thing between two items ----
+    for (;;) {
+    const bool nxt = WALK && item + istep < n_items;
+#pragma unroll
+    for (int mt = 0; mt < MTW; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < NTW; ++nt)
+#pragma unroll
+            for (int r = 0; r < ACC; ++r) acc[mt][nt][r] = 0.f;
+    for (int c = 0; c < nch_run; ++c, ++q) {
 #pragma unroll
         for (int ky = 0; ky < KH; ++ky, ++g) {
-            const bool last_row = ky == KH - 1, more = c + 1 < nch;
-            if (last_row && !more) {
-                if constexpr (NW == 4) load_zraw();      // (8-wave blocks live under the 256-register cap: there the 8 extra
-                load_epi();                              //  float4 spill 100 registers -- their z is requested after the loop)
-            }
+            const bool last_row = ky == KH - 1, more_c = c + 1 < nch, more = more_c || nxt;
+            const int c_next = more_c ? (c + 1) * 16 : 0;      // first channel of the tile staged next (chunk 0 of the next item)
             if (last_row && more) {
                 // The conversion below consumes the input registers requested two tap rows ago.  hipcc waits vmcnt(0)
                 // at their first use -- which would also wait for the weight DMA issued in THIS step (a full L2 round
@@ -502,46 +566,55 @@ __global__ __launch_bounds__(64 * NW, NIMG == 1 ? (NW == 4 ? 2 : 1) : 1) void co
                     touch_raw(pin[k][0]); touch_raw(pin[k][1]);
                     if constexpr (GB) { touch_raw(pz[k][0]); touch_raw(pz[k][1]); }
                 }
-                if constexpr (NIMG == 2) begin_store((c + 1) * 16);     // (one image: after the sweep -- 16-24 registers less in it)
+                if constexpr (NIMG == 2) begin_store(c_next);     // (one image: after the sweep -- 16-24 registers less in it)
+            }
+            if (last_row && !more_c) {
+                if constexpr (NW == 4) load_zraw();      // (8-wave blocks live under the 256-register cap: there the 8 extra
+                load_epi();                              //  float4 spill 100 registers -- their z is requested after the loop)
             }
 #if !(defined(BX_DBG) && BX_DBG == 5)      // (5: timing experiment without the in-loop weight DMA)
             if (!last_row) dma_slab(c, ky + 1, (g + 1) & 1);
-            else if (more) dma_slab(c + 1, 0, (g + 1) & 1);
+            else if (more) dma_slab(more_c ? c + 1 : 0, 0, (g + 1) & 1);
 #endif
-            if (ky == 0 && more) load_in((c + 1) * 16);
+            if (ky == 0 && more) {
+                if constexpr (WALK) { if (!more_c) set_stage(item + istep); }    // (this item's tiles are all converted)
+                load_in(c_next);
+            }
             if constexpr (NIMG == 2) {
-                if (last_row && more) sweep_row(ky, g & 1, c & 1, std::true_type{}, (c + 1) & 1);
-                else sweep_row(ky, g & 1, c & 1, std::false_type{}, 0);
+                if (last_row && more) sweep_row(ky, g & 1, q & 1, std::true_type{}, (q + 1) & 1);
+                else sweep_row(ky, g & 1, q & 1, std::false_type{}, 0);
             } else {
                 sweep_row(ky, g & 1, 0, std::false_type{}, 0);
                 if (last_row && more) {          // every wave is done with the image: overwrite it with the next K chunk
-                    begin_store((c + 1) * 16);
-                    __syncthreads();
+                    begin_store(c_next);
+                    // (raw barrier without a drain: the slab DMA of this step stays in flight under the conversion)
+                    bx_wait_barrier<false>();
 #pragma unroll
                     for (int k = 0; k < NSLOT; ++k) store_slot(k, 0);
                 }
             }
             // an LDS-DMA becomes visible to other waves' ds_reads only through the issuing wave's vmcnt wait followed by
-            // a barrier: drain explicitly (hipcc also does before __syncthreads() while a DMA is in flight)
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#if !(defined(BX_DBG) && BX_DBG == 1)      // (1: timing experiment without the per-step barrier)
-            __syncthreads();
-#endif
+            // a barrier: drain (lgkmcnt(0) makes this wave's store_slot writes visible).  A counted wait that leaves the
+            // next tile's loads in flight across this barrier was built and measured inside the noise.
+            bx_wait_barrier<true>();
         }
     }
 #if defined(BX_DBG) && BX_DBG == 1
     __syncthreads();
 #endif
 
-    // ---- epilogue (same forms as conv_igemm_k; the weight slots are free now) ----
-    float* const epi = reinterpret_cast<float*>(WTs);
-    float* const red = reinterpret_cast<float*>(WTs + EPI_B);
+    // ---- epilogue (same forms as conv_igemm_k; the weight slots are free now -- WALK: the slot of the last tap row is, the
+    // other one already holds the next item's first slab) ----
+    static_assert(!WALK || EPI_B + RED_B <= SLAB_B, "the epilogue scratch fits one slab slot");
+    char* const EPs = WALK ? WTs + ((g + 1) & 1) * SLAB_B : WTs;
+    float* const epi = reinterpret_cast<float*>(EPs);
+    float* const red = reinterpret_cast<float*>(EPs + EPI_B);
     if constexpr (NW != 4) load_zraw();
     if constexpr (EPI != EPI_RAW) {
 #pragma unroll
         for (int i = 0; i < EPF; ++i) { const int e = tid + i * NTHR; if (e < EPN) epi[e] = epi_pf[i]; }     // (requested before the last tap row)
     }
-    float* const gam = reinterpret_cast<float*>(WTs + EPI_B + RED_B);                  // POOLS: [MB]
+    float* const gam = reinterpret_cast<float*>(EPs + EPI_B + RED_B);                  // POOLS: [MB]
     if constexpr (POOLS) { if (tid < MB) gam[tid] = gam_pf; }
     __syncthreads();
     float s1[MTW][ACC], s2[MTW][ACC];
@@ -642,6 +715,11 @@ __global__ __launch_bounds__(64 * NW, NIMG == 1 ? (NW == 4 ? 2 : 1) : 1) void co
                     A.part[((size_t)b * A.tiles + tile) * (2 * A.Mout) + (size_t)stat * A.Mout + m0 + ml] = s;
             }
         }
+    }
+    if (!nxt) break;
+    item += istep;
+    set_out(item);
+    __syncthreads();         // the scratch reads above are done before the next tap row's DMA overwrites that slot
     }
 }
 

@@ -97,9 +97,30 @@ inline double pool_out_bytes(const IgemmArgs& a, int B) { return a.pool_out ? (d
 // GB: the input is a masked gradient g' whose BN-backward transform is applied while it is staged (backward-data only)
 template <int KH, int AMODE, int EPI, int TH, int MB, int NW, int NIMG = 2>
 int launch_bx_nw(IgemmArgs a, const LaunchCtx& c, int* rows) {
-    a.tiles_x = cdiv(a.Wo, 32); a.tiles = a.tiles_x * cdiv(a.Ho, TH);
+    a.tiles_x = cdiv(a.Wo, 32); a.tiles = a.tiles_x * cdiv(a.Ho, TH); a.total_tiles = c.B * a.tiles;
     dim3 grid(a.tiles, cdiv(a.Mout, MB), c.B), block(64 * NW);
     const bool gb = a.gb_z != nullptr;
+    if constexpr (AMODE == A_DOWN2) {
+        // the stride-2 forms walk (image, tile) items: "bx_down2_ring" = as many blocks as are resident at once (the next
+        // item's tile is staged under the current one's last tap row), 0 = one block per item.  One statistic row per ITEM either way.
+        static_assert(NIMG == 2, "the tile ring needs both input images");
+        int nblk = a.total_tiles;
+        if (c.o->bx_down2_ring) {
+            static int occ[2][2] = {{0, 0}, {0, 0}};
+            int& oc = occ[a.act_bf16 ? 1 : 0][gb ? 1 : 0];
+            if (!oc) {
+                int nb = 0;
+                hipError_t e;
+                if (a.act_bf16) e = gb ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, conv_bx_k<KH, AMODE, EPI, TH, MB, 1, false, NW, bf16_t, true, NIMG>, 64 * NW, 0)
+                                       : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, conv_bx_k<KH, AMODE, EPI, TH, MB, 1, false, NW, bf16_t, false, NIMG>, 64 * NW, 0);
+                else e = gb ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, conv_bx_k<KH, AMODE, EPI, TH, MB, 3, false, NW, float, true, NIMG>, 64 * NW, 0)
+                            : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, conv_bx_k<KH, AMODE, EPI, TH, MB, 3, false, NW, float, false, NIMG>, 64 * NW, 0);
+                oc = (e != hipSuccess || nb < 1) ? 1 : nb;
+            }
+            nblk = cap_grid(std::min(a.total_tiles, std::max(1, 256 * oc / cdiv(a.Mout, MB))), *c.o);
+        }
+        grid = dim3(nblk, cdiv(a.Mout, MB), 1);
+    }
     // the pooled tensor from the epilogue: forward 3x3 launches with two tile rows per wave, fp32 storage (conv_bx_k POOLS)
     if (!(EPI == EPI_FWD && AMODE == A_NORMAL && KH == 3 && TH / NW == 2) || a.act_bf16) a.pool_out = nullptr;
     if (a.pool_out && c.pooled) *c.pooled = true;
