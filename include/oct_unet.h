@@ -34,6 +34,8 @@
  *   oct_unet_forward_mc / oct_mc_update (none: Monte-Carlo dropout prediction; the Dropout(0.5) it keeps on is models/unet.py:130)
  *   oct_augment_batch                  BatchGenerator.get_aug_fly/_nofly common/data_generator.py:140-283,
  *                                      flip_aug / add_noise_aug       common/augmentation.py:43-103
+ *   oct_warp_batch                     (none at training time; the per-column np.roll of roll_image_offset /
+ *                                      flatten_image_boundary        dataset_construction.py is its dataset-preparation kin)
  */
 #ifndef OCT_UNET_H
 #define OCT_UNET_H
@@ -348,6 +350,51 @@ typedef struct oct_aug_op {      /* one per sample of the batch, 32 bytes, in DE
 int oct_augment_batch(const unsigned char* x_u8_dev, const unsigned char* labels_dev, const oct_aug_op* ops_dev,
                       int B, int H, int W, int C, unsigned long long seed,
                       float* x_out_dev, unsigned char* labels_out_dev, oct_stream_t stream);
+
+/* ---- geometric training augmentations on device: (B,H,W,C) u8 images -> u8 images, each sample shifted per column or mapped
+ * through an affine transform; (B,H,W) u8 labels moved alongside.  Runs in FRONT of oct_augment_batch, whose flips and noise
+ * then apply to its output.  (The reference has only the per-column np.roll of roll_image_offset / flatten_image_boundary in
+ * dataset_construction.py, as dataset preparation.)  Integer arithmetic only, so the kernel, the numpy restatement
+ * (common/augmentation.py warp_reference) and the host augmentation path give the same bytes.  Stand-alone: no handle, no
+ * allocation, one asynchronous launch on `stream`, graph-capturable.  Per sample b, op = ops_dev[b]; `/` below is FLOOR
+ * division, `>>` an arithmetic shift, all intermediates are 64-bit signed integers.
+ *   border, applied to every source index i of an axis of length n on its own:
+ *     0 replicate: min(max(i, 0), n-1);  1 wrap: i mod n, non-negative;  2 constant: i outside 0..n-1 makes the tap read
+ *     `fill` (image, low 8 bits) or `fill_label` (labels, low 8 bits).
+ *   kind 0 none: copy.
+ *   kind 1 column shift, a = p[0], b = p[1], c = p[2] in 1/256 pixel (translation, rise of the right edge against the centre,
+ *     sag of both edges).  With t = 2x - (W-1), D = max(W-1, 1):
+ *       s(x) = (a D^2 + b t D + c t^2 + 128 D^2) / (256 D^2)
+ *       out[y, x, :] = in[src(y - s(x)), x, :], labels the same.  b = c = 0, a = 256 k, wrap: np.roll(image, k, axis=0).
+ *   kind 2 affine, an inverse map: m00, m01, m10, m11 = p[0..3] in Q16, t0, t1 = p[4], p[5] in Q16 HALF pixels.  With
+ *     X = 2x - (W-1), Y = 2y - (H-1):  U = m00 X + m01 Y + t0,  V = m10 X + m11 Y + t1,
+ *       sx = (U + (W-1) 65536) >> 1,  sy = (V + (H-1) 65536) >> 1                       (source position in Q16 pixels)
+ *     image: ix = sx >> 16, fx = (sx >> 8) & 255, iy, fy likewise; taps p00 = (ix, iy), p01 = (ix+1, iy), p10 = (ix, iy+1),
+ *       p11 = (ix+1, iy+1), each through the border rule;
+ *       out = ((256-fx)(256-fy) p00 + fx (256-fy) p01 + (256-fx) fy p10 + fx fy p11 + 32768) >> 16
+ *     labels: the nearest pixel ((sx + 32768) >> 16, (sy + 32768) >> 16) through the border rule.
+ *     m00 = m11 = 65536, rest 0 is the identity, byte for byte; m00 = m11 = -65536 flips both axes.
+ *   Parameter ranges (OCT_WARP_MAX_*): H, W <= 16384, |a|, |b|, |c| <= 2^22, |m..| <= 2^20, t0, t1 any int32.  Then
+ *     |a D^2 + b t D + c t^2 + 128 D^2| < 2^52 and |U|, |V| < 2^36: no intermediate leaves int64, and every source index
+ *     fits an int32.  The ranges are only visible on the device: REFUSE anything outside them on the host, before upload
+ *     (common/augmentation.py check_warp_ops).  A kind or border outside 0..2 is TREATED AS kind 0 (no device-side flag).
+ *   labels_dev == NULL or labels_out_dev == NULL: no labels written.  Nothing depends on b, B or the launch geometry.
+ * Errors (negative, nothing launched): null x_u8_dev / ops_dev / x_out_dev, non-positive sizes, B > 65535, H or W >
+ * 16384, H*W*C >= 2^31, labels_out_dev without labels_dev, an output range overlapping an input range or the other output
+ * (the stage gathers: it cannot run in place). */
+#define OCT_WARP_MAX_DIM   16384
+#define OCT_WARP_MAX_SHIFT (1 << 22)   /* |a|, |b|, |c| of kind 1 */
+#define OCT_WARP_MAX_M     (1 << 20)   /* |m00|, |m01|, |m10|, |m11| of kind 2 */
+typedef struct oct_warp_op {     /* one per sample of the batch, 40 bytes, in DEVICE memory */
+    int kind;                    /* 0 none, 1 column shift, 2 affine */
+    int border;                  /* 0 replicate, 1 wrap, 2 constant */
+    int p[6];
+    int fill;                    /* image value 0..255 of a tap outside the image (border 2) */
+    int fill_label;              /* label value 0..255 outside the image (border 2) */
+} oct_warp_op;
+int oct_warp_batch(const unsigned char* x_u8_dev, const unsigned char* labels_dev, const oct_warp_op* ops_dev,
+                   int B, int H, int W, int C,
+                   unsigned char* x_out_dev, unsigned char* labels_out_dev, oct_stream_t stream);
 
 /* ---- min-path boundary search on the device ----
  * The boundary delineation of min_path_processing/graph_search.py for (B, M, H, W) uint8 boundary maps as

@@ -122,6 +122,8 @@ SYMBOLS = [
                                         C.c_double, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     ("oct_augment_batch", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_ulonglong,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("oct_warp_batch", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                 C.c_void_p]),
     ("oct_minpath_workspace_bytes", C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     ("oct_minpath_device", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

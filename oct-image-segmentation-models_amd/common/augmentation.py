@@ -62,8 +62,34 @@ def add_noise_aug(image, mask, aug_args, desc_only=False):
     return np.clip(out, 0.0, 1.0), mask
 
 
+def _public_args(aug_args):
+    return {k: v for k, v in (aug_args or {}).items() if k != "op"}
+
+
+def column_shift_aug(image, mask, aug_args, desc_only=False):
+    """Shift every column of the scan along the depth axis: a random translation, tilt and curvature of the retina
+    (``max_shift``, ``max_tilt``, ``max_curvature`` in pixels, each drawn uniformly in [-max, max]; ``border`` "wrap" as
+    the reference's ``np.roll`` in ``roll_image_offset``, "replicate" or "constant").  uint8 in, uint8 out; a float image
+    in [0, 1] (the generator's host path) is taken as float32(u8 / 255) and returned in that form.  Built on
+    ``warp_reference``: the device stage ``oct_warp_batch`` gives the same bytes."""
+    if desc_only is not False:
+        return "column shift: " + str(_public_args(aug_args))
+    return _warp_aug(column_shift_aug, image, mask, aug_args)
+
+
+def affine_aug(image, mask, aug_args, desc_only=False):
+    """Rotate, zoom and translate the scan about its centre, bilinear for the image and nearest for the mask
+    (``max_rotation`` in degrees, ``scale_range`` (lo, hi), ``max_translate`` (dx, dy) in pixels, each drawn uniformly;
+    ``border`` "replicate", "wrap" or "constant" with ``fill`` / ``fill_label``).  Types as ``column_shift_aug``."""
+    if desc_only is not False:
+        return "affine: " + str(_public_args(aug_args))
+    return _warp_aug(affine_aug, image, mask, aug_args)
+
+
 augmentation_map = {
     "add_noise": add_noise_aug,
+    "affine": affine_aug,
+    "column_shift": column_shift_aug,
     "flip": flip_aug,
     "no_augmentation": no_aug,
 }
@@ -104,7 +130,8 @@ def philox4x32_10(counter4, key2) -> np.ndarray:
 def aug_ops_from(aug_fn_args):
     """Descriptor templates (``AUG_OP_DTYPE`` array, one per augmentation, ``noise_id`` 0) of a list of
     ``(function, arguments)`` pairs, or ``None`` if any of them is not one of ``augmentation_map``'s functions with
-    arguments the device implements -- such a list keeps the host path."""
+    arguments the device implements -- such a list keeps the host path.  A ``column_shift`` / ``affine`` entry is kind 0 here:
+    its pixels are moved by the stage in front, whose templates ``warp_ops_from`` gives."""
     ops = np.zeros(len(aug_fn_args), dtype=AUG_OP_DTYPE)
     for j, (fn, args) in enumerate(aug_fn_args):
         args = args or {}
@@ -122,6 +149,12 @@ def aug_ops_from(aug_fn_args):
             ops[j]["kind"] = AUG_SP
             ops[j]["p0"] = float(args.get("amount", 0.05))
             ops[j]["p1"] = {"s&p": float(args.get("salt_vs_pepper", 0.5)), "salt": 1.0, "pepper": 0.0}[args["mode"]]
+        elif fn in (column_shift_aug, affine_aug):
+            try:
+                _warp_spec(fn, args)
+            except ValueError:
+                return None
+            ops[j]["kind"] = AUG_NONE      # the warp stage in front (warp_ops_from) moves the pixels; this one converts them
         else:
             return None
     return ops
@@ -181,3 +214,282 @@ def device_aug_reference(images_u8, labels_u8, ops, seed, dtype=np.float64):
         v = v + v * noise if kind == AUG_SPECKLE else v + noise
         x[b] = np.clip(v, dt(0.0), dt(1.0)).astype(np.float32)
     return x, labels
+
+
+# ---- geometric augmentation: descriptors, parameter draws and the numpy restatement of oct_warp_batch (include/oct_unet.h) ----
+# One descriptor per sample; the layout is the C struct oct_warp_op (40 bytes).  Everything is integer arithmetic, so the
+# kernel, warp_reference and the host augmentation functions built on it give the same bytes.
+WARP_OP_DTYPE = np.dtype([("kind", "<i4"), ("border", "<i4"), ("p", "<i4", (6,)), ("fill", "<i4"), ("fill_label", "<i4")])
+WARP_NONE, WARP_COLUMN_SHIFT, WARP_AFFINE = range(3)
+WARP_REPLICATE, WARP_WRAP, WARP_CONSTANT = range(3)
+WARP_BORDERS = {"replicate": WARP_REPLICATE, "wrap": WARP_WRAP, "constant": WARP_CONSTANT}
+# the ranges inside which no intermediate of the definition leaves int64 (OCT_WARP_MAX_* of include/oct_unet.h)
+WARP_MAX_DIM, WARP_MAX_SHIFT, WARP_MAX_M = 16384, 1 << 22, 1 << 20
+WARP_DRAWS = 4      # uniform numbers a sample's parameters are drawn from, whatever its augmentation
+
+
+def check_warp_ops(ops, H=None, W=None) -> None:
+    """Refuse (``ValueError``) descriptors or image sizes outside the ranges ``oct_warp_batch`` is defined for: the device
+    cannot report them."""
+    ops = np.asarray(ops)
+    if ops.dtype != WARP_OP_DTYPE:
+        raise TypeError("warp descriptors must be a WARP_OP_DTYPE array")
+    for name, v in (("H", H), ("W", W)):
+        if v is not None and not 1 <= int(v) <= WARP_MAX_DIM:
+            raise ValueError(f"warp: {name} = {v} outside 1..{WARP_MAX_DIM}")
+    if ops.size == 0:
+        return
+    for name, hi in (("kind", WARP_AFFINE), ("border", WARP_CONSTANT), ("fill", 255), ("fill_label", 255)):
+        if ops[name].min() < 0 or ops[name].max() > hi:
+            raise ValueError(f"warp: descriptor {name} outside 0..{hi}")
+    p = ops["p"].astype(np.int64).reshape(-1, 6)
+    kind = ops["kind"].reshape(-1)
+    if np.abs(p[kind == WARP_COLUMN_SHIFT, :3]).max(initial=0) > WARP_MAX_SHIFT:
+        raise ValueError(f"warp: column shift parameters a, b, c must be within +-{WARP_MAX_SHIFT} (1/256 pixel)")
+    if np.abs(p[kind == WARP_AFFINE, :4]).max(initial=0) > WARP_MAX_M:
+        raise ValueError(f"warp: affine matrix entries must be within +-{WARP_MAX_M} (Q16)")
+
+
+def _nonneg(args, key, hi, default=0.0):
+    v = float(args.get(key, default))
+    if not 0.0 <= v <= hi:
+        raise ValueError(f"{key} must be within 0..{hi}, got {args.get(key)!r}")
+    return v
+
+
+def _pair(args, key, default):
+    v = args.get(key, default)
+    try:
+        a, b = (float(e) for e in v)
+    except (TypeError, ValueError):
+        raise ValueError(f"{key} must be a pair of numbers, got {v!r}") from None
+    return a, b
+
+
+def _warp_spec(fn, args):
+    """The validated arguments of one list entry as a dict, ``None`` for a function that is not a warp; ``ValueError``
+    for arguments outside what the integer definition covers."""
+    if fn is not column_shift_aug and fn is not affine_aug:
+        return None
+    args = args or {}
+    known = {"op", "border", "fill", "fill_label"} | ({"max_shift", "max_tilt", "max_curvature"} if fn is column_shift_aug
+                                                     else {"max_rotation", "scale_range", "max_translate"})
+    if set(args) - known:
+        raise ValueError(f"{fn.__name__}: unknown arguments {sorted(set(args) - known)}")
+    border = args.get("border", "wrap" if fn is column_shift_aug else "replicate")
+    if border not in WARP_BORDERS:
+        raise ValueError(f"border must be one of {sorted(WARP_BORDERS)}, got {border!r}")
+    spec = {"border": WARP_BORDERS[border]}
+    for key in ("fill", "fill_label"):
+        v = args.get(key, 0)
+        if int(v) != v or not 0 <= int(v) <= 255:
+            raise ValueError(f"{key} must be an integer in 0..255, got {v!r}")
+        spec[key] = int(v)
+    if fn is column_shift_aug:
+        px = WARP_MAX_SHIFT / 256.0
+        spec.update(kind=WARP_COLUMN_SHIFT, max_shift=_nonneg(args, "max_shift", px), max_tilt=_nonneg(args, "max_tilt", px),
+                    max_curvature=_nonneg(args, "max_curvature", px))
+        return spec
+    lo, hi = _pair(args, "scale_range", (1.0, 1.0))
+    if not 65536.0 / WARP_MAX_M <= lo <= hi < np.inf:
+        raise ValueError(f"scale_range must satisfy {65536.0 / WARP_MAX_M} <= lo <= hi, got {(lo, hi)}")
+    dx, dy = _pair(args, "max_translate", (0.0, 0.0))
+    # |t| <= (1/lo) 2 (dx + dy) 65536 has to fit the descriptor's int32
+    if not (dx >= 0.0 and dy >= 0.0 and 2.0 * (dx + dy) * 65536.0 / lo < 2.0 ** 31 - 1):
+        raise ValueError(f"max_translate must be non-negative and 2 (dx + dy) / lo below 32768 pixels, got {(dx, dy)}")
+    spec.update(kind=WARP_AFFINE, max_rotation=_nonneg(args, "max_rotation", 360.0), scale=(lo, hi), max_translate=(dx, dy))
+    return spec
+
+
+def warp_ops_from(aug_fn_args):
+    """Descriptor templates (``WARP_OP_DTYPE`` array, one per augmentation: kind, border and fill values set, parameters 0;
+    kind 0 for an entry that is not a warp) of a list of ``(function, arguments)`` pairs, or ``None`` if the list holds no
+    ``column_shift`` / ``affine``.  ``ValueError`` for arguments the integer definition does not cover."""
+    specs = [_warp_spec(fn, args) for fn, args in aug_fn_args]
+    if not any(s is not None for s in specs):
+        return None
+    ops = np.zeros(len(specs), dtype=WARP_OP_DTYPE)
+    for j, s in enumerate(specs):
+        if s is not None:
+            ops[j]["kind"], ops[j]["border"], ops[j]["fill"], ops[j]["fill_label"] = s["kind"], s["border"], s["fill"], s["fill_label"]
+    return ops
+
+
+def draw_warp_ops(aug_fn_args, j, u):
+    """The descriptors of ``len(j)`` samples: sample i gets augmentation ``aug_fn_args[j[i]]`` with parameters taken from
+    its ``WARP_DRAWS`` uniform numbers ``u[i]`` in [0, 1).  The one place where parameters are drawn, for the host path
+    (one sample at a time) and the device path (a batch at a time) alike; float64, rounded with ``np.rint``.
+      column_shift: a, b, c = rint(256 max (2 u - 1)) for shift, tilt, curvature (u[0], u[1], u[2]).
+      affine: theta = max_rotation (2 u[0] - 1), s = lo + (hi - lo) u[1], d = max_translate (2 u[2] - 1, 2 u[3] - 1);
+        m = (1/s) [[cos, sin], [-sin, cos]], t = -m (2 d); descriptor = rint(65536 (m00, m01, m10, m11, t0, t1))."""
+    j = np.asarray(j, dtype=np.int64).reshape(-1)
+    u = np.asarray(u, dtype=np.float64).reshape(j.size, WARP_DRAWS)
+    ops = np.zeros(j.size, dtype=WARP_OP_DTYPE)
+    for k, (fn, args) in enumerate(aug_fn_args):
+        spec = _warp_spec(fn, args)
+        sel = np.flatnonzero(j == k)
+        if spec is None or sel.size == 0:
+            continue
+        for name in ("kind", "border", "fill", "fill_label"):
+            ops[name][sel] = spec[name]
+        v = 2.0 * u[sel] - 1.0
+        if spec["kind"] == WARP_COLUMN_SHIFT:
+            p = 256.0 * np.stack([spec["max_shift"] * v[:, 0], spec["max_tilt"] * v[:, 1], spec["max_curvature"] * v[:, 2]], axis=1)
+        else:
+            theta = np.radians(spec["max_rotation"] * v[:, 0])
+            s = spec["scale"][0] + (spec["scale"][1] - spec["scale"][0]) * u[sel, 1]
+            dx, dy = spec["max_translate"][0] * v[:, 2], spec["max_translate"][1] * v[:, 3]
+            m00, m01 = np.cos(theta) / s, np.sin(theta) / s
+            m10, m11 = -m01, m00
+            p = 65536.0 * np.stack([m00, m01, m10, m11, -(m00 * 2.0 * dx + m01 * 2.0 * dy), -(m10 * 2.0 * dx + m11 * 2.0 * dy)], axis=1)
+        ops["p"][sel, :p.shape[1]] = np.rint(p).astype(np.int64)
+    check_warp_ops(ops)
+    return ops
+
+
+def column_shifts(W: int, a: int, b: int, c: int) -> np.ndarray:
+    """s(x) of the column shift for x = 0..W-1 (int64): floor((a D^2 + b t D + c t^2 + 128 D^2) / (256 D^2)) with
+    t = 2x - (W-1) and D = max(W-1, 1)."""
+    W, a, b, c = int(W), int(a), int(b), int(c)
+    D = max(W - 1, 1)
+    t = 2 * np.arange(W, dtype=np.int64) - (W - 1)
+    return (a * D * D + b * D * t + c * t * t + 128 * D * D) // (256 * D * D)
+
+
+def _border_index(i, n, border):
+    """Source indices of the int64 array ``i`` on an axis of length ``n``: (indices inside 0..n-1, outside mask or None)."""
+    if border == WARP_WRAP:
+        return np.mod(i, n), None
+    inside = np.clip(i, 0, n - 1)
+    return inside, ((i < 0) | (i >= n) if border == WARP_CONSTANT else None)
+
+
+def _any_outside(*masks):
+    masks = [m for m in masks if m is not None]
+    out = None
+    for m in masks:
+        out = m if out is None else out | m
+    return out
+
+
+def _warp_positions(H, W, op):
+    """Q16 source position (sx, sy), int64 (H, W) arrays, of every output pixel under the affine descriptor ``op``."""
+    p = [int(v) for v in op["p"]]
+    X = (2 * np.arange(W, dtype=np.int64) - (W - 1))[None, :]
+    Y = (2 * np.arange(H, dtype=np.int64) - (H - 1))[:, None]
+    U = p[0] * X + p[1] * Y + p[4]
+    V = p[2] * X + p[3] * Y + p[5]
+    return (U + (W - 1) * 65536) >> 1, (V + (H - 1) * 65536) >> 1
+
+
+def _warp_kind(op):
+    kind, border = int(op["kind"]), int(op["border"])
+    return kind if 0 <= kind <= WARP_AFFINE and 0 <= border <= WARP_CONSTANT else WARP_NONE
+
+
+def warp_label_index(H, W, op):
+    """Where every output pixel's LABEL comes from: ``(rows, cols, outside)``, (H, W) int64 index arrays and a bool mask of
+    the pixels that read ``fill_label`` (``None`` if there are none by construction)."""
+    kind, border = _warp_kind(op), int(op["border"])
+    cols = np.broadcast_to(np.arange(W, dtype=np.int64)[None, :], (H, W))
+    rows = np.broadcast_to(np.arange(H, dtype=np.int64)[:, None], (H, W))
+    if kind == WARP_COLUMN_SHIFT:
+        s = column_shifts(W, *op["p"][:3])
+        rows, outside = _border_index(rows - s[None, :], H, border)
+        return rows, cols, outside
+    if kind == WARP_AFFINE:
+        sx, sy = _warp_positions(H, W, op)
+        cols, ox = _border_index((sx + 32768) >> 16, W, border)
+        rows, oy = _border_index((sy + 32768) >> 16, H, border)
+        return rows, cols, _any_outside(ox, oy)
+    return rows, cols, None
+
+
+def _warp_image(img, op):
+    """One (H, W, C) uint8 image through the descriptor ``op``."""
+    kind, border, fill = _warp_kind(op), int(op["border"]), int(op["fill"]) & 255
+    H, W = img.shape[:2]
+    if kind != WARP_AFFINE:         # a pure gather, the labels' rule
+        rows, cols, outside = warp_label_index(H, W, op)
+        out = img[rows, cols]
+        if outside is not None:
+            out[outside] = fill
+        return out
+    sx, sy = _warp_positions(H, W, op)
+    ix, fx, iy, fy = sx >> 16, (sx >> 8) & 255, sy >> 16, (sy >> 8) & 255
+    acc = np.zeros(img.shape, dtype=np.int64)
+    for dy, wy in ((0, 256 - fy), (1, fy)):
+        rows, oy = _border_index(iy + dy, H, border)
+        for dx, wx in ((0, 256 - fx), (1, fx)):
+            cols, ox = _border_index(ix + dx, W, border)
+            tap = img[rows, cols].astype(np.int64)
+            outside = _any_outside(ox, oy)
+            if outside is not None:
+                tap[outside] = fill
+            acc += (wx * wy)[..., None] * tap
+    return ((acc + 32768) >> 16).astype(np.uint8)
+
+
+def warp_reference(images_u8, labels_u8, ops):
+    """What ``oct_warp_batch`` computes, by its definition in include/oct_unet.h, vectorised in int64: ``(images uint8
+    (B,H,W,C), labels uint8)`` (``labels_u8`` may be ``None``, (B,H,W) or (B,H,W,1)).  Refuses what the device entry point
+    is not defined for (``check_warp_ops``)."""
+    images_u8 = np.asarray(images_u8)
+    if images_u8.dtype != np.uint8 or images_u8.ndim != 4:
+        raise TypeError("warp_reference needs (B,H,W,C) uint8 images")
+    ops = np.asarray(ops)
+    B, H, W, _ = images_u8.shape
+    check_warp_ops(ops, H, W)
+    if ops.shape != (B,):
+        raise ValueError("one descriptor per sample")
+    labels = None if labels_u8 is None else np.array(labels_u8, dtype=np.uint8)
+    if labels is not None and labels.size != B * H * W:
+        raise ValueError("labels must be (B,H,W) or (B,H,W,1)")
+    out = np.empty_like(images_u8)
+    for b, op in enumerate(ops):
+        out[b] = _warp_image(images_u8[b], op)
+        if labels is not None and _warp_kind(op) != WARP_NONE:
+            rows, cols, outside = warp_label_index(H, W, op)
+            moved = labels[b].reshape(H, W)[rows, cols]
+            if outside is not None:
+                moved[outside] = int(op["fill_label"]) & 255
+            labels[b] = moved.reshape(labels[b].shape)
+    return out, labels
+
+
+def _warp_aug(fn, image, mask, aug_args):
+    """The host side of ``column_shift`` / ``affine``: the sample's descriptor is ``aug_args["op"]`` (a generator that
+    walks the device path's parameter stream puts it there) or drawn from the module RNG; the image goes through
+    ``warp_reference`` and the mask -- (H,W), (H,W,1) or one-hot (H,W,K), any dtype -- through the label rule."""
+    args = aug_args or {}
+    op = args.get("op")
+    if op is None:
+        op = draw_warp_ops([(fn, args)], [0], _rng.random((1, WARP_DRAWS)))
+    op = np.asarray(op, dtype=WARP_OP_DTYPE).reshape(1)
+    img = np.asarray(image)
+    shape = img.shape
+    if img.ndim == 2:
+        img = img[..., None]
+    as_float = img.dtype != np.uint8
+    if as_float:        # float32(u8 / 255) -> u8 is exact; anything else is quantised to 8 bits here
+        img = np.clip(np.rint(img.astype(np.float64) * 255.0), 0, 255).astype(np.uint8)
+    out = warp_reference(img[None], None, op)[0][0].reshape(shape)
+    if as_float:
+        out = out.astype(np.float32) / np.float32(255.0)
+    if mask is None:
+        return out, None
+    m = np.asarray(mask)
+    H, W = img.shape[:2]
+    if _warp_kind(op[0]) == WARP_NONE:
+        return out, m
+    rows, cols, outside = warp_label_index(H, W, op[0])
+    moved = m[rows, cols]
+    if outside is not None:
+        fill = int(op[0]["fill_label"])
+        if m.ndim == 3 and m.shape[-1] > 1:     # one-hot: the fill class's row
+            if fill >= m.shape[-1]:
+                raise ValueError(f"fill_label {fill} is not one of the mask's {m.shape[-1]} classes")
+            moved[outside] = np.eye(m.shape[-1], dtype=m.dtype)[fill]
+        else:
+            moved[outside] = fill
+    return out, moved

@@ -21,7 +21,13 @@ so the /255 happens on the GPU while the first conv loads the image.
 ``device_aug=True`` (off by default) moves the augmentations of ``common.augmentation.augmentation_map`` to the device:
 ``next_batch_aug`` walks the generator's state exactly as ``get_batch_list`` does but returns the raw uint8 samples and one
 ``oct_aug_op`` descriptor per sample; the engine's ``oct_augment_batch`` applies them (flips exactly; noise from its own
-documented Philox stream, not from numpy's).  Nothing is pre-computed or kept in float on the host in that mode."""
+documented Philox stream, not from numpy's).  Nothing is pre-computed or kept in float on the host in that mode.
+
+The geometric augmentations (``column_shift``, ``affine``) draw their per-sample parameters from a SECOND stream of the
+generator, spawned from its seed: ``WARP_DRAWS`` uniform numbers per sample handed out, whatever augmentation the sample gets,
+in the order of the global sample walk (``aug_fly``), or one table entry per (image, augmentation) pair (pre-computed set).
+``augmentation.draw_warp_ops`` turns them into integer descriptors for the host path (one sample at a time) and the device
+path (``next_batch_aug`` then returns a fourth array, one ``oct_warp_op`` per sample) alike, so both apply the same warp."""
 from __future__ import annotations
 
 import logging as log
@@ -30,6 +36,8 @@ from math import floor
 from typing import Callable, List, Optional, Tuple
 
 import numpy as np
+
+from . import augmentation
 
 
 class BatchGenerator:
@@ -63,9 +71,16 @@ class BatchGenerator:
         self.images = None
         self.aug_ops = None         # descriptor templates of aug_fn_args (device path)
         self.samples_drawn = 0      # GLOBAL-batch samples handed out by next_batch_aug since construction
-        if aug_mode != "none" and device_aug:
-            from . import augmentation
-            self.aug_ops = augmentation.aug_ops_from(aug_fn_args)
+        self.warp_ops = None        # warp descriptor templates: aug_fn_args holds a column_shift / affine
+        if aug_mode != "none":
+            self.warp_ops = augmentation.warp_ops_from(aug_fn_args)      # (refuses arguments outside the definition)
+            if device_aug:
+                self.aug_ops = augmentation.aug_ops_from(aug_fn_args)
+        if self.warp_ops is not None:
+            # the parameter stream of the warps: a child of the seed, beside the stream of the shuffle and the choices
+            self._warp_rng = np.random.default_rng(np.random.SeedSequence(seed).spawn(1)[0])
+            if aug_fly is False:    # pre-computed set: one parameter draw per (image, augmentation) pair, for good
+                self._warp_table = self._warp_rng.random((self.total_full_images, self.total_augs, augmentation.WARP_DRAWS))
         if aug_mode != "none" and self.aug_ops is None:
             self._setup_host_aug()
         self.handle_epoch_end()
@@ -82,8 +97,16 @@ class BatchGenerator:
         aug_labels = np.zeros((self.total_full_images, self.total_augs) + tuple(self.labels_shape[1:]), dtype=self.labels.dtype)
         for i in range(self.total_full_images):
             for j, (aug_fn, aug_arg) in enumerate(self.aug_fn_args):
+                aug_arg = self._with_warp_op(j, aug_arg, None if self.warp_ops is None else self._warp_table[i, j])
                 aug_images[i, j], aug_labels[i, j] = aug_fn(self.images[i], self.labels[i], aug_arg)
         return aug_images, aug_labels
+
+    def _with_warp_op(self, j, aug_arg, u):
+        """``aug_arg`` of augmentation ``j`` with the sample's warp descriptor, drawn from its uniform numbers ``u``, under
+        "op" -- where that augmentation is a warp."""
+        if self.warp_ops is None or self.warp_ops[j]["kind"] == 0:
+            return aug_arg
+        return dict(aug_arg or {}, op=augmentation.draw_warp_ops(self.aug_fn_args, [j], u))
 
     def _next_augmented(self):
         """One (image in [0,1], label) sample with the reference's counter semantics (get_aug_fly / get_aug_nofly)."""
@@ -99,6 +122,8 @@ class BatchGenerator:
             self.full_counter += 1
         if self.aug_fly:
             aug_fn, aug_arg = self.aug_fn_args[j]
+            if self.warp_ops is not None:       # every sample takes its numbers, whatever its augmentation
+                aug_arg = self._with_warp_op(j, aug_arg, self._warp_rng.random(augmentation.WARP_DRAWS))
             img, lab = aug_fn(self.images[ind], self.labels[ind], aug_arg)
         else:
             img, lab = self.aug_images[ind, j], self.aug_labels[ind, j]
@@ -165,7 +190,9 @@ class BatchGenerator:
         ``get_batch_list``, so one seed gives one sequence of (image, augmentation) pairs through either path.
         ``noise_id``: with ``aug_fly`` a running count of the samples drawn since construction (fresh noise every epoch); without,
         ``image_index * n_augs + j`` (the same noise for a pair in every epoch: what the pre-computed set means).  With
-        ``shard = (lo, hi)`` only samples lo..hi-1 are gathered; their descriptors are those of the one-rank run."""
+        ``shard = (lo, hi)`` only samples lo..hi-1 are gathered; their descriptors are those of the one-rank run.
+        A list with a ``column_shift`` / ``affine`` returns a fourth array, one ``augmentation.WARP_OP_DTYPE`` descriptor per
+        sample (kind 0 for a sample that is not warped), drawn for the GLOBAL batch and sliced like the others."""
         if self.aug_ops is None:
             raise TypeError("next_batch_aug needs device_aug=True, an augmentation mode and augmentations the device "
                             "implements (augmentation.aug_ops_from)")
@@ -189,8 +216,15 @@ class BatchGenerator:
         else:
             ops["noise_id"] = idx.astype(np.uint64) * np.uint64(A) + j.astype(np.uint64)
         self.samples_drawn += B
+        wops = None
+        if self.warp_ops is not None:
+            u = self._warp_rng.random((B, augmentation.WARP_DRAWS)) if self.aug_fly else self._warp_table[idx, j]
+            wops = augmentation.draw_warp_ops(self.aug_fn_args, j, u)
         if shard is not None:
             idx, ops = idx[shard[0]:shard[1]], ops[shard[0]:shard[1]]
+            wops = None if wops is None else wops[shard[0]:shard[1]]
+        if wops is not None:
+            return self.images_u8[idx], self.sparse_labels()[idx], ops, wops
         return self.images_u8[idx], self.sparse_labels()[idx], ops
 
     def handle_epoch_end(self):

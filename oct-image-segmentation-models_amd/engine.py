@@ -439,6 +439,41 @@ class UNetEngine:
                   lab_out.data_ptr() if labels is not None else None, self._stream())
         return x_out, (lab_out if labels is not None else None)
 
+    def warp(self, x_u8: torch.Tensor, labels: Optional[torch.Tensor], ops, out=None):
+        """The geometric augmentations on the device (``oct_warp_batch``): (B,H,W,C) uint8 images, (B,H,W[,1]) uint8 labels
+        or ``None`` and one ``common.augmentation.WARP_OP_DTYPE`` descriptor per sample -> ``(images uint8, labels uint8)``
+        (moved alongside; ``None`` without labels), the input of ``augment``.  ``ops``: a numpy descriptor array (validated
+        with ``check_warp_ops``, then uploaded) or a uint8 device tensor of B*40 bytes that already holds validated
+        descriptors.  ``out``: optional ``(x_out, labels_out)`` tensors to write into; the stage gathers, so neither may
+        be an input.  Asynchronous on the current stream."""
+        from .common.augmentation import WARP_OP_DTYPE, check_warp_ops
+        u8 = dict(device=self.device, dtype=torch.uint8)
+        _hip.expect(x_u8, "warp: images (B,H,W,C)", shape=(None, None, None, None), **u8)
+        B, H, W, Cn = x_u8.shape
+        if labels is not None:
+            _hip.expect(labels, "warp: labels (B,H,W[,1])", numel=B * H * W, **u8)
+        if isinstance(ops, np.ndarray):
+            if ops.dtype != WARP_OP_DTYPE or ops.shape != (B,):
+                raise OctError("warp: ops must hold one WARP_OP_DTYPE descriptor per sample")
+            try:
+                check_warp_ops(ops, H, W)
+            except ValueError as e:
+                raise OctError(str(e)) from None
+            ops = torch.from_numpy(np.ascontiguousarray(ops).view(np.uint8).copy()).to(self.device)
+        _hip.expect(ops, "warp: ops (B*40 descriptor bytes)", numel=B * WARP_OP_DTYPE.itemsize, **u8)
+        x_out, lab_out = out if out is not None else (None, None)
+        if x_out is None:
+            x_out = torch.empty_like(x_u8)
+        if labels is not None and lab_out is None:
+            lab_out = torch.empty_like(labels)
+        _hip.expect(x_out, "warp: out[0]", shape=tuple(x_u8.shape), **u8)
+        if labels is not None:
+            _hip.expect(lab_out, "warp: out[1]", numel=labels.numel(), **u8)
+        _hip.call("oct_warp_batch", self.device, x_u8.data_ptr(), labels.data_ptr() if labels is not None else None,
+                  ops.data_ptr(), B, H, W, Cn, x_out.data_ptr(), lab_out.data_ptr() if labels is not None else None,
+                  self._stream())
+        return x_out, (lab_out if labels is not None else None)
+
     # ---- weights exchange --------------------------------------------------------------------------
     def get_weights(self) -> List[np.ndarray]:
         """Keras ``get_weights()`` order: Conv2D [kernel HWIO, bias]; BN [gamma, beta, moving_mean, moving_var]."""

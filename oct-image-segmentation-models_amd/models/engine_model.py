@@ -241,9 +241,11 @@ class Model:
     # ---- training -------------------------------------------------------------------------------------
     def _host_batch(self, seq, index, rank, world):
         """One GLOBAL batch from the Sequence -> this rank's (x, sparse uint8 labels) host arrays; for a Sequence that
-        augments on the device (``oct_device_aug``) the raw uint8 images and a third array, the per-sample descriptors."""
+        augments on the device (``oct_device_aug``) the raw uint8 images and a third array, the per-sample descriptors --
+        and a fourth, the warp descriptors, where this rank's slice holds a sample that is warped."""
         if getattr(seq, "oct_device_aug", False):
-            return seq.next_batch_aug(parallel.shard_batch(seq.batch_size, rank, world) if world > 1 else None)
+            hb = seq.next_batch_aug(parallel.shard_batch(seq.batch_size, rank, world) if world > 1 else None)
+            return hb[:3] if len(hb) > 3 and not hb[3]["kind"].any() else hb      # no warp sample: the stage is skipped
         if getattr(seq, "oct_fast_path", False):
             if world > 1:      # gather this rank's slice only (8 ranks: 1/8 of the host work per step and rank)
                 return seq.next_batch_u8(parallel.shard_batch(seq.batch_size, rank, world))
@@ -256,20 +258,23 @@ class Model:
         lo, hi = parallel.shard_batch(X.shape[0], rank, world)
         return X[lo:hi], lab[lo:hi]
 
-    def _upload(self, X: np.ndarray, lab: np.ndarray, slot: int, ops: Optional[np.ndarray] = None):
+    def _upload(self, X: np.ndarray, lab: np.ndarray, slot: int, ops: Optional[np.ndarray] = None,
+                wops: Optional[np.ndarray] = None):
         """Queue the upload of one batch into device slot ``slot`` on the COPY stream (never on the compute stream: 8 MB of
         uint8 per 32-scan batch would otherwise sit in front of every step).  Pinned staging buffers and device buffers come
         in THREE slots: slot s is refilled only after the step that last read its device tensors has finished -- a HOST
         wait on that step's event, two steps back, which also keeps this thread at most two steps ahead of the GPU.  (With two
         slots the copy had to wait for the previous step on the copy stream; the H2D call then held the host until that
         step was over and every step started with the launch latency exposed: 0.91 of the resident-input rate.)
-        ``ops`` (device augmentation: one 32-byte descriptor per sample) travels through the same slot as raw bytes.
-        Returns (x, labels, ready event, descriptor bytes or None)."""
+        ``ops`` (device augmentation: one 32-byte descriptor per sample) travels through the same slot as raw bytes, and so
+        does ``wops`` (one 40-byte warp descriptor per sample).
+        Returns (x, labels, ready event, descriptor bytes or None), with ``wops`` a fifth element, the warp descriptor bytes."""
         dev = self._engine.device if self._engine is not None else self._dev()
         st = self.__dict__.setdefault("_up", {"copy": None, "ev": {}, "done": {}, "dev": {}})
         if dev.type != "cuda":
+            raw = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).copy())
             return (torch.from_numpy(np.ascontiguousarray(X)), torch.from_numpy(np.ascontiguousarray(lab)), None,
-                    None if ops is None else torch.from_numpy(np.ascontiguousarray(ops).view(np.uint8).copy()))
+                    raw(ops)) + (() if wops is None else (raw(wops),))
         if st["copy"] is None:
             st["copy"] = torch.cuda.Stream(device=dev)
         if slot in st["done"]:
@@ -278,6 +283,7 @@ class Model:
             st["ev"][slot].synchronize()          # host: the H2D copies that last read this slot's pinned buffers have executed
         xp, lp = self._staged(("x", slot), X), self._staged(("l", slot), lab)
         op = None if ops is None else self._staged(("o", slot), np.ascontiguousarray(ops).view(np.uint8))
+        wop = None if wops is None else self._staged(("w", slot), np.ascontiguousarray(wops).view(np.uint8))
         bufs = st["dev"].get(slot)
         if bufs is None or bufs[0].shape != xp.shape or bufs[0].dtype != xp.dtype or bufs[1].shape != lp.shape:
             bufs = st["dev"][slot] = (torch.empty(xp.shape, dtype=xp.dtype, device=dev), torch.empty(lp.shape, dtype=lp.dtype, device=dev))
@@ -286,18 +292,31 @@ class Model:
             obuf = st.setdefault("ops", {}).get(slot)
             if obuf is None or obuf.shape != op.shape:
                 obuf = st["ops"][slot] = torch.empty(op.shape, dtype=torch.uint8, device=dev)
+        wbuf = None
+        if wop is not None:
+            wbuf = st.setdefault("wops", {}).get(slot)
+            if wbuf is None or wbuf.shape != wop.shape:
+                wbuf = st["wops"][slot] = torch.empty(wop.shape, dtype=torch.uint8, device=dev)
         with torch.cuda.stream(st["copy"]):
             bufs[0].copy_(xp, non_blocking=True); bufs[1].copy_(lp, non_blocking=True)
             if op is not None:
                 obuf.copy_(op, non_blocking=True)
+            if wop is not None:
+                wbuf.copy_(wop, non_blocking=True)
             ev = torch.cuda.Event(); ev.record(st["copy"])
         st["ev"][slot] = ev
-        return bufs[0], bufs[1], ev, obuf
+        return (bufs[0], bufs[1], ev, obuf) + (() if wbuf is None else (wbuf,))
 
-    def _augment(self, eng, seq, x, lab, ops):
+    def _augment(self, eng, seq, x, lab, ops, wops=None):
         """Device augmentation of one uploaded batch on the compute stream (behind the slot's ready event) into ONE
         model-owned pair of buffers: the next step's augment is queued on the same stream behind this step's backward, the
-        last reader of the pair, so one pair is enough."""
+        last reader of the pair, so one pair is enough.  With warp descriptors the batch first goes through ``warp`` into
+        a second, uint8 pair under the same rule: its only reader is the ``augment`` queued right behind it."""
+        if wops is not None:
+            wbuf = self.__dict__.get("_warp_out")
+            if wbuf is None or wbuf[0].shape != x.shape or wbuf[1].shape != lab.shape or wbuf[0].device != x.device:
+                wbuf = self._warp_out = (torch.empty_like(x), torch.empty_like(lab))
+            x, lab = eng.warp(x, lab, wops, out=wbuf)
         buf = self.__dict__.get("_aug_out")
         if buf is None or buf[0].shape != x.shape or buf[1].shape != lab.shape or buf[0].device != x.device:
             buf = self._aug_out = (torch.empty(x.shape, dtype=torch.float32, device=x.device), torch.empty_like(lab))
@@ -335,14 +354,14 @@ class Model:
             return self._upload(hb[0], hb[1], index % 3, *hb[2:])
         nxt = queue(0) if n else None
         for i in range(n):
-            x, lab, ready, ops = nxt
+            x, lab, ready, ops, *wops = nxt
             if ready is not None:
                 torch.cuda.current_stream(x.device).wait_event(ready)
             if i + 1 < n:
                 nxt = queue(i + 1)
             eng = self._ensure_engine(x.shape[0], training)
             if ops is not None:
-                x, lab = self._augment(eng, seq, x, lab, ops)
+                x, lab = self._augment(eng, seq, x, lab, ops, *wops)
             if focal:      # (re)selected per batch: _ensure_engine may have built a new engine
                 eng.set_focal_dice(focal["focal_loss_weight"], focal["gamma"], focal["class_weight"])
             elif getattr(eng, "_focal_active", False):

@@ -17,7 +17,7 @@ from pathlib import Path
 import numpy as np
 
 from .. import parallel
-from ..common import custom_losses, custom_metrics, data_generator as data_gen, dataset_loader, h5io, utils
+from ..common import augmentation, custom_losses, custom_metrics, data_generator as data_gen, dataset_loader, h5io, utils
 from ..models import get_model_class
 from ..models.engine_model import EarlyStopping, ModelCheckpoint
 from . import training_callbacks
@@ -45,6 +45,16 @@ def save_training_params_file(save_foldername: Path, model_summary: str, model_c
         "aug_device": bool(train_params.aug_device),
         "optimizer": np.array(train_params.opt_con.__name__, dtype="S100"),
     }
+    # the geometric augmentations, in the reference file's scheme for an augmentation list (training.py:79-112): "aug_<n>" =
+    # the function's name, "aug_<n>_param: <key>" = each argument (n counts the whole list from 1)
+    if train_params.aug_mode != "none":
+        for n, (aug_fn, aug_arg) in enumerate(train_params.aug_fn_args, start=1):
+            if aug_fn not in (augmentation.column_shift_aug, augmentation.affine_aug):
+                continue
+            attrs[f"aug_{n}"] = np.array(aug_fn.__name__, dtype="S100")
+            for key, val in (aug_arg or {}).items():
+                attrs[f"aug_{n}_param: {key}"] = (np.array(val, dtype="S100") if isinstance(val, str) else
+                                                  val if np.isscalar(val) else np.asarray(val, dtype=np.float64))
     for key, val in opt.get_config().items():
         attrs["opt_param: " + key] = np.bytes_(str(val)) if isinstance(val, (dict, str)) else val
     datasets = {} if class_weight is None else {"class_weight": np.asarray(class_weight)}
