@@ -34,6 +34,7 @@
  *   oct_unet_forward_mc / oct_mc_update (none: Monte-Carlo dropout prediction; the Dropout(0.5) it keeps on is models/unet.py:130)
  *   oct_augment_batch                  BatchGenerator.get_aug_fly/_nofly common/data_generator.py:140-283,
  *                                      flip_aug / add_noise_aug       common/augmentation.py:43-103
+ *   oct_pad_batch / oct_crop_batch     (none: Keras raises on a size that is no multiple of 2^pool_layers, in the skip concatenation)
  *   oct_warp_batch                     (none at training time; the per-column np.roll of roll_image_offset /
  *                                      flatten_image_boundary        dataset_construction.py is its dataset-preparation kin)
  */
@@ -212,6 +213,14 @@ int oct_unet_dropout_mask(oct_unet* h, int B, unsigned char* mask_dev, oct_strea
 /* ---- inference hipGraph: capture one forward (training=0) with fixed buffers, then replay ---- */
 int oct_unet_graph_capture(oct_unet* h, const void* x_dev, int x_is_u8, int B, const oct_unet_io* io,
                            oct_stream_t stream);
+/* The same capture for scans of a size (H, W) that is no multiple of 2^pool_layers, around a handle built at the padded
+ * size (cfg.H, cfg.W): oct_pad_batch of x_dev (B,H,W,in_ch) into x_pad_dev (B,cfg.H,cfg.W,in_ch) at (top, left), the forward
+ * of x_pad_dev into io_pad (padded-size buffers), and one oct_crop_batch per output that io_crop asks for -- probs and / or
+ * argmax, (B,H,W[,n_cls]) -- all inside the one graph that oct_unet_graph_launch replays.  io_pad must hold every output
+ * io_crop asks for; labels are not used.  The argument errors of the three calls apply. */
+int oct_unet_graph_capture_padded(oct_unet* h, const void* x_dev, int x_is_u8, int B, int H, int W, int top, int left,
+                                  int pad_mode, float pad_value, void* x_pad_dev, const oct_unet_io* io_pad,
+                                  const oct_unet_io* io_crop, oct_stream_t stream);
 int oct_unet_graph_launch(oct_unet* h, oct_stream_t stream);
 
 /* ---- per-launch profiler: HIP events recorded around every kernel launch, on the launch stream ----
@@ -395,6 +404,30 @@ typedef struct oct_warp_op {     /* one per sample of the batch, 40 bytes, in DE
 int oct_warp_batch(const unsigned char* x_u8_dev, const unsigned char* labels_dev, const oct_warp_op* ops_dev,
                    int B, int H, int W, int C,
                    unsigned char* x_out_dev, unsigned char* labels_out_dev, oct_stream_t stream);
+
+/* ---- pad and crop on device: scans whose size is no multiple of 2^pool_layers ----
+ * oct_pad_batch places a (B,H,W,ch) batch -- uint8 (is_u8) or float32 -- at (top, left) of a (B,Hp,Wp,ch) batch of the same
+ * type and fills the frame: out[b, y, x, :] = in[b, sy(y - top), sx(x - left), :] with, on an axis of length n,
+ *   OCT_PAD_EDGE      s(i) = min(max(i, 0), n-1)                                    np.pad(mode="edge")
+ *   OCT_PAD_REFLECT   s(i) = -i for i < 0, 2(n-1) - i for i >= n, else i            np.pad(mode="reflect"): no repeated edge
+ *   OCT_PAD_CONSTANT  a pixel with i outside 0..n-1 on either axis is `value`       np.pad(mode="constant")
+ * (uint8: `value` must be a whole number in 0..255; float32: `value` itself).  Hp == H, Wp == W is a copy.
+ * oct_crop_batch is the inverse window: out[b, y, x] = in[b, y + top, x + left] over (B,Hp,Wp) pixels of `pixel_bytes`
+ * bytes each -- 1 for arg-max maps, 4 for entropy / mutual information, 4 n_cls for probabilities; the kernel moves bytes.
+ * Stand-alone: no handle, no allocation, one asynchronous launch on `stream` each, graph-capturable.  common/utils.py
+ * pad_reference / crop_reference restate them; padded_geometry there holds THE placement rule of the callers
+ * (top = (Hp - H) / 2, left = (Wp - W) / 2, floor: the odd pixel goes to the bottom / right).
+ * Errors (negative, nothing launched): null or overlapping buffers; non-positive B, H, W, ch, Hp, Wp; top or left < 0,
+ * top + H > Hp, left + W > Wp; an unknown mode; reflect with a pad >= the image's dimension on that axis; a uint8 constant
+ * that is no whole number in 0..255; float32 buffers that are not 4-byte aligned; pixel_bytes outside {1, 2, 4, 8, 12, ...,
+ * 32}; element counts that overflow the kernels' indexing (B, Hp or the bytes of a row > 2^30, a buffer >= 2^62 bytes). */
+#define OCT_PAD_EDGE     0
+#define OCT_PAD_REFLECT  1
+#define OCT_PAD_CONSTANT 2
+int oct_pad_batch(const void* src_dev, int is_u8, int B, int H, int W, int ch, int Hp, int Wp, int top, int left, int mode,
+                  float value, void* dst_dev, oct_stream_t stream);
+int oct_crop_batch(const void* src_dev, int B, int Hp, int Wp, int pixel_bytes, int H, int W, int top, int left,
+                   void* dst_dev, oct_stream_t stream);
 
 /* ---- min-path boundary search on the device ----
  * The boundary delineation of min_path_processing/graph_search.py for (B, M, H, W) uint8 boundary maps as

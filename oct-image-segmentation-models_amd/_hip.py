@@ -74,6 +74,9 @@ class McOut(C.Structure):
 
 MC_MAX_SAMPLES = 64
 
+# oct_pad_batch modes (include/oct_unet.h), by the public pad_mode names
+PAD_MODES = {"edge": 0, "reflect": 1, "constant": 2}
+
 
 # every symbol include/oct_unet.h declares: (name, restype, argtypes)
 _P = C.POINTER
@@ -107,6 +110,8 @@ SYMBOLS = [
     ("oct_unet_set_dropout_step", C.c_int, [C.c_void_p, C.c_ulonglong]),
     ("oct_unet_dropout_mask", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     ("oct_unet_graph_capture", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _P(UNetIO), C.c_void_p]),
+    ("oct_unet_graph_capture_padded", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                C.c_float, C.c_void_p, _P(UNetIO), _P(UNetIO), C.c_void_p]),
     ("oct_unet_graph_launch", C.c_int, [C.c_void_p, C.c_void_p]),
     ("oct_unet_profile_begin", C.c_int, [C.c_void_p]),
     ("oct_unet_profile_end", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _P(C.c_int)]),
@@ -123,6 +128,10 @@ SYMBOLS = [
     ("oct_augment_batch", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_ulonglong,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
     ("oct_warp_batch", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                 C.c_void_p]),
+    ("oct_pad_batch", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                C.c_float, C.c_void_p, C.c_void_p]),
+    ("oct_crop_batch", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                  C.c_void_p]),
     ("oct_minpath_workspace_bytes", C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     ("oct_minpath_device", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,

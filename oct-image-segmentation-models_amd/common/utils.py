@@ -159,6 +159,68 @@ def mc_reduce_reference(probs_stack, dtype=np.float32) -> Tuple[np.ndarray, np.n
     return m, arg, entropy, mutual_info
 
 
+PAD_MODES = ("edge", "reflect", "constant")
+
+
+def check_pad_mode(pad_mode, pad_value=0):
+    """The public ``pad_mode`` / ``pad_value`` pair, validated: ``(None | "edge" | "reflect" | "constant", float)``.
+    Anything else is a ``ValueError``."""
+    if pad_mode is not None and pad_mode not in PAD_MODES:
+        raise ValueError(f'pad_mode must be None, "edge", "reflect" or "constant", not {pad_mode!r}')
+    try:
+        value = float(pad_value)
+    except (TypeError, ValueError):
+        raise ValueError(f"pad_value must be a number, not {pad_value!r}") from None
+    if not np.isfinite(value):
+        raise ValueError(f"pad_value must be finite, not {pad_value!r}")
+    return pad_mode, value
+
+
+def padded_geometry(H: int, W: int, pool_layers: int) -> Tuple[int, int, int, int]:
+    """``(Hp, Wp, top, left)``: the smallest multiples of 2^pool_layers that hold an H x W scan, and where the scan sits in
+    them.  THE placement rule: ``top = (Hp - H) // 2``, ``left = (Wp - W) // 2`` -- the odd pixel goes to the bottom / right."""
+    m = 1 << int(pool_layers)
+    Hp, Wp = -(-int(H) // m) * m, -(-int(W) // m) * m
+    return Hp, Wp, (Hp - int(H)) // 2, (Wp - int(W)) // 2
+
+
+def pad_reference(x, Hp: int, Wp: int, top: int, left: int, mode: str, value=0) -> np.ndarray:
+    """``oct_pad_batch`` (include/oct_unet.h) restated with index arrays: (B,H,W,ch) of any dtype -> (B,Hp,Wp,ch) with the
+    input at (top, left); ``edge`` clamps the index, ``reflect`` mirrors it about the border pixel without repeating it,
+    ``constant`` writes ``value`` (cast to the input's dtype) outside.  Equal to ``np.pad`` of the two image axes."""
+    x = np.asarray(x)
+    B, H, W = x.shape[:3]
+    if mode not in PAD_MODES:
+        raise ValueError(f"pad_reference: unknown mode {mode!r}")
+    if top < 0 or left < 0 or top + H > Hp or left + W > Wp:
+        raise ValueError("pad_reference: the image does not fit")
+
+    def index(n_out, n, off):
+        i = np.arange(n_out) - off
+        if mode == "edge":
+            return np.clip(i, 0, n - 1), np.ones(n_out, bool)
+        if mode == "reflect":
+            if off >= n or n_out - off - n >= n:
+                raise ValueError("pad_reference: reflect needs every pad smaller than the dimension")
+            return np.where(i < 0, -i, np.where(i >= n, 2 * (n - 1) - i, i)), np.ones(n_out, bool)
+        return np.clip(i, 0, n - 1), (i >= 0) & (i < n)
+
+    (iy, oky), (ix, okx) = index(Hp, H, top), index(Wp, W, left)
+    out = x[:, iy][:, :, ix]
+    if mode == "constant":
+        inside = oky[:, None] & okx[None, :]
+        out[:, ~inside] = np.asarray(value).astype(x.dtype)
+    return np.ascontiguousarray(out)
+
+
+def crop_reference(t, H: int, W: int, top: int, left: int) -> np.ndarray:
+    """``oct_crop_batch`` restated: the (B,H,W,...) window at (top, left) of a (B,Hp,Wp,...) array, contiguous."""
+    t = np.asarray(t)
+    if top < 0 or left < 0 or top + H > t.shape[1] or left + W > t.shape[2]:
+        raise ValueError("crop_reference: the window does not fit")
+    return np.ascontiguousarray(t[:, top:top + H, left:left + W])
+
+
 def entropy_to_u8(entropy, num_classes: int) -> np.ndarray:
     """Predictive entropy (nats) -> uint8 gray levels for ``uncertainty_map.png``: floor(min(entropy / ln C, 1) * 255 + 0.5),
     so 255 is the entropy of the uniform distribution over the ``num_classes`` classes."""

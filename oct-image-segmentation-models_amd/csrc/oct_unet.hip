@@ -1297,6 +1297,35 @@ int oct_unet_graph_capture(oct_unet* h, const void* x, int x_is_u8, int B, const
     return 0;
 }
 
+int oct_unet_graph_capture_padded(oct_unet* h, const void* x, int x_is_u8, int B, int H, int W, int top, int left, int pad_mode,
+                                  float pad_value, void* x_pad, const oct_unet_io* io_pad, const oct_unet_io* io_crop,
+                                  oct_stream_t stream) {
+    if (!h || !x || !x_pad || !io_pad || !io_crop) return fail(-1, "null handle, input, padded input or io");
+    if (B < 1 || B > h->cfg.max_batch) return fail(-1, "B out of range (1..max_batch)");
+    if ((io_crop->probs && !io_pad->probs) || (io_crop->argmax && !io_pad->argmax))
+        return fail(-1, "graph_capture_padded: io_crop asks for an output that io_pad does not hold");
+    hipStream_t s = (hipStream_t)stream;
+    if (!s) return fail(-1, "graph capture needs a non-default stream");
+    if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
+    if (h->graph) { (void)hipGraphDestroy(h->graph); h->graph = nullptr; }
+    t_prof = nullptr;  // no event records inside a capture
+    const int Hp = h->cfg.H, Wp = h->cfg.W;
+    oct_unet_io io = *io_pad;
+    io.labels = nullptr;
+    HIP_OK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    int rc = oct_pad_batch(x, x_is_u8, B, H, W, h->cfg.in_ch, Hp, Wp, top, left, pad_mode, pad_value, x_pad, s);
+    if (!rc) rc = forward_impl(h, x_pad, x_is_u8, B, 0, &io, s);
+    if (!rc && io_crop->probs)
+        rc = oct_crop_batch(io.probs, B, Hp, Wp, h->cfg.n_cls * (int)sizeof(float), H, W, top, left, io_crop->probs, s);
+    if (!rc && io_crop->argmax) rc = oct_crop_batch(io.argmax, B, Hp, Wp, 1, H, W, top, left, io_crop->argmax, s);
+    const std::string msg = rc ? oct_last_error() : "";
+    hipError_t e = hipStreamEndCapture(s, &h->graph);
+    if (rc) return fail(rc, msg);
+    if (e != hipSuccess) return fail(-5, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
+    HIP_OK(hipGraphInstantiate(&h->graph_exec, h->graph, nullptr, nullptr, 0));
+    return 0;
+}
+
 int oct_unet_graph_launch(oct_unet* h, oct_stream_t stream) {
     if (!h || !h->graph_exec) return fail(-1, "no captured graph");
     HIP_OK(hipGraphLaunch(h->graph_exec, (hipStream_t)stream));

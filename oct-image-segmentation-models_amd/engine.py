@@ -474,6 +474,63 @@ class UNetEngine:
                   self._stream())
         return x_out, (lab_out if labels is not None else None)
 
+    # ---- pad and crop: scans whose size is no multiple of 2^pool_layers ------------------------------
+    def pad(self, x: torch.Tensor, Hp: int, Wp: int, top: int, left: int, mode: str, value=0, out=None) -> torch.Tensor:
+        """(B,H,W,ch) uint8 or float32 -> (B,Hp,Wp,ch) of the same type with ``x`` at (top, left) and the frame filled by
+        ``mode`` -- ``"edge"``, ``"reflect"`` or ``"constant"`` (``value``) -- on the device (``oct_pad_batch``;
+        ``common.utils.pad_reference`` restates it).  ``out``: optional tensor to write into.  Asynchronous on the
+        current stream."""
+        _hip.expect(x, "pad: x (B,H,W,ch)", device=self.device, dtype=(torch.uint8, torch.float32), shape=(None, None, None, None))
+        if mode not in _hip.PAD_MODES:
+            raise OctError(f'pad: mode must be "edge", "reflect" or "constant", not {mode!r}')
+        B, H, W, ch = x.shape
+        if out is None:
+            out = torch.empty((B, int(Hp), int(Wp), ch), dtype=x.dtype, device=self.device)
+        _hip.expect(out, "pad: out", device=self.device, dtype=x.dtype, shape=(B, int(Hp), int(Wp), ch))
+        _hip.call("oct_pad_batch", self.device, x.data_ptr(), int(x.dtype == torch.uint8), B, H, W, ch, int(Hp), int(Wp), int(top),
+                  int(left), _hip.PAD_MODES[mode], float(value), out.data_ptr(), self._stream())
+        return out
+
+    def crop(self, t: torch.Tensor, H: int, W: int, top: int, left: int, out=None) -> torch.Tensor:
+        """(B,Hp,Wp[,C]) uint8 or float32 -> its (B,H,W[,C]) window at (top, left), on the device (``oct_crop_batch``, one
+        byte-generic kernel; ``common.utils.crop_reference`` restates it).  ``out``: optional tensor to write into.
+        Asynchronous on the current stream."""
+        if t.dim() not in (3, 4):
+            raise OctError(f"crop: t must be (B,Hp,Wp) or (B,Hp,Wp,C), not {tuple(t.shape)}")
+        _hip.expect(t, "crop: t (B,Hp,Wp[,C])", device=self.device, dtype=(torch.uint8, torch.float32), shape=(None,) * t.dim())
+        B, Hp, Wp = t.shape[:3]
+        shape = (B, int(H), int(W)) + tuple(t.shape[3:])
+        if out is None:
+            out = torch.empty(shape, dtype=t.dtype, device=self.device)
+        _hip.expect(out, "crop: out", device=self.device, dtype=t.dtype, shape=shape)
+        _hip.call("oct_crop_batch", self.device, t.data_ptr(), B, Hp, Wp, t.element_size() * int(np.prod(t.shape[3:], dtype=np.int64)),
+                  int(H), int(W), int(top), int(left), out.data_ptr(), self._stream())
+        return out
+
+    def graph_capture_padded(self, x: torch.Tensor, top: int, left: int, mode: str, value=0, want_probs=True, want_argmax=False):
+        """``graph_capture`` for scans of a size that is no multiple of 2^pool_layers, on an engine built at the padded
+        size: captures ``pad`` of the fixed (B,H,W,ch) input ``x`` at (top, left), the forward and the ``crop`` of every
+        output into ONE graph (``oct_unet_graph_capture_padded``); returns the (probs, argmax) tensors of size (H, W) that
+        every ``graph_launch`` refills.  ``x`` must be refilled in place between launches."""
+        _hip.expect(x, "input", device=self.device, dtype=(torch.uint8, torch.float32), shape=(None, None, None, self.cfg.in_ch))
+        if mode not in _hip.PAD_MODES:
+            raise OctError(f'graph_capture_padded: mode must be "edge", "reflect" or "constant", not {mode!r}')
+        B, H, W, _ = x.shape
+        if not 1 <= B <= self.cfg.max_batch:
+            raise OctError(f"batch {B} outside 1..max_batch={self.cfg.max_batch}")
+        x_pad = torch.empty((B, self.cfg.H, self.cfg.W, self.cfg.in_ch), dtype=x.dtype, device=self.device)
+        io_pad, probs_pad, am_pad = self._io(B, None, want_probs, want_argmax)
+        probs = torch.empty((B, H, W, self.cfg.n_cls), dtype=torch.float32, device=self.device) if want_probs else None
+        am = torch.empty((B, H, W), dtype=torch.uint8, device=self.device) if want_argmax else None
+        io_crop = UNetIO(probs.data_ptr() if probs is not None else None, am.data_ptr() if am is not None else None, None)
+        self._graph_keep = [x, x_pad, probs_pad, am_pad, probs, am]
+        s = torch.cuda.Stream(self.device)
+        s.wait_stream(torch.cuda.current_stream(self.device))
+        self._call("oct_unet_graph_capture_padded", x.data_ptr(), int(x.dtype == torch.uint8), B, H, W, int(top), int(left),
+                   _hip.PAD_MODES[mode], float(value), x_pad.data_ptr(), C.byref(io_pad), C.byref(io_crop), C.c_void_p(s.cuda_stream))
+        torch.cuda.current_stream(self.device).wait_stream(s)
+        return probs, am
+
     # ---- weights exchange --------------------------------------------------------------------------
     def get_weights(self) -> List[np.ndarray]:
         """Keras ``get_weights()`` order: Conv2D [kernel HWIO, bias]; BN [gamma, beta, moving_mean, moving_var]."""

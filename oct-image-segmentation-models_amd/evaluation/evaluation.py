@@ -158,7 +158,8 @@ def evaluate_model(eval_params: EvaluationParameters) -> List[EvaluationOutput]:
                       gt=gt_maps, surface=want_surface, confusion=metrics_device and want_dice,
                       graph_search=eval_params.graph_search, gsgrad=eval_params.gsgrad, gs_device=eval_params.gs_device,
                       gs_device_ties=eval_params.gs_device_ties, gs_workers=eval_params.gs_workers,
-                      soft_maps=not getattr(eval_params, "binarize", True)) as run:
+                      soft_maps=not getattr(eval_params, "binarize", True),
+                      pad_mode=getattr(eval_params, "pad_mode", None), pad_value=getattr(eval_params, "pad_value", 0)) as run:
         t_prev = time.time()
         for batch in run:
             b0, b1 = lo + batch.lo, lo + batch.hi
@@ -288,6 +289,9 @@ def save_eval_config_file(eval_params: EvaluationParameters):
         attrs["binarize"] = np.array(False)      # recorded only when it departs from the default: binarize=True files stay as they were
     if getattr(eval_params, "png_plots", False):
         attrs["png_plots"] = np.array(True)      # likewise
+    if getattr(eval_params, "pad_mode", None) is not None:
+        attrs["pad_mode"] = np.array(str(eval_params.pad_mode), dtype="S1000")      # likewise, with the constant
+        attrs["pad_value"] = np.array(float(getattr(eval_params, "pad_value", 0)))
     h5io.save(eval_params.save_foldername / Path("eval_params.hdf5"), {}, attrs)
 
 

@@ -26,7 +26,13 @@ class EvaluationParameters:
                  graph_search: bool, metrics: List[str], gsgrad=1, dice_errors: bool = True, binarize: bool = True,
                  bg_ilm: bool = True, bg_csi: bool = False, batch_size: int = 32, gs_device: bool = False,
                  gs_device_ties: str = "host", gs_workers: Optional[int] = None, metrics_device: bool = False,
-                 png_plots: bool = False):
+                 png_plots: bool = False, pad_mode: Optional[str] = None, pad_value=0):
+        # extension: scans whose size is no multiple of 2^pool_layers (the reference raises on them) are padded on the
+        # device in front of the forward -- "edge", "reflect" or "constant" with pad_value in raw counts -- and the arg-max
+        # maps (with binarize=False the probabilities too) are cropped directly behind the head: metrics, searches, files
+        # and pictures have the scans' own size.  None: such sizes are refused.  Sizes that are multiples are never padded;
+        # the engine follows the dataset's size, whatever model_config.json records
+        self.pad_mode, self.pad_value = utils.check_pad_mode(pad_mode, pad_value)
         self.model_path = Path(model_path)
         self.mlflow_tracking_uri = mlflow_tracking_uri
         self.mlflow_run_uuid = mlflow_run_uuid

@@ -15,6 +15,7 @@ from typing import Iterable, Iterator, NamedTuple, Optional, Tuple
 import numpy as np
 import torch
 
+from ..common.utils import check_pad_mode, padded_geometry
 from ..min_path_processing.device_search import DeviceMinPath, LazyPool, merge_ties
 from ..min_path_processing.pool import SegmentPool, default_workers
 from .dice_device import ConfusionCounts, DelineationLabels
@@ -99,21 +100,38 @@ class BatchedPredictor:
     probabilities are then those of the MEAN prediction, everything behind them is unchanged, and ``Batch.entropy`` /
     ``Batch.mutual_info`` carry the two uncertainty maps, downloaded through pinned double buffers like the labels.  The
     dropout stream is indexed by the position in the batch's bottleneck tensor and seeded per rank: an image's result
-    depends on its position in its batch and on the rank that predicts it."""
+    depends on its position in its batch and on the rank that predicts it.
+
+    With ``hw`` -- the images' true size (H, W), no multiple of 2^pool_layers -- and a ``pad_mode`` ("edge", "reflect" or
+    "constant" with ``pad_value``) the engine is one built at the padded size (``common.utils.padded_geometry``): the
+    captured graph is then ``oct_pad_batch`` of the true-size input, the forward and ``oct_crop_batch`` of the arg-max maps
+    (and of the probabilities with ``soft_maps``), the pinned upload buffers and everything behind the graph are true-size,
+    and every stage runs on the cropped tensors.  A Monte-Carlo batch pads in front of ``forward_mc`` and crops its arg-max,
+    entropy, mutual information and mean probabilities.  Without ``hw`` nothing is launched that was not before."""
 
     def __init__(self, engine, batch: int, want_maps: bool = True, bg_ilm: bool = True, bg_csi: bool = False,
-                 surface=None, minpath=None, confusion=None, soft_maps: bool = False, mc_samples: int = 0, mc_step0: int = 0):
+                 surface=None, minpath=None, confusion=None, soft_maps: bool = False, mc_samples: int = 0, mc_step0: int = 0,
+                 hw=None, pad_mode: Optional[str] = None, pad_value=0):
         if soft_maps and not want_maps:
             raise ValueError("soft_maps: needs want_maps=True")
         if not 0 <= int(mc_samples) <= 64:
             raise ValueError(f"mc_samples must be in 0..64, not {mc_samples}")
+        self.pad_mode, self.pad_value = check_pad_mode(pad_mode, pad_value)
         self.soft_maps, self.mc_samples, self.mc_step0 = bool(soft_maps), int(mc_samples), int(mc_step0)
         if not 1 <= batch <= engine.cfg.max_batch:
             raise ValueError(f"batch {batch} outside 1..max_batch={engine.cfg.max_batch}")
         self.eng, self.B, self.want_maps, self.bg = engine, int(batch), want_maps, (bg_ilm, bg_csi)
         dev, H, W, C = engine.device, engine.cfg.H, engine.cfg.W, engine.cfg.n_cls
         ic = engine.cfg.in_ch
-        self.x_dev = torch.zeros((self.B, H, W, ic), dtype=torch.uint8, device=dev)       # the graph's fixed input
+        self.at = None                                      # (top, left) of the images inside the engine's geometry, if padded
+        if hw is not None and (int(hw[0]), int(hw[1])) != (H, W):
+            Hp, Wp, top, left = padded_geometry(int(hw[0]), int(hw[1]), engine.cfg.pool_layers)
+            if self.pad_mode is None or (Hp, Wp) != (H, W):
+                raise ValueError(f"images of {hw[0]}x{hw[1]} on an engine built for {H}x{W}: needs a pad_mode and the engine of "
+                                 f"the padded size {Hp}x{Wp}")
+            (H, W), self.at = (int(hw[0]), int(hw[1])), (top, left)
+        self.hw = (H, W)
+        self.x_dev = torch.zeros((self.B, H, W, ic), dtype=torch.uint8, device=dev)       # the graph's fixed input (true size)
         self.x_stage = [torch.empty_like(self.x_dev) for _ in range(2)]                    # H2D landing buffers
         self.x_pin = [torch.empty((self.B, H, W, ic), dtype=torch.uint8).pin_memory() for _ in range(2)]
         self.lab_pin = [torch.empty((self.B, H, W), dtype=torch.uint8).pin_memory() for _ in range(2)]
@@ -141,6 +159,16 @@ class BatchedPredictor:
             self.unc_dev = [tuple(torch.empty((self.B, H, W), dtype=torch.float32, device=dev) for _ in range(2)) for _ in range(2)]
             self.unc_pin = [tuple(torch.empty((self.B, H, W), dtype=torch.float32).pin_memory() for _ in range(2)) for _ in range(2)]
             self.probs = self.am = None                     # the engine's forward_mc buffers: set by every batch
+            if self.at is not None:                         # the padded input and the crops' own buffers: made once, kept
+                f32 = dict(dtype=torch.float32, device=dev)
+                self.x_pad = torch.empty((self.B, engine.cfg.H, engine.cfg.W, ic), dtype=torch.uint8, device=dev)
+                self.mc_crop = dict(argmax=torch.empty((self.B, H, W), dtype=torch.uint8, device=dev),
+                                    entropy=torch.empty((self.B, H, W), **f32), mutual_info=torch.empty((self.B, H, W), **f32))
+                if self.soft_maps:
+                    self.mc_crop["mean_probs"] = torch.empty((self.B, H, W, C), **f32)
+        elif self.at is not None:
+            self.probs, self.am = engine.graph_capture_padded(self.x_dev, *self.at, self.pad_mode, self.pad_value,
+                                                              want_probs=self.soft_maps, want_argmax=True)
         else:
             self.probs, self.am = engine.graph_capture(self.x_dev, want_probs=self.soft_maps, want_argmax=True)
 
@@ -196,7 +224,12 @@ class BatchedPredictor:
             x_free[s].record(main)
             mc = None
             if self.mc_samples:
-                mc = eng.forward_mc(self.x_dev, self.mc_samples, step0=self.mc_step0, want_mean_probs=self.soft_maps)
+                x_in = self.x_dev
+                if self.at is not None:
+                    x_in = eng.pad(self.x_dev, eng.cfg.H, eng.cfg.W, *self.at, self.pad_mode, self.pad_value, out=self.x_pad)
+                mc = eng.forward_mc(x_in, self.mc_samples, step0=self.mc_step0, want_mean_probs=self.soft_maps)
+                if self.at is not None:
+                    mc = {k: eng.crop(t, *self.hw, *self.at, out=self.mc_crop[k]) for k, t in mc.items()}
                 self.am, self.probs = mc["argmax"], mc.get("mean_probs")
             else:
                 eng.graph_launch()
@@ -250,10 +283,13 @@ class BatchedPredictor:
 
 
 def host_batches(model, images: np.ndarray, batch: int, *, gt_u8: Optional[np.ndarray] = None, surface=None,
-                 minpath=None, confusion=None, soft_maps: bool = False, mc_samples: int = 0, mc_step0: int = 0) -> Iterator[Batch]:
+                 minpath=None, confusion=None, soft_maps: bool = False, mc_samples: int = 0, mc_step0: int = 0,
+                 pad_mode: Optional[str] = None, pad_value=0) -> Iterator[Batch]:
     """The same records for images that are not uint8: x / 255 on the host (``Model.predict_labels``), one synchronous
     forward per batch, no overlap.  ``surface`` / ``minpath`` / ``confusion`` / ``soft_maps`` / ``mc_samples`` /
-    ``mc_step0`` as in ``BatchedPredictor``; each stage writes its own output buffers."""
+    ``mc_step0`` as in ``BatchedPredictor``; each stage writes its own output buffers.  ``pad_mode`` / ``pad_value`` (in raw
+    counts) go to ``Model.predict_labels``, which pads and crops on the device."""
+    pad_mode, pad_value = check_pad_mode(pad_mode, pad_value)
     stages = _stages(surface, confusion, minpath, have_gt=gt_u8 is not None)
     on_labels, on_maps = any(not st.on_maps for st in stages), any(st.on_maps for st in stages)
 
@@ -263,7 +299,8 @@ def host_batches(model, images: np.ndarray, batch: int, *, gt_u8: Optional[np.nd
     for lo in range(0, images.shape[0], batch):
         hi = min(lo + batch, images.shape[0])
         labels, maps, *unc = model.predict_labels(images[lo:hi], batch_size=batch, want_maps=True, bg_ilm=True, bg_csi=False,
-                                                  soft_maps=soft_maps, mc_samples=mc_samples, mc_step0=mc_step0)
+                                                  soft_maps=soft_maps, mc_samples=mc_samples, mc_step0=mc_step0,
+                                                  pad_mode=pad_mode, pad_value=pad_value)
         lab_dev, gt_dev = (upload(labels.astype(np.uint8)), upload(gt_u8[lo:hi])) if on_labels else (None, None)
         maps_dev = upload(maps) if on_maps else None
         fields = {}
@@ -294,12 +331,20 @@ class InferenceRun:
     ``Batch.labels`` / ``Batch.maps`` are those of the mean prediction, and ``Batch.entropy`` / ``Batch.mutual_info`` are
     filled (see ``BatchedPredictor`` for what the result depends on).
 
+    The engine follows the images: the model is asked for the engine of ``images.shape[1:3]``, whatever its config
+    records.  ``pad_mode`` ("edge", "reflect", "constant" with ``pad_value`` in raw counts; None: off) admits sizes that are
+    no multiple of 2^pool_layers: the engine is then the one of the padded size, the source pads in front of the forward and
+    crops directly behind the head, and every stage, search and picture works at the true size.  For sizes that are
+    multiples nothing changes and nothing more is launched.
+
     ``batches`` replaces the model by a ready source of records (tests of the host side: no device is touched)."""
 
     def __init__(self, model, images: np.ndarray, batch: int, num_classes: int, *, gt: Optional[np.ndarray] = None,
                  graph_search: bool = False, gsgrad: int = 1, gs_device: bool = False, gs_device_ties: str = "host",
                  gs_workers: Optional[int] = None, batches: Optional[Iterable[Batch]] = None, surface: bool = True,
-                 confusion: bool = False, soft_maps: bool = False, mc_samples: int = 0, mc_step0: int = 0):
+                 confusion: bool = False, soft_maps: bool = False, mc_samples: int = 0, mc_step0: int = 0,
+                 pad_mode: Optional[str] = None, pad_value=0):
+        pad_mode, pad_value = check_pad_mode(pad_mode, pad_value)
         n, (H, W), C = images.shape[0], images.shape[1:3], int(num_classes)
         self.pool = self.host_ties = None
         self._gs = self._gs_geom = None                   # gs_labels' own device buffers: made by its first call
@@ -320,6 +365,7 @@ class InferenceRun:
             return
         try:
             bs, dev = max(1, min(int(batch), n)), model._dev()
+            geom, _ = model._geometry((H, W), pad_mode)      # refuses a size that is no multiple, before anything is built
             self._gs_geom = (bs, H, W, C, dev)
             minpath = DeviceMinPath(bs, C - 1, H, W, gsgrad, dev) if self.host_ties is not None else None
             surface = SurfaceDistances(bs, H, W, C, dev) if gt_u8 is not None and surface else None
@@ -327,14 +373,15 @@ class InferenceRun:
             if surface is None and confusion is None:
                 gt_u8 = None
             if images.dtype == np.uint8:
-                predictor = BatchedPredictor(model._ensure_engine(bs, False), bs, want_maps=True, bg_ilm=True, bg_csi=False,
-                                             surface=surface, minpath=minpath, confusion=confusion,
-                                             soft_maps=soft_maps, mc_samples=mc_samples, mc_step0=mc_step0)
+                predictor = BatchedPredictor(model._ensure_engine(bs, False, hw=geom), bs, want_maps=True, bg_ilm=True,
+                                             bg_csi=False, surface=surface, minpath=minpath, confusion=confusion,
+                                             soft_maps=soft_maps, mc_samples=mc_samples, mc_step0=mc_step0,
+                                             hw=(H, W), pad_mode=pad_mode, pad_value=pad_value)
                 self._batches = predictor.run(images, gt_u8)
             else:
                 self._batches = host_batches(model, images, bs, gt_u8=gt_u8, surface=surface, minpath=minpath,
                                              confusion=confusion, soft_maps=soft_maps, mc_samples=mc_samples,
-                                             mc_step0=mc_step0)
+                                             mc_step0=mc_step0, pad_mode=pad_mode, pad_value=pad_value)
         except BaseException:
             self.close()
             raise

@@ -111,8 +111,13 @@ class Model:
         self.stop_training = False
         self.optimizer = None
         self._loss_name = self._metric_name = None
-        self._engine = None
+        self._engine = None             # the ACTIVE engine: the one that holds the model's current weights
+        self._engines = {}              # the geometry cache: {"train": engine, "other": engine}, at most these two
+        self._wver = 0                  # version of the model's weights; an engine's _wver says which version it holds
         self._pending_weights = None
+        # the model's default for predict / predict_mc / predict_labels on sizes that are no multiple of 2^pool_layers:
+        # None (refuse them), "edge", "reflect" or "constant" with pad_value; a call's own pad_mode goes first
+        self.pad_mode, self.pad_value = None, 0
         self._device = device
         self.history = None
 
@@ -123,35 +128,94 @@ class Model:
         _, local_rank, _ = parallel.env_rank()
         return torch.device("cuda", local_rank if torch.cuda.is_available() and local_rank < max(torch.cuda.device_count(), 1) else 0)
 
-    def _ensure_engine(self, batch: int, training: bool):
+    def _geometry(self, hw=None, pad_mode=None):
+        """The engine geometry for images of size ``hw`` (None: the config's) and where they sit in it:
+        ``((He, We), None)`` for a size that is a multiple of 2^pool_layers, ``((Hp, Wp), (top, left))`` for another one
+        under a ``pad_mode``, and an ``OctError`` for another one without."""
+        from ..common.utils import padded_geometry
+        c = self.config
+        H, W = (int(c["image_height"]), int(c["image_width"])) if hw is None else (int(hw[0]), int(hw[1]))
+        m = 1 << int(c.get("pool_layers", 4))
+        if H < 1 or W < 1:
+            raise OctError(f"image size {H}x{W}: both dimensions must be positive")
+        if H % m == 0 and W % m == 0:
+            return (H, W), None
+        if pad_mode is None:
+            raise OctError(f"image size {H}x{W} is not a multiple of {m} (2^pool_layers) in both dimensions: crop or pad the "
+                           f"images, or predict with pad_mode='edge' | 'reflect' | 'constant' to pad them on the device "
+                           f"(pad_mode is None)")
+        Hp, Wp, top, left = padded_geometry(H, W, c.get("pool_layers", 4))
+        return (Hp, Wp), (top, left)
+
+    def _mark_changed(self, eng) -> None:
+        """``eng`` -- the active engine -- has changed the model's weights (an optimizer step, ``set_weights``, the moving
+        statistics of a training forward): every other cached engine is stale from here on."""
+        self._wver += 1
+        eng._wver = self._wver
+
+    def _activate(self, eng):
+        """Make ``eng`` the active engine; if another engine changed the weights since ``eng`` last held them, they move
+        first: a device-to-device copy of the two flat tensors, whose layout does not depend on H, W."""
+        cur = self._engine
+        if cur is not None and cur is not eng and getattr(eng, "_wver", -1) != self._wver:
+            eng.params.copy_(cur.params); eng.state.copy_(cur.state)
+        eng._wver = self._wver
+        self._engine = eng
+        return eng
+
+    def _ensure_engine(self, batch: int, training: bool, hw=None):
+        """The engine for ``batch`` images of size ``hw`` -- (H, W), a multiple of 2^pool_layers; None: the config's
+        geometry -- holding the model's current weights.  Engines are cached by geometry, at most two: the most recent
+        training engine and the most recent other one (a training engine also serves inference at its geometry)."""
         from ..engine import UNetEngine
-        e = self._engine
-        if e is not None and e.cfg.max_batch >= batch and (e.cfg.training or not training):
-            return e
-        weights = e.get_weights() if e is not None else self._pending_weights
-        opt_state = None if e is None else (e._opt, e.opt_step)
+        (H, W), _ = self._geometry(hw)
+        fits = lambda e: (e.cfg.H, e.cfg.W) == (H, W)       # noqa: E731
+        serves = lambda e: fits(e) and e.cfg.max_batch >= batch and (e.cfg.training or not training)      # noqa: E731
+        cache = self._engines
+        for e in (self._engine, cache.get("train"), cache.get("other")):
+            if e is not None and serves(e):
+                return self._activate(e)
+        # build: a cached engine of this geometry is replaced (its batch and its training flag are kept)
+        old = [e for e in cache.values() if fits(e)]
+        max_batch = max([batch] + [e.cfg.max_batch for e in old])
+        training = training or any(bool(e.cfg.training) for e in old)
         rank, _, _ = parallel.env_rank()
         c = self.config
-        self._engine = UNetEngine(
+        new = UNetEngine(
             device=self._dev(), input_channels=c["input_channels"], num_classes=c["num_classes"],
-            image_height=c["image_height"], image_width=c["image_width"],
+            image_height=H, image_width=W,
             start_neurons=c.get("start_neurons", 8), pool_layers=c.get("pool_layers", 4),
             conv_layers=c.get("conv_layers", 2), enc_kernel=tuple(c.get("enc_kernel", (3, 3))),
             dec_kernel=tuple(c.get("dec_kernel", (2, 2))),
-            max_batch=max(batch, e.cfg.max_batch if e is not None else 1),
-            training=training or (e is not None and bool(e.cfg.training)),
+            max_batch=max_batch, training=training,
             seed=int(c.get("seed", 0)) * 1000003 + rank, init_seed=int(c.get("seed", 0)),
             dtype=c.get("dtype", "float32"))   # extension key: 'bfloat16' = bf16 activation storage (BASELINE configs[2])
-        if weights is not None:
-            self._engine.set_weights(weights)
-        if opt_state is not None:
-            self._engine._opt, self._engine.opt_step = opt_state
+        cur = self._engine
+        if cur is None and self._pending_weights is not None:
+            new.set_weights(self._pending_weights)
         self._pending_weights = None
-        return self._engine
+        if training:
+            # the optimizer slots follow the training engine; failing one, the engine of this geometry that is replaced
+            donor = cache.get("train") or next(iter(old), None)
+            if donor is not None:
+                new._opt, new.opt_step = donor._opt, donor.opt_step
+        for k in [k for k, e in cache.items() if fits(e)]:
+            del cache[k]
+        cache["train" if training else "other"] = new
+        return self._activate(new)
+
+    def release_engines(self) -> None:
+        """Drop every cached engine (their device memory goes back once nothing else refers to them).  The model keeps its
+        weights -- the next use builds an engine and loads them -- but not the optimizer slots."""
+        if self._engine is not None:
+            self._pending_weights = self._engine.get_weights()
+        self._engine = None
+        self._engines = {}
+        self.__dict__.pop("_reducer", None)
 
     @property
     def engine(self):
-        return self._ensure_engine(1, False)
+        return self._engine if self._engine is not None else self._ensure_engine(1, False)
 
     # ---- keras.Model surface -------------------------------------------------------------------------
     def compile(self, optimizer=None, loss=None, metrics=None, **kwargs):
@@ -209,6 +273,7 @@ class Model:
             self._pending_weights = [np.asarray(w, np.float32) for w in weights]
         else:
             self._engine.set_weights(weights)
+            self._mark_changed(self._engine)
 
     def save(self, filepath, **kwargs) -> Path:
         """Write architecture config + weights (Keras ``get_weights()`` order).  A ``.h5`` / ``.hdf5`` path is
@@ -359,7 +424,7 @@ class Model:
                 torch.cuda.current_stream(x.device).wait_event(ready)
             if i + 1 < n:
                 nxt = queue(i + 1)
-            eng = self._ensure_engine(x.shape[0], training)
+            eng = self._ensure_engine(x.shape[0], training, hw=tuple(x.shape[1:3]))     # validation data may have another size
             if ops is not None:
                 x, lab = self._augment(eng, seq, x, lab, ops, *wops)
             if focal:      # (re)selected per batch: _ensure_engine may have built a new engine
@@ -379,6 +444,7 @@ class Model:
                 # backward + all-reduce (the decoder half on a side stream under the encoder backward)
                 red.backward_and_reduce(lab, macro=macro, loss_scale=1.0 / world)
                 self.optimizer.apply(eng)
+                self._mark_changed(eng)      # (the training forward's moving statistics included)
             acc = loss4.clone() if acc is None else acc + loss4
             self._release(i % 3)
         if acc is None:
@@ -436,18 +502,43 @@ class Model:
         return [logs.get("loss")] + ([logs[self._metric_name]] if self._metric_name else [])
 
     # ---- inference --------------------------------------------------------------------------------------
-    def predict(self, x, verbose=0, batch_size: Optional[int] = None, **kwargs) -> np.ndarray:
-        """(n,H,W,C) float input ALREADY preprocessed to [0,1] (or raw uint8) -> (n,H,W,num_classes) float32."""
+    def _pad_options(self, pad_mode, pad_value):
+        """The validated (pad_mode, pad_value) of a call: its own, or with ``pad_mode=None`` the model's attributes."""
+        from ..common.utils import check_pad_mode
+        if pad_mode is None:
+            pad_mode, pad_value = self.pad_mode, self.pad_value
+        return check_pad_mode(pad_mode, pad_value)
+
+    def _inference_engine(self, batch: int, hw, pad_mode=None):
+        """``(engine, at)`` for inference on ``batch`` images of size ``hw``: the engine of that geometry and ``at = None``
+        -- or, for a size that is no multiple of 2^pool_layers under a ``pad_mode``, the engine of the padded geometry and
+        ``at = (top, left)``, where ``UNetEngine.pad`` places the images and ``UNetEngine.crop`` finds the outputs."""
+        geom, at = self._geometry(hw, pad_mode)
+        return self._ensure_engine(batch, False, hw=geom), at
+
+    def predict(self, x, verbose=0, batch_size: Optional[int] = None, pad_mode: Optional[str] = None, pad_value=0,
+                **kwargs) -> np.ndarray:
+        """(n,H,W,C) float input ALREADY preprocessed to [0,1] (or raw uint8) -> (n,H,W,num_classes) float32.  The engine
+        follows the images' size, whatever the config records.  A size that is no multiple of 2^pool_layers needs
+        ``pad_mode`` ("edge", "reflect" or "constant" with ``pad_value``, in the units of ``x``): the batch is padded on
+        the device in front of the forward and the output cropped behind it (placement: ``common.utils.padded_geometry``).
+        ``pad_mode=None`` takes the model's ``pad_mode`` / ``pad_value`` attributes, which are None / 0 unless set."""
+        pad_mode, pad_value = self._pad_options(pad_mode, pad_value)
         x = np.asarray(x)
         if x.dtype != np.uint8:
             x = np.ascontiguousarray(x, dtype=np.float32)   # Keras casts the float64 the reference passes to float32
         n = x.shape[0]
         bs = int(batch_size or min(n, 32))
-        eng = self._ensure_engine(min(bs, n), False)
-        out = np.empty((n,) + tuple(x.shape[1:3]) + (self.config["num_classes"],), np.float32)
+        (H, W) = x.shape[1:3]
+        eng, at = self._inference_engine(min(bs, n), (H, W), pad_mode)
+        out = np.empty((n, H, W, self.config["num_classes"]), np.float32)
         for lo in range(0, n, bs):
             xb = torch.from_numpy(np.ascontiguousarray(x[lo:lo + bs])).to(eng.device)
+            if at is not None:
+                xb = eng.pad(xb, eng.cfg.H, eng.cfg.W, *at, pad_mode, pad_value)
             probs, _ = eng.forward(xb, training=False)
+            if at is not None:
+                probs = eng.crop(probs, H, W, *at)
             out[lo:lo + bs] = probs.cpu().numpy()
         return out
 
@@ -456,50 +547,70 @@ class Model:
         steps ``step0 .. step0+samples-1``, the same for every batch; ``UNetEngine.forward_mc``), reduced on the device.
         Input as for ``predict``; returns ``(mean_probs (n,H,W,num_classes), entropy (n,H,W), mutual_info (n,H,W))``
         float32.  The dropout stream is indexed by the element's position in the bottleneck tensor of its BATCH and seeded
-        per rank, so an image's result depends on its position in its batch (hence on ``batch_size``) and on the rank."""
+        per rank, so an image's result depends on its position in its batch (hence on ``batch_size``) and on the rank.
+        Padding as for ``predict``, from the model's ``pad_mode`` / ``pad_value`` attributes (this method's parameter list
+        is fixed): the three maps are cropped on the device."""
+        pad_mode, pad_value = self._pad_options(None, 0)
         x = np.asarray(x)
         if x.dtype != np.uint8:
             x = np.ascontiguousarray(x, dtype=np.float32)
         n = x.shape[0]
         bs = int(batch_size or min(n, 32))
-        eng = self._ensure_engine(min(bs, n), False)
-        mean = np.empty((n,) + tuple(x.shape[1:3]) + (self.config["num_classes"],), np.float32)
+        (H, W) = x.shape[1:3]
+        eng, at = self._inference_engine(min(bs, n), (H, W), pad_mode)
+        mean = np.empty((n, H, W, self.config["num_classes"]), np.float32)
         ent, mi = np.empty(x.shape[:3], np.float32), np.empty(x.shape[:3], np.float32)
         for lo in range(0, n, bs):
             xb = torch.from_numpy(np.ascontiguousarray(x[lo:lo + bs])).to(eng.device)
+            if at is not None:
+                xb = eng.pad(xb, eng.cfg.H, eng.cfg.W, *at, pad_mode, pad_value)
             out = eng.forward_mc(xb, samples, step0=step0, want_mean_probs=True)
+            if at is not None:
+                out = {k: eng.crop(out[k], H, W, *at) for k in ("mean_probs", "entropy", "mutual_info")}
             mean[lo:lo + bs], ent[lo:lo + bs], mi[lo:lo + bs] = (out[k].cpu().numpy() for k in ("mean_probs", "entropy", "mutual_info"))
         return mean, ent, mi
 
     def predict_labels(self, x_u8: np.ndarray, batch_size: int = 32, want_maps: bool = False, bg_ilm: bool = True,
-                       bg_csi: bool = False, soft_maps: bool = False, mc_samples: int = 0, mc_step0: int = 0):
+                       bg_csi: bool = False, soft_maps: bool = False, mc_samples: int = 0, mc_step0: int = 0,
+                       pad_mode: Optional[str] = None, pad_value=0):
         """Raw uint8 images -> uint8 arg-max class maps (n,H,W), computed on the device (1 B/px back instead of
         4*C B/px).  With ``want_maps`` also the (n, C-1, H, W) uint8 boundary maps of
         ``convert_predictions_to_maps_semantic``, computed on the device from the class maps -- or, with ``soft_maps``,
         from the class probabilities, which stay on the device (``UNetEngine.boundary_maps_soft``).
         With ``mc_samples`` > 0 every batch is a Monte-Carlo dropout prediction (``predict_mc``): the class maps and
         boundary maps are those of the mean prediction, and the (n,H,W) float32 predictive entropy and mutual information
-        are returned behind them -- ``(labels, entropy, mutual_info)`` or ``(labels, maps, entropy, mutual_info)``."""
+        are returned behind them -- ``(labels, entropy, mutual_info)`` or ``(labels, maps, entropy, mutual_info)``.
+        ``pad_mode`` / ``pad_value`` (in raw counts, like ``x_u8``) as for ``predict``: the arg-max maps -- and the
+        probabilities and uncertainty maps where they are made -- are cropped on the device directly behind the head, and
+        the boundary maps are those of the cropped tensors."""
         if soft_maps and not want_maps:
             raise ValueError("soft_maps: needs want_maps=True")
+        pad_mode, pad_value = self._pad_options(pad_mode, pad_value)
         x_u8 = np.ascontiguousarray(x_u8)
         if x_u8.dtype != np.uint8:
             # the reference normalises x / 255 whatever the dtype (models/unet.py:87-91); the engine's float32 input
             # path means "already normalised", so do the division here rather than silently skipping it
             x_u8 = np.ascontiguousarray(x_u8.astype(np.float32) / np.float32(255.0))
-        n = x_u8.shape[0]
-        eng = self._ensure_engine(min(batch_size, n), False)
+            pad_value = float(np.float32(pad_value) / np.float32(255.0))
+        n, (H, W) = x_u8.shape[0], x_u8.shape[1:3]
+        eng, at = self._inference_engine(min(batch_size, n), (H, W), pad_mode)
         out = np.empty(x_u8.shape[:3], np.uint8)
         maps = np.empty((n, self.config["num_classes"] - 1) + tuple(x_u8.shape[1:3]), np.uint8) if want_maps else None
         unc = (np.empty(x_u8.shape[:3], np.float32), np.empty(x_u8.shape[:3], np.float32)) if mc_samples else ()
         for lo in range(0, n, batch_size):
             xb = torch.from_numpy(x_u8[lo:lo + batch_size]).to(eng.device)
+            if at is not None:
+                xb = eng.pad(xb, eng.cfg.H, eng.cfg.W, *at, pad_mode, pad_value)
             if mc_samples:
                 mc = eng.forward_mc(xb, mc_samples, step0=mc_step0, want_mean_probs=soft_maps)
+                if at is not None:
+                    mc = {k: eng.crop(t, H, W, *at) for k, t in mc.items()}
                 probs, am = mc.get("mean_probs"), mc["argmax"]
                 unc[0][lo:lo + batch_size], unc[1][lo:lo + batch_size] = mc["entropy"].cpu().numpy(), mc["mutual_info"].cpu().numpy()
             else:
                 probs, am = eng.forward(xb, training=False, want_probs=soft_maps, want_argmax=True)
+                if at is not None:
+                    probs, am = (None if probs is None else eng.crop(probs, H, W, *at)), eng.crop(am, H, W, *at)
             out[lo:lo + batch_size] = am.cpu().numpy()
             if want_maps:
                 dev_maps = (eng.boundary_maps_soft(probs, bg_ilm=bg_ilm, bg_csi=bg_csi) if soft_maps

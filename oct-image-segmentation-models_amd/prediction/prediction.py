@@ -71,7 +71,9 @@ def predict(predict_params: PredictionParams) -> List[PredictionOutput]:
                       graph_search=predict_params.graph_search, gs_device=predict_params.gs_device,
                       gs_device_ties=predict_params.gs_device_ties, gs_workers=predict_params.gs_workers,
                       soft_maps=not getattr(predict_params, "binarize", True),
-                      mc_samples=mc_samples, mc_step0=getattr(predict_params, "mc_step0", 0)) as run:
+                      mc_samples=mc_samples, mc_step0=getattr(predict_params, "mc_step0", 0),
+                      pad_mode=getattr(predict_params, "pad_mode", None),
+                      pad_value=getattr(predict_params, "pad_value", 0)) as run:
         t0 = time.time()
         for batch in run:
             b0, b1 = lo + batch.lo, lo + batch.hi
@@ -141,6 +143,9 @@ def save_predict_config_file(predict_params: PredictionParams):
     if getattr(predict_params, "mc_samples", 0):
         attrs["mc_samples"] = np.array(int(predict_params.mc_samples))      # likewise, with the first dropout step
         attrs["mc_step0"] = np.array(int(getattr(predict_params, "mc_step0", 0)))
+    if getattr(predict_params, "pad_mode", None) is not None:
+        attrs["pad_mode"] = np.array(str(predict_params.pad_mode), dtype="S1000")      # likewise, with the constant
+        attrs["pad_value"] = np.array(float(getattr(predict_params, "pad_value", 0)))
     h5io.save(predict_params.config_output_dir / Path("prediction_params.hdf5"), {}, attrs)
 
 

@@ -25,9 +25,15 @@ class PredictionParams:
                  graph_search: bool = False, trim_maps: bool = False, trim_ref_ind: int = 0,
                  trim_window: tuple = (0, 0), col_error_range: tuple = None, batch_size: int = 32, gs_device: bool = False,
                  gs_device_ties: str = "host", gs_workers: Union[int, None] = None, gs_labels_device: bool = False,
-                 binarize: bool = True, png_plots: bool = False, mc_samples: int = 0, mc_step0: int = 0) -> None:
+                 binarize: bool = True, png_plots: bool = False, mc_samples: int = 0, mc_step0: int = 0,
+                 pad_mode: Union[str, None] = None, pad_value=0) -> None:
         if not 0 <= int(mc_samples) <= 64:
             raise ValueError(f"mc_samples must be in 0..64, not {mc_samples}")
+        # extension: scans whose size is no multiple of 2^pool_layers (the reference raises on them) are padded on the
+        # device in front of the forward -- "edge", "reflect" or "constant" with pad_value in raw counts -- and every output
+        # is cropped directly behind the head, so every file has the scans' own size.  None: such sizes are refused.  Sizes
+        # that are multiples are never padded; the engine follows the dataset's size, whatever model_config.json records
+        self.pad_mode, self.pad_value = utils.check_pad_mode(pad_mode, pad_value)
         self.model_path = Path(model_path)
         self.mlflow_tracking_uri = mlflow_tracking_uri
         self.mlflow_run_uuid = mlflow_run_uuid
