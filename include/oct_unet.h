@@ -143,6 +143,23 @@ int oct_unet_loss_focal_dice(oct_unet* h, float smooth, float* out8_dev, oct_str
  * restatement under the same setting. */
 int oct_unet_set_bce_dice(oct_unet* h, int on);
 int oct_unet_loss_bce_dice(oct_unet* h, float smooth, float* out8_dev, oct_stream_t stream);
+/* Ignore label: pixels whose label byte equals `label` do not count in the loss.  Per handle; holds for the following
+ * forward / loss / backward calls (a forward made under another setting cannot be finalized or differentiated: call
+ * forward again).  label = -1 [default] switches it off; n_classes..255 are accepted, anything else is an argument error.
+ * Without it a label byte >= n_classes is NOT ignored: such a pixel has an all-zero one-hot row and still counts in P, Ph
+ * and the gradient.  With it, a pixel of that label
+ *   - adds nothing to the Dice sums I, T, P, Ih, Ph of any class, nor to the focal / BCE sum; probs and argmax are
+ *     written for it as for any pixel;
+ *   - has dlogits = 0 exactly for every class (Dice, focal and BCE parts), so the gradient stored for the last conv block
+ *     is 0 there and it adds nothing to the BN-backward statistics or the head's kernel / bias gradient;
+ *   - and the focal mean divides by the number of COUNTED pixels of the batch, the BCE mean by that number times
+ *     n_classes (the count is formed on the device by the loss call; oct_unet_backward reads it from the workspace).
+ * Defined edge cases: an image without a counted pixel has per-class macro score s/s = 1 (smooth > 0); a batch without
+ * one has focal = bce = 0, loss w*0 + (1-w)*0 for smooth > 0 and all-zero gradients; its dice_coef_micro is 0/0 = nan as
+ * the reference's formula gives on empty sums, its dice_coef_macro 1 by that metric's own 1e-5 epsilon.
+ * A captured graph (oct_unet_graph_capture*) keeps the setting it was captured under.
+ * The reference has no counterpart; the tests compare with a torch-fp64 masked restatement. */
+int oct_unet_set_ignore_label(oct_unet* h, int label);
 /* After training forward + loss_dice: fills the grads buffer with d(loss_scale*loss)/dparams. */
 int oct_unet_backward(oct_unet* h, const unsigned char* labels_dev, int macro, float loss_scale,
                       oct_stream_t stream);

@@ -97,6 +97,7 @@ SYMBOLS = [
     ("oct_unet_loss_focal_dice", C.c_int, [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
     ("oct_unet_set_bce_dice", C.c_int, [C.c_void_p, C.c_int]),
     ("oct_unet_loss_bce_dice", C.c_int, [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
+    ("oct_unet_set_ignore_label", C.c_int, [C.c_void_p, C.c_int]),
     ("oct_unet_backward", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p]),
     ("oct_unet_set_tail_event", C.c_int, [C.c_void_p, C.c_void_p]),
     ("oct_unet_grad_tail_offset", C.c_size_t, [_P(UNetCfg)]),

@@ -97,6 +97,53 @@ def bce_dice_loss(*, num_classes: int, bce_inner_eps: bool = True, **kwargs):
     return _bce_dice_loss
 
 
+def masked_loss_reference(labels, probs, num_classes: int, ignore, kind: str = "dice", *, smooth: float = 1e-05,
+                          gamma: float = 2.0, class_weight=None, focal_loss_weight: float = 0.5, bce_inner_eps: bool = True) -> dict:
+    """The losses above and the two Dice metrics with an ignore label, as the engine defines them
+    (``oct_unet_set_ignore_label``): sparse ``labels`` (B,H,W[,1]), ``probs`` (B,H,W,C), fp64.  A pixel whose label equals
+    ``ignore`` (``None``: no such pixel) is dropped from every sum -- its one-hot row AND its probabilities -- and the focal
+    / BCE mean divides by the number of counted pixels of the batch (times C for BCE), 0 where there is none.
+    ``kind``: ``"dice"``, ``"focal"`` or ``"bce"``.  Returns a dict of ``dice_loss_macro``, ``dice_loss_micro``,
+    ``dice_coef_macro``, ``dice_coef_micro``, ``term`` (the focal or BCE mean; 0 for ``"dice"``) and the combined
+    ``loss_macro`` / ``loss_micro``: ``w term + (1 - w) dice`` for focal, ``term + dice_loss_micro`` for BCE (whose
+    ``loss_macro`` is ``None``: the reference defines that loss with the micro Dice only), the Dice losses themselves for
+    ``"dice"``.  A batch without a counted pixel has ``dice_coef_micro = 0/0 = nan``, as the reference's formula gives."""
+    if kind not in ("dice", "focal", "bce"):
+        raise ValueError(f"masked_loss_reference: unknown kind {kind!r}")
+    lab = np.asarray(labels)
+    lab = (lab[..., 0] if (lab.ndim == 4 and lab.shape[-1] == 1) else lab).astype(np.int64)
+    p = np.asarray(probs, np.float64)
+    m = np.ones(lab.shape, bool) if ignore is None else lab != int(ignore)
+    safe = np.where(m & (lab < num_classes), lab, 0)
+    y = np.eye(num_classes, dtype=np.float64)[safe] * (m & (lab < num_classes))[..., None]   # a value that is no class: all-zero row
+    pm = p * m[..., None]
+    ph = (p > 0.5) * m[..., None]
+    ax = (1, 2)
+    I, T, P = np.sum(y * pm, axis=ax), np.sum(y, axis=ax), np.sum(pm, axis=ax)
+    Ih, Ph = np.sum(y * ph, axis=ax), np.sum(ph, axis=ax)
+    out = {"dice_loss_macro": float(1.0 - np.mean((2.0 * I + smooth) / (T + P + smooth))),
+           "dice_loss_micro": float(1.0 - (2.0 * I.sum() + smooth) / (T.sum() + P.sum() + smooth)),
+           "dice_coef_macro": float(np.mean((2.0 * Ih + 1e-05) / (T + Ph + 1e-05)))}
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out["dice_coef_micro"] = float(np.float64(2.0) * Ih.sum() / (T.sum() + Ph.sum()))
+    count = int(m.sum())
+    inv = 1.0 / count if count else 0.0
+    if kind == "focal":
+        py = np.clip(np.take_along_axis(p, safe[..., None], axis=-1)[..., 0], FOCAL_EPS, 1.0 - FOCAL_EPS)
+        cw = 1.0 if class_weight is None else np.asarray(class_weight, np.float64)[safe]
+        term, w = float(np.sum((cw * (1.0 - py) ** gamma * -np.log(py))[m]) * inv), float(focal_loss_weight)
+        out.update(term=term, loss_macro=w * term + (1.0 - w) * out["dice_loss_macro"],
+                   loss_micro=w * term + (1.0 - w) * out["dice_loss_micro"])
+    elif kind == "bce":
+        e = FOCAL_EPS if bce_inner_eps else 0.0
+        pc, qc = np.clip(p, FOCAL_EPS, 1.0 - FOCAL_EPS), np.clip(1.0 - p, FOCAL_EPS, 1.0 - FOCAL_EPS)
+        term = float(np.sum(-(y * np.log(pc + e) + (1.0 - y) * np.log(qc + e))[m]) * inv / num_classes)
+        out.update(term=term, loss_macro=None, loss_micro=term + out["dice_loss_micro"])
+    else:
+        out.update(term=0.0, loss_macro=out["dice_loss_macro"], loss_micro=out["dice_loss_micro"])
+    return out
+
+
 def _out_of_scope(name, why=None):
     def factory(**kwargs):
         raise NotImplementedError(why or f"loss '{name}' is outside the accelerated path (only the Dice losses, "

@@ -255,8 +255,22 @@ struct HeadBwdArgs {
     int focal_clip_mod;                // see HeadFwdArgs
     // bce_dice_loss: L = bce + dice_micro (focal_w = 0, macro = 0); bce_scale = loss_scale / (B*H*W*C)
     int bce_on; float bce_inner, bce_scale;
+    // ignore label (oct_unet_set_ignore_label; -1 = off): dl of such a pixel is exactly 0 for every class, so g is stored as 0
+    // and the pixel adds nothing to the statistics or the head dW / db partials.  With it set, the means' 1 / (counted
+    // pixels) comes from bc[2*B*C + 2] (dice_finalize_k) and stands in for inv_count, also inside bce_scale
+    int ignore;
     FinDesc fin;                       // BN-backward sums of the last conv block finalized by the last block (kernels_fin.hpp)
 };
+
+// the two constants of the focal / BCE means: the host's with the mask off, else formed from the device's count by the same
+// float expressions, read once in front of the chunk loop
+struct HeadMeans { float inv_count, bce_scale; };
+template <int C>
+__device__ __forceinline__ HeadMeans head_means(const HeadBwdArgs& A) {
+    HeadMeans m{A.inv_count, A.bce_scale};
+    if (A.ignore >= 0) { m.inv_count = (float)A.bc[2 * A.B * C + 2]; m.bce_scale = A.loss_scale * m.inv_count / (float)C; }
+    return m;
+}
 
 template <int C, int CIN, typename AT>
 __global__ __launch_bounds__(kBlock) void head_bwd_k(const HeadBwdArgs A) {
@@ -276,7 +290,8 @@ __global__ __launch_bounds__(kBlock) void head_bwd_k(const HeadBwdArgs A) {
         num[c] = (float)k[0]; den[c] = (float)k[1];
     }
     const float scale = (1.f - A.focal_w) * (A.macro ? A.loss_scale / (float)(A.B * C) : A.loss_scale);
-    const float fscale = A.focal_w * A.loss_scale * A.inv_count;
+    const HeadMeans hm = head_means<C>(A);
+    const float fscale = A.focal_w * A.loss_scale * hm.inv_count;
 
     HeadQueue<CIN, kHeadBwdAhead, AT> hq(reinterpret_cast<const AT*>(A.z) + (size_t)b * A.HW * CIN, A.labels + (size_t)b * A.HW, A.HW);
     hq.fill(blockIdx.x, gridDim.x);
@@ -286,6 +301,7 @@ __global__ __launch_bounds__(kBlock) void head_bwd_k(const HeadBwdArgs A) {
         const size_t pix = (size_t)b * A.HW + (valid ? px : 0);
         float y[CIN], zr[CIN], p[C];
         const int lab = hq.pop(zr, chunk + kHeadBwdAhead * (int)gridDim.x);     // later chunks' pixels are requested before this one is used
+        const bool counted = valid && lab != A.ignore;  // folded into the selects that `valid` already feeds: no new branch
         head_logits<C, CIN>(A.bn, A.w, A.bias, y, zr, p);
         float dp[C], dot = 0.f;
 #pragma unroll
@@ -319,8 +335,8 @@ __global__ __launch_bounds__(kBlock) void head_bwd_k(const HeadBwdArgs A) {
             softmax_complement<C>(p, q);
 #pragma unroll
             for (int c = 0; c < C; ++c) {
-                const bool inr = valid && p[c] >= kFocalEps && q[c] >= kFocalEps;
-                const float r = A.bce_scale / ((lab == c ? p[c] : q[c]) + A.bce_inner);      // y picks the term
+                const bool inr = counted && p[c] >= kFocalEps && q[c] >= kFocalEps;
+                const float r = hm.bce_scale / ((lab == c ? p[c] : q[c]) + A.bce_inner);     // y picks the term
                 db[c] = inr ? (lab == c ? -r : r) : 0.f;
             }
 #pragma unroll
@@ -333,7 +349,7 @@ __global__ __launch_bounds__(kBlock) void head_bwd_k(const HeadBwdArgs A) {
         }
         float dl[C];
 #pragma unroll
-        for (int c = 0; c < C; ++c) { dl[c] = (valid ? p[c] * (dp[c] - dot) : 0.f) + dlb[c]; wv[CIN * C + c] += dl[c]; }
+        for (int c = 0; c < C; ++c) { dl[c] = (counted ? p[c] * (dp[c] - dot) : 0.f) + dlb[c]; wv[CIN * C + c] += dl[c]; }
         float g[CIN];
 #pragma unroll
         for (int i = 0; i < CIN; ++i) {

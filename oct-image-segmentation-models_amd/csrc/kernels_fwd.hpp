@@ -317,6 +317,9 @@ struct HeadFwdArgs {
     //   sum_c -( y ln(pc + e) + (1 - y) ln(qc + e) ),  pc = clip(p, eps, 1-eps), qc = clip(1 - p, eps, 1-eps),  e = eps or 0
     // Never together with focal_on: the two share slot 5*C.
     int bce_on; float bce_inner;       // bce_inner = e (option bce_inner_eps)
+    // ignore label (oct_unet_set_ignore_label): a pixel with this label byte adds nothing to the Dice sums or to slot 5*C;
+    // its probs / argmax are written as ever.  -1 = off: a label byte never compares equal
+    int ignore;
 };
 constexpr float kFocalEps = 1e-7f;
 
@@ -432,6 +435,8 @@ __global__ __launch_bounds__(kBlock) void head_fwd_k(const HeadFwdArgs A) {
                 for (int c = 1; c < C; ++c) if (p[c] > best) { best = p[c]; am = c; }  // first maximum, as np.argmax
                 A.argmax[pix] = (unsigned char)am;
             }
+        }
+        if (valid && lab != A.ignore) {                     // the loss sums: counted pixels only
             if (A.labels) {
 #pragma unroll
                 for (int c = 0; c < C; ++c) {
@@ -465,7 +470,8 @@ __global__ __launch_bounds__(kBlock) void head_fwd_k(const HeadFwdArgs A) {
 
 // Dice finalize: per-(b,c) sums in fp64 -> losses, metrics, and the per-(b,c) constants backward needs.
 //   out4 = {dice_loss_macro, dice_loss_micro, dice_coef_macro, dice_coef_micro}
-//   bc   = per (b,c): {Num = 2I+s, Den = T+P+s}; then the micro pair at [2*B*C], [2*B*C+1]
+//   bc   = per (b,c): {Num = 2I+s, Den = T+P+s}; then the micro pair at [2*B*C], [2*B*C+1]; with an ignore label
+//          1 / (counted pixels) at [2*B*C+2]
 //   out8 = out4 + {focal mean, w*focal + (1-w)*dice_macro, w*focal + (1-w)*dice_micro, 0}   (focal_dice_loss)
 //   out8 = out4 + {bce mean, 0, bce + dice_micro, 0}                                        (bce_dice_loss, bce_on)
 struct DiceFinArgs {
@@ -473,6 +479,8 @@ struct DiceFinArgs {
     float smooth; float* out4; float* out4_user; double* bc;
     int n_user;            // floats copied to out4_user: 4 (loss_dice) or 8 (loss_focal_dice)
     double inv_count;      // 1 / (B*H*W)
+    int masked;            // an ignore label is set: the means divide by the counted pixels (sum of T) instead, 0 if there are
+                           // none, and that 1 / count is left at bc[2*B*C + 2] for head_bwd_*
     float focal_w;
     int bce_on;            // slot 5*C holds the BCE sum: its mean is over B*H*W*C
 };
@@ -547,13 +555,15 @@ static __global__ __launch_bounds__(kBlock) void dice_finalize_k(const DiceFinAr
         o4[1] = (float)(1.0 - num / den);
         o4[2] = (float)(sh[1][0] / n);
         o4[3] = (float)(2.0 * sh[5][0] / (sh[3][0] + sh[6][0]));  // no epsilon: 0/0 -> nan as the reference
-        const double focal = sh[7][0] * A.inv_count, w = A.focal_w;
+        const double inv_count = A.masked ? (sh[3][0] > 0.0 ? 1.0 / sh[3][0] : 0.0) : A.inv_count;   // sum of T: exact, every counted pixel has one class
+        if (A.masked) A.bc[2 * n + 2] = inv_count;
+        const double focal = sh[7][0] * inv_count, w = A.focal_w;
         o4[4] = (float)focal;
         o4[5] = (float)(w * focal + (1.0 - w) * (1.0 - sh[0][0] / n));
         o4[6] = (float)(w * focal + (1.0 - w) * (1.0 - num / den));
         o4[7] = 0.f;
         if (A.bce_on) {
-            const double bce = sh[7][0] * (A.inv_count / A.C);
+            const double bce = sh[7][0] * (inv_count / A.C);
             o4[4] = (float)bce; o4[5] = 0.f; o4[6] = (float)(bce + (1.0 - num / den));
         }
         for (int j = 0; j < 8; ++j) { A.out4[j] = o4[j]; if (A.out4_user && j < A.n_user) A.out4_user[j] = o4[j]; }

@@ -12,7 +12,7 @@
 //     13 accumulators of 4 VGPRs (3 per channel group + the bias) are carried across the chunks a block walks.
 // Summation order: MFMA k-steps in pixel order within a wave's 64 pixels, chunk after chunk, then (w0 + w1) + (w2 + w3)
 // over the block's waves: fixed, so two runs give the same bits.  No atomics.  Invalid lanes of a ragged last chunk write
-// dl = 0 and a = 0 (and a finite y of pixel 0), i.e. exact zeros into every sum.
+// dl = 0 and a = 0 (and a finite y of pixel 0), i.e. exact zeros into every sum; so do the pixels of the ignore label.
 // Same buffers, same layouts as the register kernels: probs / argmax / Dice rows, g, part [B*nblk][2*CIN], wpart
 // [B*nblk][CIN*C + C].  grid (nblk, B), a block walks chunks blockIdx.x, + nblk, ... of one image.
 #pragma once
@@ -77,8 +77,10 @@ __global__ __launch_bounds__(kBlock) void head_fwd_wide_k(const HeadFwdArgs A, c
                 for (int c = 1; c < C; ++c) if (p[c] > best) { best = p[c]; am = c; }  // first maximum, as np.argmax
                 A.argmax[pix] = (unsigned char)am;
             }
+        }
+        const int lab = A.labels ? A.labels[pix] : 0;
+        if (valid && lab != A.ignore) {                     // the loss sums: counted pixels only (see head_fwd_k)
             if (A.labels) {
-                const int lab = A.labels[pix];
 #pragma unroll
                 for (int c = 0; c < C; ++c) {
                     const float yv = lab == c ? 1.f : 0.f, ph = p[c] > 0.5f ? 1.f : 0.f;
@@ -129,7 +131,8 @@ __global__ __launch_bounds__(kBlock, 2) void head_bwd_wide_k(const HeadBwdArgs A
         num[c] = (float)k[0]; den[c] = (float)k[1];
     }
     const float scale = (1.f - A.focal_w) * (A.macro ? A.loss_scale / (float)(A.B * C) : A.loss_scale);
-    const float fscale = A.focal_w * A.loss_scale * A.inv_count;
+    const HeadMeans hm = head_means<C>(A);
+    const float fscale = A.focal_w * A.loss_scale * hm.inv_count;
 
     for (int chunk = blockIdx.x; chunk * kBlock < A.HW; chunk += gridDim.x) {
         const int px = chunk * kBlock + tid;
@@ -137,6 +140,7 @@ __global__ __launch_bounds__(kBlock, 2) void head_bwd_wide_k(const HeadBwdArgs A
         const size_t pix = (size_t)b * A.HW + (valid ? px : 0);
         const AT* const zp = reinterpret_cast<const AT*>(A.z) + pix * CIN;
         const int lab = A.labels[pix];
+        const bool counted = valid && lab != A.ignore;   // see head_bwd_k
         float p[C];
         head_logits_stream<C, AT>(zp, A.bn, A.w, A.bias, CIN, p);
         float dp[C], dot = 0.f;
@@ -162,8 +166,8 @@ __global__ __launch_bounds__(kBlock, 2) void head_bwd_wide_k(const HeadBwdArgs A
             softmax_complement<C>(p, q);
 #pragma unroll
             for (int c = 0; c < C; ++c) {
-                const bool inr = valid && p[c] >= kFocalEps && q[c] >= kFocalEps;
-                const float r = A.bce_scale / ((lab == c ? p[c] : q[c]) + A.bce_inner);
+                const bool inr = counted && p[c] >= kFocalEps && q[c] >= kFocalEps;
+                const float r = hm.bce_scale / ((lab == c ? p[c] : q[c]) + A.bce_inner);
                 db[c] = inr ? (lab == c ? -r : r) : 0.f;
             }
 #pragma unroll
@@ -178,7 +182,7 @@ __global__ __launch_bounds__(kBlock, 2) void head_bwd_wide_k(const HeadBwdArgs A
 #pragma unroll
         for (int c = 0; c < 16; ++c) dl[c] = 0.f;
 #pragma unroll
-        for (int c = 0; c < C; ++c) dl[c] = (valid ? p[c] * (dp[c] - dot) : 0.f) + dlb[c];
+        for (int c = 0; c < C; ++c) dl[c] = (counted ? p[c] * (dp[c] - dot) : 0.f) + dlb[c];
 
         __syncthreads();                            // the previous chunk's operand reads are done
 #pragma unroll

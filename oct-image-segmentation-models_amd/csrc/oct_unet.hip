@@ -255,6 +255,7 @@ struct oct_unet {
     float* dice_part = nullptr; double* dice_bc = nullptr; float* loss4 = nullptr;   // loss4: 8 floats (dice_finalize_k)
     float focal_w = 0.f, focal_gamma = 2.f; const float* focal_cw = nullptr;           // focal_dice_loss (0 = plain Dice)
     int bce_on = 0;                                                                    // bce_dice_loss (never with focal_w > 0)
+    int ignore = -1;                                                                   // ignore label of the loss (-1 = none)
     WtDesc* wt_descs = nullptr; int n_wt = 0; unsigned wt_total = 0;
     WbxDesc* wbx_descs = nullptr; int n_wbx_f = 0, n_wbx_b = 0; unsigned wbx_f_total = 0, wbx_b_total = 0;   // [fwd..., bwd...]
     WbtDesc* wbt_descs = nullptr; int n_wbt_f = 0, n_wbt_b = 0; unsigned wbt_f_total = 0, wbt_b_total = 0;   // [fwd..., bwd...]
@@ -313,7 +314,7 @@ size_t carve(const oct_unet_cfg& c, Plan& pl, oct_unet* h, char* base, const Opt
     stat_max = std::max(stat_max, B * nblk_head * 2 * (size_t)c.start_neurons);
     float* sp = (float*)take(stat_max * 4);
     float* dp = (float*)take(B * nblk_head * 64 * 4);
-    double* bc = (double*)take((B * 8 * 2 + 2) * 8);
+    double* bc = (double*)take((B * 8 * 2 + 3) * 8);       // per (b, c) pairs, the micro pair, 1 / (counted pixels)
     float* l4 = (float*)take(8 * 4);
     unsigned* fc = (unsigned*)take(2 * pl.L.size() * sizeof(unsigned));
     if (h) h->fin_counters = fc;
@@ -601,7 +602,7 @@ int forward_head(oct_unet* h, int B, const oct_unet_io* io, hipStream_t s) {
     a.probs = io ? io->probs : nullptr; a.argmax = io ? io->argmax : nullptr; a.labels = io ? io->labels : nullptr;
     a.dice_part = h->dice_part; a.HW = hd.H * hd.W; a.nblk = head_nblk(a.HW, B); a.act_bf16 = h->cfg.dtype;
     a.focal_on = h->focal_w > 0.f; a.focal_gamma = h->focal_gamma; a.focal_cw = h->focal_cw; a.focal_clip_mod = h->opt.focal_clip_mod;
-    a.bce_on = h->bce_on; a.bce_inner = h->opt.bce_inner_eps ? kFocalEps : 0.f;
+    a.bce_on = h->bce_on; a.bce_inner = h->opt.bce_inner_eps ? kFocalEps : 0.f; a.ignore = h->ignore;
     const int rc = DISPATCH_C(launch_head_fwd, h->cfg.n_cls, a, hd.cin, B, s, head_is_wide(h->opt, hd.cin));
     if (rc) return rc;
     h->have_dice = a.labels != nullptr;
@@ -839,6 +840,7 @@ int head_backward(oct_unet* h, const unsigned char* labels, int macro, float los
     hb.HW = hd.H * hd.W; hb.nblk = head_nblk(hb.HW, B); hb.B = B; hb.macro = macro; hb.loss_scale = loss_scale; hb.act_bf16 = h->cfg.dtype;
     hb.focal_w = h->focal_w; hb.focal_gamma = h->focal_gamma; hb.focal_cw = h->focal_cw; hb.focal_clip_mod = h->opt.focal_clip_mod; hb.inv_count = 1.f / ((float)B * hb.HW);
     hb.bce_on = h->bce_on; hb.bce_inner = h->opt.bce_inner_eps ? kFocalEps : 0.f; hb.bce_scale = loss_scale * hb.inv_count / (float)h->cfg.n_cls;
+    hb.ignore = h->ignore;       // >= 0: the kernels take 1 / (counted pixels) from dice_bc instead of inv_count
     const bool wide = head_is_wide(h->opt, hd.cin);          // (only the register kernels finalize the statistics in the launch)
     if (!wide && fin_ok(h, last)) { hb.fin = fin_desc(h, nl - 2, 1, B); *fin = true; }
     *rows = B * hb.nblk;
@@ -1205,6 +1207,7 @@ static int loss_finalize(oct_unet* h, const char* what, float smooth, float* out
     a.part = h->dice_part; a.B = h->last_B; a.C = h->cfg.n_cls; a.nblk = head_nblk(h->cfg.H * h->cfg.W, h->last_B);
     a.N = dice_n(a.C); a.smooth = smooth; a.out4 = h->loss4; a.out4_user = out; a.bc = h->dice_bc;
     a.n_user = n_user; a.inv_count = 1.0 / ((double)h->last_B * h->cfg.H * h->cfg.W); a.focal_w = h->focal_w; a.bce_on = h->bce_on;
+    a.masked = h->ignore >= 0;
     dice_finalize_k<<<1, kBlock, 0, (hipStream_t)stream>>>(a);
     HIP_OK(hipGetLastError());
     h->dice_final = 1;
@@ -1227,6 +1230,15 @@ int oct_unet_set_bce_dice(oct_unet* h, int on) {
     if (!h) return fail(-1, "null handle");
     h->bce_on = on != 0;
     if (h->bce_on) h->focal_w = 0.f;
+    return 0;
+}
+
+int oct_unet_set_ignore_label(oct_unet* h, int label) {
+    if (!h) return fail(-1, "null handle");
+    if (label != -1 && (label < h->cfg.n_cls || label > 255))
+        return fail(-1, "ignore label must be -1 (none) or in n_classes..255: got " + std::to_string(label));
+    if (label != h->ignore) { h->have_dice = 0; h->dice_final = 0; }    // sums of a forward under the other setting are not this loss's
+    h->ignore = label;
     return 0;
 }
 

@@ -104,6 +104,7 @@ class UNetEngine:
         self.opt_step = 0
         self._keep = []  # tensors referenced by an in-flight / captured launch
         self._mc: Dict[int, dict] = {}  # forward_mc's buffers per batch size
+        self.ignore_label: Optional[int] = None   # set_ignore_label
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -202,6 +203,13 @@ class UNetEngine:
     def loss_bce_dice(self, smooth: float = 1e-5) -> torch.Tensor:
         """loss_dice() + [bce mean, 0, bce + dice_loss_micro, 0] (device tensor, 8 floats)."""
         return self._loss("oct_unet_loss_bce_dice", 8, smooth)
+
+    def set_ignore_label(self, label: Optional[int]) -> None:
+        """Pixels whose label byte equals ``label`` (``num_classes..255``) do not count in the loss of the following
+        forward / loss / backward calls: nothing in the Dice sums and metrics, nothing in the focal / BCE mean -- which then
+        divides by the counted pixels -- and a zero gradient (``oct_unet_set_ignore_label``).  ``None`` switches it off."""
+        self._call("oct_unet_set_ignore_label", -1 if label is None else int(label))
+        self.ignore_label = None if label is None else int(label)
 
     def backward(self, labels: torch.Tensor, macro: bool = True, loss_scale: float = 1.0):
         self._check_labels(labels, labels.shape[0])

@@ -117,7 +117,15 @@ class Model:
         self._pending_weights = None
         # the model's default for predict / predict_mc / predict_labels on sizes that are no multiple of 2^pool_layers:
         # None (refuse them), "edge", "reflect" or "constant" with pad_value; a call's own pad_mode goes first
+        # fit / evaluate consult the same pair, but only in a model compiled for it (compile(pad_mode=...), which also sets
+        # the pair): a batch of such a size is then padded on the device behind the augmentations and its label frame
+        # filled with the ignore label, so that the loss sees the window only.  Setting the
+        # attributes alone keeps padding to inference and fit refuses such sizes, as before
         self.pad_mode, self.pad_value = None, 0
+        self._pad_fit = False
+        # label value whose pixels do not count in the loss, the Dice metrics or the gradient (compile(ignore_label=...));
+        # None: every pixel counts
+        self.ignore_label = None
         self._device = device
         self.history = None
 
@@ -218,7 +226,25 @@ class Model:
         return self._engine if self._engine is not None else self._ensure_engine(1, False)
 
     # ---- keras.Model surface -------------------------------------------------------------------------
-    def compile(self, optimizer=None, loss=None, metrics=None, **kwargs):
+    def compile(self, optimizer=None, loss=None, metrics=None, ignore_label=None, pad_mode=None, pad_value=0, **kwargs):
+        """``ignore_label``: a label value in ``num_classes..255`` whose pixels ``fit`` / ``evaluate`` leave out of the loss,
+        the Dice metrics and the gradient (``UNetEngine.set_ignore_label``); ``None``: every pixel counts.
+        ``pad_mode`` ("edge", "reflect" or "constant" with ``pad_value``): sets the model's ``pad_mode`` / ``pad_value``
+        attributes and lets ``fit`` / ``evaluate`` consult them, i.e. pad batches whose size is no multiple of 2^pool_layers
+        and keep the frame out of the loss.  ``None`` leaves the attributes alone and ``fit`` / ``evaluate`` refusing such
+        sizes whatever the attributes say (they then serve inference only)."""
+        from ..common.utils import check_pad_mode
+        if pad_mode is not None:
+            try:
+                self.pad_mode, self.pad_value = check_pad_mode(pad_mode, pad_value)
+            except ValueError as e:
+                raise OctError(f"compile(pad_mode=...): {e}") from None
+        self._pad_fit = pad_mode is not None
+        if ignore_label is not None:
+            if int(ignore_label) != ignore_label or not int(self.config["num_classes"]) <= int(ignore_label) <= 255:
+                raise OctError(f"compile(ignore_label=...): must be None or an integer in num_classes..255, not {ignore_label!r}")
+            ignore_label = int(ignore_label)
+        self.ignore_label = ignore_label
         loss_name = getattr(loss, "oct_loss", None) if loss is not None else None
         if loss is not None and loss_name not in ("dice_loss_macro", "dice_loss_micro", "focal_dice_loss", "bce_dice_loss"):
             raise OctError("compile(loss=...): only the Dice losses, focal_dice_loss and bce_dice_loss from common.custom_losses are "
@@ -235,21 +261,27 @@ class Model:
         self.optimizer, self._loss_name, self._metric_name = optimizer, loss_name, metric_name
 
     def count_params(self) -> int:
+        from ..common.utils import padded_geometry
         from ..engine import make_cfg
         from .. import _hip
         import ctypes as C
         c = self.config
-        cfg = make_cfg(input_channels=c["input_channels"], num_classes=c["num_classes"], image_height=c["image_height"],
-                       image_width=c["image_width"], start_neurons=c.get("start_neurons", 8),
+        # (the table is that of the padded geometry where the config's size is no multiple of 2^pool_layers)
+        Hp, Wp, _, _ = padded_geometry(c["image_height"], c["image_width"], c.get("pool_layers", 4))
+        cfg = make_cfg(input_channels=c["input_channels"], num_classes=c["num_classes"], image_height=Hp,
+                       image_width=Wp, start_neurons=c.get("start_neurons", 8),
                        pool_layers=c.get("pool_layers", 4), conv_layers=c.get("conv_layers", 2))
         l = _hip.lib()
         return int(l.oct_unet_param_count(C.byref(cfg)) + l.oct_unet_state_count(C.byref(cfg)))
 
     def summary(self, print_fn=print):
+        from ..common.utils import padded_geometry
         from ..engine import make_cfg, layer_table
         c = self.config
-        cfg = make_cfg(input_channels=c["input_channels"], num_classes=c["num_classes"], image_height=c["image_height"],
-                       image_width=c["image_width"], start_neurons=c.get("start_neurons", 8),
+        # (the table is that of the padded geometry where the config's size is no multiple of 2^pool_layers)
+        Hp, Wp, _, _ = padded_geometry(c["image_height"], c["image_width"], c.get("pool_layers", 4))
+        cfg = make_cfg(input_channels=c["input_channels"], num_classes=c["num_classes"], image_height=Hp,
+                       image_width=Wp, start_neurons=c.get("start_neurons", 8),
                        pool_layers=c.get("pool_layers", 4), conv_layers=c.get("conv_layers", 2))
         print_fn(f'Model: "{self.name}"  (MI355X HIP engine)')
         print_fn(f"{'layer':14s}{'kernel':>8s}{'in':>6s}{'out':>6s}{'HxW':>12s}{'params':>10s}")
@@ -387,6 +419,21 @@ class Model:
             buf = self._aug_out = (torch.empty(x.shape, dtype=torch.float32, device=x.device), torch.empty_like(lab))
         return eng.augment(x, lab, ops, seq.oct_aug_seed, out=buf)
 
+    def _pad_batch(self, eng, x, lab, at, pad_mode, pad_value, ignore):
+        """One batch of a size that is no multiple of 2^pool_layers -> the engine's geometry, on the compute stream: the images
+        by ``pad_mode``, the labels -- same kernel, it moves bytes -- in ``constant`` mode with the ignore label.  The padded
+        pair belongs to ``eng`` and is made once per batch size (and image type): its last reader, this step's backward,
+        is queued on the same stream in front of the next step's pad, so one pair is enough."""
+        bufs = eng.__dict__.setdefault("_pad_bufs", {})
+        B, (Hp, Wp) = x.shape[0], (eng.cfg.H, eng.cfg.W)
+        pair = bufs.get((B, x.dtype))
+        if pair is None:
+            pair = bufs[(B, x.dtype)] = (torch.empty((B, Hp, Wp, x.shape[3]), dtype=x.dtype, device=x.device),
+                                         torch.empty((B, Hp, Wp, 1), dtype=torch.uint8, device=x.device))
+        xp = eng.pad(x, Hp, Wp, *at, pad_mode, pad_value, out=pair[0])
+        lp = eng.pad(lab.view(B, x.shape[1], x.shape[2], 1), Hp, Wp, *at, "constant", ignore, out=pair[1])
+        return xp, lp
+
     def _release(self, slot: int):
         """The compute stream is done reading device slot ``slot`` (recorded behind the step that used it)."""
         st = self.__dict__.get("_up")
@@ -410,6 +457,7 @@ class Model:
         focal = getattr(self, "_focal", None)
         bce = self._loss_name == "bce_dice_loss"        # bce + dice_loss_micro: the micro combination only
         macro = focal["dice_macro"] if focal else self._loss_name not in ("dice_loss_micro", "bce_dice_loss")
+        pad_mode, pad_value = self._pad_options(None, 0) if self._pad_fit else (None, 0.0)
         acc = None
         n = len(seq)
         # the upload of batch i+1 (host gather -> pinned buffers -> H2D on the copy stream) is queued before step i is
@@ -424,9 +472,24 @@ class Model:
                 torch.cuda.current_stream(x.device).wait_event(ready)
             if i + 1 < n:
                 nxt = queue(i + 1)
-            eng = self._ensure_engine(x.shape[0], training, hw=tuple(x.shape[1:3]))     # validation data may have another size
+            # validation data may have another size; one that is no multiple of 2^pool_layers runs on the engine of the padded
+            # geometry under the model's pad_mode (None, or a model not compiled with one: the OctError of _geometry)
+            hw, raw_u8 = tuple(x.shape[1:3]), x.dtype == torch.uint8
+            try:
+                geom, at = self._geometry(hw, pad_mode)
+            except OctError as e:
+                raise OctError(f"{e}; fit / evaluate pad such batches in a model compiled with compile(pad_mode=...)") from None
+            eng = self._ensure_engine(x.shape[0], training, hw=geom)
             if ops is not None:
-                x, lab = self._augment(eng, seq, x, lab, ops, *wops)
+                x, lab = self._augment(eng, seq, x, lab, ops, *wops)    # at the true size: the frame is not warped or flipped
+            ignore = self.ignore_label
+            if at is not None:
+                ignore = 255 if ignore is None else ignore
+                # pad_value is in the units of the Sequence's batches: raw counts where the augment stage has turned them to [0, 1]
+                x, lab = self._pad_batch(eng, x, lab, at, pad_mode, pad_value / 255.0 if raw_u8 and x.dtype != torch.uint8 else pad_value,
+                                         ignore)
+            if eng.ignore_label != ignore:     # also: an engine last used by a masked model goes back to counting every pixel
+                eng.set_ignore_label(ignore)
             if focal:      # (re)selected per batch: _ensure_engine may have built a new engine
                 eng.set_focal_dice(focal["focal_loss_weight"], focal["gamma"], focal["class_weight"])
             elif getattr(eng, "_focal_active", False):

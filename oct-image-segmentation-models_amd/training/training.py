@@ -61,10 +61,19 @@ def save_training_params_file(save_foldername: Path, model_summary: str, model_c
     h5io.save(save_foldername / Path("training_params.hdf5"), datasets, attrs)
 
 
-def _balanced_class_weight(labels: np.ndarray) -> np.ndarray:
-    """sklearn ``compute_class_weight("balanced")``: n_samples / (n_classes * bincount)."""
+def _balanced_class_weight(labels: np.ndarray, ignore_label=None) -> np.ndarray:
+    """sklearn ``compute_class_weight("balanced")``: n_samples / (n_classes * bincount), over the pixels whose label is not
+    ``ignore_label``."""
+    if ignore_label is not None:
+        labels = labels[labels != ignore_label]
     classes, counts = np.unique(labels, return_counts=True)
     return labels.size / (len(classes) * counts.astype(np.float64))
+
+
+def _count_classes(train_labels: np.ndarray, ignore_label=None) -> int:
+    """The reference's ``len(np.unique(train_labels))``, the ignore label not counted."""
+    values = np.unique(train_labels)
+    return int(len(values) - (ignore_label is not None and ignore_label in values))
 
 
 def train_model(training_params: TrainingParams, mlflow_params=None):
@@ -77,7 +86,8 @@ def train_model(training_params: TrainingParams, mlflow_params=None):
     train_images, train_labels = dataset_loader.load_training_data(data)
     val_images, val_labels = dataset_loader.load_validation_data(data)
 
-    num_classes = len(np.unique(train_labels))
+    ignore_label = training_params.ignore_label
+    num_classes = _count_classes(train_labels, ignore_label)
     log.info(f"Detected {num_classes} classes")
     _, image_height, image_width, input_channels = train_images.shape
     log.info(f"Detected input image dimensions (h x w): {image_height} x {image_width}.")
@@ -91,7 +101,7 @@ def train_model(training_params: TrainingParams, mlflow_params=None):
         log.error(f"Loss '{training_params.loss}' not found. Exiting...")
         exit(1)
     if training_params.class_weight == "balanced":
-        c_weight = _balanced_class_weight(np.concatenate((train_labels, val_labels)))
+        c_weight = _balanced_class_weight(np.concatenate((train_labels, val_labels)), ignore_label)
     elif type(training_params.class_weight) == list:
         c_weight = np.array(training_params.class_weight)
     else:
@@ -138,7 +148,10 @@ def train_model(training_params: TrainingParams, mlflow_params=None):
         model = model_container.build_model()
         if training_params.seed is not None:
             model.config["seed"] = int(training_params.seed)
-    model.compile(optimizer=optimizer, loss=loss_fn, metrics=[metric_fn])
+    # scans whose size is no multiple of 2^pool_layers: with a pad_mode fit and its validation pad each batch on the device
+    # and keep the frame out of the loss (pad_mode None: they raise, as ever)
+    model.compile(optimizer=optimizer, loss=loss_fn, metrics=[metric_fn], ignore_label=ignore_label,
+                  pad_mode=training_params.pad_mode, pad_value=training_params.pad_value)
 
     batch_size = training_params.batch_size
     aug_val_mode = training_params.aug_mode if training_params.aug_val else "none"

@@ -19,7 +19,8 @@ class TrainingParams:
                  model_save_best: bool = True, model_save_monitor=("val_acc", "max"),
                  class_weight: Union[list, str, None] = None, channels_last: bool = True,
                  early_stopping: bool = True, restore_best_weights: bool = True, patience: int = 50,
-                 seed: Union[int, None] = None, aug_device: bool = False):
+                 seed: Union[int, None] = None, aug_device: bool = False, pad_mode: Union[str, None] = None,
+                 pad_value=0, ignore_label: Union[int, None] = None):
         if (model_architecture is None and initial_model is None) or (
                 model_architecture is not None and initial_model is not None):
             log.error("Either 'model_architecture' or 'initial_model' need to be provided in the `config.json`.")
@@ -62,6 +63,12 @@ class TrainingParams:
         self.early_stopping = early_stopping
         self.restore_best_weights = restore_best_weights
         self.patience = patience
+        # extensions: scans whose size is no multiple of 2^pool_layers are padded on the device ("edge", "reflect" or "constant"
+        # with pad_value, in raw counts; None refuses them), and pixels labelled ignore_label (a value that is no class) stay
+        # out of the class count, the balanced class weights, the loss and its gradient
+        self.pad_mode = pad_mode
+        self.pad_value = pad_value
+        self.ignore_label = ignore_label
         self.seed = seed  # extension: reproducible shuffling / init (the reference is unseeded)
         if self.model_save_monitor[0] == "val_acc":
             self.model_save_monitor = ["val_" + self.metric, model_save_monitor[1]]
