@@ -20,6 +20,9 @@ from . import _hip
 from ._hip import OctError, UNetCfg, UNetIO, LayerInfo
 
 
+def _ptr(t: Optional[torch.Tensor]): return None if t is None else t.data_ptr()
+
+
 def _require_gpu(device) -> torch.device:
     dev = torch.device(device)
     if dev.type != "cuda" or not torch.cuda.is_available():
@@ -80,6 +83,7 @@ def glorot_init(cfg: UNetCfg, seed: int = 0):
 
 class UNetEngine:
     def __init__(self, *, device="cuda:0", init_seed: int = 0, **cfg_kwargs):
+        self._h = None
         self.device = _require_gpu(device)
         self.cfg = make_cfg(**cfg_kwargs)
         self.layers = layer_table(self.cfg)
@@ -93,24 +97,24 @@ class UNetEngine:
             self.state = torch.from_numpy(s0).to(self.device)
             self.grads = torch.zeros(self.n_params, dtype=torch.float32, device=self.device) if self.cfg.training else None
             self.workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
-            self._loss4 = torch.zeros(4, dtype=torch.float32, device=self.device)
             h = C.c_void_p()
-            _hip.check(l.oct_unet_create(C.byref(self.cfg), self.params.data_ptr(),
-                                         self.grads.data_ptr() if self.grads is not None else None,
-                                         self.state.data_ptr(), self.workspace.data_ptr(), ws_bytes, C.byref(h)),
-                       "oct_unet_create")
+            _hip.check(l.oct_unet_create(C.byref(self.cfg), self.params.data_ptr(), _ptr(self.grads), self.state.data_ptr(),
+                                         self.workspace.data_ptr(), ws_bytes, C.byref(h)), "oct_unet_create")
         self._h = h
         self._opt: Dict[str, torch.Tensor] = {}
         self.opt_step = 0
-        self._keep = []  # tensors referenced by an in-flight / captured launch
+        # kept alive: the tensors an in-flight launch and the captured graph refer to, the event of set_tail_event
+        self._keep, self._graph_keep, self._tail_event = [], [], None
         self._mc: Dict[int, dict] = {}  # forward_mc's buffers per batch size
-        self.ignore_label: Optional[int] = None   # set_ignore_label
+        self._pad_bufs, self._wver = {}, -1  # its Model's: the padded pair per (batch size, image type); the version of the weights held
+        # the loss state: what the set_* calls last selected (set_focal_dice's device buffer and parameters by value too); select_loss's kind
+        self.ignore_label, self._focal_active, self._bce_active = None, False, False
+        self._focal_cw, self._focal_sel, self._loss_kind = None, None, "dice"
 
     def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
+        if self._h:
             try:
-                _hip.lib().oct_unet_destroy(h)
+                _hip.lib().oct_unet_destroy(self._h)
             except Exception:   # interpreter teardown: module globals may already be gone
                 pass
             self._h = None
@@ -130,27 +134,24 @@ class UNetEngine:
         """``name(handle, *args)`` of the library, on the engine's device."""
         _hip.call(name, self.device, self._h, *args)
 
-    def _check_x(self, x: torch.Tensor):
-        # uint8: raw scans; float32: already / 255
+    def _check_x(self, x: torch.Tensor, any_size: bool = False):
+        # uint8: raw scans; float32: already / 255; of the engine's size (any_size: graph_capture_padded's input)
         _hip.expect(x, "input", device=self.device, dtype=(torch.uint8, torch.float32),
-                    shape=(None, self.cfg.H, self.cfg.W, self.cfg.in_ch))
+                    shape=(None,) + ((None, None) if any_size else (self.cfg.H, self.cfg.W)) + (self.cfg.in_ch,))
         if not 1 <= x.shape[0] <= self.cfg.max_batch:
             raise OctError(f"batch {x.shape[0]} outside 1..max_batch={self.cfg.max_batch}")
 
     def _check_labels(self, labels: torch.Tensor, B: int):
         _hip.expect(labels, "labels (B,H,W[,1])", device=self.device, dtype=torch.uint8, numel=B * self.cfg.H * self.cfg.W)
 
-    def _io(self, B, labels, want_probs, want_argmax, probs_out=None, argmax_out=None):
+    def _io(self, B, labels, want_probs, want_argmax, probs_out=None, argmax_out=None, hw=None):
+        H, W = hw or (self.cfg.H, self.cfg.W)
         probs = am = None
         if want_probs:
-            probs = probs_out if probs_out is not None else torch.empty(
-                (B, self.cfg.H, self.cfg.W, self.cfg.n_cls), dtype=torch.float32, device=self.device)
+            probs = probs_out if probs_out is not None else torch.empty((B, H, W, self.cfg.n_cls), dtype=torch.float32, device=self.device)
         if want_argmax:
-            am = argmax_out if argmax_out is not None else torch.empty(
-                (B, self.cfg.H, self.cfg.W), dtype=torch.uint8, device=self.device)
-        io = UNetIO(probs.data_ptr() if probs is not None else None, am.data_ptr() if am is not None else None,
-                    labels.data_ptr() if labels is not None else None)
-        return io, probs, am
+            am = argmax_out if argmax_out is not None else torch.empty((B, H, W), dtype=torch.uint8, device=self.device)
+        return UNetIO(_ptr(probs), _ptr(am), _ptr(labels)), probs, am
 
     # ---- hot path --------------------------------------------------------------------------------
     def forward(self, x: torch.Tensor, training: bool = False, labels: Optional[torch.Tensor] = None,
@@ -176,16 +177,16 @@ class UNetEngine:
     def set_focal_dice(self, focal_loss_weight: float = 0.5, gamma: float = 2.0, class_weight=None) -> None:
         """Select ``focal_dice_loss`` (reference custom_losses.py:98-178) for the following forward / loss / backward
         calls: L = w*focal + (1-w)*dice.  ``focal_loss_weight = 0`` restores the plain Dice losses."""
-        cw = None
-        if class_weight is not None:
-            cw = torch.as_tensor(np.asarray(class_weight, np.float32), device=self.device).contiguous()
-            if cw.numel() != self.cfg.n_cls:
-                raise OctError(f"class_weight must have {self.cfg.n_cls} entries")
+        host = None if class_weight is None else np.asarray(class_weight, np.float32)
+        cw = None if host is None else torch.as_tensor(host, device=self.device).contiguous()
+        if cw is not None and cw.numel() != self.cfg.n_cls:
+            raise OctError(f"class_weight must have {self.cfg.n_cls} entries")
         self._focal_cw = cw          # keep the device buffer alive: the library only stores the pointer
+        self._focal_sel = (float(focal_loss_weight), float(gamma), None if host is None else host.tolist())     # by value
         self._focal_active = float(focal_loss_weight) > 0.0
         if self._focal_active:
             self._bce_active = False     # the library clears it too: the two losses share one slot of the Dice rows
-        self._call("oct_unet_set_focal_dice", float(focal_loss_weight), float(gamma), cw.data_ptr() if cw is not None else None)
+        self._call("oct_unet_set_focal_dice", float(focal_loss_weight), float(gamma), _ptr(cw))
 
     def loss_focal_dice(self, smooth: float = 1e-5) -> torch.Tensor:
         """loss_dice() + [focal term, w*focal+(1-w)*dice_macro, w*focal+(1-w)*dice_micro, 0] (device tensor, 8 floats)."""
@@ -210,6 +211,25 @@ class UNetEngine:
         divides by the counted pixels -- and a zero gradient (``oct_unet_set_ignore_label``).  ``None`` switches it off."""
         self._call("oct_unet_set_ignore_label", -1 if label is None else int(label))
         self.ignore_label = None if label is None else int(label)
+
+    def select_loss(self, kind: str = "dice", focal_loss_weight=0.5, gamma=2.0, class_weight=None, ignore_label=None) -> None:
+        """Put the handle into the loss state a model asks for: ``kind`` "dice", "focal" (with ``set_focal_dice``'s parameters,
+        compared by value) or "bce", and the ignore label.  Only the ``set_*`` calls that change what the engine last had selected
+        are issued: an engine last used by a focal, BCE or masked model comes back to plain Dice over every pixel."""
+        if self.ignore_label != ignore_label:
+            self.set_ignore_label(ignore_label)
+        want = (float(focal_loss_weight), float(gamma), None if class_weight is None else np.asarray(class_weight, np.float32).tolist())
+        if kind == "focal" and not (self._focal_active and self._focal_sel == want):
+            self.set_focal_dice(*want)
+        elif kind != "focal" and self._focal_active:
+            self.set_focal_dice(0.0)
+        if (kind == "bce") != self._bce_active:
+            self.set_bce_dice(kind == "bce")
+        self._loss_kind = kind
+
+    def loss_selected(self, smooth: float = 1e-5) -> torch.Tensor:
+        """The loss vector of the kind last given to ``select_loss``: ``loss_dice``, ``loss_focal_dice`` or ``loss_bce_dice``."""
+        return {"dice": self.loss_dice, "focal": self.loss_focal_dice, "bce": self.loss_bce_dice}[self._loss_kind](smooth)
 
     def backward(self, labels: torch.Tensor, macro: bool = True, loss_scale: float = 1.0):
         self._check_labels(labels, labels.shape[0])
@@ -373,8 +393,7 @@ class UNetEngine:
                                     (entropy, "entropy", torch.float32, (B, H, W)), (mutual_info, "mutual_info", torch.float32, (B, H, W))):
             if t_ is not None:
                 _hip.expect(t_, what, device=self.device, dtype=dt, shape=shape)
-        ptr = lambda t_: t_.data_ptr() if t_ is not None else None
-        out = _hip.McOut(ptr(mean_probs), ptr(argmax), ptr(entropy), ptr(mutual_info))
+        out = _hip.McOut(_ptr(mean_probs), _ptr(argmax), _ptr(entropy), _ptr(mutual_info))
         _hip.call("oct_mc_update", self.device, probs.data_ptr(), B, H, W, Cn, int(t), int(samples), ws.data_ptr(), ws.numel(),
                   C.byref(out), self._stream())
 
@@ -385,12 +404,15 @@ class UNetEngine:
         self._check_x(x)
         io, probs, am = self._io(x.shape[0], None, want_probs, want_argmax)
         self._graph_keep = [x, probs, am]
+        self._capture("oct_unet_graph_capture", x.data_ptr(), int(x.dtype == torch.uint8), x.shape[0], C.byref(io))
+        return probs, am
+
+    def _capture(self, name: str, *args) -> None:
+        """The library's capture call ``name(handle, *args, stream)`` on a side stream, joined to the current one on both ends."""
         s = torch.cuda.Stream(self.device)
         s.wait_stream(torch.cuda.current_stream(self.device))
-        self._call("oct_unet_graph_capture", x.data_ptr(), int(x.dtype == torch.uint8), x.shape[0], C.byref(io),
-                   C.c_void_p(s.cuda_stream))
+        self._call(name, *args, C.c_void_p(s.cuda_stream))
         torch.cuda.current_stream(self.device).wait_stream(s)
-        return probs, am
 
     def graph_launch(self):
         self._call("oct_unet_graph_launch", self._stream())
@@ -422,30 +444,13 @@ class UNetEngine:
         uploaded) or a uint8 device tensor of B*32 bytes that already holds validated descriptors.  ``out``: optional
         ``(x_out, labels_out)`` tensors to write into.  Asynchronous on the current stream."""
         from .common.augmentation import AUG_OP_DTYPE, AUG_SP
-        u8 = dict(device=self.device, dtype=torch.uint8)
-        _hip.expect(x_u8, "augment: images (B,H,W,C)", shape=(None, None, None, None), **u8)
-        B, H, W, Cn = x_u8.shape
-        if labels is not None:
-            _hip.expect(labels, "augment: labels (B,H,W[,1])", numel=B * H * W, **u8)
-        if isinstance(ops, np.ndarray):
-            if ops.dtype != AUG_OP_DTYPE or ops.shape != (B,):
-                raise OctError("augment: ops must hold one AUG_OP_DTYPE descriptor per sample")
+        def check(ops, H, W):
             if ops["kind"].min() < 0 or ops["kind"].max() > AUG_SP:
-                raise OctError("augment: descriptor kind outside 0..5")
-            ops = torch.from_numpy(np.ascontiguousarray(ops).view(np.uint8).copy()).to(self.device)
-        _hip.expect(ops, "augment: ops (B*32 descriptor bytes)", numel=B * AUG_OP_DTYPE.itemsize, **u8)
-        x_out, lab_out = out if out is not None else (None, None)
-        if x_out is None:
-            x_out = torch.empty(x_u8.shape, dtype=torch.float32, device=self.device)
-        if labels is not None and lab_out is None:
-            lab_out = torch.empty(labels.shape, dtype=torch.uint8, device=self.device)
-        _hip.expect(x_out, "augment: out[0]", device=self.device, dtype=torch.float32, shape=tuple(x_u8.shape))
-        if labels is not None:
-            _hip.expect(lab_out, "augment: out[1]", numel=labels.numel(), **u8)
-        _hip.call("oct_augment_batch", self.device, x_u8.data_ptr(), labels.data_ptr() if labels is not None else None,
-                  ops.data_ptr(), B, H, W, Cn, int(seed) & 0xFFFFFFFFFFFFFFFF, x_out.data_ptr(),
-                  lab_out.data_ptr() if labels is not None else None, self._stream())
-        return x_out, (lab_out if labels is not None else None)
+                raise ValueError("augment: descriptor kind outside 0..5")
+        ops, x_out, lab_out = self._stage_io("augment", x_u8, labels, ops, "AUG_OP_DTYPE", AUG_OP_DTYPE, check, out, torch.float32)
+        _hip.call("oct_augment_batch", self.device, x_u8.data_ptr(), _ptr(labels), ops.data_ptr(), *x_u8.shape,
+                  int(seed) & 0xFFFFFFFFFFFFFFFF, x_out.data_ptr(), _ptr(lab_out), self._stream())
+        return x_out, lab_out
 
     def warp(self, x_u8: torch.Tensor, labels: Optional[torch.Tensor], ops, out=None):
         """The geometric augmentations on the device (``oct_warp_batch``): (B,H,W,C) uint8 images, (B,H,W[,1]) uint8 labels
@@ -455,32 +460,35 @@ class UNetEngine:
         descriptors.  ``out``: optional ``(x_out, labels_out)`` tensors to write into; the stage gathers, so neither may
         be an input.  Asynchronous on the current stream."""
         from .common.augmentation import WARP_OP_DTYPE, check_warp_ops
+        ops, x_out, lab_out = self._stage_io("warp", x_u8, labels, ops, "WARP_OP_DTYPE", WARP_OP_DTYPE, check_warp_ops, out, torch.uint8)
+        _hip.call("oct_warp_batch", self.device, x_u8.data_ptr(), _ptr(labels), ops.data_ptr(), *x_u8.shape, x_out.data_ptr(),
+                  _ptr(lab_out), self._stream())
+        return x_out, lab_out
+
+    def _stage_io(self, what, x_u8, labels, ops, op_name, op_dtype, check, out, x_dtype):
+        """``augment`` / ``warp`` (``what``): validates images, labels, descriptors (a numpy array: also by ``check(ops, H, W)``, then
+        uploaded) and ``out``, and makes what of it is missing.  Returns ``(descriptor bytes, x_out, labels_out or None)``."""
         u8 = dict(device=self.device, dtype=torch.uint8)
-        _hip.expect(x_u8, "warp: images (B,H,W,C)", shape=(None, None, None, None), **u8)
-        B, H, W, Cn = x_u8.shape
+        _hip.expect(x_u8, f"{what}: images (B,H,W,C)", shape=(None, None, None, None), **u8)
+        B, H, W, _ = x_u8.shape
         if labels is not None:
-            _hip.expect(labels, "warp: labels (B,H,W[,1])", numel=B * H * W, **u8)
+            _hip.expect(labels, f"{what}: labels (B,H,W[,1])", numel=B * H * W, **u8)
         if isinstance(ops, np.ndarray):
-            if ops.dtype != WARP_OP_DTYPE or ops.shape != (B,):
-                raise OctError("warp: ops must hold one WARP_OP_DTYPE descriptor per sample")
+            if ops.dtype != op_dtype or ops.shape != (B,):
+                raise OctError(f"{what}: ops must hold one {op_name} descriptor per sample")
             try:
-                check_warp_ops(ops, H, W)
+                check(ops, H, W)
             except ValueError as e:
                 raise OctError(str(e)) from None
             ops = torch.from_numpy(np.ascontiguousarray(ops).view(np.uint8).copy()).to(self.device)
-        _hip.expect(ops, "warp: ops (B*40 descriptor bytes)", numel=B * WARP_OP_DTYPE.itemsize, **u8)
+        _hip.expect(ops, f"{what}: ops (B*{op_dtype.itemsize} descriptor bytes)", numel=B * op_dtype.itemsize, **u8)
         x_out, lab_out = out if out is not None else (None, None)
-        if x_out is None:
-            x_out = torch.empty_like(x_u8)
-        if labels is not None and lab_out is None:
-            lab_out = torch.empty_like(labels)
-        _hip.expect(x_out, "warp: out[0]", shape=tuple(x_u8.shape), **u8)
+        x_out = torch.empty(x_u8.shape, dtype=x_dtype, device=self.device) if x_out is None else x_out
+        lab_out = None if labels is None else torch.empty_like(labels) if lab_out is None else lab_out
+        _hip.expect(x_out, f"{what}: out[0]", device=self.device, dtype=x_dtype, shape=tuple(x_u8.shape))
         if labels is not None:
-            _hip.expect(lab_out, "warp: out[1]", numel=labels.numel(), **u8)
-        _hip.call("oct_warp_batch", self.device, x_u8.data_ptr(), labels.data_ptr() if labels is not None else None,
-                  ops.data_ptr(), B, H, W, Cn, x_out.data_ptr(), lab_out.data_ptr() if labels is not None else None,
-                  self._stream())
-        return x_out, (lab_out if labels is not None else None)
+            _hip.expect(lab_out, f"{what}: out[1]", numel=labels.numel(), **u8)
+        return ops, x_out, lab_out
 
     # ---- pad and crop: scans whose size is no multiple of 2^pool_layers ------------------------------
     def pad(self, x: torch.Tensor, Hp: int, Wp: int, top: int, left: int, mode: str, value=0, out=None) -> torch.Tensor:
@@ -520,23 +528,16 @@ class UNetEngine:
         size: captures ``pad`` of the fixed (B,H,W,ch) input ``x`` at (top, left), the forward and the ``crop`` of every
         output into ONE graph (``oct_unet_graph_capture_padded``); returns the (probs, argmax) tensors of size (H, W) that
         every ``graph_launch`` refills.  ``x`` must be refilled in place between launches."""
-        _hip.expect(x, "input", device=self.device, dtype=(torch.uint8, torch.float32), shape=(None, None, None, self.cfg.in_ch))
+        self._check_x(x, any_size=True)
         if mode not in _hip.PAD_MODES:
             raise OctError(f'graph_capture_padded: mode must be "edge", "reflect" or "constant", not {mode!r}')
         B, H, W, _ = x.shape
-        if not 1 <= B <= self.cfg.max_batch:
-            raise OctError(f"batch {B} outside 1..max_batch={self.cfg.max_batch}")
         x_pad = torch.empty((B, self.cfg.H, self.cfg.W, self.cfg.in_ch), dtype=x.dtype, device=self.device)
         io_pad, probs_pad, am_pad = self._io(B, None, want_probs, want_argmax)
-        probs = torch.empty((B, H, W, self.cfg.n_cls), dtype=torch.float32, device=self.device) if want_probs else None
-        am = torch.empty((B, H, W), dtype=torch.uint8, device=self.device) if want_argmax else None
-        io_crop = UNetIO(probs.data_ptr() if probs is not None else None, am.data_ptr() if am is not None else None, None)
+        io_crop, probs, am = self._io(B, None, want_probs, want_argmax, hw=(H, W))
         self._graph_keep = [x, x_pad, probs_pad, am_pad, probs, am]
-        s = torch.cuda.Stream(self.device)
-        s.wait_stream(torch.cuda.current_stream(self.device))
-        self._call("oct_unet_graph_capture_padded", x.data_ptr(), int(x.dtype == torch.uint8), B, H, W, int(top), int(left),
-                   _hip.PAD_MODES[mode], float(value), x_pad.data_ptr(), C.byref(io_pad), C.byref(io_crop), C.c_void_p(s.cuda_stream))
-        torch.cuda.current_stream(self.device).wait_stream(s)
+        self._capture("oct_unet_graph_capture_padded", x.data_ptr(), int(x.dtype == torch.uint8), B, H, W, int(top), int(left),
+                      _hip.PAD_MODES[mode], float(value), x_pad.data_ptr(), C.byref(io_pad), C.byref(io_crop))
         return probs, am
 
     # ---- weights exchange --------------------------------------------------------------------------
@@ -608,7 +609,6 @@ class UNetEngine:
 
     def handle_option(self, name: str) -> int:
         """The value of a tuning option as this handle snapshotted it at creation."""
-        import ctypes as C
         v = C.c_int(0)
         _hip.check(_hip.lib().oct_unet_get_option(self._h, name.encode(), C.byref(v)), f"oct_unet_get_option({name})")
         return int(v.value)

@@ -23,6 +23,7 @@ import torch
 
 from .. import parallel
 from .._hip import OctError
+from .batch_feed import BatchFeed
 
 WEIGHTS_FORMAT = "oct_unet_weights_v1"
 
@@ -110,7 +111,8 @@ class Model:
         self.output = SimpleNamespace(shape=(None, None, None, int(config["num_classes"])))
         self.stop_training = False
         self.optimizer = None
-        self._loss_name = self._metric_name = None
+        self._loss_name = self._metric_name = self._focal = None      # _focal: focal_dice_loss's parameters
+        self._feed = self._reducer = None     # the input path of fit / evaluate (``feed``); the training engine's GradReducer
         self._engine = None             # the ACTIVE engine: the one that holds the model's current weights
         self._engines = {}              # the geometry cache: {"train": engine, "other": engine}, at most these two
         self._wver = 0                  # version of the model's weights; an engine's _wver says which version it holds
@@ -155,6 +157,17 @@ class Model:
         Hp, Wp, top, left = padded_geometry(H, W, c.get("pool_layers", 4))
         return (Hp, Wp), (top, left)
 
+    def _cfg_kwargs(self, hw=None) -> dict:
+        """The architecture keywords of ``make_cfg`` / ``UNetEngine`` from the config, at geometry ``hw`` -- None: the config's
+        size, padded where it is no multiple of 2^pool_layers."""
+        c = self.config
+        H, W = hw or self._geometry(None, "edge")[0]
+        return dict(input_channels=c["input_channels"], num_classes=c["num_classes"], image_height=H, image_width=W,
+                    start_neurons=c.get("start_neurons", 8), pool_layers=c.get("pool_layers", 4),
+                    conv_layers=c.get("conv_layers", 2), enc_kernel=tuple(c.get("enc_kernel", (3, 3))),
+                    dec_kernel=tuple(c.get("dec_kernel", (2, 2))),
+                    dtype=c.get("dtype", "float32"))   # extension key: 'bfloat16' = bf16 activation storage (BASELINE configs[2])
+
     def _mark_changed(self, eng) -> None:
         """``eng`` -- the active engine -- has changed the model's weights (an optimizer step, ``set_weights``, the moving
         statistics of a training forward): every other cached engine is stale from here on."""
@@ -165,7 +178,7 @@ class Model:
         """Make ``eng`` the active engine; if another engine changed the weights since ``eng`` last held them, they move
         first: a device-to-device copy of the two flat tensors, whose layout does not depend on H, W."""
         cur = self._engine
-        if cur is not None and cur is not eng and getattr(eng, "_wver", -1) != self._wver:
+        if cur is not None and cur is not eng and eng._wver != self._wver:
             eng.params.copy_(cur.params); eng.state.copy_(cur.state)
         eng._wver = self._wver
         self._engine = eng
@@ -187,19 +200,10 @@ class Model:
         old = [e for e in cache.values() if fits(e)]
         max_batch = max([batch] + [e.cfg.max_batch for e in old])
         training = training or any(bool(e.cfg.training) for e in old)
-        rank, _, _ = parallel.env_rank()
-        c = self.config
-        new = UNetEngine(
-            device=self._dev(), input_channels=c["input_channels"], num_classes=c["num_classes"],
-            image_height=H, image_width=W,
-            start_neurons=c.get("start_neurons", 8), pool_layers=c.get("pool_layers", 4),
-            conv_layers=c.get("conv_layers", 2), enc_kernel=tuple(c.get("enc_kernel", (3, 3))),
-            dec_kernel=tuple(c.get("dec_kernel", (2, 2))),
-            max_batch=max_batch, training=training,
-            seed=int(c.get("seed", 0)) * 1000003 + rank, init_seed=int(c.get("seed", 0)),
-            dtype=c.get("dtype", "float32"))   # extension key: 'bfloat16' = bf16 activation storage (BASELINE configs[2])
-        cur = self._engine
-        if cur is None and self._pending_weights is not None:
+        seed, rank = int(self.config.get("seed", 0)), parallel.env_rank()[0]
+        new = UNetEngine(device=self._dev(), max_batch=max_batch, training=training, seed=seed * 1000003 + rank, init_seed=seed,
+                         **self._cfg_kwargs((H, W)))
+        if self._engine is None and self._pending_weights is not None:
             new.set_weights(self._pending_weights)
         self._pending_weights = None
         if training:
@@ -219,7 +223,7 @@ class Model:
             self._pending_weights = self._engine.get_weights()
         self._engine = None
         self._engines = {}
-        self.__dict__.pop("_reducer", None)
+        self._reducer = None
 
     @property
     def engine(self):
@@ -261,28 +265,16 @@ class Model:
         self.optimizer, self._loss_name, self._metric_name = optimizer, loss_name, metric_name
 
     def count_params(self) -> int:
-        from ..common.utils import padded_geometry
         from ..engine import make_cfg
         from .. import _hip
         import ctypes as C
-        c = self.config
-        # (the table is that of the padded geometry where the config's size is no multiple of 2^pool_layers)
-        Hp, Wp, _, _ = padded_geometry(c["image_height"], c["image_width"], c.get("pool_layers", 4))
-        cfg = make_cfg(input_channels=c["input_channels"], num_classes=c["num_classes"], image_height=Hp,
-                       image_width=Wp, start_neurons=c.get("start_neurons", 8),
-                       pool_layers=c.get("pool_layers", 4), conv_layers=c.get("conv_layers", 2))
+        cfg = make_cfg(**self._cfg_kwargs())    # (the padded geometry's table where the config's size is no multiple of 2^pool_layers)
         l = _hip.lib()
         return int(l.oct_unet_param_count(C.byref(cfg)) + l.oct_unet_state_count(C.byref(cfg)))
 
     def summary(self, print_fn=print):
-        from ..common.utils import padded_geometry
         from ..engine import make_cfg, layer_table
-        c = self.config
-        # (the table is that of the padded geometry where the config's size is no multiple of 2^pool_layers)
-        Hp, Wp, _, _ = padded_geometry(c["image_height"], c["image_width"], c.get("pool_layers", 4))
-        cfg = make_cfg(input_channels=c["input_channels"], num_classes=c["num_classes"], image_height=Hp,
-                       image_width=Wp, start_neurons=c.get("start_neurons", 8),
-                       pool_layers=c.get("pool_layers", 4), conv_layers=c.get("conv_layers", 2))
+        cfg = make_cfg(**self._cfg_kwargs())    # (the padded geometry's table where the config's size is no multiple of 2^pool_layers)
         print_fn(f'Model: "{self.name}"  (MI355X HIP engine)')
         print_fn(f"{'layer':14s}{'kernel':>8s}{'in':>6s}{'out':>6s}{'HxW':>12s}{'params':>10s}")
         tot = 0
@@ -336,187 +328,87 @@ class Model:
         return path
 
     # ---- training -------------------------------------------------------------------------------------
-    def _host_batch(self, seq, index, rank, world):
-        """One GLOBAL batch from the Sequence -> this rank's (x, sparse uint8 labels) host arrays; for a Sequence that
-        augments on the device (``oct_device_aug``) the raw uint8 images and a third array, the per-sample descriptors --
-        and a fourth, the warp descriptors, where this rank's slice holds a sample that is warped."""
-        if getattr(seq, "oct_device_aug", False):
-            hb = seq.next_batch_aug(parallel.shard_batch(seq.batch_size, rank, world) if world > 1 else None)
-            return hb[:3] if len(hb) > 3 and not hb[3]["kind"].any() else hb      # no warp sample: the stage is skipped
-        if getattr(seq, "oct_fast_path", False):
-            if world > 1:      # gather this rank's slice only (8 ranks: 1/8 of the host work per step and rank)
-                return seq.next_batch_u8(parallel.shard_batch(seq.batch_size, rank, world))
-            X, lab = seq.next_batch_u8()
-        else:
-            X, y = seq[index]
-            X = np.ascontiguousarray(X, dtype=np.float32)
-            y = np.asarray(y)
-            lab = (np.argmax(y, axis=-1) if (y.ndim == 4 and y.shape[-1] > 1) else y.reshape(y.shape[:3])).astype(np.uint8)
-        lo, hi = parallel.shard_batch(X.shape[0], rank, world)
-        return X[lo:hi], lab[lo:hi]
+    @property
+    def feed(self) -> BatchFeed:
+        """The model's input path, made at first use (the device may be set after construction)."""
+        self._feed = self._feed or BatchFeed(self._dev())
+        return self._feed
 
-    def _upload(self, X: np.ndarray, lab: np.ndarray, slot: int, ops: Optional[np.ndarray] = None,
-                wops: Optional[np.ndarray] = None):
-        """Queue the upload of one batch into device slot ``slot`` on the COPY stream (never on the compute stream: 8 MB of
-        uint8 per 32-scan batch would otherwise sit in front of every step).  Pinned staging buffers and device buffers come
-        in THREE slots: slot s is refilled only after the step that last read its device tensors has finished -- a HOST
-        wait on that step's event, two steps back, which also keeps this thread at most two steps ahead of the GPU.  (With two
-        slots the copy had to wait for the previous step on the copy stream; the H2D call then held the host until that
-        step was over and every step started with the launch latency exposed: 0.91 of the resident-input rate.)
-        ``ops`` (device augmentation: one 32-byte descriptor per sample) travels through the same slot as raw bytes, and so
-        does ``wops`` (one 40-byte warp descriptor per sample).
-        Returns (x, labels, ready event, descriptor bytes or None), with ``wops`` a fifth element, the warp descriptor bytes."""
-        dev = self._engine.device if self._engine is not None else self._dev()
-        st = self.__dict__.setdefault("_up", {"copy": None, "ev": {}, "done": {}, "dev": {}})
-        if dev.type != "cuda":
-            raw = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).copy())
-            return (torch.from_numpy(np.ascontiguousarray(X)), torch.from_numpy(np.ascontiguousarray(lab)), None,
-                    raw(ops)) + (() if wops is None else (raw(wops),))
-        if st["copy"] is None:
-            st["copy"] = torch.cuda.Stream(device=dev)
-        if slot in st["done"]:
-            st["done"][slot].synchronize()        # host: the step that read this slot three batches ago is over
-        if slot in st["ev"]:
-            st["ev"][slot].synchronize()          # host: the H2D copies that last read this slot's pinned buffers have executed
-        xp, lp = self._staged(("x", slot), X), self._staged(("l", slot), lab)
-        op = None if ops is None else self._staged(("o", slot), np.ascontiguousarray(ops).view(np.uint8))
-        wop = None if wops is None else self._staged(("w", slot), np.ascontiguousarray(wops).view(np.uint8))
-        bufs = st["dev"].get(slot)
-        if bufs is None or bufs[0].shape != xp.shape or bufs[0].dtype != xp.dtype or bufs[1].shape != lp.shape:
-            bufs = st["dev"][slot] = (torch.empty(xp.shape, dtype=xp.dtype, device=dev), torch.empty(lp.shape, dtype=lp.dtype, device=dev))
-        obuf = None
-        if op is not None:
-            obuf = st.setdefault("ops", {}).get(slot)
-            if obuf is None or obuf.shape != op.shape:
-                obuf = st["ops"][slot] = torch.empty(op.shape, dtype=torch.uint8, device=dev)
-        wbuf = None
-        if wop is not None:
-            wbuf = st.setdefault("wops", {}).get(slot)
-            if wbuf is None or wbuf.shape != wop.shape:
-                wbuf = st["wops"][slot] = torch.empty(wop.shape, dtype=torch.uint8, device=dev)
-        with torch.cuda.stream(st["copy"]):
-            bufs[0].copy_(xp, non_blocking=True); bufs[1].copy_(lp, non_blocking=True)
-            if op is not None:
-                obuf.copy_(op, non_blocking=True)
-            if wop is not None:
-                wbuf.copy_(wop, non_blocking=True)
-            ev = torch.cuda.Event(); ev.record(st["copy"])
-        st["ev"][slot] = ev
-        return (bufs[0], bufs[1], ev, obuf) + (() if wbuf is None else (wbuf,))
-
-    def _augment(self, eng, seq, x, lab, ops, wops=None):
-        """Device augmentation of one uploaded batch on the compute stream (behind the slot's ready event) into ONE
-        model-owned pair of buffers: the next step's augment is queued on the same stream behind this step's backward, the
-        last reader of the pair, so one pair is enough.  With warp descriptors the batch first goes through ``warp`` into
-        a second, uint8 pair under the same rule: its only reader is the ``augment`` queued right behind it."""
-        if wops is not None:
-            wbuf = self.__dict__.get("_warp_out")
-            if wbuf is None or wbuf[0].shape != x.shape or wbuf[1].shape != lab.shape or wbuf[0].device != x.device:
-                wbuf = self._warp_out = (torch.empty_like(x), torch.empty_like(lab))
-            x, lab = eng.warp(x, lab, wops, out=wbuf)
-        buf = self.__dict__.get("_aug_out")
-        if buf is None or buf[0].shape != x.shape or buf[1].shape != lab.shape or buf[0].device != x.device:
-            buf = self._aug_out = (torch.empty(x.shape, dtype=torch.float32, device=x.device), torch.empty_like(lab))
-        return eng.augment(x, lab, ops, seq.oct_aug_seed, out=buf)
+    def _staged(self, key, arr: np.ndarray) -> torch.Tensor: return self.feed.staged(key, arr)
 
     def _pad_batch(self, eng, x, lab, at, pad_mode, pad_value, ignore):
         """One batch of a size that is no multiple of 2^pool_layers -> the engine's geometry, on the compute stream: the images
         by ``pad_mode``, the labels -- same kernel, it moves bytes -- in ``constant`` mode with the ignore label.  The padded
         pair belongs to ``eng`` and is made once per batch size (and image type): its last reader, this step's backward,
         is queued on the same stream in front of the next step's pad, so one pair is enough."""
-        bufs = eng.__dict__.setdefault("_pad_bufs", {})
         B, (Hp, Wp) = x.shape[0], (eng.cfg.H, eng.cfg.W)
-        pair = bufs.get((B, x.dtype))
+        pair = eng._pad_bufs.get((B, x.dtype))
         if pair is None:
-            pair = bufs[(B, x.dtype)] = (torch.empty((B, Hp, Wp, x.shape[3]), dtype=x.dtype, device=x.device),
-                                         torch.empty((B, Hp, Wp, 1), dtype=torch.uint8, device=x.device))
+            pair = eng._pad_bufs[(B, x.dtype)] = (torch.empty((B, Hp, Wp, x.shape[3]), dtype=x.dtype, device=x.device),
+                                                  torch.empty((B, Hp, Wp, 1), dtype=torch.uint8, device=x.device))
         xp = eng.pad(x, Hp, Wp, *at, pad_mode, pad_value, out=pair[0])
         lp = eng.pad(lab.view(B, x.shape[1], x.shape[2], 1), Hp, Wp, *at, "constant", ignore, out=pair[1])
         return xp, lp
 
-    def _release(self, slot: int):
-        """The compute stream is done reading device slot ``slot`` (recorded behind the step that used it)."""
-        st = self.__dict__.get("_up")
-        if st and st["copy"] is not None:
-            dev = self._engine.device
-            e = torch.cuda.Event(); e.record(torch.cuda.current_stream(dev)); st["done"][slot] = e
-
-    def _staged(self, key, arr: np.ndarray) -> torch.Tensor:
-        arr = np.ascontiguousarray(arr)
-        pool = self.__dict__.setdefault("_pinned", {})
-        buf = pool.get(key)
-        if buf is None or buf.shape != arr.shape or buf.numpy().dtype != arr.dtype:
-            buf = torch.from_numpy(np.empty_like(arr))
-            if torch.cuda.is_available():
-                buf = buf.pin_memory()
-            pool[key] = buf
-        buf.numpy()[...] = arr
-        return buf
+    def _loss_plan(self):
+        """``(kind, focal parameters)`` for ``UNetEngine.select_loss``, ``macro`` for the backward, and the index of the logged
+        loss in the loss vector of that kind (bce_dice_loss is bce + dice_loss_micro: the micro combination only)."""
+        f = self._focal
+        kind = "focal" if f else "bce" if self._loss_name == "bce_dice_loss" else "dice"
+        macro = f["dice_macro"] if f else self._loss_name not in ("dice_loss_micro", "bce_dice_loss")
+        params = (f["focal_loss_weight"], f["gamma"], f["class_weight"]) if f else ()
+        return kind, params, macro, (0 if kind == "dice" else 5) + (0 if macro else 1)
 
     def _run_epoch(self, seq, training: bool, rank: int, world: int):
-        focal = getattr(self, "_focal", None)
-        bce = self._loss_name == "bce_dice_loss"        # bce + dice_loss_micro: the micro combination only
-        macro = focal["dice_macro"] if focal else self._loss_name not in ("dice_loss_micro", "bce_dice_loss")
+        kind, focal, macro, loss_at = self._loss_plan()
         pad_mode, pad_value = self._pad_options(None, 0) if self._pad_fit else (None, 0.0)
-        acc = None
-        n = len(seq)
+        feed, acc, n = self.feed, None, len(seq)
         # the upload of batch i+1 (host gather -> pinned buffers -> H2D on the copy stream) is queued before step i is
         # launched, so it runs under that step
-        def queue(index):       # (x, labels[, descriptors]) of batch `index` into slot index % 3
-            hb = self._host_batch(seq, index, rank, world)
-            return self._upload(hb[0], hb[1], index % 3, *hb[2:])
+        queue = lambda i: feed.upload(feed.host_batch(seq, i, rank, world), i % 3)      # noqa: E731
         nxt = queue(0) if n else None
         for i in range(n):
-            x, lab, ready, ops, *wops = nxt
-            if ready is not None:
-                torch.cuda.current_stream(x.device).wait_event(ready)
+            b = nxt
+            if b.ready is not None:
+                torch.cuda.current_stream(b.x.device).wait_event(b.ready)
             if i + 1 < n:
                 nxt = queue(i + 1)
             # validation data may have another size; one that is no multiple of 2^pool_layers runs on the engine of the padded
             # geometry under the model's pad_mode (None, or a model not compiled with one: the OctError of _geometry)
+            x, lab = b.x, b.labels
             hw, raw_u8 = tuple(x.shape[1:3]), x.dtype == torch.uint8
             try:
                 geom, at = self._geometry(hw, pad_mode)
             except OctError as e:
                 raise OctError(f"{e}; fit / evaluate pad such batches in a model compiled with compile(pad_mode=...)") from None
             eng = self._ensure_engine(x.shape[0], training, hw=geom)
-            if ops is not None:
-                x, lab = self._augment(eng, seq, x, lab, ops, *wops)    # at the true size: the frame is not warped or flipped
+            if b.ops is not None:
+                x, lab = feed.augment(eng, seq.oct_aug_seed, b)    # at the true size: the frame is not warped or flipped
             ignore = self.ignore_label
             if at is not None:
                 ignore = 255 if ignore is None else ignore
                 # pad_value is in the units of the Sequence's batches: raw counts where the augment stage has turned them to [0, 1]
                 x, lab = self._pad_batch(eng, x, lab, at, pad_mode, pad_value / 255.0 if raw_u8 and x.dtype != torch.uint8 else pad_value,
                                          ignore)
-            if eng.ignore_label != ignore:     # also: an engine last used by a masked model goes back to counting every pixel
-                eng.set_ignore_label(ignore)
-            if focal:      # (re)selected per batch: _ensure_engine may have built a new engine
-                eng.set_focal_dice(focal["focal_loss_weight"], focal["gamma"], focal["class_weight"])
-            elif getattr(eng, "_focal_active", False):
-                eng.set_focal_dice(0.0)     # an engine last used by a focal model goes back to the plain Dice losses
-            if bce:
-                eng.set_bce_dice(True)
-            elif getattr(eng, "_bce_active", False):
-                eng.set_bce_dice(False)     # ... and one last used by a BCE model too
+            eng.select_loss(kind, *focal, ignore_label=ignore)      # per batch: the engine may be new, or another model's last
             eng.forward(x, training=training, labels=lab, want_probs=False)
-            loss4 = eng.loss_focal_dice() if focal else (eng.loss_bce_dice() if bce else eng.loss_dice())
+            loss = eng.loss_selected()
             if training:
-                red = getattr(self, "_reducer", None)
-                if red is None or red.engine is not eng:       # _ensure_engine may have built a new engine
-                    red = self._reducer = parallel.GradReducer(eng, overlap=True)
+                if self._reducer is None or self._reducer.engine is not eng:       # _ensure_engine may have built a new engine
+                    self._reducer = parallel.GradReducer(eng, overlap=True)
                 # backward + all-reduce (the decoder half on a side stream under the encoder backward)
-                red.backward_and_reduce(lab, macro=macro, loss_scale=1.0 / world)
+                self._reducer.backward_and_reduce(lab, macro=macro, loss_scale=1.0 / world)
                 self.optimizer.apply(eng)
                 self._mark_changed(eng)      # (the training forward's moving statistics included)
-            acc = loss4.clone() if acc is None else acc + loss4
-            self._release(i % 3)
+            acc = loss.clone() if acc is None else acc + loss
+            feed.release(i % 3)
         if acc is None:
             return {}
         acc = acc / n
         if world > 1:
             torch.distributed.all_reduce(acc); acc /= world
         v = acc.cpu().numpy()
-        out = {"loss": float((v[5] if macro else v[6]) if (focal or bce) else (v[0] if macro else v[1]))}
+        out = {"loss": float(v[loss_at])}
         if self._metric_name:
             out[self._metric_name] = float(v[2] if self._metric_name == "dice_coef_macro" else v[3])
         return out
@@ -572,12 +464,22 @@ class Model:
             pad_mode, pad_value = self.pad_mode, self.pad_value
         return check_pad_mode(pad_mode, pad_value)
 
-    def _inference_engine(self, batch: int, hw, pad_mode=None):
-        """``(engine, at)`` for inference on ``batch`` images of size ``hw``: the engine of that geometry and ``at = None``
-        -- or, for a size that is no multiple of 2^pool_layers under a ``pad_mode``, the engine of the padded geometry and
-        ``at = (top, left)``, where ``UNetEngine.pad`` places the images and ``UNetEngine.crop`` finds the outputs."""
-        geom, at = self._geometry(hw, pad_mode)
-        return self._ensure_engine(batch, False, hw=geom), at
+    def _inference_batches(self, x: np.ndarray, bs: int, pad):
+        """The loop of the predict methods over host array ``x`` in batches of ``bs`` under the validated ``pad`` = (pad_mode,
+        pad_value): yields per batch the host slice bounds ``lo, hi``, the engine of the images' geometry, the batch on the device
+        and ``crop``, the identity.  For a size that is no multiple of 2^pool_layers the engine is that of the padded geometry, the
+        batch is padded (``UNetEngine.pad``) and ``crop`` takes a tensor, a dict of tensors or None back to the images' size."""
+        n, (H, W) = x.shape[0], x.shape[1:3]
+        geom, at = self._geometry((H, W), pad[0])
+        eng = self._ensure_engine(min(bs, n), False, hw=geom)
+
+        def crop(t):
+            if at is None or t is None:
+                return t
+            return {k: crop(v) for k, v in t.items()} if isinstance(t, dict) else eng.crop(t, H, W, *at)
+        for lo in range(0, n, bs):
+            xb = torch.from_numpy(np.ascontiguousarray(x[lo:lo + bs])).to(eng.device)
+            yield lo, min(lo + bs, n), eng, (xb if at is None else eng.pad(xb, eng.cfg.H, eng.cfg.W, *at, *pad)), crop
 
     def predict(self, x, verbose=0, batch_size: Optional[int] = None, pad_mode: Optional[str] = None, pad_value=0,
                 **kwargs) -> np.ndarray:
@@ -586,23 +488,13 @@ class Model:
         ``pad_mode`` ("edge", "reflect" or "constant" with ``pad_value``, in the units of ``x``): the batch is padded on
         the device in front of the forward and the output cropped behind it (placement: ``common.utils.padded_geometry``).
         ``pad_mode=None`` takes the model's ``pad_mode`` / ``pad_value`` attributes, which are None / 0 unless set."""
-        pad_mode, pad_value = self._pad_options(pad_mode, pad_value)
+        pad = self._pad_options(pad_mode, pad_value)
         x = np.asarray(x)
         if x.dtype != np.uint8:
             x = np.ascontiguousarray(x, dtype=np.float32)   # Keras casts the float64 the reference passes to float32
-        n = x.shape[0]
-        bs = int(batch_size or min(n, 32))
-        (H, W) = x.shape[1:3]
-        eng, at = self._inference_engine(min(bs, n), (H, W), pad_mode)
-        out = np.empty((n, H, W, self.config["num_classes"]), np.float32)
-        for lo in range(0, n, bs):
-            xb = torch.from_numpy(np.ascontiguousarray(x[lo:lo + bs])).to(eng.device)
-            if at is not None:
-                xb = eng.pad(xb, eng.cfg.H, eng.cfg.W, *at, pad_mode, pad_value)
-            probs, _ = eng.forward(xb, training=False)
-            if at is not None:
-                probs = eng.crop(probs, H, W, *at)
-            out[lo:lo + bs] = probs.cpu().numpy()
+        out = np.empty(x.shape[:3] + (self.config["num_classes"],), np.float32)
+        for lo, hi, eng, xb, crop in self._inference_batches(x, int(batch_size or min(x.shape[0], 32)), pad):
+            out[lo:hi] = crop(eng.forward(xb, training=False)[0]).cpu().numpy()
         return out
 
     def predict_mc(self, x, samples: int, batch_size: Optional[int] = None, step0: int = 0):
@@ -613,24 +505,16 @@ class Model:
         per rank, so an image's result depends on its position in its batch (hence on ``batch_size``) and on the rank.
         Padding as for ``predict``, from the model's ``pad_mode`` / ``pad_value`` attributes (this method's parameter list
         is fixed): the three maps are cropped on the device."""
-        pad_mode, pad_value = self._pad_options(None, 0)
         x = np.asarray(x)
         if x.dtype != np.uint8:
             x = np.ascontiguousarray(x, dtype=np.float32)
-        n = x.shape[0]
-        bs = int(batch_size or min(n, 32))
-        (H, W) = x.shape[1:3]
-        eng, at = self._inference_engine(min(bs, n), (H, W), pad_mode)
-        mean = np.empty((n, H, W, self.config["num_classes"]), np.float32)
+        keys = ("mean_probs", "entropy", "mutual_info")
+        mean = np.empty(x.shape[:3] + (self.config["num_classes"],), np.float32)
         ent, mi = np.empty(x.shape[:3], np.float32), np.empty(x.shape[:3], np.float32)
-        for lo in range(0, n, bs):
-            xb = torch.from_numpy(np.ascontiguousarray(x[lo:lo + bs])).to(eng.device)
-            if at is not None:
-                xb = eng.pad(xb, eng.cfg.H, eng.cfg.W, *at, pad_mode, pad_value)
+        for lo, hi, eng, xb, crop in self._inference_batches(x, int(batch_size or min(x.shape[0], 32)), self._pad_options(None, 0)):
             out = eng.forward_mc(xb, samples, step0=step0, want_mean_probs=True)
-            if at is not None:
-                out = {k: eng.crop(out[k], H, W, *at) for k in ("mean_probs", "entropy", "mutual_info")}
-            mean[lo:lo + bs], ent[lo:lo + bs], mi[lo:lo + bs] = (out[k].cpu().numpy() for k in ("mean_probs", "entropy", "mutual_info"))
+            out = crop({k: out[k] for k in keys})
+            mean[lo:hi], ent[lo:hi], mi[lo:hi] = (out[k].cpu().numpy() for k in keys)
         return mean, ent, mi
 
     def predict_labels(self, x_u8: np.ndarray, batch_size: int = 32, want_maps: bool = False, bg_ilm: bool = True,
@@ -655,30 +539,21 @@ class Model:
             # path means "already normalised", so do the division here rather than silently skipping it
             x_u8 = np.ascontiguousarray(x_u8.astype(np.float32) / np.float32(255.0))
             pad_value = float(np.float32(pad_value) / np.float32(255.0))
-        n, (H, W) = x_u8.shape[0], x_u8.shape[1:3]
-        eng, at = self._inference_engine(min(batch_size, n), (H, W), pad_mode)
         out = np.empty(x_u8.shape[:3], np.uint8)
-        maps = np.empty((n, self.config["num_classes"] - 1) + tuple(x_u8.shape[1:3]), np.uint8) if want_maps else None
+        maps = np.empty((x_u8.shape[0], self.config["num_classes"] - 1) + tuple(x_u8.shape[1:3]), np.uint8) if want_maps else None
         unc = (np.empty(x_u8.shape[:3], np.float32), np.empty(x_u8.shape[:3], np.float32)) if mc_samples else ()
-        for lo in range(0, n, batch_size):
-            xb = torch.from_numpy(x_u8[lo:lo + batch_size]).to(eng.device)
-            if at is not None:
-                xb = eng.pad(xb, eng.cfg.H, eng.cfg.W, *at, pad_mode, pad_value)
+        for lo, hi, eng, xb, crop in self._inference_batches(x_u8, batch_size, (pad_mode, pad_value)):
             if mc_samples:
-                mc = eng.forward_mc(xb, mc_samples, step0=mc_step0, want_mean_probs=soft_maps)
-                if at is not None:
-                    mc = {k: eng.crop(t, H, W, *at) for k, t in mc.items()}
+                mc = crop(eng.forward_mc(xb, mc_samples, step0=mc_step0, want_mean_probs=soft_maps))
                 probs, am = mc.get("mean_probs"), mc["argmax"]
-                unc[0][lo:lo + batch_size], unc[1][lo:lo + batch_size] = mc["entropy"].cpu().numpy(), mc["mutual_info"].cpu().numpy()
+                unc[0][lo:hi], unc[1][lo:hi] = mc["entropy"].cpu().numpy(), mc["mutual_info"].cpu().numpy()
             else:
-                probs, am = eng.forward(xb, training=False, want_probs=soft_maps, want_argmax=True)
-                if at is not None:
-                    probs, am = (None if probs is None else eng.crop(probs, H, W, *at)), eng.crop(am, H, W, *at)
-            out[lo:lo + batch_size] = am.cpu().numpy()
+                probs, am = map(crop, eng.forward(xb, training=False, want_probs=soft_maps, want_argmax=True))
+            out[lo:hi] = am.cpu().numpy()
             if want_maps:
                 dev_maps = (eng.boundary_maps_soft(probs, bg_ilm=bg_ilm, bg_csi=bg_csi) if soft_maps
                             else eng.boundary_maps(am, bg_ilm=bg_ilm, bg_csi=bg_csi))
-                maps[lo:lo + batch_size] = dev_maps.cpu().numpy()
+                maps[lo:hi] = dev_maps.cpu().numpy()
         return ((out, maps) if want_maps else out) if not mc_samples else ((out, maps) + unc if want_maps else (out,) + unc)
 
 

@@ -219,11 +219,10 @@ def _augmented_batches(rank, world):
     gen = DataGenerator(images, labels, G, DP_AUGS, "one", (0.4, 0.2, 0.2, 0.2), True, None, seed=77, device_aug=True)
     outs = []
     for i in range(3):
-        hb = model._host_batch(gen, i, rank, world)
-        x, lab, ready, ops = model._upload(hb[0], hb[1], i % 3, *hb[2:])
-        torch.cuda.current_stream().wait_event(ready)
-        e = model._ensure_engine(x.shape[0], True)
-        xa, la = model._augment(e, gen, x, lab, ops)
+        b = model.feed.upload(model.feed.host_batch(gen, i, rank, world), i % 3)
+        torch.cuda.current_stream().wait_event(b.ready)
+        e = model._ensure_engine(b.x.shape[0], True)
+        xa, la = model.feed.augment(e, gen.oct_aug_seed, b)
         torch.cuda.synchronize()
         outs.append((xa.cpu().numpy().copy(), la.cpu().numpy().copy()))
         if i == 0:

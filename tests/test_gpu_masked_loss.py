@@ -394,7 +394,7 @@ def test_ignore_label_without_padding_in_fit():
     model = _compiled(cfg, w0, ignore_label=200)
     hist = model.fit(_Batches(images, labels, 2), epochs=1, verbose=0)
     eng = model._engines["train"]
-    assert eng.ignore_label == 200 and "_pad_bufs" not in eng.__dict__
+    assert eng.ignore_label == 200 and eng._pad_bufs == {}
     native = _engine(cfg, w0, 2, training=True)
     native.set_ignore_label(200)
     x, lab = _Batches(images, labels, 2).items[0]

@@ -230,7 +230,7 @@ def test_fit_with_warps_equals_the_host_path(mode, probs, batch):
         torch.cuda.synchronize()
         got.append((model.engine.params.cpu().numpy(), model.engine.state.cpu().numpy(), hist.history["loss"]))
         if device_aug:
-            assert "_warp_out" in model.__dict__         # the warp stage ran
+            assert model.feed.warp_out is not None       # the warp stage ran
     assert np.array_equal(got[0][0], got[1][0]) and np.array_equal(got[0][1], got[1][1]) and got[0][2] == got[1][2]
     assert np.isfinite(got[0][0]).all() and len(got[0][2]) == 2
 

@@ -181,7 +181,7 @@ class _HostEngine:
 
     def __init__(self, H, W):
         self.cfg = SimpleNamespace(H=H, W=W)
-        self.calls = []
+        self.calls, self._pad_bufs = [], {}
 
     def pad(self, x, Hp, Wp, top, left, mode, value=0, out=None):
         from oct_image_segmentation_models_amd.common.utils import pad_reference

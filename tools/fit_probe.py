@@ -52,9 +52,10 @@ def timed(obj, name, key):
     def w(*a, **k):
         t = time.perf_counter(); r = f(*a, **k); acc[key] += time.perf_counter() - t; return r
     setattr(obj, name, w)
-timed(model, "_host_batch", "host_batch"); timed(model, "_upload", "upload"); timed(model, "_release", "release")
+feed = model.feed
+timed(feed, "host_batch", "host_batch"); timed(feed, "upload", "upload"); timed(feed, "release", "release")
 eng = model._engine
-timed(eng, "forward", "forward"); timed(eng, "loss_dice", "loss")
+timed(eng, "forward", "forward"); timed(eng, "select_loss", "select_loss"); timed(eng, "loss_selected", "loss")
 timed(model.optimizer, "apply", "adam")
 import oct_image_segmentation_models_amd.parallel as par
 orig = par.GradReducer.backward_and_reduce

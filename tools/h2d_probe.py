@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Runs on the GPU box: H2D copy rate of a pinned 4 MB uint8 buffer on a side stream, as Model._upload issues it --
+"""Runs on the GPU box: H2D copy rate of a pinned 4 MB uint8 buffer on a side stream, as BatchFeed.upload issues it --
 alone, and while a stream of kernels keeps the GPU busy on the default stream."""
 import time
 import numpy as np
