@@ -347,6 +347,19 @@ size_t oct_surface_workspace_bytes(int B, int H, int W, int n_cls);
 int oct_surface_distances(const unsigned char* pred_dev, const unsigned char* gt_dev, int B, int H, int W, int n_cls,
                           double spacing_row, double spacing_col, double percent,
                           void* workspace_dev, size_t workspace_bytes, double* out_dev, oct_stream_t stream);
+/* oct_surface_distances_masked: the same metrics on partially labelled ground truth (host
+ * restatement: common/custom_metrics.py::compute_surface_distances(..., valid=)).  A ground-truth pixel equal to
+ * ignore_label (a value in n_cls..255) is unknown: a 2x2 cell is a border element only if none of its in-image pixels is
+ * unknown, in the ground-truth mask and in the prediction mask alike (the validity comes from gt_dev for both; the zero
+ * padding outside the image is known background).  Surfaces are those seen entirely inside the labelled region; the rim
+ * of an unknown region is never one.  Only the column pass differs: workspace, output rows, distances, lengths, the
+ * percentile and the NaN / +inf / 0 of an empty element set are those of oct_surface_distances, and with no pixel equal
+ * to ignore_label the rows are equal bit for bit.  Rejected as there; the label check passes ignore_label in gt_dev only
+ * (any other value >= n_cls there, and every value >= n_cls in pred_dev, is an error), and ignore_label outside
+ * n_cls..255 is an argument error. */
+int oct_surface_distances_masked(const unsigned char* pred_dev, const unsigned char* gt_dev, int B, int H, int W, int n_cls,
+                                 int ignore_label, double spacing_row, double spacing_col, double percent,
+                                 void* workspace_dev, size_t workspace_bytes, double* out_dev, oct_stream_t stream);
 
 /* ---- training augmentations on device: (B,H,W,C) u8 images -> f32 in [0,1], flipped or with noise added; (B,H,W) u8 labels
  * flipped alongside (reference common/data_generator.py:140-283 chooses an augmentation per sample, common/augmentation.py:
@@ -489,12 +502,19 @@ int oct_minpath_device(const unsigned char* maps_dev, int B, int M, int H, int W
  * in the row.  The call overwrites counts_dev (zeroing is part of it).  1 <= B <= 65535, H*W < 2^32, 2 <= n_cls <= 32.
  * Every Dice metric of the evaluation is a function of one row (dice_from_counts).
  *
+ * oct_confusion_counts_masked: the same for partially labelled ground truth, rows of n_cls*n_cls + 2 words.  A pixel with
+ * gt == ignore_label (a value in n_cls..255) is counted in word n_cls*n_cls + 1 and nowhere else, whatever its prediction;
+ * words 0..n_cls*n_cls-1 are the confusion matrix of the other pixels and word n_cls*n_cls counts those of them where
+ * either label is >= n_cls.  Limits as above; ignore_label outside n_cls..255 is an argument error.
+ *
  * oct_area_labels: the class map, in the (H,W) frame, that graph-search delineations enclose -- exactly
  * common/utils.py::labels_from_delineations.  Per column, with M = n_cls - 1 and s_i = segs[b][i][col]: going up in i,
  * s_i == 0 becomes the first non-zero s_j with j > i, or H; row r then gets M if r >= s_{M-1}, else the largest k in
  * 1..M-1 with s_{k-1} <= r < s_k, else 0.  Boundaries may cross; values >= H reach no row.  H <= 65535, else as above. */
 int oct_confusion_counts(const unsigned char* pred_dev, const unsigned char* gt_dev, int B, int H, int W, int n_cls,
                          unsigned int* counts_dev /* (B, n_cls*n_cls + 1) */, oct_stream_t stream);
+int oct_confusion_counts_masked(const unsigned char* pred_dev, const unsigned char* gt_dev, int B, int H, int W, int n_cls,
+                                int ignore_label, unsigned int* counts_dev /* (B, n_cls*n_cls + 2) */, oct_stream_t stream);
 int oct_area_labels(const unsigned short* segs_dev /* (B, n_cls-1, W) */, int B, int H, int W, int n_cls,
                     unsigned char* labels_dev /* (B, H, W) */, oct_stream_t stream);
 

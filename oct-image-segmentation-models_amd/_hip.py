@@ -126,6 +126,8 @@ SYMBOLS = [
     ("oct_surface_workspace_bytes", C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     ("oct_surface_distances", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
                                         C.c_double, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    ("oct_surface_distances_masked", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
+                                               C.c_double, C.c_double, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     ("oct_augment_batch", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_ulonglong,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
     ("oct_warp_batch", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
@@ -138,7 +140,9 @@ SYMBOLS = [
     ("oct_minpath_device", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("oct_confusion_counts", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
-    ("oct_area_labels", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    ("oct_confusion_counts_masked", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                              C.c_void_p]),
+    ("oct_area_labels", C.c_int,[C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     ("oct_render_rgba", C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, _P(RenderStyle), C.c_int, C.c_int, C.c_int,
                                   C.c_void_p, C.c_void_p]),
     ("oct_set_option", C.c_int, [C.c_char_p, C.c_int]),

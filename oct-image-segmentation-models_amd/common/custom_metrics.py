@@ -125,15 +125,32 @@ def _directed_distances(qi: np.ndarray, qj: np.ndarray, target_border: np.ndarra
     return np.sqrt(best)
 
 
-def compute_surface_distances(mask_gt: np.ndarray, mask_pred: np.ndarray, spacing) -> dict:
+def _known_cells(valid: np.ndarray) -> np.ndarray:
+    """(H, W) validity of the pixels -> (H+1, W+1) bool: the cells none of whose in-image pixels is invalid (the zero
+    padding outside the image is known background)."""
+    u = np.pad(~np.asarray(valid, bool), 1)
+    return ~(u[:-1, :-1] | u[:-1, 1:] | u[1:, :-1] | u[1:, 1:])
+
+
+def compute_surface_distances(mask_gt: np.ndarray, mask_pred: np.ndarray, spacing, valid=None) -> dict:
     """Surfels of both masks with their distance to the other surface and contour length, sorted by
     (distance, length) as the package sorts them (``sorted(zip(...))``).  Besides the package's four keys the result
-    holds ``surfel_kinds_gt`` / ``surfel_kinds_pred`` (0: d, 1: h, 2: v, 3: 2d) for the exact percentile."""
+    holds ``surfel_kinds_gt`` / ``surfel_kinds_pred`` (0: d, 1: h, 2: v, 3: 2d) for the exact percentile.
+
+    ``valid`` (extension, ``oct_surface_distances_masked``): an (H, W) bool array, False where the ground truth is unknown.
+    A cell is then a surfel only if none of its in-image pixels is unknown, in both masks alike: surfaces are those seen
+    entirely inside the labelled region, and the rim of an unknown region is never one.  Everything else is unchanged."""
     mask_gt, mask_pred = np.asarray(mask_gt, bool), np.asarray(mask_pred, bool)
     if mask_gt.ndim != 2 or mask_gt.shape != mask_pred.shape:
         raise ValueError("compute_surface_distances: two 2D masks of one shape")
     lengths = _surfel_lengths(spacing)
     kg, kp = _cell_kinds(mask_gt), _cell_kinds(mask_pred)
+    if valid is not None:
+        valid = np.asarray(valid, bool)
+        if valid.shape != mask_gt.shape:
+            raise ValueError("compute_surface_distances: valid must have the masks' shape")
+        unknown = ~_known_cells(valid)
+        kg, kp = np.where(unknown, np.uint8(255), kg), np.where(unknown, np.uint8(255), kp)
     bg, bp = kg != 255, kp != 255
     out = {}
     for name, kinds, border, other in (("gt", kg, bg, bp), ("pred", kp, bp, bg)):

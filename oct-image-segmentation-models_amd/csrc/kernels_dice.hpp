@@ -12,6 +12,8 @@
 //                   The 16-byte loads start at the first 16-byte boundary of the image's pred map; the pixels before it
 //                   and after the last whole vector are read as bytes.  Where the two maps of an image sit at different
 //                   offsets from a 16-byte boundary, the whole image is read as bytes.
+//   confusion_masked_k  the same body with one more compare on the ground-truth byte: gt == ignore_label goes to a word
+//                   of its own, n_cls^2 + 1 (rows of n_cls^2 + 2 words), and to no other.
 //   area_labels_k   grid (ceil(W / 256), ceil(H / 32), B), 256 threads: a tile of 256 columns x 32 rows.  The block
 //                   stages the tile's boundaries into LDS after the zero replacement (going up in i, s_i == 0 becomes the
 //                   first non-zero s_j, j > i, or H); a thread then labels 4 adjacent columns of 8 rows,
@@ -30,14 +32,15 @@ constexpr int kAreaTileW = 256;       // columns of an area_labels_k tile: 64 la
 constexpr int kAreaRowsPerThread = 8;
 constexpr int kAreaTileH = (kDiceThreads / 64) * kAreaRowsPerThread;
 
-// npix = H * W < 2^32; counts rows of n_cls^2 + 1 words, zeroed by the caller
-__global__ void __launch_bounds__(kDiceThreads) confusion_k(const unsigned char* __restrict__ pred,
-                                                            const unsigned char* __restrict__ gt, size_t npix, int n_cls,
-                                                            unsigned int* __restrict__ counts) {
-    __shared__ unsigned int s_cnt[kDiceMaxClasses * kDiceMaxClasses + 1];
+// npix = H * W < 2^32; counts rows of n_cls^2 + 1 words (kMasked: + 2), zeroed by the caller.  kMasked: a pixel with
+// gt == ignore (a value in n_cls..255) goes to word n_cls^2 + 1 and nowhere else, whatever its prediction.
+template <bool kMasked>
+__device__ __forceinline__ void confusion_body(const unsigned char* __restrict__ pred, const unsigned char* __restrict__ gt,
+                                               size_t npix, int n_cls, unsigned ignore, unsigned int* __restrict__ counts) {
+    __shared__ unsigned int s_cnt[kDiceMaxClasses * kDiceMaxClasses + (kMasked ? 2 : 1)];
     const int tid = threadIdx.x;
     const unsigned bad = (unsigned)(n_cls * n_cls);
-    const int nk = (int)bad + 1;
+    const int nk = (int)bad + (kMasked ? 2 : 1);
     for (int k = tid; k < nk; k += kDiceThreads) s_cnt[k] = 0u;
     __syncthreads();
     const size_t b = blockIdx.y;
@@ -51,7 +54,8 @@ __global__ void __launch_bounds__(kDiceThreads) confusion_k(const unsigned char*
     }
     unsigned cur = bad, run = 0;      // the open run of this thread
     auto add = [&](unsigned pv, unsigned gv) {
-        const unsigned key = (pv < (unsigned)n_cls && gv < (unsigned)n_cls) ? gv * (unsigned)n_cls + pv : bad;
+        unsigned key = (pv < (unsigned)n_cls && gv < (unsigned)n_cls) ? gv * (unsigned)n_cls + pv : bad;
+        if (kMasked && gv == ignore) key = bad + 1u;
         if (key == cur) {
             ++run;
         } else {
@@ -85,6 +89,19 @@ __global__ void __launch_bounds__(kDiceThreads) confusion_k(const unsigned char*
         const unsigned int v = s_cnt[k];
         if (v) atomicAdd(&row[k], v);
     }
+}
+
+__global__ void __launch_bounds__(kDiceThreads) confusion_k(const unsigned char* __restrict__ pred,
+                                                            const unsigned char* __restrict__ gt, size_t npix, int n_cls,
+                                                            unsigned int* __restrict__ counts) {
+    confusion_body<false>(pred, gt, npix, n_cls, 0u, counts);
+}
+
+__global__ void __launch_bounds__(kDiceThreads) confusion_masked_k(const unsigned char* __restrict__ pred,
+                                                                   const unsigned char* __restrict__ gt, size_t npix,
+                                                                   int n_cls, unsigned ignore,
+                                                                   unsigned int* __restrict__ counts) {
+    confusion_body<true>(pred, gt, npix, n_cls, ignore, counts);
 }
 
 // segs (B, M, W) uint16, labels (B, H, W) uint8; M = n_cls - 1 in 1..31, H <= 65535

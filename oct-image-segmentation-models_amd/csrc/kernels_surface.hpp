@@ -9,7 +9,8 @@
 //   contour length by kind: d = sqrt(v^2+h^2)/2 (one corner in or out), h (horizontal edge), v (vertical edge), 2d (saddle).
 // Three launches, no device allocation:
 //   surf_col_k     one thread per (b, c, m, cell column): cell kinds + nearest border row above/below in the column
-//                  (uint16 row distance, 0xFFFF = none in that column); also flags labels >= n_cls.
+//                  (uint16 row distance, 0xFFFF = none in that column); also flags labels >= n_cls.  Its masked
+//                  instantiation (an ignore label in the ground truth) drops the cells that touch an ignored pixel.
 //   surf_row_k     one block per (b, c, m, cell row): for each border cell of m, the exact nearest border cell of the other
 //                  mask -- min over columns of (v*dy)^2 + (h*dx)^2, searched outward from the cell's column and stopped once
 //                  (h*dx)^2 alone reaches the best so far (O(dx of the nearest) per cell, O(W) at worst).  fp64 with FMA
@@ -47,9 +48,13 @@ __device__ inline unsigned char surf_kind(int code) {
 }
 
 // plane index of (b, c, m): ((b * (n_cls-1) + c-1) * 2 + m)
+// kMasked (oct_surface_distances_masked): a ground-truth pixel equal to `ignore` (a value in n_cls..255) is unknown.  A
+// cell with such a pixel among its in-image pixels is no border cell, in the gt plane and in the pred plane alike -- the
+// pred planes read the ground-truth bytes beside their own -- and the label check passes that value in the ground truth.
+template <bool kMasked>
 __global__ void __launch_bounds__(256) surf_col_k(const unsigned char* __restrict__ gt, const unsigned char* __restrict__ pred,
-                                                  SurfGeom g, unsigned char* __restrict__ kind, unsigned short* __restrict__ dy,
-                                                  unsigned int* __restrict__ bad) {
+                                                  SurfGeom g, int ignore, unsigned char* __restrict__ kind,
+                                                  unsigned short* __restrict__ dy, unsigned int* __restrict__ bad) {
     const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int nc = g.n_cls - 1;
     if (t >= (size_t)g.B * nc * 2 * g.Wc) return;
@@ -65,22 +70,33 @@ __global__ void __launch_bounds__(256) surf_col_k(const unsigned char* __restric
     unsigned int badv = 0;
     // forward: kinds, distance to the nearest border row at or above
     int tl = 0, tr = 0, last = -1;
+    int ti = 0;                               // kMasked: a pixel of the row above, left or right, is ignored
+    const unsigned char* gtb = gt + (size_t)b * g.H * g.W;
     constexpr int U = 8;
     for (int i0 = 0; i0 < g.Hc; i0 += U) {
-        unsigned char l[U], r[U];
+        unsigned char l[U], r[U], gl[U], gr[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int i = i0 + u;
             l[u] = (i < g.H && j >= 1) ? lab[(size_t)i * g.W + j - 1] : 0;
             r[u] = (i < g.H && j < g.W) ? lab[(size_t)i * g.W + j] : 0;
+            if (kMasked) {                    // the ground-truth bytes: the plane's own for m == 0 (the padding is 0: known)
+                gl[u] = m == 0 ? l[u] : (i < g.H && j >= 1) ? gtb[(size_t)i * g.W + j - 1] : 0;
+                gr[u] = m == 0 ? r[u] : (i < g.H && j < g.W) ? gtb[(size_t)i * g.W + j] : 0;
+            }
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int i = i0 + u;
             if (i >= g.Hc) break;
-            if (check && i < g.H && r[u] >= g.n_cls) badv = 1;
+            if (check && i < g.H && r[u] >= g.n_cls && !(kMasked && m == 0 && r[u] == ignore)) badv = 1;
             const int bl = l[u] == c, br = r[u] == c;
-            const unsigned char k = surf_kind(8 * tl + 4 * tr + 2 * bl + br);
+            unsigned char k = surf_kind(8 * tl + 4 * tr + 2 * bl + br);
+            if (kMasked) {
+                const int bi = (gl[u] == ignore) | (gr[u] == ignore);
+                if (ti | bi) k = kSurfNotBorder;
+                ti = bi;
+            }
             kp[(size_t)i * g.Wc] = k;
             if (k != kSurfNotBorder) last = i;
             dp[(size_t)i * g.Wc] = last < 0 ? kSurfNone : (unsigned short)(i - last);

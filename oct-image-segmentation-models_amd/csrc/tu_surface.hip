@@ -1,5 +1,6 @@
 // One translation unit of liboct_unet_hip.so (see host.hpp): surface-distance metrics of class maps
-// (kernels_surface.hpp) and their C ABI, oct_surface_workspace_bytes / oct_surface_distances (include/oct_unet.h).
+// (kernels_surface.hpp) and their C ABI, oct_surface_workspace_bytes / oct_surface_distances /
+// oct_surface_distances_masked (include/oct_unet.h).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -42,9 +43,11 @@ size_t oct_surface_workspace_bytes(int B, int H, int W, int n_cls) {
     return geom(B, H, W, n_cls, &g) ? layout(g).total : 0;
 }
 
-int oct_surface_distances(const unsigned char* pred, const unsigned char* gt, int B, int H, int W, int n_cls,
-                          double spacing_row, double spacing_col, double percent, void* workspace, size_t workspace_bytes,
-                          double* out, oct_stream_t stream) {
+namespace {
+// ignore_label < 0: oct_surface_distances; else the masked column pass in front of the same row and select passes
+int surface_distances(const unsigned char* pred, const unsigned char* gt, int B, int H, int W, int n_cls, int ignore_label,
+                      double spacing_row, double spacing_col, double percent, void* workspace, size_t workspace_bytes,
+                      double* out, oct_stream_t stream) {
     SurfGeom g;
     if (!pred || !gt || !workspace || !out) return fail(-1, "surface_distances: null pointer");
     if (!geom(B, H, W, n_cls, &g))
@@ -67,13 +70,18 @@ int oct_surface_distances(const unsigned char* pred, const unsigned char* gt, in
 
     HIP_OK(hipMemsetAsync(bad, 0, sizeof(unsigned int), st));
     const size_t ncol = (size_t)planes * g.Wc;
-    surf_col_k<<<(unsigned)((ncol + 255) / 256), 256, 0, st>>>(gt, pred, g, kind, dy, bad);
+    if (ignore_label >= 0)
+        surf_col_k<true><<<(unsigned)((ncol + 255) / 256), 256, 0, st>>>(gt, pred, g, ignore_label, kind, dy, bad);
+    else
+        surf_col_k<false><<<(unsigned)((ncol + 255) / 256), 256, 0, st>>>(gt, pred, g, -1, kind, dy, bad);
     HIP_OK(hipGetLastError());
     // labels >= n_cls are an argument error: the column pass flags them and the call reports it before the distance passes
     unsigned int flag = 0;
     HIP_OK(hipMemcpyAsync(&flag, bad, sizeof(flag), hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
-    if (flag) return fail(-2, "surface_distances: a label is >= n_cls=" + std::to_string(n_cls));
+    if (flag)
+        return fail(-2, "surface_distances: a label is >= n_cls=" + std::to_string(n_cls) +
+                        (ignore_label >= 0 ? " and not the ignore label " + std::to_string(ignore_label) : std::string()));
 
     surf_row_k<<<dim3((unsigned)g.Hc, planes), 256, (size_t)g.Wc * sizeof(unsigned short), st>>>(g, kind, dy, dist,
                                                                                                 spacing_row, spacing_col);
@@ -87,4 +95,21 @@ int oct_surface_distances(const unsigned char* pred, const unsigned char* gt, in
     surf_select_k<<<planes, kSurfSelectThreads, 0, st>>>(g, kind, dist, ld, lh, lv, l2, percent / 100.0, out);
     HIP_OK(hipGetLastError());
     return 0;
+}
+}  // namespace
+
+int oct_surface_distances(const unsigned char* pred, const unsigned char* gt, int B, int H, int W, int n_cls,
+                          double spacing_row, double spacing_col, double percent, void* workspace, size_t workspace_bytes,
+                          double* out, oct_stream_t stream) {
+    return surface_distances(pred, gt, B, H, W, n_cls, -1, spacing_row, spacing_col, percent, workspace, workspace_bytes, out,
+                             stream);
+}
+
+int oct_surface_distances_masked(const unsigned char* pred, const unsigned char* gt, int B, int H, int W, int n_cls,
+                                 int ignore_label, double spacing_row, double spacing_col, double percent, void* workspace,
+                                 size_t workspace_bytes, double* out, oct_stream_t stream) {
+    if (ignore_label < n_cls || ignore_label < 0 || ignore_label > 255)
+        return fail(-1, "surface_distances_masked: ignore_label must lie in n_cls..255");
+    return surface_distances(pred, gt, B, H, W, n_cls, ignore_label, spacing_row, spacing_col, percent, workspace,
+                             workspace_bytes, out, stream);
 }

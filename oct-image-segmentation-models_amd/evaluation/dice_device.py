@@ -25,15 +25,36 @@ MAX_CLASSES = 32
 MAX_EXACT_PIXELS = 1 << 23
 
 
-def confusion_counts_reference(pred: np.ndarray, gt: np.ndarray, num_classes: int) -> np.ndarray:
+def check_ignore_label(ignore_label, num_classes: int) -> Optional[int]:
+    """The public ``ignore_label`` of the evaluation, validated: None, or an int in ``num_classes..255`` (a ground-truth
+    value that is no class).  Anything else is a ``ValueError``."""
+    if ignore_label is None:
+        return None
+    if isinstance(ignore_label, (bool, np.bool_)) or not isinstance(ignore_label, (int, np.integer)) \
+            or not int(num_classes) <= int(ignore_label) <= 255:
+        raise ValueError(f"ignore_label must be None or an int in {int(num_classes)}..255, not {ignore_label!r}")
+    return int(ignore_label)
+
+
+def confusion_counts_reference(pred: np.ndarray, gt: np.ndarray, num_classes: int,
+                               ignore_label: Optional[int] = None) -> np.ndarray:
     """(n,H,W) class maps -> (n, C*C + 1) uint32: word ``g*C + p`` counts the pixels with gt == g and pred == p, the last
-    word those where either label is >= C (they appear nowhere else in the row)."""
+    word those where either label is >= C (they appear nowhere else in the row).
+
+    With ``ignore_label`` (``oct_confusion_counts_masked``) the rows have C*C + 2 words: a pixel with gt == ignore_label is
+    counted in word C*C + 1 and nowhere else, whatever its prediction; the words before it are as above, over the other
+    (the counted) pixels."""
     pred, gt, Cc = np.asarray(pred).astype(np.int64), np.asarray(gt).astype(np.int64), int(num_classes)
     if pred.shape != gt.shape or pred.ndim != 3:
         raise ValueError("pred and gt must be (n,H,W) class maps of one shape")
+    ignore_label = check_ignore_label(ignore_label, Cc)
     bad = (pred < 0) | (pred >= Cc) | (gt < 0) | (gt >= Cc)
-    key = np.where(bad, Cc * Cc, gt * Cc + pred).reshape(pred.shape[0], -1)
-    return np.stack([np.bincount(k, minlength=Cc * Cc + 1) for k in key]).astype(np.uint32)
+    key = np.where(bad, Cc * Cc, gt * Cc + pred)
+    nk = Cc * Cc + 1
+    if ignore_label is not None:
+        key, nk = np.where(gt == ignore_label, Cc * Cc + 1, key), Cc * Cc + 2
+    key = key.reshape(pred.shape[0], -1)
+    return np.stack([np.bincount(k, minlength=nk) for k in key]).astype(np.uint32)
 
 
 def area_labels_reference(segs: np.ndarray, H: int, W: int) -> np.ndarray:
@@ -59,10 +80,13 @@ def area_labels_reference(segs: np.ndarray, H: int, W: int) -> np.ndarray:
     return lab[0] if single else lab
 
 
-def counts_matrix(rows: np.ndarray, num_classes: int, first_image: int = 0) -> np.ndarray:
-    """(n, C*C + 1) rows of the device -> (n, C, C) uint32; a non-zero out-of-range word raises with the image index."""
+def counts_matrix(rows: np.ndarray, num_classes: int, first_image: int = 0, ignored: bool = False) -> np.ndarray:
+    """(n, C*C + 1) rows of the device -> (n, C, C) uint32; a non-zero out-of-range word raises with the image index.
+    ``ignored``: the rows are the masked kernel's, C*C + 2 words; the count of ignored pixels is dropped."""
     rows = np.asarray(rows).view(np.uint32) if np.asarray(rows).dtype == np.int32 else np.asarray(rows, np.uint32)
     Cc = int(num_classes)
+    if rows.ndim != 2 or rows.shape[1] != Cc * Cc + (2 if ignored else 1):
+        raise ValueError(f"rows of {Cc * Cc + (2 if ignored else 1)} words expected, not an array of shape {rows.shape}")
     bad = np.nonzero(rows[:, Cc * Cc])[0]
     if bad.size:
         i = int(bad[0])
@@ -95,27 +119,34 @@ def dice_from_counts(counts: np.ndarray, metrics) -> Tuple[Optional[np.ndarray],
 
 class ConfusionCounts:
     """``oct_confusion_counts`` for up to ``batch`` images of one shape: ``(pred, gt)`` -> (n, C*C + 1) int32 rows on the
-    device (the bits are the uint32 counts), queued on the current stream."""
+    device (the bits are the uint32 counts), queued on the current stream.  With ``ignore_label`` it is
+    ``oct_confusion_counts_masked``: rows of C*C + 2 words, ground-truth pixels of that value counted in the last alone."""
 
-    def __init__(self, batch: int, H: int, W: int, num_classes: int, device):
+    def __init__(self, batch: int, H: int, W: int, num_classes: int, device, ignore_label: Optional[int] = None):
         self.B, self.H, self.W, self.C = int(batch), int(H), int(W), int(num_classes)
+        self.ignore_label = check_ignore_label(ignore_label, self.C)
         if not (1 <= self.B <= 65535 and self.H >= 1 and self.W >= 1 and self.H * self.W < 1 << 32
                 and 2 <= self.C <= MAX_CLASSES):
             raise _hip.OctError(f"oct_confusion_counts does not support B={batch}, {H}x{W}, {num_classes} classes")
         self.device = torch.device(device)
-        self.out = torch.empty((self.B, self.C * self.C + 1), dtype=torch.int32, device=self.device)
+        self.out = torch.empty((self.B, self.C * self.C + (1 if self.ignore_label is None else 2)), dtype=torch.int32,
+                               device=self.device)
         self.outs, self.geometry = (self.out,), (self.B, self.H, self.W, self.C)
 
     def __call__(self, pred: torch.Tensor, gt: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         n = _hip.expect_map_pair(pred, gt, device=self.device, batch=self.B, H=self.H, W=self.W)
         out = _hip.out_view(out, self.out, n)
-        _hip.call("oct_confusion_counts", self.device, pred.data_ptr(), gt.data_ptr(), n, self.H, self.W, self.C,
-                  out.data_ptr(), _hip.stream_ptr(self.device))
+        if self.ignore_label is None:
+            _hip.call("oct_confusion_counts", self.device, pred.data_ptr(), gt.data_ptr(), n, self.H, self.W, self.C,
+                      out.data_ptr(), _hip.stream_ptr(self.device))
+        else:
+            _hip.call("oct_confusion_counts_masked", self.device, pred.data_ptr(), gt.data_ptr(), n, self.H, self.W, self.C,
+                      self.ignore_label, out.data_ptr(), _hip.stream_ptr(self.device))
         return out
 
     def to_host(self, rows: torch.Tensor, first_image: int = 0) -> np.ndarray:
         """Device rows -> (n, C, C) uint32 on the host (waits for the stream); out-of-range labels raise."""
-        return counts_matrix(rows.cpu().numpy(), self.C, first_image)
+        return counts_matrix(rows.cpu().numpy(), self.C, first_image, ignored=self.ignore_label is not None)
 
 
 class AreaLabels:
@@ -145,11 +176,11 @@ class DelineationLabels:
     """The stage behind ``InferenceRun.gs_labels``: a batch's final delineations (n, C-1, W) uint16 on the host -> the
     class maps they enclose, (n,H,W) uint8 on the host, and with the batch's ground-truth class maps (n,H,W) the
     (n, C, C) uint32 confusion counts of those maps against it (else None).  It owns its device buffers and uploads
-    both inputs itself; the call waits for the device."""
+    both inputs itself; the call waits for the device.  ``ignore_label``: as ``ConfusionCounts``."""
 
-    def __init__(self, batch: int, H: int, W: int, num_classes: int, device):
+    def __init__(self, batch: int, H: int, W: int, num_classes: int, device, ignore_label: Optional[int] = None):
         self.area = AreaLabels(batch, H, W, num_classes, device)
-        self.counts = ConfusionCounts(batch, H, W, num_classes, device)
+        self.counts = ConfusionCounts(batch, H, W, num_classes, device, ignore_label=ignore_label)
 
     def __call__(self, segs: np.ndarray, gt: Optional[np.ndarray] = None,
                  first_image: int = 0) -> Tuple[np.ndarray, Optional[np.ndarray]]:

@@ -11,7 +11,9 @@ graph-search class maps from ``oct_area_labels`` (``evaluation/dice_device.py``)
 set is sharded by contiguous index range (no collective); rank 0 aggregates.  With ``EvaluationParameters(png_plots=True)``
 the reference's PNG pictures of every image are rasterised on the device (``oct_render_rgba``, ``evaluation/render.py``) and
 written by ``common/png.py``; each rank writes those of its own shard.  ``performance_plot.png`` and
-``categorical_pred_N.png`` are out of scope."""
+``categorical_pred_N.png`` are out of scope.  With ``EvaluationParameters(ignore_label=...)`` ground-truth pixels of that value
+are unknown: out of every Dice count, no surface element at their rim, no truth boundary under them, mid-grey in the
+ground-truth pictures; without it the value is refused and every file is what it was."""
 from __future__ import annotations
 
 import logging as log
@@ -94,6 +96,15 @@ def _batch_dice(metrics, num_classes, batch, k, label_onehot_hw, categorical_pre
     return _dice_metrics(metrics, num_classes, label_onehot_hw, categorical_pred)
 
 
+def _masked_onehot(labels_hw, num_classes, ignore_label):
+    """(H,W) ground-truth labels with ``ignore_label`` -> the one-hot truth (H,W,C) float32 with an all-zero vector at the
+    ignored pixels, and ``keep`` (H,W) bool, the counted pixels (``masked_loss_reference`` forms the same pair)."""
+    keep = labels_hw != ignore_label
+    onehot = common_utils.to_categorical(np.where(keep, labels_hw, 0), num_classes)
+    onehot[~keep] = 0.0
+    return onehot, keep
+
+
 def _surface_metrics(metrics, rows):
     """Per-image surface-distance datasets (evaluation.py:207-262) from one (C-1, 6) row block of the device, restricted
     to the metrics asked for."""
@@ -122,8 +133,18 @@ def evaluate_model(eval_params: EvaluationParameters) -> List[EvaluationOutput]:
         eval_image_names = [Path(f"image_{i}") for i in range(n_images)]
     eval_image_output_dirs = [eval_params.save_foldername / Path(f"image_{i}") for i in range(n_images)]
 
-    eval_segments = np.swapaxes(utils.generate_boundary(np.squeeze(eval_labels, axis=3), axis=1), 0, 1)
     num_classes = eval_params.num_classes
+    # ignore_label: ground-truth pixels of that value are unknown; None is the reference's workflow
+    ignore_label = getattr(eval_params, "ignore_label", None)
+    if ignore_label is None:
+        eval_segments = np.swapaxes(utils.generate_boundary(np.squeeze(eval_labels, axis=3), axis=1), 0, 1)
+    else:
+        label_maps = np.squeeze(eval_labels, axis=3)
+        bad = np.nonzero(((label_maps < 0) | (label_maps >= num_classes)) & (label_maps != ignore_label))[0]
+        if bad.size:
+            raise ValueError(f"image {int(bad[0])}: ground-truth labels outside 0..{num_classes - 1} that are not the ignore "
+                             f"label {ignore_label}")
+        eval_segments = np.swapaxes(utils.generate_boundary_masked(label_maps, num_classes, ignore_label, axis=1), 0, 1)
     if rank == 0:
         os.makedirs(eval_params.save_foldername, exist_ok=True)
         save_eval_config_file(eval_params)
@@ -159,7 +180,8 @@ def evaluate_model(eval_params: EvaluationParameters) -> List[EvaluationOutput]:
                       graph_search=eval_params.graph_search, gsgrad=eval_params.gsgrad, gs_device=eval_params.gs_device,
                       gs_device_ties=eval_params.gs_device_ties, gs_workers=eval_params.gs_workers,
                       soft_maps=not getattr(eval_params, "binarize", True),
-                      pad_mode=getattr(eval_params, "pad_mode", None), pad_value=getattr(eval_params, "pad_value", 0)) as run:
+                      pad_mode=getattr(eval_params, "pad_mode", None), pad_value=getattr(eval_params, "pad_value", 0),
+                      ignore_label=ignore_label) as run:
         t_prev = time.time()
         for batch in run:
             b0, b1 = lo + batch.lo, lo + batch.hi
@@ -174,18 +196,25 @@ def evaluate_model(eval_params: EvaluationParameters) -> List[EvaluationOutput]:
             if png_plots:
                 pictures = run.render_pngs(batch, eval_images[b0:b1], gs_found, gt=np.squeeze(eval_labels[b0:b1], axis=3),
                                            truths=eval_segments[b0:b1], gs_labels=gs_labels,
-                                           pred_map=eval_params.save_params.predicted_labels is True)
+                                           pred_map=eval_params.save_params.predicted_labels is True,
+                                           ignore_label=ignore_label)
             for ind in range(b0, b1):
                 eval_image, eval_image_name = eval_images[ind], eval_image_names[ind]
                 eval_seg, eval_image_output_dir = eval_segments[ind], eval_image_output_dirs[ind]
-                eval_label = common_utils.to_categorical(eval_labels[ind], num_classes)        # (H,W,C)
+                keep = raw_label = None
+                if ignore_label is None:
+                    eval_label = common_utils.to_categorical(eval_labels[ind], num_classes)        # (H,W,C)
+                else:                                                     # zero one-hot vectors at the ignored pixels
+                    raw_label = np.squeeze(eval_labels[ind], axis=2)
+                    eval_label, keep = _masked_onehot(raw_label, num_classes, ignore_label)
                 os.makedirs(eval_image_output_dir, exist_ok=True)
                 predicted_labels = batch.labels[ind - b0:ind - b0 + 1].astype(np.int64)        # (1,H,W)
                 categorical_pred = common_utils.labels_to_categorical(predicted_labels, num_classes)
                 # on device: == convert_predictions_to_maps_semantic(categorical_pred); with binarize=False, of the probabilities
                 boundary_maps = batch.maps[ind - b0:ind - b0 + 1]
                 dice_classes, dice_macro, dice_micro = _batch_dice(eval_params.metrics, num_classes, batch, ind - b0,
-                                                                   eval_label, categorical_pred)
+                                                                   eval_label, categorical_pred if keep is None
+                                                                   else categorical_pred * keep.astype(np.float32))
                 surface_ds = _surface_metrics(eval_params.metrics, None if batch.surface is None else batch.surface[ind - b0])
 
                 predicted_labels = np.squeeze(predicted_labels, axis=0)
@@ -193,7 +222,7 @@ def evaluate_model(eval_params: EvaluationParameters) -> List[EvaluationOutput]:
                 boundary_maps = np.squeeze(boundary_maps, axis=0)
                 _save_image_evaluation_results(eval_params, eval_image, eval_image_name, predicted_labels, categorical_pred,
                                                eval_label, eval_seg, dice_classes, dice_macro, dice_micro, predict_time,
-                                               eval_image_output_dir, surface_ds)
+                                               eval_image_output_dir, surface_ds, raw_label)
 
                 gs_pred_segs = errors = mean_abs_err = mean_err = abs_err_sd = err_sd = None
                 if eval_params.graph_search:
@@ -208,6 +237,8 @@ def evaluate_model(eval_params: EvaluationParameters) -> List[EvaluationOutput]:
                     else:
                         gs_eval_label, reconstructed_maps = common_utils.labels_from_delineations(eval_image_t.shape,
                                                                                                  gs_pred_segs, num_classes)
+                        if keep is not None:                              # (1, C, W, H): the search's transposed frame
+                            reconstructed_maps = reconstructed_maps * np.transpose(keep).astype(np.float32)
                         gs_dc, gs_dm, gs_dmi = _dice_metrics(eval_params.metrics, num_classes, eval_label,
                                                              reconstructed_maps, transposed=True)
                         graph_time = time.time() - start_graph_time
@@ -232,7 +263,9 @@ def evaluate_model(eval_params: EvaluationParameters) -> List[EvaluationOutput]:
 
 def _save_image_evaluation_results(eval_params, eval_image, image_name, predicted_labels, categorical_pred, eval_labels,
                                    eval_segs, dice_classes, dice_macro, dice_micro, predict_time, output_dir,
-                                   surface_ds=None):
+                                   surface_ds=None, raw_labels=None):
+    """``raw_labels`` (H,W): the ground truth as given, where ``eval_labels`` is a one-hot array with ignored pixels zeroed
+    (``ignore_label``): the files store it, ignore value included."""
     with open(output_dir / "input_image_name.txt", "w") as f:
         f.write(str(image_name))
     np.savetxt(output_dir / Path("predicted_segmentation_map.csv"), predicted_labels, fmt="%d", delimiter=",")
@@ -242,7 +275,7 @@ def _save_image_evaluation_results(eval_params, eval_image, image_name, predicte
     if eval_params.save_params.predicted_labels is True:
         ds["predicted_segmentation_map"] = predicted_labels.astype("uint8")
     ds["raw_image"] = eval_image.astype("uint8")
-    eval_labels = np.argmax(eval_labels, axis=2)
+    eval_labels = np.argmax(eval_labels, axis=2) if raw_labels is None else raw_labels
     ds["eval_labels"] = eval_labels.astype("uint8")
     np.savetxt(output_dir / Path("ground_truth_segmentation_map.csv"), eval_labels, fmt="%d", delimiter=",")
     ds["raw_segs"] = eval_segs.astype("uint16")
@@ -292,6 +325,8 @@ def save_eval_config_file(eval_params: EvaluationParameters):
     if getattr(eval_params, "pad_mode", None) is not None:
         attrs["pad_mode"] = np.array(str(eval_params.pad_mode), dtype="S1000")      # likewise, with the constant
         attrs["pad_value"] = np.array(float(getattr(eval_params, "pad_value", 0)))
+    if getattr(eval_params, "ignore_label", None) is not None:
+        attrs["ignore_label"] = np.array(int(eval_params.ignore_label))      # likewise
     h5io.save(eval_params.save_foldername / Path("eval_params.hdf5"), {}, attrs)
 
 

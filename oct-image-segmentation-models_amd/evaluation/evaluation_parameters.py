@@ -8,6 +8,7 @@ from pathlib import Path
 from typing import List, Optional
 
 from ..common import EVALUATION_METRICS, utils
+from .dice_device import check_ignore_label
 
 
 class EvaluationSaveParams:
@@ -26,7 +27,7 @@ class EvaluationParameters:
                  graph_search: bool, metrics: List[str], gsgrad=1, dice_errors: bool = True, binarize: bool = True,
                  bg_ilm: bool = True, bg_csi: bool = False, batch_size: int = 32, gs_device: bool = False,
                  gs_device_ties: str = "host", gs_workers: Optional[int] = None, metrics_device: bool = False,
-                 png_plots: bool = False, pad_mode: Optional[str] = None, pad_value=0):
+                 png_plots: bool = False, pad_mode: Optional[str] = None, pad_value=0, ignore_label: Optional[int] = None):
         # extension: scans whose size is no multiple of 2^pool_layers (the reference raises on them) are padded on the
         # device in front of the forward -- "edge", "reflect" or "constant" with pad_value in raw counts -- and the arg-max
         # maps (with binarize=False the probabilities too) are cropped directly behind the head: metrics, searches, files
@@ -75,3 +76,9 @@ class EvaluationParameters:
         self.loaded_model, self.model_config = utils.load_model_and_config(
             self.model_path, mlflow_tracking_uri=mlflow_tracking_uri, mlflow_run_uuid=mlflow_run_uuid)
         self.num_classes = self.loaded_model.output.shape[-1]
+        # extension: the test set's labels are known in part only (annotated column ranges, masked optic-nerve heads): ground-truth
+        # pixels of this value, an int in num_classes..255, are "unknown" wherever a metric, a truth boundary or a ground-truth
+        # picture is formed -- out of the Dice counts, no surface element at their rim, no truth boundary underneath them,
+        # mid-grey in the pictures.  The predictions and everything made of them alone do not depend on
+        # it.  None: such values are refused, and no file changes
+        self.ignore_label = check_ignore_label(ignore_label, self.num_classes)

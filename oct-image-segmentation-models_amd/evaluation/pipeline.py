@@ -18,7 +18,7 @@ import torch
 from ..common.utils import check_pad_mode, padded_geometry
 from ..min_path_processing.device_search import DeviceMinPath, LazyPool, merge_ties
 from ..min_path_processing.pool import SegmentPool, default_workers
-from .dice_device import ConfusionCounts, DelineationLabels
+from .dice_device import ConfusionCounts, DelineationLabels, check_ignore_label
 from .render import PngRenderer, batch_pictures
 from .surface import SurfaceDistances
 
@@ -337,15 +337,20 @@ class InferenceRun:
     crops directly behind the head, and every stage, search and picture works at the true size.  For sizes that are
     multiples nothing changes and nothing more is launched.
 
+    ``ignore_label`` (None, or an int in num_classes..255) marks ground-truth pixels whose class is unknown: ``gt`` may then
+    hold that value, and it is handed to the ``surface`` and ``confusion`` stages and to ``gs_labels``, which run their
+    masked kernels.  Labels, maps, searches and pictures do not depend on it.
+
     ``batches`` replaces the model by a ready source of records (tests of the host side: no device is touched)."""
 
     def __init__(self, model, images: np.ndarray, batch: int, num_classes: int, *, gt: Optional[np.ndarray] = None,
                  graph_search: bool = False, gsgrad: int = 1, gs_device: bool = False, gs_device_ties: str = "host",
                  gs_workers: Optional[int] = None, batches: Optional[Iterable[Batch]] = None, surface: bool = True,
                  confusion: bool = False, soft_maps: bool = False, mc_samples: int = 0, mc_step0: int = 0,
-                 pad_mode: Optional[str] = None, pad_value=0):
+                 pad_mode: Optional[str] = None, pad_value=0, ignore_label: Optional[int] = None):
         pad_mode, pad_value = check_pad_mode(pad_mode, pad_value)
         n, (H, W), C = images.shape[0], images.shape[1:3], int(num_classes)
+        self.ignore_label = ignore_label = check_ignore_label(ignore_label, C)
         self.pool = self.host_ties = None
         self._gs = self._gs_geom = None                   # gs_labels' own device buffers: made by its first call
         self._png = None                                  # render_pngs' own device and pinned buffers, likewise
@@ -354,7 +359,12 @@ class InferenceRun:
             return
         gt_u8 = None
         if gt is not None:
-            if gt.min() < 0 or gt.max() >= C:
+            if ignore_label is not None:
+                bad = np.nonzero(((gt < 0) | (gt >= C)) & (gt != ignore_label))[0]
+                if bad.size:
+                    raise ValueError(f"image {int(bad[0])}: ground-truth labels outside 0..{C - 1} that are not the ignore "
+                                     f"label {ignore_label}")
+            elif gt.min() < 0 or gt.max() >= C:
                 raise ValueError(f"ground-truth labels outside 0..{C - 1}")
             gt_u8 = np.ascontiguousarray(gt.astype(np.uint8))
         if graph_search and gs_device:
@@ -368,8 +378,8 @@ class InferenceRun:
             geom, _ = model._geometry((H, W), pad_mode)      # refuses a size that is no multiple, before anything is built
             self._gs_geom = (bs, H, W, C, dev)
             minpath = DeviceMinPath(bs, C - 1, H, W, gsgrad, dev) if self.host_ties is not None else None
-            surface = SurfaceDistances(bs, H, W, C, dev) if gt_u8 is not None and surface else None
-            confusion = ConfusionCounts(bs, H, W, C, dev) if gt_u8 is not None and confusion else None
+            surface = SurfaceDistances(bs, H, W, C, dev, ignore_label=ignore_label) if gt_u8 is not None and surface else None
+            confusion = ConfusionCounts(bs, H, W, C, dev, ignore_label=ignore_label) if gt_u8 is not None and confusion else None
             if surface is None and confusion is None:
                 gt_u8 = None
             if images.dtype == np.uint8:
@@ -402,7 +412,7 @@ class InferenceRun:
 
     def _delineation_labels(self) -> DelineationLabels:
         if self._gs is None:
-            self._gs = DelineationLabels(*self._gs_geom)
+            self._gs = DelineationLabels(*self._gs_geom, ignore_label=self.ignore_label)
         return self._gs
 
     def gs_labels(self, batch: Batch, found: list, gt: Optional[np.ndarray] = None) -> Tuple[np.ndarray, Optional[np.ndarray]]:
@@ -420,7 +430,7 @@ class InferenceRun:
 
     def render_pngs(self, batch: Batch, images: np.ndarray, found: Optional[list] = None, *,
                     gt: Optional[np.ndarray] = None, truths: Optional[np.ndarray] = None, gs_labels: Optional[np.ndarray] = None,
-                    pred_map: bool = True, col_range=None) -> dict:
+                    pred_map: bool = True, col_range=None, ignore_label: Optional[int] = None) -> dict:
         """The PNG pictures of a batch as host RGBA arrays (n,H,W,4) uint8, rasterised on the device by
         ``oct_render_rgba`` (``evaluation.render.batch_pictures`` names the keys): ``raw`` of the batch's ``images``
         (n,H,W,ic), ``pred`` of the arg-max maps (unless ``pred_map`` is off), with the ground-truth class maps ``gt``
@@ -429,7 +439,8 @@ class InferenceRun:
         are given, ``gs_both``.  ``gs_labels`` are the class maps of the delineations where the caller has them
         (``gs_labels()``); otherwise ``oct_area_labels`` makes them here, on the device.  Everything is uploaded here,
         into buffers of this method -- the predictor's double buffers are recycled two batches ahead -- and nothing of
-        the batch is referenced once the call returns.  Waits for the device."""
+        the batch is referenced once the call returns.  With ``ignore_label`` the pixels of ``gt`` that carry it are
+        mid-grey in ``gt`` and under the truth overlays (``batch_pictures``).  Waits for the device."""
         if self._gs_geom is None:
             raise RuntimeError("render_pngs needs the device: this run was built over injected batches")
         bs, H, W, C, dev = self._gs_geom
@@ -445,7 +456,8 @@ class InferenceRun:
                 gs_labels = self._delineation_labels().area(torch.from_numpy(np.ascontiguousarray(gs_segs).view(np.int16)).to(dev))
         return batch_pictures(self._png, C, images, pred_labels=batch.labels if pred_map else None, gt_labels=gt,
                               truths=truths, gs_segs=gs_segs, gs_labels=gs_labels,
-                              both_overlay=truths is not None and gs_segs is not None, col_range=col_range)
+                              both_overlay=truths is not None and gs_segs is not None, col_range=col_range,
+                              ignore_label=ignore_label)
 
     def render_gray(self, gray_u8: np.ndarray) -> np.ndarray:
         """(n,H,W) uint8 -> (n,H,W,4) RGBA on the host: the values as a gray scan with no lines, through the renderer of

@@ -123,6 +123,9 @@ PREDICTION_PNG_NAMES = {"pred": "segmentation_map.png", "raw": "raw_image.png",
                         "uncertainty": "uncertainty_map.png"}        # (no counterpart in the reference: Monte-Carlo dropout)
 
 
+IGNORED_RGB = (128, 128, 128)     # ground-truth pixels that carry the evaluation's ignore_label
+
+
 def write_pictures(output_dir, pictures: Dict[str, np.ndarray], k: int, names: Dict[str, str]) -> None:
     """Image ``k`` of every picture of a batch -> ``output_dir / names[key]``."""
     for key, arr in pictures.items():
@@ -132,17 +135,23 @@ def write_pictures(output_dir, pictures: Dict[str, np.ndarray], k: int, names: D
 def batch_pictures(renderer: PngRenderer, num_classes: int, images: np.ndarray, *, pred_labels: Optional[np.ndarray] = None,
                    gt_labels: Optional[np.ndarray] = None, truths: Optional[np.ndarray] = None,
                    gs_segs: Optional[np.ndarray] = None, gs_labels=None, both_overlay: bool = False,
-                   col_range: Optional[Sequence[int]] = None) -> Dict[str, np.ndarray]:
+                   col_range: Optional[Sequence[int]] = None, ignore_label: Optional[int] = None) -> Dict[str, np.ndarray]:
     """The pictures of one batch, keyed by what they show; each value is (n,H,W,4) uint8 on the host.
 
     ``raw``: the scans.  ``pred``: ``pred_labels`` (n,H,W) through the region colours.  ``gt``: ``gt_labels`` likewise.
     ``truth``: the scans with ``truths`` (n,M,W) solid in the truth colours.  With ``gs_segs`` (n,M,W): ``gs_map``, the
     class maps ``gs_labels`` (host array or device tensor) through the region colours; ``gs_bounds``, the scans with
     ``gs_segs`` solid in the truth colours (the reference passes them as truths); and with ``both_overlay`` ``gs_both``,
-    ``truths`` solid in the truth colours, then ``gs_segs`` dotted in the prediction colours."""
+    ``truths`` solid in the truth colours, then ``gs_segs`` dotted in the prediction colours.
+
+    ``ignore_label``: the value of ``gt_labels`` that means "unknown".  Those pixels are mid-grey, ``IGNORED_RGB``, in ``gt``
+    -- remapped on the host to one more palette entry, index ``num_classes``; the classes keep their colours -- and in the
+    scan under the truth overlays ``truth`` and ``gs_both``, whose truth lines skip the columns where the boundary is 0 as
+    they always do.  No other picture changes."""
     images = np.ascontiguousarray(np.asarray(images).astype(np.uint8, copy=False))
     if images.ndim == 3:
         images = images[..., None]
+    scans = images
     images = torch.from_numpy(images).to(renderer.device)          # uploaded once, the base of up to four pictures
     palette = plotting.region_palette(num_classes)
     out = {"raw": renderer.render(images)}
@@ -155,11 +164,22 @@ def batch_pictures(renderer: PngRenderer, num_classes: int, images: np.ndarray, 
 
     if pred_labels is not None:
         out["pred"] = renderer.render(u8(pred_labels), palette=palette)
-    if gt_labels is not None:
+    truth_base = images                                            # the scan under the truth overlays
+    if gt_labels is not None and ignore_label is None:
         out["gt"] = renderer.render(u8(gt_labels), palette=palette)
+    elif gt_labels is not None:
+        if num_classes + 1 > plotting.MAX_CLASSES:
+            raise ValueError(f"ignore_label: the ground-truth picture needs a palette entry more than the {num_classes} classes")
+        ignored = np.asarray(gt_labels) == ignore_label
+        out["gt"] = renderer.render(u8(np.where(ignored, num_classes, gt_labels)),
+                                    palette=np.concatenate([palette, np.array([IGNORED_RGB], np.uint8)]))
+        if truths is not None and ignored.any():
+            grey = scans.copy()
+            grey[ignored] = IGNORED_RGB[0]
+            truth_base = torch.from_numpy(grey).to(renderer.device)
     if truths is not None:
         truths = u16(truths)
-        out["truth"] = renderer.render(images, lines=truths, colours=plotting.TRUTH_COLOURS[:truths.shape[1]])
+        out["truth"] = renderer.render(truth_base, lines=truths, colours=plotting.TRUTH_COLOURS[:truths.shape[1]])
     if gs_segs is not None:
         gs_segs = u16(gs_segs)
         M = gs_segs.shape[1]
@@ -167,7 +187,7 @@ def batch_pictures(renderer: PngRenderer, num_classes: int, images: np.ndarray, 
         out["gs_bounds"] = renderer.render(images, lines=gs_segs, colours=plotting.TRUTH_COLOURS[:M], col_range=col_range)
         if both_overlay:
             out["gs_both"] = renderer.render(
-                images, lines=np.concatenate([truths, gs_segs], axis=1),
+                truth_base, lines=np.concatenate([truths, gs_segs], axis=1),
                 colours=plotting.TRUTH_COLOURS[:truths.shape[1]] + plotting.PREDICT_COLOURS[:M],
                 styles=[plotting.SOLID] * truths.shape[1] + [plotting.DOTTED] * M, col_range=col_range)
     return out

@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from .. import _hip
+from .dice_device import check_ignore_label
 
 SPACING = (0.01111111, 0.01111111)
 PERCENT = 95.0
@@ -21,9 +22,13 @@ ASD_GT_TO_PRED, ASD_PRED_TO_GT, PERC_GT_TO_PRED, PERC_PRED_TO_GT, N_SURFELS_GT, 
 
 
 class SurfaceDistances:
+    """``ignore_label`` (None, or an int in num_classes..255) selects ``oct_surface_distances_masked``: ground-truth pixels
+    of that value are unknown, and a cell that touches one is a surface element of neither map."""
+
     def __init__(self, batch: int, H: int, W: int, num_classes: int, device, spacing: Tuple[float, float] = SPACING,
-                 percent: float = PERCENT):
+                 percent: float = PERCENT, ignore_label: Optional[int] = None):
         self.B, self.H, self.W, self.C = int(batch), int(H), int(W), int(num_classes)
+        self.ignore_label = check_ignore_label(ignore_label, self.C)
         self.device = torch.device(device)
         self.spacing, self.percent = (float(spacing[0]), float(spacing[1])), float(percent)
         nbytes = _hip.lib().oct_surface_workspace_bytes(self.B, self.H, self.W, self.C)
@@ -39,9 +44,13 @@ class SurfaceDistances:
         The call waits for that stream once: it checks the labels on the device before the distance passes."""
         n = _hip.expect_map_pair(pred, gt, device=self.device, batch=self.B, H=self.H, W=self.W)
         out = _hip.out_view(out, self.out, n)
-        _hip.call("oct_surface_distances", self.device, pred.data_ptr(), gt.data_ptr(), n, self.H, self.W, self.C,
-                  self.spacing[0], self.spacing[1], self.percent, self.workspace.data_ptr(), self.workspace.numel(),
-                  out.data_ptr(), _hip.stream_ptr(self.device))
+        tail = (self.spacing[0], self.spacing[1], self.percent, self.workspace.data_ptr(), self.workspace.numel(),
+                out.data_ptr(), _hip.stream_ptr(self.device))
+        if self.ignore_label is None:
+            _hip.call("oct_surface_distances", self.device, pred.data_ptr(), gt.data_ptr(), n, self.H, self.W, self.C, *tail)
+        else:
+            _hip.call("oct_surface_distances_masked", self.device, pred.data_ptr(), gt.data_ptr(), n, self.H, self.W, self.C,
+                      self.ignore_label, *tail)
         return out
 
     @staticmethod
