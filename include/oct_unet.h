@@ -32,6 +32,7 @@
  *   gradient buffer (caller-owned)     MirroredStrategy all-reduce    training/training.py:185-188,243
  *   oct_unet_graph_capture/_launch     (none: replaces per-call Keras dispatch overhead, evaluation.py:108-135)
  *   oct_unet_forward_mc / oct_mc_update (none: Monte-Carlo dropout prediction; the Dropout(0.5) it keeps on is models/unet.py:130)
+ *   oct_unet_forward_tta / oct_tta_update / oct_flip_batch (none: test-time augmentation, the flips of flip_aug at prediction time)
  *   oct_augment_batch                  BatchGenerator.get_aug_fly/_nofly common/data_generator.py:140-283,
  *                                      flip_aug / add_noise_aug       common/augmentation.py:43-103
  *   oct_pad_batch / oct_crop_batch     (none: Keras raises on a size that is no multiple of 2^pool_layers, in the skip concatenation)
@@ -329,6 +330,62 @@ int oct_mc_update(const float* probs_dev /* (B,H,W,n_cls) f32 */, int B, int H, 
 int oct_unet_forward_mc(oct_unet* h, const void* x_dev, int x_is_u8, int B, int T, unsigned long long step0,
                         float* probs_scratch_dev /* (B,H,W,n_cls) f32 */, void* mc_ws_dev, size_t mc_ws_bytes,
                         const oct_mc_out* out, oct_stream_t stream);
+
+/* ---- test-time augmentation on device: the softmax outputs of mirrored views of a batch, mirrored back and averaged ----
+ * A view code v is in 0..3: bit 0 mirrors columns (xv = W-1-x, "flip_lr"), bit 1 mirrors rows (yv = H-1-y, "flip_ud");
+ * 0 identity, 1 flip_lr, 2 flip_ud, 3 flip_both.  A flip is its own inverse.
+ *
+ * oct_flip_batch: dst[b, y, x] = src[b, yv, xv] over (B,H,W) pixels of `pixel_bytes` bytes each, the set oct_crop_batch
+ * accepts (1, 2, 4, 8, 12, ..., 32: uint8 scans of 1 / 2 / 4 / ... channels, float32 scans of up to 8, every map of
+ * oct_mc_out); the kernel only moves bytes.  Out of place.  Where a row is a whole number of dwords and both bases are
+ * 4-byte aligned it moves dwords (pixels below 4 bytes: whole dwords from the mirrored position, their pixels reversed),
+ * otherwise single bytes; no alignment is required.  common/utils.py::flip_reference restates it.
+ * Errors (negative, oct_last_error(), nothing launched): null or overlapping buffers; non-positive B, H, W; pixel_bytes
+ * outside the set; view outside 0..3; element counts that overflow the kernel's indexing (as oct_crop_batch).
+ *
+ * oct_tta_update is oct_mc_update with ONE change: the running sums and the outputs of pixel (b, y, x) take sample t's pixel
+ * (b, yv, xv) under `view` -- sample t being the softmax output of the batch flipped by `view`, this mirrors it back while
+ * folding.  Workspace (oct_mc_workspace_bytes), oct_mc_out, the fp32 operations, their order and the no-contraction rule
+ * are oct_mc_update's: t == 0 assigns, t == T-1 finishes in registers, sums in class order, the arg-max the lowest index
+ * among equal maxima.  common/utils.py::tta_reduce_reference restates it.  Hence
+ *   - with view == 0 the four maps equal oct_mc_update's byte for byte;
+ *   - for any view, folding the flipped sample (oct_flip_batch(p_t, view)) under that view equals oct_mc_update on p_t
+ *     byte for byte.
+ * With 16-byte aligned buffers, n_cls <= 8 and W % 4 == 0 the kernel moves float4s: 4 adjacent output pixels read 4 adjacent
+ * source pixels, permuted in registers; every other case goes pixel by pixel.  One thread owns an output pixel: no
+ * atomics, deterministic.  Stand-alone like oct_mc_update: no handle, no allocation, ONE asynchronous launch, never waits,
+ * records into a stream capture.  Errors: those of oct_mc_update, and view outside 0..3, T outside 1..4. */
+int oct_flip_batch(const void* src_dev, int B, int H, int W, int pixel_bytes, int view, void* dst_dev, oct_stream_t stream);
+int oct_tta_update(const float* probs_dev /* (B,H,W,n_cls) f32 */, int B, int H, int W, int n_cls, int view, int t, int T,
+                   void* ws_dev, size_t ws_bytes, const oct_mc_out* out /* read when t == T-1 */, oct_stream_t stream);
+
+/* Inference forward of T views of one batch, reduced by oct_tta_update.  For t = 0..T-1: oct_flip_batch(x_dev, views[t]) into
+ * x_view_dev (skipped for view 0: the forward reads x_dev itself), a plain forward (training = 0) of it into
+ * probs_scratch_dev, oct_tta_update(views[t], t, T) into ws_dev; `out` receives the maps of the mean prediction.  The
+ * weights are prepared once for the T forwards; each forward's probabilities are bit for bit those of oct_unet_forward on
+ * the flipped batch.  `views`: HOST array of T codes in 0..3.  x_view_dev: a batch like x_dev (same type and shape); may be
+ * NULL if every view is 0.  Works on training and inference handles, f32 and bf16 (cfg.dtype 1).  Leaves the handle as
+ * oct_unet_forward_mc does: parameters, moving statistics and the dropout step untouched, a pending Dice sum dropped.
+ * Allocates nothing, asynchronous on `stream`, one chain of launches with no second stream -- and deterministic, so unlike
+ * oct_unet_forward_mc it CAN be captured:
+ *
+ * oct_unet_graph_capture_tta records the chain for oct_unet_graph_launch to replay.  x_pad_dev == NULL: (H, W) must be the
+ * handle's size and `out_pad` receives the maps (out_crop is not read).  x_pad_dev != NULL: as
+ * oct_unet_graph_capture_padded, oct_pad_batch of x_dev (B,H,W,in_ch) into x_pad_dev (B,cfg.H,cfg.W,in_ch) in front, the chain
+ * on x_pad_dev into out_pad (padded-size buffers), and one oct_crop_batch per map that out_crop asks for (out_pad must hold
+ * it).  The padded batch is THE input: the views are flips of the padded batch, the fold runs at the padded size and the crop
+ * comes last, so the result equals oct_unet_forward_tta of a handle of the padded size on the padded batch, cropped.
+ * Errors (negative, oct_last_error(), nothing launched): null handle, x, views, scratch, workspace or out; B outside
+ * 1..max_batch; T outside 1..4; a view outside 0..3; a flipped view without x_view_dev or with an input pixel that
+ * oct_flip_batch does not take (in_ch * element size outside its set); the errors of oct_flip_batch and oct_tta_update;
+ * capture: also a default stream, a size other than the handle's without x_pad_dev, the errors of the pad and the crops. */
+int oct_unet_forward_tta(oct_unet* h, const void* x_dev, int x_is_u8, int B, const int* views /* host, T entries */, int T,
+                         void* x_view_dev, float* probs_scratch_dev /* (B,H,W,n_cls) f32 */, void* ws_dev, size_t ws_bytes,
+                         const oct_mc_out* out, oct_stream_t stream);
+int oct_unet_graph_capture_tta(oct_unet* h, const void* x_dev, int x_is_u8, int B, const int* views, int T, void* x_view_dev,
+                               float* probs_scratch_dev, void* ws_dev, size_t ws_bytes, int H, int W, int top, int left,
+                               int pad_mode, float pad_value, void* x_pad_dev, const oct_mc_out* out_pad,
+                               const oct_mc_out* out_crop, oct_stream_t stream);
 
 /* ---- evaluation metrics on device: average surface distance and robust Hausdorff distance of every foreground class
  * (reference evaluation/evaluation.py:207-262 -> common/custom_metrics.py:103-119 -> google-deepmind/surface-distance

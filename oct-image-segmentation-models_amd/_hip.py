@@ -123,6 +123,14 @@ SYMBOLS = [
                                 _P(McOut), C.c_void_p]),
     ("oct_unet_forward_mc", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_ulonglong, C.c_void_p, C.c_void_p,
                                       C.c_size_t, _P(McOut), C.c_void_p]),
+    ("oct_flip_batch", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    ("oct_tta_update", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                 _P(McOut), C.c_void_p]),
+    ("oct_unet_forward_tta", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _P(C.c_int), C.c_int, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_size_t, _P(McOut), C.c_void_p]),
+    ("oct_unet_graph_capture_tta", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _P(C.c_int), C.c_int, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                             C.c_void_p, _P(McOut), _P(McOut), C.c_void_p]),
     ("oct_surface_workspace_bytes", C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     ("oct_surface_distances", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
                                         C.c_double, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),

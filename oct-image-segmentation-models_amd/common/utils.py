@@ -159,6 +159,68 @@ def mc_reduce_reference(probs_stack, dtype=np.float32) -> Tuple[np.ndarray, np.n
     return m, arg, entropy, mutual_info
 
 
+TTA_VIEWS = {"identity": 0, "flip_lr": 1, "flip_ud": 2, "flip_both": 3}    # bit 0 mirrors columns, bit 1 mirrors rows
+TTA_VIEW_NAMES = tuple(TTA_VIEWS)                                          # the name of code v is TTA_VIEW_NAMES[v]
+
+
+def parse_tta(value) -> Tuple[int, ...]:
+    """A test-time-augmentation setting -> its view codes: ``None`` or ``()`` (off) -> ``()``; else a sequence of 1..4
+    distinct names out of ``TTA_VIEWS``, e.g. ``("identity", "flip_lr")`` -> ``(0, 1)``.  Anything else is a ``ValueError``
+    that names the offender."""
+    if value is None:
+        return ()
+    if isinstance(value, str) or not isinstance(value, (tuple, list)):
+        raise ValueError(f"tta must be None or a sequence of view names out of {TTA_VIEW_NAMES}, not {value!r}")
+    if len(value) > len(TTA_VIEWS):
+        raise ValueError(f"tta: at most {len(TTA_VIEWS)} views, not the {len(value)} of {tuple(value)!r}")
+    codes = []
+    for name in value:
+        if not isinstance(name, str) or name not in TTA_VIEWS:
+            raise ValueError(f"tta: unknown view {name!r} (the views are {TTA_VIEW_NAMES})")
+        if TTA_VIEWS[name] in codes:
+            raise ValueError(f"tta: view {name!r} is given twice")
+        codes.append(TTA_VIEWS[name])
+    return tuple(codes)
+
+
+def check_tta(tta, mc_samples: int = 0) -> Tuple[str, ...]:
+    """The public ``tta`` setting, validated (``parse_tta``): the tuple of its view names, ``()`` for off.
+    Together with ``mc_samples`` > 0 it is a ``ValueError``."""
+    parse_tta(tta)
+    names = () if tta is None else tuple(tta)
+    if names and int(mc_samples) > 0:
+        raise ValueError(f"tta={names!r} together with mc_samples={mc_samples}: test-time augmentation and Monte-Carlo "
+                         "dropout are not combined")
+    return names
+
+
+def flip_reference(a, view: int) -> np.ndarray:
+    """``oct_flip_batch`` (include/oct_unet.h) restated with index arrays: ``out[b, y, x] = a[b, yv, xv]`` for a (B,H,W,...)
+    array of any dtype; bit 0 of ``view`` mirrors the columns (``xv = W-1-x``), bit 1 the rows (``yv = H-1-y``)."""
+    a = np.asarray(a)
+    if a.ndim < 3 or not 0 <= int(view) <= 3:
+        raise ValueError("flip_reference: need a (B,H,W,...) array and a view in 0..3")
+    H, W = a.shape[1:3]
+    iy = H - 1 - np.arange(H) if int(view) & 2 else np.arange(H)
+    ix = W - 1 - np.arange(W) if int(view) & 1 else np.arange(W)
+    return np.ascontiguousarray(a[:, iy][:, :, ix])
+
+
+def tta_reduce_reference(probs_stack, views, dtype=np.float32) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """``oct_tta_update`` (include/oct_unet.h) restated: a stack (T, n, H, W, C) whose sample t is the softmax output of the
+    batch flipped by ``views[t]`` (codes in 0..3) -> ``(mean_probs, argmax, entropy, mutual_info)`` of the views mirrored
+    back.  Pixel (b, y, x) of the sums takes sample t's pixel (b, yv, xv), a flip being its own inverse; what follows are
+    the float32 steps of ``mc_reduce_reference``, in its order: ``h_t = -sum_c plogp(p_c)`` in class order, ``S = p`` and
+    ``E = h_0`` for t == 0 and ``S += p``, ``E += h_t`` after, ``m = S * float32(1 / T)``, the arg-max as the lowest index among
+    equal maxima, ``entropy = -sum_c plogp(m_c)`` and ``mutual_info = max(entropy - E * float32(1 / T), 0)``.  So
+    ``mean_probs`` and ``argmax`` equal the kernel's bit for bit; ``dtype=np.float64`` is for the entropy checks."""
+    p = np.asarray(probs_stack, dtype=np.float32)
+    views = tuple(int(v) for v in views)
+    if p.ndim != 5 or not 1 <= p.shape[0] <= len(TTA_VIEWS) or len(views) != p.shape[0]:
+        raise ValueError("tta_reduce_reference: need a (T, n, H, W, C) stack with T in 1..4 and one view code per sample")
+    return mc_reduce_reference(np.stack([flip_reference(p[t], v) for t, v in enumerate(views)]), dtype)
+
+
 PAD_MODES = ("edge", "reflect", "constant")
 
 

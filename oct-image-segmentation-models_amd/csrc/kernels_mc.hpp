@@ -63,10 +63,11 @@ struct McPixel {
     }
 };
 
+// pixel px of the sums and the outputs takes the sample's classes at p (oct_mc_update: the same pixel of probs; oct_tta_update:
+// the mirrored one, kernels_tta.hpp)
 template <bool FIRST, bool LAST>
-__device__ __forceinline__ void mc_pixel(const McArgs& A, size_t px) {
+__device__ __forceinline__ void mc_pixel_from(const McArgs& A, size_t px, const float* p) {
 #pragma clang fp contract(off)
-    const float* p = A.probs + px * A.C;
     float* s = A.S + px * A.C;
     McPixel st{0.f, 0.f, 0.f, 0};
     for (int c = 0; c < A.C; ++c) {
@@ -93,6 +94,76 @@ __device__ __forceinline__ void mc_pixel(const McArgs& A, size_t px) {
     }
 }
 
+template <bool FIRST, bool LAST>
+__device__ __forceinline__ void mc_pixel(const McArgs& A, size_t px) { mc_pixel_from<FIRST, LAST>(A, px, A.probs + px * A.C); }
+
+// load VC float4s = 4 pixels x VC classes of one sample
+template <int VC>
+__device__ __forceinline__ void mc_load4(const float* p, float (&pv)[4 * VC]) {
+    const float4* p4 = reinterpret_cast<const float4*>(p);
+#pragma unroll
+    for (int q = 0; q < VC; ++q) {
+        const float4 a = p4[q];
+        pv[4 * q] = a.x; pv[4 * q + 1] = a.y; pv[4 * q + 2] = a.z; pv[4 * q + 3] = a.w;
+    }
+}
+
+// the float4 item: pixels px0..px0+3 of the sums and the outputs take the sample values pv (pixel j, class c at pv[j * VC + c])
+template <int VC, bool FIRST, bool LAST>
+__device__ __forceinline__ void mc_item4(const McArgs& A, size_t px0, const float (&pv)[4 * VC]) {
+#pragma clang fp contract(off)
+    float4* s4 = reinterpret_cast<float4*>(A.S + px0 * VC);
+    float sv[4 * VC];
+    if constexpr (FIRST) {
+#pragma unroll
+        for (int i = 0; i < 4 * VC; ++i) sv[i] = pv[i];
+    } else {
+#pragma unroll
+        for (int q = 0; q < VC; ++q) {
+            const float4 a = s4[q];
+            sv[4 * q] = a.x + pv[4 * q]; sv[4 * q + 1] = a.y + pv[4 * q + 1];
+            sv[4 * q + 2] = a.z + pv[4 * q + 2]; sv[4 * q + 3] = a.w + pv[4 * q + 3];
+        }
+    }
+    if constexpr (LAST) {
+#pragma unroll
+        for (int i = 0; i < 4 * VC; ++i) sv[i] = sv[i] * A.inv_t;      // sv is now the mean m
+        if (A.mean) {
+            float4* m4 = reinterpret_cast<float4*>(A.mean + px0 * VC);
+#pragma unroll
+            for (int q = 0; q < VC; ++q) m4[q] = make_float4(sv[4 * q], sv[4 * q + 1], sv[4 * q + 2], sv[4 * q + 3]);
+        }
+    } else {
+#pragma unroll
+        for (int q = 0; q < VC; ++q) s4[q] = make_float4(sv[4 * q], sv[4 * q + 1], sv[4 * q + 2], sv[4 * q + 3]);
+    }
+    float e[4], ent[4]; unsigned char bi[4];
+    float4 e_in = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (!FIRST) e_in = *reinterpret_cast<const float4*>(A.E + px0);
+    const float ev[4] = {e_in.x, e_in.y, e_in.z, e_in.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        McPixel st{0.f, 0.f, 0.f, 0};
+#pragma unroll
+        for (int c = 0; c < VC; ++c) st.add<LAST>(c, pv[j * VC + c], sv[j * VC + c]);
+        const float ht = -st.h;
+        e[j] = FIRST ? ht : ev[j] + ht;
+        ent[j] = -st.hm; bi[j] = (unsigned char)st.bi;
+    }
+    if constexpr (LAST) {
+        if (A.am) *reinterpret_cast<uchar4*>(A.am + px0) = make_uchar4(bi[0], bi[1], bi[2], bi[3]);
+        if (A.ent) *reinterpret_cast<float4*>(A.ent + px0) = make_float4(ent[0], ent[1], ent[2], ent[3]);
+        if (A.mi) {
+            float v[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = fmaxf(ent[j] - e[j] * A.inv_t, 0.f);
+            *reinterpret_cast<float4*>(A.mi + px0) = make_float4(v[0], v[1], v[2], v[3]);
+        }
+    } else {
+        *reinterpret_cast<float4*>(A.E + px0) = make_float4(e[0], e[1], e[2], e[3]);
+    }
+}
+
 // items = ceil(npix / 4) with VC > 0, npix with VC == 0
 template <int VC, bool FIRST, bool LAST>
 __global__ void __launch_bounds__(kMcThreads) mc_update_k(const McArgs A, size_t items) {
@@ -107,62 +178,9 @@ __global__ void __launch_bounds__(kMcThreads) mc_update_k(const McArgs A, size_t
                 for (size_t px = px0; px < A.npix; ++px) mc_pixel<FIRST, LAST>(A, px);
                 continue;
             }
-            const float4* p4 = reinterpret_cast<const float4*>(A.probs + px0 * VC);
-            float4* s4 = reinterpret_cast<float4*>(A.S + px0 * VC);
-            float pv[4 * VC], sv[4 * VC];
-#pragma unroll
-            for (int q = 0; q < VC; ++q) {
-                const float4 a = p4[q];
-                pv[4 * q] = a.x; pv[4 * q + 1] = a.y; pv[4 * q + 2] = a.z; pv[4 * q + 3] = a.w;
-            }
-            if constexpr (FIRST) {
-#pragma unroll
-                for (int i = 0; i < 4 * VC; ++i) sv[i] = pv[i];
-            } else {
-#pragma unroll
-                for (int q = 0; q < VC; ++q) {
-                    const float4 a = s4[q];
-                    sv[4 * q] = a.x + pv[4 * q]; sv[4 * q + 1] = a.y + pv[4 * q + 1];
-                    sv[4 * q + 2] = a.z + pv[4 * q + 2]; sv[4 * q + 3] = a.w + pv[4 * q + 3];
-                }
-            }
-            if constexpr (LAST) {
-#pragma unroll
-                for (int i = 0; i < 4 * VC; ++i) sv[i] = sv[i] * A.inv_t;      // sv is now the mean m
-                if (A.mean) {
-                    float4* m4 = reinterpret_cast<float4*>(A.mean + px0 * VC);
-#pragma unroll
-                    for (int q = 0; q < VC; ++q) m4[q] = make_float4(sv[4 * q], sv[4 * q + 1], sv[4 * q + 2], sv[4 * q + 3]);
-                }
-            } else {
-#pragma unroll
-                for (int q = 0; q < VC; ++q) s4[q] = make_float4(sv[4 * q], sv[4 * q + 1], sv[4 * q + 2], sv[4 * q + 3]);
-            }
-            float e[4], ent[4]; unsigned char bi[4];
-            float4 e_in = make_float4(0.f, 0.f, 0.f, 0.f);
-            if constexpr (!FIRST) e_in = *reinterpret_cast<const float4*>(A.E + px0);
-            const float ev[4] = {e_in.x, e_in.y, e_in.z, e_in.w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                McPixel st{0.f, 0.f, 0.f, 0};
-#pragma unroll
-                for (int c = 0; c < VC; ++c) st.add<LAST>(c, pv[j * VC + c], sv[j * VC + c]);
-                const float ht = -st.h;
-                e[j] = FIRST ? ht : ev[j] + ht;
-                ent[j] = -st.hm; bi[j] = (unsigned char)st.bi;
-            }
-            if constexpr (LAST) {
-                if (A.am) *reinterpret_cast<uchar4*>(A.am + px0) = make_uchar4(bi[0], bi[1], bi[2], bi[3]);
-                if (A.ent) *reinterpret_cast<float4*>(A.ent + px0) = make_float4(ent[0], ent[1], ent[2], ent[3]);
-                if (A.mi) {
-                    float v[4];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) v[j] = fmaxf(ent[j] - e[j] * A.inv_t, 0.f);
-                    *reinterpret_cast<float4*>(A.mi + px0) = make_float4(v[0], v[1], v[2], v[3]);
-                }
-            } else {
-                *reinterpret_cast<float4*>(A.E + px0) = make_float4(e[0], e[1], e[2], e[3]);
-            }
+            float pv[4 * VC];
+            mc_load4<VC>(A.probs + px0 * VC, pv);
+            mc_item4<VC, FIRST, LAST>(A, px0, pv);
         }
     }
 }

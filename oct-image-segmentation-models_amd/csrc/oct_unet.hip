@@ -1199,6 +1199,49 @@ int oct_unet_forward_mc(oct_unet* h, const void* x, int x_is_u8, int B, int T, u
     return rc;
 }
 
+// what oct_unet_forward_tta's launches would refuse, with nothing launched
+static int tta_check(oct_unet* h, const void* x, int x_is_u8, int B, const int* views, int T, const void* x_view,
+                     const float* probs_scratch, const void* ws, size_t ws_bytes, const oct_mc_out* out) {
+    if (!h || !x || !views || !probs_scratch || !ws || !out) return fail(-1, "forward_tta: null handle, input, views, scratch, workspace or out");
+    if (B < 1 || B > h->cfg.max_batch) return fail(-1, "B out of range (1..max_batch)");
+    if (T < 1 || T > 4) return fail(-1, "forward_tta: T out of range (1..4)");
+    const oct_unet_cfg& c = h->cfg;
+    const int64_t pb = (int64_t)c.in_ch * (x_is_u8 ? 1 : 4);
+    for (int t = 0; t < T; ++t) {
+        if (views[t] < 0 || views[t] > 3) return fail(-1, "forward_tta: view " + std::to_string(views[t]) + " outside 0..3");
+        if (!views[t]) continue;
+        if (!x_view) return fail(-1, "forward_tta: a flipped view needs x_view_dev");
+        if (pb > 32) return fail(-1, "forward_tta: a pixel of the input has more than 32 bytes");
+        if (int rc = flip_validate(x, B, c.H, c.W, (int)pb, views[t], x_view, nullptr)) return rc;
+    }
+    return tta_validate(probs_scratch, B, c.H, c.W, c.n_cls, views[T - 1], T - 1, T, ws, ws_bytes, out);
+}
+
+// the T-view chain on stream s: one weight preparation, then per view the flip (unless identity), the forward and the fold
+static int tta_chain(oct_unet* h, const void* x, int x_is_u8, int B, const int* views, int T, void* x_view, float* probs_scratch,
+                     void* ws, size_t ws_bytes, const oct_mc_out* out, hipStream_t s) {
+    const oct_unet_cfg& c = h->cfg;
+    const int nl = (int)h->plan.L.size(), pb = c.in_ch * (x_is_u8 ? 1 : 4);
+    oct_unet_io io{}; io.probs = probs_scratch;
+    int rc = forward_prepare(h, 0, false, s);
+    for (int t = 0; t < T && !rc; ++t) {
+        const void* xt = x;
+        if (views[t]) { rc = oct_flip_batch(x, B, c.H, c.W, pb, views[t], x_view, s); xt = x_view; }
+        if (!rc) rc = forward_stages(h, xt, x_is_u8, B, 0, false, false, 0, nl - 1, s);
+        if (!rc) rc = forward_head(h, B, &io, s);
+        if (!rc) rc = oct_tta_update(probs_scratch, B, c.H, c.W, c.n_cls, views[t], t, T, ws, ws_bytes, out, s);
+    }
+    h->have_dice = 0; h->dice_final = 0;
+    return rc;
+}
+
+int oct_unet_forward_tta(oct_unet* h, const void* x, int x_is_u8, int B, const int* views, int T, void* x_view,
+                         float* probs_scratch, void* ws, size_t ws_bytes, const oct_mc_out* out, oct_stream_t stream) {
+    if (int rc = tta_check(h, x, x_is_u8, B, views, T, x_view, probs_scratch, ws, ws_bytes, out)) return rc;
+    t_prof = &h->prof;
+    return tta_chain(h, x, x_is_u8, B, views, T, x_view, probs_scratch, ws, ws_bytes, out, (hipStream_t)stream);
+}
+
 // Dice (and focal) loss of the last forward: out holds n_user floats
 static int loss_finalize(oct_unet* h, const char* what, float smooth, float* out, int n_user, oct_stream_t stream) {
     if (!h) return fail(-1, "null handle");
@@ -1330,6 +1373,43 @@ int oct_unet_graph_capture_padded(oct_unet* h, const void* x, int x_is_u8, int B
     if (!rc && io_crop->probs)
         rc = oct_crop_batch(io.probs, B, Hp, Wp, h->cfg.n_cls * (int)sizeof(float), H, W, top, left, io_crop->probs, s);
     if (!rc && io_crop->argmax) rc = oct_crop_batch(io.argmax, B, Hp, Wp, 1, H, W, top, left, io_crop->argmax, s);
+    const std::string msg = rc ? oct_last_error() : "";
+    hipError_t e = hipStreamEndCapture(s, &h->graph);
+    if (rc) return fail(rc, msg);
+    if (e != hipSuccess) return fail(-5, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
+    HIP_OK(hipGraphInstantiate(&h->graph_exec, h->graph, nullptr, nullptr, 0));
+    return 0;
+}
+
+int oct_unet_graph_capture_tta(oct_unet* h, const void* x, int x_is_u8, int B, const int* views, int T, void* x_view,
+                               float* probs_scratch, void* ws, size_t ws_bytes, int H, int W, int top, int left, int pad_mode,
+                               float pad_value, void* x_pad, const oct_mc_out* out_pad, const oct_mc_out* out_crop,
+                               oct_stream_t stream) {
+    if (!h) return fail(-1, "graph_capture_tta: null handle");
+    const int Hp = h->cfg.H, Wp = h->cfg.W, nc = h->cfg.n_cls;
+    const void* xin = x_pad ? x_pad : x;                       // THE input of the views: the padded batch where there is one
+    if (int rc = tta_check(h, x ? xin : nullptr, x_is_u8, B, views, T, x_view, probs_scratch, ws, ws_bytes, out_pad)) return rc;
+    if (!x_pad && (H != Hp || W != Wp)) return fail(-1, "graph_capture_tta: a size other than the handle's needs x_pad_dev");
+    if (x_pad && !out_crop) return fail(-1, "graph_capture_tta: null out_crop beside x_pad_dev");
+    if (x_pad && ((out_crop->mean_probs && !out_pad->mean_probs) || (out_crop->argmax && !out_pad->argmax) ||
+                  (out_crop->entropy && !out_pad->entropy) || (out_crop->mutual_info && !out_pad->mutual_info)))
+        return fail(-1, "graph_capture_tta: out_crop asks for a map that out_pad does not hold");
+    hipStream_t s = (hipStream_t)stream;
+    if (!s) return fail(-1, "graph capture needs a non-default stream");
+    if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
+    if (h->graph) { (void)hipGraphDestroy(h->graph); h->graph = nullptr; }
+    t_prof = nullptr;  // no event records inside a capture
+    HIP_OK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    int rc = 0;
+    if (x_pad) rc = oct_pad_batch(x, x_is_u8, B, H, W, h->cfg.in_ch, Hp, Wp, top, left, pad_mode, pad_value, x_pad, s);
+    if (!rc) rc = tta_chain(h, xin, x_is_u8, B, views, T, x_view, probs_scratch, ws, ws_bytes, out_pad, s);
+    if (x_pad) {
+        const void* from[4] = {out_pad->mean_probs, out_pad->argmax, out_pad->entropy, out_pad->mutual_info};
+        void* to[4] = {out_crop->mean_probs, out_crop->argmax, out_crop->entropy, out_crop->mutual_info};
+        const int pb[4] = {nc * (int)sizeof(float), 1, (int)sizeof(float), (int)sizeof(float)};
+        for (int i = 0; i < 4 && !rc; ++i)
+            if (to[i]) rc = oct_crop_batch(from[i], B, Hp, Wp, pb[i], H, W, top, left, to[i], s);
+    }
     const std::string msg = rc ? oct_last_error() : "";
     hipError_t e = hipStreamEndCapture(s, &h->graph);
     if (rc) return fail(rc, msg);

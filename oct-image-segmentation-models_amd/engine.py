@@ -23,6 +23,16 @@ from ._hip import OctError, UNetCfg, UNetIO, LayerInfo
 def _ptr(t: Optional[torch.Tensor]): return None if t is None else t.data_ptr()
 
 
+def _view_code(view) -> int:
+    """A view of ``common.utils.TTA_VIEWS`` by name, or its code 0..3 as it is (the library checks the range)."""
+    from .common.utils import TTA_VIEWS
+    if isinstance(view, str):
+        if view not in TTA_VIEWS:
+            raise OctError(f"unknown view {view!r} (the views are {tuple(TTA_VIEWS)})")
+        return TTA_VIEWS[view]
+    return int(view)
+
+
 def _require_gpu(device) -> torch.device:
     dev = torch.device(device)
     if dev.type != "cuda" or not torch.cuda.is_available():
@@ -386,6 +396,13 @@ class UNetEngine:
         """Fold softmax sample ``t`` of ``samples`` -- ``probs`` (B,H,W,C) float32, any C in 2..32 -- into the running sums
         in ``ws`` (a uint8 tensor of ``oct_mc_workspace_bytes`` bytes); the call with ``t == samples - 1`` writes the maps
         that are given (``oct_mc_update``; ``common.utils.mc_reduce_reference`` restates it).  Calls go in order of t."""
+        out = self._mc_out(probs, ws, mean_probs, argmax, entropy, mutual_info)
+        B, H, W, Cn = probs.shape
+        _hip.call("oct_mc_update", self.device, probs.data_ptr(), B, H, W, Cn, int(t), int(samples), ws.data_ptr(), ws.numel(),
+                  C.byref(out), self._stream())
+
+    def _mc_out(self, probs, ws, mean_probs, argmax, entropy, mutual_info) -> "_hip.McOut":
+        """The tensor checks of ``mc_update`` / ``tta_update`` -> the ``oct_mc_out`` of the maps that are given."""
         _hip.expect(probs, "probs (B,H,W,C)", device=self.device, dtype=torch.float32, shape=(None, None, None, None))
         B, H, W, Cn = probs.shape
         _hip.expect(ws, "mc workspace", device=self.device, dtype=torch.uint8, shape=(None,))
@@ -393,9 +410,96 @@ class UNetEngine:
                                     (entropy, "entropy", torch.float32, (B, H, W)), (mutual_info, "mutual_info", torch.float32, (B, H, W))):
             if t_ is not None:
                 _hip.expect(t_, what, device=self.device, dtype=dt, shape=shape)
-        out = _hip.McOut(_ptr(mean_probs), _ptr(argmax), _ptr(entropy), _ptr(mutual_info))
-        _hip.call("oct_mc_update", self.device, probs.data_ptr(), B, H, W, Cn, int(t), int(samples), ws.data_ptr(), ws.numel(),
-                  C.byref(out), self._stream())
+        return _hip.McOut(_ptr(mean_probs), _ptr(argmax), _ptr(entropy), _ptr(mutual_info))
+
+    # ---- test-time augmentation: flipped views averaged on the device ---------------------------------
+    def flip(self, t: torch.Tensor, view, out=None) -> torch.Tensor:
+        """(B,H,W[,C]) uint8 or float32 -> the same shape mirrored by ``view`` -- a name of ``common.utils.TTA_VIEWS`` or its
+        code 0..3 -- on the device (``oct_flip_batch``, one byte-moving kernel; ``common.utils.flip_reference`` restates it).
+        ``out``: optional tensor to write into, never ``t`` itself.  Asynchronous on the current stream."""
+        if t.dim() not in (3, 4):
+            raise OctError(f"flip: t must be (B,H,W) or (B,H,W,C), not {tuple(t.shape)}")
+        _hip.expect(t, "flip: t (B,H,W[,C])", device=self.device, dtype=(torch.uint8, torch.float32), shape=(None,) * t.dim())
+        if out is None:
+            out = torch.empty_like(t)
+        _hip.expect(out, "flip: out", device=self.device, dtype=t.dtype, shape=tuple(t.shape))
+        B, H, W = t.shape[:3]
+        _hip.call("oct_flip_batch", self.device, t.data_ptr(), B, H, W, t.element_size() * int(np.prod(t.shape[3:], dtype=np.int64)),
+                  _view_code(view), out.data_ptr(), self._stream())
+        return out
+
+    def tta_update(self, probs: torch.Tensor, view, t: int, samples: int, ws: torch.Tensor, *, mean_probs=None, argmax=None,
+                   entropy=None, mutual_info=None) -> None:
+        """``mc_update`` for the softmax output ``probs`` of the batch flipped by ``view``: pixel (b, y, x) of the sums and
+        of the maps takes the mirrored pixel of ``probs`` (``oct_tta_update``; ``common.utils.tta_reduce_reference``).
+        ``samples`` is the number of views, 1..4; calls go in order of t."""
+        out = self._mc_out(probs, ws, mean_probs, argmax, entropy, mutual_info)
+        B, H, W, Cn = probs.shape
+        _hip.call("oct_tta_update", self.device, probs.data_ptr(), B, H, W, Cn, _view_code(view), int(t), int(samples),
+                  ws.data_ptr(), ws.numel(), C.byref(out), self._stream())
+
+    def _tta_buffers(self, B: int, x: torch.Tensor) -> dict:
+        """``_mc_buffers`` plus the flipped input of ``forward_tta`` for batch ``B`` and the input's type: made once, kept."""
+        b = self._mc_buffers(B)
+        key = "x_view_u8" if x.dtype == torch.uint8 else "x_view_f32"
+        if key not in b:
+            b[key] = torch.empty((B, self.cfg.H, self.cfg.W, self.cfg.in_ch), dtype=x.dtype, device=self.device)
+        return dict(b, x_view=b[key])
+
+    @staticmethod
+    def _tta_views(views):
+        from .common.utils import parse_tta
+        try:
+            codes = parse_tta(views)
+        except ValueError as e:
+            raise OctError(str(e)) from None
+        if not codes:
+            raise OctError("tta: at least one view is needed")
+        return (C.c_int * len(codes))(*codes), len(codes)
+
+    def forward_tta(self, x: torch.Tensor, views, want_mean_probs: bool = False) -> Dict[str, torch.Tensor]:
+        """One inference forward per view of ``views`` -- 1..4 distinct names of ``common.utils.TTA_VIEWS`` -- on the batch
+        flipped by it, mirrored back and averaged on the device (``oct_unet_forward_tta``): a dict of device tensors like
+        ``forward_mc``'s, ``argmax`` being that of the mean prediction.  The tensors are the engine's own buffers for this
+        batch size, shared with ``forward_mc``: the next call of either refills them.  Asynchronous on the current stream."""
+        self._check_x(x)
+        codes, T = self._tta_views(views)
+        B = x.shape[0]
+        b = self._tta_buffers(B, x)
+        keys = ("argmax", "entropy", "mutual_info") + (("mean_probs",) if want_mean_probs else ())
+        out = _hip.McOut(**{k: b[k].data_ptr() for k in keys})
+        self._call("oct_unet_forward_tta", x.data_ptr(), int(x.dtype == torch.uint8), B, codes, T, b["x_view"].data_ptr(),
+                   b["scratch"].data_ptr(), b["ws"].data_ptr(), b["ws"].numel(), C.byref(out), self._stream())
+        self._keep = [x]
+        return {k: b[k] for k in keys}
+
+    def graph_capture_tta(self, x: torch.Tensor, views, want_mean_probs: bool = False, pad=None) -> Dict[str, torch.Tensor]:
+        """Capture ``forward_tta`` of the fixed input ``x`` into the graph that ``graph_launch`` replays; returns the dict
+        of output tensors every replay refills (the engine's buffers for this batch size, as ``forward_tta``; with ``pad``,
+        tensors of the input's own size that the capture owns).  ``pad``: ``(top, left, mode, value)`` for an input of a
+        size that is no multiple of 2^pool_layers on an engine built at the padded size -- the graph then pads in front,
+        takes the views of the PADDED batch and crops every map behind (``oct_unet_graph_capture_tta``).  ``x`` must be
+        refilled in place between launches."""
+        self._check_x(x, any_size=pad is not None)
+        codes, T = self._tta_views(views)
+        B, H, W, _ = x.shape
+        b = self._tta_buffers(B, x)
+        keys = ("argmax", "entropy", "mutual_info") + (("mean_probs",) if want_mean_probs else ())
+        out_pad = _hip.McOut(**{k: b[k].data_ptr() for k in keys})
+        outs, x_pad, out_crop, at = {k: b[k] for k in keys}, None, None, (0, 0, 0, 0.0)
+        if pad is not None:
+            top, left, mode, value = pad
+            if mode not in _hip.PAD_MODES:
+                raise OctError(f'graph_capture_tta: mode must be "edge", "reflect" or "constant", not {mode!r}')
+            at = (int(top), int(left), _hip.PAD_MODES[mode], float(value))
+            x_pad = torch.empty((B, self.cfg.H, self.cfg.W, self.cfg.in_ch), dtype=x.dtype, device=self.device)
+            outs = {k: torch.empty((B, H, W) + tuple(b[k].shape[3:]), dtype=b[k].dtype, device=self.device) for k in keys}
+            out_crop = _hip.McOut(**{k: outs[k].data_ptr() for k in keys})
+        self._graph_keep = [x, x_pad, b, outs]
+        self._capture("oct_unet_graph_capture_tta", x.data_ptr(), int(x.dtype == torch.uint8), B, codes, T, b["x_view"].data_ptr(),
+                      b["scratch"].data_ptr(), b["ws"].data_ptr(), b["ws"].numel(), H, W, *at, _ptr(x_pad), C.byref(out_pad),
+                      None if out_crop is None else C.byref(out_crop))
+        return outs
 
     # ---- inference hipGraph ------------------------------------------------------------------------
     def graph_capture(self, x: torch.Tensor, want_probs=True, want_argmax=False):

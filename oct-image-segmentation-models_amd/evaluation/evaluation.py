@@ -181,7 +181,7 @@ def evaluate_model(eval_params: EvaluationParameters) -> List[EvaluationOutput]:
                       gs_device_ties=eval_params.gs_device_ties, gs_workers=eval_params.gs_workers,
                       soft_maps=not getattr(eval_params, "binarize", True),
                       pad_mode=getattr(eval_params, "pad_mode", None), pad_value=getattr(eval_params, "pad_value", 0),
-                      ignore_label=ignore_label) as run:
+                      ignore_label=ignore_label, tta=getattr(eval_params, "tta", None)) as run:
         t_prev = time.time()
         for batch in run:
             b0, b1 = lo + batch.lo, lo + batch.hi
@@ -288,6 +288,8 @@ def _save_image_evaluation_results(eval_params, eval_image, image_name, predicte
     for k, v in (surface_ds or {}).items():          # evaluation.py:573-597
         ds[k] = np.asarray(v, dtype="float64")
     attrs = common_utils.result_attrs(eval_params.model_path, image_name, predict_time=np.array(predict_time))
+    if getattr(eval_params, "tta", None):
+        attrs["tta_views"] = np.array(",".join(eval_params.tta), dtype="S1000")      # only when set: other files stay as they were
     h5io.save(output_dir / Path(EVALUATION_RESULTS_FILENAME), ds, attrs)
 
 
@@ -327,6 +329,8 @@ def save_eval_config_file(eval_params: EvaluationParameters):
         attrs["pad_value"] = np.array(float(getattr(eval_params, "pad_value", 0)))
     if getattr(eval_params, "ignore_label", None) is not None:
         attrs["ignore_label"] = np.array(int(eval_params.ignore_label))      # likewise
+    if getattr(eval_params, "tta", None):
+        attrs["tta_views"] = np.array(",".join(eval_params.tta), dtype="S1000")      # likewise
     h5io.save(eval_params.save_foldername / Path("eval_params.hdf5"), {}, attrs)
 
 

@@ -27,7 +27,14 @@ class EvaluationParameters:
                  graph_search: bool, metrics: List[str], gsgrad=1, dice_errors: bool = True, binarize: bool = True,
                  bg_ilm: bool = True, bg_csi: bool = False, batch_size: int = 32, gs_device: bool = False,
                  gs_device_ties: str = "host", gs_workers: Optional[int] = None, metrics_device: bool = False,
-                 png_plots: bool = False, pad_mode: Optional[str] = None, pad_value=0, ignore_label: Optional[int] = None):
+                 png_plots: bool = False, pad_mode: Optional[str] = None, pad_value=0, ignore_label: Optional[int] = None,
+                 tta=None):
+        # extension: test-time augmentation.  1..4 distinct view names out of common.utils.TTA_VIEWS ("identity", "flip_lr",
+        # "flip_ud", "flip_both"): every batch is predicted once per view on the mirrored scans, the softmax outputs are mirrored
+        # back and averaged on the device, and all metrics, boundary maps, graph-search delineations and pictures come from
+        # that mean prediction; the result files record tta_views.  Everything behind the prediction is unchanged, so it
+        # combines with pad_mode, ignore_label, binarize=False, metrics_device, gs_device and png_plots.  None or (): off
+        self.tta = utils.check_tta(tta)
         # extension: scans whose size is no multiple of 2^pool_layers (the reference raises on them) are padded on the
         # device in front of the forward -- "edge", "reflect" or "constant" with pad_value in raw counts -- and the arg-max
         # maps (with binarize=False the probabilities too) are cropped directly behind the head: metrics, searches, files

@@ -15,7 +15,7 @@ from typing import Iterable, Iterator, NamedTuple, Optional, Tuple
 import numpy as np
 import torch
 
-from ..common.utils import check_pad_mode, padded_geometry
+from ..common.utils import check_pad_mode, check_tta, padded_geometry
 from ..min_path_processing.device_search import DeviceMinPath, LazyPool, merge_ties
 from ..min_path_processing.pool import SegmentPool, default_workers
 from .dice_device import ConfusionCounts, DelineationLabels, check_ignore_label
@@ -34,9 +34,10 @@ class Batch(NamedTuple):
     minpath: Optional[Tuple[np.ndarray, ...]] = None   # rows (n, C-1, W) uint16, cost (n, C-1) float64, tied (n, C-1) bool
     confusion: Optional[np.ndarray] = None         # (n, C, C) uint32 confusion counts [gt][pred] of labels against the ground truth
 
-    # Monte-Carlo dropout runs (mc_samples > 0) also carry two (n, H, W) float32 maps: the predictive entropy (nats) and the
-    # mutual information (BALD) of the samples.  They are ATTRIBUTES, not tuple fields -- the seven fields above are what
-    # every positional construction and unpacking of a record relies on -- and None on every other record.
+    # Monte-Carlo dropout runs (mc_samples > 0) and test-time-augmentation runs (tta) also carry two (n, H, W) float32 maps:
+    # the predictive entropy (nats) and the mutual information (BALD) of the samples / views.  They are ATTRIBUTES, not tuple
+    # fields -- the seven fields above are what every positional construction and unpacking of a record relies on -- and
+    # None on every other record.
     entropy = None
     mutual_info = None
 
@@ -107,15 +108,23 @@ class BatchedPredictor:
     captured graph is then ``oct_pad_batch`` of the true-size input, the forward and ``oct_crop_batch`` of the arg-max maps
     (and of the probabilities with ``soft_maps``), the pinned upload buffers and everything behind the graph are true-size,
     and every stage runs on the cropped tensors.  A Monte-Carlo batch pads in front of ``forward_mc`` and crops its arg-max,
-    entropy, mutual information and mean probabilities.  Without ``hw`` nothing is launched that was not before."""
+    entropy, mutual information and mean probabilities.  Without ``hw`` nothing is launched that was not before.
+
+    With ``tta`` -- 1..4 distinct view names of ``common.utils.TTA_VIEWS`` -- every batch is a test-time-augmented
+    prediction, and unlike the Monte-Carlo one it IS a graph: the graph captured here is ``engine.graph_capture_tta`` (per
+    view the flip of the input, the forward and the mirrored fold; with ``hw`` the pad in front, the views taken of the
+    padded batch, and the crops behind).  As for ``mc_samples`` the arg-max maps and (with ``soft_maps``) the probabilities
+    are those of the MEAN prediction and ``Batch.entropy`` / ``Batch.mutual_info`` carry the two maps over the views;
+    the result does not depend on the batch an image sits in.  ``tta`` with ``mc_samples`` > 0 is refused."""
 
     def __init__(self, engine, batch: int, want_maps: bool = True, bg_ilm: bool = True, bg_csi: bool = False,
                  surface=None, minpath=None, confusion=None, soft_maps: bool = False, mc_samples: int = 0, mc_step0: int = 0,
-                 hw=None, pad_mode: Optional[str] = None, pad_value=0):
+                 hw=None, pad_mode: Optional[str] = None, pad_value=0, tta=None):
         if soft_maps and not want_maps:
             raise ValueError("soft_maps: needs want_maps=True")
         if not 0 <= int(mc_samples) <= 64:
             raise ValueError(f"mc_samples must be in 0..64, not {mc_samples}")
+        self.tta = check_tta(tta, mc_samples)
         self.pad_mode, self.pad_value = check_pad_mode(pad_mode, pad_value)
         self.soft_maps, self.mc_samples, self.mc_step0 = bool(soft_maps), int(mc_samples), int(mc_step0)
         if not 1 <= batch <= engine.cfg.max_batch:
@@ -155,9 +164,15 @@ class BatchedPredictor:
         self.copy_in = torch.cuda.Stream(device=dev)
         self.copy_out = torch.cuda.Stream(device=dev)
         self.unc_dev = self.unc_pin = None                  # (entropy, mutual_info) double buffers
-        if self.mc_samples:
+        if self.mc_samples or self.tta:
             self.unc_dev = [tuple(torch.empty((self.B, H, W), dtype=torch.float32, device=dev) for _ in range(2)) for _ in range(2)]
             self.unc_pin = [tuple(torch.empty((self.B, H, W), dtype=torch.float32).pin_memory() for _ in range(2)) for _ in range(2)]
+        self.tta_out = None                                 # the maps every replay of the TTA graph refills
+        if self.tta:
+            pad = None if self.at is None else (*self.at, self.pad_mode, self.pad_value)
+            self.tta_out = engine.graph_capture_tta(self.x_dev, self.tta, want_mean_probs=self.soft_maps, pad=pad)
+            self.am, self.probs = self.tta_out["argmax"], self.tta_out.get("mean_probs")
+        elif self.mc_samples:
             self.probs = self.am = None                     # the engine's forward_mc buffers: set by every batch
             if self.at is not None:                         # the padded input and the crops' own buffers: made once, kept
                 f32 = dict(dtype=torch.float32, device=dev)
@@ -233,6 +248,7 @@ class BatchedPredictor:
                 self.am, self.probs = mc["argmax"], mc.get("mean_probs")
             else:
                 eng.graph_launch()
+                mc = self.tta_out
             if i >= 2:
                 main.wait_event(out_done[s])                                            # device out buffers of batch i-2 downloaded
             self.lab_dev[s].copy_(self.am)
@@ -284,12 +300,13 @@ class BatchedPredictor:
 
 def host_batches(model, images: np.ndarray, batch: int, *, gt_u8: Optional[np.ndarray] = None, surface=None,
                  minpath=None, confusion=None, soft_maps: bool = False, mc_samples: int = 0, mc_step0: int = 0,
-                 pad_mode: Optional[str] = None, pad_value=0) -> Iterator[Batch]:
+                 pad_mode: Optional[str] = None, pad_value=0, tta=None) -> Iterator[Batch]:
     """The same records for images that are not uint8: x / 255 on the host (``Model.predict_labels``), one synchronous
     forward per batch, no overlap.  ``surface`` / ``minpath`` / ``confusion`` / ``soft_maps`` / ``mc_samples`` /
-    ``mc_step0`` as in ``BatchedPredictor``; each stage writes its own output buffers.  ``pad_mode`` / ``pad_value`` (in raw
+    ``mc_step0`` / ``tta`` as in ``BatchedPredictor``; each stage writes its own output buffers.  ``pad_mode`` / ``pad_value`` (in raw
     counts) go to ``Model.predict_labels``, which pads and crops on the device."""
     pad_mode, pad_value = check_pad_mode(pad_mode, pad_value)
+    tta = check_tta(tta, mc_samples)
     stages = _stages(surface, confusion, minpath, have_gt=gt_u8 is not None)
     on_labels, on_maps = any(not st.on_maps for st in stages), any(st.on_maps for st in stages)
 
@@ -300,7 +317,7 @@ def host_batches(model, images: np.ndarray, batch: int, *, gt_u8: Optional[np.nd
         hi = min(lo + batch, images.shape[0])
         labels, maps, *unc = model.predict_labels(images[lo:hi], batch_size=batch, want_maps=True, bg_ilm=True, bg_csi=False,
                                                   soft_maps=soft_maps, mc_samples=mc_samples, mc_step0=mc_step0,
-                                                  pad_mode=pad_mode, pad_value=pad_value)
+                                                  pad_mode=pad_mode, pad_value=pad_value, tta=tta)
         lab_dev, gt_dev = (upload(labels.astype(np.uint8)), upload(gt_u8[lo:hi])) if on_labels else (None, None)
         maps_dev = upload(maps) if on_maps else None
         fields = {}
@@ -331,6 +348,9 @@ class InferenceRun:
     ``Batch.labels`` / ``Batch.maps`` are those of the mean prediction, and ``Batch.entropy`` / ``Batch.mutual_info`` are
     filled (see ``BatchedPredictor`` for what the result depends on).
 
+    ``tta`` (1..4 distinct view names of ``common.utils.TTA_VIEWS``; None or () : off) is passed on likewise: every batch is
+    then the mean prediction over the flipped views, with the same two maps filled.  With ``mc_samples`` > 0 it is refused.
+
     The engine follows the images: the model is asked for the engine of ``images.shape[1:3]``, whatever its config
     records.  ``pad_mode`` ("edge", "reflect", "constant" with ``pad_value`` in raw counts; None: off) admits sizes that are
     no multiple of 2^pool_layers: the engine is then the one of the padded size, the source pads in front of the forward and
@@ -347,8 +367,9 @@ class InferenceRun:
                  graph_search: bool = False, gsgrad: int = 1, gs_device: bool = False, gs_device_ties: str = "host",
                  gs_workers: Optional[int] = None, batches: Optional[Iterable[Batch]] = None, surface: bool = True,
                  confusion: bool = False, soft_maps: bool = False, mc_samples: int = 0, mc_step0: int = 0,
-                 pad_mode: Optional[str] = None, pad_value=0, ignore_label: Optional[int] = None):
+                 pad_mode: Optional[str] = None, pad_value=0, ignore_label: Optional[int] = None, tta=None):
         pad_mode, pad_value = check_pad_mode(pad_mode, pad_value)
+        self.tta = tta = check_tta(tta, mc_samples)
         n, (H, W), C = images.shape[0], images.shape[1:3], int(num_classes)
         self.ignore_label = ignore_label = check_ignore_label(ignore_label, C)
         self.pool = self.host_ties = None
@@ -386,12 +407,12 @@ class InferenceRun:
                 predictor = BatchedPredictor(model._ensure_engine(bs, False, hw=geom), bs, want_maps=True, bg_ilm=True,
                                              bg_csi=False, surface=surface, minpath=minpath, confusion=confusion,
                                              soft_maps=soft_maps, mc_samples=mc_samples, mc_step0=mc_step0,
-                                             hw=(H, W), pad_mode=pad_mode, pad_value=pad_value)
+                                             hw=(H, W), pad_mode=pad_mode, pad_value=pad_value, tta=tta)
                 self._batches = predictor.run(images, gt_u8)
             else:
                 self._batches = host_batches(model, images, bs, gt_u8=gt_u8, surface=surface, minpath=minpath,
                                              confusion=confusion, soft_maps=soft_maps, mc_samples=mc_samples,
-                                             mc_step0=mc_step0, pad_mode=pad_mode, pad_value=pad_value)
+                                             mc_step0=mc_step0, pad_mode=pad_mode, pad_value=pad_value, tta=tta)
         except BaseException:
             self.close()
             raise

@@ -517,9 +517,28 @@ class Model:
             mean[lo:hi], ent[lo:hi], mi[lo:hi] = (out[k].cpu().numpy() for k in keys)
         return mean, ent, mi
 
+    def predict_tta(self, x, views, batch_size: Optional[int] = None):
+        """Test-time-augmented prediction: one forward per view of ``views`` -- 1..4 distinct names of
+        ``common.utils.TTA_VIEWS``, e.g. ``("identity", "flip_lr")`` -- on the batch mirrored by it, mirrored back and
+        averaged on the device (``UNetEngine.forward_tta``).  Input as for ``predict``; returns ``(mean_probs
+        (n,H,W,num_classes) float32, argmax (n,H,W) uint8 of the mean, entropy (n,H,W), mutual_info (n,H,W))``, the last two
+        float32: the predictive entropy of the mean and the mutual information over the views.  Deterministic, and
+        independent of the batch an image sits in.  Padding as for ``predict_mc``, from the model's ``pad_mode`` /
+        ``pad_value`` attributes: the views are flips of the PADDED batch and the four maps are cropped on the device."""
+        x = np.asarray(x)
+        if x.dtype != np.uint8:
+            x = np.ascontiguousarray(x, dtype=np.float32)
+        keys = ("mean_probs", "argmax", "entropy", "mutual_info")
+        mean = np.empty(x.shape[:3] + (self.config["num_classes"],), np.float32)
+        am, ent, mi = np.empty(x.shape[:3], np.uint8), np.empty(x.shape[:3], np.float32), np.empty(x.shape[:3], np.float32)
+        for lo, hi, eng, xb, crop in self._inference_batches(x, int(batch_size or min(x.shape[0], 32)), self._pad_options(None, 0)):
+            out = crop(eng.forward_tta(xb, views, want_mean_probs=True))
+            mean[lo:hi], am[lo:hi], ent[lo:hi], mi[lo:hi] = (out[k].cpu().numpy() for k in keys)
+        return mean, am, ent, mi
+
     def predict_labels(self, x_u8: np.ndarray, batch_size: int = 32, want_maps: bool = False, bg_ilm: bool = True,
                        bg_csi: bool = False, soft_maps: bool = False, mc_samples: int = 0, mc_step0: int = 0,
-                       pad_mode: Optional[str] = None, pad_value=0):
+                       pad_mode: Optional[str] = None, pad_value=0, tta=None):
         """Raw uint8 images -> uint8 arg-max class maps (n,H,W), computed on the device (1 B/px back instead of
         4*C B/px).  With ``want_maps`` also the (n, C-1, H, W) uint8 boundary maps of
         ``convert_predictions_to_maps_semantic``, computed on the device from the class maps -- or, with ``soft_maps``,
@@ -527,11 +546,15 @@ class Model:
         With ``mc_samples`` > 0 every batch is a Monte-Carlo dropout prediction (``predict_mc``): the class maps and
         boundary maps are those of the mean prediction, and the (n,H,W) float32 predictive entropy and mutual information
         are returned behind them -- ``(labels, entropy, mutual_info)`` or ``(labels, maps, entropy, mutual_info)``.
+        With ``tta`` (view names as for ``predict_tta``; not together with ``mc_samples``) every batch is the mean prediction
+        over the flipped views instead, returned in the same form.
         ``pad_mode`` / ``pad_value`` (in raw counts, like ``x_u8``) as for ``predict``: the arg-max maps -- and the
         probabilities and uncertainty maps where they are made -- are cropped on the device directly behind the head, and
         the boundary maps are those of the cropped tensors."""
         if soft_maps and not want_maps:
             raise ValueError("soft_maps: needs want_maps=True")
+        from ..common.utils import check_tta
+        tta = check_tta(tta, mc_samples)
         pad_mode, pad_value = self._pad_options(pad_mode, pad_value)
         x_u8 = np.ascontiguousarray(x_u8)
         if x_u8.dtype != np.uint8:
@@ -541,10 +564,11 @@ class Model:
             pad_value = float(np.float32(pad_value) / np.float32(255.0))
         out = np.empty(x_u8.shape[:3], np.uint8)
         maps = np.empty((x_u8.shape[0], self.config["num_classes"] - 1) + tuple(x_u8.shape[1:3]), np.uint8) if want_maps else None
-        unc = (np.empty(x_u8.shape[:3], np.float32), np.empty(x_u8.shape[:3], np.float32)) if mc_samples else ()
+        unc = (np.empty(x_u8.shape[:3], np.float32), np.empty(x_u8.shape[:3], np.float32)) if mc_samples or tta else ()
         for lo, hi, eng, xb, crop in self._inference_batches(x_u8, batch_size, (pad_mode, pad_value)):
-            if mc_samples:
-                mc = crop(eng.forward_mc(xb, mc_samples, step0=mc_step0, want_mean_probs=soft_maps))
+            if mc_samples or tta:
+                mc = crop(eng.forward_tta(xb, tta, want_mean_probs=soft_maps) if tta else
+                          eng.forward_mc(xb, mc_samples, step0=mc_step0, want_mean_probs=soft_maps))
                 probs, am = mc.get("mean_probs"), mc["argmax"]
                 unc[0][lo:hi], unc[1][lo:hi] = mc["entropy"].cpu().numpy(), mc["mutual_info"].cpu().numpy()
             else:
@@ -554,7 +578,7 @@ class Model:
                 dev_maps = (eng.boundary_maps_soft(probs, bg_ilm=bg_ilm, bg_csi=bg_csi) if soft_maps
                             else eng.boundary_maps(am, bg_ilm=bg_ilm, bg_csi=bg_csi))
                 maps[lo:hi] = dev_maps.cpu().numpy()
-        return ((out, maps) if want_maps else out) if not mc_samples else ((out, maps) + unc if want_maps else (out,) + unc)
+        return ((out, maps) if want_maps else out) if not unc else ((out, maps) + unc if want_maps else (out,) + unc)
 
 
 def load_model(path) -> Model:

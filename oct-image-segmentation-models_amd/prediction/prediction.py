@@ -46,7 +46,11 @@ def predict(predict_params: PredictionParams) -> List[PredictionOutput]:
     With ``predict_params.mc_samples`` > 0 every batch is a Monte-Carlo dropout prediction (``InferenceRun(mc_samples=)``):
     every file describes the MEAN prediction, prediction_info.hdf5 gains the float32 (H,W) datasets ``predictive_entropy``
     and ``mutual_information`` and the attribute ``mc_samples``, and with the PNG pictures on ``uncertainty_map.png`` (the
-    entropy over ln C as a gray scan) is written too.  With 0 every file is byte for byte what it was."""
+    entropy over ln C as a gray scan) is written too.  With 0 every file is byte for byte what it was.
+
+    With ``predict_params.tta`` (view names, ``common.utils.TTA_VIEWS``) every batch is the mean prediction over the flipped
+    views (``InferenceRun(tta=)``): the same two datasets and picture, and the attribute ``tta_views`` -- the names joined
+    by commas -- in place of ``mc_samples``.  Unset, nothing more is launched and every file is byte for byte what it was."""
     rank, _, _ = parallel.init()
     world = parallel.world_size()
     dataset = predict_params.dataset
@@ -73,7 +77,7 @@ def predict(predict_params: PredictionParams) -> List[PredictionOutput]:
                       soft_maps=not getattr(predict_params, "binarize", True),
                       mc_samples=mc_samples, mc_step0=getattr(predict_params, "mc_step0", 0),
                       pad_mode=getattr(predict_params, "pad_mode", None),
-                      pad_value=getattr(predict_params, "pad_value", 0)) as run:
+                      pad_value=getattr(predict_params, "pad_value", 0), tta=getattr(predict_params, "tta", None)) as run:
         t0 = time.time()
         for batch in run:
             b0, b1 = lo + batch.lo, lo + batch.hi
@@ -143,6 +147,8 @@ def save_predict_config_file(predict_params: PredictionParams):
     if getattr(predict_params, "mc_samples", 0):
         attrs["mc_samples"] = np.array(int(predict_params.mc_samples))      # likewise, with the first dropout step
         attrs["mc_step0"] = np.array(int(getattr(predict_params, "mc_step0", 0)))
+    if getattr(predict_params, "tta", None):
+        attrs["tta_views"] = np.array(",".join(predict_params.tta), dtype="S1000")      # likewise
     if getattr(predict_params, "pad_mode", None) is not None:
         attrs["pad_mode"] = np.array(str(predict_params.pad_mode), dtype="S1000")      # likewise, with the constant
         attrs["pad_value"] = np.array(float(getattr(predict_params, "pad_value", 0)))
@@ -151,8 +157,8 @@ def save_predict_config_file(predict_params: PredictionParams):
 
 def save_image_prediction_results(pred_params, predict_image, image_name, predicted_labels, categorical_pred,
                                   boundary_maps, predict_time, convert_time, output_dir, entropy=None, mutual_info=None):
-    """``entropy`` / ``mutual_info``: the (H,W) maps of a Monte-Carlo dropout prediction, stored (with the sample count)
-    only when given: without them the file is what it always was."""
+    """``entropy`` / ``mutual_info``: the (H,W) maps of a Monte-Carlo dropout or test-time-augmented prediction, stored
+    (with the sample count, or the views) only when given: without them the file is what it always was."""
     ds = {}
     if pred_params.save_params.categorical_pred is True:
         ds["categorical_pred"] = categorical_pred.astype("uint8")
@@ -166,7 +172,10 @@ def save_image_prediction_results(pred_params, predict_image, image_name, predic
     if entropy is not None:
         ds["predictive_entropy"] = np.asarray(entropy, np.float32)
         ds["mutual_information"] = np.asarray(mutual_info, np.float32)
-        attrs["mc_samples"] = np.array(int(getattr(pred_params, "mc_samples", 0)))
+        if getattr(pred_params, "tta", None):
+            attrs["tta_views"] = np.array(",".join(pred_params.tta), dtype="S1000")
+        else:
+            attrs["mc_samples"] = np.array(int(getattr(pred_params, "mc_samples", 0)))
     h5io.save(output_dir / Path("prediction_info.hdf5"), ds, attrs)
 
 

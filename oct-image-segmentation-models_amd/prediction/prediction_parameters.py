@@ -26,9 +26,15 @@ class PredictionParams:
                  trim_window: tuple = (0, 0), col_error_range: tuple = None, batch_size: int = 32, gs_device: bool = False,
                  gs_device_ties: str = "host", gs_workers: Union[int, None] = None, gs_labels_device: bool = False,
                  binarize: bool = True, png_plots: bool = False, mc_samples: int = 0, mc_step0: int = 0,
-                 pad_mode: Union[str, None] = None, pad_value=0) -> None:
+                 pad_mode: Union[str, None] = None, pad_value=0, tta=None) -> None:
         if not 0 <= int(mc_samples) <= 64:
             raise ValueError(f"mc_samples must be in 0..64, not {mc_samples}")
+        # extension: test-time augmentation.  1..4 distinct view names out of common.utils.TTA_VIEWS ("identity", "flip_lr",
+        # "flip_ud", "flip_both"): every batch is predicted once per view on the mirrored scans and the softmax outputs are
+        # mirrored back and averaged on the device; every file describes the mean prediction, and prediction_info.hdf5 gains
+        # predictive_entropy / mutual_information and the attribute tta_views.  Deterministic; not combined with mc_samples.
+        # None or (): one view per scan, every file as it was
+        self.tta = utils.check_tta(tta, mc_samples)
         # extension: scans whose size is no multiple of 2^pool_layers (the reference raises on them) are padded on the
         # device in front of the forward -- "edge", "reflect" or "constant" with pad_value in raw counts -- and every output
         # is cropped directly behind the head, so every file has the scans' own size.  None: such sizes are refused.  Sizes
