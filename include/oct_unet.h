@@ -30,9 +30,9 @@
  *   oct_adam_step / oct_sgd_step       optimizer.apply_gradients      training/training.py:190-193
  *   oct_opt_step                       ... of any other opt_con, and the clipnorm / clipvalue / global_clipnorm options
  *   gradient buffer (caller-owned)     MirroredStrategy all-reduce    training/training.py:185-188,243
- *   oct_unet_graph_capture/_launch     (none: replaces per-call Keras dispatch overhead, evaluation.py:108-135)
- *   oct_unet_forward_mc / oct_mc_update (none: Monte-Carlo dropout prediction; the Dropout(0.5) it keeps on is models/unet.py:130)
- *   oct_unet_forward_tta / oct_tta_update / oct_flip_batch (none: test-time augmentation, the flips of flip_aug at prediction time)
+ *   oct_unet_graph_capture_infer / oct_unet_graph_launch  (none: replaces per-call Keras dispatch overhead, evaluation.py:108-135)
+ *   oct_unet_infer, kind MC / oct_mc_update  (none: Monte-Carlo dropout prediction; the Dropout(0.5) it keeps on is models/unet.py:130)
+ *   oct_unet_infer, kind TTA / oct_tta_update / oct_flip_batch  (none: test-time augmentation, the flips of flip_aug at prediction time)
  *   oct_augment_batch                  BatchGenerator.get_aug_fly/_nofly common/data_generator.py:140-283,
  *                                      flip_aug / add_noise_aug       common/augmentation.py:43-103
  *   oct_pad_batch / oct_crop_batch     (none: Keras raises on a size that is no multiple of 2^pool_layers, in the skip concatenation)
@@ -158,7 +158,7 @@ int oct_unet_loss_bce_dice(oct_unet* h, float smooth, float* out8_dev, oct_strea
  * Defined edge cases: an image without a counted pixel has per-class macro score s/s = 1 (smooth > 0); a batch without
  * one has focal = bce = 0, loss w*0 + (1-w)*0 for smooth > 0 and all-zero gradients; its dice_coef_micro is 0/0 = nan as
  * the reference's formula gives on empty sums, its dice_coef_macro 1 by that metric's own 1e-5 epsilon.
- * A captured graph (oct_unet_graph_capture*) keeps the setting it was captured under.
+ * A captured graph (oct_unet_graph_capture_infer) keeps the setting it was captured under.
  * The reference has no counterpart; the tests compare with a torch-fp64 masked restatement. */
 int oct_unet_set_ignore_label(oct_unet* h, int label);
 /* After training forward + loss_dice: fills the grads buffer with d(loss_scale*loss)/dparams. */
@@ -227,19 +227,6 @@ int oct_opt_step(const oct_opt_desc* desc, float* params_dev, const float* grads
 int oct_unet_set_dropout_step(oct_unet* h, unsigned long long step);
 /* keep-mask (B, H/2^P, W/2^P, start_neurons*2^P) u8 {0,1} that a training forward at the current step uses */
 int oct_unet_dropout_mask(oct_unet* h, int B, unsigned char* mask_dev, oct_stream_t stream);
-
-/* ---- inference hipGraph: capture one forward (training=0) with fixed buffers, then replay ---- */
-int oct_unet_graph_capture(oct_unet* h, const void* x_dev, int x_is_u8, int B, const oct_unet_io* io,
-                           oct_stream_t stream);
-/* The same capture for scans of a size (H, W) that is no multiple of 2^pool_layers, around a handle built at the padded
- * size (cfg.H, cfg.W): oct_pad_batch of x_dev (B,H,W,in_ch) into x_pad_dev (B,cfg.H,cfg.W,in_ch) at (top, left), the forward
- * of x_pad_dev into io_pad (padded-size buffers), and one oct_crop_batch per output that io_crop asks for -- probs and / or
- * argmax, (B,H,W[,n_cls]) -- all inside the one graph that oct_unet_graph_launch replays.  io_pad must hold every output
- * io_crop asks for; labels are not used.  The argument errors of the three calls apply. */
-int oct_unet_graph_capture_padded(oct_unet* h, const void* x_dev, int x_is_u8, int B, int H, int W, int top, int left,
-                                  int pad_mode, float pad_value, void* x_pad_dev, const oct_unet_io* io_pad,
-                                  const oct_unet_io* io_crop, oct_stream_t stream);
-int oct_unet_graph_launch(oct_unet* h, oct_stream_t stream);
 
 /* ---- per-launch profiler: HIP events recorded around every kernel launch, on the launch stream ----
  * begin() arms it; every forward/backward call of this handle made on the calling thread is then recorded;
@@ -313,24 +300,6 @@ size_t oct_mc_workspace_bytes(int B, int H, int W, int n_cls);   /* B*H*W*(n_cls
 int oct_mc_update(const float* probs_dev /* (B,H,W,n_cls) f32 */, int B, int H, int W, int n_cls, int t, int T,
                   void* ws_dev, size_t ws_bytes, const oct_mc_out* out /* read when t == T-1 */, oct_stream_t stream);
 
-/* Inference forward with the bottleneck dropout ON, T times, reduced by oct_mc_update: per-pixel uncertainty of a batch.
- * BN runs from the moving statistics (as training = 0) and the weights are prepared once; the encoder and the bottleneck
- * sit in front of the dropout and are deterministic, so layers [0, k) run ONCE -- k = the up-convolution behind the
- * bottleneck -- and for t = 0..T-1 layers [k, head] run with the dropout stream of step step0 + t on the input of layer k:
- * exactly the keep-mask oct_unet_dropout_mask returns after oct_unet_set_dropout_step(step0 + t), kept values scaled by
- * 1 / (1 - dropout_rate) as in training.  The head writes sample t to probs_scratch_dev and oct_mc_update(t, T) folds it
- * into mc_ws_dev; `out` receives the maps of the T samples.  With dropout_rate == 0 the samples are identical.
- * Works on training and inference handles, f32 and bf16 (cfg.dtype 1).  No statistic rows are written, the moving
- * statistics and parameters are untouched, nothing is saved for a backward, the handle's dropout step is as before the
- * call; a pending Dice sum is dropped (a following oct_unet_loss_dice needs a new forward with io.labels).  Allocates
- * nothing and is asynchronous on `stream`.  NOT for graph capture: the dropout step travels by value in the kernel
- * arguments, so a replay would repeat the captured steps -- which is also why each call is cheap to vary.
- * Errors (negative, oct_last_error(), nothing launched): null handle, x, scratch, workspace or out; B outside
- * 1..max_batch; T outside 1..64; mc_ws_bytes < oct_mc_workspace_bytes(B, H, W, n_cls); overlapping ranges as above. */
-int oct_unet_forward_mc(oct_unet* h, const void* x_dev, int x_is_u8, int B, int T, unsigned long long step0,
-                        float* probs_scratch_dev /* (B,H,W,n_cls) f32 */, void* mc_ws_dev, size_t mc_ws_bytes,
-                        const oct_mc_out* out, oct_stream_t stream);
-
 /* ---- test-time augmentation on device: the softmax outputs of mirrored views of a batch, mirrored back and averaged ----
  * A view code v is in 0..3: bit 0 mirrors columns (xv = W-1-x, "flip_lr"), bit 1 mirrors rows (yv = H-1-y, "flip_ud");
  * 0 identity, 1 flip_lr, 2 flip_ud, 3 flip_both.  A flip is its own inverse.
@@ -359,33 +328,64 @@ int oct_flip_batch(const void* src_dev, int B, int H, int W, int pixel_bytes, in
 int oct_tta_update(const float* probs_dev /* (B,H,W,n_cls) f32 */, int B, int H, int W, int n_cls, int view, int t, int T,
                    void* ws_dev, size_t ws_bytes, const oct_mc_out* out /* read when t == T-1 */, oct_stream_t stream);
 
-/* Inference forward of T views of one batch, reduced by oct_tta_update.  For t = 0..T-1: oct_flip_batch(x_dev, views[t]) into
- * x_view_dev (skipped for view 0: the forward reads x_dev itself), a plain forward (training = 0) of it into
- * probs_scratch_dev, oct_tta_update(views[t], t, T) into ws_dev; `out` receives the maps of the mean prediction.  The
- * weights are prepared once for the T forwards; each forward's probabilities are bit for bit those of oct_unet_forward on
- * the flipped batch.  `views`: HOST array of T codes in 0..3.  x_view_dev: a batch like x_dev (same type and shape); may be
- * NULL if every view is 0.  Works on training and inference handles, f32 and bf16 (cfg.dtype 1).  Leaves the handle as
- * oct_unet_forward_mc does: parameters, moving statistics and the dropout step untouched, a pending Dice sum dropped.
- * Allocates nothing, asynchronous on `stream`, one chain of launches with no second stream -- and deterministic, so unlike
- * oct_unet_forward_mc it CAN be captured:
- *
- * oct_unet_graph_capture_tta records the chain for oct_unet_graph_launch to replay.  x_pad_dev == NULL: (H, W) must be the
- * handle's size and `out_pad` receives the maps (out_crop is not read).  x_pad_dev != NULL: as
- * oct_unet_graph_capture_padded, oct_pad_batch of x_dev (B,H,W,in_ch) into x_pad_dev (B,cfg.H,cfg.W,in_ch) in front, the chain
- * on x_pad_dev into out_pad (padded-size buffers), and one oct_crop_batch per map that out_crop asks for (out_pad must hold
- * it).  The padded batch is THE input: the views are flips of the padded batch, the fold runs at the padded size and the crop
- * comes last, so the result equals oct_unet_forward_tta of a handle of the padded size on the padded batch, cropped.
- * Errors (negative, oct_last_error(), nothing launched): null handle, x, views, scratch, workspace or out; B outside
- * 1..max_batch; T outside 1..4; a view outside 0..3; a flipped view without x_view_dev or with an input pixel that
- * oct_flip_batch does not take (in_ch * element size outside its set); the errors of oct_flip_batch and oct_tta_update;
- * capture: also a default stream, a size other than the handle's without x_pad_dev, the errors of the pad and the crops. */
-int oct_unet_forward_tta(oct_unet* h, const void* x_dev, int x_is_u8, int B, const int* views /* host, T entries */, int T,
-                         void* x_view_dev, float* probs_scratch_dev /* (B,H,W,n_cls) f32 */, void* ws_dev, size_t ws_bytes,
-                         const oct_mc_out* out, oct_stream_t stream);
-int oct_unet_graph_capture_tta(oct_unet* h, const void* x_dev, int x_is_u8, int B, const int* views, int T, void* x_view_dev,
-                               float* probs_scratch_dev, void* ws_dev, size_t ws_bytes, int H, int W, int top, int left,
-                               int pad_mode, float pad_value, void* x_pad_dev, const oct_mc_out* out_pad,
-                               const oct_mc_out* out_crop, oct_stream_t stream);
+/* ---- inference: one chain of launches, described by oct_infer ----
+ * Three independent choices:
+ *   kind       OCT_INFER_PLAIN  one forward (training = 0).  The head writes out.mean_probs (its probabilities) and out.argmax
+ *                               itself: no scratch, no reduction launch; out.entropy and out.mutual_info must be NULL.
+ *              OCT_INFER_MC     Monte-Carlo dropout: the encoder and the bottleneck sit in front of the dropout and are
+ *                               deterministic, so layers [0, k) run ONCE -- k = the up-convolution behind the bottleneck -- and
+ *                               for t = 0..T-1 layers [k, head] run with the dropout stream of step step0 + t on the input of
+ *                               layer k: exactly the keep-mask oct_unet_dropout_mask returns after oct_unet_set_dropout_step(
+ *                               step0 + t), kept values scaled by 1 / (1 - dropout_rate) as in training.  The head writes
+ *                               sample t to probs_scratch_dev and oct_mc_update(t, T) folds it into ws_dev.  T in 1..64.  With
+ *                               dropout_rate == 0 the samples are identical.
+ *              OCT_INFER_TTA    for t = 0..T-1: oct_flip_batch(input, views[t]) into x_view_dev (skipped for view 0: the forward
+ *                               reads the input itself), a plain forward of it into probs_scratch_dev, oct_tta_update(views[t], t,
+ *                               T) into ws_dev.  T in 1..4, views in 0..3.  x_view_dev: a batch like the input (same type, the
+ *                               handle's size); may be NULL if every view is 0.  Each forward's probabilities are bit for bit
+ *                               those of oct_unet_forward on the flipped batch.
+ *              For MC and TTA `out` receives the maps of the T samples / of the mean prediction, ws_bytes >=
+ *              oct_mc_workspace_bytes(B, cfg.H, cfg.W, n_cls), and at least one map is asked for.
+ *   padding    x_pad_dev == NULL: x_dev is (B,cfg.H,cfg.W,in_ch); (H, W) must be the handle's size; out_crop is not read.
+ *              x_pad_dev != NULL: x_dev is (B,H,W,in_ch), a size that is no multiple of 2^pool_layers, around a handle built at
+ *              the padded size: oct_pad_batch of x_dev into x_pad_dev (B,cfg.H,cfg.W,in_ch) at (top, left) in front, the chain on
+ *              x_pad_dev into `out` (padded-size buffers), and one oct_crop_batch per map that out_crop asks for, (B,H,W[,n_cls]);
+ *              `out` must hold it.  The padded batch is THE input: the views are flips of the padded batch, the fold runs at the
+ *              padded size and the crop comes last, so the result equals the unpadded chain of that handle on the padded batch,
+ *              cropped.
+ *   execution  oct_unet_infer runs the chain on `stream`; oct_unet_graph_capture_infer records the same launches into the
+ *              handle's graph (replacing an earlier one) for oct_unet_graph_launch to replay -- one stream, no forked branch;
+ *              it needs a non-default stream.  An MC chain is NOT captured (refused): the dropout step travels by value in
+ *              the kernel arguments, so a replay would repeat the captured steps -- which is also why each call is cheap to vary.
+ * Every kind prepares the weights once, runs BN from the moving statistics, works on training and inference handles, f32 and
+ * bf16 (cfg.dtype 1), allocates nothing and is asynchronous.  No statistic rows are written, parameters, moving statistics
+ * and the dropout step are as before the call, nothing is saved for a backward.  MC and TTA drop a pending Dice sum (a following
+ * oct_unet_loss_dice needs a new oct_unet_forward with io.labels); PLAIN leaves the handle as oct_unet_forward(training = 0)
+ * without labels does.  oct_unet_forward stays the training and labelled forward.
+ * Errors (negative, oct_last_error(), nothing launched): null handle, descriptor or input; a kind outside the three; B outside
+ * 1..max_batch; a size other than the handle's without x_pad_dev; PLAIN with entropy or mutual_info; MC / TTA: null scratch or
+ * workspace, no map asked for, T out of range, a view outside 0..3, a flipped view without x_view_dev or with an input pixel
+ * that oct_flip_batch does not take (in_ch * element size outside its set), the errors of oct_flip_batch, oct_mc_update and
+ * oct_tta_update (workspace too small, overlapping ranges, ...); padded: the errors of oct_pad_batch, out_crop asking for a map
+ * that `out` does not hold or that overlaps it; capture: also a default stream. */
+enum { OCT_INFER_PLAIN = 0, OCT_INFER_MC = 1, OCT_INFER_TTA = 2 };
+typedef struct oct_infer {
+    const void* x_dev;            /* the batch, u8 (x_is_u8) or f32 in [0,1]                          */
+    int x_is_u8, B;
+    int kind, T;                  /* OCT_INFER_*; samples (MC) or views (TTA), ignored for PLAIN     */
+    unsigned long long step0;     /* MC: dropout step of sample 0                                     */
+    int views[4];                 /* TTA: T view codes                                                */
+    void* x_view_dev;             /* TTA scratch: the flipped input                                   */
+    float* probs_scratch_dev;     /* MC / TTA scratch: (B,cfg.H,cfg.W,n_cls) f32, one sample          */
+    void* ws_dev; size_t ws_bytes;   /* MC / TTA: the reduction workspace                             */
+    int H, W, top, left;          /* size of x_dev and its place inside the handle's size            */
+    int pad_mode; float pad_value;   /* OCT_PAD_*, as oct_pad_batch (declared below)                  */
+    void* x_pad_dev;              /* NULL: no padding                                                 */
+    oct_mc_out out, out_crop;     /* maps at the handle's size; at (H, W), read only when padding    */
+} oct_infer;
+int oct_unet_infer(oct_unet* h, const oct_infer* d, oct_stream_t stream);
+int oct_unet_graph_capture_infer(oct_unet* h, const oct_infer* d, oct_stream_t stream);
+int oct_unet_graph_launch(oct_unet* h, oct_stream_t stream);
 
 /* ---- evaluation metrics on device: average surface distance and robust Hausdorff distance of every foreground class
  * (reference evaluation/evaluation.py:207-262 -> common/custom_metrics.py:103-119 -> google-deepmind/surface-distance

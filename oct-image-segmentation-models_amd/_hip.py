@@ -72,6 +72,15 @@ class McOut(C.Structure):
     _fields_ = [("mean_probs", C.c_void_p), ("argmax", C.c_void_p), ("entropy", C.c_void_p), ("mutual_info", C.c_void_p)]
 
 
+class Infer(C.Structure):
+    """``oct_infer``: one inference chain -- kind (plain, MC, TTA), padding, buffers -- for ``oct_unet_infer`` / ``oct_unet_graph_capture_infer``."""
+    _fields_ = [("x_dev", C.c_void_p), ("x_is_u8", C.c_int), ("B", C.c_int), ("kind", C.c_int), ("T", C.c_int),
+                ("step0", C.c_ulonglong), ("views", C.c_int * 4), ("x_view_dev", C.c_void_p), ("probs_scratch_dev", C.c_void_p),
+                ("ws_dev", C.c_void_p), ("ws_bytes", C.c_size_t), ("H", C.c_int), ("W", C.c_int), ("top", C.c_int), ("left", C.c_int),
+                ("pad_mode", C.c_int), ("pad_value", C.c_float), ("x_pad_dev", C.c_void_p), ("out", McOut), ("out_crop", McOut)]
+
+
+INFER_PLAIN, INFER_MC, INFER_TTA = range(3)
 MC_MAX_SAMPLES = 64
 
 # oct_pad_batch modes (include/oct_unet.h), by the public pad_mode names
@@ -110,9 +119,8 @@ SYMBOLS = [
                                C.c_size_t, C.c_void_p, C.c_void_p]),
     ("oct_unet_set_dropout_step", C.c_int, [C.c_void_p, C.c_ulonglong]),
     ("oct_unet_dropout_mask", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
-    ("oct_unet_graph_capture", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _P(UNetIO), C.c_void_p]),
-    ("oct_unet_graph_capture_padded", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                C.c_float, C.c_void_p, _P(UNetIO), _P(UNetIO), C.c_void_p]),
+    ("oct_unet_infer", C.c_int, [C.c_void_p, _P(Infer), C.c_void_p]),
+    ("oct_unet_graph_capture_infer", C.c_int, [C.c_void_p, _P(Infer), C.c_void_p]),
     ("oct_unet_graph_launch", C.c_int, [C.c_void_p, C.c_void_p]),
     ("oct_unet_profile_begin", C.c_int, [C.c_void_p]),
     ("oct_unet_profile_end", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _P(C.c_int)]),
@@ -121,16 +129,9 @@ SYMBOLS = [
     ("oct_mc_workspace_bytes", C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     ("oct_mc_update", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                 _P(McOut), C.c_void_p]),
-    ("oct_unet_forward_mc", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_ulonglong, C.c_void_p, C.c_void_p,
-                                      C.c_size_t, _P(McOut), C.c_void_p]),
     ("oct_flip_batch", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     ("oct_tta_update", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                  _P(McOut), C.c_void_p]),
-    ("oct_unet_forward_tta", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _P(C.c_int), C.c_int, C.c_void_p, C.c_void_p,
-                                       C.c_void_p, C.c_size_t, _P(McOut), C.c_void_p]),
-    ("oct_unet_graph_capture_tta", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _P(C.c_int), C.c_int, C.c_void_p, C.c_void_p,
-                                             C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
-                                             C.c_void_p, _P(McOut), _P(McOut), C.c_void_p]),
     ("oct_surface_workspace_bytes", C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     ("oct_surface_distances", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
                                         C.c_double, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),

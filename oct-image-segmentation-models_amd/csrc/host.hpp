@@ -170,12 +170,12 @@ int launch_head_fwd_wide(const oct::HeadFwdArgs& a, int C, int cin, int B, hipSt
 int launch_head_bwd_wide(const oct::HeadBwdArgs& a, int C, int cin, int B, hipStream_t s);
 
 // Monte-Carlo dropout reduction (tu_mc.hip): every argument error of oct_mc_update(probs, ..., t, T, ws, ws_bytes, out), with
-// nothing launched -- oct_unet_forward_mc asks about its last sample before its first launch
+// nothing launched -- oct_unet_infer (kind MC) asks about its last sample before its first launch
 int mc_validate(const float* probs, int B, int H, int W, int n_cls, int t, int T, const void* ws, size_t ws_bytes,
                 const oct_mc_out* out);
 
 // Test-time augmentation (tu_tta.hip): every argument error of oct_flip_batch / oct_tta_update, with nothing launched --
-// oct_unet_forward_tta asks about all of its views before its first launch.  *bytes (optional): the size of either buffer
+// oct_unet_infer (kind TTA) asks about all of its views before its first launch.  *bytes (optional): the size of either buffer
 int flip_validate(const void* src, int B, int H, int W, int pixel_bytes, int view, const void* dst, size_t* bytes);
 int tta_validate(const float* probs, int B, int H, int W, int n_cls, int view, int t, int T, const void* ws, size_t ws_bytes,
                  const oct_mc_out* out);

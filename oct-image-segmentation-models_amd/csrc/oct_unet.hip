@@ -1172,74 +1172,101 @@ int oct_unet_forward(oct_unet* h, const void* x, int x_is_u8, int B, int trainin
     return 0;
 }
 
-int oct_unet_forward_mc(oct_unet* h, const void* x, int x_is_u8, int B, int T, unsigned long long step0, float* probs_scratch,
-                        void* mc_ws, size_t mc_ws_bytes, const oct_mc_out* out, oct_stream_t stream) {
-    if (!h || !x || !probs_scratch || !mc_ws || !out) return fail(-1, "forward_mc: null handle, input, scratch, workspace or out");
-    if (B < 1 || B > h->cfg.max_batch) return fail(-1, "B out of range (1..max_batch)");
-    if (T < 1 || T > 64) return fail(-1, "forward_mc: T out of range (1..64)");
+// ---- inference: ONE chain described by oct_infer, run eagerly (oct_unet_infer) or recorded (oct_unet_graph_capture_infer) ----
+// the four maps of an oct_mc_out with the bytes of a pixel of each
+struct MapSet { void* p[4]; int pb[4]; };
+static MapSet map_set(const oct_mc_out& o, int n_cls) {
+    return {{o.mean_probs, o.argmax, o.entropy, o.mutual_info}, {n_cls * (int)sizeof(float), 1, (int)sizeof(float), (int)sizeof(float)}};
+}
+
+// What the chain's launches would refuse, with nothing launched.  (oct_pad_batch raises its own errors: it is the first launch.)
+static int infer_check(oct_unet* h, const oct_infer* d) {
+    if (!h || !d) return fail(-1, "infer: null handle or descriptor");
+    if (d->kind != OCT_INFER_PLAIN && d->kind != OCT_INFER_MC && d->kind != OCT_INFER_TTA)
+        return fail(-1, "infer: unknown kind " + std::to_string(d->kind));
     const oct_unet_cfg& c = h->cfg;
-    // what the T reductions would refuse (the last one reads `out`), before anything is launched
-    if (int rc = mc_validate(probs_scratch, B, c.H, c.W, c.n_cls, T - 1, T, mc_ws, mc_ws_bytes, out)) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    t_prof = &h->prof;
-    const int nl = (int)h->plan.L.size(), k = first_dec_layer(h->plan);
+    const oct_mc_out& o = d->out;
+    const bool plain = d->kind == OCT_INFER_PLAIN, padded = d->x_pad_dev != nullptr;
+    if (!d->x_dev || (!plain && (!d->probs_scratch_dev || !d->ws_dev || !(o.mean_probs || o.argmax || o.entropy || o.mutual_info))))
+        return fail(-1, "infer: null input, scratch, workspace or out (no map asked for)");
+    if (d->B < 1 || d->B > c.max_batch) return fail(-1, "B out of range (1..max_batch)");
+    if (!padded && (d->H != c.H || d->W != c.W)) return fail(-1, "infer: a size other than the handle's needs x_pad_dev");
+    if (plain && (o.entropy || o.mutual_info)) return fail(-1, "infer: a plain forward has no entropy or mutual_info");
+    const int T = d->T;
+    if (d->kind == OCT_INFER_MC) {      // what the T reductions would refuse: the last one reads `out`
+        if (T < 1 || T > 64) return fail(-1, "infer: T out of range (1..64)");
+        if (int rc = mc_validate(d->probs_scratch_dev, d->B, c.H, c.W, c.n_cls, T - 1, T, d->ws_dev, d->ws_bytes, &o)) return rc;
+    } else if (d->kind == OCT_INFER_TTA) {
+        if (T < 1 || T > 4) return fail(-1, "infer: T out of range (1..4)");
+        const void* x = padded ? d->x_pad_dev : d->x_dev;      // THE input of the views: the padded batch where there is one
+        const int64_t pb = (int64_t)c.in_ch * (d->x_is_u8 ? 1 : 4);
+        for (int t = 0; t < T; ++t) {
+            const int v = d->views[t];
+            if (v < 0 || v > 3) return fail(-1, "infer: view " + std::to_string(v) + " outside 0..3");
+            if (!v) continue;
+            if (!d->x_view_dev) return fail(-1, "infer: a flipped view needs x_view_dev");
+            if (pb > 32) return fail(-1, "infer: a pixel of the input has more than 32 bytes");
+            if (int rc = flip_validate(x, d->B, c.H, c.W, (int)pb, v, d->x_view_dev, nullptr)) return rc;
+        }
+        if (int rc = tta_validate(d->probs_scratch_dev, d->B, c.H, c.W, c.n_cls, d->views[T - 1], T - 1, T, d->ws_dev, d->ws_bytes, &o))
+            return rc;
+    }
+    if (!padded) return 0;
+    const MapSet from = map_set(o, c.n_cls), to = map_set(d->out_crop, c.n_cls);
+    for (int i = 0; i < 4; ++i) {
+        if (!to.p[i]) continue;
+        if (!from.p[i]) return fail(-1, "infer: out_crop asks for a map that out does not hold");
+        // the one error of oct_crop_batch that the pad in front does not raise first (a size that does not fit is the pad's)
+        const uintptr_t a = (uintptr_t)from.p[i], b = (uintptr_t)to.p[i];
+        const size_t px = (size_t)d->B * from.pb[i], na = px * c.H * c.W, nb = px * std::max(d->H, 0) * std::max(d->W, 0);
+        if (a < b + nb && b < a + na) return fail(-1, "infer: a map of out_crop overlaps its source in out");
+    }
+    return 0;
+}
+
+// The chain on stream s: the pad; one weight preparation; per sample or view the flip (unless identity), the conv blocks -- for
+// MC only those behind the dropout, the encoder and the bottleneck having run once --, the head and the fold; the crops.
+static int infer_chain(oct_unet* h, const oct_infer& d, hipStream_t s) {
+    const oct_unet_cfg& c = h->cfg;
+    const bool plain = d.kind == OCT_INFER_PLAIN, mc = d.kind == OCT_INFER_MC;
+    const int nl = (int)h->plan.L.size(), B = d.B, u8 = d.x_is_u8, T = plain ? 1 : d.T;
+    const int k = mc ? first_dec_layer(h->plan) : 0;           // the up-convolution behind the bottleneck: the dropout sits on its input
+    const void* x = d.x_dev;
+    int rc = 0;
+    if (d.x_pad_dev) {
+        rc = oct_pad_batch(x, u8, B, d.H, d.W, c.in_ch, c.H, c.W, d.top, d.left, d.pad_mode, d.pad_value, d.x_pad_dev, s);
+        x = d.x_pad_dev;
+    }
+    oct_unet_io io{};                                           // PLAIN: the head writes the caller's maps itself
+    io.probs = plain ? d.out.mean_probs : d.probs_scratch_dev; io.argmax = plain ? d.out.argmax : nullptr;
     const unsigned long long step_saved = h->drop_step;
-    const int advance_saved = h->drop_advance;
-    oct_unet_io io{}; io.probs = probs_scratch;
-    int rc = forward_prepare(h, 0, false, s);
-    if (!rc) rc = forward_stages(h, x, x_is_u8, B, 0, false, false, 0, k, s);       // encoder + bottleneck: once
+    if (!rc) rc = forward_prepare(h, 0, false, s);
+    if (!rc) rc = forward_stages(h, x, u8, B, 0, false, false, 0, k, s);
     for (int t = 0; t < T && !rc; ++t) {
-        h->drop_step = step0 + (unsigned long long)t;                               // by value into layer k's kernel arguments
-        rc = forward_stages(h, x, x_is_u8, B, 0, true, false, k, nl - 1, s);
-        if (!rc) rc = forward_head(h, B, &io, s);
-        if (!rc) rc = oct_mc_update(probs_scratch, B, c.H, c.W, c.n_cls, t, T, mc_ws, mc_ws_bytes, out, stream);
-    }
-    h->drop_step = step_saved; h->drop_advance = advance_saved;
-    h->have_dice = 0; h->dice_final = 0;
-    return rc;
-}
-
-// what oct_unet_forward_tta's launches would refuse, with nothing launched
-static int tta_check(oct_unet* h, const void* x, int x_is_u8, int B, const int* views, int T, const void* x_view,
-                     const float* probs_scratch, const void* ws, size_t ws_bytes, const oct_mc_out* out) {
-    if (!h || !x || !views || !probs_scratch || !ws || !out) return fail(-1, "forward_tta: null handle, input, views, scratch, workspace or out");
-    if (B < 1 || B > h->cfg.max_batch) return fail(-1, "B out of range (1..max_batch)");
-    if (T < 1 || T > 4) return fail(-1, "forward_tta: T out of range (1..4)");
-    const oct_unet_cfg& c = h->cfg;
-    const int64_t pb = (int64_t)c.in_ch * (x_is_u8 ? 1 : 4);
-    for (int t = 0; t < T; ++t) {
-        if (views[t] < 0 || views[t] > 3) return fail(-1, "forward_tta: view " + std::to_string(views[t]) + " outside 0..3");
-        if (!views[t]) continue;
-        if (!x_view) return fail(-1, "forward_tta: a flipped view needs x_view_dev");
-        if (pb > 32) return fail(-1, "forward_tta: a pixel of the input has more than 32 bytes");
-        if (int rc = flip_validate(x, B, c.H, c.W, (int)pb, views[t], x_view, nullptr)) return rc;
-    }
-    return tta_validate(probs_scratch, B, c.H, c.W, c.n_cls, views[T - 1], T - 1, T, ws, ws_bytes, out);
-}
-
-// the T-view chain on stream s: one weight preparation, then per view the flip (unless identity), the forward and the fold
-static int tta_chain(oct_unet* h, const void* x, int x_is_u8, int B, const int* views, int T, void* x_view, float* probs_scratch,
-                     void* ws, size_t ws_bytes, const oct_mc_out* out, hipStream_t s) {
-    const oct_unet_cfg& c = h->cfg;
-    const int nl = (int)h->plan.L.size(), pb = c.in_ch * (x_is_u8 ? 1 : 4);
-    oct_unet_io io{}; io.probs = probs_scratch;
-    int rc = forward_prepare(h, 0, false, s);
-    for (int t = 0; t < T && !rc; ++t) {
+        const int v = plain || mc ? 0 : d.views[t];
         const void* xt = x;
-        if (views[t]) { rc = oct_flip_batch(x, B, c.H, c.W, pb, views[t], x_view, s); xt = x_view; }
-        if (!rc) rc = forward_stages(h, xt, x_is_u8, B, 0, false, false, 0, nl - 1, s);
+        if (v) { rc = oct_flip_batch(x, B, c.H, c.W, c.in_ch * (u8 ? 1 : 4), v, d.x_view_dev, s); xt = d.x_view_dev; }
+        if (mc) h->drop_step = d.step0 + (unsigned long long)t;                     // by value into layer k's kernel arguments
+        if (!rc) rc = forward_stages(h, xt, u8, B, 0, mc, false, k, nl - 1, s);
         if (!rc) rc = forward_head(h, B, &io, s);
-        if (!rc) rc = oct_tta_update(probs_scratch, B, c.H, c.W, c.n_cls, views[t], t, T, ws, ws_bytes, out, s);
+        if (!rc && mc) rc = oct_mc_update(io.probs, B, c.H, c.W, c.n_cls, t, T, d.ws_dev, d.ws_bytes, &d.out, s);
+        if (!rc && !mc && !plain) rc = oct_tta_update(io.probs, B, c.H, c.W, c.n_cls, v, t, T, d.ws_dev, d.ws_bytes, &d.out, s);
     }
-    h->have_dice = 0; h->dice_final = 0;
+    h->drop_step = step_saved;
+    if (!plain) { h->have_dice = 0; h->dice_final = 0; }       // a pending Dice sum is dropped
+    else if (!rc) { h->last_B = B; h->last_training = 0; }     // as forward_impl leaves the handle
+    if (d.x_pad_dev) {
+        const MapSet from = map_set(d.out, c.n_cls), to = map_set(d.out_crop, c.n_cls);
+        for (int i = 0; i < 4 && !rc; ++i)
+            if (to.p[i]) rc = oct_crop_batch(from.p[i], B, c.H, c.W, to.pb[i], d.H, d.W, d.top, d.left, to.p[i], s);
+    }
     return rc;
 }
 
-int oct_unet_forward_tta(oct_unet* h, const void* x, int x_is_u8, int B, const int* views, int T, void* x_view,
-                         float* probs_scratch, void* ws, size_t ws_bytes, const oct_mc_out* out, oct_stream_t stream) {
-    if (int rc = tta_check(h, x, x_is_u8, B, views, T, x_view, probs_scratch, ws, ws_bytes, out)) return rc;
+int oct_unet_infer(oct_unet* h, const oct_infer* d, oct_stream_t stream) {
+    if (int rc = infer_check(h, d)) return rc;
     t_prof = &h->prof;
-    return tta_chain(h, x, x_is_u8, B, views, T, x_view, probs_scratch, ws, ws_bytes, out, (hipStream_t)stream);
+    return infer_chain(h, *d, (hipStream_t)stream);
 }
 
 // Dice (and focal) loss of the last forward: out holds n_user floats
@@ -1335,82 +1362,19 @@ int oct_unet_dropout_mask(oct_unet* h, int B, unsigned char* mask, oct_stream_t 
     return 0;
 }
 
-int oct_unet_graph_capture(oct_unet* h, const void* x, int x_is_u8, int B, const oct_unet_io* io, oct_stream_t stream) {
-    if (!h || !x) return fail(-1, "null handle or input");
-    if (B < 1 || B > h->cfg.max_batch) return fail(-1, "B out of range (1..max_batch)");
+int oct_unet_graph_capture_infer(oct_unet* h, const oct_infer* d, oct_stream_t stream) {
+    if (int rc = infer_check(h, d)) return rc;
+    if (d->kind == OCT_INFER_MC)
+        return fail(-1, "graph_capture_infer: a Monte-Carlo chain cannot be captured: the dropout step travels by value in the "
+                        "kernel arguments, so a replay would repeat the captured steps");
     hipStream_t s = (hipStream_t)stream;
     if (!s) return fail(-1, "graph capture needs a non-default stream");
     if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
     if (h->graph) { (void)hipGraphDestroy(h->graph); h->graph = nullptr; }
     t_prof = nullptr;  // no event records inside a capture
     HIP_OK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    const int rc = forward_impl(h, x, x_is_u8, B, 0, io, s);
-    hipError_t e = hipStreamEndCapture(s, &h->graph);
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(-5, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-    HIP_OK(hipGraphInstantiate(&h->graph_exec, h->graph, nullptr, nullptr, 0));
-    return 0;
-}
-
-int oct_unet_graph_capture_padded(oct_unet* h, const void* x, int x_is_u8, int B, int H, int W, int top, int left, int pad_mode,
-                                  float pad_value, void* x_pad, const oct_unet_io* io_pad, const oct_unet_io* io_crop,
-                                  oct_stream_t stream) {
-    if (!h || !x || !x_pad || !io_pad || !io_crop) return fail(-1, "null handle, input, padded input or io");
-    if (B < 1 || B > h->cfg.max_batch) return fail(-1, "B out of range (1..max_batch)");
-    if ((io_crop->probs && !io_pad->probs) || (io_crop->argmax && !io_pad->argmax))
-        return fail(-1, "graph_capture_padded: io_crop asks for an output that io_pad does not hold");
-    hipStream_t s = (hipStream_t)stream;
-    if (!s) return fail(-1, "graph capture needs a non-default stream");
-    if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
-    if (h->graph) { (void)hipGraphDestroy(h->graph); h->graph = nullptr; }
-    t_prof = nullptr;  // no event records inside a capture
-    const int Hp = h->cfg.H, Wp = h->cfg.W;
-    oct_unet_io io = *io_pad;
-    io.labels = nullptr;
-    HIP_OK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    int rc = oct_pad_batch(x, x_is_u8, B, H, W, h->cfg.in_ch, Hp, Wp, top, left, pad_mode, pad_value, x_pad, s);
-    if (!rc) rc = forward_impl(h, x_pad, x_is_u8, B, 0, &io, s);
-    if (!rc && io_crop->probs)
-        rc = oct_crop_batch(io.probs, B, Hp, Wp, h->cfg.n_cls * (int)sizeof(float), H, W, top, left, io_crop->probs, s);
-    if (!rc && io_crop->argmax) rc = oct_crop_batch(io.argmax, B, Hp, Wp, 1, H, W, top, left, io_crop->argmax, s);
-    const std::string msg = rc ? oct_last_error() : "";
-    hipError_t e = hipStreamEndCapture(s, &h->graph);
-    if (rc) return fail(rc, msg);
-    if (e != hipSuccess) return fail(-5, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-    HIP_OK(hipGraphInstantiate(&h->graph_exec, h->graph, nullptr, nullptr, 0));
-    return 0;
-}
-
-int oct_unet_graph_capture_tta(oct_unet* h, const void* x, int x_is_u8, int B, const int* views, int T, void* x_view,
-                               float* probs_scratch, void* ws, size_t ws_bytes, int H, int W, int top, int left, int pad_mode,
-                               float pad_value, void* x_pad, const oct_mc_out* out_pad, const oct_mc_out* out_crop,
-                               oct_stream_t stream) {
-    if (!h) return fail(-1, "graph_capture_tta: null handle");
-    const int Hp = h->cfg.H, Wp = h->cfg.W, nc = h->cfg.n_cls;
-    const void* xin = x_pad ? x_pad : x;                       // THE input of the views: the padded batch where there is one
-    if (int rc = tta_check(h, x ? xin : nullptr, x_is_u8, B, views, T, x_view, probs_scratch, ws, ws_bytes, out_pad)) return rc;
-    if (!x_pad && (H != Hp || W != Wp)) return fail(-1, "graph_capture_tta: a size other than the handle's needs x_pad_dev");
-    if (x_pad && !out_crop) return fail(-1, "graph_capture_tta: null out_crop beside x_pad_dev");
-    if (x_pad && ((out_crop->mean_probs && !out_pad->mean_probs) || (out_crop->argmax && !out_pad->argmax) ||
-                  (out_crop->entropy && !out_pad->entropy) || (out_crop->mutual_info && !out_pad->mutual_info)))
-        return fail(-1, "graph_capture_tta: out_crop asks for a map that out_pad does not hold");
-    hipStream_t s = (hipStream_t)stream;
-    if (!s) return fail(-1, "graph capture needs a non-default stream");
-    if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
-    if (h->graph) { (void)hipGraphDestroy(h->graph); h->graph = nullptr; }
-    t_prof = nullptr;  // no event records inside a capture
-    HIP_OK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    int rc = 0;
-    if (x_pad) rc = oct_pad_batch(x, x_is_u8, B, H, W, h->cfg.in_ch, Hp, Wp, top, left, pad_mode, pad_value, x_pad, s);
-    if (!rc) rc = tta_chain(h, xin, x_is_u8, B, views, T, x_view, probs_scratch, ws, ws_bytes, out_pad, s);
-    if (x_pad) {
-        const void* from[4] = {out_pad->mean_probs, out_pad->argmax, out_pad->entropy, out_pad->mutual_info};
-        void* to[4] = {out_crop->mean_probs, out_crop->argmax, out_crop->entropy, out_crop->mutual_info};
-        const int pb[4] = {nc * (int)sizeof(float), 1, (int)sizeof(float), (int)sizeof(float)};
-        for (int i = 0; i < 4 && !rc; ++i)
-            if (to[i]) rc = oct_crop_batch(from[i], B, Hp, Wp, pb[i], H, W, top, left, to[i], s);
-    }
-    const std::string msg = rc ? oct_last_error() : "";
+    const int rc = infer_chain(h, *d, s);
+    const std::string msg = rc ? oct_last_error() : "";        // the body's message, not that of the capture's end
     hipError_t e = hipStreamEndCapture(s, &h->graph);
     if (rc) return fail(rc, msg);
     if (e != hipSuccess) return fail(-5, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));

@@ -31,7 +31,7 @@ void mc_launch(const McArgs& a, size_t items, unsigned grid, bool first, bool la
 
 namespace octh {
 
-// every argument error of oct_mc_update, without launching: oct_unet_forward_mc asks before its first launch
+// every argument error of oct_mc_update, without launching: oct_unet_infer asks before its first launch
 int mc_validate(const float* probs, int B, int H, int W, int n_cls, int t, int T, const void* ws, size_t ws_bytes,
                 const oct_mc_out* out) {
     if (!probs || !ws) return fail(-1, "mc_update: null pointer");

@@ -47,7 +47,7 @@ int flip_validate(const void* src, int B, int H, int W, int pb, int view, const 
     return 0;
 }
 
-// every argument error of oct_tta_update, without launching: oct_unet_forward_tta asks before its first launch
+// every argument error of oct_tta_update, without launching: oct_unet_infer asks before its first launch
 int tta_validate(const float* probs, int B, int H, int W, int n_cls, int view, int t, int T, const void* ws, size_t ws_bytes,
                  const oct_mc_out* out) {
     if (view < 0 || view > 3) return fail(-1, "tta_update: view must be in 0..3 (bit 0 mirrors columns, bit 1 rows), not " + std::to_string(view));

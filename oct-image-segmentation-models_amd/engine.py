@@ -115,7 +115,7 @@ class UNetEngine:
         self.opt_step = 0
         # kept alive: the tensors an in-flight launch and the captured graph refer to, the event of set_tail_event
         self._keep, self._graph_keep, self._tail_event = [], [], None
-        self._mc: Dict[int, dict] = {}  # forward_mc's buffers per batch size
+        self._mc: Dict[int, dict] = {}  # infer's buffer set per batch size
         self._pad_bufs, self._wver = {}, -1  # its Model's: the padded pair per (batch size, image type); the version of the weights held
         # the loss state: what the set_* calls last selected (set_focal_dice's device buffer and parameters by value too); select_loss's kind
         self.ignore_label, self._focal_active, self._bce_active = None, False, False
@@ -145,7 +145,7 @@ class UNetEngine:
         _hip.call(name, self.device, self._h, *args)
 
     def _check_x(self, x: torch.Tensor, any_size: bool = False):
-        # uint8: raw scans; float32: already / 255; of the engine's size (any_size: graph_capture_padded's input)
+        # uint8: raw scans; float32: already / 255; of the engine's size (any_size: the input of a padded infer)
         _hip.expect(x, "input", device=self.device, dtype=(torch.uint8, torch.float32),
                     shape=(None,) + ((None, None) if any_size else (self.cfg.H, self.cfg.W)) + (self.cfg.in_ch,))
         if not 1 <= x.shape[0] <= self.cfg.max_batch:
@@ -154,8 +154,8 @@ class UNetEngine:
     def _check_labels(self, labels: torch.Tensor, B: int):
         _hip.expect(labels, "labels (B,H,W[,1])", device=self.device, dtype=torch.uint8, numel=B * self.cfg.H * self.cfg.W)
 
-    def _io(self, B, labels, want_probs, want_argmax, probs_out=None, argmax_out=None, hw=None):
-        H, W = hw or (self.cfg.H, self.cfg.W)
+    def _io(self, B, labels, want_probs, want_argmax, probs_out=None, argmax_out=None):
+        H, W = self.cfg.H, self.cfg.W
         probs = am = None
         if want_probs:
             probs = probs_out if probs_out is not None else torch.empty((B, H, W, self.cfg.n_cls), dtype=torch.float32, device=self.device)
@@ -358,38 +358,135 @@ class UNetEngine:
         self._call("oct_unet_dropout_mask", B, m.data_ptr(), self._stream())
         return m
 
-    # ---- Monte-Carlo dropout: per-pixel uncertainty ---------------------------------------------------
+    # ---- inference: one chain -- plain, Monte-Carlo dropout or test-time augmentation; padded or not; eager or captured ----
+    _MAPS = ("mean_probs", "argmax", "entropy", "mutual_info")
+
+    def _buf(self, B: int, key, shape, dtype) -> torch.Tensor:
+        """Tensor ``key`` of the buffer set of batch size ``B``: made at its first use, kept."""
+        b = self._mc.setdefault(B, {})
+        if key not in b:
+            b[key] = torch.empty(shape, dtype=dtype, device=self.device)
+        return b[key]
+
+    def _map(self, B: int, k: str, hw=None) -> torch.Tensor:
+        """Map ``k`` of ``_MAPS`` in the buffer set: at the engine's size, or the cropped one of true size ``hw``."""
+        H, W = hw or (self.cfg.H, self.cfg.W)
+        return self._buf(B, k if hw is None else (k, H, W), (B, H, W) + ((self.cfg.n_cls,) if k == "mean_probs" else ()),
+                         torch.uint8 if k == "argmax" else torch.float32)
+
     def _mc_buffers(self, B: int) -> dict:
-        """Scratch probabilities, reduction workspace and output maps of ``forward_mc`` for batch ``B``: made once, kept."""
-        bufs = self._mc
-        if B not in bufs:
-            H, W, Cn = self.cfg.H, self.cfg.W, self.cfg.n_cls
-            f32 = dict(dtype=torch.float32, device=self.device)
-            bufs[B] = dict(
-                scratch=torch.empty((B, H, W, Cn), **f32),
-                ws=torch.empty(int(_hip.lib().oct_mc_workspace_bytes(B, H, W, Cn)), dtype=torch.uint8, device=self.device),
-                mean_probs=torch.empty((B, H, W, Cn), **f32), argmax=torch.empty((B, H, W), dtype=torch.uint8, device=self.device),
-                entropy=torch.empty((B, H, W), **f32), mutual_info=torch.empty((B, H, W), **f32))
-        return bufs[B]
+        """The buffer set of batch size ``B`` with what every Monte-Carlo / TTA chain needs: scratch probabilities, reduction
+        workspace and the four maps at the engine's size."""
+        H, W, Cn = self.cfg.H, self.cfg.W, self.cfg.n_cls
+        self._buf(B, "scratch", (B, H, W, Cn), torch.float32)
+        self._buf(B, "ws", (int(_hip.lib().oct_mc_workspace_bytes(B, H, W, Cn)),), torch.uint8)
+        for k in self._MAPS:
+            self._map(B, k)
+        return self._mc[B]
+
+    def _tta_buffers(self, B: int, x: torch.Tensor) -> dict:
+        """``_mc_buffers`` plus ``x_view``, the flipped input of a TTA chain for the input's type."""
+        b = self._mc_buffers(B)
+        return dict(b, x_view=self._buf(B, "x_view_u8" if x.dtype == torch.uint8 else "x_view_f32",
+                                        (B, self.cfg.H, self.cfg.W, self.cfg.in_ch), x.dtype))
+
+    def infer(self, x: torch.Tensor, *, mc=None, tta=None, pad=None, want_probs: bool, want_argmax: bool,
+              capture: bool = False) -> Dict[str, torch.Tensor]:
+        """THE inference entry (``oct_unet_infer`` / ``oct_unet_graph_capture_infer``): one chain of launches on the current stream.
+
+        * kind -- neither ``mc`` nor ``tta``: one forward; the dict holds ``probs`` (B,H,W,C) float32 and / or ``argmax`` (B,H,W)
+          uint8 as wanted.  ``mc=(samples, step0)``: ``samples`` forwards with the bottleneck dropout on (dropout steps ``step0 ..
+          step0+samples-1``; the encoder and the bottleneck run once), reduced on the device.  ``tta=views``, 1..4 distinct
+          names of ``common.utils.TTA_VIEWS``: one forward per view on the batch flipped by it, mirrored back and averaged on the
+          device.  Both give ``entropy`` and ``mutual_info`` (B,H,W) float32, ``argmax`` -- of the mean prediction -- with
+          ``want_argmax`` and ``mean_probs`` with ``want_probs``.
+        * ``pad=(top, left, mode, value)``: ``x`` has a size that is no multiple of 2^pool_layers and the engine is one built at
+          the padded size; the chain pads in front (``oct_pad_batch``), takes the views of the PADDED batch and crops every map
+          it returns behind (``oct_crop_batch``).
+        * ``capture``: record the chain over the fixed input ``x`` into the graph that ``graph_launch`` replays, instead of
+          running it; ``x`` must be refilled in place between launches, and every replay refills the tensors returned here.
+          Not with ``mc``: the dropout step travels by value.
+
+        The tensors of an unpadded plain forward are new ones; all others belong to the engine's buffer set for this batch
+        size (and true size): the next ``infer`` of that batch size refills them."""
+        if mc is not None and tta is not None:
+            raise OctError("infer: mc and tta exclude each other")
+        self._check_x(x, any_size=pad is not None)
+        B, H, W, _ = x.shape
+        plain = mc is None and tta is None
+        d = _hip.Infer(x_dev=x.data_ptr(), x_is_u8=int(x.dtype == torch.uint8), B=B, H=H, W=W)
+        if plain and pad is None:
+            _, probs, am = self._io(B, None, want_probs, want_argmax)
+            full = {k: t for k, t in (("mean_probs", probs), ("argmax", am)) if t is not None}
+        else:
+            keys = (("mean_probs",) if want_probs else ()) + (("argmax",) if want_argmax else ()) + (() if plain else self._MAPS[2:])
+            full = {k: self._map(B, k) for k in keys}
+        if mc is not None:
+            samples, step0 = mc
+            if not 1 <= int(samples) <= _hip.MC_MAX_SAMPLES:
+                raise OctError(f"infer: mc samples must be in 1..{_hip.MC_MAX_SAMPLES}, not {samples}")
+            d.kind, d.T, d.step0 = _hip.INFER_MC, int(samples), int(step0) & 0xFFFFFFFFFFFFFFFF
+        if tta is not None:
+            from .common.utils import parse_tta
+            try:
+                codes = parse_tta(tta)
+            except ValueError as e:
+                raise OctError(str(e)) from None
+            if not codes:
+                raise OctError("tta: at least one view is needed")
+            d.kind, d.T, d.views = _hip.INFER_TTA, len(codes), (C.c_int * 4)(*codes)
+            d.x_view_dev = self._tta_buffers(B, x)["x_view"].data_ptr()
+        if not plain:
+            b = self._mc_buffers(B)
+            d.probs_scratch_dev, d.ws_dev, d.ws_bytes = b["scratch"].data_ptr(), b["ws"].data_ptr(), b["ws"].numel()
+        outs = full
+        if pad is not None:
+            top, left, mode, value = pad
+            if mode not in _hip.PAD_MODES:
+                raise OctError(f'infer: the pad mode must be "edge", "reflect" or "constant", not {mode!r}')
+            d.top, d.left, d.pad_mode, d.pad_value = int(top), int(left), _hip.PAD_MODES[mode], float(value)
+            d.x_pad_dev = self._buf(B, ("x_pad", x.dtype), (B, self.cfg.H, self.cfg.W, self.cfg.in_ch), x.dtype).data_ptr()
+            outs = {k: self._map(B, k, (H, W)) for k in full}
+            d.out_crop = _hip.McOut(**{k: t.data_ptr() for k, t in outs.items()})
+        d.out = _hip.McOut(**{k: t.data_ptr() for k, t in full.items()})
+        if plain:
+            outs = {("probs" if k == "mean_probs" else k): t for k, t in outs.items()}
+        if capture:
+            s = torch.cuda.Stream(self.device)                  # a side stream, joined to the current one on both ends
+            s.wait_stream(torch.cuda.current_stream(self.device))
+            self._call("oct_unet_graph_capture_infer", C.byref(d), C.c_void_p(s.cuda_stream))
+            torch.cuda.current_stream(self.device).wait_stream(s)
+            # the fixed input, what else the graph refers to outside the buffer set, the arg-max map it refills
+            self._graph_keep = [x, full, outs.get("argmax")]
+        else:
+            self._call("oct_unet_infer", C.byref(d), self._stream())
+            self._keep = [x, full]
+        return outs
 
     def forward_mc(self, x: torch.Tensor, samples: int, step0: int = 0, want_mean_probs: bool = False) -> Dict[str, torch.Tensor]:
-        """``samples`` inference forwards with the bottleneck dropout on (dropout steps ``step0 .. step0+samples-1``, the
-        encoder and bottleneck run once), reduced on the device (``oct_unet_forward_mc``): a dict of device tensors
-        ``argmax`` (B,H,W) uint8 -- of the mean probabilities --, ``entropy`` and ``mutual_info`` (B,H,W) float32 and, with
-        ``want_mean_probs``, ``mean_probs`` (B,H,W,C) float32.  The tensors are the engine's own buffers for this batch
-        size: the next ``forward_mc`` of the same batch size refills them.  Asynchronous on the current stream."""
-        self._check_x(x)
-        if not 1 <= int(samples) <= _hip.MC_MAX_SAMPLES:
-            raise OctError(f"forward_mc: samples must be in 1..{_hip.MC_MAX_SAMPLES}, not {samples}")
-        B = x.shape[0]
-        b = self._mc_buffers(B)
-        keys = ("argmax", "entropy", "mutual_info") + (("mean_probs",) if want_mean_probs else ())
-        out = _hip.McOut(**{k: b[k].data_ptr() for k in keys})
-        self._call("oct_unet_forward_mc", x.data_ptr(), int(x.dtype == torch.uint8), B, int(samples),
-                   int(step0) & 0xFFFFFFFFFFFFFFFF, b["scratch"].data_ptr(), b["ws"].data_ptr(), b["ws"].numel(), C.byref(out),
-                   self._stream())
-        self._keep = [x]
-        return {k: b[k] for k in keys}
+        """``infer(x, mc=(samples, step0))``: ``argmax``, ``entropy``, ``mutual_info`` and, with ``want_mean_probs``,
+        ``mean_probs`` -- the engine's own buffers for this batch size.  Asynchronous on the current stream."""
+        return self.infer(x, mc=(samples, step0), want_probs=want_mean_probs, want_argmax=True)
+
+    def forward_tta(self, x: torch.Tensor, views, want_mean_probs: bool = False) -> Dict[str, torch.Tensor]:
+        """``infer(x, tta=views)``: a dict like ``forward_mc``'s, in the same buffers."""
+        return self.infer(x, tta=views, want_probs=want_mean_probs, want_argmax=True)
+
+    def graph_capture_tta(self, x: torch.Tensor, views, want_mean_probs: bool = False, pad=None) -> Dict[str, torch.Tensor]:
+        """``infer(x, tta=views, pad=pad, capture=True)``: the dict of tensors every ``graph_launch`` refills."""
+        return self.infer(x, tta=views, pad=pad, want_probs=want_mean_probs, want_argmax=True, capture=True)
+
+    def graph_capture(self, x: torch.Tensor, want_probs=True, want_argmax=False):
+        """Capture one inference forward over fixed buffers; returns (probs, argmax) output tensors that every
+        ``graph_launch`` refills.  ``x`` must be refilled in place (``x.copy_``) between launches."""
+        out = self.infer(x, want_probs=want_probs, want_argmax=want_argmax, capture=True)
+        return out.get("probs"), out.get("argmax")
+
+    def graph_capture_padded(self, x: torch.Tensor, top: int, left: int, mode: str, value=0, want_probs=True, want_argmax=False):
+        """``graph_capture`` of a (B,H,W,ch) input of a size that is no multiple of 2^pool_layers, on an engine built at the
+        padded size: pad, forward and crops in ONE graph; the (probs, argmax) tensors are of size (H, W)."""
+        out = self.infer(x, pad=(top, left, mode, value), want_probs=want_probs, want_argmax=want_argmax, capture=True)
+        return out.get("probs"), out.get("argmax")
 
     def mc_update(self, probs: torch.Tensor, t: int, samples: int, ws: torch.Tensor, *, mean_probs=None, argmax=None,
                   entropy=None, mutual_info=None) -> None:
@@ -438,86 +535,7 @@ class UNetEngine:
         _hip.call("oct_tta_update", self.device, probs.data_ptr(), B, H, W, Cn, _view_code(view), int(t), int(samples),
                   ws.data_ptr(), ws.numel(), C.byref(out), self._stream())
 
-    def _tta_buffers(self, B: int, x: torch.Tensor) -> dict:
-        """``_mc_buffers`` plus the flipped input of ``forward_tta`` for batch ``B`` and the input's type: made once, kept."""
-        b = self._mc_buffers(B)
-        key = "x_view_u8" if x.dtype == torch.uint8 else "x_view_f32"
-        if key not in b:
-            b[key] = torch.empty((B, self.cfg.H, self.cfg.W, self.cfg.in_ch), dtype=x.dtype, device=self.device)
-        return dict(b, x_view=b[key])
-
-    @staticmethod
-    def _tta_views(views):
-        from .common.utils import parse_tta
-        try:
-            codes = parse_tta(views)
-        except ValueError as e:
-            raise OctError(str(e)) from None
-        if not codes:
-            raise OctError("tta: at least one view is needed")
-        return (C.c_int * len(codes))(*codes), len(codes)
-
-    def forward_tta(self, x: torch.Tensor, views, want_mean_probs: bool = False) -> Dict[str, torch.Tensor]:
-        """One inference forward per view of ``views`` -- 1..4 distinct names of ``common.utils.TTA_VIEWS`` -- on the batch
-        flipped by it, mirrored back and averaged on the device (``oct_unet_forward_tta``): a dict of device tensors like
-        ``forward_mc``'s, ``argmax`` being that of the mean prediction.  The tensors are the engine's own buffers for this
-        batch size, shared with ``forward_mc``: the next call of either refills them.  Asynchronous on the current stream."""
-        self._check_x(x)
-        codes, T = self._tta_views(views)
-        B = x.shape[0]
-        b = self._tta_buffers(B, x)
-        keys = ("argmax", "entropy", "mutual_info") + (("mean_probs",) if want_mean_probs else ())
-        out = _hip.McOut(**{k: b[k].data_ptr() for k in keys})
-        self._call("oct_unet_forward_tta", x.data_ptr(), int(x.dtype == torch.uint8), B, codes, T, b["x_view"].data_ptr(),
-                   b["scratch"].data_ptr(), b["ws"].data_ptr(), b["ws"].numel(), C.byref(out), self._stream())
-        self._keep = [x]
-        return {k: b[k] for k in keys}
-
-    def graph_capture_tta(self, x: torch.Tensor, views, want_mean_probs: bool = False, pad=None) -> Dict[str, torch.Tensor]:
-        """Capture ``forward_tta`` of the fixed input ``x`` into the graph that ``graph_launch`` replays; returns the dict
-        of output tensors every replay refills (the engine's buffers for this batch size, as ``forward_tta``; with ``pad``,
-        tensors of the input's own size that the capture owns).  ``pad``: ``(top, left, mode, value)`` for an input of a
-        size that is no multiple of 2^pool_layers on an engine built at the padded size -- the graph then pads in front,
-        takes the views of the PADDED batch and crops every map behind (``oct_unet_graph_capture_tta``).  ``x`` must be
-        refilled in place between launches."""
-        self._check_x(x, any_size=pad is not None)
-        codes, T = self._tta_views(views)
-        B, H, W, _ = x.shape
-        b = self._tta_buffers(B, x)
-        keys = ("argmax", "entropy", "mutual_info") + (("mean_probs",) if want_mean_probs else ())
-        out_pad = _hip.McOut(**{k: b[k].data_ptr() for k in keys})
-        outs, x_pad, out_crop, at = {k: b[k] for k in keys}, None, None, (0, 0, 0, 0.0)
-        if pad is not None:
-            top, left, mode, value = pad
-            if mode not in _hip.PAD_MODES:
-                raise OctError(f'graph_capture_tta: mode must be "edge", "reflect" or "constant", not {mode!r}')
-            at = (int(top), int(left), _hip.PAD_MODES[mode], float(value))
-            x_pad = torch.empty((B, self.cfg.H, self.cfg.W, self.cfg.in_ch), dtype=x.dtype, device=self.device)
-            outs = {k: torch.empty((B, H, W) + tuple(b[k].shape[3:]), dtype=b[k].dtype, device=self.device) for k in keys}
-            out_crop = _hip.McOut(**{k: outs[k].data_ptr() for k in keys})
-        self._graph_keep = [x, x_pad, b, outs]
-        self._capture("oct_unet_graph_capture_tta", x.data_ptr(), int(x.dtype == torch.uint8), B, codes, T, b["x_view"].data_ptr(),
-                      b["scratch"].data_ptr(), b["ws"].data_ptr(), b["ws"].numel(), H, W, *at, _ptr(x_pad), C.byref(out_pad),
-                      None if out_crop is None else C.byref(out_crop))
-        return outs
-
     # ---- inference hipGraph ------------------------------------------------------------------------
-    def graph_capture(self, x: torch.Tensor, want_probs=True, want_argmax=False):
-        """Capture one inference forward over fixed buffers; returns (probs, argmax) output tensors that every
-        ``graph_launch`` refills.  ``x`` must be refilled in place (``x.copy_``) between launches."""
-        self._check_x(x)
-        io, probs, am = self._io(x.shape[0], None, want_probs, want_argmax)
-        self._graph_keep = [x, probs, am]
-        self._capture("oct_unet_graph_capture", x.data_ptr(), int(x.dtype == torch.uint8), x.shape[0], C.byref(io))
-        return probs, am
-
-    def _capture(self, name: str, *args) -> None:
-        """The library's capture call ``name(handle, *args, stream)`` on a side stream, joined to the current one on both ends."""
-        s = torch.cuda.Stream(self.device)
-        s.wait_stream(torch.cuda.current_stream(self.device))
-        self._call(name, *args, C.c_void_p(s.cuda_stream))
-        torch.cuda.current_stream(self.device).wait_stream(s)
-
     def graph_launch(self):
         self._call("oct_unet_graph_launch", self._stream())
 
@@ -626,23 +644,6 @@ class UNetEngine:
         _hip.call("oct_crop_batch", self.device, t.data_ptr(), B, Hp, Wp, t.element_size() * int(np.prod(t.shape[3:], dtype=np.int64)),
                   int(H), int(W), int(top), int(left), out.data_ptr(), self._stream())
         return out
-
-    def graph_capture_padded(self, x: torch.Tensor, top: int, left: int, mode: str, value=0, want_probs=True, want_argmax=False):
-        """``graph_capture`` for scans of a size that is no multiple of 2^pool_layers, on an engine built at the padded
-        size: captures ``pad`` of the fixed (B,H,W,ch) input ``x`` at (top, left), the forward and the ``crop`` of every
-        output into ONE graph (``oct_unet_graph_capture_padded``); returns the (probs, argmax) tensors of size (H, W) that
-        every ``graph_launch`` refills.  ``x`` must be refilled in place between launches."""
-        self._check_x(x, any_size=True)
-        if mode not in _hip.PAD_MODES:
-            raise OctError(f'graph_capture_padded: mode must be "edge", "reflect" or "constant", not {mode!r}')
-        B, H, W, _ = x.shape
-        x_pad = torch.empty((B, self.cfg.H, self.cfg.W, self.cfg.in_ch), dtype=x.dtype, device=self.device)
-        io_pad, probs_pad, am_pad = self._io(B, None, want_probs, want_argmax)
-        io_crop, probs, am = self._io(B, None, want_probs, want_argmax, hw=(H, W))
-        self._graph_keep = [x, x_pad, probs_pad, am_pad, probs, am]
-        self._capture("oct_unet_graph_capture_padded", x.data_ptr(), int(x.dtype == torch.uint8), B, H, W, int(top), int(left),
-                      _hip.PAD_MODES[mode], float(value), x_pad.data_ptr(), C.byref(io_pad), C.byref(io_crop))
-        return probs, am
 
     # ---- weights exchange --------------------------------------------------------------------------
     def get_weights(self) -> List[np.ndarray]:

@@ -96,7 +96,7 @@ class BatchedPredictor:
     Labels, surface distances, confusion counts, the min-path stage behind the maps and every transfer are the same.
 
     With ``mc_samples`` > 0 every batch is a Monte-Carlo dropout prediction: no graph is captured, and the per-batch graph
-    launch is ``engine.forward_mc`` on the same fixed input buffer -- ``mc_samples`` forwards with the bottleneck dropout on,
+    launch is the eager ``engine.infer(mc=...)`` on the same fixed input buffer -- ``mc_samples`` forwards with the bottleneck dropout on,
     dropout steps ``mc_step0 .. mc_step0+mc_samples-1`` for EVERY batch.  The arg-max maps and (with ``soft_maps``) the
     probabilities are then those of the MEAN prediction, everything behind them is unchanged, and ``Batch.entropy`` /
     ``Batch.mutual_info`` carry the two uncertainty maps, downloaded through pinned double buffers like the labels.  The
@@ -107,11 +107,11 @@ class BatchedPredictor:
     "constant" with ``pad_value``) the engine is one built at the padded size (``common.utils.padded_geometry``): the
     captured graph is then ``oct_pad_batch`` of the true-size input, the forward and ``oct_crop_batch`` of the arg-max maps
     (and of the probabilities with ``soft_maps``), the pinned upload buffers and everything behind the graph are true-size,
-    and every stage runs on the cropped tensors.  A Monte-Carlo batch pads in front of ``forward_mc`` and crops its arg-max,
-    entropy, mutual information and mean probabilities.  Without ``hw`` nothing is launched that was not before.
+    and every stage runs on the cropped tensors.  A Monte-Carlo batch is the same chain run eagerly: the pad in front, the crops
+    of its arg-max, entropy, mutual information and mean probabilities behind.  Without ``hw`` nothing is launched that was not before.
 
     With ``tta`` -- 1..4 distinct view names of ``common.utils.TTA_VIEWS`` -- every batch is a test-time-augmented
-    prediction, and unlike the Monte-Carlo one it IS a graph: the graph captured here is ``engine.graph_capture_tta`` (per
+    prediction, and unlike the Monte-Carlo one it IS a graph: the graph captured here is ``engine.infer(tta=..., capture=True)`` (per
     view the flip of the input, the forward and the mirrored fold; with ``hw`` the pad in front, the views taken of the
     padded batch, and the crops behind).  As for ``mc_samples`` the arg-max maps and (with ``soft_maps``) the probabilities
     are those of the MEAN prediction and ``Batch.entropy`` / ``Batch.mutual_info`` carry the two maps over the views;
@@ -167,25 +167,13 @@ class BatchedPredictor:
         if self.mc_samples or self.tta:
             self.unc_dev = [tuple(torch.empty((self.B, H, W), dtype=torch.float32, device=dev) for _ in range(2)) for _ in range(2)]
             self.unc_pin = [tuple(torch.empty((self.B, H, W), dtype=torch.float32).pin_memory() for _ in range(2)) for _ in range(2)]
-        self.tta_out = None                                 # the maps every replay of the TTA graph refills
-        if self.tta:
-            pad = None if self.at is None else (*self.at, self.pad_mode, self.pad_value)
-            self.tta_out = engine.graph_capture_tta(self.x_dev, self.tta, want_mean_probs=self.soft_maps, pad=pad)
-            self.am, self.probs = self.tta_out["argmax"], self.tta_out.get("mean_probs")
-        elif self.mc_samples:
-            self.probs = self.am = None                     # the engine's forward_mc buffers: set by every batch
-            if self.at is not None:                         # the padded input and the crops' own buffers: made once, kept
-                f32 = dict(dtype=torch.float32, device=dev)
-                self.x_pad = torch.empty((self.B, engine.cfg.H, engine.cfg.W, ic), dtype=torch.uint8, device=dev)
-                self.mc_crop = dict(argmax=torch.empty((self.B, H, W), dtype=torch.uint8, device=dev),
-                                    entropy=torch.empty((self.B, H, W), **f32), mutual_info=torch.empty((self.B, H, W), **f32))
-                if self.soft_maps:
-                    self.mc_crop["mean_probs"] = torch.empty((self.B, H, W, C), **f32)
-        elif self.at is not None:
-            self.probs, self.am = engine.graph_capture_padded(self.x_dev, *self.at, self.pad_mode, self.pad_value,
-                                                              want_probs=self.soft_maps, want_argmax=True)
-        else:
-            self.probs, self.am = engine.graph_capture(self.x_dev, want_probs=self.soft_maps, want_argmax=True)
+        # THE chain over the fixed input: captured once and replayed per batch, or -- Monte-Carlo -- repeated eagerly per batch
+        pad = None if self.at is None else (*self.at, self.pad_mode, self.pad_value)
+        self._infer = lambda capture: engine.infer(self.x_dev, mc=(self.mc_samples, self.mc_step0) if self.mc_samples else None,
+                                                   tta=self.tta or None, pad=pad, want_probs=self.soft_maps, want_argmax=True,
+                                                   capture=capture)
+        self.out = self._infer(not self.mc_samples)         # the maps every batch refills (engine-owned buffers)
+        self.am, self.probs = self.out["argmax"], self.out.get("mean_probs", self.out.get("probs"))
 
     def run(self, images_u8: np.ndarray, gt_u8: Optional[np.ndarray] = None) -> Iterator[Batch]:
         images_u8 = np.ascontiguousarray(images_u8)
@@ -237,18 +225,11 @@ class BatchedPredictor:
             main.wait_event(up_done[s])
             self.x_dev.copy_(self.x_stage[s])                                           # D2D, then the staging buffer is free
             x_free[s].record(main)
-            mc = None
             if self.mc_samples:
-                x_in = self.x_dev
-                if self.at is not None:
-                    x_in = eng.pad(self.x_dev, eng.cfg.H, eng.cfg.W, *self.at, self.pad_mode, self.pad_value, out=self.x_pad)
-                mc = eng.forward_mc(x_in, self.mc_samples, step0=self.mc_step0, want_mean_probs=self.soft_maps)
-                if self.at is not None:
-                    mc = {k: eng.crop(t, *self.hw, *self.at, out=self.mc_crop[k]) for k, t in mc.items()}
-                self.am, self.probs = mc["argmax"], mc.get("mean_probs")
+                self._infer(False)
             else:
                 eng.graph_launch()
-                mc = self.tta_out
+            mc = self.out if self.unc_dev is not None else None
             if i >= 2:
                 main.wait_event(out_done[s])                                            # device out buffers of batch i-2 downloaded
             self.lab_dev[s].copy_(self.am)

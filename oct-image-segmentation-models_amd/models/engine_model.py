@@ -464,22 +464,17 @@ class Model:
             pad_mode, pad_value = self.pad_mode, self.pad_value
         return check_pad_mode(pad_mode, pad_value)
 
-    def _inference_batches(self, x: np.ndarray, bs: int, pad):
+    def _inference_batches(self, x: np.ndarray, bs: int, pad, **kind):
         """The loop of the predict methods over host array ``x`` in batches of ``bs`` under the validated ``pad`` = (pad_mode,
-        pad_value): yields per batch the host slice bounds ``lo, hi``, the engine of the images' geometry, the batch on the device
-        and ``crop``, the identity.  For a size that is no multiple of 2^pool_layers the engine is that of the padded geometry, the
-        batch is padded (``UNetEngine.pad``) and ``crop`` takes a tensor, a dict of tensors or None back to the images' size."""
+        pad_value): yields per batch the host slice bounds ``lo, hi``, the engine of the images' geometry and the maps of
+        ``UNetEngine.infer(batch, **kind)``, of the images' size.  For a size that is no multiple of 2^pool_layers the engine is
+        that of the padded geometry and ``infer`` pads in front and crops behind."""
         n, (H, W) = x.shape[0], x.shape[1:3]
         geom, at = self._geometry((H, W), pad[0])
         eng = self._ensure_engine(min(bs, n), False, hw=geom)
-
-        def crop(t):
-            if at is None or t is None:
-                return t
-            return {k: crop(v) for k, v in t.items()} if isinstance(t, dict) else eng.crop(t, H, W, *at)
         for lo in range(0, n, bs):
             xb = torch.from_numpy(np.ascontiguousarray(x[lo:lo + bs])).to(eng.device)
-            yield lo, min(lo + bs, n), eng, (xb if at is None else eng.pad(xb, eng.cfg.H, eng.cfg.W, *at, *pad)), crop
+            yield lo, min(lo + bs, n), eng, eng.infer(xb, pad=None if at is None else (*at, *pad), **kind)
 
     def predict(self, x, verbose=0, batch_size: Optional[int] = None, pad_mode: Optional[str] = None, pad_value=0,
                 **kwargs) -> np.ndarray:
@@ -493,13 +488,13 @@ class Model:
         if x.dtype != np.uint8:
             x = np.ascontiguousarray(x, dtype=np.float32)   # Keras casts the float64 the reference passes to float32
         out = np.empty(x.shape[:3] + (self.config["num_classes"],), np.float32)
-        for lo, hi, eng, xb, crop in self._inference_batches(x, int(batch_size or min(x.shape[0], 32)), pad):
-            out[lo:hi] = crop(eng.forward(xb, training=False)[0]).cpu().numpy()
+        for lo, hi, _, maps in self._inference_batches(x, int(batch_size or min(x.shape[0], 32)), pad, want_probs=True, want_argmax=False):
+            out[lo:hi] = maps["probs"].cpu().numpy()
         return out
 
     def predict_mc(self, x, samples: int, batch_size: Optional[int] = None, step0: int = 0):
         """Monte-Carlo dropout prediction: ``samples`` stochastic forwards per batch with the bottleneck dropout on (dropout
-        steps ``step0 .. step0+samples-1``, the same for every batch; ``UNetEngine.forward_mc``), reduced on the device.
+        steps ``step0 .. step0+samples-1``, the same for every batch; ``UNetEngine.infer(mc=...)``), reduced on the device.
         Input as for ``predict``; returns ``(mean_probs (n,H,W,num_classes), entropy (n,H,W), mutual_info (n,H,W))``
         float32.  The dropout stream is indexed by the element's position in the bottleneck tensor of its BATCH and seeded
         per rank, so an image's result depends on its position in its batch (hence on ``batch_size``) and on the rank.
@@ -511,16 +506,15 @@ class Model:
         keys = ("mean_probs", "entropy", "mutual_info")
         mean = np.empty(x.shape[:3] + (self.config["num_classes"],), np.float32)
         ent, mi = np.empty(x.shape[:3], np.float32), np.empty(x.shape[:3], np.float32)
-        for lo, hi, eng, xb, crop in self._inference_batches(x, int(batch_size or min(x.shape[0], 32)), self._pad_options(None, 0)):
-            out = eng.forward_mc(xb, samples, step0=step0, want_mean_probs=True)
-            out = crop({k: out[k] for k in keys})
+        for lo, hi, _, out in self._inference_batches(x, int(batch_size or min(x.shape[0], 32)), self._pad_options(None, 0),
+                                                      mc=(samples, step0), want_probs=True, want_argmax=True):
             mean[lo:hi], ent[lo:hi], mi[lo:hi] = (out[k].cpu().numpy() for k in keys)
         return mean, ent, mi
 
     def predict_tta(self, x, views, batch_size: Optional[int] = None):
         """Test-time-augmented prediction: one forward per view of ``views`` -- 1..4 distinct names of
         ``common.utils.TTA_VIEWS``, e.g. ``("identity", "flip_lr")`` -- on the batch mirrored by it, mirrored back and
-        averaged on the device (``UNetEngine.forward_tta``).  Input as for ``predict``; returns ``(mean_probs
+        averaged on the device (``UNetEngine.infer(tta=...)``).  Input as for ``predict``; returns ``(mean_probs
         (n,H,W,num_classes) float32, argmax (n,H,W) uint8 of the mean, entropy (n,H,W), mutual_info (n,H,W))``, the last two
         float32: the predictive entropy of the mean and the mutual information over the views.  Deterministic, and
         independent of the batch an image sits in.  Padding as for ``predict_mc``, from the model's ``pad_mode`` /
@@ -531,8 +525,8 @@ class Model:
         keys = ("mean_probs", "argmax", "entropy", "mutual_info")
         mean = np.empty(x.shape[:3] + (self.config["num_classes"],), np.float32)
         am, ent, mi = np.empty(x.shape[:3], np.uint8), np.empty(x.shape[:3], np.float32), np.empty(x.shape[:3], np.float32)
-        for lo, hi, eng, xb, crop in self._inference_batches(x, int(batch_size or min(x.shape[0], 32)), self._pad_options(None, 0)):
-            out = crop(eng.forward_tta(xb, views, want_mean_probs=True))
+        for lo, hi, _, out in self._inference_batches(x, int(batch_size or min(x.shape[0], 32)), self._pad_options(None, 0),
+                                                      tta=views, want_probs=True, want_argmax=True):
             mean[lo:hi], am[lo:hi], ent[lo:hi], mi[lo:hi] = (out[k].cpu().numpy() for k in keys)
         return mean, am, ent, mi
 
@@ -565,14 +559,11 @@ class Model:
         out = np.empty(x_u8.shape[:3], np.uint8)
         maps = np.empty((x_u8.shape[0], self.config["num_classes"] - 1) + tuple(x_u8.shape[1:3]), np.uint8) if want_maps else None
         unc = (np.empty(x_u8.shape[:3], np.float32), np.empty(x_u8.shape[:3], np.float32)) if mc_samples or tta else ()
-        for lo, hi, eng, xb, crop in self._inference_batches(x_u8, batch_size, (pad_mode, pad_value)):
-            if mc_samples or tta:
-                mc = crop(eng.forward_tta(xb, tta, want_mean_probs=soft_maps) if tta else
-                          eng.forward_mc(xb, mc_samples, step0=mc_step0, want_mean_probs=soft_maps))
-                probs, am = mc.get("mean_probs"), mc["argmax"]
+        kind = dict(mc=(mc_samples, mc_step0) if mc_samples else None, tta=tta or None, want_probs=soft_maps, want_argmax=True)
+        for lo, hi, eng, mc in self._inference_batches(x_u8, batch_size, (pad_mode, pad_value), **kind):
+            probs, am = mc.get("mean_probs", mc.get("probs")), mc["argmax"]
+            if unc:
                 unc[0][lo:hi], unc[1][lo:hi] = mc["entropy"].cpu().numpy(), mc["mutual_info"].cpu().numpy()
-            else:
-                probs, am = map(crop, eng.forward(xb, training=False, want_probs=soft_maps, want_argmax=True))
             out[lo:hi] = am.cpu().numpy()
             if want_maps:
                 dev_maps = (eng.boundary_maps_soft(probs, bg_ilm=bg_ilm, bg_csi=bg_csi) if soft_maps

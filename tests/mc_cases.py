@@ -8,7 +8,7 @@ from oracle import unet_numpy as on
 def forward_mc_oracle(cfg, params, state, x, mask):
     """Softmax output of an INFERENCE forward (BN from the moving statistics) with the dropout keep-``mask``
     (B, H/2^P, W/2^P, start_neurons*2^P) of {0,1} applied, times 1 / (1 - rate), behind the bottleneck -- what one sample
-    of ``oct_unet_forward_mc`` computes.  ``oracle.unet_numpy.forward`` applies the mask only when ``training`` (which also
+    of ``oct_unet_infer`` (kind MC) computes.  ``oracle.unet_numpy.forward`` applies the mask only when ``training`` (which also
     switches BN to batch statistics), so the combination is composed here from its layer functions, walking ``build_plan``
     exactly as it does.  fp64 throughout: ``params`` / ``state`` / ``x`` are float64."""
     plan = on.build_plan(cfg)

@@ -246,5 +246,6 @@ def test_crop_batch_argument_errors_return_before_any_launch(hip, kw, msg):
 def test_pad_modes_are_bound_by_their_public_names(hip):
     assert hip.PAD_MODES == {"edge": 0, "reflect": 1, "constant": 2}
     lib = hip.lib()
-    assert lib.oct_unet_graph_capture_padded(None, 0x1000, 1, 1, 5, 7, 1, 0, 0, 0.0, 0x2000, None, None, None) < 0
+    d = hip.Infer(x_dev=0x1000, x_is_u8=1, B=1, kind=hip.INFER_PLAIN, H=5, W=7, top=1, left=0, pad_mode=0, pad_value=0.0, x_pad_dev=0x2000)
+    assert lib.oct_unet_graph_capture_infer(None, C.byref(d), None) < 0
     assert "null" in lib.oct_last_error().decode()

@@ -438,3 +438,66 @@ def test_sizes_that_are_multiples_are_never_padded(tmp_path):
     for a, b, name in (("e0", "e1", "eval_params.hdf5"), ("p0", "p1", "prediction_params.hdf5")):
         (tmp_path / a / name).unlink(); (tmp_path / b / name).unlink()       # differ by the recorded option alone (above)
         _same_tree(tmp_path / a, tmp_path / b)
+
+
+# ---- 9. UNetEngine.infer: the one chain -- every kind padded eagerly, eager against captured, the refusals -------------------------
+INFER_KINDS = {"plain": {}, "mc": dict(mc=(2, 3)), "tta": dict(tta=("identity", "flip_both"))}
+PAD_37x70 = (1, 1, "edge", 0)
+
+
+def _kind_on_native(native, xp, kind):
+    """The kind's maps of the native-size batch ``xp`` through the public calls of before ``infer``."""
+    if kind == "mc":
+        return native.forward_mc(xp, 2, step0=3, want_mean_probs=True)
+    if kind == "tta":
+        return native.forward_tta(xp, ("identity", "flip_both"), want_mean_probs=True)
+    probs, am = native.forward(xp, training=False, want_probs=True, want_argmax=True)
+    return dict(probs=probs, argmax=am)
+
+
+@pytest.mark.parametrize("kind", list(INFER_KINDS))
+def test_eager_padded_infer_equals_crop_of_the_kind_on_the_padded_batch(padded_case, kind):
+    """The pad and the crops issued by the library outside a capture: every map ``infer(x, pad=...)`` returns is byte-equal to
+    ``crop(<kind>(pad(x)))`` composed from the public pieces (``crop`` makes new tensors: the next call does not refill them)."""
+    _, native, x = padded_case
+    x = _up(x[:3])
+    want = {k: native.crop(t, 37, 70, 1, 1) for k, t in _kind_on_native(native, native.pad(x, 40, 72, 1, 1, "edge"), kind).items()}
+    got = native.infer(x, pad=PAD_37x70, want_probs=True, want_argmax=True, **INFER_KINDS[kind])
+    assert set(got) == set(want) == ({"probs", "argmax"} if kind == "plain" else {"mean_probs", "argmax", "entropy", "mutual_info"})
+    for k in want:
+        assert got[k].shape == want[k].shape and got[k].shape[:3] == (3, 37, 70) and torch.equal(got[k], want[k]), k
+
+
+@pytest.mark.parametrize("padded", [False, True], ids=["native", "padded"])
+@pytest.mark.parametrize("kind", ["plain", "tta"])
+def test_captured_infer_equals_eager_infer(padded_case, kind, padded):
+    """Two replays of the captured chain, the fixed input refilled in place between them, against the eager chain.  The eager
+    call may write the very buffers the graph refills: its maps are cloned and the buffers scrubbed before each replay."""
+    _, native, x = padded_case
+    pad = PAD_37x70 if padded else None
+    batches = [_up(x[:3]), _up(x[2:5])] if padded else [_up(_scans(3, 40, 72, seed)[0]) for seed in (51, 52)]
+    ask = dict(pad=pad, want_probs=True, want_argmax=True, **INFER_KINDS[kind])
+    x_fix = torch.zeros_like(batches[0])
+    outs = native.infer(x_fix, capture=True, **ask)
+    for xb in batches:
+        want = {k: t.clone() for k, t in native.infer(xb, **ask).items()}
+        for t in outs.values():
+            t.fill_(SENTINEL if t.dtype == torch.uint8 else -7.0)
+        x_fix.copy_(xb)
+        native.graph_launch()
+        assert set(outs) == set(want)
+        for k in want:
+            assert torch.equal(outs[k], want[k]), k
+
+
+def test_infer_refusals_leave_the_engine_usable(padded_case):
+    from oct_image_segmentation_models_amd._hip import OctError
+    _, native, x = padded_case
+    xp = native.pad(_up(x[:3]), 40, 72, 1, 1, "edge")
+    before = native.forward(xp, training=False)[0].clone()
+    with pytest.raises(OctError, match="dropout step"):             # a Monte-Carlo chain is not captured, and says why
+        native.infer(xp, mc=(2, 0), want_probs=True, want_argmax=True, capture=True)
+    assert torch.equal(native.forward(xp, training=False)[0], before)
+    with pytest.raises(OctError, match="mc and tta"):
+        native.infer(xp, mc=(2, 0), tta=("identity",), want_probs=True, want_argmax=True)
+    assert torch.equal(native.forward(xp, training=False)[0], before)

@@ -1,5 +1,5 @@
 """GPU tests of the Monte-Carlo dropout prediction: ``oct_mc_update`` against its numpy restatement, one stochastic sample
-of ``oct_unet_forward_mc`` against the fp64 oracle with the replayed mask, the reuse of the encoder across samples, the
+of ``oct_unet_infer`` (kind MC) against the fp64 oracle with the replayed mask, the reuse of the encoder across samples, the
 absence of side effects on the handle, the known answer without dropout, and ``predict`` with ``mc_samples``."""
 import ctypes as C
 from pathlib import Path
@@ -207,8 +207,10 @@ def test_forward_mc_argument_errors_launch_nothing():
     lib, need = _hip.lib(), b["ws"].numel()
     assert need == lib.oct_mc_workspace_bytes(B, H, W, Cn)
 
-    def call(x_ptr=x.data_ptr(), Bn=B, T=4, scratch=b["scratch"].data_ptr(), ws=b["ws"].data_ptr(), ws_bytes=need, o=C.byref(out)):
-        return lib.oct_unet_forward_mc(eng._h, x_ptr, 1, Bn, T, 0, scratch, ws, ws_bytes, o, None), lib.oct_last_error().decode()
+    def call(x_ptr=x.data_ptr(), Bn=B, T=4, scratch=b["scratch"].data_ptr(), ws=b["ws"].data_ptr(), ws_bytes=need, o=out):
+        d = _hip.Infer(x_dev=x_ptr, x_is_u8=1, B=Bn, kind=_hip.INFER_MC, T=T, step0=0, probs_scratch_dev=scratch, ws_dev=ws,
+                       ws_bytes=ws_bytes, H=H, W=W, out=o or _hip.McOut())      # the maps are in the descriptor: "no out" is no map
+        return lib.oct_unet_infer(eng._h, C.byref(d), None), lib.oct_last_error().decode()
 
     for kw, msg in ((dict(x_ptr=None), "null"), (dict(scratch=None), "null"), (dict(ws=None), "null"), (dict(o=None), "null"),
                     (dict(Bn=0), "B out of range"), (dict(Bn=3), "B out of range"), (dict(T=0), "T out of range"),

@@ -310,11 +310,13 @@ def test_forward_tta_argument_errors_launch_nothing():
     lib, need = _hip.lib(), b["ws"].numel()
 
     def call(x_ptr=x.data_ptr(), Bn=B, views=(0, 1), T=2, xv=b["x_view"].data_ptr(), scratch=b["scratch"].data_ptr(),
-             ws=b["ws"].data_ptr(), ws_bytes=need, o=C.byref(out)):
-        v = None if views is None else (C.c_int * len(views))(*views)
-        return lib.oct_unet_forward_tta(eng._h, x_ptr, 1, Bn, v, T, xv, scratch, ws, ws_bytes, o, None), lib.oct_last_error().decode()
+             ws=b["ws"].data_ptr(), ws_bytes=need, o=out):
+        # the views are an array inside the descriptor (there is no views pointer to be null); "no out" is no map asked for
+        d = _hip.Infer(x_dev=x_ptr, x_is_u8=1, B=Bn, kind=_hip.INFER_TTA, T=T, views=(C.c_int * 4)(*views[:4]), x_view_dev=xv,
+                       probs_scratch_dev=scratch, ws_dev=ws, ws_bytes=ws_bytes, H=H, W=W, out=o or _hip.McOut())
+        return lib.oct_unet_infer(eng._h, C.byref(d), None), lib.oct_last_error().decode()
 
-    for kw, msg in ((dict(x_ptr=None), "null"), (dict(views=None), "null"), (dict(scratch=None), "null"), (dict(ws=None), "null"),
+    for kw, msg in ((dict(x_ptr=None), "null"), (dict(scratch=None), "null"), (dict(ws=None), "null"),
                     (dict(o=None), "null"), (dict(Bn=0), "B out of range"), (dict(Bn=3), "B out of range"), (dict(T=0), "T out of range"),
                     (dict(views=(0, 1, 2, 3, 0), T=5), "T out of range"), (dict(views=(0, 4)), "outside 0..3"),
                     (dict(views=(-1, 0)), "outside 0..3"), (dict(xv=None), "x_view_dev"), (dict(xv=x.data_ptr()), "overlaps"),

@@ -1,5 +1,5 @@
 """CPU tests of the Monte-Carlo dropout prediction: the numpy restatement ``mc_reduce_reference`` on hand-made stacks, the
-workspace size, the argument errors of ``oct_mc_update`` / ``oct_unet_forward_mc`` that return before any launch, the
+workspace size, the argument errors of ``oct_mc_update`` / ``oct_unet_infer`` that return before any launch, the
 public parameters, and ``InferenceRun`` carrying the uncertainty maps of injected batches to ``predict``'s savers."""
 import ctypes as C
 import inspect
@@ -136,7 +136,9 @@ def test_mc_update_argument_errors_return_before_any_launch(hip, kw, msg):
 def test_forward_mc_refuses_a_null_handle_and_is_bound(hip):
     lib = hip.lib()
     out = hip.McOut(0x40000, 0x50000, 0x60000, 0x70000)
-    assert lib.oct_unet_forward_mc(None, 0x1000, 1, 1, 4, 0, 0x2000, 0x3000, 1 << 20, C.byref(out), None) < 0
+    d = hip.Infer(x_dev=0x1000, x_is_u8=1, B=1, kind=hip.INFER_MC, T=4, step0=0, probs_scratch_dev=0x2000, ws_dev=0x3000,
+                  ws_bytes=1 << 20, out=out)
+    assert lib.oct_unet_infer(None, C.byref(d), None) < 0
     assert "null" in lib.oct_last_error().decode()
     assert hip.MC_MAX_SAMPLES == 64
 

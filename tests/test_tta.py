@@ -211,12 +211,11 @@ def test_tta_update_argument_errors(hip):
 
 def test_engine_calls_refuse_a_null_handle_and_are_bound(hip):
     _hip, lib = hip
-    out = _hip.McOut(None, 0x5000, None, None)
-    views = (C.c_int * 2)(0, 1)
-    assert lib.oct_unet_forward_tta(None, 0x1000, 1, 1, views, 2, 0x2000, 0x3000, 0x4000, 1 << 20, C.byref(out), None) < 0
+    d = _hip.Infer(x_dev=0x1000, x_is_u8=1, B=1, kind=_hip.INFER_TTA, T=2, views=(C.c_int * 4)(0, 1), x_view_dev=0x2000,
+                   probs_scratch_dev=0x3000, ws_dev=0x4000, ws_bytes=1 << 20, H=16, W=32, out=_hip.McOut(None, 0x5000, None, None))
+    assert lib.oct_unet_infer(None, C.byref(d), None) < 0
     assert "null" in lib.oct_last_error().decode()
-    assert lib.oct_unet_graph_capture_tta(None, 0x1000, 1, 1, views, 2, 0x2000, 0x3000, 0x4000, 1 << 20, 16, 32, 0, 0, 0, 0.0, None,
-                                          C.byref(out), None, None) < 0
+    assert lib.oct_unet_graph_capture_infer(None, C.byref(d), None) < 0
     assert "null" in lib.oct_last_error().decode()
     names = [s[0] for s in _hip.SYMBOLS]
-    assert all(n in names for n in ("oct_flip_batch", "oct_tta_update", "oct_unet_forward_tta", "oct_unet_graph_capture_tta"))
+    assert all(n in names for n in ("oct_flip_batch", "oct_tta_update", "oct_unet_infer", "oct_unet_graph_capture_infer"))
