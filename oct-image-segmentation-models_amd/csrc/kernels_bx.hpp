@@ -736,7 +736,8 @@ __global__ __launch_bounds__(64 * NW, NIMG == 1 ? (NW == 4 ? 2 : 1) : 1) void co
 // pixel row w of every tile and all taps (9 accumulator tiles); global loads run two tiles ahead in registers, the
 // LDS images are double buffered (the split of tile t+1 is written while tile t is multiplied), one barrier per tile;
 // a fixed-order 4-wave sum through LDS at the end writes ONE partial slab per block (reduce_all_k sums the slabs).
-// UP: the conv input is the nearest-upsampled low-res tensor (2x2 up-conv): the VIRTUAL high-res tile is staged.
+// UP: the conv input is the nearest-upsampled low-res tensor (2x2 up-conv): the LDS image is the VIRTUAL high-res tile, staged
+// from its low-res footprint (each footprint pixel converted once and written to the slots it covers).
 // grid (npb, Cin/32, Cout/32); A.tiles / A.tiles_x for 4 x 32 tiles.
 // ------------------------------------------------------------------------------------------------------------------
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
@@ -752,6 +753,12 @@ __global__ __launch_bounds__(kBlock, 1) void conv_dwbx_k(const ConvBwdWArgs A) {
     constexpr int XPL = NPXP * 64, DPL = NPD * 64;              // bytes of one term's image (32 channels x bf16 per pixel)
     constexpr int BUF_B = NS * (XPL + DPL);
     static_assert((NPD * 4) % kBlock == 0, "dz tile items");
+    // UP: the IH x IW slots of the virtual tile are copies of an LH x LW low-res footprint (tiles start at even rows and
+    // columns).  It is staged: ONE X item per thread -- a (low-res pixel, octet) is loaded, converted and split once and its
+    // planes are written to every slot it covers (2 x 2; the footprint's last row and column cover one slot row / column).
+    constexpr int LH = TH / 2 + 1, LW = TW / 2 + 1, NPL = LH * LW;
+    constexpr int NXI = UP ? 1 : NXS, XCP = UP ? 4 : 1;         // X items per thread; LDS slots an X item is written to
+    static_assert(!UP || (NPL <= kBlock / 4 && NPX + kBlock / 4 - NPL <= NPXP), "one footprint item per thread; spare slots for the rest");
     constexpr int RED_B = TAPS * 4 * 16 * 64 * 4;              // the 4-wave sum of all taps (epilogue), then the bias scratch
     constexpr int SMEM_B = 2 * BUF_B > RED_B ? 2 * BUF_B : RED_B;
     static_assert(SMEM_B >= 4096 * 4 + kBlock * 8 * 4, "bias scratch fits");
@@ -781,13 +788,29 @@ __global__ __launch_bounds__(kBlock, 1) void conv_dwbx_k(const ConvBwdWArgs A) {
     }
     float ga[GB ? 8 : 1], gb[GB ? 8 : 1], gd[GB ? 8 : 1];
     if constexpr (GB) load_gb8(A.bnf, A.Cout, co0 + o8, ga, gb, gd);
-    int xly[NXS], xlx[NXS];
+    int xly[NXI], xlx[NXI], xsl[XCP];
+    if constexpr (UP) {
+        // footprint pixel (xly, xlx) of this thread and the byte offsets of the slots it covers; a slot row / column past the
+        // tile repeats the last one (the same planes to the same address).  Threads past the footprint convert a clamped
+        // pixel into a spare slot of their own behind the image, which no fragment read reaches.
+        const int P = tid >> 2;
+        const bool fp = P < NPL;
+        xly[0] = P / LW; xlx[0] = P % LW;
+        const int dy = fp && 2 * xly[0] + 1 < IH ? IW : 0, dx = fp && 2 * xlx[0] + 1 < IW ? 1 : 0;
+        const int s = fp ? 2 * xly[0] * IW + 2 * xlx[0] : NPX + P - NPL;
+        // a 16-byte store is banked per 8 lanes = 2 footprint pixels, 128 bytes apart in one slot column: odd pixels take
+        // the right column first: the pair falls on different banks
+        const int l = xlx[0] & 1 ? dx : 0, r = dx - l;
+        xsl[0] = (s + l) * 64; xsl[1] = (s + r) * 64; xsl[2] = (s + dy + l) * 64; xsl[3] = (s + dy + r) * 64;
+    } else {
 #pragma unroll
-    for (int k = 0; k < NXS; ++k) {
-        const int P = (tid >> 2) + k * (kBlock / 4);
-        xly[k] = P < NPX ? P / IW : -1000000; xlx[k] = P % IW;      // pad pixels fall outside every image -> zeros
+        for (int k = 0; k < NXS; ++k) {
+            const int P = (tid >> 2) + k * (kBlock / 4);
+            xly[k] = P < NPX ? P / IW : -1000000; xlx[k] = P % IW;      // pad pixels fall outside every image -> zeros
+        }
+        xsl[0] = 0;
     }
-    struct Regs { typename Raw4<AT>::type x[NXS][2], d[NDS][2], z[GB ? NDS : 1][2]; };
+    struct Regs { typename Raw4<AT>::type x[NXI][2], d[NDS][2], z[GB ? NDS : 1][2]; };
     float bsum[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) bsum[i] = 0.f;
@@ -802,15 +825,20 @@ __global__ __launch_bounds__(kBlock, 1) void conv_dwbx_k(const ConvBwdWArgs A) {
     struct Geo { int b, y0, x0; };
     auto geo_of = [&](int tl) { Geo g; tile_of(tl, g.b, g.y0, g.x0); return g; };
     auto load_item = [&](int i, const Geo& g, Regs& R) {
-        if (i < NXS) {
+        if (i < NXI) {
             const int k = i;
-            int gy = g.y0 + xly[k] - PT, gx = g.x0 + xlx[k] - PT;         // position in the conv-input (high-res) image
-            gy = gy < 0 ? 0 : (gy >= A.H ? A.H - 1 : gy); gx = gx < 0 ? 0 : (gx >= A.W ? A.W - 1 : gx);
-            const int sy = UP ? gy >> 1 : gy, sx = UP ? gx >> 1 : gx;
+            int sy, sx;                                                   // position in the source image
+            if constexpr (UP) {
+                sy = (g.y0 >> 1) + xly[k]; sx = (g.x0 >> 1) + xlx[k];
+                sy = sy >= Hs ? Hs - 1 : sy; sx = sx >= Ws ? Ws - 1 : sx;
+            } else {
+                sy = g.y0 + xly[k] - PT; sx = g.x0 + xlx[k] - PT;
+                sy = sy < 0 ? 0 : (sy >= A.H ? A.H - 1 : sy); sx = sx < 0 ? 0 : (sx >= A.W ? A.W - 1 : sx);
+            }
             const AT* p = xsrc + (((size_t)g.b * Hs + sy) * Ws + sx) * Cs;
             R.x[k][0] = ldraw4<AT>(p); R.x[k][1] = ldraw4<AT>(p + 4);
         } else {
-            const int k = i - NXS;
+            const int k = i - NXI;
             const int P = (tid >> 2) + k * (kBlock / 4);
             int py = g.y0 + P / TW, px = g.x0 + P % TW;
             py = py >= A.H ? A.H - 1 : py; px = px >= A.W ? A.W - 1 : px;
@@ -821,28 +849,36 @@ __global__ __launch_bounds__(kBlock, 1) void conv_dwbx_k(const ConvBwdWArgs A) {
     };
     // `live`: false for the dummy store issued behind the last tile (keeps the loop body branch-free)
     auto store_item = [&](int i, const Geo& g, const Regs& R, int buf, bool live) {
-        if (i < NXS) {
+        if (i < NXI) {
             const int k = i;
             const float4 v0 = widen4(R.x[k][0]), v1 = widen4(R.x[k][1]);
             float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-            const int gy = g.y0 + xly[k] - PT, gx = g.x0 + xlx[k] - PT;
-            const bool in = gy >= 0 && gy < A.H && gx >= 0 && gx < A.W;
+            // UP: the image is 2 Hs x 2 Ws, so the slots a footprint pixel covers lie inside it exactly when the pixel lies
+            // inside the low-res image: a slot outside gets zeros, as it did slot by slot
+            const int sy = UP ? (g.y0 >> 1) + xly[k] : g.y0 + xly[k] - PT, sx = UP ? (g.x0 >> 1) + xlx[k] : g.x0 + xlx[k] - PT;
+            const bool in = sy >= 0 && sy < Hs && sx >= 0 && sx < Ws;
             act8(v, fa, fb, lo, in);
             if constexpr (DROP) {              // (only the up-conv behind the bottleneck; compile-time: a runtime branch here
                                                //  would cut the conversion out of the basic block that holds the MFMAs)
-                const int sy = UP ? gy >> 1 : gy, sx = UP ? gx >> 1 : gx;
                 const uint32_t el = (uint32_t)((((size_t)g.b * Hs + sy) * Ws + sx) * Cs + ccx);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) v[e] = in ? v[e] * drop_mul(A.drop, el + e) : 0.f;
             }
             uint4 pl[NS];
             split8<NS>(v, pl);
-            const int P = (tid >> 2) + k * (kBlock / 4);
-            char* d = smem + buf * BUF_B + o8 * 2 + P * 64;
+            char* d = smem + buf * BUF_B + o8 * 2;
+            if constexpr (UP) {
 #pragma unroll
-            for (int p = 0; p < NS; ++p) *reinterpret_cast<uint4*>(d + p * XPL) = pl[p];
+                for (int c = 0; c < XCP; ++c)
+#pragma unroll
+                    for (int p = 0; p < NS; ++p) *reinterpret_cast<uint4*>(d + xsl[c] + p * XPL) = pl[p];
+            } else {
+                const int P = (tid >> 2) + k * (kBlock / 4);
+#pragma unroll
+                for (int p = 0; p < NS; ++p) *reinterpret_cast<uint4*>(d + P * 64 + p * XPL) = pl[p];
+            }
         } else {
-            const int k = i - NXS;
+            const int k = i - NXI;
             const int P = (tid >> 2) + k * (kBlock / 4);
             const bool in = live && g.y0 + P / TW < A.H && g.x0 + P % TW < A.W;
             const float4 v0 = widen4(R.d[k][0]), v1 = widen4(R.d[k][1]);
@@ -864,7 +900,7 @@ __global__ __launch_bounds__(kBlock, 1) void conv_dwbx_k(const ConvBwdWArgs A) {
             for (int p = 0; p < NS; ++p) *reinterpret_cast<uint4*>(d + p * DPL) = pl[p];
         }
     };
-    constexpr int NIT = NXS + NDS;
+    constexpr int NIT = NXI + NDS;
     auto load = [&](int tl, Regs& R) {
         const Geo g = geo_of(tl);
 #pragma unroll
@@ -933,8 +969,8 @@ __global__ __launch_bounds__(kBlock, 1) void conv_dwbx_k(const ConvBwdWArgs A) {
         }
         __builtin_amdgcn_s_setprio(0);
         constexpr int NPROD = NS == 3 ? 6 : 1, RPF = 2 * NS;                 // MFMAs per step; LDS reads per fragment fetch
-        constexpr int VPS = NS == 3 ? (UP ? 40 : 26) : (UP ? 24 : 14);      // conversion VALU placed under a step's MFMAs
-        constexpr int WPS = NS;                                             // LDS writes of one staging item
+        constexpr int VPS = NS == 3 ? (UP ? 32 : 26) : (UP ? 24 : 14);      // conversion VALU placed under a step's MFMAs
+        constexpr int WPS = NS;                                             // LDS writes of one staging item per slot
         __builtin_amdgcn_sched_group_barrier(0x100, 3 * RPF, 0);
 #pragma unroll
         for (int st = 0; st < STEPS; ++st) {
@@ -943,8 +979,9 @@ __global__ __launch_bounds__(kBlock, 1) void conv_dwbx_k(const ConvBwdWArgs A) {
             __builtin_amdgcn_sched_group_barrier(0x008, NPROD, 0);
             __builtin_amdgcn_sched_group_barrier(0x002, VPS, 0);
             if (((st + 1) * NIT) / STEPS != (st * NIT) / STEPS) {           // a staging item ends behind this step
-                __builtin_amdgcn_sched_group_barrier(0x200, WPS, 0);
-                if (GB && (st * NIT) / STEPS >= NXS) __builtin_amdgcn_sched_group_barrier(0x020, 4, 0);   // and its registers are
+                if ((st * NIT) / STEPS < NXI) __builtin_amdgcn_sched_group_barrier(0x200, XCP * WPS, 0);     // (UP: every covered slot)
+                else __builtin_amdgcn_sched_group_barrier(0x200, WPS, 0);
+                if (GB && (st * NIT) / STEPS >= NXI) __builtin_amdgcn_sched_group_barrier(0x020, 4, 0);   // and its registers are
                 else __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);                                  // re-loaded for tile t+2
             }
         }
@@ -998,9 +1035,8 @@ __global__ __launch_bounds__(kBlock, 1) void conv_dwbx_k(const ConvBwdWArgs A) {
                              (w0.z + w1.z) + (w2.z + w3.z), (w0.w + w1.w) + (w2.w + w3.w)};
         const int col = lane & 31, row0 = 8 * q + 4 * (lane >> 5);            // C/D layout: row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
 #pragma unroll
-        for (int jr = 0; jr < 4; ++jr)
-            if (ci0 + row0 + jr < A.Cin && co0 + col < A.Cout)
-                out[((size_t)t * A.Cin + ci0 + row0 + jr) * A.Cout + co0 + col] = sv[jr];
+        for (int jr = 0; jr < 4; ++jr)           // (Cin and Cout are multiples of 32 -- launch_dw_bf16pipe refuses others: every row and column exists)
+            out[((size_t)t * A.Cin + ci0 + row0 + jr) * A.Cout + co0 + col] = sv[jr];
     }
     __syncthreads();
     float* const bs = red + 4096;

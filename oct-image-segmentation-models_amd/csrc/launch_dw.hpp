@@ -33,6 +33,9 @@ int launch_dw_bf16pipe(const ConvBwdWArgs& a, const DwPlan& p, int kh, bool up, 
         return 0;
     }
     if (p.kind != DW_BX) return fail(-3, "launch_dw_bf16pipe: bad kind");
+    // the kernel stages whole channel octets of a 32 x 32 chunk and stores its slab unguarded
+    if (a.Cin % 32 || a.Cout % 32) return fail(-3, "conv_dwbx_k: input and output channels must be multiples of 32");
+    if (up && ((a.H | a.W) & 1)) return fail(-3, "conv_dwbx_k: the up-conv's image is twice its source, rows and columns");
     dim3 grid(p.npb, a.Cin / 32, a.Cout / 32), block(kBlock);
     char nm[72]; snprintf(nm, sizeof nm, "conv_dwbx_k<%d,%s,%d,%s%s>", kh, up ? "true" : "false", bf ? 1 : 3, AT_NAME(bf), gb ? ",gb" : "");
     ProfScope ps(s, nm, c.layer, c.flops, c.bytes);
