@@ -53,7 +53,10 @@ typedef void* oct_stream_t;         /* a hipStream_t (NULL = default stream) */
 
 typedef struct oct_unet_cfg {
     int in_ch;            /* input_channels                       (unet.py:65)          */
-    int n_cls;            /* num_classes, 2..8                    (training.py:176)     */
+    int n_cls;            /* num_classes, 2..16                   (training.py:176).  9..16 run   */
+                          /*     the class-streaming head kernels (kernels_head_cls.hpp).  The   */
+                          /*     probability maps are indexed with 32 bits downstream:           */
+                          /*     max_batch*H*W*n_cls < 2^31 -- at 16 classes max_batch*H*W < 2^27 */
     int H, W;             /* image_height, image_width; multiples of 2^pool_layers     */
     int max_batch;        /* largest per-rank batch any call will pass                  */
     int start_neurons;    /* default 8; multiple of 4 in 4..64    (unet.py:69).  Widths  */
@@ -146,7 +149,8 @@ int oct_unet_set_bce_dice(oct_unet* h, int on);
 int oct_unet_loss_bce_dice(oct_unet* h, float smooth, float* out8_dev, oct_stream_t stream);
 /* Ignore label: pixels whose label byte equals `label` do not count in the loss.  Per handle; holds for the following
  * forward / loss / backward calls (a forward made under another setting cannot be finalized or differentiated: call
- * forward again).  label = -1 [default] switches it off; n_classes..255 are accepted, anything else is an argument error.
+ * forward again).  label = -1 [default] switches it off; n_classes..255 (n_classes up to 16) are accepted, anything else is an
+ * argument error.
  * Without it a label byte >= n_classes is NOT ignored: such a pixel has an all-zero one-hot row and still counts in P, Ph
  * and the gradient.  With it, a pixel of that label
  *   - adds nothing to the Dice sums I, T, P, Ih, Ph of any class, nor to the focal / BCE sum; probs and argmax are
@@ -501,6 +505,8 @@ int oct_warp_batch(const unsigned char* x_u8_dev, const unsigned char* labels_de
  * (uint8: `value` must be a whole number in 0..255; float32: `value` itself).  Hp == H, Wp == W is a copy.
  * oct_crop_batch is the inverse window: out[b, y, x] = in[b, y + top, x + left] over (B,Hp,Wp) pixels of `pixel_bytes`
  * bytes each -- 1 for arg-max maps, 4 for entropy / mutual information, 4 n_cls for probabilities; the kernel moves bytes.
+ * (A pixel of more than 32 bytes, the probabilities of 9..16 classes, is cropped as 4-byte pixels of rows n_cls times as
+ * long, with `left` scaled alike: oct_unet_infer and UNetEngine.crop do so.)
  * Stand-alone: no handle, no allocation, one asynchronous launch on `stream` each, graph-capturable.  common/utils.py
  * pad_reference / crop_reference restate them; padded_geometry there holds THE placement rule of the callers
  * (top = (Hp - H) / 2, left = (Wp - W) / 2, floor: the odd pixel goes to the bottom / right).

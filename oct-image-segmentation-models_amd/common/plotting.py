@@ -38,6 +38,20 @@ def region_palette(num_classes: int) -> np.ndarray:
     return np.array(REGION_COLOURS[:int(num_classes)], np.uint8)
 
 
+# The truth + prediction overlay draws 2 (num_classes - 1) lines out of MAX_LINES, and a picture's lines and regions take
+# their colours from the 12-entry tables above: pictures exist up to this class count
+PNG_MAX_CLASSES = MAX_LINES // 2 + 1
+
+
+def check_png_classes(png_plots: bool, num_classes: int) -> bool:
+    """``png_plots`` as a bool; ``ValueError`` where pictures are asked for with more classes than the renderer holds.  The
+    parameter objects of ``evaluate_model`` / ``predict`` call it, so nothing has run when it raises."""
+    if png_plots and int(num_classes) > PNG_MAX_CLASSES:
+        raise ValueError(f"png_plots=True needs num_classes <= {PNG_MAX_CLASSES} (an overlay draws 2 (num_classes - 1) lines, the "
+                         f"renderer holds {MAX_LINES}), not {int(num_classes)}; png_plots=False works up to 16 classes")
+    return bool(png_plots)
+
+
 def half_width_of(linewidth: float) -> int:
     """A matplotlib line width in points at 100 dpi -> the half width in eighths of a pixel (4.0 -> 22)."""
     return int(round(float(linewidth) * 100.0 / 72.0 * 4.0))

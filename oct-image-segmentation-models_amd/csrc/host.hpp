@@ -169,6 +169,16 @@ int launch_dw_f32pipe(const oct::ConvBwdWArgs& a, const DwPlan& p, int kh, bool 
 int launch_head_fwd_wide(const oct::HeadFwdArgs& a, int C, int cin, int B, hipStream_t s);
 int launch_head_bwd_wide(const oct::HeadBwdArgs& a, int C, int cin, int B, hipStream_t s);
 
+// Class-streaming head (kernels_head_cls.hpp): C in 9..16 classes, cin as above; same argument blocks, buffers and layouts.
+// tu_head_cls.hip holds the two launchers; the kernels are instantiated four class counts to a unit (launch_head_cls.hpp),
+// head_cls_launch_<0 forward | 1 backward>_<first C>.
+int launch_head_fwd_cls(const oct::HeadFwdArgs& a, int C, int cin, int B, hipStream_t s);
+int launch_head_bwd_cls(const oct::HeadBwdArgs& a, int C, int cin, int B, hipStream_t s);
+int head_cls_launch_0_9(const oct::HeadFwdArgs& a, int C, int cin, dim3 grid, hipStream_t s);
+int head_cls_launch_0_13(const oct::HeadFwdArgs& a, int C, int cin, dim3 grid, hipStream_t s);
+int head_cls_launch_1_9(const oct::HeadBwdArgs& a, int C, int cin, dim3 grid, hipStream_t s);
+int head_cls_launch_1_13(const oct::HeadBwdArgs& a, int C, int cin, dim3 grid, hipStream_t s);
+
 // Monte-Carlo dropout reduction (tu_mc.hip): every argument error of oct_mc_update(probs, ..., t, T, ws, ws_bytes, out), with
 // nothing launched -- oct_unet_infer (kind MC) asks about its last sample before its first launch
 int mc_validate(const float* probs, int B, int H, int W, int n_cls, int t, int T, const void* ws, size_t ws_bytes,

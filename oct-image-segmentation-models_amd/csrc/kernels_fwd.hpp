@@ -302,7 +302,10 @@ __global__ __launch_bounds__(kBlock) void pool_fwd_k(const AT* __restrict__ z, c
 
 // ---- head: BN+ReLU on load, 1x1 conv, softmax, optional probs / argmax / Dice partial sums ---------------
 constexpr int kDiceVals = 5;  // per class: I = sum y*p, T = sum y, P = sum p, Ih = sum y*[p>.5], Ph = sum [p>.5]
-template <int C> struct DiceN { static constexpr int value = (5 * C <= 16) ? 16 : (5 * C <= 32 ? 32 : 64); };
+// floats of a Dice partial row: 5 C sums and slot 5 C.  Up to 12 classes a power of two (one block_reduce_store); 13..16
+// classes need 66..81 and take 96 = 64 + 32 (kernels_head_cls.hpp).  oct_unet.hip::dice_n is the run-time twin.
+constexpr int dice_row_floats(int C) { return 5 * C <= 16 ? 16 : (5 * C <= 32 ? 32 : (5 * C < 64 ? 64 : 96)); }
+template <int C> struct DiceN { static constexpr int value = dice_row_floats(C); };
 
 struct HeadFwdArgs {
     const void* z; const float* ab;    // last conv's raw output (activation storage type) + BN record

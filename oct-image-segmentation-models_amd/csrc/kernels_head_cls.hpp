@@ -1,62 +1,35 @@
-// Channel-streaming head kernels: the head of kernels_fwd.hpp / kernels_bwd.hpp with the input channel count CIN (=
-// start_neurons) as a RUNTIME argument, any multiple of 4 up to 64.  The register kernels keep a pixel's CIN activations and,
-// in the backward pass, CIN*C + C + 2*CIN per-thread partial sums in VGPRs (264 accumulators at CIN 32, C 8); these keep
-// nothing that grows with CIN:
-//   * the logits are accumulated while z streams past in 16-byte steps (same fmaf chain per class, channel by channel, as
-//     head_logits: the probabilities are bit-identical to the register kernels');
-//   * the backward kernel reads z a second time (L2) in groups of 16 channels.  Per group every wave writes y, the masked
-//     a = sum_c w dl and a * xhat of its 64 pixels to LDS tiles [pixel][16], dl once per chunk as [pixel][C padded to 16],
-//     and forms the sums over pixels with v_mfma_f32_16x16x4_f32 (an exact fp32 fma chain), K = pixels:
-//         dW[ch][c] = y^T dl,   sum a = a^T 1,   sum a xhat = (a xhat)^T 1,   db[c] = dl^T 1
-//     Lane l reads tile[4t + (l >> 4)][l & 15] = word 64 t + l: 64 consecutive words, conflict-free, for both operands.
-//     13 accumulators of 4 VGPRs (3 per channel group + the bias) are carried across the chunks a block walks.
-// Summation order: MFMA k-steps in pixel order within a wave's 64 pixels, chunk after chunk, then (w0 + w1) + (w2 + w3)
-// over the block's waves: fixed, so two runs give the same bits.  No atomics.  Invalid lanes of a ragged last chunk write
-// dl = 0 and a = 0 (and a finite y of pixel 0), i.e. exact zeros into every sum; so do the pixels of the ignore label.
-// Same buffers, same layouts as the register kernels: probs / argmax / Dice rows, g, part [B*nblk][2*CIN], wpart
-// [B*nblk][CIN*C + C].  grid (nblk, B), a block walks chunks blockIdx.x, + nblk, ... of one image.
-// Routing (oct_unet.hip): C = 2..8 with start_neurons > 32, or every width under option "head_wide".  C = 9..16 is
-// kernels_head_cls.hpp at every width; it shares head_logits_stream below, so its probabilities are formed the same way.
+// Class-streaming head kernels: the head for C = 9..16 classes, head_fwd_cls_k<C, AT> / head_bwd_cls_k<C, AT>.  The register
+// kernels (kernels_fwd.hpp / kernels_bwd.hpp) and the channel-streaming ones (kernels_head_wide.hpp) stop at 8 classes; these
+// take every class count above, at every start_neurons 4..64 (CIN is a RUNTIME argument, as in kernels_head_wide.hpp), and
+// nothing below.  They are the channel-streaming kernels with what 16 classes change:
+//   * probabilities: head_logits_stream, the same function in both kernels -- the backward pass recomputes the forward's
+//     probabilities bit for bit.  Same max-subtract / expf / one reciprocal, same first-maximum arg-max.
+//   * forward loss sums: a thread carries 5 C Dice sums and the focal / BCE sum at slot 5 C.  DiceN<C> = 64 holds them up to
+//     C = 12 (61 slots); C = 13..16 (66..81 slots) take rows of 96 floats, reduced as 64 + 32 by two block_reduce_store
+//     calls (fixed order).  dice_finalize_k takes C and the row width at run time.
+//   * backward: the Dice derivative of class c takes one of two values per block, dp(y = 0) and dp(y = 1), formed once in
+//     front of the chunk loop from the block-uniform (Num, Den) pair by the expression head_bwd_k evaluates per pixel (same
+//     bits) and kept in SGPRs: 2 C scalar registers instead of 2 C VGPRs and C divisions per pixel.
+//   * the BCE term is formed in a pass of its own over the classes, into the dl registers, after the Dice / focal term:
+//     q, db and the O(C^2) Jacobian sum are live only inside it.
+//   * dl goes to the [pixel][16] LDS tile, all 16 columns in use at C = 16; the sums over pixels are the fp32 MFMA chains of
+//     head_bwd_wide_k (mfma_f32_16x16x4_f32, K = pixels, fixed order, no atomics).
+// Same buffers and layouts as the other head kernels: probs / argmax / Dice rows [B][nblk][DiceN], g, part [B*nblk][2*CIN],
+// wpart [B*nblk][CIN*C + C].  grid (nblk, B), a block walks chunks blockIdx.x, + nblk, ... of one image.  Invalid lanes of
+// a ragged last chunk and pixels of the ignore label add exact zeros to every sum.
 #pragma once
-#include "kernels_bwd.hpp"
-#include "kernels_fwd.hpp"
+#include "kernels_head_wide.hpp"
 
 namespace oct {
 
-constexpr int kHeadWideMaxCin = 64;
-typedef float hw_f32x4 __attribute__((ext_vector_type(4)));
-
-// softmax probabilities of one pixel, z streamed from memory: head_logits without the y[] / zr[] arrays
-template <int C, typename AT>
-__device__ inline void head_logits_stream(const AT* __restrict__ zp, const float* __restrict__ ab, const float* __restrict__ w,
-                                          const float* __restrict__ bias, const int CIN, float (&p)[C]) {
-#pragma unroll
-    for (int c = 0; c < C; ++c) p[c] = bias[c];
-#pragma unroll 4
-    for (int i = 0; i < CIN; i += 4) {
-        const float4 v = lda4<AT>(zp + i);
-        const float zz[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float y = fmaxf(fmaf(ab[i + k], zz[k], ab[CIN + i + k]), 0.f);
-#pragma unroll
-            for (int c = 0; c < C; ++c) p[c] = fmaf(y, w[(i + k) * C + c], p[c]);
-        }
-    }
-    float mx = -3.4e38f;
-#pragma unroll
-    for (int c = 0; c < C; ++c) mx = fmaxf(mx, p[c]);
-    float sum = 0.f;
-#pragma unroll
-    for (int c = 0; c < C; ++c) { p[c] = expf(p[c] - mx); sum += p[c]; }
-    const float inv = 1.f / sum;
-#pragma unroll
-    for (int c = 0; c < C; ++c) p[c] *= inv;
-}
+constexpr int kHeadClsMin = 9, kHeadClsMax = 16;     // 16 = the columns of one dl tile
 
 template <int C, typename AT>
-__global__ __launch_bounds__(kBlock) void head_fwd_wide_k(const HeadFwdArgs A, const int CIN) {
+__global__ __launch_bounds__(kBlock) void head_fwd_cls_k(const HeadFwdArgs A, const int CIN) {
+    static_assert(C >= kHeadClsMin && C <= kHeadClsMax, "the class-streaming head carries 9..16 classes");
     constexpr int N = DiceN<C>::value;
+    static_assert(N == 64 || N == 96, "rows of 64 floats, or 64 + 32");
+    static_assert(C * kDiceVals < N, "slot 5 C is spare");
     __shared__ float red[256];
     const int b = blockIdx.y;
     float v[N];
@@ -70,8 +43,14 @@ __global__ __launch_bounds__(kBlock) void head_fwd_wide_k(const HeadFwdArgs A, c
         head_logits_stream<C, AT>(reinterpret_cast<const AT*>(A.z) + pix * CIN, A.ab, A.w, A.bias, CIN, p);
         if (valid) {
             if (A.probs) {
+                float* const o = A.probs + pix * C;
+                if constexpr (C % 4 == 0) {                 // rows of 16 C bytes: 16-byte aligned with the buffer
 #pragma unroll
-                for (int c = 0; c < C; ++c) A.probs[pix * C + c] = p[c];
+                    for (int c = 0; c < C; c += 4) st4(o + c, make_float4(p[c], p[c + 1], p[c + 2], p[c + 3]));
+                } else {
+#pragma unroll
+                    for (int c = 0; c < C; ++c) o[c] = p[c];
+                }
             }
             if (A.argmax) {
                 int am = 0; float best = p[0];
@@ -110,13 +89,29 @@ __global__ __launch_bounds__(kBlock) void head_fwd_wide_k(const HeadFwdArgs A, c
             }
         }
     }
-    if (A.labels) block_reduce_store<N>(v, red, A.dice_part + ((size_t)b * gridDim.x + blockIdx.x) * N, N);
+    if (A.labels) {
+        float* const out = A.dice_part + ((size_t)b * gridDim.x + blockIdx.x) * N;
+        if constexpr (N == 64) {
+            block_reduce_store<64>(v, red, out, 64);
+        } else {
+            float lo[64], hi[32];
+#pragma unroll
+            for (int i = 0; i < 64; ++i) lo[i] = v[i];
+#pragma unroll
+            for (int i = 0; i < 32; ++i) hi[i] = v[64 + i];
+            block_reduce_store<64>(lo, red, out, 64);
+            block_reduce_store<32>(hi, red, out + 64, 32);
+        }
+    }
 }
 
+// a wave-uniform float held in a scalar register
+__device__ __forceinline__ float head_uniform(float x) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x))); }
+
 template <int C, typename AT>
-__global__ __launch_bounds__(kBlock, 2) void head_bwd_wide_k(const HeadBwdArgs A, const int CIN) {
+__global__ __launch_bounds__(kBlock, 2) void head_bwd_cls_k(const HeadBwdArgs A, const int CIN) {
     constexpr int MAXG = kHeadWideMaxCin / 16, TILE = 64 * 16, NSLOT = 3 * MAXG + 1;
-    static_assert(C <= 16, "dl rows are padded to 16 columns");
+    static_assert(C >= kHeadClsMin && C <= kHeadClsMax, "the class-streaming head carries 9..16 classes; dl rows have 16 columns");
     static_assert(4 * NSLOT * 256 <= 4 * 4 * TILE, "the 4-wave sum reuses the tiles");
     __shared__ __attribute__((aligned(16))) float lds[4 * 4 * TILE];          // per wave: dl, y, a, a*xhat tiles of 64 pixels x 16
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -126,13 +121,16 @@ __global__ __launch_bounds__(kBlock, 2) void head_bwd_wide_k(const HeadBwdArgs A
 #pragma unroll
     for (int g = 0; g < MAXG; ++g) { accw[g] = hw_f32x4{0.f, 0.f, 0.f, 0.f}; acc1[g] = accw[g]; acc2[g] = accw[g]; }
     const float one = (lane & 15) == 0 ? 1.f : 0.f;      // B operand "column 0 = ones": D[row][0] = sum over pixels of A
-    float num[C], den[C];
+    const float scale = (1.f - A.focal_w) * (A.macro ? A.loss_scale / (float)(A.B * C) : A.loss_scale);
+    // Dice derivative of class c at a pixel whose label is / is not c: head_bwd_k's expression at y = 0 and y = 1
+    float dp0[C], dp1[C];
 #pragma unroll
     for (int c = 0; c < C; ++c) {
         const double* k = A.macro ? A.bc + 2 * (b * C + c) : A.bc + 2 * A.B * C;
-        num[c] = (float)k[0]; den[c] = (float)k[1];
+        const float num = (float)k[0], den = (float)k[1];
+        dp0[c] = head_uniform(-scale * (2.f * 0.f * den - num) / (den * den));
+        dp1[c] = head_uniform(-scale * (2.f * 1.f * den - num) / (den * den));
     }
-    const float scale = (1.f - A.focal_w) * (A.macro ? A.loss_scale / (float)(A.B * C) : A.loss_scale);
     const HeadMeans hm = head_means<C>(A);
     const float fscale = A.focal_w * A.loss_scale * hm.inv_count;
 
@@ -145,25 +143,25 @@ __global__ __launch_bounds__(kBlock, 2) void head_bwd_wide_k(const HeadBwdArgs A
         const bool counted = valid && lab != A.ignore;   // see head_bwd_k
         float p[C];
         head_logits_stream<C, AT>(zp, A.bn, A.w, A.bias, CIN, p);
-        float dp[C], dot = 0.f;
+        float dl[16], dot = 0.f;                         // dl holds dp until the Jacobian below
+#pragma unroll
+        for (int c = 0; c < 16; ++c) dl[c] = 0.f;
 #pragma unroll
         for (int c = 0; c < C; ++c) {
-            const float yv = lab == c ? 1.f : 0.f;
-            dp[c] = -scale * (2.f * yv * den[c] - num[c]) / (den[c] * den[c]);
+            dl[c] = lab == c ? dp1[c] : dp0[c];
             if (fscale != 0.f && lab == c) {        // focal term: see head_bwd_k
                 const bool inr = p[c] >= kFocalEps && p[c] <= 1.f - kFocalEps;
                 if (inr || !A.focal_clip_mod) {
                     const float pc = fminf(fmaxf(p[c], kFocalEps), 1.f - kFocalEps);
                     const float q = 1.f - p[c], cw = A.focal_cw ? A.focal_cw[c] : 1.f, qg1 = powf(q, A.focal_gamma - 1.f);
-                    dp[c] += fscale * cw * (A.focal_gamma * qg1 * logf(pc) - (inr ? qg1 * q / pc : 0.f));
+                    dl[c] += fscale * cw * (A.focal_gamma * qg1 * logf(pc) - (inr ? qg1 * q / pc : 0.f));
                 }
             }
-            dot = fmaf(p[c], dp[c], dot);
+            dot = fmaf(p[c], dl[c], dot);
         }
-        float dlb[C];
 #pragma unroll
-        for (int c = 0; c < C; ++c) dlb[c] = 0.f;
-        if (A.bce_on) {                             // BCE term: see head_bwd_k
+        for (int c = 0; c < C; ++c) dl[c] = counted ? p[c] * (dl[c] - dot) : 0.f;
+        if (A.bce_on) {                             // BCE term, a second pass over the classes: see head_bwd_k
             float q[C], db[C];
             softmax_complement<C>(p, q);
 #pragma unroll
@@ -177,14 +175,9 @@ __global__ __launch_bounds__(kBlock, 2) void head_bwd_wide_k(const HeadBwdArgs A
                 float o = 0.f;
 #pragma unroll
                 for (int k = 0; k < C; ++k) if (k != c) o = fmaf(p[k], db[k], o);
-                dlb[c] = p[c] * (q[c] * db[c] - o);
+                dl[c] += p[c] * (q[c] * db[c] - o);
             }
         }
-        float dl[16];
-#pragma unroll
-        for (int c = 0; c < 16; ++c) dl[c] = 0.f;
-#pragma unroll
-        for (int c = 0; c < C; ++c) dl[c] = (counted ? p[c] * (dp[c] - dot) : 0.f) + dlb[c];
 
         __syncthreads();                            // the previous chunk's operand reads are done
 #pragma unroll
@@ -229,8 +222,8 @@ __global__ __launch_bounds__(kBlock, 2) void head_bwd_wide_k(const HeadBwdArgs A
             }
         }
     }
-    // ---- 4-wave sum through LDS (fixed order), then the two partial rows.  Accumulator register r of lane l is
-    // D[row 4 (l >> 4) + r][column l & 15]; slot 3g + {0, 1, 2} = dW / sum a / sum a xhat of group g, slot 3 MAXG = the bias ----
+    // ---- 4-wave sum through LDS (fixed order), then the two partial rows: as head_bwd_wide_k.  Accumulator register r of
+    // lane l is D[row 4 (l >> 4) + r][column l & 15]; slot 3g + {0, 1, 2} = dW / sum a / sum a xhat of group g, slot 3 MAXG = the bias ----
     __syncthreads();
     float* const red = lds + wave * NSLOT * 256;
 #pragma unroll

@@ -76,7 +76,7 @@ struct Plan {
 int check_cfg(const oct_unet_cfg* c) {
     if (!c) return fail(-1, "null cfg");
     if (c->in_ch < 1) return fail(-1, "in_ch must be >= 1");
-    if (c->n_cls < 2 || c->n_cls > 8) return fail(-1, "n_cls must be in 2..8");
+    if (c->n_cls < 2 || c->n_cls > 16) return fail(-1, "n_cls must be in 2..16");
     if (c->pool_layers < 1 || c->pool_layers > 6) return fail(-1, "pool_layers must be in 1..6");
     if (c->conv_layers < 1) return fail(-1, "conv_layers must be >= 1");
     if (c->start_neurons < 4 || c->start_neurons > 64 || c->start_neurons % 4)
@@ -95,6 +95,9 @@ int check_cfg(const oct_unet_cfg* c) {
         return fail(-1, "bottleneck tensor too large for 32-bit dropout indexing");
     if ((size_t)c->max_batch * c->H * c->W * (size_t)(2 * c->start_neurons) >= (1ull << 31))
         return fail(-1, "max_batch * H * W too large for the 32-bit element indexing used inside a layer");
+    // (B,H,W,n_cls) probabilities: only at start_neurons 4 with more than 8 classes is this the tighter bound of the two
+    if ((size_t)c->max_batch * c->H * c->W * (size_t)c->n_cls >= (1ull << 31))
+        return fail(-1, "max_batch * H * W * n_cls must stay below 2^31 (32-bit element indexing of the probability maps)");
     return 0;
 }
 
@@ -313,8 +316,9 @@ size_t carve(const oct_unet_cfg& c, Plan& pl, oct_unet* h, char* base, const Opt
     const int nblk_head = cdiv(c.H * c.W, kBlock);
     stat_max = std::max(stat_max, B * nblk_head * 2 * (size_t)c.start_neurons);
     float* sp = (float*)take(stat_max * 4);
-    float* dp = (float*)take(B * nblk_head * 64 * 4);
-    double* bc = (double*)take((B * 8 * 2 + 3) * 8);       // per (b, c) pairs, the micro pair, 1 / (counted pixels)
+    // (rows of 64 floats and 8 pairs per image up to 8 classes, whatever n_cls: those workspaces keep their size)
+    float* dp = (float*)take(B * nblk_head * (size_t)std::max(64, dice_row_floats(c.n_cls)) * 4);
+    double* bc = (double*)take((B * std::max(8, c.n_cls) * 2 + 3) * 8);       // per (b, c) pairs, the micro pair, 1 / (counted pixels)
     float* l4 = (float*)take(8 * 4);
     unsigned* fc = (unsigned*)take(2 * pl.L.size() * sizeof(unsigned));
     if (h) h->fin_counters = fc;
@@ -468,7 +472,8 @@ int conv_forward(oct_unet* h, int li, const void* x_in, int x_is_u8, int B, int 
 
 // the register head kernels are instantiated for every start_neurons (= the head's input channels) up to 32: run
 // f(constant cin).  Wider heads, and every head under option "head_wide", take the channel-streaming kernels
-// (kernels_head_wide.hpp), whose register use does not grow with cin
+// (kernels_head_wide.hpp), whose register use does not grow with cin.  More than 8 classes: the class-streaming kernels
+// (kernels_head_cls.hpp) at every width, whatever "head_wide" says -- neither of the other two families is built there
 inline bool head_is_wide(const Options& o, int cin) { return cin > 32 || o.head_wide; }
 template <typename F>
 int head_cin_dispatch(int cin, F f) {
@@ -517,11 +522,12 @@ int launch_head_bwd(const HeadBwdArgs& a, int cin, int B, hipStream_t s, bool wi
             default: return fail(-3, "bad n_cls");      \
         }                                               \
     })()
+inline bool head_is_cls(int n_cls) { return n_cls > 8; }
 
 // blocks per image of the head kernels: ~2048 blocks in total, each walking several 256-pixel chunks
 int head_nblk(int HW, int B) { return std::max(1, std::min(cdiv(HW, kBlock), cdiv(2048, B))); }
 
-int dice_n(int C) { return 5 * C <= 16 ? 16 : (5 * C <= 32 ? 32 : 64); }
+int dice_n(int C) { return dice_row_floats(C); }
 
 // this step's weights in the operand layouts of the bf16-pipe conv kernels (split in fp32 mode, rounded in bf16 mode):
 // one launch per kernel family, over the forward descriptors or the backward-data ones (which read the prep_wt_k output)
@@ -603,7 +609,8 @@ int forward_head(oct_unet* h, int B, const oct_unet_io* io, hipStream_t s) {
     a.dice_part = h->dice_part; a.HW = hd.H * hd.W; a.nblk = head_nblk(a.HW, B); a.act_bf16 = h->cfg.dtype;
     a.focal_on = h->focal_w > 0.f; a.focal_gamma = h->focal_gamma; a.focal_cw = h->focal_cw; a.focal_clip_mod = h->opt.focal_clip_mod;
     a.bce_on = h->bce_on; a.bce_inner = h->opt.bce_inner_eps ? kFocalEps : 0.f; a.ignore = h->ignore;
-    const int rc = DISPATCH_C(launch_head_fwd, h->cfg.n_cls, a, hd.cin, B, s, head_is_wide(h->opt, hd.cin));
+    const int rc = head_is_cls(h->cfg.n_cls) ? launch_head_fwd_cls(a, h->cfg.n_cls, hd.cin, B, s)
+                                             : DISPATCH_C(launch_head_fwd, h->cfg.n_cls, a, hd.cin, B, s, head_is_wide(h->opt, hd.cin));
     if (rc) return rc;
     h->have_dice = a.labels != nullptr;
     return 0;
@@ -841,9 +848,11 @@ int head_backward(oct_unet* h, const unsigned char* labels, int macro, float los
     hb.focal_w = h->focal_w; hb.focal_gamma = h->focal_gamma; hb.focal_cw = h->focal_cw; hb.focal_clip_mod = h->opt.focal_clip_mod; hb.inv_count = 1.f / ((float)B * hb.HW);
     hb.bce_on = h->bce_on; hb.bce_inner = h->opt.bce_inner_eps ? kFocalEps : 0.f; hb.bce_scale = loss_scale * hb.inv_count / (float)h->cfg.n_cls;
     hb.ignore = h->ignore;       // >= 0: the kernels take 1 / (counted pixels) from dice_bc instead of inv_count
+    const bool cls = head_is_cls(h->cfg.n_cls);
     const bool wide = head_is_wide(h->opt, hd.cin);          // (only the register kernels finalize the statistics in the launch)
-    if (!wide && fin_ok(h, last)) { hb.fin = fin_desc(h, nl - 2, 1, B); *fin = true; }
+    if (!wide && !cls && fin_ok(h, last)) { hb.fin = fin_desc(h, nl - 2, 1, B); *fin = true; }
     *rows = B * hb.nblk;
+    if (cls) return launch_head_bwd_cls(hb, h->cfg.n_cls, hd.cin, B, s);
     return DISPATCH_C(launch_head_bwd, h->cfg.n_cls, hb, hd.cin, B, s, wide);
 }
 
@@ -1258,7 +1267,12 @@ static int infer_chain(oct_unet* h, const oct_infer& d, hipStream_t s) {
     if (d.x_pad_dev) {
         const MapSet from = map_set(d.out, c.n_cls), to = map_set(d.out_crop, c.n_cls);
         for (int i = 0; i < 4 && !rc; ++i)
-            if (to.p[i]) rc = oct_crop_batch(from.p[i], B, c.H, c.W, to.pb[i], d.H, d.W, d.top, d.left, to.p[i], s);
+            if (to.p[i]) {
+                // oct_crop_batch takes pixels of up to 32 bytes: the probabilities of more than 8 classes go as n_cls 4-byte
+                // pixels each (the kernel moves a row's bytes; a pixel is only what `left` and the widths count in)
+                const int k = to.pb[i] > 32 ? to.pb[i] / 4 : 1;
+                rc = oct_crop_batch(from.p[i], B, c.H, c.W * k, to.pb[i] / k, d.H, d.W * k, d.top, d.left * k, to.p[i], s);
+            }
     }
     return rc;
 }

@@ -1,6 +1,7 @@
 // One translation unit of liboct_unet_hip.so (see host.hpp): the channel-streaming head kernels (kernels_head_wide.hpp),
 // head_fwd_wide_k<C, AT> / head_bwd_wide_k<C, AT> for C = 2..8 classes and both activation storage types, behind the two
 // launchers oct_unet.hip routes start_neurons > 32 (or every width, option "head_wide") to.  Neither allocates or waits.
+// More than 8 classes never come here: at every width they take the class-streaming kernels (tu_head_cls.hip).
 #include <hip/hip_runtime.h>
 
 #include <cstdio>

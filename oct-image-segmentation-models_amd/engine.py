@@ -46,7 +46,18 @@ def make_cfg(*, input_channels: int, num_classes: int, image_height: int, image_
              enc_kernel: Sequence[int] = (3, 3), dec_kernel: Sequence[int] = (2, 2),
              max_batch: int = 1, training: bool = False, seed: int = 0,
              bn_eps: float = 1e-3, bn_momentum: float = 0.99, dropout_rate: float = 0.5,
-             bn_unbiased_moving_var: bool = True, dtype="float32") -> UNetCfg:
+             bn_unbiased_moving_var: bool = True, dtype="float32", max_classes: int = 8) -> UNetCfg:
+    """The checked configuration of an engine.
+
+    ``max_classes`` (8..16) is the largest ``num_classes`` this call accepts.  The library takes 2..16; the default here
+    stays at 8, the limit of the register and channel-streaming head kernels, so that a caller written against that limit
+    (and the test that pins ``num_classes=9`` as an error) meets it unchanged.  9..16 classes run the class-streaming head
+    kernels; ``Model`` always passes ``max_classes=16``, so the model classes, ``train_model``, ``evaluate_model`` and
+    ``predict`` need no opt-in."""
+    if not 8 <= int(max_classes) <= 16:
+        raise OctError(f"max_classes must be in 8..16, got {max_classes}")
+    if num_classes > max_classes:
+        raise OctError(f"num_classes {num_classes} exceeds max_classes {max_classes} (pass max_classes up to 16)")
     ek, dk = tuple(enc_kernel), tuple(dec_kernel)
     if ek[0] != ek[1] or dk[0] != dk[1]:
         raise OctError("only square kernels are supported")
@@ -641,8 +652,10 @@ class UNetEngine:
         if out is None:
             out = torch.empty(shape, dtype=t.dtype, device=self.device)
         _hip.expect(out, "crop: out", device=self.device, dtype=t.dtype, shape=shape)
-        _hip.call("oct_crop_batch", self.device, t.data_ptr(), B, Hp, Wp, t.element_size() * int(np.prod(t.shape[3:], dtype=np.int64)),
-                  int(H), int(W), int(top), int(left), out.data_ptr(), self._stream())
+        pb = t.element_size() * int(np.prod(t.shape[3:], dtype=np.int64))
+        k = pb // 4 if pb > 32 and pb % 4 == 0 else 1      # the call takes pixels of up to 32 bytes: wider ones go as 4-byte pixels
+        _hip.call("oct_crop_batch", self.device, t.data_ptr(), B, Hp, Wp * k, pb // k,
+                  int(H), int(W) * k, int(top), int(left) * k, out.data_ptr(), self._stream())
         return out
 
     # ---- weights exchange --------------------------------------------------------------------------

@@ -7,7 +7,7 @@ import logging as log
 from pathlib import Path
 from typing import List, Optional
 
-from ..common import EVALUATION_METRICS, utils
+from ..common import EVALUATION_METRICS, plotting, utils
 from .dice_device import check_ignore_label
 
 
@@ -83,6 +83,7 @@ class EvaluationParameters:
         self.loaded_model, self.model_config = utils.load_model_and_config(
             self.model_path, mlflow_tracking_uri=mlflow_tracking_uri, mlflow_run_uuid=mlflow_run_uuid)
         self.num_classes = self.loaded_model.output.shape[-1]
+        plotting.check_png_classes(self.png_plots, self.num_classes)     # pictures exist up to 9 classes: refused here, up front
         # extension: the test set's labels are known in part only (annotated column ranges, masked optic-nerve heads): ground-truth
         # pixels of this value, an int in num_classes..255, are "unknown" wherever a metric, a truth boundary or a ground-truth
         # picture is formed -- out of the Dice counts, no surface element at their rim, no truth boundary underneath them,

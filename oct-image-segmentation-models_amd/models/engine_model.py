@@ -166,7 +166,8 @@ class Model:
                     start_neurons=c.get("start_neurons", 8), pool_layers=c.get("pool_layers", 4),
                     conv_layers=c.get("conv_layers", 2), enc_kernel=tuple(c.get("enc_kernel", (3, 3))),
                     dec_kernel=tuple(c.get("dec_kernel", (2, 2))),
-                    dtype=c.get("dtype", "float32"))   # extension key: 'bfloat16' = bf16 activation storage (BASELINE configs[2])
+                    dtype=c.get("dtype", "float32"),   # extension key: 'bfloat16' = bf16 activation storage (BASELINE configs[2])
+                    max_classes=16)                    # the model follows the data: every class count the library takes
 
     def _mark_changed(self, eng) -> None:
         """``eng`` -- the active engine -- has changed the model's weights (an optimizer step, ``set_weights``, the moving

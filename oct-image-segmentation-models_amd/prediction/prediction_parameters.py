@@ -5,7 +5,7 @@ from __future__ import annotations
 from pathlib import Path
 from typing import Union
 
-from ..common import utils
+from ..common import plotting, utils
 from ..common.dataset import Dataset
 
 
@@ -68,6 +68,7 @@ class PredictionParams:
         # extension, as EvaluationParameters.png_plots: segmentation_map.png, raw_image.png and, with graph search,
         # gs_predicted_segmentation_map.png and gs_predicted_boundaries_ovelay_plot.png (columns col_error_range)
         self.png_plots = bool(png_plots)
+        plotting.check_png_classes(self.png_plots, self.num_classes)     # pictures exist up to 9 classes: refused here, up front
         # extension: Monte-Carlo dropout prediction.  mc_samples > 0: every batch is predicted mc_samples times with the
         # bottleneck dropout on (dropout steps mc_step0 .. mc_step0+mc_samples-1, the same for every batch); the class maps,
         # boundary maps and everything behind them are those of the mean prediction, and prediction_info.hdf5 gains
