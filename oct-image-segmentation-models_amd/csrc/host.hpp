@@ -2,7 +2,8 @@
 // HIP-event profiler, the ONE shape rule that says which bf16-pipe kernel family can serve a conv launch (pipe_fit) and the
 // signatures of the conv launchers.  The library is built from several .hip files compiled in parallel (build.sh):
 // oct_unet.hip holds the plan (build_plan / carve at creation, plan_backward per backward call), the C ABI and the
-// streaming kernels; tu_*.hip each instantiate one family of the MFMA conv kernels behind the launcher declared here.
+// streaming kernels; tu_*.hip each instantiate one family of kernels (the MFMA convs, the head, ...) behind the launcher
+// declared here.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -14,7 +15,6 @@
 #include "kernels_bwd.hpp"
 #include "kernels_igemm.hpp"
 
-namespace oct { struct HeadFwdArgs; }     // kernels_fwd.hpp
 struct oct_mc_out;                        // include/oct_unet.h
 
 namespace octh {
@@ -164,20 +164,34 @@ struct DwPlan { DwKind kind; int cic, coc, th, chunks, npb, tiles; };
 int launch_dw_bf16pipe(const oct::ConvBwdWArgs& a, const DwPlan& p, int kh, bool up, const LaunchCtx& c);
 int launch_dw_f32pipe(const oct::ConvBwdWArgs& a, const DwPlan& p, int kh, bool up, const LaunchCtx& c);
 
-// Channel-streaming head (kernels_head_wide.hpp, instantiated in tu_head_wide.hip): C classes, cin a runtime multiple of 4 in
-// 4..64.  Same argument blocks and output buffers as the register kernels of oct_unet.hip; a.fin must be empty.
-int launch_head_fwd_wide(const oct::HeadFwdArgs& a, int C, int cin, int B, hipStream_t s);
-int launch_head_bwd_wide(const oct::HeadBwdArgs& a, int C, int cin, int B, hipStream_t s);
-
-// Class-streaming head (kernels_head_cls.hpp): C in 9..16 classes, cin as above; same argument blocks, buffers and layouts.
-// tu_head_cls.hip holds the two launchers; the kernels are instantiated four class counts to a unit (launch_head_cls.hpp),
-// head_cls_launch_<0 forward | 1 backward>_<first C>.
-int launch_head_fwd_cls(const oct::HeadFwdArgs& a, int C, int cin, int B, hipStream_t s);
-int launch_head_bwd_cls(const oct::HeadBwdArgs& a, int C, int cin, int B, hipStream_t s);
-int head_cls_launch_0_9(const oct::HeadFwdArgs& a, int C, int cin, dim3 grid, hipStream_t s);
-int head_cls_launch_0_13(const oct::HeadFwdArgs& a, int C, int cin, dim3 grid, hipStream_t s);
-int head_cls_launch_1_9(const oct::HeadBwdArgs& a, int C, int cin, dim3 grid, hipStream_t s);
-int head_cls_launch_1_13(const oct::HeadBwdArgs& a, int C, int cin, dim3 grid, hipStream_t s);
+// The head's kernel family (kernels_head.hpp, kernels_head_wide.hpp, kernels_head_cls.hpp).  THE routing rule of the head: forward_head, head_backward and the gate of the
+// in-launch statistics finalize (register kernels only) ask here.  The register kernels are instantiated for every
+// start_neurons (= the head's input channels) up to 32; wider heads, and every head under option "head_wide", take the
+// channel-streaming kernels, whose register use does not grow with cin.  More than 8 classes: the class-streaming kernels at
+// every width, whatever "head_wide" says -- neither of the other two families is built there.
+enum HeadRoute { HEAD_REG = 0, HEAD_WIDE = 1, HEAD_CLS = 2 };
+inline HeadRoute head_route(const Options& o, int n_cls, int cin) {
+    return n_cls >= oct::kHeadClsMin ? HEAD_CLS : (cin > 32 || o.head_wide ? HEAD_WIDE : HEAD_REG);
+}
+// The two head launchers (tu_head.hip): C classes, cin input channels, on the family r.  Same argument blocks, output buffers
+// and layouts on every family; a.fin is for HEAD_REG alone.  Neither allocates or waits.
+int launch_head_fwd(const oct::HeadFwdArgs& a, HeadRoute r, int C, int cin, int B, hipStream_t s);
+int launch_head_bwd(const oct::HeadBwdArgs& a, HeadRoute r, int C, int cin, int B, hipStream_t s);
+// The kernels are instantiated a class range to a translation unit (launch_head.hpp; tu_head_<family>_<direction>_<first C>.hip),
+// sized so that build.sh compiles them side by side and none is the slowest unit of the build.  X(family, direction: 0 forward |
+// 1 backward, first C, last C); unit X's entry point is head_unit_<family>_<direction>_<first C>.  A unit whose four defines are
+// not a row of this list does not compile (launch_head.hpp).
+#define OCT_HEAD_UNITS(X)                                             \
+    X(0, 0, 2, 5) X(0, 0, 6, 8)                                       \
+    X(0, 1, 2, 4) X(0, 1, 5, 6) X(0, 1, 7, 7) X(0, 1, 8, 8)           \
+    X(1, 0, 2, 8) X(1, 1, 2, 8)                                       \
+    X(2, 0, 9, 12) X(2, 0, 13, 16) X(2, 1, 9, 12) X(2, 1, 13, 16)
+#define OCT_HEAD_UNIT_ARGS_0 ::oct::HeadFwdArgs
+#define OCT_HEAD_UNIT_ARGS_1 ::oct::HeadBwdArgs
+#define OCT_HEAD_UNIT_DECL(fam, bwd, c0, c1) \
+    int head_unit_##fam##_##bwd##_##c0(const OCT_HEAD_UNIT_ARGS_##bwd& a, int C, int cin, dim3 grid, hipStream_t s);
+OCT_HEAD_UNITS(OCT_HEAD_UNIT_DECL)
+#undef OCT_HEAD_UNIT_DECL
 
 // Monte-Carlo dropout reduction (tu_mc.hip): every argument error of oct_mc_update(probs, ..., t, T, ws, ws_bytes, out), with
 // nothing launched -- oct_unet_infer (kind MC) asks about its last sample before its first launch

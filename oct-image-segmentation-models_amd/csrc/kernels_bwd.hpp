@@ -237,152 +237,6 @@ static __global__ __launch_bounds__(kBlock) void bn_bwd_apply8_bf16_k(bf16_t* __
     }
 }
 
-// ---- head backward: Dice gradient -> softmax Jacobian -> 1x1 conv backward (data AND weights) -> mask + stats ------
-// Everything the head needs is in registers here (y, p, dlogits), so its dW/db are accumulated in the same pass:
-// no dlogits tensor, no second read of z.  grid (nblk, B); a block walks chunks of one image and emits one row of
-// BN-backward statistics and one row of head-weight partials.
-struct HeadBwdArgs {
-    const void* z; const float* bn;      // last conv block (z: activation storage type)
-    const float* w; const float* bias;   // head (CIN,C),(C)
-    const unsigned char* labels;
-    const double* bc;                    // Dice constants from dice_finalize_k
-    void* g;                             // (B,H,W,CIN) masked gradient of the last conv block (activation storage type)
-    float* part;                         // [B*nblk][2*CIN]       BN-backward statistics
-    float* wpart;                        // [B*nblk][CIN*C + C]   head kernel / bias gradient partials
-    int HW, nblk, B, macro; float loss_scale; int act_bf16;
-    // focal_dice_loss: L = w * focal + (1 - w) * dice  (focal_w = 0: plain Dice)
-    float focal_w, focal_gamma; const float* focal_cw; float inv_count;   // inv_count = 1 / (B*H*W)
-    int focal_clip_mod;                // see HeadFwdArgs
-    // bce_dice_loss: L = bce + dice_micro (focal_w = 0, macro = 0); bce_scale = loss_scale / (B*H*W*C)
-    int bce_on; float bce_inner, bce_scale;
-    // ignore label (oct_unet_set_ignore_label; -1 = off): dl of such a pixel is exactly 0 for every class, so g is stored as 0
-    // and the pixel adds nothing to the statistics or the head dW / db partials.  With it set, the means' 1 / (counted
-    // pixels) comes from bc[2*B*C + 2] (dice_finalize_k) and stands in for inv_count, also inside bce_scale
-    int ignore;
-    FinDesc fin;                       // BN-backward sums of the last conv block finalized by the last block (kernels_fin.hpp)
-};
-
-// the two constants of the focal / BCE means: the host's with the mask off, else formed from the device's count by the same
-// float expressions, read once in front of the chunk loop
-struct HeadMeans { float inv_count, bce_scale; };
-template <int C>
-__device__ __forceinline__ HeadMeans head_means(const HeadBwdArgs& A) {
-    HeadMeans m{A.inv_count, A.bce_scale};
-    if (A.ignore >= 0) { m.inv_count = (float)A.bc[2 * A.B * C + 2]; m.bce_scale = A.loss_scale * m.inv_count / (float)C; }
-    return m;
-}
-
-template <int C, int CIN, typename AT>
-__global__ __launch_bounds__(kBlock) void head_bwd_k(const HeadBwdArgs A) {
-    constexpr int NV = CIN * C + C, NG = (NV + 31) / 32;
-    constexpr int CP = CIN <= 4 ? 4 : (CIN <= 8 ? 8 : (CIN <= 16 ? 16 : 32));     // the block reduction takes powers of two
-    __shared__ float red[256];
-    const int b = blockIdx.y;
-    float s1[CP], s2[CP], wv[NG * 32];
-#pragma unroll
-    for (int i = 0; i < CP; ++i) { s1[i] = 0.f; s2[i] = 0.f; }
-#pragma unroll
-    for (int i = 0; i < NG * 32; ++i) wv[i] = 0.f;
-    float num[C], den[C];
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-        const double* k = A.macro ? A.bc + 2 * (b * C + c) : A.bc + 2 * A.B * C;
-        num[c] = (float)k[0]; den[c] = (float)k[1];
-    }
-    const float scale = (1.f - A.focal_w) * (A.macro ? A.loss_scale / (float)(A.B * C) : A.loss_scale);
-    const HeadMeans hm = head_means<C>(A);
-    const float fscale = A.focal_w * A.loss_scale * hm.inv_count;
-
-    HeadQueue<CIN, kHeadBwdAhead, AT> hq(reinterpret_cast<const AT*>(A.z) + (size_t)b * A.HW * CIN, A.labels + (size_t)b * A.HW, A.HW);
-    hq.fill(blockIdx.x, gridDim.x);
-    for (int chunk = blockIdx.x; chunk * kBlock < A.HW; chunk += gridDim.x) {
-        const int px = chunk * kBlock + threadIdx.x;
-        const bool valid = px < A.HW;
-        const size_t pix = (size_t)b * A.HW + (valid ? px : 0);
-        float y[CIN], zr[CIN], p[C];
-        const int lab = hq.pop(zr, chunk + kHeadBwdAhead * (int)gridDim.x);     // later chunks' pixels are requested before this one is used
-        const bool counted = valid && lab != A.ignore;  // folded into the selects that `valid` already feeds: no new branch
-        head_logits<C, CIN>(A.bn, A.w, A.bias, y, zr, p);
-        float dp[C], dot = 0.f;
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            const float yv = lab == c ? 1.f : 0.f;
-            dp[c] = -scale * (2.f * yv * den[c] - num[c]) / (den[c] * den[c]);
-            if (fscale != 0.f && lab == c) {
-                // d/dp [ cw (1-p)^g (-log pc) ],  pc = clip(p, eps, 1-eps):  cw ( g (1-p)^(g-1) log pc - (1-p)^g / pc * [p == pc] );
-                // with the modulation clipped too (focal_clip_mod) both terms vanish where the clip is active
-                const bool inr = p[c] >= kFocalEps && p[c] <= 1.f - kFocalEps;
-                if (inr || !A.focal_clip_mod) {
-                    const float pc = fminf(fmaxf(p[c], kFocalEps), 1.f - kFocalEps);
-                    const float q = 1.f - p[c], cw = A.focal_cw ? ldc(A.focal_cw + c) : 1.f, qg1 = powf(q, A.focal_gamma - 1.f);
-                    dp[c] += fscale * cw * (A.focal_gamma * qg1 * logf(pc) - (inr ? qg1 * q / pc : 0.f));
-                }
-            }
-            dot = fmaf(p[c], dp[c], dot);
-        }
-        // BCE half of bce_dice_loss.  The branch sits HERE, at the join behind the focal branch of the last class, and its
-        // result is added below unconditionally (x + 0 = x: the Dice and focal paths stay bit-identical): a branch between
-        // dl and the 1x1 backward costs <3, 8, float> 8 VGPRs (126 -> 134) and with them the fourth wave per SIMD
-        float dlb[C];
-#pragma unroll
-        for (int c = 0; c < C; ++c) dlb[c] = 0.f;
-        if (A.bce_on) {
-            // dBCE/dp_c = s ( -y/(pc + e) + (1 - y)/(qc + e) ) where neither clip is active.  With q = 1 - p and the usual
-            // p (dp - dot) the result is lost where p saturates: 1/q blows up exactly where 1 - p and dp - dot cancel
-            // (DESIGN.md section 11).  So q comes from the other classes' probabilities, and the Jacobian is applied as
-            //   dl_c = p_c ( q_c dp_c - sum_{k != c} p_k dp_k )
-            float q[C], db[C];
-            softmax_complement<C>(p, q);
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                const bool inr = counted && p[c] >= kFocalEps && q[c] >= kFocalEps;
-                const float r = hm.bce_scale / ((lab == c ? p[c] : q[c]) + A.bce_inner);     // y picks the term
-                db[c] = inr ? (lab == c ? -r : r) : 0.f;
-            }
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                float o = 0.f;
-#pragma unroll
-                for (int k = 0; k < C; ++k) if (k != c) o = fmaf(p[k], db[k], o);
-                dlb[c] = p[c] * (q[c] * db[c] - o);
-            }
-        }
-        float dl[C];
-#pragma unroll
-        for (int c = 0; c < C; ++c) { dl[c] = (counted ? p[c] * (dp[c] - dot) : 0.f) + dlb[c]; wv[CIN * C + c] += dl[c]; }
-        float g[CIN];
-#pragma unroll
-        for (int i = 0; i < CIN; ++i) {
-            float a = 0.f;
-#pragma unroll
-            for (int c = 0; c < C; ++c) { a = fmaf(ldc(A.w + i * C + c), dl[c], a); wv[i * C + c] = fmaf(y[i], dl[c], wv[i * C + c]); }
-            a = (valid && y[i] > 0.f) ? a : 0.f;
-            const float xh = (zr[i] - ldc(A.bn + BN_MEAN * CIN + i)) * ldc(A.bn + BN_RSTD * CIN + i);
-            g[i] = a; s1[i] += a; s2[i] += a * xh;
-        }
-        if (valid) {
-#pragma unroll
-            for (int i = 0; i < CIN; i += 4) sta4<AT>(reinterpret_cast<AT*>(A.g) + pix * CIN + i, make_float4(g[i], g[i + 1], g[i + 2], g[i + 3]));
-        }
-    }
-    const size_t row = (size_t)b * gridDim.x + blockIdx.x;
-    float* out = A.part + row * (2 * CIN);
-    block_reduce_store<CP, true>(s1, red, out, CIN);
-    block_reduce_store<CP, true>(s2, red, out + CIN, CIN);
-    float* wout = A.wpart + row * NV;
-#pragma unroll
-    for (int gi = 0; gi < NG; ++gi) {
-        float t[32];
-#pragma unroll
-        for (int k = 0; k < 32; ++k) t[k] = wv[gi * 32 + k];
-        block_reduce_store<32>(t, red, wout + gi * 32, NV - gi * 32 < 32 ? NV - gi * 32 : 32);
-    }
-    if (A.fin.counter) {
-        __shared__ __attribute__((aligned(16))) char fin_lds[16 + kBlock * 16 + 2 * CP * 8];
-        finalize_in_launch(A.fin, A.part, gridDim.x * gridDim.y, CIN, gridDim.x * gridDim.y, fin_lds);
-    }
-}
-
 // ---- conv backward-weights (LDS-staged tiles, per-block partial dW, deterministic second-stage sum) ------------
 struct ConvBwdWArgs {
     const void* x0; const float* ab0; int C0;   // conv input, same fetch semantics as the forward kernel

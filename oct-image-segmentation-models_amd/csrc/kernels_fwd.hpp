@@ -1,5 +1,5 @@
 // Forward kernels: conv (+bias, +BN-stat partials, input transform fused on load), BN finalize,
-// max-pool (BN+ReLU fused on load), 1x1 head + softmax + Dice partial sums (+argmax).
+// max-pool (BN+ReLU fused on load), Dice finalize.  (The 1x1 head, both directions: kernels_head.hpp.)
 //
 // Fusion contract: a conv WRITES its raw output z (pre-BN); BatchNorm+ReLU (+dropout,
 // +nearest-upsample, +concat) are applied by the CONSUMER when it loads z, using the per-channel
@@ -7,6 +7,7 @@
 #pragma once
 #include "common.hpp"
 #include "kernels_fin.hpp"
+#include "kernels_head.hpp"
 
 namespace oct {
 
@@ -298,177 +299,6 @@ __global__ __launch_bounds__(kBlock) void pool_fwd_k(const AT* __restrict__ z, c
             }
         sta4<AT>(p + (((size_t)b * Ho + yo) * Wo + xo) * C + c, m);
     }
-}
-
-// ---- head: BN+ReLU on load, 1x1 conv, softmax, optional probs / argmax / Dice partial sums ---------------
-constexpr int kDiceVals = 5;  // per class: I = sum y*p, T = sum y, P = sum p, Ih = sum y*[p>.5], Ph = sum [p>.5]
-// floats of a Dice partial row: 5 C sums and slot 5 C.  Up to 12 classes a power of two (one block_reduce_store); 13..16
-// classes need 66..81 and take 96 = 64 + 32 (kernels_head_cls.hpp).  oct_unet.hip::dice_n is the run-time twin.
-constexpr int dice_row_floats(int C) { return 5 * C <= 16 ? 16 : (5 * C <= 32 ? 32 : (5 * C < 64 ? 64 : 96)); }
-template <int C> struct DiceN { static constexpr int value = dice_row_floats(C); };
-
-struct HeadFwdArgs {
-    const void* z; const float* ab;    // last conv's raw output (activation storage type) + BN record
-    const float* w; const float* bias; // (CIN, C), (C)
-    float* probs; unsigned char* argmax; const unsigned char* labels;
-    float* dice_part;                  // [B][nblk][DiceN]; slot 5*C (always spare: 5*C < DiceN) = focal-loss sum, or the BCE sum
-    int HW, nblk, act_bf16;
-    // focal half of focal_dice_loss (custom_losses.py:98-178): cw[y] * (1 - p_y)^gamma * (-log p_y), p clipped to [1e-7, 1-1e-7]
-    int focal_on; float focal_gamma; const float* focal_cw;   // class weights (C) or nullptr
-    int focal_clip_mod;                // 1: the (1 - p)^gamma modulation also sees the clipped p; 0: only the logarithm does
-    // BCE half of bce_dice_loss (custom_losses.py:84-91; Keras 2.9 backend.binary_crossentropy restated, parity unpinned):
-    //   sum_c -( y ln(pc + e) + (1 - y) ln(qc + e) ),  pc = clip(p, eps, 1-eps), qc = clip(1 - p, eps, 1-eps),  e = eps or 0
-    // Never together with focal_on: the two share slot 5*C.
-    int bce_on; float bce_inner;       // bce_inner = e (option bce_inner_eps)
-    // ignore label (oct_unet_set_ignore_label): a pixel with this label byte adds nothing to the Dice sums or to slot 5*C;
-    // its probs / argmax are written as ever.  -1 = off: a label byte never compares equal
-    int ignore;
-};
-constexpr float kFocalEps = 1e-7f;
-
-// q_c = 1 - p_c of a softmax row, taken as the sum of the other classes: `1.f - p` has an absolute error of one ulp of p,
-// which is all of q where p saturates (and 1/q is what the BCE gradient multiplies by)
-template <int C>
-__device__ inline void softmax_complement(const float (&p)[C], float (&q)[C]) {
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-        float s = 0.f;
-#pragma unroll
-        for (int k = 0; k < C; ++k) if (k != c) s += p[k];
-        q[c] = s;
-    }
-}
-
-// raw z of one pixel (CIN values) -> registers; split from the arithmetic so that the head kernels can request later
-// chunks' pixels before they work on the current one (HeadQueue)
-template <int CIN, typename AT>
-__device__ inline void head_load(const AT* __restrict__ zp, float (&zr)[CIN]) {
-#pragma unroll
-    for (int i = 0; i < CIN; i += 4) {
-        const float4 v = lda4<AT>(zp + i);
-        zr[i] = v.x; zr[i + 1] = v.y; zr[i + 2] = v.z; zr[i + 3] = v.w;
-    }
-}
-
-// The head kernels' chunk walk keeps D chunks requested ahead of the one in work: a thread's pixel (CIN raw values) and its
-// label byte sit in registers from D chunks before they are used, so a block has D x 256 x (CIN x 4 + 1) bytes in flight
-// while it computes.  pop() hands out the oldest entry and requests chunk `next` into the freed slot (nothing once the
-// walk runs past the image: the slot then keeps stale values that are never handed out).
-constexpr int kHeadFwdAhead = 1, kHeadBwdAhead = 1;
-template <int CIN, int D, typename AT>
-struct HeadQueue {
-    const AT* zb; const unsigned char* lb; int HW;
-    float zq[D][CIN]; int lq[D];
-    __device__ HeadQueue(const AT* z, const unsigned char* l, int hw) : zb(z), lb(l), HW(hw) {}
-    __device__ __forceinline__ void request(int d, int chunk) {
-        if (chunk * kBlock < HW) {
-            const int px = chunk * kBlock + (int)threadIdx.x, q = px < HW ? px : 0;
-            head_load<CIN, AT>(zb + (size_t)q * CIN, zq[d]);
-            if (lb) lq[d] = lb[q];
-        }
-    }
-    __device__ __forceinline__ void fill(int first, int stride) {
-#pragma unroll
-        for (int d = 0; d < D; ++d) { lq[d] = 0; request(d, first + d * stride); }
-    }
-    __device__ __forceinline__ int pop(float (&zr)[CIN], int next) {
-        const int lab = lq[0];
-#pragma unroll
-        for (int i = 0; i < CIN; ++i) zr[i] = zq[0][i];
-#pragma unroll
-        for (int d = 0; d + 1 < D; ++d) {
-            lq[d] = lq[d + 1];
-#pragma unroll
-            for (int i = 0; i < CIN; ++i) zq[d][i] = zq[d + 1][i];
-        }
-        request(D - 1, next);
-        return lab;
-    }
-};
-
-template <int C, int CIN>
-__device__ inline void head_logits(const float* __restrict__ ab, const float* __restrict__ w, const float* __restrict__ bias,
-                                   float (&y)[CIN], const float (&zr)[CIN], float (&p)[C]) {
-#pragma unroll
-    for (int i = 0; i < CIN; ++i) y[i] = fmaxf(fmaf(ldc(ab + i), zr[i], ldc(ab + CIN + i)), 0.f);
-    float mx = -3.4e38f;
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-        float l = ldc(bias + c);
-#pragma unroll
-        for (int i = 0; i < CIN; ++i) l = fmaf(y[i], ldc(w + i * C + c), l);
-        p[c] = l; mx = fmaxf(mx, l);
-    }
-    float sum = 0.f;
-#pragma unroll
-    for (int c = 0; c < C; ++c) { p[c] = expf(p[c] - mx); sum += p[c]; }
-    const float inv = 1.f / sum;
-#pragma unroll
-    for (int c = 0; c < C; ++c) p[c] *= inv;
-}
-
-// grid (nblk, B): each block walks the 256-pixel chunks  blockIdx.x, blockIdx.x + nblk, ...  of ONE image and emits
-// one row of Dice partial sums
-template <int C, int CIN, typename AT>
-__global__ __launch_bounds__(kBlock) void head_fwd_k(const HeadFwdArgs A) {
-    constexpr int N = DiceN<C>::value;
-    __shared__ float red[256];
-    const int b = blockIdx.y;
-    float v[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) v[i] = 0.f;
-    HeadQueue<CIN, kHeadFwdAhead, AT> hq(reinterpret_cast<const AT*>(A.z) + (size_t)b * A.HW * CIN,
-                                         A.labels ? A.labels + (size_t)b * A.HW : nullptr, A.HW);
-    hq.fill(blockIdx.x, gridDim.x);
-    for (int chunk = blockIdx.x; chunk * kBlock < A.HW; chunk += gridDim.x) {
-        const int px = chunk * kBlock + threadIdx.x;
-        const bool valid = px < A.HW;
-        const size_t pix = (size_t)b * A.HW + (valid ? px : 0);
-        float y[CIN], zr[CIN], p[C];
-        const int lab = hq.pop(zr, chunk + kHeadFwdAhead * (int)gridDim.x);     // this chunk's pixel; the one kHeadFwdAhead chunks on is requested
-        head_logits<C, CIN>(A.ab, A.w, A.bias, y, zr, p);
-        if (valid) {
-            if (A.probs) {
-#pragma unroll
-                for (int c = 0; c < C; ++c) A.probs[pix * C + c] = p[c];
-            }
-            if (A.argmax) {
-                int am = 0; float best = p[0];
-#pragma unroll
-                for (int c = 1; c < C; ++c) if (p[c] > best) { best = p[c]; am = c; }  // first maximum, as np.argmax
-                A.argmax[pix] = (unsigned char)am;
-            }
-        }
-        if (valid && lab != A.ignore) {                     // the loss sums: counted pixels only
-            if (A.labels) {
-#pragma unroll
-                for (int c = 0; c < C; ++c) {
-                    const float yv = lab == c ? 1.f : 0.f, ph = p[c] > 0.5f ? 1.f : 0.f;
-                    v[c * kDiceVals + 0] += yv * p[c]; v[c * kDiceVals + 1] += yv; v[c * kDiceVals + 2] += p[c];
-                    v[c * kDiceVals + 3] += yv * ph;   v[c * kDiceVals + 4] += ph;
-                }
-                if (A.focal_on) {
-                    float py = p[0];
-#pragma unroll
-                    for (int c = 1; c < C; ++c) py = lab == c ? p[c] : py;
-                    const float pc = fminf(fmaxf(py, kFocalEps), 1.f - kFocalEps);
-                    const float cw = A.focal_cw ? A.focal_cw[lab < C ? lab : 0] : 1.f;
-                    v[C * kDiceVals] += cw * powf(1.f - (A.focal_clip_mod ? pc : py), A.focal_gamma) * -logf(pc);
-                }
-                if (A.bce_on) {
-                    float q[C], t = 0.f;
-                    softmax_complement<C>(p, q);
-#pragma unroll
-                    for (int c = 0; c < C; ++c) {
-                        const float u = lab == c ? p[c] : q[c];        // y picks one of the two logarithms
-                        t -= logf(fminf(fmaxf(u, kFocalEps), 1.f - kFocalEps) + A.bce_inner);
-                    }
-                    v[C * kDiceVals] += t;
-                }
-            }
-        }
-    }
-    if (A.labels) block_reduce_store<N>(v, red, A.dice_part + ((size_t)b * gridDim.x + blockIdx.x) * N, N);
 }
 
 // Dice finalize: per-(b,c) sums in fp64 -> losses, metrics, and the per-(b,c) constants backward needs.

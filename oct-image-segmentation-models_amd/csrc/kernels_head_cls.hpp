@@ -1,5 +1,5 @@
 // Class-streaming head kernels: the head for C = 9..16 classes, head_fwd_cls_k<C, AT> / head_bwd_cls_k<C, AT>.  The register
-// kernels (kernels_fwd.hpp / kernels_bwd.hpp) and the channel-streaming ones (kernels_head_wide.hpp) stop at 8 classes; these
+// kernels (kernels_head.hpp) and the channel-streaming ones (kernels_head_wide.hpp) stop at 8 classes; these
 // take every class count above, at every start_neurons 4..64 (CIN is a RUNTIME argument, as in kernels_head_wide.hpp), and
 // nothing below.  They are the channel-streaming kernels with what 16 classes change:
 //   * probabilities: head_logits_stream, the same function in both kernels -- the backward pass recomputes the forward's
@@ -21,8 +21,6 @@
 #include "kernels_head_wide.hpp"
 
 namespace oct {
-
-constexpr int kHeadClsMin = 9, kHeadClsMax = 16;     // 16 = the columns of one dl tile
 
 template <int C, typename AT>
 __global__ __launch_bounds__(kBlock) void head_fwd_cls_k(const HeadFwdArgs A, const int CIN) {
@@ -61,48 +59,10 @@ __global__ __launch_bounds__(kBlock) void head_fwd_cls_k(const HeadFwdArgs A, co
         }
         const int lab = A.labels ? A.labels[pix] : 0;
         if (valid && lab != A.ignore) {                     // the loss sums: counted pixels only (see head_fwd_k)
-            if (A.labels) {
-#pragma unroll
-                for (int c = 0; c < C; ++c) {
-                    const float yv = lab == c ? 1.f : 0.f, ph = p[c] > 0.5f ? 1.f : 0.f;
-                    v[c * kDiceVals + 0] += yv * p[c]; v[c * kDiceVals + 1] += yv; v[c * kDiceVals + 2] += p[c];
-                    v[c * kDiceVals + 3] += yv * ph;   v[c * kDiceVals + 4] += ph;
-                }
-                if (A.focal_on) {
-                    float py = p[0];
-#pragma unroll
-                    for (int c = 1; c < C; ++c) py = lab == c ? p[c] : py;
-                    const float pc = fminf(fmaxf(py, kFocalEps), 1.f - kFocalEps);
-                    const float cw = A.focal_cw ? A.focal_cw[lab < C ? lab : 0] : 1.f;
-                    v[C * kDiceVals] += cw * powf(1.f - (A.focal_clip_mod ? pc : py), A.focal_gamma) * -logf(pc);
-                }
-                if (A.bce_on) {
-                    float q[C], t = 0.f;
-                    softmax_complement<C>(p, q);
-#pragma unroll
-                    for (int c = 0; c < C; ++c) {
-                        const float u = lab == c ? p[c] : q[c];        // y picks one of the two logarithms
-                        t -= logf(fminf(fmaxf(u, kFocalEps), 1.f - kFocalEps) + A.bce_inner);
-                    }
-                    v[C * kDiceVals] += t;
-                }
-            }
+            if (A.labels) head_loss_sums<C, N>(A, lab, p, v);
         }
     }
-    if (A.labels) {
-        float* const out = A.dice_part + ((size_t)b * gridDim.x + blockIdx.x) * N;
-        if constexpr (N == 64) {
-            block_reduce_store<64>(v, red, out, 64);
-        } else {
-            float lo[64], hi[32];
-#pragma unroll
-            for (int i = 0; i < 64; ++i) lo[i] = v[i];
-#pragma unroll
-            for (int i = 0; i < 32; ++i) hi[i] = v[64 + i];
-            block_reduce_store<64>(lo, red, out, 64);
-            block_reduce_store<32>(hi, red, out + 64, 32);
-        }
-    }
+    if (A.labels) head_rows_store<N>(v, red, A.dice_part + ((size_t)b * gridDim.x + blockIdx.x) * N);
 }
 
 // a wave-uniform float held in a scalar register

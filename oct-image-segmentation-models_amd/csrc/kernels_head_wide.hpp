@@ -1,4 +1,4 @@
-// Channel-streaming head kernels: the head of kernels_fwd.hpp / kernels_bwd.hpp with the input channel count CIN (=
+// Channel-streaming head kernels: the head of kernels_head.hpp with the input channel count CIN (=
 // start_neurons) as a RUNTIME argument, any multiple of 4 up to 64.  The register kernels keep a pixel's CIN activations and,
 // in the backward pass, CIN*C + C + 2*CIN per-thread partial sums in VGPRs (264 accumulators at CIN 32, C 8); these keep
 // nothing that grows with CIN:
@@ -15,11 +15,10 @@
 // dl = 0 and a = 0 (and a finite y of pixel 0), i.e. exact zeros into every sum; so do the pixels of the ignore label.
 // Same buffers, same layouts as the register kernels: probs / argmax / Dice rows, g, part [B*nblk][2*CIN], wpart
 // [B*nblk][CIN*C + C].  grid (nblk, B), a block walks chunks blockIdx.x, + nblk, ... of one image.
-// Routing (oct_unet.hip): C = 2..8 with start_neurons > 32, or every width under option "head_wide".  C = 9..16 is
+// Routing (host.hpp head_route): C = 2..8 with start_neurons > 32, or every width under option "head_wide".  C = 9..16 is
 // kernels_head_cls.hpp at every width; it shares head_logits_stream below, so its probabilities are formed the same way.
 #pragma once
-#include "kernels_bwd.hpp"
-#include "kernels_fwd.hpp"
+#include "kernels_head.hpp"
 
 namespace oct {
 
@@ -46,12 +45,7 @@ __device__ inline void head_logits_stream(const AT* __restrict__ zp, const float
     float mx = -3.4e38f;
 #pragma unroll
     for (int c = 0; c < C; ++c) mx = fmaxf(mx, p[c]);
-    float sum = 0.f;
-#pragma unroll
-    for (int c = 0; c < C; ++c) { p[c] = expf(p[c] - mx); sum += p[c]; }
-    const float inv = 1.f / sum;
-#pragma unroll
-    for (int c = 0; c < C; ++c) p[c] *= inv;
+    head_softmax<C>(p, mx);
 }
 
 template <int C, typename AT>
@@ -82,35 +76,10 @@ __global__ __launch_bounds__(kBlock) void head_fwd_wide_k(const HeadFwdArgs A, c
         }
         const int lab = A.labels ? A.labels[pix] : 0;
         if (valid && lab != A.ignore) {                     // the loss sums: counted pixels only (see head_fwd_k)
-            if (A.labels) {
-#pragma unroll
-                for (int c = 0; c < C; ++c) {
-                    const float yv = lab == c ? 1.f : 0.f, ph = p[c] > 0.5f ? 1.f : 0.f;
-                    v[c * kDiceVals + 0] += yv * p[c]; v[c * kDiceVals + 1] += yv; v[c * kDiceVals + 2] += p[c];
-                    v[c * kDiceVals + 3] += yv * ph;   v[c * kDiceVals + 4] += ph;
-                }
-                if (A.focal_on) {
-                    float py = p[0];
-#pragma unroll
-                    for (int c = 1; c < C; ++c) py = lab == c ? p[c] : py;
-                    const float pc = fminf(fmaxf(py, kFocalEps), 1.f - kFocalEps);
-                    const float cw = A.focal_cw ? A.focal_cw[lab < C ? lab : 0] : 1.f;
-                    v[C * kDiceVals] += cw * powf(1.f - (A.focal_clip_mod ? pc : py), A.focal_gamma) * -logf(pc);
-                }
-                if (A.bce_on) {
-                    float q[C], t = 0.f;
-                    softmax_complement<C>(p, q);
-#pragma unroll
-                    for (int c = 0; c < C; ++c) {
-                        const float u = lab == c ? p[c] : q[c];        // y picks one of the two logarithms
-                        t -= logf(fminf(fmaxf(u, kFocalEps), 1.f - kFocalEps) + A.bce_inner);
-                    }
-                    v[C * kDiceVals] += t;
-                }
-            }
+            if (A.labels) head_loss_sums<C, N>(A, lab, p, v);
         }
     }
-    if (A.labels) block_reduce_store<N>(v, red, A.dice_part + ((size_t)b * gridDim.x + blockIdx.x) * N, N);
+    if (A.labels) head_rows_store<N>(v, red, A.dice_part + ((size_t)b * gridDim.x + blockIdx.x) * N);
 }
 
 template <int C, typename AT>

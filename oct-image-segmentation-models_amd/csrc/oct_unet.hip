@@ -470,60 +470,6 @@ int conv_forward(oct_unet* h, int li, const void* x_in, int x_is_u8, int B, int 
     return 0;
 }
 
-// the register head kernels are instantiated for every start_neurons (= the head's input channels) up to 32: run
-// f(constant cin).  Wider heads, and every head under option "head_wide", take the channel-streaming kernels
-// (kernels_head_wide.hpp), whose register use does not grow with cin.  More than 8 classes: the class-streaming kernels
-// (kernels_head_cls.hpp) at every width, whatever "head_wide" says -- neither of the other two families is built there
-inline bool head_is_wide(const Options& o, int cin) { return cin > 32 || o.head_wide; }
-template <typename F>
-int head_cin_dispatch(int cin, F f) {
-    switch (cin) {
-#define HEAD_CIN(N) case N: f(std::integral_constant<int, N>{}); return 0;
-        HEAD_CIN(4) HEAD_CIN(8) HEAD_CIN(16) HEAD_CIN(12) HEAD_CIN(20) HEAD_CIN(24) HEAD_CIN(28) HEAD_CIN(32)
-#undef HEAD_CIN
-        default: return fail(-3, "head: unsupported start_neurons");
-    }
-}
-
-template <int C>
-int launch_head_fwd(const HeadFwdArgs& a, int cin, int B, hipStream_t s, bool wide) {
-    if (wide) return launch_head_fwd_wide(a, C, cin, B, s);
-    dim3 grid(a.nblk, B), block(kBlock);
-    const double px = (double)B * a.HW;
-    char nm[64]; snprintf(nm, sizeof nm, "head_fwd_k<%d,%d,%s>", C, cin, AT_NAME(a.act_bf16));
-    ProfScope ps(s, nm, "head", 2.0 * cin * C * px, px * (cin * 4 + (a.probs ? C * 4 : 0) + (a.argmax ? 1 : 0) + (a.labels ? 1 : 0)));
-    if (int rc = head_cin_dispatch(cin, [&](auto ci) { AT_DISPATCH(a.act_bf16, head_fwd_k<C, decltype(ci)::value, AT><<<grid, block, 0, s>>>(a)); })) return rc;
-    HIP_OK(hipGetLastError());
-    return 0;
-}
-
-template <int C>
-int launch_head_bwd(const HeadBwdArgs& a, int cin, int B, hipStream_t s, bool wide) {
-    if (wide) return launch_head_bwd_wide(a, C, cin, B, s);
-    dim3 grid(a.nblk, B), block(kBlock);
-    const double px = (double)B * a.HW;
-    char nm[64]; snprintf(nm, sizeof nm, "head_bwd_k<%d,%d,%s>", C, cin, AT_NAME(a.act_bf16));
-    ProfScope ps(s, nm, "head", 6.0 * cin * C * px, px * (cin * 4 * 2 + 1));
-    if (int rc = head_cin_dispatch(cin, [&](auto ci) { AT_DISPATCH(a.act_bf16, head_bwd_k<C, decltype(ci)::value, AT><<<grid, block, 0, s>>>(a)); })) return rc;
-    HIP_OK(hipGetLastError());
-    return 0;
-}
-
-#define DISPATCH_C(fn, ncls, ...)                       \
-    ([&]() -> int {                                     \
-        switch (ncls) {                                 \
-            case 2: return fn<2>(__VA_ARGS__);          \
-            case 3: return fn<3>(__VA_ARGS__);          \
-            case 4: return fn<4>(__VA_ARGS__);          \
-            case 5: return fn<5>(__VA_ARGS__);          \
-            case 6: return fn<6>(__VA_ARGS__);          \
-            case 7: return fn<7>(__VA_ARGS__);          \
-            case 8: return fn<8>(__VA_ARGS__);          \
-            default: return fail(-3, "bad n_cls");      \
-        }                                               \
-    })()
-inline bool head_is_cls(int n_cls) { return n_cls > 8; }
-
 // blocks per image of the head kernels: ~2048 blocks in total, each walking several 256-pixel chunks
 int head_nblk(int HW, int B) { return std::max(1, std::min(cdiv(HW, kBlock), cdiv(2048, B))); }
 
@@ -609,9 +555,7 @@ int forward_head(oct_unet* h, int B, const oct_unet_io* io, hipStream_t s) {
     a.dice_part = h->dice_part; a.HW = hd.H * hd.W; a.nblk = head_nblk(a.HW, B); a.act_bf16 = h->cfg.dtype;
     a.focal_on = h->focal_w > 0.f; a.focal_gamma = h->focal_gamma; a.focal_cw = h->focal_cw; a.focal_clip_mod = h->opt.focal_clip_mod;
     a.bce_on = h->bce_on; a.bce_inner = h->opt.bce_inner_eps ? kFocalEps : 0.f; a.ignore = h->ignore;
-    const int rc = head_is_cls(h->cfg.n_cls) ? launch_head_fwd_cls(a, h->cfg.n_cls, hd.cin, B, s)
-                                             : DISPATCH_C(launch_head_fwd, h->cfg.n_cls, a, hd.cin, B, s, head_is_wide(h->opt, hd.cin));
-    if (rc) return rc;
+    if (int rc = launch_head_fwd(a, head_route(h->opt, h->cfg.n_cls, hd.cin), h->cfg.n_cls, hd.cin, B, s)) return rc;
     h->have_dice = a.labels != nullptr;
     return 0;
 }
@@ -848,12 +792,10 @@ int head_backward(oct_unet* h, const unsigned char* labels, int macro, float los
     hb.focal_w = h->focal_w; hb.focal_gamma = h->focal_gamma; hb.focal_cw = h->focal_cw; hb.focal_clip_mod = h->opt.focal_clip_mod; hb.inv_count = 1.f / ((float)B * hb.HW);
     hb.bce_on = h->bce_on; hb.bce_inner = h->opt.bce_inner_eps ? kFocalEps : 0.f; hb.bce_scale = loss_scale * hb.inv_count / (float)h->cfg.n_cls;
     hb.ignore = h->ignore;       // >= 0: the kernels take 1 / (counted pixels) from dice_bc instead of inv_count
-    const bool cls = head_is_cls(h->cfg.n_cls);
-    const bool wide = head_is_wide(h->opt, hd.cin);          // (only the register kernels finalize the statistics in the launch)
-    if (!wide && !cls && fin_ok(h, last)) { hb.fin = fin_desc(h, nl - 2, 1, B); *fin = true; }
+    const HeadRoute r = head_route(h->opt, h->cfg.n_cls, hd.cin);
+    if (r == HEAD_REG && fin_ok(h, last)) { hb.fin = fin_desc(h, nl - 2, 1, B); *fin = true; }   // (only the register kernels finalize the statistics in the launch)
     *rows = B * hb.nblk;
-    if (cls) return launch_head_bwd_cls(hb, h->cfg.n_cls, hd.cin, B, s);
-    return DISPATCH_C(launch_head_bwd, h->cfg.n_cls, hb, hd.cin, B, s, wide);
+    return launch_head_bwd(hb, r, h->cfg.n_cls, hd.cin, B, s);
 }
 
 // one backward-data launch of block li.  *rows = statistic partial rows it wrote; *fin = true if it finalized the

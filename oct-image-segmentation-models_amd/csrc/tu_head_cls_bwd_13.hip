@@ -1,4 +1,7 @@
 // One translation unit of liboct_unet_hip.so (see host.hpp): the class-streaming head kernels head_bwd_cls_k<C, AT>, C = 13..16.
-#define OCT_HEAD_CLS_BWD 1
-#define OCT_HEAD_CLS_C0 13
-#include "launch_head_cls.hpp"
+// (family, direction, first C, last C): a row of OCT_HEAD_UNITS in host.hpp
+#define OCT_HEAD_FAMILY 2
+#define OCT_HEAD_BWD 1
+#define OCT_HEAD_C0 13
+#define OCT_HEAD_C1 16
+#include "launch_head.hpp"

@@ -1,7 +1,7 @@
 """GPU parity at the class counts and widths the other GPU tests never reach: num_classes 5 .. 8 and start_neurons 20 / 24 / 28.
 
 num_classes >= 5 changes real code in the head: the per-block Dice partial row is 32 floats wide for C = 4 .. 6 and 64 for
-C = 7, 8 (DiceN<C>, kernels_fwd.hpp; the focal sum sits at slot 5 C), head_bwd_k keeps CIN * C + C partial sums in
+C = 7, 8 (DiceN<C>, kernels_head.hpp; the focal sum sits at slot 5 C), head_bwd_k keeps CIN * C + C partial sums in
 registers and reduces them in groups of 32 with a ragged last group (264 values at CIN 32, C 8), dice_finalize_k indexes
 its per-(image, class) sums by B * C.  start_neurons 20 / 24 / 28 give the wide MFMA kernel K = 80 / 48 / 112 input
 channels (multiples of 8 but not of 16 or 32) and send the backward-weights of those layers to conv_dw32_k with a ragged
