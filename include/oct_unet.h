@@ -165,6 +165,31 @@ int oct_unet_loss_bce_dice(oct_unet* h, float smooth, float* out8_dev, oct_strea
  * A captured graph (oct_unet_graph_capture_infer) keeps the setting it was captured under.
  * The reference has no counterpart; the tests compare with a torch-fp64 masked restatement. */
 int oct_unet_set_ignore_label(oct_unet* h, int label);
+/* Shape of the Dice term: Tversky weights, focal-Tversky exponent, class weights.  Per handle; holds for the following
+ * forward / loss / backward calls; every call drops a pending Dice sum (call forward again).  s = NULL, or alpha = beta = 0.5,
+ * gamma = 1, weight_mode = 0, is plain Dice: the launches and results are those of a handle that never had a shape.
+ * All finalize arithmetic is fp64; s is the loss call's `smooth`.  For a triple of sums (I, T, P):
+ *   N = 2I + s,  D = 2I + 2 alpha (P - I) + 2 beta (T - I) + s   [alpha = beta = 1/2: D = T + P + s],  u = 1 - N / D,
+ *   L = u if gamma == 1, else max(u, 1e-7)^gamma (gradient 0 where the clamp is active).
+ * macro: the triple is per (image b, class c) and loss = mean_b [ sum_c w_bc L_bc / sum_c w_bc ];
+ * micro: I = sum_b sum_c w_c I_bc, likewise T and P, and there is one L.
+ * weight_mode 0: every weight is 1.  1: w_bc = w_c = class_weight_dev[c], n_classes device floats, every entry finite and
+ * >= 0 and not all zero; caller-owned, kept alive while the setting holds (read back once by this call to check it).
+ * 2 ("volume", the generalized Dice loss): w = 1 / T^2 with T = T_bc of the image (macro) or T_c = sum_b T_bc of the batch
+ * (micro); a class with T = 0 takes the largest weight among the classes with T > 0 of the same image / batch, and all
+ * weights are 1 if there is none.  Weights depend on the labels only: constants of the differentiation.
+ * Argument errors: alpha or beta < 0 or not finite, alpha + beta = 0, gamma outside (0, 8], weight_mode outside 0..2,
+ * weight_mode 1 with a NULL or invalid array.
+ * With a shape set the loss calls return the shaped macro / micro loss in outputs 0 and 1 and combine the focal or BCE term
+ * with it in outputs 5 and 6; outputs 2 and 3 (dice_coef_macro / dice_coef_micro) are metrics and never change.  The
+ * gradient for class c of a pixel with one-hot y is -m_c (y A_c - B_c) / D_c^2 with A = 2D - 2(1 - alpha - beta)N,
+ * B = 2 alpha N, and m_c collecting the weight normalisation, gamma u^(gamma - 1) (0 under the clamp) and the macro / micro
+ * scale; a class with m_c = 0 gets exactly 0.  The ignore label composes: ignored pixels never enter the sums.
+ * The first call that sets a shape allocates the handle's table of backward constants on the device, O(max_batch * n_classes)
+ * doubles, freed by the destroy call: the workspace keeps its size and a handle that never has a shape allocates nothing.
+ * The reference has no counterpart; the tests compare with a numpy restatement and torch-fp64 autograd. */
+typedef struct oct_dice_shape { float alpha, beta, gamma; int weight_mode; const float* class_weight_dev; } oct_dice_shape;
+int oct_unet_set_dice_shape(oct_unet* h, const oct_dice_shape* s /* NULL: plain Dice */);
 /* After training forward + loss_dice: fills the grads buffer with d(loss_scale*loss)/dparams. */
 int oct_unet_backward(oct_unet* h, const unsigned char* labels_dev, int macro, float loss_scale,
                       oct_stream_t stream);

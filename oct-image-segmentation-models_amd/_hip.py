@@ -63,6 +63,15 @@ RENDER_BASE_IMAGE, RENDER_BASE_LABELS = 0, 1
 RENDER_MAX_CLASSES, RENDER_MAX_LINES = 32, 16
 
 
+class DiceShape(C.Structure):
+    """``oct_dice_shape``: the shape of the Dice term for ``oct_unet_set_dice_shape``."""
+    _fields_ = [("alpha", C.c_float), ("beta", C.c_float), ("gamma", C.c_float), ("weight_mode", C.c_int),
+                ("class_weight_dev", C.c_void_p)]
+
+
+DICE_WEIGHT_NONE, DICE_WEIGHT_CLASS, DICE_WEIGHT_VOLUME = range(3)
+
+
 class UNetIO(C.Structure):
     _fields_ = [("probs", C.c_void_p), ("argmax", C.c_void_p), ("labels", C.c_void_p)]
 
@@ -107,6 +116,7 @@ SYMBOLS = [
     ("oct_unet_set_bce_dice", C.c_int, [C.c_void_p, C.c_int]),
     ("oct_unet_loss_bce_dice", C.c_int, [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
     ("oct_unet_set_ignore_label", C.c_int, [C.c_void_p, C.c_int]),
+    ("oct_unet_set_dice_shape", C.c_int, [C.c_void_p, _P(DiceShape)]),
     ("oct_unet_backward", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p]),
     ("oct_unet_set_tail_event", C.c_int, [C.c_void_p, C.c_void_p]),
     ("oct_unet_grad_tail_offset", C.c_size_t, [_P(UNetCfg)]),

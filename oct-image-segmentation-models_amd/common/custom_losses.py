@@ -6,7 +6,12 @@ loss by the ``oct_loss`` tag of the callable; the callables themselves are numpy
 arrays (e.g. for evaluation code).  ``focal_dice_loss`` (reference :98-178, built on the third-party ``focal-loss``
 package: published formula restated, parity unpinned) and ``bce_dice_loss`` (reference :84-91, Keras 2.9's
 ``binary_crossentropy`` restated, parity unpinned) are implemented the same way; ``bce_focal_loss`` and the plain
-focal loss raise."""
+focal loss raise.
+
+The Dice term of all four takes a SHAPE: ``alpha`` / ``beta`` (Tversky index), ``tversky_gamma``
+(focal-Tversky exponent) and ``dice_class_weight`` (a sequence of ``num_classes`` weights, or ``"volume"`` for the
+generalized Dice loss).  A factory called with any of them tags its callable with ``oct_dice_shape``, which
+``Model.compile`` hands to ``UNetEngine.set_dice_shape``; with none of them the callables are what they were."""
 from __future__ import annotations
 
 import numpy as np
@@ -19,23 +24,135 @@ def _one_hot(y_true, num_classes):
     return np.eye(num_classes, dtype=np.float64)[lab.astype(np.int64)]
 
 
-def dice_loss_micro(*, is_y_true_sparse: bool, num_classes: int, **kwargs):
+DICE_CLAMP = 1e-7     # focal-Tversky: L = max(1 - TI, DICE_CLAMP) ** gamma for gamma != 1
+
+
+def check_dice_shape(num_classes: int, alpha=0.5, beta=0.5, gamma=1.0, class_weight=None):
+    """The validated shape ``{"alpha", "beta", "gamma", "class_weight"}`` (``class_weight``: None, ``"volume"`` or a list of
+    ``num_classes`` floats), or None where it is plain Dice (alpha = beta = 1/2, gamma = 1, no weights).  ``ValueError`` for
+    alpha or beta < 0, alpha + beta = 0, gamma outside (0, 8], weights that are negative, not finite, all zero or of
+    another length."""
+    alpha, beta, gamma = float(alpha), float(beta), float(gamma)
+    if not (np.isfinite(alpha) and np.isfinite(beta) and alpha >= 0.0 and beta >= 0.0 and alpha + beta > 0.0):
+        raise ValueError(f"dice shape: alpha, beta must be finite and >= 0 with alpha + beta > 0, not {alpha}, {beta}")
+    if not 0.0 < gamma <= 8.0:
+        raise ValueError(f"dice shape: gamma must be in (0, 8], not {gamma}")
+    if class_weight is not None and not (isinstance(class_weight, str) and class_weight == "volume"):
+        if isinstance(class_weight, str):
+            raise ValueError(f'dice shape: class_weight must be None, "volume" or {num_classes} weights, not {class_weight!r}')
+        w = np.asarray(class_weight, np.float64)
+        if w.shape != (num_classes,) or not np.all(np.isfinite(w)) or np.any(w < 0.0) or not np.any(w > 0.0):
+            raise ValueError(f"dice shape: class_weight must be {num_classes} finite weights >= 0, not all zero")
+        class_weight = w.tolist()
+    if alpha == 0.5 and beta == 0.5 and gamma == 1.0 and class_weight is None:
+        return None
+    return {"alpha": alpha, "beta": beta, "gamma": gamma, "class_weight": class_weight}
+
+
+def _volume_weights(T):
+    """1 / T^2 along the last axis; a T of 0 takes the largest weight of its row, a row of zeros all ones."""
+    T = np.asarray(T, np.float64)
+    with np.errstate(divide="ignore"):
+        w = np.where(T > 0.0, 1.0 / (T * T), 0.0)
+    wmax = w.max(axis=-1, keepdims=True)
+    return np.where(wmax == 0.0, 1.0, np.where(T > 0.0, w, wmax))
+
+
+def _shape_term(u, gamma):
+    """``(L, dL/du)`` of ``u = 1 - TI``."""
+    u = np.asarray(u, np.float64)
+    if gamma == 1.0:
+        return u, np.ones_like(u)
+    on = u > DICE_CLAMP
+    uc = np.where(on, u, DICE_CLAMP)
+    return uc ** gamma, np.where(on, gamma * uc ** (gamma - 1.0), 0.0)
+
+
+def fold_dice_constants(m, A, B, D):
+    """The pair ``(num', den')`` the head backward kernels read in place of Dice's ``(2I + s, T + P + s)``: they form
+    ``-(2 y den' - num') / den'^2`` in float32, and ``den' = 2 D^2 / (A m)``, ``num' = 4 B D^2 / (A^2 m)`` make that
+    ``-m (y A - B) / D^2``.  ``m == 0`` -- or a ``den'`` of 1e18 and more -- is stored as ``(0, 1e30)``: the square of 1e30
+    overflows float32 to +inf and the quotient is exactly 0."""
+    m, A, B, D = np.broadcast_arrays(*(np.asarray(v, np.float64) for v in (m, A, B, D)))
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        den, num = 2.0 * D * D / (A * m), 4.0 * B * D * D / (A * A * m)
+    zero = ~(m > 0.0) | ~(den < 1e18)
+    return np.where(zero, 0.0, num), np.where(zero, 1e30, den)
+
+
+def _shaped_dice(y, p, smooth, alpha=0.5, beta=0.5, gamma=1.0, class_weight=None) -> dict:
+    """The definition on a one-hot ``y`` and probabilities ``p`` (B,H,W,C), ignored pixels already zeroed in both."""
+    ax = tuple(range(1, p.ndim - 1))
+    I, T, P = np.sum(y * p, axis=ax), np.sum(y, axis=ax), np.sum(p, axis=ax)       # (B, C)
+    Bn, C = I.shape
+    if class_weight is None:
+        w_bc, w_c = np.ones((Bn, C)), np.ones(C)
+    elif isinstance(class_weight, str):
+        w_bc, w_c = _volume_weights(T), _volume_weights(T.sum(axis=0))
+    else:
+        w_c = np.asarray(class_weight, np.float64)
+        w_bc = np.broadcast_to(w_c, (Bn, C))
+
+    def consts(I, T, P):
+        N = 2.0 * I + smooth
+        D = 2.0 * I + 2.0 * alpha * (P - I) + 2.0 * beta * (T - I) + smooth
+        L, gu = _shape_term(1.0 - N / D, gamma)
+        return L, gu, D, 2.0 * D - 2.0 * (1.0 - alpha - beta) * N, 2.0 * alpha * N
+
+    L, gu, D, A, Bc = consts(I, T, P)
+    wn = w_bc / w_bc.sum(axis=1, keepdims=True)
+    macro = {"w": w_bc, "L": L, "D": D, "A": A, "B": Bc, "m": wn * gu / Bn}
+    Lu, guu, Du, Au, Bu = consts(np.sum(w_c * I), np.sum(w_c * T), np.sum(w_c * P))
+    micro = {"w": w_c, "L": Lu, "D": Du, "A": Au, "B": Bu, "m": w_c * guu}
+    return {"loss_macro": float(np.mean(np.sum(wn * L, axis=1))), "loss_micro": float(Lu), "macro": macro, "micro": micro,
+            "I": I, "T": T, "P": P}
+
+
+def shaped_dice_reference(labels, probs, num_classes: int, ignore=None, *, smooth: float = 1e-05, **shape) -> dict:
+    """The shaped Dice term as the engine defines it (``oct_unet_set_dice_shape``), in fp64: sparse
+    ``labels`` (B,H,W[,1]), ``probs`` (B,H,W,C), ``ignore`` as in ``masked_loss_reference``, ``shape`` the keywords of
+    ``UNetEngine.set_dice_shape`` (``alpha``, ``beta``, ``gamma``, ``class_weight``).  Returns ``loss_macro``, ``loss_micro``,
+    the sums ``I``, ``T``, ``P`` (B, C) and, under ``macro`` (arrays (B, C)) and ``micro`` (``w``, ``m`` (C,), the rest
+    scalars), the constants ``w``, ``L``, ``D``, ``A``, ``B``, ``m`` of the gradient
+    ``dloss/dp = -m (y A - B) / D^2`` for a pixel's class-c probability with one-hot y."""
+    sh = check_dice_shape(num_classes, **shape) or {}
+    lab = np.asarray(labels)
+    lab = (lab[..., 0] if (lab.ndim == 4 and lab.shape[-1] == 1) else lab).astype(np.int64)
+    p = np.asarray(probs, np.float64)
+    m = np.ones(lab.shape, bool) if ignore is None else lab != int(ignore)
+    ok = m & (lab < num_classes)
+    y = np.eye(num_classes, dtype=np.float64)[np.where(ok, lab, 0)] * ok[..., None]
+    return _shaped_dice(y, p * m[..., None], smooth, **sh)
+
+
+def dice_loss_micro(*, is_y_true_sparse: bool, num_classes: int, alpha: float = 0.5, beta: float = 0.5,
+                    tversky_gamma: float = 1.0, dice_class_weight=None, **kwargs):
+    shape = check_dice_shape(num_classes, alpha, beta, tversky_gamma, dice_class_weight)
+
     def _dice_loss_micro(y_true, y_pred, smooth=1e-05):
         if is_y_true_sparse:
             y_true = _one_hot(y_true, num_classes)
+        if shape:
+            return _shaped_dice(np.asarray(y_true, np.float64), np.asarray(y_pred, np.float64), smooth, **shape)["loss_micro"]
         y_true_f = np.asarray(y_true, np.float64).ravel()
         y_pred_f = np.asarray(y_pred, np.float64).ravel()
         score = (2.0 * np.sum(y_true_f * y_pred_f) + smooth) / (np.sum(y_true_f) + np.sum(y_pred_f) + smooth)
         return 1.0 - score
 
     _dice_loss_micro.oct_loss = "dice_loss_micro"
+    _dice_loss_micro.oct_dice_shape = shape
     return _dice_loss_micro
 
 
-def dice_loss_macro(*, is_y_true_sparse: bool, num_classes: int, **kwargs):
+def dice_loss_macro(*, is_y_true_sparse: bool, num_classes: int, alpha: float = 0.5, beta: float = 0.5,
+                    tversky_gamma: float = 1.0, dice_class_weight=None, **kwargs):
+    shape = check_dice_shape(num_classes, alpha, beta, tversky_gamma, dice_class_weight)
+
     def _dice_loss_macro(y_true, y_pred, smooth=1e-05):
         if is_y_true_sparse:
             y_true = _one_hot(y_true, num_classes)
+        if shape:
+            return _shaped_dice(np.asarray(y_true, np.float64), np.asarray(y_pred, np.float64), smooth, **shape)["loss_macro"]
         y_true = np.asarray(y_true, np.float64)
         y_pred = np.asarray(y_pred, np.float64)
         reduce_axis = tuple(range(1, y_pred.ndim - 1))
@@ -45,6 +162,7 @@ def dice_loss_macro(*, is_y_true_sparse: bool, num_classes: int, **kwargs):
         return 1.0 - np.mean(score)
 
     _dice_loss_macro.oct_loss = "dice_loss_macro"
+    _dice_loss_macro.oct_dice_shape = shape
     return _dice_loss_macro
 
 
@@ -52,13 +170,17 @@ FOCAL_EPS = 1e-7   # keras backend epsilon: probabilities are clipped to [eps, 1
 
 
 def focal_dice_loss(*, num_classes: int, gamma: float = 2, class_weight=None, focal_loss_weight: float = 0.5,
-                    dice_macro: bool = True, **kwargs):
+                    dice_macro: bool = True, alpha: float = 0.5, beta: float = 0.5, tversky_gamma: float = 1.0,
+                    dice_class_weight=None, **kwargs):
     """``focal_dice_loss`` / ``SparseCategoricalFocalDiceLoss`` (reference custom_losses.py:98-178), sparse labels:
-    ``w * sum_px[cw[y] (1-p_y)^gamma (-log p_y)] / size(y_true) + (1 - w) * dice_loss_{macro|micro}``."""
+    ``w * sum_px[cw[y] (1-p_y)^gamma (-log p_y)] / size(y_true) + (1 - w) * dice_loss_{macro|micro}``.  ``gamma`` and
+    ``class_weight`` belong to the focal term; ``alpha``, ``beta``, ``tversky_gamma``, ``dice_class_weight`` shape the Dice term."""
     cw = None if class_weight is None else np.asarray(class_weight, np.float64)
     if cw is not None and cw.shape != (num_classes,):
         raise ValueError(f"class_weight must have {num_classes} entries")
-    dice_fn = (dice_loss_macro if dice_macro else dice_loss_micro)(is_y_true_sparse=True, num_classes=num_classes)
+    dice_fn = (dice_loss_macro if dice_macro else dice_loss_micro)(
+        is_y_true_sparse=True, num_classes=num_classes, alpha=alpha, beta=beta, tversky_gamma=tversky_gamma,
+        dice_class_weight=dice_class_weight)
 
     def _focal_dice_loss(y_true, y_pred):
         lab = np.asarray(y_true)
@@ -72,16 +194,19 @@ def focal_dice_loss(*, num_classes: int, gamma: float = 2, class_weight=None, fo
     _focal_dice_loss.oct_loss = "focal_dice_loss"
     _focal_dice_loss.oct_focal = {"gamma": float(gamma), "class_weight": None if cw is None else cw.tolist(),
                                   "focal_loss_weight": float(focal_loss_weight), "dice_macro": bool(dice_macro)}
+    _focal_dice_loss.oct_dice_shape = dice_fn.oct_dice_shape
     return _focal_dice_loss
 
 
-def bce_dice_loss(*, num_classes: int, bce_inner_eps: bool = True, **kwargs):
+def bce_dice_loss(*, num_classes: int, bce_inner_eps: bool = True, alpha: float = 0.5, beta: float = 0.5,
+                  tversky_gamma: float = 1.0, dice_class_weight=None, **kwargs):
     """``bce_dice_loss`` (reference custom_losses.py:84-91): ``keras.losses.binary_crossentropy(y, p) + dice_loss_micro``.
     The cross-entropy restates Keras 2.9's ``backend.binary_crossentropy`` (``from_logits=False``) on the clipped
     probabilities, ``-(y ln(pc + e) + (1 - y) ln(1 - pc + e))``, averaged over the class axis and then over the batch
     (one mean over every element).  ``bce_inner_eps=False`` drops the inner ``+ e`` (engine option "bce_inner_eps").
     Sparse ``y_true`` (labels) is accepted as well as the dense one-hot the reference feeds it."""
-    dice_fn = dice_loss_micro(is_y_true_sparse=False, num_classes=num_classes)
+    dice_fn = dice_loss_micro(is_y_true_sparse=False, num_classes=num_classes, alpha=alpha, beta=beta,
+                              tversky_gamma=tversky_gamma, dice_class_weight=dice_class_weight)
     e = FOCAL_EPS if bce_inner_eps else 0.0
 
     def _bce_dice_loss(y_true, y_pred):
@@ -94,6 +219,7 @@ def bce_dice_loss(*, num_classes: int, bce_inner_eps: bool = True, **kwargs):
         return np.mean(bce) + dice_fn(y, p)
 
     _bce_dice_loss.oct_loss = "bce_dice_loss"
+    _bce_dice_loss.oct_dice_shape = dice_fn.oct_dice_shape
     return _bce_dice_loss
 
 

@@ -403,6 +403,149 @@ static __global__ __launch_bounds__(kBlock) void dice_finalize_k(const DiceFinAr
     }
 }
 
+// ---- shaped Dice finalize (oct_unet_set_dice_shape) ---------------------------------
+// Stands in for dice_finalize_k while a shape is set: Tversky weights alpha / beta, the focal-Tversky exponent g and class
+// weights (wmode 0: none, 1: cw[c], 2: 1 / T^2 of the label volume).  Per triple of sums (I, T, P), all in fp64:
+//   N = 2I + s,  D = 2I + 2 alpha (P - I) + 2 beta (T - I) + s,  u = 1 - N/D,  L = u (g == 1) or max(u, 1e-7)^g
+//   macro: triple per (b, c), loss = mean_b [ sum_c w_bc L_bc / sum_c w_bc ];  micro: one triple of sum_bc w_c (I, T, P)_bc
+// out4[0], out4[1] and the combinations in out8 take the shaped losses; the two metrics, the focal / BCE mean and the
+// counted-pixel count are dice_finalize_k's, sum for sum.
+// The backward constants are FOLDED into the (num, den) pairs head_bwd_* read: those kernels form
+// -scale (2y den - num) / den^2 in float, and  den' = 2 D^2 / (A m),  num' = 4 B D^2 / (A^2 m)  with
+// A = 2D - 2(1 - alpha - beta)N, B = 2 alpha N  make that  -scale m (yA - B) / D^2.  Both tables are per (b, c) -- bcm for
+// macro = 1, bcu for macro = 0 -- and head_backward runs the kernels on either with their per-(b, c) indexing, whose
+// 1 / (B C) is inside m.  m == 0 (a zero class weight, the clamp of L active) or a den' of 1e18 and more is stored as
+// (num', den') = (0, 1e30): den'^2 overflows float to +inf and (2y 1e30 - 0) / inf is exactly 0.
+struct DiceShapeArgs {
+    DiceFinArgs f;                     // what dice_finalize_k takes (f.bc is not written)
+    float alpha, beta, gamma; int wmode; const float* cw;
+    double* bcm; double* bcu;          // 2*B*C + 3 doubles each; [2*B*C + 2] = 1 / (counted pixels) with an ignore label
+    double* tab;                       // 3*B*C doubles (I, T, P of every pair): used where B*C > kBlock, else LDS holds them
+};
+
+__device__ __forceinline__ void dice_fold(double m, double A, double B, double D, double* out) {
+    double den = 2.0 * D * D / (A * m), num = 4.0 * B * D * D / (A * A * m);
+    if (!(m > 0.0) || !(den < 1e18)) { num = 0.0; den = 1e30; }
+    out[0] = num; out[1] = den;
+}
+
+// L and dL/du of one triple
+__device__ __forceinline__ void dice_shape_term(double u, double g, double& L, double& gu) {
+    if (g == 1.0) { L = u; gu = 1.0; return; }
+    const bool clamped = !(u > 1e-7);
+    L = pow(clamped ? 1e-7 : u, g);
+    gu = clamped ? 0.0 : g * pow(u, g - 1.0);
+}
+
+// One block, dice_finalize_k's ownership of pairs and its order of additions.  The cross-class passes (sum of weights, largest
+// weight) read the per-pair sums back: from LDS for B*C <= 256, from S.tab above; the class passes of the micro form
+// go through cls[][] (C <= 16).  No atomics: repeated calls give the same bits.
+static __global__ __launch_bounds__(kBlock) void dice_shape_finalize_k(const DiceShapeArgs S) {
+    const DiceFinArgs& A = S.f;
+    __shared__ double sh[11][kBlock];  // + macro loss [0], weighted micro I, T, P [8..10]
+    __shared__ double lt[3][kBlock];
+    __shared__ double cls[2][16];      // T_c = sum_b T_bc;  the micro weight w_c
+    double acc[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    const int n = A.B * A.C;
+    double* const tI = n <= kBlock ? lt[0] : S.tab;
+    double* const tT = n <= kBlock ? lt[1] : S.tab + n;
+    double* const tP = n <= kBlock ? lt[2] : S.tab + 2 * (size_t)n;
+    const int hb = kBlock - 1 - (int)threadIdx.x;
+    const bool helper = hb < A.B && n + hb < kBlock;
+    double hs[1] = {0};
+    if (helper) dice_rows_all<1>(A.part + (size_t)hb * A.nblk * A.N + A.C * kDiceVals, A.N, A.nblk, hs);
+    for (int i = threadIdx.x; i < n; i += kBlock) {
+        const int b = i / A.C, c = i % A.C;
+        double v[kDiceVals] = {0, 0, 0, 0, 0};
+        dice_rows_all<kDiceVals>(A.part + (size_t)b * A.nblk * A.N + c * kDiceVals, A.N, A.nblk, v);
+        tI[i] = v[0]; tT[i] = v[1]; tP[i] = v[2];
+        acc[1] += (2.0 * v[3] + 1e-5) / (v[1] + v[4] + 1e-5);
+        acc[2] += v[0]; acc[3] += v[1]; acc[4] += v[2]; acc[5] += v[3]; acc[6] += v[4];
+        if (c == 0 && n + b >= kBlock) {
+            double f[1] = {acc[7]};
+            dice_rows_all<1>(A.part + (size_t)b * A.nblk * A.N + A.C * kDiceVals, A.N, A.nblk, f);
+            acc[7] = f[0];
+        }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < A.C) {
+        double t = 0.0;
+        for (int b = 0; b < A.B; ++b) t += tT[b * A.C + threadIdx.x];
+        cls[0][threadIdx.x] = t;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < A.C) {
+        double w = 1.0;
+        if (S.wmode == 1) w = (double)S.cw[threadIdx.x];
+        if (S.wmode == 2) {
+            double wmax = 0.0;
+            for (int k = 0; k < A.C; ++k) if (cls[0][k] > 0.0) wmax = fmax(wmax, 1.0 / (cls[0][k] * cls[0][k]));
+            const double t = cls[0][threadIdx.x];
+            w = wmax == 0.0 ? 1.0 : (t > 0.0 ? 1.0 / (t * t) : wmax);
+        }
+        cls[1][threadIdx.x] = w;
+    }
+    __syncthreads();
+    const double s = A.smooth, al = S.alpha, be = S.beta, g = S.gamma;
+    for (int i = threadIdx.x; i < n; i += kBlock) {
+        const int b = i / A.C, c = i % A.C;
+        double wmax = 0.0;
+        if (S.wmode == 2)
+            for (int k = 0; k < A.C; ++k) { const double t = tT[b * A.C + k]; if (t > 0.0) wmax = fmax(wmax, 1.0 / (t * t)); }
+        double wsum = 0.0, wi = 0.0;
+        for (int k = 0; k < A.C; ++k) {
+            double w = 1.0;
+            if (S.wmode == 1) w = (double)S.cw[k];
+            if (S.wmode == 2) { const double t = tT[b * A.C + k]; w = wmax == 0.0 ? 1.0 : (t > 0.0 ? 1.0 / (t * t) : wmax); }
+            wsum += w;
+            if (k == c) wi = w;
+        }
+        const double I = tI[i], T = tT[i], P = tP[i];
+        const double N = 2.0 * I + s, D = 2.0 * I + 2.0 * al * (P - I) + 2.0 * be * (T - I) + s;
+        double L, gu;
+        dice_shape_term(1.0 - N / D, g, L, gu);
+        const double wn = wi / wsum;
+        acc[0] += wn * L;
+        dice_fold(wn * gu * A.C, 2.0 * D - 2.0 * (1.0 - al - be) * N, 2.0 * al * N, D, S.bcm + 2 * i);
+        const double wc = cls[1][c];
+        acc[8] += wc * I; acc[9] += wc * T; acc[10] += wc * P;
+    }
+    for (int j = 0; j < 11; ++j) sh[j][threadIdx.x] = acc[j];
+    __syncthreads();
+    if (helper) sh[7][hb * A.C] = hs[0];
+    __syncthreads();
+    for (int o = kBlock / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) for (int j = 0; j < 11; ++j) sh[j][threadIdx.x] += sh[j][threadIdx.x + o];
+        __syncthreads();
+    }
+    const double I = sh[8][0], T = sh[9][0], P = sh[10][0];
+    const double N = 2.0 * I + s, D = 2.0 * I + 2.0 * al * (P - I) + 2.0 * be * (T - I) + s;
+    double L, gu;
+    dice_shape_term(1.0 - N / D, g, L, gu);
+    for (int i = threadIdx.x; i < n; i += kBlock)
+        dice_fold(cls[1][i % A.C] * gu * n, 2.0 * D - 2.0 * (1.0 - al - be) * N, 2.0 * al * N, D, S.bcu + 2 * i);
+    if (threadIdx.x == 0) {
+        const double lmacro = sh[0][0] / A.B;
+        float o4[8];
+        o4[0] = (float)lmacro;
+        o4[1] = (float)L;
+        o4[2] = (float)(sh[1][0] / n);
+        o4[3] = (float)(2.0 * sh[5][0] / (sh[3][0] + sh[6][0]));
+        const double inv_count = A.masked ? (sh[3][0] > 0.0 ? 1.0 / sh[3][0] : 0.0) : A.inv_count;
+        if (A.masked) { S.bcm[2 * n + 2] = inv_count; S.bcu[2 * n + 2] = inv_count; }
+        const double focal = sh[7][0] * inv_count, w = A.focal_w;
+        o4[4] = (float)focal;
+        o4[5] = (float)(w * focal + (1.0 - w) * lmacro);
+        o4[6] = (float)(w * focal + (1.0 - w) * L);
+        o4[7] = 0.f;
+        if (A.bce_on) {
+            const double bce = sh[7][0] * (inv_count / A.C);
+            o4[4] = (float)bce; o4[5] = 0.f; o4[6] = (float)(bce + L);
+        }
+        for (int j = 0; j < 8; ++j) { A.out4[j] = o4[j]; if (A.out4_user && j < A.n_user) A.out4_user[j] = o4[j]; }
+    }
+}
+
 // ---- post-step on device: class map -> boundary maps, the reference's
 // convert_predictions_to_maps_semantic (common/utils.py:115-168) on the one-hot of the arg-max:
 //   cur = [label == k],  g = 2*max(+-gradient_rows(cur), 0)  (np.gradient: central differences, one-sided at the

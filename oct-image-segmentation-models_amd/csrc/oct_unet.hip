@@ -259,6 +259,11 @@ struct oct_unet {
     float focal_w = 0.f, focal_gamma = 2.f; const float* focal_cw = nullptr;           // focal_dice_loss (0 = plain Dice)
     int bce_on = 0;                                                                    // bce_dice_loss (never with focal_w > 0)
     int ignore = -1;                                                                   // ignore label of the loss (-1 = none)
+    // oct_unet_set_dice_shape (shape_on = 0: plain Dice, dice_finalize_k).  The folded macro and micro tables, each laid out as
+    // dice_bc, and the sums table live in one device buffer the handle allocates at the first shape and frees in destroy: the
+    // workspace keeps its size (tests/test_many_classes.py pins it)
+    int shape_on = 0, shape_wmode = 0; float shape_alpha = .5f, shape_beta = .5f, shape_gamma = 1.f; const float* shape_cw = nullptr;
+    double* shape_bcm = nullptr; double* shape_bcu = nullptr; double* shape_tab = nullptr;
     WtDesc* wt_descs = nullptr; int n_wt = 0; unsigned wt_total = 0;
     WbxDesc* wbx_descs = nullptr; int n_wbx_f = 0, n_wbx_b = 0; unsigned wbx_f_total = 0, wbx_b_total = 0;   // [fwd..., bwd...]
     WbtDesc* wbt_descs = nullptr; int n_wbt_f = 0, n_wbt_b = 0; unsigned wbt_f_total = 0, wbt_b_total = 0;   // [fwd..., bwd...]
@@ -792,6 +797,8 @@ int head_backward(oct_unet* h, const unsigned char* labels, int macro, float los
     hb.focal_w = h->focal_w; hb.focal_gamma = h->focal_gamma; hb.focal_cw = h->focal_cw; hb.focal_clip_mod = h->opt.focal_clip_mod; hb.inv_count = 1.f / ((float)B * hb.HW);
     hb.bce_on = h->bce_on; hb.bce_inner = h->opt.bce_inner_eps ? kFocalEps : 0.f; hb.bce_scale = loss_scale * hb.inv_count / (float)h->cfg.n_cls;
     hb.ignore = h->ignore;       // >= 0: the kernels take 1 / (counted pixels) from dice_bc instead of inv_count
+    // shaped Dice: the folded per-(b, c) table of this combination, read with the macro indexing (its 1 / (B C) is folded in)
+    if (h->shape_on) { hb.bc = macro ? h->shape_bcm : h->shape_bcu; hb.macro = 1; }
     const HeadRoute r = head_route(h->opt, h->cfg.n_cls, hd.cin);
     if (r == HEAD_REG && fin_ok(h, last)) { hb.fin = fin_desc(h, nl - 2, 1, B); *fin = true; }   // (only the register kernels finalize the statistics in the launch)
     *rows = B * hb.nblk;
@@ -1103,6 +1110,7 @@ void oct_unet_destroy(oct_unet* h) {
         if (h->prep_ev) (void)hipEventDestroy(h->prep_ev);
         (void)hipStreamDestroy(h->side);
     }
+    if (h->shape_bcm) (void)hipFree(h->shape_bcm);
     if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec);
     if (h->graph) (void)hipGraphDestroy(h->graph);
     delete h;
@@ -1234,7 +1242,17 @@ static int loss_finalize(oct_unet* h, const char* what, float smooth, float* out
     a.N = dice_n(a.C); a.smooth = smooth; a.out4 = h->loss4; a.out4_user = out; a.bc = h->dice_bc;
     a.n_user = n_user; a.inv_count = 1.0 / ((double)h->last_B * h->cfg.H * h->cfg.W); a.focal_w = h->focal_w; a.bce_on = h->bce_on;
     a.masked = h->ignore >= 0;
-    dice_finalize_k<<<1, kBlock, 0, (hipStream_t)stream>>>(a);
+    t_prof = &h->prof;
+    if (h->shape_on) {
+        DiceShapeArgs sa{};
+        sa.f = a; sa.alpha = h->shape_alpha; sa.beta = h->shape_beta; sa.gamma = h->shape_gamma; sa.wmode = h->shape_wmode;
+        sa.cw = h->shape_cw; sa.bcm = h->shape_bcm; sa.bcu = h->shape_bcu; sa.tab = h->shape_tab;
+        ProfScope ps((hipStream_t)stream, "dice_shape_finalize_k", "loss", 0, (double)a.B * a.nblk * a.N * 4);
+        dice_shape_finalize_k<<<1, kBlock, 0, (hipStream_t)stream>>>(sa);
+    } else {
+        ProfScope ps((hipStream_t)stream, "dice_finalize_k", "loss", 0, (double)a.B * a.nblk * a.N * 4);
+        dice_finalize_k<<<1, kBlock, 0, (hipStream_t)stream>>>(a);
+    }
     HIP_OK(hipGetLastError());
     h->dice_final = 1;
     return 0;
@@ -1265,6 +1283,38 @@ int oct_unet_set_ignore_label(oct_unet* h, int label) {
         return fail(-1, "ignore label must be -1 (none) or in n_classes..255: got " + std::to_string(label));
     if (label != h->ignore) { h->have_dice = 0; h->dice_final = 0; }    // sums of a forward under the other setting are not this loss's
     h->ignore = label;
+    return 0;
+}
+
+int oct_unet_set_dice_shape(oct_unet* h, const oct_dice_shape* s) {
+    if (!h) return fail(-1, "null handle");
+    oct_dice_shape d{0.5f, 0.5f, 1.f, 0, nullptr};
+    if (s) d = *s;
+    if (!(d.alpha >= 0.f) || !(d.beta >= 0.f) || !(d.alpha + d.beta > 0.f) || !std::isfinite(d.alpha) || !std::isfinite(d.beta))
+        return fail(-1, "dice_shape: alpha, beta must be finite and >= 0 with alpha + beta > 0");
+    if (!(d.gamma > 0.f && d.gamma <= 8.f)) return fail(-1, "dice_shape: gamma must be in (0, 8]");
+    if (d.weight_mode < 0 || d.weight_mode > 2) return fail(-1, "dice_shape: weight_mode must be 0 (none), 1 (class_weight_dev) or 2 (volume)");
+    if (d.weight_mode == 1) {
+        if (!d.class_weight_dev) return fail(-1, "dice_shape: weight_mode 1 needs class_weight_dev");
+        float w[16]; bool any = false;                 // the setter is no hot path: read the weights back once
+        HIP_OK(hipMemcpy(w, d.class_weight_dev, sizeof(float) * h->cfg.n_cls, hipMemcpyDeviceToHost));
+        for (int c = 0; c < h->cfg.n_cls; ++c) {
+            if (!(w[c] >= 0.f) || !std::isfinite(w[c])) return fail(-1, "dice_shape: class weights must be finite and >= 0");
+            any = any || w[c] > 0.f;
+        }
+        if (!any) return fail(-1, "dice_shape: class weights must not all be zero");
+    }
+    const bool on = !(d.alpha == 0.5f && d.beta == 0.5f && d.gamma == 1.f && d.weight_mode == 0);
+    if (on && !h->shape_bcm) {
+        const size_t pairs = (size_t)h->cfg.max_batch * h->cfg.n_cls, bc_n = 2 * pairs + 3;
+        void* p = nullptr;
+        HIP_OK(hipMalloc(&p, (2 * bc_n + 3 * pairs) * sizeof(double)));
+        h->shape_bcm = (double*)p; h->shape_bcu = h->shape_bcm + bc_n; h->shape_tab = h->shape_bcm + 2 * bc_n;
+    }
+    h->have_dice = 0; h->dice_final = 0;               // sums finalized under the other setting are not this loss's
+    h->shape_alpha = d.alpha; h->shape_beta = d.beta; h->shape_gamma = d.gamma; h->shape_wmode = d.weight_mode;
+    h->shape_cw = d.weight_mode == 1 ? d.class_weight_dev : nullptr;
+    h->shape_on = on;
     return 0;
 }
 

@@ -131,6 +131,7 @@ class UNetEngine:
         # the loss state: what the set_* calls last selected (set_focal_dice's device buffer and parameters by value too); select_loss's kind
         self.ignore_label, self._focal_active, self._bce_active = None, False, False
         self._focal_cw, self._focal_sel, self._loss_kind = None, None, "dice"
+        self.dice_shape, self._shape_cw = None, None       # set_dice_shape's validated keywords (None: plain Dice) and its device weights
 
     def __del__(self):
         if self._h:
@@ -233,10 +234,38 @@ class UNetEngine:
         self._call("oct_unet_set_ignore_label", -1 if label is None else int(label))
         self.ignore_label = None if label is None else int(label)
 
-    def select_loss(self, kind: str = "dice", focal_loss_weight=0.5, gamma=2.0, class_weight=None, ignore_label=None) -> None:
+    def set_dice_shape(self, alpha=0.5, beta: float = 0.5, gamma: float = 1.0, class_weight=None) -> None:
+        """Shape the Dice term of the following forward / loss / backward calls (``oct_unet_set_dice_shape``, DESIGN.md section
+        32): Tversky weights ``alpha`` (false positives) and ``beta`` (false negatives), the focal-Tversky exponent ``gamma``
+        and class weights -- ``None``, a sequence of ``num_classes`` weights, or ``"volume"`` (generalized Dice, 1 / T^2 of the
+        label volume).  The defaults, or ``set_dice_shape(None)``, restore plain Dice.  A pending forward is dropped: call
+        ``forward`` again before the loss."""
+        from .common.custom_losses import check_dice_shape
+        try:
+            shape = None if alpha is None else check_dice_shape(self.cfg.n_cls, alpha, beta, gamma, class_weight)
+        except (ValueError, TypeError) as e:
+            raise OctError(f"set_dice_shape: {e}") from None
+        cw = None
+        if shape is None:
+            self._call("oct_unet_set_dice_shape", None)
+        else:
+            w = shape["class_weight"]
+            mode = _hip.DICE_WEIGHT_NONE if w is None else _hip.DICE_WEIGHT_VOLUME if w == "volume" else _hip.DICE_WEIGHT_CLASS
+            if mode == _hip.DICE_WEIGHT_CLASS:
+                cw = torch.as_tensor(np.asarray(w, np.float32), device=self.device).contiguous()
+            d = _hip.DiceShape(shape["alpha"], shape["beta"], shape["gamma"], mode, _ptr(cw))
+            self._call("oct_unet_set_dice_shape", C.byref(d))
+        self._shape_cw = cw          # keep the device buffer alive: the library only stores the pointer
+        self.dice_shape = shape
+
+    def select_loss(self, kind: str = "dice", focal_loss_weight=0.5, gamma=2.0, class_weight=None, ignore_label=None,
+                    dice_shape=None) -> None:
         """Put the handle into the loss state a model asks for: ``kind`` "dice", "focal" (with ``set_focal_dice``'s parameters,
-        compared by value) or "bce", and the ignore label.  Only the ``set_*`` calls that change what the engine last had selected
-        are issued: an engine last used by a focal, BCE or masked model comes back to plain Dice over every pixel."""
+        compared by value) or "bce", the ignore label and the shape of the Dice term (``set_dice_shape``'s keywords as a dict,
+        None: plain Dice).  Only the ``set_*`` calls that change what the engine last had selected are issued: an engine last
+        used by a focal, BCE, masked or shaped model comes back to plain Dice over every pixel."""
+        if self.dice_shape != dice_shape:
+            self.set_dice_shape(**dice_shape) if dice_shape else self.set_dice_shape(None)
         if self.ignore_label != ignore_label:
             self.set_ignore_label(ignore_label)
         want = (float(focal_loss_weight), float(gamma), None if class_weight is None else np.asarray(class_weight, np.float32).tolist())

@@ -128,6 +128,7 @@ class Model:
         # label value whose pixels do not count in the loss, the Dice metrics or the gradient (compile(ignore_label=...));
         # None: every pixel counts
         self.ignore_label = None
+        self._dice_shape = None
         self._device = device
         self.history = None
 
@@ -255,6 +256,9 @@ class Model:
             raise OctError("compile(loss=...): only the Dice losses, focal_dice_loss and bce_dice_loss from common.custom_losses are "
                            "implemented by the HIP engine (the loss arithmetic is fused into the head kernels)")
         self._focal = dict(getattr(loss, "oct_focal", None) or {}) if loss_name == "focal_dice_loss" else None
+        # the shape of the Dice term (the factories' alpha / beta / tversky_gamma / dice_class_weight; None: plain Dice): every
+        # engine this model steps gets it with the loss kind, per batch (select_loss), the padded-size training engine included
+        self._dice_shape = getattr(loss, "oct_dice_shape", None) if loss is not None else None
         metric_name = None
         for m in metrics or []:
             metric_name = getattr(m, "oct_metric", None)
@@ -391,7 +395,7 @@ class Model:
                 # pad_value is in the units of the Sequence's batches: raw counts where the augment stage has turned them to [0, 1]
                 x, lab = self._pad_batch(eng, x, lab, at, pad_mode, pad_value / 255.0 if raw_u8 and x.dtype != torch.uint8 else pad_value,
                                          ignore)
-            eng.select_loss(kind, *focal, ignore_label=ignore)      # per batch: the engine may be new, or another model's last
+            eng.select_loss(kind, *focal, ignore_label=ignore, dice_shape=self._dice_shape)      # per batch: the engine may be new, or another model's last
             eng.forward(x, training=training, labels=lab, want_probs=False)
             loss = eng.loss_selected()
             if training:

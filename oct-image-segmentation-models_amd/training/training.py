@@ -24,6 +24,9 @@ from . import training_callbacks
 from .training_parameters import TrainingParams
 
 
+SHAPE_KEYS = ("alpha", "beta", "tversky_gamma", "dice_class_weight")     # the loss factories' keywords that shape the Dice term
+
+
 def save_training_params_file(save_foldername: Path, model_summary: str, model_config: dict,
                               training_dataset_md5: str, class_weight, timestamp, train_params: TrainingParams, opt):
     """``model_config.json`` + ``training_params.hdf5`` attributes (training.py:39-132)."""
@@ -57,6 +60,11 @@ def save_training_params_file(save_foldername: Path, model_summary: str, model_c
                                                   val if np.isscalar(val) else np.asarray(val, dtype=np.float64))
     for key, val in opt.get_config().items():
         attrs["opt_param: " + key] = np.bytes_(str(val)) if isinstance(val, (dict, str)) else val
+    # the shape of the Dice term: only the keys that were given (loss_fn_kwargs, or apply_class_weight's), so that a run
+    # without them writes the file it always wrote
+    for key, val in (getattr(train_params, "loss_shape_kwargs", None) or {}).items():
+        attrs["loss_param: " + key] = np.array(val, dtype="S100") if isinstance(val, str) else \
+            val if np.isscalar(val) else np.asarray(val, dtype=np.float64)
     datasets = {} if class_weight is None else {"class_weight": np.asarray(class_weight)}
     h5io.save(save_foldername / Path("training_params.hdf5"), datasets, attrs)
 
@@ -68,6 +76,18 @@ def _balanced_class_weight(labels: np.ndarray, ignore_label=None) -> np.ndarray:
         labels = labels[labels != ignore_label]
     classes, counts = np.unique(labels, return_counts=True)
     return labels.size / (len(classes) * counts.astype(np.float64))
+
+
+def loss_factory_kwargs(training_params: TrainingParams, c_weight) -> dict:
+    """The keywords ``train_model`` gives the loss factory: ``loss_fn_kwargs``, and with ``apply_class_weight`` the computed
+    class weights as ``dice_class_weight`` -- for ``focal_dice_loss`` also as the focal term's ``class_weight`` -- where
+    ``loss_fn_kwargs`` does not name them."""
+    kw = dict(training_params.loss_fn_kwargs)
+    if getattr(training_params, "apply_class_weight", False) and c_weight is not None:
+        kw.setdefault("dice_class_weight", [float(w) for w in c_weight])
+        if training_params.loss == "focal_dice_loss":
+            kw.setdefault("class_weight", [float(w) for w in c_weight])
+    return kw
 
 
 def _count_classes(train_labels: np.ndarray, ignore_label=None) -> int:
@@ -105,11 +125,13 @@ def train_model(training_params: TrainingParams, mlflow_params=None):
     elif type(training_params.class_weight) == list:
         c_weight = np.array(training_params.class_weight)
     else:
-        c_weight = None  # as in the reference, the weights are recorded but never reach the loss (Appendix D.2)
+        c_weight = None
+    # as in the reference, the weights are recorded but do not reach the loss (Appendix D.2) -- unless apply_class_weight asks
+    loss_kwargs = loss_factory_kwargs(training_params, c_weight)
+    training_params.loss_shape_kwargs = {k: loss_kwargs[k] for k in SHAPE_KEYS if k in loss_kwargs}
     sparse_labels = loss["takes_sparse"]
     try:
-        loss_fn = loss["function"](num_classes=num_classes, is_y_true_sparse=sparse_labels,
-                                   **training_params.loss_fn_kwargs)
+        loss_fn = loss["function"](num_classes=num_classes, is_y_true_sparse=sparse_labels, **loss_kwargs)
     except NotImplementedError as e:
         log.error(e)
         exit(1)

@@ -20,7 +20,7 @@ class TrainingParams:
                  class_weight: Union[list, str, None] = None, channels_last: bool = True,
                  early_stopping: bool = True, restore_best_weights: bool = True, patience: int = 50,
                  seed: Union[int, None] = None, aug_device: bool = False, pad_mode: Union[str, None] = None,
-                 pad_value=0, ignore_label: Union[int, None] = None):
+                 pad_value=0, ignore_label: Union[int, None] = None, apply_class_weight: bool = False):
         if (model_architecture is None and initial_model is None) or (
                 model_architecture is not None and initial_model is not None):
             log.error("Either 'model_architecture' or 'initial_model' need to be provided in the `config.json`.")
@@ -69,6 +69,9 @@ class TrainingParams:
         self.pad_mode = pad_mode
         self.pad_value = pad_value
         self.ignore_label = ignore_label
+        # extension: hand the computed class weights ("balanced" or a list) to the loss factory as dice_class_weight -- and, for
+        # focal_dice_loss, as the focal term's class_weight -- unless loss_fn_kwargs names them.  Off: they are only recorded
+        self.apply_class_weight = bool(apply_class_weight)
         self.seed = seed  # extension: reproducible shuffling / init (the reference is unseeded)
         if self.model_save_monitor[0] == "val_acc":
             self.model_save_monitor = ["val_" + self.metric, model_save_monitor[1]]
