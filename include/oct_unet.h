@@ -38,6 +38,8 @@
  *   oct_pad_batch / oct_crop_batch     (none: Keras raises on a size that is no multiple of 2^pool_layers, in the skip concatenation)
  *   oct_warp_batch                     (none at training time; the per-column np.roll of roll_image_offset /
  *                                      flatten_image_boundary        dataset_construction.py is its dataset-preparation kin)
+ *   oct_calibration_counts / oct_temperature_apply / oct_temperature_nll  (none: reliability counts, ECE / NLL / Brier and
+ *                                      temperature scaling of the softmax output, Guo et al. 2017)
  */
 #ifndef OCT_UNET_H
 #define OCT_UNET_H
@@ -605,6 +607,59 @@ int oct_confusion_counts_masked(const unsigned char* pred_dev, const unsigned ch
                                 int ignore_label, unsigned int* counts_dev /* (B, n_cls*n_cls + 2) */, oct_stream_t stream);
 int oct_area_labels(const unsigned short* segs_dev /* (B, n_cls-1, W) */, int B, int H, int W, int n_cls,
                     unsigned char* labels_dev /* (B, H, W) */, oct_stream_t stream);
+
+/* ---- calibration on the device (csrc/kernels_calibration.hpp; numpy restatement: evaluation/calibration.py; the reference has
+ * no counterpart: nothing there asks whether its softmax output is a probability) ----
+ * Three calls on class probabilities probs_dev (B, npix, n_cls) float32 -- the (B,H,W,n_cls) tensor the head, oct_mc_update or
+ * oct_tta_update leave on the device, npix = H*W -- two of them against ground-truth labels_dev (B, npix) uint8.  A pixel is
+ * COUNTED iff its label y < n_cls and y != ignore_label (-1: none, else 0..255).  EPS = 1e-7f (FOCAL_EPS of the losses).  Every
+ * per-pixel step is one IEEE fp32 operation, sums over classes run in class order, nothing is contracted, logf / expf are the
+ * OCML library functions; every sum over pixels is fp64.
+ *
+ * oct_calibration_counts, per image over its counted pixels, with M = n_bins in 1..64:
+ *   m    = the lowest index of the maximum of p          conf = min(max(p_m, 0), 1)
+ *   k    = (uint32) floor(conf * 2^28)                   (the product is exact: a power of two)
+ *   bin  = min(M - 1, (uint64(k) * M) >> 28)             (integers: a confidence on a bin edge has one answer; 1.0 -> M - 1)
+ *   counts[b][bin] += (1, m == y, k)                     counts_dev: uint64 (B, M, 3) = pixels, correct pixels, sum of k
+ *   nll   = -logf(min(max(p_y, EPS), 1 - EPS))           (1 - EPS in fp32; the cross-entropy of the focal and BCE terms)
+ *   brier = sum_c (p_c - [c == y])^2                     (fp32: subtract, square, add in class order)
+ *   sums_dev: float64 (B, 4) = sum nll, sum brier, counted pixels, pixels with y >= n_cls that are not ignore_label.
+ *   The integer words do not depend on any order and are compared bit for bit with the restatement; the fp64 sums are
+ *   reduced thread -> wave -> block -> image in a fixed order, so repeated calls give identical bytes.  The confidence of a
+ *   distribution over <= 32 classes is >= 2^-5, hence a multiple of 2^-28: for such input k loses nothing.
+ *
+ * oct_temperature_apply, per pixel of (npix_total, n_cls), beta = 1 / T finite and > 0:
+ *   l_c = logf(max(p_c, EPS))   L = max_c l_c   e_c = expf(beta * (l_c - L))   S = e_0 + e_1 + ...   q_c = e_c / S
+ *   i.e. softmax(logits / T) formed from the probabilities alone.  probs_out_dev may be probs_in_dev (a pixel is owned by one
+ *   thread); any other overlap is an error.
+ *
+ * oct_temperature_nll, per image over its counted pixels and for each of the K = n_betas <= 8 values betas[k] (a HOST array,
+ * read during the call), with l, L, e, S, q as above:
+ *   nll = logf(S) - beta * (l_y - L)
+ *   mu  = q_0 * l_0 + q_1 * l_1 + ...                    g = mu - l_y
+ *   h   = q_0 * ((l_0 - mu) * (l_0 - mu)) + ...          (the centred form: E[l^2] - E[l]^2 cancels)
+ *   out_dev: float64, (B, K, 3) sums of nll, g, h, then (B) counted pixels.  g and h are the first and second derivative in
+ *   beta of the summed NLL, which is convex in beta.  The row of a beta does not depend on K or on its position.
+ *
+ * All are stand-alone like oct_mc_update: no handle, no allocation, asynchronous on `stream` (counts and nll: a launch over the
+ * pixels that leaves one partial row per block in the caller-owned workspace, and a small one that adds the rows per image;
+ * no global atomics), never wait, record into a stream capture.  Pointers need their natural alignment (outputs and
+ * workspace: 8 bytes); with 16-byte aligned probabilities, n_cls <= 8 and npix*n_cls % 4 == 0 the kernels move float4s.
+ * Errors (negative, oct_last_error(), nothing launched): null pointers, B outside 1..65535, npix < 1, B*npix >= 2^31, n_cls
+ * outside 2..32, n_bins outside 1..64, n_betas outside 1..8, a beta that is not finite and positive, ignore_label outside
+ * -1..255, a workspace smaller than the _workspace_bytes of the call, misaligned buffers, overlapping ranges.  The
+ * _workspace_bytes functions return 0 for a shape the calls refuse. */
+size_t oct_calibration_workspace_bytes(int B, size_t npix, int n_cls, int n_bins);
+int oct_calibration_counts(const float* probs_dev /* (B, npix, n_cls) f32 */, const unsigned char* labels_dev /* (B, npix) */,
+                           int B, size_t npix, int n_cls, int ignore_label, int n_bins,
+                           unsigned long long* counts_dev /* (B, n_bins, 3) */, double* sums_dev /* (B, 4) */,
+                           void* ws_dev, size_t ws_bytes, oct_stream_t stream);
+int oct_temperature_apply(const float* probs_in_dev, float* probs_out_dev /* (npix_total, n_cls) f32 */, size_t npix_total,
+                          int n_cls, float beta, oct_stream_t stream);
+size_t oct_temperature_workspace_bytes(int B, size_t npix, int n_cls, int n_betas);
+int oct_temperature_nll(const float* probs_dev, const unsigned char* labels_dev, int B, size_t npix, int n_cls, int ignore_label,
+                        const float* betas /* host, n_betas values */, int n_betas,
+                        double* out_dev /* (B, n_betas, 3) then (B) */, void* ws_dev, size_t ws_bytes, oct_stream_t stream);
 
 /* ---- PNG pictures on the device (csrc/kernels_render.hpp; numpy restatement: common/plotting.py::render_reference) ----
  * oct_render_rgba renders B images of H x W into out_dev (B, H, W, 4) uint8 RGBA with A = 255: a base layer, then

@@ -549,6 +549,75 @@ class UNetEngine:
                 _hip.expect(t_, what, device=self.device, dtype=dt, shape=shape)
         return _hip.McOut(_ptr(mean_probs), _ptr(argmax), _ptr(entropy), _ptr(mutual_info))
 
+    # ---- calibration: reliability counts and temperature on the device (evaluation/calibration.py restates them) ----
+    def _cal_inputs(self, what: str, probs: torch.Tensor, labels: torch.Tensor, ignore_label):
+        """The tensor checks of ``calibration_counts`` / ``temperature_nll`` -> ``(B, npix, C, ignore_label as the ABI's int)``."""
+        if probs.dim() < 3:
+            raise OctError(f"{what}: probs must be (B,...,C), not {tuple(probs.shape)}")
+        _hip.expect(probs, f"{what}: probs (B,...,C)", device=self.device, dtype=torch.float32, shape=(None,) * probs.dim())
+        B, Cn = probs.shape[0], probs.shape[-1]
+        npix = probs.numel() // max(B * Cn, 1)
+        _hip.expect(labels, f"{what}: labels (B,...)", device=self.device, dtype=torch.uint8, numel=B * npix)
+        if ignore_label is not None and not (int(ignore_label) == ignore_label and 0 <= int(ignore_label) <= 255):
+            raise OctError(f"{what}: ignore_label must be None or an int in 0..255, not {ignore_label!r}")
+        return B, npix, Cn, -1 if ignore_label is None else int(ignore_label)
+
+    def _cal_ws(self, ws, nbytes: int, what: str) -> torch.Tensor:
+        if not nbytes:
+            raise OctError(f"{what}: unsupported shape (oct_last_error: {_hip.lib().oct_last_error().decode()})")
+        if ws is None:
+            return torch.empty((nbytes,), dtype=torch.uint8, device=self.device)
+        _hip.expect(ws, f"{what}: workspace", device=self.device, dtype=torch.uint8, shape=(None,))
+        return ws
+
+    def calibration_counts(self, probs: torch.Tensor, labels: torch.Tensor, n_bins: int, ignore_label: Optional[int] = None, *,
+                           counts=None, sums=None, ws=None):
+        """Reliability counts of class probabilities ``probs`` (B,...,C) float32, any C in 2..32, against ``labels`` (B,...)
+        uint8 in ``n_bins`` = 1..64 confidence bins (``oct_calibration_counts``; ``calibration_counts_reference``): returns
+        ``(counts (B, n_bins, 3) int64 -- the bits are uint64 [pixels, correct, sum of floor(conf 2^28)] --, sums (B, 4) float64 =
+        [sum nll, sum brier, counted, labels >= C that are not ignore_label])`` on the device.  ``counts`` / ``sums`` / ``ws``
+        (uint8, ``oct_calibration_workspace_bytes``): optional tensors to use.  Asynchronous on the current stream."""
+        B, npix, Cn, ig = self._cal_inputs("calibration_counts", probs, labels, ignore_label)
+        M = int(n_bins)
+        ws = self._cal_ws(ws, int(_hip.lib().oct_calibration_workspace_bytes(B, npix, Cn, M)), "calibration_counts")
+        counts = torch.empty((B, M, 3), dtype=torch.int64, device=self.device) if counts is None else counts
+        sums = torch.empty((B, 4), dtype=torch.float64, device=self.device) if sums is None else sums
+        _hip.expect(counts, "calibration_counts: counts", device=self.device, dtype=torch.int64, shape=(B, M, 3))
+        _hip.expect(sums, "calibration_counts: sums", device=self.device, dtype=torch.float64, shape=(B, 4))
+        _hip.call("oct_calibration_counts", self.device, probs.data_ptr(), labels.data_ptr(), B, npix, Cn, ig, M, counts.data_ptr(),
+                  sums.data_ptr(), ws.data_ptr(), ws.numel(), self._stream())
+        return counts, sums
+
+    def temperature_apply(self, probs: torch.Tensor, beta: float, out=None) -> torch.Tensor:
+        """softmax(beta * log p) over the last axis of ``probs`` (...,C) float32 -- the class probabilities at temperature
+        1 / beta, formed from the probabilities alone (``oct_temperature_apply``; ``temperature_apply_reference``).  ``out``:
+        optional tensor to write into; it may be ``probs`` itself.  Asynchronous on the current stream."""
+        if probs.dim() < 2:
+            raise OctError(f"temperature_apply: probs must be (...,C), not {tuple(probs.shape)}")
+        _hip.expect(probs, "temperature_apply: probs (...,C)", device=self.device, dtype=torch.float32, shape=(None,) * probs.dim())
+        out = torch.empty_like(probs) if out is None else out
+        _hip.expect(out, "temperature_apply: out", device=self.device, dtype=torch.float32, shape=tuple(probs.shape))
+        Cn = probs.shape[-1]
+        _hip.call("oct_temperature_apply", self.device, probs.data_ptr(), out.data_ptr(), probs.numel() // max(Cn, 1), Cn, float(beta),
+                  self._stream())
+        return out
+
+    def temperature_nll(self, probs: torch.Tensor, labels: torch.Tensor, betas, ignore_label: Optional[int] = None, *,
+                        out=None, ws=None):
+        """For each of the 1..8 ``betas``: the per-image sums over the counted pixels of the NLL of the probabilities tempered
+        by it and of its first and second derivative in beta (``oct_temperature_nll``; ``temperature_nll_reference``).
+        Returns ``(sums (B, K, 3) float64, counted (B) float64)``, two views of ``out`` -- optional, float64 of B*K*3 + B
+        elements.  Asynchronous on the current stream."""
+        B, npix, Cn, ig = self._cal_inputs("temperature_nll", probs, labels, ignore_label)
+        bs = [float(b) for b in np.atleast_1d(np.asarray(betas, dtype=np.float64))]
+        K = len(bs)
+        ws = self._cal_ws(ws, int(_hip.lib().oct_temperature_workspace_bytes(B, npix, Cn, K)), "temperature_nll")
+        out = torch.empty((B * K * 3 + B,), dtype=torch.float64, device=self.device) if out is None else out
+        _hip.expect(out, "temperature_nll: out", device=self.device, dtype=torch.float64, shape=(B * K * 3 + B,))
+        _hip.call("oct_temperature_nll", self.device, probs.data_ptr(), labels.data_ptr(), B, npix, Cn, ig, (C.c_float * K)(*bs), K,
+                  out.data_ptr(), ws.data_ptr(), ws.numel(), self._stream())
+        return out[:B * K * 3].view(B, K, 3), out[B * K * 3:]
+
     # ---- test-time augmentation: flipped views averaged on the device ---------------------------------
     def flip(self, t: torch.Tensor, view, out=None) -> torch.Tensor:
         """(B,H,W[,C]) uint8 or float32 -> the same shape mirrored by ``view`` -- a name of ``common.utils.TTA_VIEWS`` or its

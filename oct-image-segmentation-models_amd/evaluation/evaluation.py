@@ -32,6 +32,7 @@ from ..common import (EVALUATION_METRIC_AVERAGE_SURFACE_DISTANCE, EVALUATION_MET
 from ..common import utils as common_utils
 from ..min_path_processing import graph_search, utils
 from ..models import get_model_class
+from .calibration import CALIBRATION_METRICS, calibration_from_counts, counts_as_float, pooled_calibration
 from .dice_device import DICE_METRICS, MAX_EXACT_PIXELS, dice_from_counts
 from .evaluation_parameters import EvaluationParameters
 from .pipeline import InferenceRun
@@ -170,7 +171,9 @@ def evaluate_model(eval_params: EvaluationParameters) -> List[EvaluationOutput]:
     if metrics_device and eval_images.shape[1] * eval_images.shape[2] > MAX_EXACT_PIXELS:
         log.info(f"metrics_device: images above {MAX_EXACT_PIXELS} pixels keep the host metrics")
         metrics_device = False
-    need_gt = want_surface or (metrics_device and want_dice)
+    # calibration_bins / temperature: reliability counts of the (tempered) probabilities on the device
+    calibration_bins, temperature = getattr(eval_params, "calibration_bins", 0), getattr(eval_params, "temperature", 1.0)
+    need_gt = want_surface or (metrics_device and want_dice) or calibration_bins > 0
     gt_maps = np.squeeze(eval_labels[lo:hi], axis=3) if need_gt else None
     # BASELINE configs[4] path (evaluation/pipeline.py::InferenceRun): search mode, batch source and worker pools
     # png_plots: the pictures of evaluation.py:488-548 and :673-695 of the reference, under its save_params conditions
@@ -181,7 +184,8 @@ def evaluate_model(eval_params: EvaluationParameters) -> List[EvaluationOutput]:
                       gs_device_ties=eval_params.gs_device_ties, gs_workers=eval_params.gs_workers,
                       soft_maps=not getattr(eval_params, "binarize", True),
                       pad_mode=getattr(eval_params, "pad_mode", None), pad_value=getattr(eval_params, "pad_value", 0),
-                      ignore_label=ignore_label, tta=getattr(eval_params, "tta", None)) as run:
+                      ignore_label=ignore_label, tta=getattr(eval_params, "tta", None),
+                      calibration_bins=calibration_bins, temperature=temperature) as run:
         t_prev = time.time()
         for batch in run:
             b0, b1 = lo + batch.lo, lo + batch.hi
@@ -222,7 +226,8 @@ def evaluate_model(eval_params: EvaluationParameters) -> List[EvaluationOutput]:
                 boundary_maps = np.squeeze(boundary_maps, axis=0)
                 _save_image_evaluation_results(eval_params, eval_image, eval_image_name, predicted_labels, categorical_pred,
                                                eval_label, eval_seg, dice_classes, dice_macro, dice_micro, predict_time,
-                                               eval_image_output_dir, surface_ds, raw_label)
+                                               eval_image_output_dir, surface_ds, raw_label,
+                                               None if batch.calibration is None else tuple(t[ind - b0] for t in batch.calibration))
 
                 gs_pred_segs = errors = mean_abs_err = mean_err = abs_err_sd = err_sd = None
                 if eval_params.graph_search:
@@ -263,9 +268,10 @@ def evaluate_model(eval_params: EvaluationParameters) -> List[EvaluationOutput]:
 
 def _save_image_evaluation_results(eval_params, eval_image, image_name, predicted_labels, categorical_pred, eval_labels,
                                    eval_segs, dice_classes, dice_macro, dice_micro, predict_time, output_dir,
-                                   surface_ds=None, raw_labels=None):
+                                   surface_ds=None, raw_labels=None, calibration=None):
     """``raw_labels`` (H,W): the ground truth as given, where ``eval_labels`` is a one-hot array with ignored pixels zeroed
-    (``ignore_label``): the files store it, ignore value included."""
+    (``ignore_label``): the files store it, ignore value included.  ``calibration``: the image's ``(counts (M, 3) uint64,
+    sums (4,))`` of ``Batch.calibration``; the file gains ``calibration_counts`` and the four metrics made of them."""
     with open(output_dir / "input_image_name.txt", "w") as f:
         f.write(str(image_name))
     np.savetxt(output_dir / Path("predicted_segmentation_map.csv"), predicted_labels, fmt="%d", delimiter=",")
@@ -287,6 +293,10 @@ def _save_image_evaluation_results(eval_params, eval_image, image_name, predicte
         ds[EVALUATION_METRIC_DICE_MICRO] = np.expand_dims(dice_micro, axis=0).astype("float64")
     for k, v in (surface_ds or {}).items():          # evaluation.py:573-597
         ds[k] = np.asarray(v, dtype="float64")
+    if calibration is not None:
+        ds["calibration_counts"] = counts_as_float(calibration[0])
+        for k, v in calibration_from_counts(*calibration).items():
+            ds[k] = np.array([v], dtype="float64")
     attrs = common_utils.result_attrs(eval_params.model_path, image_name, predict_time=np.array(predict_time))
     if getattr(eval_params, "tta", None):
         attrs["tta_views"] = np.array(",".join(eval_params.tta), dtype="S1000")      # only when set: other files stay as they were
@@ -331,6 +341,10 @@ def save_eval_config_file(eval_params: EvaluationParameters):
         attrs["ignore_label"] = np.array(int(eval_params.ignore_label))      # likewise
     if getattr(eval_params, "tta", None):
         attrs["tta_views"] = np.array(",".join(eval_params.tta), dtype="S1000")      # likewise
+    if getattr(eval_params, "calibration_bins", 0):
+        attrs["calibration_bins"] = np.array(int(eval_params.calibration_bins))      # likewise
+    if getattr(eval_params, "temperature", 1.0) != 1.0:
+        attrs["temperature"] = np.array(float(eval_params.temperature))      # likewise
     h5io.save(eval_params.save_foldername / Path("eval_params.hdf5"), {}, attrs)
 
 
@@ -368,6 +382,15 @@ def _calc_overall_dataset_errors(eval_params: EvaluationParameters, eval_image_n
             save_metric(name, stack(files, name))
     if EVALUATION_METRIC_HAUSDORFF_DISTANCE in metrics:
         save_metric("hausdorff_distances", stack(files, "hausdorff_distances"))
+    if getattr(eval_params, "calibration_bins", 0):
+        for m in CALIBRATION_METRICS:
+            save_metric(m, stack(files, m))
+        # the POOLED values: of the counts summed over the images, re-read from the per-image files (ranks exchange nothing)
+        tables = stack(files, "calibration_counts")
+        out["calibration_counts"], pooled = pooled_calibration(tables, stack(files, "nll")[:, 0], stack(files, "brier")[:, 0])
+        for m in CALIBRATION_METRICS:
+            out[f"pooled_{m}"] = np.array([pooled[m]], dtype="float64")
+            lines.append(f"Pooled {m},{pooled[m]:.7f}")
     if eval_params.graph_search:
         for m in (EVALUATION_METRIC_DICE_CLASSES, EVALUATION_METRIC_DICE_MACRO, EVALUATION_METRIC_DICE_MICRO):
             if m in metrics:

@@ -28,7 +28,18 @@ class EvaluationParameters:
                  bg_ilm: bool = True, bg_csi: bool = False, batch_size: int = 32, gs_device: bool = False,
                  gs_device_ties: str = "host", gs_workers: Optional[int] = None, metrics_device: bool = False,
                  png_plots: bool = False, pad_mode: Optional[str] = None, pad_value=0, ignore_label: Optional[int] = None,
-                 tta=None):
+                 tta=None, calibration_bins: int = 0, temperature: float = 1.0):
+        # extension: calibration of the class probabilities.  calibration_bins, an int in 0..64: with
+        # M > 0 the reliability counts of the probabilities against the ground truth are made on the device in M confidence
+        # bins; each image's results gain calibration_counts (M, 3) = [n, correct, sum of confidences], ece, mce, nll and brier,
+        # the overall results their mean / sd and the pooled values.  With tta the counts are those of the mean prediction.
+        # temperature, a number in [1/16, 16]: the probabilities are tempered on the device (softmax(logits / temperature)) in
+        # front of the binarize=False maps and the counts; not together with tta.  Defaults: nothing is launched, no file changes
+        from .calibration import check_bins, check_temperature
+        self.calibration_bins, self.temperature = check_bins(calibration_bins), check_temperature(temperature)
+        if self.temperature != 1.0 and utils.check_tta(tta):
+            raise ValueError("temperature != 1 together with tta: the views would have to be tempered before they are averaged, "
+                             "which is not implemented")
         # extension: test-time augmentation.  1..4 distinct view names out of common.utils.TTA_VIEWS ("identity", "flip_lr",
         # "flip_ud", "flip_both"): every batch is predicted once per view on the mirrored scans, the softmax outputs are mirrored
         # back and averaged on the device, and all metrics, boundary maps, graph-search delineations and pictures come from

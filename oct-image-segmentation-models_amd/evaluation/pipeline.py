@@ -18,6 +18,7 @@ import torch
 from ..common.utils import check_pad_mode, check_tta, padded_geometry
 from ..min_path_processing.device_search import DeviceMinPath, LazyPool, merge_ties
 from ..min_path_processing.pool import SegmentPool, default_workers
+from .calibration import CalibrationCounts, check_bins, check_temperature
 from .dice_device import ConfusionCounts, DelineationLabels, check_ignore_label
 from .render import PngRenderer, batch_pictures
 from .surface import SurfaceDistances
@@ -40,38 +41,50 @@ class Batch(NamedTuple):
     # None on every other record.
     entropy = None
     mutual_info = None
+    # Runs with calibration_bins > 0 carry the reliability counts of the class probabilities against the ground truth:
+    # (counts (n, M, 3) uint64 = [pixels, correct, sum of floor(conf 2^28)], sums (n, 4) float64 = [sum nll, sum brier, counted,
+    # 0]) -- evaluation/calibration.py.  An ATTRIBUTE for the same reason, None on every other record.
+    calibration = None
 
     def with_uncertainty(self, entropy: np.ndarray, mutual_info: np.ndarray) -> "Batch":
         """This record with ``entropy`` / ``mutual_info`` set."""
         b = _UncertainBatch(*self)
-        b.entropy, b.mutual_info = entropy, mutual_info
+        b.entropy, b.mutual_info, b.calibration = entropy, mutual_info, self.calibration
+        return b
+
+    def with_calibration(self, calibration) -> "Batch":
+        """This record with ``calibration`` set."""
+        b = _UncertainBatch(*self)
+        b.entropy, b.mutual_info, b.calibration = self.entropy, self.mutual_info, calibration
         return b
 
 
 class _UncertainBatch(Batch):
-    """A ``Batch`` that can hold the two attributes (a NamedTuple instance has no dictionary; an instance of this has)."""
+    """A ``Batch`` that can hold the attributes (a NamedTuple instance has no dictionary; an instance of this has)."""
 
 
 class _Stage(NamedTuple):
     """One per-batch device post-process: the ``Batch`` field it fills, the wrapper that runs it -- ``run(*inputs, *outs)``
     queues it on the current stream, ``run.outs`` are its own output buffers for a full batch, ``run.to_host`` turns
-    output rows into the field's value -- and what it reads: the boundary maps, or else the arg-max maps and the ground
-    truth."""
+    output rows into the field's value -- and what it reads: the boundary maps, or else the ground truth with the arg-max
+    maps or (``on_probs``) with the class probabilities."""
     field: str
     run: object
     on_maps: bool
+    on_probs: bool = False
 
-    def launch(self, n: int, outs, labels, gt, maps) -> None:
-        inputs = (maps[:n],) if self.on_maps else (labels[:n], gt[:n])
+    def launch(self, n: int, outs, labels, gt, maps, probs=None) -> None:
+        inputs = (maps[:n],) if self.on_maps else (probs[:n], gt[:n]) if self.on_probs else (labels[:n], gt[:n])
         self.run(*inputs, *(t[:n] for t in outs))
 
     def to_host(self, n: int, outs, first_image: int):
         return self.run.to_host(*(t[:n] for t in outs), first_image=first_image)
 
 
-def _stages(surface, confusion, minpath, have_gt: bool = True) -> list:
+def _stages(surface, confusion, minpath, have_gt: bool = True, calibration=None) -> list:
     """The stages to run, in their order on the stream; those that read the ground truth only when there is one."""
-    every = (_Stage("surface", surface, False), _Stage("confusion", confusion, False), _Stage("minpath", minpath, True))
+    every = (_Stage("surface", surface, False), _Stage("confusion", confusion, False),
+             _Stage("calibration", calibration, False, True), _Stage("minpath", minpath, True))
     return [st for st in every if st.run is not None and (st.on_maps or have_gt)]
 
 
@@ -115,11 +128,22 @@ class BatchedPredictor:
     view the flip of the input, the forward and the mirrored fold; with ``hw`` the pad in front, the views taken of the
     padded batch, and the crops behind).  As for ``mc_samples`` the arg-max maps and (with ``soft_maps``) the probabilities
     are those of the MEAN prediction and ``Batch.entropy`` / ``Batch.mutual_info`` carry the two maps over the views;
-    the result does not depend on the batch an image sits in.  ``tta`` with ``mc_samples`` > 0 is refused."""
+    the result does not depend on the batch an image sits in.  ``tta`` with ``mc_samples`` > 0 is refused.
+
+    With ``calibration`` (an ``evaluation.calibration.CalibrationCounts`` for this batch and shape) the chain is asked for the
+    class probabilities, which stay on the device; the ground truth is uploaded as for ``confusion``, ``oct_calibration_counts``
+    runs on the (cropped; with ``mc_samples`` / ``tta`` the MEAN) probabilities, and ``Batch.calibration`` holds ``(counts,
+    sums)``.  With ``temperature`` != 1 ``oct_temperature_apply`` tempers the probabilities in place behind the chain, in
+    front of the soft maps and the counts; the arg-max maps do not depend on it.  It is refused together with ``mc_samples`` or
+    ``tta``: the samples would have to be tempered before the fold.  With ``temperature`` == 1.0 nothing is launched."""
 
     def __init__(self, engine, batch: int, want_maps: bool = True, bg_ilm: bool = True, bg_csi: bool = False,
                  surface=None, minpath=None, confusion=None, soft_maps: bool = False, mc_samples: int = 0, mc_step0: int = 0,
-                 hw=None, pad_mode: Optional[str] = None, pad_value=0, tta=None):
+                 hw=None, pad_mode: Optional[str] = None, pad_value=0, tta=None, calibration=None, temperature: float = 1.0):
+        self.temperature = check_temperature(temperature)
+        if self.temperature != 1.0 and (mc_samples or tta):
+            raise ValueError("temperature != 1 with mc_samples or tta: the samples would have to be tempered before they are "
+                             "folded, which is not implemented")
         if soft_maps and not want_maps:
             raise ValueError("soft_maps: needs want_maps=True")
         if not 0 <= int(mc_samples) <= 64:
@@ -147,9 +171,9 @@ class BatchedPredictor:
         self.map_pin = [torch.empty((self.B, C - 1, H, W), dtype=torch.uint8).pin_memory() for _ in range(2)] if want_maps else None
         self.lab_dev = [torch.empty((self.B, H, W), dtype=torch.uint8, device=dev) for _ in range(2)]
         self.map_dev = [torch.empty((self.B, C - 1, H, W), dtype=torch.uint8, device=dev) for _ in range(2)] if want_maps else None
-        self.wrappers = (surface, confusion, minpath)
+        self.wrappers, self.calibration = (surface, confusion, minpath), calibration
         self.out_dev, self.out_pin = {}, {}                 # per stage field: device and pinned double buffers
-        every = _stages(*self.wrappers)
+        every = _stages(*self.wrappers, calibration=calibration)
         for st in every:
             if st.on_maps and not want_maps:
                 raise ValueError(f"{st.field}: needs want_maps=True")
@@ -170,7 +194,8 @@ class BatchedPredictor:
         # THE chain over the fixed input: captured once and replayed per batch, or -- Monte-Carlo -- repeated eagerly per batch
         pad = None if self.at is None else (*self.at, self.pad_mode, self.pad_value)
         self._infer = lambda capture: engine.infer(self.x_dev, mc=(self.mc_samples, self.mc_step0) if self.mc_samples else None,
-                                                   tta=self.tta or None, pad=pad, want_probs=self.soft_maps, want_argmax=True,
+                                                   tta=self.tta or None, pad=pad, want_argmax=True,
+                                                   want_probs=self.soft_maps or calibration is not None or self.temperature != 1.0,
                                                    capture=capture)
         self.out = self._infer(not self.mc_samples)         # the maps every batch refills (engine-owned buffers)
         self.am, self.probs = self.out["argmax"], self.out.get("mean_probs", self.out.get("probs"))
@@ -180,10 +205,10 @@ class BatchedPredictor:
         if images_u8.dtype != np.uint8:
             raise TypeError("the batched pipeline takes raw uint8 images (the /255 happens on the device)")
         have_gt = gt_u8 is not None
-        stages = _stages(*self.wrappers, have_gt=have_gt)
+        stages = _stages(*self.wrappers, have_gt=have_gt, calibration=self.calibration)
         if have_gt:
             if all(st.on_maps for st in stages):
-                raise ValueError("ground-truth maps given to a BatchedPredictor built without surface= or confusion=")
+                raise ValueError("ground-truth maps given to a BatchedPredictor built without surface=, confusion= or calibration=")
             gt_u8 = np.ascontiguousarray(gt_u8)
             if gt_u8.dtype != np.uint8 or gt_u8.shape != images_u8.shape[:3]:
                 raise TypeError(f"gt_u8 must be uint8 class maps of shape {images_u8.shape[:3]}")
@@ -233,10 +258,13 @@ class BatchedPredictor:
             if i >= 2:
                 main.wait_event(out_done[s])                                            # device out buffers of batch i-2 downloaded
             self.lab_dev[s].copy_(self.am)
+            if self.temperature != 1.0:                                                 # in place, in front of the soft maps and the counts
+                eng.temperature_apply(self.probs, 1.0 / self.temperature, out=self.probs)
             if mc is not None:
                 self.unc_dev[s][0].copy_(mc["entropy"]); self.unc_dev[s][1].copy_(mc["mutual_info"])
             outs = [self.out_dev[st.field][s] for st in stages]
-            srcs = (self.lab_dev[s], self.gt_dev[s], self.map_dev[s] if self.want_maps else None)
+            # (the probabilities are the chain's own buffer: the stage that reads them is queued in front of the next batch's launch)
+            srcs = (self.lab_dev[s], self.gt_dev[s], self.map_dev[s] if self.want_maps else None, self.probs)
             for st, o in zip(stages, outs):
                 if not st.on_maps:
                     st.launch(hi - lo, o, *srcs)
@@ -273,7 +301,11 @@ class BatchedPredictor:
         ev.synchronize()
         labels = self.lab_pin[s][:hi - lo].numpy().copy()
         maps = self.map_pin[s][:hi - lo].numpy().copy() if self.want_maps else None
-        batch = Batch(lo, hi, labels, maps, **{st.field: st.to_host(hi - lo, self.out_pin[st.field][s], lo) for st in stages})
+        fields = {st.field: st.to_host(hi - lo, self.out_pin[st.field][s], lo) for st in stages}
+        calibration = fields.pop("calibration", None)
+        batch = Batch(lo, hi, labels, maps, **fields)
+        if calibration is not None:
+            batch = batch.with_calibration(calibration)
         if self.unc_pin is not None:
             batch = batch.with_uncertainty(*(t[:hi - lo].numpy().copy() for t in self.unc_pin[s]))
         return batch
@@ -281,11 +313,16 @@ class BatchedPredictor:
 
 def host_batches(model, images: np.ndarray, batch: int, *, gt_u8: Optional[np.ndarray] = None, surface=None,
                  minpath=None, confusion=None, soft_maps: bool = False, mc_samples: int = 0, mc_step0: int = 0,
-                 pad_mode: Optional[str] = None, pad_value=0, tta=None) -> Iterator[Batch]:
+                 pad_mode: Optional[str] = None, pad_value=0, tta=None, calibration_bins: int = 0,
+                 temperature: float = 1.0) -> Iterator[Batch]:
     """The same records for images that are not uint8: x / 255 on the host (``Model.predict_labels``), one synchronous
     forward per batch, no overlap.  ``surface`` / ``minpath`` / ``confusion`` / ``soft_maps`` / ``mc_samples`` /
     ``mc_step0`` / ``tta`` as in ``BatchedPredictor``; each stage writes its own output buffers.  ``pad_mode`` / ``pad_value`` (in raw
-    counts) go to ``Model.predict_labels``, which pads and crops on the device."""
+    counts) go to ``Model.predict_labels``, which pads and crops on the device.  ``calibration_bins`` / ``temperature``: refused
+    here -- calibration exists for raw uint8 images only."""
+    if check_bins(calibration_bins) or check_temperature(temperature) != 1.0:
+        raise ValueError("calibration_bins / temperature need raw uint8 images: the path for other dtypes (host_batches) has no "
+                         "calibration stage")
     pad_mode, pad_value = check_pad_mode(pad_mode, pad_value)
     tta = check_tta(tta, mc_samples)
     stages = _stages(surface, confusion, minpath, have_gt=gt_u8 is not None)
@@ -342,15 +379,28 @@ class InferenceRun:
     hold that value, and it is handed to the ``surface`` and ``confusion`` stages and to ``gs_labels``, which run their
     masked kernels.  Labels, maps, searches and pictures do not depend on it.
 
+    ``calibration_bins`` > 0 with ``gt``: a ``CalibrationCounts`` stage with that many confidence bins fills
+    ``Batch.calibration``.  ``temperature`` != 1 tempers the probabilities on the device in front of the
+    soft maps and the counts; with ``mc_samples`` or ``tta`` it is refused.  Both need raw uint8 images: for another dtype
+    either keyword is a ``ValueError``.
+
     ``batches`` replaces the model by a ready source of records (tests of the host side: no device is touched)."""
 
     def __init__(self, model, images: np.ndarray, batch: int, num_classes: int, *, gt: Optional[np.ndarray] = None,
                  graph_search: bool = False, gsgrad: int = 1, gs_device: bool = False, gs_device_ties: str = "host",
                  gs_workers: Optional[int] = None, batches: Optional[Iterable[Batch]] = None, surface: bool = True,
                  confusion: bool = False, soft_maps: bool = False, mc_samples: int = 0, mc_step0: int = 0,
-                 pad_mode: Optional[str] = None, pad_value=0, ignore_label: Optional[int] = None, tta=None):
+                 pad_mode: Optional[str] = None, pad_value=0, ignore_label: Optional[int] = None, tta=None,
+                 calibration_bins: int = 0, temperature: float = 1.0):
         pad_mode, pad_value = check_pad_mode(pad_mode, pad_value)
         self.tta = tta = check_tta(tta, mc_samples)
+        calibration_bins, temperature = check_bins(calibration_bins), check_temperature(temperature)
+        if temperature != 1.0 and (mc_samples or tta):
+            raise ValueError("temperature != 1 with mc_samples or tta: the samples would have to be tempered before they are "
+                             "folded, which is not implemented")
+        if images.dtype != np.uint8 and (calibration_bins or temperature != 1.0):
+            raise ValueError("calibration_bins / temperature need raw uint8 images: the path for other dtypes (host_batches) has "
+                             "no calibration stage")
         n, (H, W), C = images.shape[0], images.shape[1:3], int(num_classes)
         self.ignore_label = ignore_label = check_ignore_label(ignore_label, C)
         self.pool = self.host_ties = None
@@ -382,18 +432,24 @@ class InferenceRun:
             minpath = DeviceMinPath(bs, C - 1, H, W, gsgrad, dev) if self.host_ties is not None else None
             surface = SurfaceDistances(bs, H, W, C, dev, ignore_label=ignore_label) if gt_u8 is not None and surface else None
             confusion = ConfusionCounts(bs, H, W, C, dev, ignore_label=ignore_label) if gt_u8 is not None and confusion else None
-            if surface is None and confusion is None:
-                gt_u8 = None
-            if images.dtype == np.uint8:
+            if images.dtype != np.uint8:
+                if surface is None and confusion is None:
+                    gt_u8 = None
+                self._batches = host_batches(model, images, bs, gt_u8=gt_u8, surface=surface, minpath=minpath,
+                                             confusion=confusion, soft_maps=soft_maps, mc_samples=mc_samples,
+                                             mc_step0=mc_step0, pad_mode=pad_mode, pad_value=pad_value, tta=tta,
+                                             calibration_bins=calibration_bins, temperature=temperature)
+            else:
+                calibration = (CalibrationCounts(bs, H, W, C, dev, calibration_bins, ignore_label=ignore_label)
+                               if gt_u8 is not None and calibration_bins else None)
+                if surface is None and confusion is None and calibration is None:
+                    gt_u8 = None
                 predictor = BatchedPredictor(model._ensure_engine(bs, False, hw=geom), bs, want_maps=True, bg_ilm=True,
                                              bg_csi=False, surface=surface, minpath=minpath, confusion=confusion,
                                              soft_maps=soft_maps, mc_samples=mc_samples, mc_step0=mc_step0,
-                                             hw=(H, W), pad_mode=pad_mode, pad_value=pad_value, tta=tta)
+                                             hw=(H, W), pad_mode=pad_mode, pad_value=pad_value, tta=tta,
+                                             calibration=calibration, temperature=temperature)
                 self._batches = predictor.run(images, gt_u8)
-            else:
-                self._batches = host_batches(model, images, bs, gt_u8=gt_u8, surface=surface, minpath=minpath,
-                                             confusion=confusion, soft_maps=soft_maps, mc_samples=mc_samples,
-                                             mc_step0=mc_step0, pad_mode=pad_mode, pad_value=pad_value, tta=tta)
         except BaseException:
             self.close()
             raise

@@ -482,20 +482,66 @@ class Model:
             yield lo, min(lo + bs, n), eng, eng.infer(xb, pad=None if at is None else (*at, *pad), **kind)
 
     def predict(self, x, verbose=0, batch_size: Optional[int] = None, pad_mode: Optional[str] = None, pad_value=0,
-                **kwargs) -> np.ndarray:
+                temperature: Optional[float] = None, **kwargs) -> np.ndarray:
         """(n,H,W,C) float input ALREADY preprocessed to [0,1] (or raw uint8) -> (n,H,W,num_classes) float32.  The engine
         follows the images' size, whatever the config records.  A size that is no multiple of 2^pool_layers needs
         ``pad_mode`` ("edge", "reflect" or "constant" with ``pad_value``, in the units of ``x``): the batch is padded on
         the device in front of the forward and the output cropped behind it (placement: ``common.utils.padded_geometry``).
-        ``pad_mode=None`` takes the model's ``pad_mode`` / ``pad_value`` attributes, which are None / 0 unless set."""
+        ``pad_mode=None`` takes the model's ``pad_mode`` / ``pad_value`` attributes, which are None / 0 unless set.
+        ``temperature`` (a number in [1/16, 16]; None or 1.0: off): the probabilities are tempered on the device --
+        softmax(logits / temperature), formed from the probabilities themselves (``UNetEngine.temperature_apply``)."""
+        from ..evaluation.calibration import check_temperature
+        temperature = 1.0 if temperature is None else check_temperature(temperature)
         pad = self._pad_options(pad_mode, pad_value)
         x = np.asarray(x)
         if x.dtype != np.uint8:
             x = np.ascontiguousarray(x, dtype=np.float32)   # Keras casts the float64 the reference passes to float32
         out = np.empty(x.shape[:3] + (self.config["num_classes"],), np.float32)
-        for lo, hi, _, maps in self._inference_batches(x, int(batch_size or min(x.shape[0], 32)), pad, want_probs=True, want_argmax=False):
-            out[lo:hi] = maps["probs"].cpu().numpy()
+        for lo, hi, eng, maps in self._inference_batches(x, int(batch_size or min(x.shape[0], 32)), pad, want_probs=True, want_argmax=False):
+            probs = maps["probs"]
+            if temperature != 1.0:
+                eng.temperature_apply(probs, 1.0 / temperature, out=probs)
+            out[lo:hi] = probs.cpu().numpy()
         return out
+
+    def fit_temperature(self, x_u8, labels, batch_size: Optional[int] = None, ignore_label: Optional[int] = None,
+                        pad_mode: Optional[str] = None):
+        """The temperature that minimises the NLL of this model's probabilities on ``x_u8`` (input as for ``predict``) against
+        ``labels`` (n,H,W[,1]), class maps in which ``ignore_label`` (None, or an int in num_classes..255) marks pixels that do
+        not count (temperature scaling, Guo et al. 2017; DESIGN.md section 33).  ``evaluation.calibration.fit_beta`` drives it;
+        each of its steps is one pass over the data -- per batch the forward, then ``UNetEngine.temperature_nll`` on the
+        probabilities, which never leave the device -- and the per-image sums are added on the host in image order.  Returns a
+        record with ``temperature``, ``beta`` = 1 / temperature, ``nll_before`` / ``nll_after`` (mean NLL per counted pixel at
+        temperature 1 and at the result), ``steps``, ``counted`` and ``at_bound`` (the optimum lies outside [1/16, 16]).
+        ``pad_mode`` as for ``predict`` (None: the model's attributes)."""
+        from ..evaluation.calibration import fit_with
+        from ..evaluation.dice_device import check_ignore_label
+        ignore_label = check_ignore_label(ignore_label, self.config["num_classes"])
+        pad = self._pad_options(pad_mode, 0)
+        x = np.asarray(x_u8)
+        if x.dtype != np.uint8:
+            x = np.ascontiguousarray(x, dtype=np.float32)
+        lab = np.asarray(labels)
+        lab = lab[..., 0] if lab.ndim == 4 else lab
+        if lab.shape != x.shape[:3]:
+            raise ValueError(f"labels of shape {np.asarray(labels).shape} for images of shape {x.shape}")
+        C = int(self.config["num_classes"])
+        if ((lab < 0) | ((lab >= C) & (lab != (-1 if ignore_label is None else ignore_label)))).any():
+            raise ValueError(f"labels outside 0..{C - 1}" + ("" if ignore_label is None else f" that are not the ignore label {ignore_label}"))
+        lab = np.ascontiguousarray(lab.astype(np.uint8))
+        bs = int(batch_size or min(x.shape[0], 32))
+
+        def sums_at(beta):
+            tot, n = np.zeros(3), 0.0
+            for lo, hi, eng, maps in self._inference_batches(x, bs, pad, want_probs=True, want_argmax=False):
+                y = torch.from_numpy(lab[lo:hi]).to(eng.device)
+                s, cnt = eng.temperature_nll(maps["probs"], y, [beta], ignore_label)
+                s, cnt = s.cpu().numpy(), cnt.cpu().numpy()
+                for i in range(hi - lo):
+                    tot, n = tot + s[i, 0], n + cnt[i]
+            return tot, n
+
+        return fit_with(sums_at)
 
     def predict_mc(self, x, samples: int, batch_size: Optional[int] = None, step0: int = 0):
         """Monte-Carlo dropout prediction: ``samples`` stochastic forwards per batch with the bottleneck dropout on (dropout

@@ -77,7 +77,8 @@ def predict(predict_params: PredictionParams) -> List[PredictionOutput]:
                       soft_maps=not getattr(predict_params, "binarize", True),
                       mc_samples=mc_samples, mc_step0=getattr(predict_params, "mc_step0", 0),
                       pad_mode=getattr(predict_params, "pad_mode", None),
-                      pad_value=getattr(predict_params, "pad_value", 0), tta=getattr(predict_params, "tta", None)) as run:
+                      pad_value=getattr(predict_params, "pad_value", 0), tta=getattr(predict_params, "tta", None),
+                      temperature=getattr(predict_params, "temperature", 1.0)) as run:
         t0 = time.time()
         for batch in run:
             b0, b1 = lo + batch.lo, lo + batch.hi
@@ -152,6 +153,8 @@ def save_predict_config_file(predict_params: PredictionParams):
     if getattr(predict_params, "pad_mode", None) is not None:
         attrs["pad_mode"] = np.array(str(predict_params.pad_mode), dtype="S1000")      # likewise, with the constant
         attrs["pad_value"] = np.array(float(getattr(predict_params, "pad_value", 0)))
+    if getattr(predict_params, "temperature", 1.0) != 1.0:
+        attrs["temperature"] = np.array(float(predict_params.temperature))      # likewise
     h5io.save(predict_params.config_output_dir / Path("prediction_params.hdf5"), {}, attrs)
 
 
@@ -176,6 +179,8 @@ def save_image_prediction_results(pred_params, predict_image, image_name, predic
             attrs["tta_views"] = np.array(",".join(pred_params.tta), dtype="S1000")
         else:
             attrs["mc_samples"] = np.array(int(getattr(pred_params, "mc_samples", 0)))
+    if getattr(pred_params, "temperature", 1.0) != 1.0:
+        attrs["temperature"] = np.array(float(pred_params.temperature))      # only when set
     h5io.save(output_dir / Path("prediction_info.hdf5"), ds, attrs)
 
 

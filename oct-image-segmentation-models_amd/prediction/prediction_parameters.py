@@ -26,9 +26,18 @@ class PredictionParams:
                  trim_window: tuple = (0, 0), col_error_range: tuple = None, batch_size: int = 32, gs_device: bool = False,
                  gs_device_ties: str = "host", gs_workers: Union[int, None] = None, gs_labels_device: bool = False,
                  binarize: bool = True, png_plots: bool = False, mc_samples: int = 0, mc_step0: int = 0,
-                 pad_mode: Union[str, None] = None, pad_value=0, tta=None) -> None:
+                 pad_mode: Union[str, None] = None, pad_value=0, tta=None, temperature: float = 1.0) -> None:
         if not 0 <= int(mc_samples) <= 64:
             raise ValueError(f"mc_samples must be in 0..64, not {mc_samples}")
+        # extension: temperature scaling.  A number in [1/16, 16], e.g. the one train_model(fit_temperature=True)
+        # wrote into temperature.json: the class probabilities are tempered on the device, softmax(logits / temperature).  There is
+        # no ground truth here, so it changes the binarize=False maps (and what the search makes of them) and nothing else; the
+        # result files record it when set.  Not together with mc_samples or tta.  1.0: nothing is launched, every file as it was
+        from ..evaluation.calibration import check_temperature
+        self.temperature = check_temperature(temperature)
+        if self.temperature != 1.0 and (int(mc_samples) or utils.check_tta(tta, mc_samples)):
+            raise ValueError("temperature != 1 together with mc_samples or tta: the samples would have to be tempered before they "
+                             "are averaged, which is not implemented")
         # extension: test-time augmentation.  1..4 distinct view names out of common.utils.TTA_VIEWS ("identity", "flip_lr",
         # "flip_ud", "flip_both"): every batch is predicted once per view on the mirrored scans and the softmax outputs are
         # mirrored back and averaged on the device; every file describes the mean prediction, and prediction_info.hdf5 gains

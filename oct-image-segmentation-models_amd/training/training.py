@@ -225,6 +225,16 @@ def train_model(training_params: TrainingParams, mlflow_params=None):
 
     history = model.fit(x=train_gen, validation_data=val_gen, epochs=training_params.epochs,
                         callbacks=callbacks_list, verbose=1)
+    if getattr(training_params, "fit_temperature", False):
+        # the temperature of the weights the model now holds, on the validation scans as they are (no augmentation)
+        if rank == 0:
+            from ..evaluation.calibration import TEMPERATURE_FILENAME, write_temperature
+            # (raw uint8 scans go as they are, any other dtype through the model's own preprocessing; compile() above has set
+            # the model's pad_mode / pad_value)
+            x_val = val_images if val_images.dtype == np.uint8 else model_container.get_preprocess_input_fn()(val_images)
+            record = model.fit_temperature(x_val, val_labels, batch_size, ignore_label=ignore_label)
+            write_temperature(save_foldername / Path(TEMPERATURE_FILENAME), record)
+        parallel.barrier()
     return SimpleTrainingResult(model, save_foldername, history, savemodel.saved)
 
 

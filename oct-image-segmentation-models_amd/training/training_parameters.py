@@ -20,7 +20,12 @@ class TrainingParams:
                  class_weight: Union[list, str, None] = None, channels_last: bool = True,
                  early_stopping: bool = True, restore_best_weights: bool = True, patience: int = 50,
                  seed: Union[int, None] = None, aug_device: bool = False, pad_mode: Union[str, None] = None,
-                 pad_value=0, ignore_label: Union[int, None] = None, apply_class_weight: bool = False):
+                 pad_value=0, ignore_label: Union[int, None] = None, apply_class_weight: bool = False,
+                 fit_temperature: bool = False):
+        # extension: after fit returns, rank 0 fits the temperature of the trained model on the un-augmented validation arrays
+        # (Model.fit_temperature, with the ignore_label / pad_mode above) and writes temperature.json into the run folder
+        # (evaluation.calibration.read_temperature reads it).  Off: no such file, nothing launched
+        self.fit_temperature = bool(fit_temperature)
         if (model_architecture is None and initial_model is None) or (
                 model_architecture is not None and initial_model is not None):
             log.error("Either 'model_architecture' or 'initial_model' need to be provided in the `config.json`.")
