@@ -40,6 +40,7 @@
  *                                      flatten_image_boundary        dataset_construction.py is its dataset-preparation kin)
  *   oct_calibration_counts / oct_temperature_apply / oct_temperature_nll  (none: reliability counts, ECE / NLL / Brier and
  *                                      temperature scaling of the softmax output, Guo et al. 2017)
+ *   oct_ordered_decode                 (none: the best class map per column whose class index never decreases with depth)
  */
 #ifndef OCT_UNET_H
 #define OCT_UNET_H
@@ -661,6 +662,39 @@ int oct_temperature_nll(const float* probs_dev, const unsigned char* labels_dev,
                         const float* betas /* host, n_betas values */, int n_betas,
                         double* out_dev /* (B, n_betas, 3) then (B) */, void* ws_dev, size_t ws_bytes, oct_stream_t stream);
 
+/* ---- ordered layer decode on the device (csrc/kernels_ordered.hpp; numpy restatement: common/utils.py::
+ * ordered_decode_reference; the reference has no counterpart: between its arg-max and its result files only the per-boundary
+ * min-path search repairs a column whose classes are out of depth order) ----
+ * probs_dev (B, H, W, n_cls) float32, class index == depth order.  For one column (b, x), rows r = 0..H-1, C = n_cls:
+ *   q        = p > 0 ? min(p, 1) : 0                          (NaN -> 0)
+ *   k[r][c]  = min((uint32) floor(q * 2^20), 2^20 - 1)        (the product is exact; H <= 4096 keeps every sum below 2^32)
+ *   F[r][c]  = k[r][c] + M[r-1][c],   M[-1][c] = 0            (uint32)
+ *   M[r][0]  = F[r][0],  s[r][0] = 1
+ *   M[r][c]  = F[r][c] if F[r][c] > M[r][c-1] (s[r][c] = 1) else M[r][c-1] (s[r][c] = 0)        c = 1..C-1
+ *   back-trace: c = C-1;  for r = H-1 down to 0:  while (c > 0 && !s[r][c]) c--;  label[r] = c
+ *   score    = M[H-1][C-1]
+ *   rows[i]  = number of rows with label <= i,  i = 0..C-2    (the first row of a class > i; H if there is none)
+ * The labelling maximises sum_r k[r][label[r]] over all labellings that never decrease with r -- the expected number of
+ * correctly labelled pixels of the column -- and classes may be skipped (layers of zero thickness).  Among the optima it is the
+ * one that is smallest when compared from the bottom row upward (`>` is strict: a tie goes to the lower class).
+ * labels_out_dev (B,H,W) uint8, rows_out_dev (B, n_cls-1, W) uint16, score_out_dev (B, W) uint32; each may be NULL, not all.
+ * THE LABEL MAP IS AUTHORITATIVE.  rows[i] == 0 says that the column starts below boundary i; consumers of delineations
+ * (oct_area_labels, the renderer, calc_errors) read 0 as "nothing here", so oct_area_labels(rows) reproduces the label map in
+ * the columns where every row is in 1..H-1 (and where a row is H: the classes behind it are absent from the bottom); in a
+ * column with a row of 0 it takes the boundary for missing, fills it from the next one below, and so names the column's top
+ * stretch with a lower class than the label map does.
+ * Stand-alone like oct_calibration_counts: no handle, no allocation, no atomics, ONE launch, asynchronous on `stream`, never
+ * waits, records into a stream capture; repeated calls give identical bytes.  A thread owns one column (under option "ordered_float4", oct_set_option, four adjacent
+ * ones where probs_dev is 16-byte aligned, n_cls <= 8 and W*n_cls % 4 == 0: float4 loads) and walks it twice: down, leaving the
+ * n_cls decision bits of every (row, column) as a uint16 in the caller-owned workspace, and up, reading them back.
+ * Errors (negative, oct_last_error(), nothing launched): null probs or workspace, all three outputs null, B, H or W < 1, n_cls
+ * outside 2..16, H > 4096, B*H*W >= 2^31, a workspace smaller than oct_ordered_workspace_bytes (which returns 0 for a shape the
+ * call refuses) or not 8-byte aligned, misaligned buffers, an output overlapping the input, the workspace or another output. */
+size_t oct_ordered_workspace_bytes(int B, int H, int W, int n_cls);
+int oct_ordered_decode(const float* probs_dev /* (B, H, W, n_cls) f32 */, int B, int H, int W, int n_cls, void* ws_dev, size_t ws_bytes,
+                       unsigned char* labels_out_dev /* (B, H, W) or NULL */, unsigned short* rows_out_dev /* (B, n_cls-1, W) or NULL */,
+                       unsigned int* score_out_dev /* (B, W) or NULL */, oct_stream_t stream);
+
 /* ---- PNG pictures on the device (csrc/kernels_render.hpp; numpy restatement: common/plotting.py::render_reference) ----
  * oct_render_rgba renders B images of H x W into out_dev (B, H, W, 4) uint8 RGBA with A = 255: a base layer, then
  * K >= 0 polylines over it.  Integers only; the restatement and the kernel agree bit for bit.
@@ -776,6 +810,10 @@ int oct_render_rgba(int base_mode, const unsigned char* base_dev, int ic, const 
  *   launch itself (hipExtLaunchKernelGGL stopEvent) rather than a marker recorded behind it.  "dw_fork_group" (1): blocks
  *   whose backward-weights launches share one fork (2-4: fewer waits on the caller's stream, measured slower overall).
  *   "event_sysfence" (0; read at oct_unet_create): 1 = the handle's internal fork/join events carry a system-scope fence.
+ *   "ordered_float4" (0; read by every oct_ordered_decode call): 1 = a thread takes four adjacent columns and loads their
+ *   4 n_cls floats of a row as n_cls float4s, where probs_dev is 16-byte aligned, n_cls <= 8 and W*n_cls % 4 == 0.  Measured
+ *   slower than one column per thread at every shape tried; kept so that the two forms can be tested and
+ *   timed on equal inputs.  The results do not depend on it.
  *   Experiment switches, not for production use: "dwbx_enable" (1; 0 routes the wide backward-weights layers to the
  *   fp32-pipe kernel) and "timing_skip" (0; bit 0 / 1 SKIP the forward / backward BN finalize launches after the second
  *   step -- the results are then WRONG; used once to measure what those launches cost).

@@ -169,6 +169,9 @@ SYMBOLS = [
     ("oct_temperature_workspace_bytes", C.c_size_t, [C.c_int, C.c_size_t, C.c_int, C.c_int]),
     ("oct_temperature_nll", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_int, C.c_int, _P(C.c_float), C.c_int,
                                       C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("oct_ordered_workspace_bytes", C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    ("oct_ordered_decode", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p]),
     ("oct_render_rgba", C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, _P(RenderStyle), C.c_int, C.c_int, C.c_int,
                                   C.c_void_p, C.c_void_p]),
     ("oct_set_option", C.c_int, [C.c_char_p, C.c_int]),

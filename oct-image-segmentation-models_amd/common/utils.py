@@ -330,3 +330,53 @@ def labels_from_delineations(image_shape_t: tuple, segs, num_classes: int) -> Tu
     mask = create_area_mask(image_shape_t, segs)
     labels_t, categorical = perform_argmax(np.expand_dims(to_categorical(mask, num_classes), axis=0))
     return np.transpose(np.squeeze(labels_t)), categorical
+
+
+ORDERED_MIN_CLASSES, ORDERED_MAX_CLASSES, ORDERED_MAX_H = 2, 16, 4096      # what oct_ordered_decode accepts
+ORDERED_ONE = 1 << 20                                                      # its quantisation scale
+
+
+def ordered_decode_reference(probs) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """``oct_ordered_decode`` restated (include/oct_unet.h): class probabilities (B,H,W,C) float32, class index == depth
+    order -> ``(labels (B,H,W) uint8, rows (B,C-1,W) uint16, score (B,W) uint32)``.  Per column, with rows r = 0..H-1:
+
+        q        = p > 0 ? min(p, 1) : 0                          (NaN -> 0)
+        k[r][c]  = min((uint32) floor(q * 2^20), 2^20 - 1)
+        F[r][c]  = k[r][c] + M[r-1][c],   M[-1][c] = 0
+        M[r][0]  = F[r][0],  s[r][0] = 1
+        M[r][c]  = F[r][c] if F[r][c] > M[r][c-1] (s[r][c] = 1) else M[r][c-1] (s[r][c] = 0)
+        back-trace: c = C-1;  for r = H-1 down to 0:  while (c > 0 && !s[r][c]) c--;  label[r] = c
+        score    = M[H-1][C-1]
+        rows[i]  = number of rows with label <= i,  i = 0..C-2
+
+    the labelling that maximises sum_r k[r][label[r]] among those that never decrease with r; of several, the one that is
+    smallest when compared from the bottom row upward.  Integers throughout: the kernel gives the same bits."""
+    p = np.asarray(probs, dtype=np.float32)
+    if p.ndim != 4:
+        raise ValueError(f"ordered_decode_reference: probs must be (B,H,W,C), not {p.shape}")
+    B, H, W, Cn = p.shape
+    if min(B, H, W) < 1 or not ORDERED_MIN_CLASSES <= Cn <= ORDERED_MAX_CLASSES or H > ORDERED_MAX_H or B * H * W >= 1 << 31:
+        raise ValueError(f"ordered_decode_reference: need B, H, W >= 1, H <= {ORDERED_MAX_H}, B*H*W < 2^31 and "
+                         f"{ORDERED_MIN_CLASSES} <= C <= {ORDERED_MAX_CLASSES}, not {p.shape}")
+    with np.errstate(invalid="ignore"):
+        q = np.where(p > 0, np.minimum(p, np.float32(1)), np.float32(0)).astype(np.float32)
+    k = np.minimum(np.floor(q * np.float32(ORDERED_ONE)).astype(np.uint32), np.uint32(ORDERED_ONE - 1))
+    M = np.zeros((B, W, Cn), np.uint32)
+    s = np.zeros((H, B, W, Cn), bool)
+    for r in range(H):
+        F = k[:, r] + M
+        M = np.empty_like(F)
+        M[..., 0], s[r, ..., 0] = F[..., 0], True
+        for c in range(1, Cn):
+            take = F[..., c] > M[..., c - 1]
+            s[r, ..., c] = take
+            M[..., c] = np.where(take, F[..., c], M[..., c - 1])
+    score = M[..., Cn - 1].copy()
+    c = np.full((B, W), Cn - 1, np.int64)
+    labels = np.empty((B, H, W), np.uint8)
+    for r in range(H - 1, -1, -1):
+        for _ in range(Cn - 1):                    # the while loop, for every column at once
+            c = c - ((c > 0) & ~np.take_along_axis(s[r], c[..., None], axis=-1)[..., 0])
+        labels[:, r] = c
+    rows = np.stack([(labels <= i).sum(axis=1) for i in range(Cn - 1)], axis=1).astype(np.uint16)
+    return labels, rows, score

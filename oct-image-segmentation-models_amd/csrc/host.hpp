@@ -65,6 +65,10 @@ struct Options {
                                     // accumulators (raw window extrema; consumers apply BN + ReLU on load) -- no pool_fwd_k pass
     int bx_down2_ring = 1;          // conv_bx_k, stride-2 forms: a resident grid of blocks walks the (image, tile) items and stages the next
                                     // item's first tile under the current item's last tap row (0: one block per item)
+    int ordered_float4 = 0;         // oct_ordered_decode: 1 = four adjacent columns per thread, float4 loads, wherever the alignment
+                                    // conditions hold.  Built, tested -- and measured SLOWER than one column per thread at every shape
+                                    // tried, 16 k to 1 M columns: a column is a serial chain, so the call wants
+                                    // the most waves, not the widest loads: off
     int max_blocks = 0;             // FOR TESTS ("persistent_max_blocks"): > 0 caps the grid of every persistent launch, so that
                                     // small images make blocks walk several tiles (cap_grid below); 0 = the launches' own grids
 };

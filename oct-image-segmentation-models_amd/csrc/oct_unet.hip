@@ -1465,6 +1465,7 @@ const Opt k_opts[] = {
     {"bx_two_blocks", &Options::bx_two_blocks, 0, 1}, {"fork_on_launch", &Options::fork_on_launch, 0, 1},
     {"event_sysfence", &Options::event_sysfence, 0, 1}, {"dw_fork_group", &Options::dw_fork_group, 1, 8}, {"fuse_bn_apply16", &Options::fuse_bn_apply16, 0, 1},
     {"pool_in_epilogue", &Options::pool_in_epilogue, 0, 1}, {"bx_down2_ring", &Options::bx_down2_ring, 0, 1},
+    {"ordered_float4", &Options::ordered_float4, 0, 1},
 };
 const Opt* find_opt(const char* name) {
     for (const Opt& o : k_opts) if (!strcmp(name, o.name)) return &o;

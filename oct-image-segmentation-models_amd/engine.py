@@ -618,6 +618,33 @@ class UNetEngine:
                   out.data_ptr(), ws.data_ptr(), ws.numel(), self._stream())
         return out[:B * K * 3].view(B, K, 3), out[B * K * 3:]
 
+    # ---- ordered layer decode: the best class map per column that never decreases with depth ----------
+    def ordered_decode(self, probs: torch.Tensor, *, labels=None, rows=None, score=None, ws=None):
+        """The ordered decode of class probabilities ``probs`` (B,H,W,C) float32, C in 2..16, H <= 4096, class index == depth
+        order (``oct_ordered_decode``; ``common.utils.ordered_decode_reference`` gives the same bits): returns ``(labels
+        (B,H,W) uint8, rows (B,C-1,W) int16 -- the bits are uint16 --, score (B,W) int32 -- the bits are uint32)`` on the
+        device.  ``labels`` / ``rows`` / ``score`` / ``ws`` (uint8, ``oct_ordered_workspace_bytes``): optional tensors to use.
+        ``probs`` may be a view ``[:n]`` of a larger buffer.  Asynchronous on the current stream."""
+        if probs.dim() != 4:
+            raise OctError(f"ordered_decode: probs must be (B,H,W,C), not {tuple(probs.shape)}")
+        _hip.expect(probs, "ordered_decode: probs (B,H,W,C)", device=self.device, dtype=torch.float32, shape=(None,) * 4)
+        B, H, W, Cn = probs.shape
+        nbytes = int(_hip.lib().oct_ordered_workspace_bytes(B, H, W, Cn))
+        if not nbytes:
+            raise OctError(f"ordered_decode: unsupported shape {tuple(probs.shape)}: need H <= 4096, B*H*W < 2^31 and 2..16 classes")
+        if ws is None:
+            ws = torch.empty((nbytes,), dtype=torch.uint8, device=self.device)
+        _hip.expect(ws, "ordered_decode: workspace", device=self.device, dtype=torch.uint8, shape=(None,))
+        labels = torch.empty((B, H, W), dtype=torch.uint8, device=self.device) if labels is None else labels
+        rows = torch.empty((B, Cn - 1, W), dtype=torch.int16, device=self.device) if rows is None else rows
+        score = torch.empty((B, W), dtype=torch.int32, device=self.device) if score is None else score
+        _hip.expect(labels, "ordered_decode: labels", device=self.device, dtype=torch.uint8, shape=(B, H, W))
+        _hip.expect(rows, "ordered_decode: rows", device=self.device, dtype=torch.int16, shape=(B, Cn - 1, W))
+        _hip.expect(score, "ordered_decode: score", device=self.device, dtype=torch.int32, shape=(B, W))
+        _hip.call("oct_ordered_decode", self.device, probs.data_ptr(), B, H, W, Cn, ws.data_ptr(), ws.numel(), labels.data_ptr(),
+                  rows.data_ptr(), score.data_ptr(), self._stream())
+        return labels, rows, score
+
     # ---- test-time augmentation: flipped views averaged on the device ---------------------------------
     def flip(self, t: torch.Tensor, view, out=None) -> torch.Tensor:
         """(B,H,W[,C]) uint8 or float32 -> the same shape mirrored by ``view`` -- a name of ``common.utils.TTA_VIEWS`` or its

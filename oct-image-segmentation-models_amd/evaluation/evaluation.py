@@ -35,12 +35,14 @@ from ..models import get_model_class
 from .calibration import CALIBRATION_METRICS, calibration_from_counts, counts_as_float, pooled_calibration
 from .dice_device import DICE_METRICS, MAX_EXACT_PIXELS, dice_from_counts
 from .evaluation_parameters import EvaluationParameters
+from .ordered import layer_thickness
 from .pipeline import InferenceRun
-from .render import EVALUATION_PNG_NAMES, write_pictures
+from .render import EVALUATION_PNG_NAMES, OD_PNG_NAMES, write_pictures
 from .surface import datasets as surface_datasets
 
 EVALUATION_RESULTS_FILENAME = "evaluation_results.hdf5"
 GS_EVALUATION_RESULTS_FILENAME = "gs_evaluation_results.hdf5"
+OD_EVALUATION_RESULTS_FILENAME = "od_evaluation_results.hdf5"
 OVERALL_EVALUATION_RESULTS_FILENAME_HDF5 = "overall_evaluation_results.hdf5"
 OVERALL_EVALUATION_RESULTS_FILENAME_CSV = "overall_evaluation_results.csv"
 
@@ -173,6 +175,8 @@ def evaluate_model(eval_params: EvaluationParameters) -> List[EvaluationOutput]:
         metrics_device = False
     # calibration_bins / temperature: reliability counts of the (tempered) probabilities on the device
     calibration_bins, temperature = getattr(eval_params, "calibration_bins", 0), getattr(eval_params, "temperature", 1.0)
+    # ordered_decode: the topology-correct class maps of the probabilities, decoded on the device
+    ordered_decode = bool(getattr(eval_params, "ordered_decode", False))
     need_gt = want_surface or (metrics_device and want_dice) or calibration_bins > 0
     gt_maps = np.squeeze(eval_labels[lo:hi], axis=3) if need_gt else None
     # BASELINE configs[4] path (evaluation/pipeline.py::InferenceRun): search mode, batch source and worker pools
@@ -185,11 +189,18 @@ def evaluate_model(eval_params: EvaluationParameters) -> List[EvaluationOutput]:
                       soft_maps=not getattr(eval_params, "binarize", True),
                       pad_mode=getattr(eval_params, "pad_mode", None), pad_value=getattr(eval_params, "pad_value", 0),
                       ignore_label=ignore_label, tta=getattr(eval_params, "tta", None),
-                      calibration_bins=calibration_bins, temperature=temperature) as run:
+                      calibration_bins=calibration_bins, temperature=temperature,
+                      **({"ordered_decode": True} if ordered_decode else {})) as run:
         t_prev = time.time()
         for batch in run:
             b0, b1 = lo + batch.lo, lo + batch.hi
             predict_time = (time.time() - t_prev) / (b1 - b0)
+            od_counts = od_pictures = None
+            if ordered_decode:
+                if metrics_device and want_dice:
+                    od_counts = run.ordered_counts(batch, gt_maps[batch.lo:batch.hi])
+                if png_plots:
+                    od_pictures = run.render_ordered(batch, eval_images[b0:b1])
             gs_found = run.graph_search(batch, eval_segments[b0:b1])
             gs_labels = gs_counts = None
             if metrics_device and eval_params.graph_search:
@@ -251,6 +262,19 @@ def evaluate_model(eval_params: EvaluationParameters) -> List[EvaluationOutput]:
                     _save_graph_based_evaluation_results(eval_params, eval_image_name, gs_eval_label, gs_pred_segs, gs_dc,
                                                          gs_dm, gs_dmi, errors, mean_abs_err, mean_err, abs_err_sd, err_sd,
                                                          graph_time, eval_image_output_dir)
+                if ordered_decode:
+                    od_labels, od_rows = batch.ordered[0][ind - b0], batch.ordered[1][ind - b0]
+                    if od_counts is not None:
+                        od_dice = dice_from_counts(od_counts[ind - b0], eval_params.metrics)
+                    else:
+                        od_cat = common_utils.labels_to_categorical(od_labels[None].astype(np.int64), num_classes)
+                        od_dice = _dice_metrics(eval_params.metrics, num_classes, eval_label,
+                                                od_cat if keep is None else od_cat * keep.astype(np.float32))
+                    _save_ordered_evaluation_results(eval_params, eval_image_name, od_labels, od_rows, od_dice,
+                                                     graph_search.calc_errors(od_rows, eval_seg),
+                                                     int(np.count_nonzero(od_labels != predicted_labels)), eval_image_output_dir)
+                    if od_pictures is not None:
+                        write_pictures(eval_image_output_dir, od_pictures, ind - b0, OD_PNG_NAMES)
                 if pictures is not None:
                     write_pictures(eval_image_output_dir, pictures, ind - b0, EVALUATION_PNG_NAMES)
                 eval_outputs.append(EvaluationOutput(
@@ -322,6 +346,30 @@ def _save_graph_based_evaluation_results(eval_params, image_name, gs_eval_label,
     h5io.save(output_dir / Path(GS_EVALUATION_RESULTS_FILENAME), ds, attrs)
 
 
+def _save_ordered_evaluation_results(eval_params, image_name, od_labels, od_rows, dice, errors, changed_pixels, output_dir):
+    """The ordered decode's files of one image: ``od_labels`` (H,W) uint8 and ``od_rows`` (C-1,W) uint16 of
+    ``Batch.ordered``, ``dice`` = (classes, macro, micro) as for the arg-max map, ``errors`` = ``calc_errors(od_rows, truth)``,
+    ``changed_pixels`` the pixels where the ordered map differs from the arg-max."""
+    np.savetxt(output_dir / Path("od_boundaries.csv"), od_rows, delimiter=",", fmt="%d")
+    np.savetxt(output_dir / Path("od_predicted_segmentation_map.csv"), od_labels, fmt="%d", delimiter=",")
+    mean_abs_err, mean_err, abs_err_sd, err_sd = graph_search.calculate_overall_errors(errors)
+    ds = {"od_pred_segs": od_rows.astype("uint16"), "od_predicted_labels": od_labels.astype("uint8"),
+          "errors": errors.astype("float64"), "mean_abs_err": mean_abs_err.astype("float64"),
+          "mean_err": mean_err.astype("float64"), "abs_err_sd": abs_err_sd.astype("float64"), "err_sd": err_sd.astype("float64"),
+          "changed_pixels": np.array([changed_pixels], dtype="int64")}
+    dice_classes, dice_macro, dice_micro = dice
+    if dice_classes is not None:
+        ds[EVALUATION_METRIC_DICE_CLASSES] = np.squeeze(dice_classes).astype("float64")
+    if dice_macro is not None:
+        ds[EVALUATION_METRIC_DICE_MACRO] = np.expand_dims(dice_macro, axis=0).astype("float64")
+    if dice_micro is not None:
+        ds[EVALUATION_METRIC_DICE_MICRO] = np.expand_dims(dice_micro, axis=0).astype("float64")
+    thickness, mean_thickness = layer_thickness(od_rows)
+    if thickness is not None:
+        ds["layer_thickness"], ds["mean_layer_thickness"] = thickness, mean_thickness
+    h5io.save(output_dir / Path(OD_EVALUATION_RESULTS_FILENAME), ds, common_utils.result_attrs(eval_params.model_path, image_name))
+
+
 def save_eval_config_file(eval_params: EvaluationParameters):
     p = eval_params.test_dataset_path
     md5_path = p if Path(p).exists() else Path(str(p) + ".npz")
@@ -345,6 +393,8 @@ def save_eval_config_file(eval_params: EvaluationParameters):
         attrs["calibration_bins"] = np.array(int(eval_params.calibration_bins))      # likewise
     if getattr(eval_params, "temperature", 1.0) != 1.0:
         attrs["temperature"] = np.array(float(eval_params.temperature))      # likewise
+    if getattr(eval_params, "ordered_decode", False):
+        attrs["ordered_decode"] = np.array(True)      # likewise
     h5io.save(eval_params.save_foldername / Path("eval_params.hdf5"), {}, attrs)
 
 
@@ -417,6 +467,31 @@ def _calc_overall_dataset_errors(eval_params: EvaluationParameters, eval_image_n
                            ("Median absolute errors", "median_abs_errors"), ("SD abs errors", "sd_abs_errors"),
                            ("SD errors", "sd_errors")):
             lines.append(f"{title}," + ",".join(f"{e:.7f}" for e in out[key]))
+    if getattr(eval_params, "ordered_decode", False):
+        # the ordered decode: the aggregates the graph search gets above, under od_ names, behind everything that was there
+        od_files = [h5io.load(d / Path(OD_EVALUATION_RESULTS_FILENAME)) for d in dir_list]
+        for m in (EVALUATION_METRIC_DICE_CLASSES, EVALUATION_METRIC_DICE_MACRO, EVALUATION_METRIC_DICE_MICRO):
+            if m in metrics:
+                save_metric(f"od_{m}", stack(od_files, m))
+        errors = stack(od_files, "errors")
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", category=RuntimeWarning)
+            abs_samples, samples = np.nanmean(np.abs(errors), axis=2), np.nanmean(errors, axis=2)
+            out.update({
+                "od_mean_abs_errors_cols": np.nanmean(np.abs(errors), axis=0), "od_mean_abs_errors_samples": abs_samples,
+                "od_mean_abs_errors": np.nanmean(abs_samples, axis=0), "od_sd_abs_errors": np.nanstd(abs_samples, axis=0),
+                "od_median_abs_errors": np.nanmedian(abs_samples, axis=0),
+                "od_sd_abs_errors_samples": np.nanstd(np.abs(errors), axis=2),
+                "od_mean_errors_cols": np.nanmean(errors, axis=0), "od_mean_errors_samples": samples,
+                "od_mean_errors": np.nanmean(samples, axis=0), "od_sd_errors": np.nanstd(samples, axis=0),
+                "od_median_errors": np.nanmedian(samples, axis=0), "od_errors": errors})
+        for title, key in (("OD mean abs errors", "od_mean_abs_errors"), ("OD mean errors", "od_mean_errors"),
+                           ("OD median absolute errors", "od_median_abs_errors"), ("OD SD abs errors", "od_sd_abs_errors"),
+                           ("OD SD errors", "od_sd_errors")):
+            lines.append(f"{title}," + ",".join(f"{e:.7f}" for e in out[key]))
+        save_metric("od_changed_pixels", stack(od_files, "changed_pixels"))
+        if od_files and "mean_layer_thickness" in od_files[0]:
+            save_metric("od_mean_layer_thickness", stack(od_files, "mean_layer_thickness"))
     h5io.save(output_dir / Path(OVERALL_EVALUATION_RESULTS_FILENAME_HDF5), out)
     with open(output_dir / Path(OVERALL_EVALUATION_RESULTS_FILENAME_CSV), "w") as f:
         f.write("\n".join(lines) + "\n")

@@ -28,7 +28,14 @@ class EvaluationParameters:
                  bg_ilm: bool = True, bg_csi: bool = False, batch_size: int = 32, gs_device: bool = False,
                  gs_device_ties: str = "host", gs_workers: Optional[int] = None, metrics_device: bool = False,
                  png_plots: bool = False, pad_mode: Optional[str] = None, pad_value=0, ignore_label: Optional[int] = None,
-                 tta=None, calibration_bins: int = 0, temperature: float = 1.0):
+                 tta=None, calibration_bins: int = 0, temperature: float = 1.0, ordered_decode: bool = False):
+        # extension: the ordered layer decode.  Per column the best class map whose class index never
+        # decreases with depth, decoded on the device from the class probabilities (the mean ones with tta, the tempered ones with
+        # temperature).  Every image gains od_evaluation_results.hdf5 (od_pred_segs, od_predicted_labels, errors and their four
+        # statistics, the Dice metrics asked for, layer_thickness, mean_layer_thickness, changed_pixels), od_boundaries.csv and
+        # od_predicted_segmentation_map.csv, the overall results the od_ aggregates; with png_plots two pictures.  Needs 2..16
+        # classes (checked once the model is loaded).  False: nothing is launched, no file changes
+        self.ordered_decode = bool(ordered_decode)
         # extension: calibration of the class probabilities.  calibration_bins, an int in 0..64: with
         # M > 0 the reliability counts of the probabilities against the ground truth are made on the device in M confidence
         # bins; each image's results gain calibration_counts (M, 3) = [n, correct, sum of confidences], ece, mce, nll and brier,
@@ -95,6 +102,9 @@ class EvaluationParameters:
             self.model_path, mlflow_tracking_uri=mlflow_tracking_uri, mlflow_run_uuid=mlflow_run_uuid)
         self.num_classes = self.loaded_model.output.shape[-1]
         plotting.check_png_classes(self.png_plots, self.num_classes)     # pictures exist up to 9 classes: refused here, up front
+        if self.ordered_decode:
+            from .ordered import check_ordered
+            check_ordered(self.num_classes, 1)
         # extension: the test set's labels are known in part only (annotated column ranges, masked optic-nerve heads): ground-truth
         # pixels of this value, an int in num_classes..255, are "unknown" wherever a metric, a truth boundary or a ground-truth
         # picture is formed -- out of the Dice counts, no surface element at their rim, no truth boundary underneath them,

@@ -20,6 +20,7 @@ from ..min_path_processing.device_search import DeviceMinPath, LazyPool, merge_t
 from ..min_path_processing.pool import SegmentPool, default_workers
 from .calibration import CalibrationCounts, check_bins, check_temperature
 from .dice_device import ConfusionCounts, DelineationLabels, check_ignore_label
+from .ordered import OrderedDecode, check_ordered
 from .render import PngRenderer, batch_pictures
 from .surface import SurfaceDistances
 
@@ -45,18 +46,27 @@ class Batch(NamedTuple):
     # (counts (n, M, 3) uint64 = [pixels, correct, sum of floor(conf 2^28)], sums (n, 4) float64 = [sum nll, sum brier, counted,
     # 0]) -- evaluation/calibration.py.  An ATTRIBUTE for the same reason, None on every other record.
     calibration = None
+    # Runs with the ordered decode carry its result for the batch's (mean, tempered, cropped) class probabilities: (labels
+    # (n, H, W) uint8, rows (n, C-1, W) uint16, score (n, W) uint32) -- evaluation/ordered.py.  An ATTRIBUTE likewise.
+    ordered = None
+
+    def _with(self, **attrs) -> "Batch":
+        b = _UncertainBatch(*self)
+        for k in ("entropy", "mutual_info", "calibration", "ordered"):
+            setattr(b, k, attrs.get(k, getattr(self, k)))
+        return b
 
     def with_uncertainty(self, entropy: np.ndarray, mutual_info: np.ndarray) -> "Batch":
         """This record with ``entropy`` / ``mutual_info`` set."""
-        b = _UncertainBatch(*self)
-        b.entropy, b.mutual_info, b.calibration = entropy, mutual_info, self.calibration
-        return b
+        return self._with(entropy=entropy, mutual_info=mutual_info)
 
     def with_calibration(self, calibration) -> "Batch":
         """This record with ``calibration`` set."""
-        b = _UncertainBatch(*self)
-        b.entropy, b.mutual_info, b.calibration = self.entropy, self.mutual_info, calibration
-        return b
+        return self._with(calibration=calibration)
+
+    def with_ordered(self, ordered) -> "Batch":
+        """This record with ``ordered`` set."""
+        return self._with(ordered=ordered)
 
 
 class _UncertainBatch(Batch):
@@ -67,25 +77,31 @@ class _Stage(NamedTuple):
     """One per-batch device post-process: the ``Batch`` field it fills, the wrapper that runs it -- ``run(*inputs, *outs)``
     queues it on the current stream, ``run.outs`` are its own output buffers for a full batch, ``run.to_host`` turns
     output rows into the field's value -- and what it reads: the boundary maps, or else the ground truth with the arg-max
-    maps or (``on_probs``) with the class probabilities."""
+    maps or (``on_probs``) with the class probabilities, or (``on_probs`` without ``needs_gt``) the class probabilities alone."""
     field: str
     run: object
     on_maps: bool
     on_probs: bool = False
+    needs_gt: bool = True             # (a stage on the boundary maps never reads the ground truth, whatever this says)
+
+    @property
+    def reads_gt(self) -> bool:
+        return self.needs_gt and not self.on_maps
 
     def launch(self, n: int, outs, labels, gt, maps, probs=None) -> None:
-        inputs = (maps[:n],) if self.on_maps else (probs[:n], gt[:n]) if self.on_probs else (labels[:n], gt[:n])
+        inputs = (maps[:n],) if self.on_maps else (probs[:n] if self.on_probs else labels[:n],) + ((gt[:n],) if self.needs_gt else ())
         self.run(*inputs, *(t[:n] for t in outs))
 
     def to_host(self, n: int, outs, first_image: int):
         return self.run.to_host(*(t[:n] for t in outs), first_image=first_image)
 
 
-def _stages(surface, confusion, minpath, have_gt: bool = True, calibration=None) -> list:
+def _stages(surface, confusion, minpath, have_gt: bool = True, calibration=None, ordered=None) -> list:
     """The stages to run, in their order on the stream; those that read the ground truth only when there is one."""
     every = (_Stage("surface", surface, False), _Stage("confusion", confusion, False),
-             _Stage("calibration", calibration, False, True), _Stage("minpath", minpath, True))
-    return [st for st in every if st.run is not None and (st.on_maps or have_gt)]
+             _Stage("calibration", calibration, False, True), _Stage("ordered", ordered, False, True, False),
+             _Stage("minpath", minpath, True))
+    return [st for st in every if st.run is not None and (have_gt or not st.reads_gt)]
 
 
 class BatchedPredictor:
@@ -135,11 +151,18 @@ class BatchedPredictor:
     runs on the (cropped; with ``mc_samples`` / ``tta`` the MEAN) probabilities, and ``Batch.calibration`` holds ``(counts,
     sums)``.  With ``temperature`` != 1 ``oct_temperature_apply`` tempers the probabilities in place behind the chain, in
     front of the soft maps and the counts; the arg-max maps do not depend on it.  It is refused together with ``mc_samples`` or
-    ``tta``: the samples would have to be tempered before the fold.  With ``temperature`` == 1.0 nothing is launched."""
+    ``tta``: the samples would have to be tempered before the fold.  With ``temperature`` == 1.0 nothing is launched.
+
+    With ``ordered`` (an ``evaluation.ordered.OrderedDecode`` for this batch and shape) the chain is asked for the class
+    probabilities in the same way and ``oct_ordered_decode`` runs on them -- cropped; with ``mc_samples`` / ``tta`` the MEAN;
+    with a ``temperature`` the TEMPERED ones, behind ``oct_temperature_apply``: the decode weighs rows against each other and is
+    not invariant to the temperature as the arg-max is.  It reads no ground truth, and ``Batch.ordered`` holds ``(labels,
+    rows, score)``.  It depends on none of ``soft_maps``, ``minpath``, ``confusion``; without it nothing is launched."""
 
     def __init__(self, engine, batch: int, want_maps: bool = True, bg_ilm: bool = True, bg_csi: bool = False,
                  surface=None, minpath=None, confusion=None, soft_maps: bool = False, mc_samples: int = 0, mc_step0: int = 0,
-                 hw=None, pad_mode: Optional[str] = None, pad_value=0, tta=None, calibration=None, temperature: float = 1.0):
+                 hw=None, pad_mode: Optional[str] = None, pad_value=0, tta=None, calibration=None, temperature: float = 1.0,
+                 ordered=None):
         self.temperature = check_temperature(temperature)
         if self.temperature != 1.0 and (mc_samples or tta):
             raise ValueError("temperature != 1 with mc_samples or tta: the samples would have to be tempered before they are "
@@ -171,9 +194,9 @@ class BatchedPredictor:
         self.map_pin = [torch.empty((self.B, C - 1, H, W), dtype=torch.uint8).pin_memory() for _ in range(2)] if want_maps else None
         self.lab_dev = [torch.empty((self.B, H, W), dtype=torch.uint8, device=dev) for _ in range(2)]
         self.map_dev = [torch.empty((self.B, C - 1, H, W), dtype=torch.uint8, device=dev) for _ in range(2)] if want_maps else None
-        self.wrappers, self.calibration = (surface, confusion, minpath), calibration
+        self.wrappers, self.calibration, self.ordered = (surface, confusion, minpath), calibration, ordered
         self.out_dev, self.out_pin = {}, {}                 # per stage field: device and pinned double buffers
-        every = _stages(*self.wrappers, calibration=calibration)
+        every = _stages(*self.wrappers, calibration=calibration, ordered=ordered)
         for st in every:
             if st.on_maps and not want_maps:
                 raise ValueError(f"{st.field}: needs want_maps=True")
@@ -182,8 +205,8 @@ class BatchedPredictor:
             self.out_dev[st.field] = [tuple(torch.empty_like(t) for t in st.run.outs) for _ in range(2)]
             self.out_pin[st.field] = [tuple(torch.empty(t.shape, dtype=t.dtype).pin_memory() for t in st.run.outs) for _ in range(2)]
         self.gt_pin = self.gt_dev = (None, None)
-        if not all(st.on_maps for st in every):
-            self.gt_pin = [torch.empty((self.B, H, W), dtype=torch.uint8).pin_memory() for _ in range(2)]
+        if any(st.reads_gt for st in every):
+            self.gt_pin =[torch.empty((self.B, H, W), dtype=torch.uint8).pin_memory() for _ in range(2)]
             self.gt_dev = [torch.empty((self.B, H, W), dtype=torch.uint8, device=dev) for _ in range(2)]
         self.copy_in = torch.cuda.Stream(device=dev)
         self.copy_out = torch.cuda.Stream(device=dev)
@@ -195,7 +218,8 @@ class BatchedPredictor:
         pad = None if self.at is None else (*self.at, self.pad_mode, self.pad_value)
         self._infer = lambda capture: engine.infer(self.x_dev, mc=(self.mc_samples, self.mc_step0) if self.mc_samples else None,
                                                    tta=self.tta or None, pad=pad, want_argmax=True,
-                                                   want_probs=self.soft_maps or calibration is not None or self.temperature != 1.0,
+                                                   want_probs=(self.soft_maps or calibration is not None or ordered is not None
+                                                               or self.temperature != 1.0),
                                                    capture=capture)
         self.out = self._infer(not self.mc_samples)         # the maps every batch refills (engine-owned buffers)
         self.am, self.probs = self.out["argmax"], self.out.get("mean_probs", self.out.get("probs"))
@@ -205,9 +229,9 @@ class BatchedPredictor:
         if images_u8.dtype != np.uint8:
             raise TypeError("the batched pipeline takes raw uint8 images (the /255 happens on the device)")
         have_gt = gt_u8 is not None
-        stages = _stages(*self.wrappers, have_gt=have_gt, calibration=self.calibration)
+        stages = _stages(*self.wrappers, have_gt=have_gt, calibration=self.calibration, ordered=self.ordered)
         if have_gt:
-            if all(st.on_maps for st in stages):
+            if not any(st.reads_gt for st in stages):
                 raise ValueError("ground-truth maps given to a BatchedPredictor built without surface=, confusion= or calibration=")
             gt_u8 = np.ascontiguousarray(gt_u8)
             if gt_u8.dtype != np.uint8 or gt_u8.shape != images_u8.shape[:3]:
@@ -302,10 +326,12 @@ class BatchedPredictor:
         labels = self.lab_pin[s][:hi - lo].numpy().copy()
         maps = self.map_pin[s][:hi - lo].numpy().copy() if self.want_maps else None
         fields = {st.field: st.to_host(hi - lo, self.out_pin[st.field][s], lo) for st in stages}
-        calibration = fields.pop("calibration", None)
+        calibration, ordered = fields.pop("calibration", None), fields.pop("ordered", None)
         batch = Batch(lo, hi, labels, maps, **fields)
         if calibration is not None:
             batch = batch.with_calibration(calibration)
+        if ordered is not None:
+            batch = batch.with_ordered(ordered)
         if self.unc_pin is not None:
             batch = batch.with_uncertainty(*(t[:hi - lo].numpy().copy() for t in self.unc_pin[s]))
         return batch
@@ -314,12 +340,14 @@ class BatchedPredictor:
 def host_batches(model, images: np.ndarray, batch: int, *, gt_u8: Optional[np.ndarray] = None, surface=None,
                  minpath=None, confusion=None, soft_maps: bool = False, mc_samples: int = 0, mc_step0: int = 0,
                  pad_mode: Optional[str] = None, pad_value=0, tta=None, calibration_bins: int = 0,
-                 temperature: float = 1.0) -> Iterator[Batch]:
+                 temperature: float = 1.0, ordered=None) -> Iterator[Batch]:
     """The same records for images that are not uint8: x / 255 on the host (``Model.predict_labels``), one synchronous
     forward per batch, no overlap.  ``surface`` / ``minpath`` / ``confusion`` / ``soft_maps`` / ``mc_samples`` /
     ``mc_step0`` / ``tta`` as in ``BatchedPredictor``; each stage writes its own output buffers.  ``pad_mode`` / ``pad_value`` (in raw
     counts) go to ``Model.predict_labels``, which pads and crops on the device.  ``calibration_bins`` / ``temperature``: refused
-    here -- calibration exists for raw uint8 images only."""
+    here -- calibration exists for raw uint8 images only.  ``ordered`` (anything true, an ``OrderedDecode`` included):
+    ``Model.predict_labels`` runs the ordered decode on the batch's probabilities while they are on the device, and
+    ``Batch.ordered`` is filled as by ``BatchedPredictor``."""
     if check_bins(calibration_bins) or check_temperature(temperature) != 1.0:
         raise ValueError("calibration_bins / temperature need raw uint8 images: the path for other dtypes (host_batches) has no "
                          "calibration stage")
@@ -331,11 +359,13 @@ def host_batches(model, images: np.ndarray, batch: int, *, gt_u8: Optional[np.nd
     def upload(a):
         return torch.from_numpy(np.ascontiguousarray(a)).to(stages[0].run.device)
 
+    more = {"ordered": True} if ordered else {}             # (the keyword is only passed when set)
     for lo in range(0, images.shape[0], batch):
         hi = min(lo + batch, images.shape[0])
         labels, maps, *unc = model.predict_labels(images[lo:hi], batch_size=batch, want_maps=True, bg_ilm=True, bg_csi=False,
                                                   soft_maps=soft_maps, mc_samples=mc_samples, mc_step0=mc_step0,
-                                                  pad_mode=pad_mode, pad_value=pad_value, tta=tta)
+                                                  pad_mode=pad_mode, pad_value=pad_value, tta=tta, **more)
+        decoded = unc.pop() if ordered else None
         lab_dev, gt_dev = (upload(labels.astype(np.uint8)), upload(gt_u8[lo:hi])) if on_labels else (None, None)
         maps_dev = upload(maps) if on_maps else None
         fields = {}
@@ -343,6 +373,8 @@ def host_batches(model, images: np.ndarray, batch: int, *, gt_u8: Optional[np.nd
             st.launch(hi - lo, st.run.outs, lab_dev, gt_dev, maps_dev)
             fields[st.field] = st.to_host(hi - lo, st.run.outs, lo)
         record = Batch(lo, hi, labels, maps, **fields)
+        if decoded is not None:
+            record = record.with_ordered(decoded)
         yield record.with_uncertainty(*unc) if unc else record
 
 
@@ -384,6 +416,11 @@ class InferenceRun:
     soft maps and the counts; with ``mc_samples`` or ``tta`` it is refused.  Both need raw uint8 images: for another dtype
     either keyword is a ``ValueError``.
 
+    ``ordered_decode``: an ``OrderedDecode`` stage fills ``Batch.ordered`` from the class probabilities -- the mean ones under
+    ``mc_samples`` / ``tta``, the tempered ones under ``temperature``, the cropped ones under ``pad_mode``.
+    It needs 2..16 classes and a height of at most 4096, works for every image dtype and without ``gt``, and does not depend on
+    ``soft_maps``, ``gs_device`` or ``confusion``.
+
     ``batches`` replaces the model by a ready source of records (tests of the host side: no device is touched)."""
 
     def __init__(self, model, images: np.ndarray, batch: int, num_classes: int, *, gt: Optional[np.ndarray] = None,
@@ -391,9 +428,11 @@ class InferenceRun:
                  gs_workers: Optional[int] = None, batches: Optional[Iterable[Batch]] = None, surface: bool = True,
                  confusion: bool = False, soft_maps: bool = False, mc_samples: int = 0, mc_step0: int = 0,
                  pad_mode: Optional[str] = None, pad_value=0, ignore_label: Optional[int] = None, tta=None,
-                 calibration_bins: int = 0, temperature: float = 1.0):
+                 calibration_bins: int = 0, temperature: float = 1.0, ordered_decode: bool = False):
         pad_mode, pad_value = check_pad_mode(pad_mode, pad_value)
         self.tta = tta = check_tta(tta, mc_samples)
+        if ordered_decode:
+            check_ordered(num_classes, images.shape[1])
         calibration_bins, temperature = check_bins(calibration_bins), check_temperature(temperature)
         if temperature != 1.0 and (mc_samples or tta):
             raise ValueError("temperature != 1 with mc_samples or tta: the samples would have to be tempered before they are "
@@ -438,8 +477,10 @@ class InferenceRun:
                 self._batches = host_batches(model, images, bs, gt_u8=gt_u8, surface=surface, minpath=minpath,
                                              confusion=confusion, soft_maps=soft_maps, mc_samples=mc_samples,
                                              mc_step0=mc_step0, pad_mode=pad_mode, pad_value=pad_value, tta=tta,
-                                             calibration_bins=calibration_bins, temperature=temperature)
+                                             calibration_bins=calibration_bins, temperature=temperature,
+                                             **({"ordered": True} if ordered_decode else {}))
             else:
+                ordered = OrderedDecode(bs, H, W, C, dev) if ordered_decode else None
                 calibration = (CalibrationCounts(bs, H, W, C, dev, calibration_bins, ignore_label=ignore_label)
                                if gt_u8 is not None and calibration_bins else None)
                 if surface is None and confusion is None and calibration is None:
@@ -448,7 +489,8 @@ class InferenceRun:
                                              bg_csi=False, surface=surface, minpath=minpath, confusion=confusion,
                                              soft_maps=soft_maps, mc_samples=mc_samples, mc_step0=mc_step0,
                                              hw=(H, W), pad_mode=pad_mode, pad_value=pad_value, tta=tta,
-                                             calibration=calibration, temperature=temperature)
+                                             calibration=calibration, temperature=temperature,
+                                             **({"ordered": ordered} if ordered is not None else {}))
                 self._batches = predictor.run(images, gt_u8)
         except BaseException:
             self.close()
@@ -516,6 +558,31 @@ class InferenceRun:
                               truths=truths, gs_segs=gs_segs, gs_labels=gs_labels,
                               both_overlay=truths is not None and gs_segs is not None, col_range=col_range,
                               ignore_label=ignore_label)
+
+    def ordered_counts(self, batch: Batch, gt: np.ndarray) -> np.ndarray:
+        """The (n, C, C) uint32 confusion counts of the batch's ordered class maps (``Batch.ordered``) against its ground-truth
+        class maps ``gt`` (n,H,W), by the kernel of ``gs_labels`` and with the run's ``ignore_label``.  Both are uploaded here,
+        into buffers of this method.  Waits for the device."""
+        if self._gs_geom is None:
+            raise RuntimeError("ordered_counts needs the device: this run was built over injected batches")
+        counts, dev = self._delineation_labels().counts, self._gs_geom[4]
+        pred = torch.from_numpy(np.ascontiguousarray(batch.ordered[0])).to(dev)
+        gt_dev = torch.from_numpy(np.ascontiguousarray(gt, dtype=np.uint8)).to(dev)
+        return counts.to_host(counts(pred, gt_dev), batch.lo)
+
+    def render_ordered(self, batch: Batch, images: np.ndarray, col_range=None) -> dict:
+        """The two pictures of a batch's ordered decode as host RGBA arrays (n,H,W,4) uint8 (``evaluation.render.OD_PNG_NAMES``
+        names the keys): ``od_map``, the ordered class maps through the region colours, and ``od_bounds``, the scans with the
+        ordered rows solid in the truth colours, as ``gs_bounds`` draws the delineations (a row of 0 is not drawn).  Waits
+        for the device."""
+        if self._gs_geom is None:
+            raise RuntimeError("render_ordered needs the device: this run was built over injected batches")
+        bs, H, W, C, dev = self._gs_geom
+        if self._png is None:
+            self._png = PngRenderer(bs, H, W, dev)
+        labels, rows, _ = batch.ordered
+        pics = batch_pictures(self._png, C, images, gs_segs=rows, gs_labels=labels, col_range=col_range)
+        return {"od_map": pics["gs_map"], "od_bounds": pics["gs_bounds"]}
 
     def render_gray(self, gray_u8: np.ndarray) -> np.ndarray:
         """(n,H,W) uint8 -> (n,H,W,4) RGBA on the host: the values as a gray scan with no lines, through the renderer of

@@ -122,8 +122,11 @@ PREDICTION_PNG_NAMES = {"pred": "segmentation_map.png", "raw": "raw_image.png",
                         "gs_bounds": "gs_predicted_boundaries_ovelay_plot.png",
                         "uncertainty": "uncertainty_map.png"}        # (no counterpart in the reference: Monte-Carlo dropout)
 
+# the ordered decode's pictures (no counterpart in the reference), in evaluate_model and predict alike
+OD_PNG_NAMES = {"od_map": "od_predicted_segmentation_map.png", "od_bounds": "od_predicted_boundaries_overlay_plot.png"}
 
-IGNORED_RGB = (128, 128, 128)     # ground-truth pixels that carry the evaluation's ignore_label
+
+IGNORED_RGB = (128, 128, 128)    # ground-truth pixels that carry the evaluation's ignore_label
 
 
 def write_pictures(output_dir, pictures: Dict[str, np.ndarray], k: int, names: Dict[str, str]) -> None:

@@ -581,9 +581,29 @@ class Model:
             mean[lo:hi], am[lo:hi], ent[lo:hi], mi[lo:hi] = (out[k].cpu().numpy() for k in keys)
         return mean, am, ent, mi
 
+    def predict_ordered(self, x, batch_size: Optional[int] = None):
+        """Topology-correct class maps: per column the best labelling whose class index never decreases with depth, decoded on
+        the device from the class probabilities (``UNetEngine.ordered_decode``).  Input as for
+        ``predict``; returns ``(labels (n,H,W) uint8, rows (n,C-1,W) uint16)`` -- ``rows[i]`` is the first row of a class above
+        i in the column (0: the column starts below boundary i; H: no such class), so the rows never cross.  The label map is
+        the authoritative one.  Needs 2..16 classes and H <= 4096.  Padding as for ``predict_mc``, from the model's ``pad_mode``
+        / ``pad_value`` attributes: the probabilities are cropped in front of the decode."""
+        from ..evaluation.ordered import check_ordered
+        x = np.asarray(x)
+        if x.dtype != np.uint8:
+            x = np.ascontiguousarray(x, dtype=np.float32)
+        C = int(self.config["num_classes"])
+        check_ordered(C, x.shape[1], "predict_ordered")
+        labels, rows = np.empty(x.shape[:3], np.uint8), np.empty((x.shape[0], C - 1, x.shape[2]), np.uint16)
+        for lo, hi, eng, maps in self._inference_batches(x, int(batch_size or min(x.shape[0], 32)), self._pad_options(None, 0),
+                                                         want_probs=True, want_argmax=False):
+            lab, r, _ = eng.ordered_decode(maps["probs"])
+            labels[lo:hi], rows[lo:hi] = lab.cpu().numpy(), r.cpu().numpy().view(np.uint16)
+        return labels, rows
+
     def predict_labels(self, x_u8: np.ndarray, batch_size: int = 32, want_maps: bool = False, bg_ilm: bool = True,
                        bg_csi: bool = False, soft_maps: bool = False, mc_samples: int = 0, mc_step0: int = 0,
-                       pad_mode: Optional[str] = None, pad_value=0, tta=None):
+                       pad_mode: Optional[str] = None, pad_value=0, tta=None, ordered: bool = False):
         """Raw uint8 images -> uint8 arg-max class maps (n,H,W), computed on the device (1 B/px back instead of
         4*C B/px).  With ``want_maps`` also the (n, C-1, H, W) uint8 boundary maps of
         ``convert_predictions_to_maps_semantic``, computed on the device from the class maps -- or, with ``soft_maps``,
@@ -595,7 +615,10 @@ class Model:
         over the flipped views instead, returned in the same form.
         ``pad_mode`` / ``pad_value`` (in raw counts, like ``x_u8``) as for ``predict``: the arg-max maps -- and the
         probabilities and uncertainty maps where they are made -- are cropped on the device directly behind the head, and
-        the boundary maps are those of the cropped tensors."""
+        the boundary maps are those of the cropped tensors.
+        With ``ordered`` the ordered decode (``predict_ordered``) of the same probabilities -- the mean ones under
+        ``mc_samples`` / ``tta`` -- is appended as the LAST element: ``(labels (n,H,W) uint8, rows (n,C-1,W) uint16, score (n,W)
+        uint32)``."""
         if soft_maps and not want_maps:
             raise ValueError("soft_maps: needs want_maps=True")
         from ..common.utils import check_tta
@@ -610,9 +633,16 @@ class Model:
         out = np.empty(x_u8.shape[:3], np.uint8)
         maps = np.empty((x_u8.shape[0], self.config["num_classes"] - 1) + tuple(x_u8.shape[1:3]), np.uint8) if want_maps else None
         unc = (np.empty(x_u8.shape[:3], np.float32), np.empty(x_u8.shape[:3], np.float32)) if mc_samples or tta else ()
-        kind = dict(mc=(mc_samples, mc_step0) if mc_samples else None, tta=tta or None, want_probs=soft_maps, want_argmax=True)
+        C = int(self.config["num_classes"])
+        dec = ((np.empty(x_u8.shape[:3], np.uint8), np.empty((x_u8.shape[0], C - 1, x_u8.shape[2]), np.uint16),
+                np.empty((x_u8.shape[0], x_u8.shape[2]), np.uint32)),) if ordered else ()
+        kind = dict(mc=(mc_samples, mc_step0) if mc_samples else None, tta=tta or None, want_probs=soft_maps or bool(ordered),
+                    want_argmax=True)
         for lo, hi, eng, mc in self._inference_batches(x_u8, batch_size, (pad_mode, pad_value), **kind):
             probs, am = mc.get("mean_probs", mc.get("probs")), mc["argmax"]
+            if dec:
+                for o, t, dt in zip(dec[0], eng.ordered_decode(probs), (np.uint8, np.uint16, np.uint32)):
+                    o[lo:hi] = t.cpu().numpy().view(dt)
             if unc:
                 unc[0][lo:hi], unc[1][lo:hi] = mc["entropy"].cpu().numpy(), mc["mutual_info"].cpu().numpy()
             out[lo:hi] = am.cpu().numpy()
@@ -620,6 +650,8 @@ class Model:
                 dev_maps = (eng.boundary_maps_soft(probs, bg_ilm=bg_ilm, bg_csi=bg_csi) if soft_maps
                             else eng.boundary_maps(am, bg_ilm=bg_ilm, bg_csi=bg_csi))
                 maps[lo:hi] = dev_maps.cpu().numpy()
+        if dec:
+            return ((out, maps) if want_maps else (out,)) + unc + dec
         return ((out, maps) if want_maps else out) if not unc else ((out, maps) + unc if want_maps else (out,) + unc)
 
 

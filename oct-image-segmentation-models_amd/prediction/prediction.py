@@ -16,7 +16,8 @@ import numpy as np
 from .. import parallel
 from ..common import h5io, utils
 from ..evaluation.pipeline import InferenceRun
-from ..evaluation.render import PREDICTION_PNG_NAMES, write_pictures
+from ..evaluation.ordered import layer_thickness
+from ..evaluation.render import OD_PNG_NAMES, PREDICTION_PNG_NAMES, write_pictures
 from ..min_path_processing import graph_search  # noqa: F401  (re-exported: callers build graph structures through it)
 from ..models import get_model_class
 from .prediction_parameters import PredictionParams
@@ -70,6 +71,7 @@ def predict(predict_params: PredictionParams) -> List[PredictionOutput]:
     lo, hi = parallel.shard_range(len(images), rank, world)
     png_plots = bool(getattr(predict_params, "png_plots", False)) and predict_params.save_params.png_images is True
     mc_samples = int(getattr(predict_params, "mc_samples", 0))
+    ordered_decode = bool(getattr(predict_params, "ordered_decode", False))
     # the device pipeline of evaluate_model (evaluation/pipeline.py::InferenceRun), without ground truth
     with InferenceRun(predict_params.loaded_model, images[lo:hi], predict_params.batch_size, num_classes,
                       graph_search=predict_params.graph_search, gs_device=predict_params.gs_device,
@@ -78,7 +80,8 @@ def predict(predict_params: PredictionParams) -> List[PredictionOutput]:
                       mc_samples=mc_samples, mc_step0=getattr(predict_params, "mc_step0", 0),
                       pad_mode=getattr(predict_params, "pad_mode", None),
                       pad_value=getattr(predict_params, "pad_value", 0), tta=getattr(predict_params, "tta", None),
-                      temperature=getattr(predict_params, "temperature", 1.0)) as run:
+                      temperature=getattr(predict_params, "temperature", 1.0),
+                      **({"ordered_decode": True} if ordered_decode else {})) as run:
         t0 = time.time()
         for batch in run:
             b0, b1 = lo + batch.lo, lo + batch.hi
@@ -96,6 +99,10 @@ def predict(predict_params: PredictionParams) -> List[PredictionOutput]:
                                            col_range=(predict_params.col_error_range[0], predict_params.col_error_range[-1]))
                 if batch.entropy is not None:
                     pictures["uncertainty"] = run.render_gray(utils.entropy_to_u8(batch.entropy, num_classes))
+            od_pictures = None
+            if png_plots and ordered_decode:
+                od_pictures = run.render_ordered(batch, images[b0:b1],
+                                                 col_range=(predict_params.col_error_range[0], predict_params.col_error_range[-1]))
             for i in range(b0, b1):
                 predict_image, image_name, image_output_dir = images[i], dataset.image_names[i], Path(dataset.image_output_dirs[i])
                 os.makedirs(image_output_dir, exist_ok=True)
@@ -114,7 +121,10 @@ def predict(predict_params: PredictionParams) -> List[PredictionOutput]:
                     entropy, mutual_info = batch.entropy[i - b0], batch.mutual_info[i - b0]
                 save_image_prediction_results(predict_params, predict_image, image_name, predicted_labels, categorical_pred,
                                               boundary_maps, predict_time, convert_time, image_output_dir,
-                                              entropy=entropy, mutual_info=mutual_info)
+                                              entropy=entropy, mutual_info=mutual_info,
+                                              ordered=None if batch.ordered is None else tuple(t[i - b0] for t in batch.ordered))
+                if od_pictures is not None:
+                    write_pictures(image_output_dir, od_pictures, i - b0, OD_PNG_NAMES)
                 gs_pred_segs = None
                 if predict_params.graph_search:
                     predict_image_t = np.transpose(predict_image, axes=[1, 0, 2])
@@ -155,13 +165,18 @@ def save_predict_config_file(predict_params: PredictionParams):
         attrs["pad_value"] = np.array(float(getattr(predict_params, "pad_value", 0)))
     if getattr(predict_params, "temperature", 1.0) != 1.0:
         attrs["temperature"] = np.array(float(predict_params.temperature))      # likewise
+    if getattr(predict_params, "ordered_decode", False):
+        attrs["ordered_decode"] = np.array(True)      # likewise
     h5io.save(predict_params.config_output_dir / Path("prediction_params.hdf5"), {}, attrs)
 
 
 def save_image_prediction_results(pred_params, predict_image, image_name, predicted_labels, categorical_pred,
-                                  boundary_maps, predict_time, convert_time, output_dir, entropy=None, mutual_info=None):
+                                  boundary_maps, predict_time, convert_time, output_dir, entropy=None, mutual_info=None,
+                                  ordered=None):
     """``entropy`` / ``mutual_info``: the (H,W) maps of a Monte-Carlo dropout or test-time-augmented prediction, stored
-    (with the sample count, or the views) only when given: without them the file is what it always was."""
+    (with the sample count, or the views) only when given: without them the file is what it always was.  ``ordered``: the
+    image's ``(labels (H,W), rows (C-1,W), score (W))`` of ``Batch.ordered``, likewise: the file gains ``od_predicted_labels``,
+    ``od_pred_segs`` and (from 3 classes) ``layer_thickness``, and the two od_ CSV files are written."""
     ds = {}
     if pred_params.save_params.categorical_pred is True:
         ds["categorical_pred"] = categorical_pred.astype("uint8")
@@ -181,6 +196,14 @@ def save_image_prediction_results(pred_params, predict_image, image_name, predic
             attrs["mc_samples"] = np.array(int(getattr(pred_params, "mc_samples", 0)))
     if getattr(pred_params, "temperature", 1.0) != 1.0:
         attrs["temperature"] = np.array(float(pred_params.temperature))      # only when set
+    if ordered is not None:
+        od_labels, od_rows = ordered[0], ordered[1]
+        np.savetxt(output_dir / Path("od_boundaries.csv"), od_rows, delimiter=",", fmt="%d")
+        np.savetxt(output_dir / Path("od_predicted_segmentation_map.csv"), od_labels, fmt="%d", delimiter=",")
+        ds["od_predicted_labels"], ds["od_pred_segs"] = od_labels.astype("uint8"), od_rows.astype("uint16")
+        thickness, _ = layer_thickness(od_rows)
+        if thickness is not None:
+            ds["layer_thickness"] = thickness
     h5io.save(output_dir / Path("prediction_info.hdf5"), ds, attrs)
 
 

@@ -26,7 +26,12 @@ class PredictionParams:
                  trim_window: tuple = (0, 0), col_error_range: tuple = None, batch_size: int = 32, gs_device: bool = False,
                  gs_device_ties: str = "host", gs_workers: Union[int, None] = None, gs_labels_device: bool = False,
                  binarize: bool = True, png_plots: bool = False, mc_samples: int = 0, mc_step0: int = 0,
-                 pad_mode: Union[str, None] = None, pad_value=0, tta=None, temperature: float = 1.0) -> None:
+                 pad_mode: Union[str, None] = None, pad_value=0, tta=None, temperature: float = 1.0,
+                 ordered_decode: bool = False) -> None:
+        # extension, as EvaluationParameters.ordered_decode: prediction_info.hdf5 gains od_predicted_labels, od_pred_segs and
+        # (from 3 classes) layer_thickness, and od_boundaries.csv / od_predicted_segmentation_map.csv are written.  False: nothing is
+        # launched, every file as it was
+        self.ordered_decode = bool(ordered_decode)
         if not 0 <= int(mc_samples) <= 64:
             raise ValueError(f"mc_samples must be in 0..64, not {mc_samples}")
         # extension: temperature scaling.  A number in [1/16, 16], e.g. the one train_model(fit_temperature=True)
@@ -56,6 +61,9 @@ class PredictionParams:
         self.loaded_model, self.model_config = utils.load_model_and_config(
             self.model_path, mlflow_tracking_uri=mlflow_tracking_uri, mlflow_run_uuid=mlflow_run_uuid)
         self.num_classes = self.loaded_model.output.shape[-1]
+        if self.ordered_decode:
+            from ..evaluation.ordered import check_ordered
+            check_ordered(self.num_classes, 1)
         self.config_output_dir = Path(config_output_dir)
         self.save_params = save_params
         self.graph_search = graph_search
