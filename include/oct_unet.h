@@ -41,6 +41,7 @@
  *   oct_calibration_counts / oct_temperature_apply / oct_temperature_nll  (none: reliability counts, ECE / NLL / Brier and
  *                                      temperature scaling of the softmax output, Guo et al. 2017)
  *   oct_ordered_decode                 (none: the best class map per column whose class index never decreases with depth)
+ *   oct_components / oct_component_filter  (none: connected components of the class map, island removal, lesion counts)
  */
 #ifndef OCT_UNET_H
 #define OCT_UNET_H
@@ -694,6 +695,60 @@ size_t oct_ordered_workspace_bytes(int B, int H, int W, int n_cls);
 int oct_ordered_decode(const float* probs_dev /* (B, H, W, n_cls) f32 */, int B, int H, int W, int n_cls, void* ws_dev, size_t ws_bytes,
                        unsigned char* labels_out_dev /* (B, H, W) or NULL */, unsigned short* rows_out_dev /* (B, n_cls-1, W) or NULL */,
                        unsigned int* score_out_dev /* (B, W) or NULL */, oct_stream_t stream);
+
+/* ---- connected components of a class map on the device (csrc/kernels_components.hpp; numpy restatements: common/utils.py::
+ * components_reference and component_filter_reference; the reference has no counterpart) ----
+ * labels_dev (B, H, W) uint8.  Integers throughout; the restatements and the kernels agree bit for bit.
+ *   neighbours   two pixels of ONE image with |dy| + |dx| == 1 (connectivity 4) or max(|dy|, |dx|) == 1 (connectivity 8).
+ *   component    a maximal set of pixels of equal byte value joined by chains of neighbours.  Any byte value 0..255 forms
+ *                components; n_cls bounds only the statistics.  Components never join across images.
+ *   root[b,y,x]  the smallest y*W + x over the pixel's component: canonical, whatever the order of the merges.
+ *   size[b,y,x]  the pixel count of the component at its root pixel, 0 at every other pixel.
+ *   stats[b,c]   (number of components of class c in image b, pixels of the largest one); (0, 0) when the class is absent; c < n_cls.
+ * root_out_dev (B,H,W) uint32; size_out_dev (B,H,W) uint32 or NULL; stats_out_dev (B, n_cls, 2) uint32 or NULL.
+ * Stand-alone like oct_ordered_decode: no handle, no allocation, asynchronous on `stream`, never waits, records into a stream
+ * capture; repeated calls give identical bytes.  The launches depend on the shape and on which outputs are wanted, never on
+ * the data: a memset of the statistics, a union-find per 64x64 tile in LDS, a union across the tile borders (skipped for an
+ * image of one tile; every access to the parent words there is a relaxed agent-scope atomic), a pass that flattens every pixel
+ * to its root and moves the counts there, and one that forms the statistics.  Integer atomicMin / atomicAdd / atomicMax whose
+ * final value does not depend on the order; no thread waits for another, every find / union loop follows strictly decreasing
+ * indices.  The workspace (8-byte aligned) holds the size words when size_out_dev is NULL, and the filter's scratch.
+ * Errors (negative, oct_last_error(), nothing launched): null labels, root or workspace, B outside 1..65535, H or W < 1,
+ * B*H*W >= 2^31, n_cls outside 1..32, a connectivity other than 4 or 8, a workspace smaller than
+ * oct_components_workspace_bytes (which returns 0 for a shape the call refuses) or misaligned, misaligned outputs, an output
+ * overlapping the input, the workspace or another output.
+ *
+ * oct_component_filter reads labels_dev and the root and size words of oct_components and writes the cleaned map, out of place.
+ *   removed      a pixel of class c < n_cls with root r is REMOVED if size[r] < rule->min_pixels[c], or if bit c of
+ *                rule->keep_largest is set and r is not the best root of (b, c): the component of class c with the most pixels,
+ *                among equals the one with the smallest root.  Pixels with a label >= n_cls are never removed.
+ *   kept         a kept pixel keeps its byte.
+ *   fill mode 0  a removed pixel gets rule->fill_label.
+ *   fill mode 1  a removed pixel gets the label of the nearest pixel ABOVE it in its column that is kept and has a label
+ *                < n_cls; if there is none, that of the nearest such pixel below it; if there is none, rule->fill_label.  The
+ *                rule that suits B-scans: a speck takes the class of the layer over it.
+ *   removed[b,c] the removed pixels whose original class is c; removed_out_dev (B, n_cls) uint32 or NULL.
+ * ONE pass and NOT idempotent: filled regions may join their neighbours, so the components of the cleaned map are not those of
+ * the input less the removed ones; run oct_components again on the cleaned map before filtering it again.  The workspace bytes
+ * are those of oct_components_workspace_bytes; the launches depend on the rule alone (the best roots only if keep_largest != 0,
+ * the column walk -- a thread per column -- only under fill mode 1).  Otherwise as oct_components.
+ * Errors: as oct_components, and null size, rule or output, a fill mode outside 0..1, a fill label outside 0..255,
+ * keep_largest bits at or above n_cls. */
+typedef struct oct_component_rule {   /* HOST struct, copied into the kernel arguments by the call */
+    unsigned int min_pixels[32];      /* class c: components with fewer pixels are removed (0 or 1: none) */
+    unsigned int keep_largest;        /* bit c: of class c only the largest component of each image stays */
+    int fill_mode;                    /* 0 constant, 1 column */
+    int fill_label;                   /* 0..255 */
+} oct_component_rule;
+size_t oct_components_workspace_bytes(int B, int H, int W);      /* 0 = a shape the call refuses */
+int oct_components(const unsigned char* labels_dev /* (B, H, W) */, int B, int H, int W, int n_cls, int connectivity /* 4 | 8 */,
+                   void* ws_dev, size_t ws_bytes, unsigned int* root_out_dev /* (B, H, W) */,
+                   unsigned int* size_out_dev /* (B, H, W) or NULL */, unsigned int* stats_out_dev /* (B, n_cls, 2) or NULL */,
+                   oct_stream_t stream);
+int oct_component_filter(const unsigned char* labels_dev, const unsigned int* root_dev, const unsigned int* size_dev,
+                         int B, int H, int W, int n_cls, const oct_component_rule* rule, void* ws_dev, size_t ws_bytes,
+                         unsigned char* labels_out_dev /* (B, H, W) */, unsigned int* removed_out_dev /* (B, n_cls) or NULL */,
+                         oct_stream_t stream);
 
 /* ---- PNG pictures on the device (csrc/kernels_render.hpp; numpy restatement: common/plotting.py::render_reference) ----
  * oct_render_rgba renders B images of H x W into out_dev (B, H, W, 4) uint8 RGBA with A = 255: a base layer, then

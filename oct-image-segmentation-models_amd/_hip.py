@@ -72,6 +72,12 @@ class DiceShape(C.Structure):
 DICE_WEIGHT_NONE, DICE_WEIGHT_CLASS, DICE_WEIGHT_VOLUME = range(3)
 
 
+class ComponentRuleC(C.Structure):
+    """``oct_component_rule``: what ``oct_component_filter`` removes and how it fills (``evaluation.components.ComponentRule``
+    packs it)."""
+    _fields_ = [("min_pixels", C.c_uint * 32), ("keep_largest", C.c_uint), ("fill_mode", C.c_int), ("fill_label", C.c_int)]
+
+
 class UNetIO(C.Structure):
     _fields_ = [("probs", C.c_void_p), ("argmax", C.c_void_p), ("labels", C.c_void_p)]
 
@@ -172,6 +178,11 @@ SYMBOLS = [
     ("oct_ordered_workspace_bytes", C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     ("oct_ordered_decode", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),
+    ("oct_components_workspace_bytes", C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    ("oct_components", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("oct_component_filter", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       _P(ComponentRuleC), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("oct_render_rgba", C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, _P(RenderStyle), C.c_int, C.c_int, C.c_int,
                                   C.c_void_p, C.c_void_p]),
     ("oct_set_option", C.c_int, [C.c_char_p, C.c_int]),

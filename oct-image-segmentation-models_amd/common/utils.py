@@ -380,3 +380,137 @@ def ordered_decode_reference(probs) -> Tuple[np.ndarray, np.ndarray, np.ndarray]
         labels[:, r] = c
     rows = np.stack([(labels <= i).sum(axis=1) for i in range(Cn - 1)], axis=1).astype(np.uint16)
     return labels, rows, score
+
+
+COMPONENTS_MAX_CLASSES, COMPONENTS_MAX_BATCH = 32, 65535                   # what oct_components / oct_component_filter accept
+COMPONENTS_FILL_CONSTANT, COMPONENTS_FILL_COLUMN = 0, 1                    # oct_component_rule.fill_mode
+
+
+def _components_check(name: str, labels, n_cls: int) -> np.ndarray:
+    lab = np.asarray(labels)
+    if lab.ndim != 3 or lab.dtype != np.uint8:
+        raise ValueError(f"{name}: labels must be (B,H,W) uint8, not {lab.dtype} {lab.shape}")
+    B, H, W = lab.shape
+    if not 1 <= B <= COMPONENTS_MAX_BATCH or min(H, W) < 1 or B * H * W >= 1 << 31:
+        raise ValueError(f"{name}: need 1 <= B <= {COMPONENTS_MAX_BATCH}, H, W >= 1 and B*H*W < 2^31, not {lab.shape}")
+    if not 1 <= int(n_cls) <= COMPONENTS_MAX_CLASSES:
+        raise ValueError(f"{name}: need 1 <= n_cls <= {COMPONENTS_MAX_CLASSES}, not {n_cls}")
+    return lab
+
+
+def components_reference(labels, n_cls: int, connectivity: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """``oct_components`` restated (include/oct_unet.h): a class map (B,H,W) uint8 -> ``(root (B,H,W) uint32, size (B,H,W)
+    uint32, stats (B,n_cls,2) uint32)``.
+
+        neighbours   two pixels of ONE image with |dy| + |dx| == 1 (connectivity 4) or max(|dy|, |dx|) == 1 (connectivity 8)
+        component    a maximal set of pixels of equal byte value joined by chains of neighbours; any byte value forms
+                     components, n_cls bounds only the statistics
+        root[b,y,x]  the smallest y*W + x over the pixel's component
+        size[b,y,x]  the pixel count of the component at its root pixel, 0 at every other pixel
+        stats[b,c]   (number of components of class c in image b, pixels of the largest one), (0, 0) when the class is absent
+
+    The roots are found as the kernels find them -- parents that only ever decrease, the larger of two roots hung under the
+    smaller -- but for all pixel pairs at once: hang, jump every pointer to its root, repeat until no pair of neighbours has
+    two roots.  The answer does not depend on the order.  Integers throughout: the kernels give the same bits."""
+    lab = _components_check("components_reference", labels, n_cls)
+    if connectivity not in (4, 8):
+        raise ValueError(f"components_reference: connectivity must be 4 or 8, not {connectivity}")
+    B, H, W = lab.shape
+    idx = np.arange(H * W, dtype=np.int64).reshape(H, W)
+    steps = [(0, 1), (1, 0)] + ([(1, 1), (1, -1)] if connectivity == 8 else [])
+    root = np.empty((B, H, W), np.uint32)
+    size = np.zeros((B, H, W), np.uint32)
+    stats = np.zeros((B, int(n_cls), 2), np.uint32)
+    for b in range(B):
+        pairs = []
+        for dy, dx in steps:                       # (y, x) and (y + dy, x + dx), both inside, equal bytes
+            ys, xs = slice(0, H - dy), slice(max(0, -dx), W - max(0, dx))
+            yt, xt = slice(dy, H), slice(max(0, dx), W + min(0, dx))
+            same = lab[b, ys, xs] == lab[b, yt, xt]
+            pairs.append((idx[ys, xs][same], idx[yt, xt][same]))
+        pa, pb = np.concatenate([p[0] for p in pairs]), np.concatenate([p[1] for p in pairs])
+        par = np.arange(H * W, dtype=np.int64)
+        while True:
+            while True:                            # every pointer to its root
+                nxt = par[par]
+                if np.array_equal(nxt, par):
+                    break
+                par = nxt
+            ra, rb = par[pa], par[pb]
+            differ = ra != rb
+            if not differ.any():
+                break
+            np.minimum.at(par, np.maximum(ra, rb)[differ], np.minimum(ra, rb)[differ])
+        root[b] = par.reshape(H, W)
+        counts = np.bincount(par, minlength=H * W)
+        is_root = par == np.arange(H * W)
+        size[b] = np.where(is_root, counts, 0).reshape(H, W)
+        cls = lab[b].reshape(-1)[is_root]
+        for c in range(int(n_cls)):
+            s = counts[is_root][cls == c]
+            if s.size:
+                stats[b, c] = (s.size, s.max())
+    return root, size, stats
+
+
+def component_filter_reference(labels, root, size, n_cls: int, rule) -> Tuple[np.ndarray, np.ndarray]:
+    """``oct_component_filter`` restated (include/oct_unet.h): the class map, the ``root`` and ``size`` of
+    ``components_reference`` and a rule -- anything with the fields of ``oct_component_rule``: ``min_pixels`` (a value per
+    class), ``keep_largest`` (bit c), ``fill_mode`` (0 constant, 1 column), ``fill_label`` -> ``(labels_out (B,H,W) uint8,
+    removed (B,n_cls) uint32)``.
+
+        removed      a pixel of class c < n_cls with root r, if size[r] < min_pixels[c], or if bit c of keep_largest is set and r
+                     is not the best root of (b, c): the component of class c with the most pixels, among equals the one with
+                     the smallest root.  Pixels with a label >= n_cls are never removed.
+        kept         a kept pixel keeps its byte
+        fill mode 0  a removed pixel gets fill_label
+        fill mode 1  a removed pixel gets the label of the nearest pixel ABOVE it in its column that is kept and has a label
+                     < n_cls; if there is none, that of the nearest such pixel below it; if there is none, fill_label
+        removed[b,c] the removed pixels whose original class is c
+
+    One pass, not idempotent."""
+    lab = _components_check("component_filter_reference", labels, n_cls)
+    n_cls = int(n_cls)
+    B, H, W = lab.shape
+    root, size = np.asarray(root), np.asarray(size)
+    if root.shape != lab.shape or size.shape != lab.shape:
+        raise ValueError("component_filter_reference: root and size must have the shape of labels")
+    min_pixels = [int(v) for v in list(rule.min_pixels)[:n_cls]]
+    keep, mode, fill = int(rule.keep_largest), int(rule.fill_mode), int(rule.fill_label)
+    if len(min_pixels) < n_cls or mode not in (0, 1) or not 0 <= fill <= 255 or keep >> n_cls:
+        raise ValueError("component_filter_reference: the rule needs n_cls min_pixels, fill_mode 0..1, fill_label 0..255 and "
+                         "no keep_largest bit at or above n_cls")
+    gone = np.zeros(lab.shape, bool)
+    removed = np.zeros((B, n_cls), np.uint32)
+    for b in range(B):
+        r = root[b].reshape(-1).astype(np.int64)
+        s = size[b].reshape(-1).astype(np.int64)
+        l = lab[b].reshape(-1)
+        roots = np.flatnonzero(s)
+        for c in range(n_cls):
+            of_c = l == c
+            g = of_c & (s[r] < min_pixels[c])
+            if (keep >> c) & 1:
+                rc = roots[l[roots] == c]
+                if rc.size:
+                    best = rc[np.lexsort((rc, -s[rc]))[0]]         # most pixels, then the smallest root
+                    g |= of_c & (r != best)
+            gone[b] |= g.reshape(H, W)
+            removed[b, c] = g.sum()
+    out = lab.copy()
+    if mode == COMPONENTS_FILL_CONSTANT:
+        out[gone] = fill
+        return out, removed
+    source = ~gone & (lab < n_cls)
+    above = np.full((B, H, W), -1, np.int64)                       # the label of the nearest source above, or -1
+    below = np.full((B, H, W), -1, np.int64)
+    cur = np.full((B, W), -1, np.int64)
+    for y in range(H):
+        above[:, y] = cur
+        cur = np.where(source[:, y], lab[:, y], cur)
+    cur = np.full((B, W), -1, np.int64)
+    for y in range(H - 1, -1, -1):
+        below[:, y] = cur
+        cur = np.where(source[:, y], lab[:, y], cur)
+    filled = np.where(above >= 0, above, np.where(below >= 0, below, fill))
+    return np.where(gone, filled, lab).astype(np.uint8), removed

@@ -37,12 +37,13 @@ from .dice_device import DICE_METRICS, MAX_EXACT_PIXELS, dice_from_counts
 from .evaluation_parameters import EvaluationParameters
 from .ordered import layer_thickness
 from .pipeline import InferenceRun
-from .render import EVALUATION_PNG_NAMES, OD_PNG_NAMES, write_pictures
+from .render import CC_PNG_NAMES, EVALUATION_PNG_NAMES, OD_PNG_NAMES, write_pictures
 from .surface import datasets as surface_datasets
 
 EVALUATION_RESULTS_FILENAME = "evaluation_results.hdf5"
 GS_EVALUATION_RESULTS_FILENAME = "gs_evaluation_results.hdf5"
 OD_EVALUATION_RESULTS_FILENAME = "od_evaluation_results.hdf5"
+CC_EVALUATION_RESULTS_FILENAME = "cc_evaluation_results.hdf5"
 OVERALL_EVALUATION_RESULTS_FILENAME_HDF5 = "overall_evaluation_results.hdf5"
 OVERALL_EVALUATION_RESULTS_FILENAME_CSV = "overall_evaluation_results.csv"
 
@@ -177,6 +178,8 @@ def evaluate_model(eval_params: EvaluationParameters) -> List[EvaluationOutput]:
     calibration_bins, temperature = getattr(eval_params, "calibration_bins", 0), getattr(eval_params, "temperature", 1.0)
     # ordered_decode: the topology-correct class maps of the probabilities, decoded on the device
     ordered_decode = bool(getattr(eval_params, "ordered_decode", False))
+    # components: island removal and component counts of the arg-max maps on the device
+    components = getattr(eval_params, "components", None)
     need_gt = want_surface or (metrics_device and want_dice) or calibration_bins > 0
     gt_maps = np.squeeze(eval_labels[lo:hi], axis=3) if need_gt else None
     # BASELINE configs[4] path (evaluation/pipeline.py::InferenceRun): search mode, batch source and worker pools
@@ -190,11 +193,20 @@ def evaluate_model(eval_params: EvaluationParameters) -> List[EvaluationOutput]:
                       pad_mode=getattr(eval_params, "pad_mode", None), pad_value=getattr(eval_params, "pad_value", 0),
                       ignore_label=ignore_label, tta=getattr(eval_params, "tta", None),
                       calibration_bins=calibration_bins, temperature=temperature,
-                      **({"ordered_decode": True} if ordered_decode else {})) as run:
+                      **({"ordered_decode": True} if ordered_decode else {}),
+                      **({"components": components} if components is not None else {})) as run:
         t_prev = time.time()
         for batch in run:
             b0, b1 = lo + batch.lo, lo + batch.hi
             predict_time = (time.time() - t_prev) / (b1 - b0)
+            cc_counts = cc_surface = cc_pictures = None
+            if components is not None:
+                if metrics_device and want_dice:
+                    cc_counts = run.label_counts(batch.components[0], gt_maps[batch.lo:batch.hi], batch.lo)
+                if want_surface:
+                    cc_surface = run.label_surface(batch.components[0], gt_maps[batch.lo:batch.hi])
+                if png_plots:
+                    cc_pictures = {"cc_map": run.render_labels(batch.components[0])}
             od_counts = od_pictures = None
             if ordered_decode:
                 if metrics_device and want_dice:
@@ -275,6 +287,20 @@ def evaluate_model(eval_params: EvaluationParameters) -> List[EvaluationOutput]:
                                                      int(np.count_nonzero(od_labels != predicted_labels)), eval_image_output_dir)
                     if od_pictures is not None:
                         write_pictures(eval_image_output_dir, od_pictures, ind - b0, OD_PNG_NAMES)
+                if components is not None:
+                    cc_labels = batch.components[0][ind - b0]
+                    if cc_counts is not None:
+                        cc_dice = dice_from_counts(cc_counts[ind - b0], eval_params.metrics)
+                    else:
+                        cc_cat = common_utils.labels_to_categorical(cc_labels[None].astype(np.int64), num_classes)
+                        cc_dice = _dice_metrics(eval_params.metrics, num_classes, eval_label,
+                                                cc_cat if keep is None else cc_cat * keep.astype(np.float32))
+                    _save_components_evaluation_results(
+                        eval_params, eval_image_name, cc_labels, batch.components[1][ind - b0], batch.components[2][ind - b0],
+                        cc_dice, _surface_metrics(eval_params.metrics, None if cc_surface is None else cc_surface[ind - b0]),
+                        int(np.count_nonzero(cc_labels != predicted_labels)), eval_image_output_dir)
+                    if cc_pictures is not None:
+                        write_pictures(eval_image_output_dir, cc_pictures, ind - b0, CC_PNG_NAMES)
                 if pictures is not None:
                     write_pictures(eval_image_output_dir, pictures, ind - b0, EVALUATION_PNG_NAMES)
                 eval_outputs.append(EvaluationOutput(
@@ -370,6 +396,26 @@ def _save_ordered_evaluation_results(eval_params, image_name, od_labels, od_rows
     h5io.save(output_dir / Path(OD_EVALUATION_RESULTS_FILENAME), ds, common_utils.result_attrs(eval_params.model_path, image_name))
 
 
+def _save_components_evaluation_results(eval_params, image_name, cc_labels, stats, removed, dice, surface_ds, changed_pixels,
+                                        output_dir):
+    """The component stage's file of one image: ``cc_labels`` (H,W) uint8, ``stats`` (C,2) and ``removed``
+    (C,) uint32 of ``Batch.components``, ``dice`` = (classes, macro, micro) and ``surface_ds`` of the cleaned map, formed as for
+    the arg-max map, ``changed_pixels`` the pixels where the cleaned map differs from the arg-max."""
+    ds = {"cc_predicted_labels": cc_labels.astype("uint8"), "component_count": stats[:, 0].astype("uint32"),
+          "largest_component_pixels": stats[:, 1].astype("uint32"), "removed_pixels": removed.astype("uint32"),
+          "changed_pixels": np.array([changed_pixels], dtype="int64")}
+    dice_classes, dice_macro, dice_micro = dice
+    if dice_classes is not None:
+        ds[EVALUATION_METRIC_DICE_CLASSES] = np.squeeze(dice_classes).astype("float64")
+    if dice_macro is not None:
+        ds[EVALUATION_METRIC_DICE_MACRO] = np.expand_dims(dice_macro, axis=0).astype("float64")
+    if dice_micro is not None:
+        ds[EVALUATION_METRIC_DICE_MICRO] = np.expand_dims(dice_micro, axis=0).astype("float64")
+    for k, v in (surface_ds or {}).items():
+        ds[k] = np.asarray(v, dtype="float64")
+    h5io.save(output_dir / Path(CC_EVALUATION_RESULTS_FILENAME), ds, common_utils.result_attrs(eval_params.model_path, image_name))
+
+
 def save_eval_config_file(eval_params: EvaluationParameters):
     p = eval_params.test_dataset_path
     md5_path = p if Path(p).exists() else Path(str(p) + ".npz")
@@ -395,6 +441,8 @@ def save_eval_config_file(eval_params: EvaluationParameters):
         attrs["temperature"] = np.array(float(eval_params.temperature))      # likewise
     if getattr(eval_params, "ordered_decode", False):
         attrs["ordered_decode"] = np.array(True)      # likewise
+    if getattr(eval_params, "components", None) is not None:
+        attrs["components"] = np.array(repr(eval_params.components), dtype="S1000")      # likewise
     h5io.save(eval_params.save_foldername / Path("eval_params.hdf5"), {}, attrs)
 
 
@@ -492,6 +540,20 @@ def _calc_overall_dataset_errors(eval_params: EvaluationParameters, eval_image_n
         save_metric("od_changed_pixels", stack(od_files, "changed_pixels"))
         if od_files and "mean_layer_thickness" in od_files[0]:
             save_metric("od_mean_layer_thickness", stack(od_files, "mean_layer_thickness"))
+    if getattr(eval_params, "components", None) is not None:
+        # the component stage: means and standard deviations under cc_ names, behind everything that was there
+        cc_files = [h5io.load(d / Path(CC_EVALUATION_RESULTS_FILENAME)) for d in dir_list]
+        for m in (EVALUATION_METRIC_DICE_CLASSES, EVALUATION_METRIC_DICE_MACRO, EVALUATION_METRIC_DICE_MICRO):
+            if m in metrics:
+                save_metric(f"cc_{m}", stack(cc_files, m))
+        if EVALUATION_METRIC_AVERAGE_SURFACE_DISTANCE in metrics:
+            for name in ("average_surface_distances", "average_surface_distances_gt_to_pred",
+                         "average_surface_distances_pred_to_gt"):
+                save_metric(f"cc_{name}", stack(cc_files, name))
+        if EVALUATION_METRIC_HAUSDORFF_DISTANCE in metrics:
+            save_metric("cc_hausdorff_distances", stack(cc_files, "hausdorff_distances"))
+        for name in ("component_count", "largest_component_pixels", "removed_pixels", "changed_pixels"):
+            save_metric(f"cc_{name}", stack(cc_files, name))
     h5io.save(output_dir / Path(OVERALL_EVALUATION_RESULTS_FILENAME_HDF5), out)
     with open(output_dir / Path(OVERALL_EVALUATION_RESULTS_FILENAME_CSV), "w") as f:
         f.write("\n".join(lines) + "\n")

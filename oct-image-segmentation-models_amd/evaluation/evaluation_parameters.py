@@ -28,7 +28,17 @@ class EvaluationParameters:
                  bg_ilm: bool = True, bg_csi: bool = False, batch_size: int = 32, gs_device: bool = False,
                  gs_device_ties: str = "host", gs_workers: Optional[int] = None, metrics_device: bool = False,
                  png_plots: bool = False, pad_mode: Optional[str] = None, pad_value=0, ignore_label: Optional[int] = None,
-                 tta=None, calibration_bins: int = 0, temperature: float = 1.0, ordered_decode: bool = False):
+                 tta=None, calibration_bins: int = 0, temperature: float = 1.0, ordered_decode: bool = False,
+                 components=None):
+        # extension: connected components of the arg-max class map.  A ComponentRule, or a dict of its
+        # keywords (connectivity, min_pixels, keep_largest, fill): components that the rule removes -- islands below min_pixels,
+        # all but the largest of a class -- are refilled on the device.  Every image gains cc_evaluation_results.hdf5
+        # (cc_predicted_labels, component_count / largest_component_pixels of the arg-max map and removed_pixels per class,
+        # changed_pixels, the Dice metrics and surface distances asked for, of the cleaned map), the overall results the cc_
+        # aggregates; with png_plots one picture.  The rule must fit the model's classes (checked once the model is loaded).
+        # None: nothing is launched, no file changes
+        from .components import ComponentRule
+        self.components = ComponentRule.coerce(components, "components")
         # extension: the ordered layer decode.  Per column the best class map whose class index never
         # decreases with depth, decoded on the device from the class probabilities (the mean ones with tta, the tempered ones with
         # temperature).  Every image gains od_evaluation_results.hdf5 (od_pred_segs, od_predicted_labels, errors and their four
@@ -105,6 +115,8 @@ class EvaluationParameters:
         if self.ordered_decode:
             from .ordered import check_ordered
             check_ordered(self.num_classes, 1)
+        if self.components is not None:
+            self.components.check(self.num_classes)
         # extension: the test set's labels are known in part only (annotated column ranges, masked optic-nerve heads): ground-truth
         # pixels of this value, an int in num_classes..255, are "unknown" wherever a metric, a truth boundary or a ground-truth
         # picture is formed -- out of the Dice counts, no surface element at their rim, no truth boundary underneath them,

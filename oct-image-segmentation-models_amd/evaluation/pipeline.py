@@ -19,6 +19,7 @@ from ..common.utils import check_pad_mode, check_tta, padded_geometry
 from ..min_path_processing.device_search import DeviceMinPath, LazyPool, merge_ties
 from ..min_path_processing.pool import SegmentPool, default_workers
 from .calibration import CalibrationCounts, check_bins, check_temperature
+from .components import ComponentRule, Components, check_components
 from .dice_device import ConfusionCounts, DelineationLabels, check_ignore_label
 from .ordered import OrderedDecode, check_ordered
 from .render import PngRenderer, batch_pictures
@@ -49,10 +50,14 @@ class Batch(NamedTuple):
     # Runs with the ordered decode carry its result for the batch's (mean, tempered, cropped) class probabilities: (labels
     # (n, H, W) uint8, rows (n, C-1, W) uint16, score (n, W) uint32) -- evaluation/ordered.py.  An ATTRIBUTE likewise.
     ordered = None
+    # Runs with a component rule carry the cleaned arg-max maps and the component statistics: (clean_labels (n, H, W) uint8,
+    # stats (n, C, 2) uint32 = [components, pixels of the largest] of the ARG-MAX map, removed (n, C) uint32) --
+    # evaluation/components.py.  An ATTRIBUTE likewise.
+    components = None
 
     def _with(self, **attrs) -> "Batch":
         b = _UncertainBatch(*self)
-        for k in ("entropy", "mutual_info", "calibration", "ordered"):
+        for k in ("entropy", "mutual_info", "calibration", "ordered", "components"):
             setattr(b, k, attrs.get(k, getattr(self, k)))
         return b
 
@@ -68,6 +73,10 @@ class Batch(NamedTuple):
         """This record with ``ordered`` set."""
         return self._with(ordered=ordered)
 
+    def with_components(self, components) -> "Batch":
+        """This record with ``components`` set."""
+        return self._with(components=components)
+
 
 class _UncertainBatch(Batch):
     """A ``Batch`` that can hold the attributes (a NamedTuple instance has no dictionary; an instance of this has)."""
@@ -77,7 +86,7 @@ class _Stage(NamedTuple):
     """One per-batch device post-process: the ``Batch`` field it fills, the wrapper that runs it -- ``run(*inputs, *outs)``
     queues it on the current stream, ``run.outs`` are its own output buffers for a full batch, ``run.to_host`` turns
     output rows into the field's value -- and what it reads: the boundary maps, or else the ground truth with the arg-max
-    maps or (``on_probs``) with the class probabilities, or (``on_probs`` without ``needs_gt``) the class probabilities alone."""
+    maps or (``on_probs``) with the class probabilities, or (without ``needs_gt``) the class probabilities (``on_probs``) or the arg-max maps alone."""
     field: str
     run: object
     on_maps: bool
@@ -96,11 +105,11 @@ class _Stage(NamedTuple):
         return self.run.to_host(*(t[:n] for t in outs), first_image=first_image)
 
 
-def _stages(surface, confusion, minpath, have_gt: bool = True, calibration=None, ordered=None) -> list:
+def _stages(surface, confusion, minpath, have_gt: bool = True, calibration=None, ordered=None, components=None) -> list:
     """The stages to run, in their order on the stream; those that read the ground truth only when there is one."""
     every = (_Stage("surface", surface, False), _Stage("confusion", confusion, False),
              _Stage("calibration", calibration, False, True), _Stage("ordered", ordered, False, True, False),
-             _Stage("minpath", minpath, True))
+             _Stage("components", components, False, False, False), _Stage("minpath", minpath, True))
     return [st for st in every if st.run is not None and (have_gt or not st.reads_gt)]
 
 
@@ -157,12 +166,18 @@ class BatchedPredictor:
     probabilities in the same way and ``oct_ordered_decode`` runs on them -- cropped; with ``mc_samples`` / ``tta`` the MEAN;
     with a ``temperature`` the TEMPERED ones, behind ``oct_temperature_apply``: the decode weighs rows against each other and is
     not invariant to the temperature as the arg-max is.  It reads no ground truth, and ``Batch.ordered`` holds ``(labels,
-    rows, score)``.  It depends on none of ``soft_maps``, ``minpath``, ``confusion``; without it nothing is launched."""
+    rows, score)``.  It depends on none of ``soft_maps``, ``minpath``, ``confusion``; without it nothing is launched.
+
+    With ``components`` (an ``evaluation.components.Components`` for this batch and shape) ``oct_components`` and
+    ``oct_component_filter`` run on the batch's copy of the arg-max maps -- the MEAN prediction's under ``mc_samples`` / ``tta``,
+    the cropped ones under ``hw``; a ``temperature`` does not move the arg-max -- and ``Batch.components`` holds ``(clean_labels,
+    stats, removed)``.  It reads neither the ground truth nor the probabilities and writes only buffers of its own: labels,
+    maps, the search and every other stage see the arg-max maps as before.  Without it nothing is launched."""
 
     def __init__(self, engine, batch: int, want_maps: bool = True, bg_ilm: bool = True, bg_csi: bool = False,
                  surface=None, minpath=None, confusion=None, soft_maps: bool = False, mc_samples: int = 0, mc_step0: int = 0,
                  hw=None, pad_mode: Optional[str] = None, pad_value=0, tta=None, calibration=None, temperature: float = 1.0,
-                 ordered=None):
+                 ordered=None, components=None):
         self.temperature = check_temperature(temperature)
         if self.temperature != 1.0 and (mc_samples or tta):
             raise ValueError("temperature != 1 with mc_samples or tta: the samples would have to be tempered before they are "
@@ -195,8 +210,9 @@ class BatchedPredictor:
         self.lab_dev = [torch.empty((self.B, H, W), dtype=torch.uint8, device=dev) for _ in range(2)]
         self.map_dev = [torch.empty((self.B, C - 1, H, W), dtype=torch.uint8, device=dev) for _ in range(2)] if want_maps else None
         self.wrappers, self.calibration, self.ordered = (surface, confusion, minpath), calibration, ordered
+        self.more = {"components": components} if components is not None else {}      # (the keyword is only passed when set)
         self.out_dev, self.out_pin = {}, {}                 # per stage field: device and pinned double buffers
-        every = _stages(*self.wrappers, calibration=calibration, ordered=ordered)
+        every = _stages(*self.wrappers, calibration=calibration, ordered=ordered, **self.more)
         for st in every:
             if st.on_maps and not want_maps:
                 raise ValueError(f"{st.field}: needs want_maps=True")
@@ -229,7 +245,7 @@ class BatchedPredictor:
         if images_u8.dtype != np.uint8:
             raise TypeError("the batched pipeline takes raw uint8 images (the /255 happens on the device)")
         have_gt = gt_u8 is not None
-        stages = _stages(*self.wrappers, have_gt=have_gt, calibration=self.calibration, ordered=self.ordered)
+        stages = _stages(*self.wrappers, have_gt=have_gt, calibration=self.calibration, ordered=self.ordered, **self.more)
         if have_gt:
             if not any(st.reads_gt for st in stages):
                 raise ValueError("ground-truth maps given to a BatchedPredictor built without surface=, confusion= or calibration=")
@@ -327,7 +343,10 @@ class BatchedPredictor:
         maps = self.map_pin[s][:hi - lo].numpy().copy() if self.want_maps else None
         fields = {st.field: st.to_host(hi - lo, self.out_pin[st.field][s], lo) for st in stages}
         calibration, ordered = fields.pop("calibration", None), fields.pop("ordered", None)
+        components = fields.pop("components", None)
         batch = Batch(lo, hi, labels, maps, **fields)
+        if components is not None:
+            batch = batch.with_components(components)
         if calibration is not None:
             batch = batch.with_calibration(calibration)
         if ordered is not None:
@@ -340,20 +359,21 @@ class BatchedPredictor:
 def host_batches(model, images: np.ndarray, batch: int, *, gt_u8: Optional[np.ndarray] = None, surface=None,
                  minpath=None, confusion=None, soft_maps: bool = False, mc_samples: int = 0, mc_step0: int = 0,
                  pad_mode: Optional[str] = None, pad_value=0, tta=None, calibration_bins: int = 0,
-                 temperature: float = 1.0, ordered=None) -> Iterator[Batch]:
+                 temperature: float = 1.0, ordered=None, components=None) -> Iterator[Batch]:
     """The same records for images that are not uint8: x / 255 on the host (``Model.predict_labels``), one synchronous
     forward per batch, no overlap.  ``surface`` / ``minpath`` / ``confusion`` / ``soft_maps`` / ``mc_samples`` /
     ``mc_step0`` / ``tta`` as in ``BatchedPredictor``; each stage writes its own output buffers.  ``pad_mode`` / ``pad_value`` (in raw
     counts) go to ``Model.predict_labels``, which pads and crops on the device.  ``calibration_bins`` / ``temperature``: refused
     here -- calibration exists for raw uint8 images only.  ``ordered`` (anything true, an ``OrderedDecode`` included):
     ``Model.predict_labels`` runs the ordered decode on the batch's probabilities while they are on the device, and
-    ``Batch.ordered`` is filled as by ``BatchedPredictor``."""
+    ``Batch.ordered`` is filled as by ``BatchedPredictor``.  ``components`` (a ``Components``): a stage like the others, on the
+    uploaded class maps; ``Batch.components`` likewise."""
     if check_bins(calibration_bins) or check_temperature(temperature) != 1.0:
         raise ValueError("calibration_bins / temperature need raw uint8 images: the path for other dtypes (host_batches) has no "
                          "calibration stage")
     pad_mode, pad_value = check_pad_mode(pad_mode, pad_value)
     tta = check_tta(tta, mc_samples)
-    stages = _stages(surface, confusion, minpath, have_gt=gt_u8 is not None)
+    stages = _stages(surface, confusion, minpath, have_gt=gt_u8 is not None, **({"components": components} if components is not None else {}))
     on_labels, on_maps = any(not st.on_maps for st in stages), any(st.on_maps for st in stages)
 
     def upload(a):
@@ -366,13 +386,17 @@ def host_batches(model, images: np.ndarray, batch: int, *, gt_u8: Optional[np.nd
                                                   soft_maps=soft_maps, mc_samples=mc_samples, mc_step0=mc_step0,
                                                   pad_mode=pad_mode, pad_value=pad_value, tta=tta, **more)
         decoded = unc.pop() if ordered else None
-        lab_dev, gt_dev = (upload(labels.astype(np.uint8)), upload(gt_u8[lo:hi])) if on_labels else (None, None)
+        lab_dev = upload(labels.astype(np.uint8)) if on_labels else None
+        gt_dev = upload(gt_u8[lo:hi]) if on_labels and gt_u8 is not None else None
         maps_dev = upload(maps) if on_maps else None
         fields = {}
         for st in stages:
             st.launch(hi - lo, st.run.outs, lab_dev, gt_dev, maps_dev)
             fields[st.field] = st.to_host(hi - lo, st.run.outs, lo)
+        cleaned = fields.pop("components", None)
         record = Batch(lo, hi, labels, maps, **fields)
+        if cleaned is not None:
+            record = record.with_components(cleaned)
         if decoded is not None:
             record = record.with_ordered(decoded)
         yield record.with_uncertainty(*unc) if unc else record
@@ -421,6 +445,12 @@ class InferenceRun:
     It needs 2..16 classes and a height of at most 4096, works for every image dtype and without ``gt``, and does not depend on
     ``soft_maps``, ``gs_device`` or ``confusion``.
 
+    ``components`` (a ``ComponentRule`` or a dict of its keywords; None: off): a ``Components`` stage fills ``Batch.components``
+    from the arg-max maps the chain yields -- the mean prediction's under ``mc_samples`` / ``tta``, the cropped ones under
+    ``pad_mode``, the same under any ``temperature``.  It works for every image dtype and without ``gt``
+    and changes no output of ``ordered_decode``, ``gs_device``, ``confusion`` or ``calibration_bins``; the searches keep reading
+    the arg-max maps.  A rule that does not fit ``num_classes`` is a ``ValueError``.
+
     ``batches`` replaces the model by a ready source of records (tests of the host side: no device is touched)."""
 
     def __init__(self, model, images: np.ndarray, batch: int, num_classes: int, *, gt: Optional[np.ndarray] = None,
@@ -428,8 +458,12 @@ class InferenceRun:
                  gs_workers: Optional[int] = None, batches: Optional[Iterable[Batch]] = None, surface: bool = True,
                  confusion: bool = False, soft_maps: bool = False, mc_samples: int = 0, mc_step0: int = 0,
                  pad_mode: Optional[str] = None, pad_value=0, ignore_label: Optional[int] = None, tta=None,
-                 calibration_bins: int = 0, temperature: float = 1.0, ordered_decode: bool = False):
+                 calibration_bins: int = 0, temperature: float = 1.0, ordered_decode: bool = False, components=None):
         pad_mode, pad_value = check_pad_mode(pad_mode, pad_value)
+        rule = ComponentRule.coerce(components)
+        if rule is not None:
+            rule.check(num_classes)
+            check_components(num_classes, images.shape[1], images.shape[2])
         self.tta = tta = check_tta(tta, mc_samples)
         if ordered_decode:
             check_ordered(num_classes, images.shape[1])
@@ -445,6 +479,7 @@ class InferenceRun:
         self.pool = self.host_ties = None
         self._gs = self._gs_geom = None                   # gs_labels' own device buffers: made by its first call
         self._png = None                                  # render_pngs' own device and pinned buffers, likewise
+        self._cc_surface = None                           # label_surface's own wrapper, likewise
         self.ties, self._batches = gs_device_ties, (() if batches is None else batches)
         if n == 0:
             return
@@ -471,6 +506,7 @@ class InferenceRun:
             minpath = DeviceMinPath(bs, C - 1, H, W, gsgrad, dev) if self.host_ties is not None else None
             surface = SurfaceDistances(bs, H, W, C, dev, ignore_label=ignore_label) if gt_u8 is not None and surface else None
             confusion = ConfusionCounts(bs, H, W, C, dev, ignore_label=ignore_label) if gt_u8 is not None and confusion else None
+            more = {"components": Components(bs, H, W, C, rule, dev)} if rule is not None else {}      # (only passed when set)
             if images.dtype != np.uint8:
                 if surface is None and confusion is None:
                     gt_u8 = None
@@ -478,7 +514,7 @@ class InferenceRun:
                                              confusion=confusion, soft_maps=soft_maps, mc_samples=mc_samples,
                                              mc_step0=mc_step0, pad_mode=pad_mode, pad_value=pad_value, tta=tta,
                                              calibration_bins=calibration_bins, temperature=temperature,
-                                             **({"ordered": True} if ordered_decode else {}))
+                                             **({"ordered": True} if ordered_decode else {}), **more)
             else:
                 ordered = OrderedDecode(bs, H, W, C, dev) if ordered_decode else None
                 calibration = (CalibrationCounts(bs, H, W, C, dev, calibration_bins, ignore_label=ignore_label)
@@ -490,7 +526,7 @@ class InferenceRun:
                                              soft_maps=soft_maps, mc_samples=mc_samples, mc_step0=mc_step0,
                                              hw=(H, W), pad_mode=pad_mode, pad_value=pad_value, tta=tta,
                                              calibration=calibration, temperature=temperature,
-                                             **({"ordered": ordered} if ordered is not None else {}))
+                                             **({"ordered": ordered} if ordered is not None else {}), **more)
                 self._batches = predictor.run(images, gt_u8)
         except BaseException:
             self.close()
@@ -569,6 +605,41 @@ class InferenceRun:
         pred = torch.from_numpy(np.ascontiguousarray(batch.ordered[0])).to(dev)
         gt_dev = torch.from_numpy(np.ascontiguousarray(gt, dtype=np.uint8)).to(dev)
         return counts.to_host(counts(pred, gt_dev), batch.lo)
+
+    def label_counts(self, labels: np.ndarray, gt: np.ndarray, first_image: int = 0) -> np.ndarray:
+        """The (n, C, C) uint32 confusion counts of class maps ``labels`` (n,H,W) uint8 -- the cleaned maps of
+        ``Batch.components`` -- against the ground-truth class maps ``gt`` (n,H,W), as ``ordered_counts`` forms them.  Waits for
+        the device."""
+        if self._gs_geom is None:
+            raise RuntimeError("label_counts needs the device: this run was built over injected batches")
+        counts, dev = self._delineation_labels().counts, self._gs_geom[4]
+        pred = torch.from_numpy(np.ascontiguousarray(labels, dtype=np.uint8)).to(dev)
+        gt_dev = torch.from_numpy(np.ascontiguousarray(gt, dtype=np.uint8)).to(dev)
+        return counts.to_host(counts(pred, gt_dev), first_image)
+
+    def label_surface(self, labels: np.ndarray, gt: np.ndarray) -> np.ndarray:
+        """The (n, C-1, 6) float64 surface-distance rows of class maps ``labels`` (n,H,W) uint8 -- the cleaned maps of
+        ``Batch.components`` -- against ``gt`` (n,H,W), by the kernels and with the ``ignore_label`` of the run's ``surface``
+        stage.  Waits for the device."""
+        if self._gs_geom is None:
+            raise RuntimeError("label_surface needs the device: this run was built over injected batches")
+        bs, H, W, C, dev = self._gs_geom
+        if self._cc_surface is None:
+            self._cc_surface = SurfaceDistances(bs, H, W, C, dev, ignore_label=self.ignore_label)
+        pred = torch.from_numpy(np.ascontiguousarray(labels, dtype=np.uint8)).to(dev)
+        gt_dev = torch.from_numpy(np.ascontiguousarray(gt, dtype=np.uint8)).to(dev)
+        return self._cc_surface.to_host(self._cc_surface(pred, gt_dev))
+
+    def render_labels(self, labels: np.ndarray) -> np.ndarray:
+        """Class maps (n,H,W) uint8 -> (n,H,W,4) RGBA on the host through the region colours, as the ``pred`` picture of
+        ``render_pngs`` (the cleaned maps of ``Batch.components``).  Waits for the device."""
+        if self._gs_geom is None:
+            raise RuntimeError("render_labels needs the device: this run was built over injected batches")
+        from ..common import plotting
+        bs, H, W, C, dev = self._gs_geom
+        if self._png is None:
+            self._png = PngRenderer(bs, H, W, dev)
+        return self._png.render(np.ascontiguousarray(labels, dtype=np.uint8), palette=plotting.region_palette(C))
 
     def render_ordered(self, batch: Batch, images: np.ndarray, col_range=None) -> dict:
         """The two pictures of a batch's ordered decode as host RGBA arrays (n,H,W,4) uint8 (``evaluation.render.OD_PNG_NAMES``

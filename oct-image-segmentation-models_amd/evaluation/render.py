@@ -124,6 +124,8 @@ PREDICTION_PNG_NAMES = {"pred": "segmentation_map.png", "raw": "raw_image.png",
 
 # the ordered decode's pictures (no counterpart in the reference), in evaluate_model and predict alike
 OD_PNG_NAMES = {"od_map": "od_predicted_segmentation_map.png", "od_bounds": "od_predicted_boundaries_overlay_plot.png"}
+# the picture of the component-cleaned class map (likewise)
+CC_PNG_NAMES = {"cc_map": "cc_predicted_segmentation_map.png"}
 
 
 IGNORED_RGB = (128, 128, 128)    # ground-truth pixels that carry the evaluation's ignore_label

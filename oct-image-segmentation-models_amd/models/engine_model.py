@@ -601,6 +601,32 @@ class Model:
             labels[lo:hi], rows[lo:hi] = lab.cpu().numpy(), r.cpu().numpy().view(np.uint16)
         return labels, rows
 
+    def predict_components(self, x, rule, batch_size: Optional[int] = None):
+        """Island removal and component counts of the arg-max class maps, on the device (``oct_components`` /
+        ``oct_component_filter``).  Input as for ``predict``; ``rule`` is an
+        ``evaluation.components.ComponentRule`` or a dict of its keywords.  Returns ``(labels (n,H,W) uint8, stats (n,C,2) uint32,
+        removed (n,C) uint32)``: the cleaned maps, per class (components, pixels of the largest one) of the ARG-MAX maps, and the
+        removed pixels per class.  Padding as for ``predict_mc``, from the model's ``pad_mode`` / ``pad_value`` attributes: the
+        arg-max maps are cropped in front of the labelling."""
+        from ..evaluation.components import ComponentRule, Components, check_components
+        x = np.asarray(x)
+        if x.dtype != np.uint8:
+            x = np.ascontiguousarray(x, dtype=np.float32)
+        C = int(self.config["num_classes"])
+        rule = ComponentRule.coerce(rule, "predict_components")
+        if rule is None:
+            raise ValueError("predict_components: needs a rule")
+        rule.check(C, "predict_components")
+        check_components(C, x.shape[1], x.shape[2], "predict_components")
+        n, bs = x.shape[0], int(batch_size or min(x.shape[0], 32))
+        labels, stats, removed = np.empty(x.shape[:3], np.uint8), np.empty((n, C, 2), np.uint32), np.empty((n, C), np.uint32)
+        stage = None
+        for lo, hi, eng, maps in self._inference_batches(x, bs, self._pad_options(None, 0), want_probs=False, want_argmax=True):
+            if stage is None:
+                stage = Components(bs, x.shape[1], x.shape[2], C, rule, eng.device)
+            labels[lo:hi], stats[lo:hi], removed[lo:hi] = stage.to_host(*stage(maps["argmax"].reshape(hi - lo, *x.shape[1:3])))
+        return labels, stats, removed
+
     def predict_labels(self, x_u8: np.ndarray, batch_size: int = 32, want_maps: bool = False, bg_ilm: bool = True,
                        bg_csi: bool = False, soft_maps: bool = False, mc_samples: int = 0, mc_step0: int = 0,
                        pad_mode: Optional[str] = None, pad_value=0, tta=None, ordered: bool = False):

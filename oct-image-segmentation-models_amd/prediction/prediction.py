@@ -17,7 +17,7 @@ from .. import parallel
 from ..common import h5io, utils
 from ..evaluation.pipeline import InferenceRun
 from ..evaluation.ordered import layer_thickness
-from ..evaluation.render import OD_PNG_NAMES, PREDICTION_PNG_NAMES, write_pictures
+from ..evaluation.render import CC_PNG_NAMES, OD_PNG_NAMES, PREDICTION_PNG_NAMES, write_pictures
 from ..min_path_processing import graph_search  # noqa: F401  (re-exported: callers build graph structures through it)
 from ..models import get_model_class
 from .prediction_parameters import PredictionParams
@@ -72,6 +72,7 @@ def predict(predict_params: PredictionParams) -> List[PredictionOutput]:
     png_plots = bool(getattr(predict_params, "png_plots", False)) and predict_params.save_params.png_images is True
     mc_samples = int(getattr(predict_params, "mc_samples", 0))
     ordered_decode = bool(getattr(predict_params, "ordered_decode", False))
+    components = getattr(predict_params, "components", None)
     # the device pipeline of evaluate_model (evaluation/pipeline.py::InferenceRun), without ground truth
     with InferenceRun(predict_params.loaded_model, images[lo:hi], predict_params.batch_size, num_classes,
                       graph_search=predict_params.graph_search, gs_device=predict_params.gs_device,
@@ -81,7 +82,8 @@ def predict(predict_params: PredictionParams) -> List[PredictionOutput]:
                       pad_mode=getattr(predict_params, "pad_mode", None),
                       pad_value=getattr(predict_params, "pad_value", 0), tta=getattr(predict_params, "tta", None),
                       temperature=getattr(predict_params, "temperature", 1.0),
-                      **({"ordered_decode": True} if ordered_decode else {})) as run:
+                      **({"ordered_decode": True} if ordered_decode else {}),
+                      **({"components": components} if components is not None else {})) as run:
         t0 = time.time()
         for batch in run:
             b0, b1 = lo + batch.lo, lo + batch.hi
@@ -103,6 +105,7 @@ def predict(predict_params: PredictionParams) -> List[PredictionOutput]:
             if png_plots and ordered_decode:
                 od_pictures = run.render_ordered(batch, images[b0:b1],
                                                  col_range=(predict_params.col_error_range[0], predict_params.col_error_range[-1]))
+            cc_pictures = {"cc_map": run.render_labels(batch.components[0])} if png_plots and components is not None else None
             for i in range(b0, b1):
                 predict_image, image_name, image_output_dir = images[i], dataset.image_names[i], Path(dataset.image_output_dirs[i])
                 os.makedirs(image_output_dir, exist_ok=True)
@@ -122,7 +125,11 @@ def predict(predict_params: PredictionParams) -> List[PredictionOutput]:
                 save_image_prediction_results(predict_params, predict_image, image_name, predicted_labels, categorical_pred,
                                               boundary_maps, predict_time, convert_time, image_output_dir,
                                               entropy=entropy, mutual_info=mutual_info,
-                                              ordered=None if batch.ordered is None else tuple(t[i - b0] for t in batch.ordered))
+                                              ordered=None if batch.ordered is None else tuple(t[i - b0] for t in batch.ordered),
+                                              **({"components": tuple(t[i - b0] for t in batch.components)}
+                                                 if batch.components is not None else {}))
+                if cc_pictures is not None:
+                    write_pictures(image_output_dir, cc_pictures, i - b0, CC_PNG_NAMES)
                 if od_pictures is not None:
                     write_pictures(image_output_dir, od_pictures, i - b0, OD_PNG_NAMES)
                 gs_pred_segs = None
@@ -167,16 +174,20 @@ def save_predict_config_file(predict_params: PredictionParams):
         attrs["temperature"] = np.array(float(predict_params.temperature))      # likewise
     if getattr(predict_params, "ordered_decode", False):
         attrs["ordered_decode"] = np.array(True)      # likewise
+    if getattr(predict_params, "components", None) is not None:
+        attrs["components"] = np.array(repr(predict_params.components), dtype="S1000")      # likewise
     h5io.save(predict_params.config_output_dir / Path("prediction_params.hdf5"), {}, attrs)
 
 
 def save_image_prediction_results(pred_params, predict_image, image_name, predicted_labels, categorical_pred,
                                   boundary_maps, predict_time, convert_time, output_dir, entropy=None, mutual_info=None,
-                                  ordered=None):
+                                  ordered=None, components=None):
     """``entropy`` / ``mutual_info``: the (H,W) maps of a Monte-Carlo dropout or test-time-augmented prediction, stored
     (with the sample count, or the views) only when given: without them the file is what it always was.  ``ordered``: the
     image's ``(labels (H,W), rows (C-1,W), score (W))`` of ``Batch.ordered``, likewise: the file gains ``od_predicted_labels``,
-    ``od_pred_segs`` and (from 3 classes) ``layer_thickness``, and the two od_ CSV files are written."""
+    ``od_pred_segs`` and (from 3 classes) ``layer_thickness``, and the two od_ CSV files are written.  ``components``: the image's
+    ``(clean_labels (H,W), stats (C,2), removed (C))`` of ``Batch.components``, likewise: the file gains ``cc_predicted_labels``,
+    ``component_count``, ``largest_component_pixels`` and ``removed_pixels``."""
     ds = {}
     if pred_params.save_params.categorical_pred is True:
         ds["categorical_pred"] = categorical_pred.astype("uint8")
@@ -204,6 +215,11 @@ def save_image_prediction_results(pred_params, predict_image, image_name, predic
         thickness, _ = layer_thickness(od_rows)
         if thickness is not None:
             ds["layer_thickness"] = thickness
+    if components is not None:
+        cc_labels, stats, removed = components
+        ds["cc_predicted_labels"] = cc_labels.astype("uint8")
+        ds["component_count"], ds["largest_component_pixels"] = stats[:, 0].astype("uint32"), stats[:, 1].astype("uint32")
+        ds["removed_pixels"] = removed.astype("uint32")
     h5io.save(output_dir / Path("prediction_info.hdf5"), ds, attrs)
 
 

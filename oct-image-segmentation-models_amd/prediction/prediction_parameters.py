@@ -27,7 +27,12 @@ class PredictionParams:
                  gs_device_ties: str = "host", gs_workers: Union[int, None] = None, gs_labels_device: bool = False,
                  binarize: bool = True, png_plots: bool = False, mc_samples: int = 0, mc_step0: int = 0,
                  pad_mode: Union[str, None] = None, pad_value=0, tta=None, temperature: float = 1.0,
-                 ordered_decode: bool = False) -> None:
+                 ordered_decode: bool = False, components=None) -> None:
+        # extension, as EvaluationParameters.components (a ComponentRule or a dict of its keywords): prediction_info.hdf5 gains
+        # cc_predicted_labels, component_count, largest_component_pixels and removed_pixels; with png_plots
+        # cc_predicted_segmentation_map.png is written.  None: nothing is launched, every file as it was
+        from ..evaluation.components import ComponentRule
+        self.components = ComponentRule.coerce(components, "components")
         # extension, as EvaluationParameters.ordered_decode: prediction_info.hdf5 gains od_predicted_labels, od_pred_segs and
         # (from 3 classes) layer_thickness, and od_boundaries.csv / od_predicted_segmentation_map.csv are written.  False: nothing is
         # launched, every file as it was
@@ -64,6 +69,8 @@ class PredictionParams:
         if self.ordered_decode:
             from ..evaluation.ordered import check_ordered
             check_ordered(self.num_classes, 1)
+        if self.components is not None:
+            self.components.check(self.num_classes)
         self.config_output_dir = Path(config_output_dir)
         self.save_params = save_params
         self.graph_search = graph_search
