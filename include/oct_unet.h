@@ -38,6 +38,7 @@
  *   oct_pad_batch / oct_crop_batch     (none: Keras raises on a size that is no multiple of 2^pool_layers, in the skip concatenation)
  *   oct_warp_batch                     (none at training time; the per-column np.roll of roll_image_offset /
  *                                      flatten_image_boundary        dataset_construction.py is its dataset-preparation kin)
+ *   oct_elastic_batch                  (none: the smooth random elastic deformation of the U-Net paper, a training augmentation)
  *   oct_calibration_counts / oct_temperature_apply / oct_temperature_nll  (none: reliability counts, ECE / NLL / Brier and
  *                                      temperature scaling of the softmax output, Guo et al. 2017)
  *   oct_ordered_decode                 (none: the best class map per column whose class index never decreases with depth)
@@ -524,6 +525,56 @@ typedef struct oct_warp_op {     /* one per sample of the batch, 40 bytes, in DE
 int oct_warp_batch(const unsigned char* x_u8_dev, const unsigned char* labels_dev, const oct_warp_op* ops_dev,
                    int B, int H, int W, int C,
                    unsigned char* x_out_dev, unsigned char* labels_out_dev, oct_stream_t stream);
+
+/* ---- elastic deformation on device: (B,H,W,C) u8 images -> u8 images sampled through a smooth random displacement field;
+ * (B,H,W) u8 labels moved alongside.  The U-Net paper's augmentation (Ronneberger et al. 2015, section 3.1); the reference has
+ * no counterpart.  A stage of its own, in FRONT of oct_warp_batch: a sample may be deformed whatever warp, flip or noise it
+ * then gets.  Integer arithmetic only, so the kernel, the numpy restatement (common/augmentation.py elastic_reference) and
+ * the host generator give the same bytes.  Stand-alone: no handle, no allocation, one asynchronous launch on `stream`,
+ * graph-capturable.  Per sample b, op = ops_dev[b]; `/` below is FLOOR division, `>>` an arithmetic shift, all intermediates
+ * are 64-bit signed integers; the border rule is oct_warp_batch's.
+ *   kind 0 none: copy.  kind 1 elastic, S = spacing:
+ *   control grid: point (i, j), i = 0..(H-1)/S + 3, j = 0..(W-1)/S + 3, has the displacement (dx, dy) in 1/256 pixel
+ *       r0..r3 = philox4x32_10(counter = (j, i, 0, 0x454C4153), key = (seed_lo, seed_hi))     (oct_augment_batch's generator)
+ *       dx = (int)(((uint64)r0 (2 amp_x + 1)) >> 32) - amp_x,  dy likewise from r1 and amp_y: uniform integers in [-amp, amp].
+ *   weights: pixel x has the cell cx = x / S and the offset k = x % S, and takes the uniform cubic B-spline of control columns
+ *     cx..cx+3 with the numerators over 6 S^3
+ *       b0 = (S-k)^3,  b1 = 3k^3 - 6Sk^2 + 4S^3,  b2 = -3k^3 + 3Sk^2 + 3S^2 k + S^3,  b3 = k^3     (all >= 0, sum 6 S^3);
+ *     row y likewise with cy = y / S.
+ *   displacement in 1/256 pixel, for dx and dy each:
+ *       N = sum_a sum_b by_a bx_b d(cy + a, cx + b),   disp = (N + 18 S^6) / (36 S^6)              |disp| <= amp
+ *   sampling: sx = 256 x + disp_x, sy = 256 y + disp_y (source position in 1/256 pixel)
+ *     image: ix = sx >> 8, fx = sx & 255, iy, fy likewise; taps p00 = (ix, iy), p01 = (ix+1, iy), p10 = (ix, iy+1),
+ *       p11 = (ix+1, iy+1), each through the border rule;
+ *       out = ((256-fx)(256-fy) p00 + fx (256-fy) p01 + (256-fx) fy p10 + fx fy p11 + 32768) >> 16
+ *     labels: the nearest pixel ((sx + 128) >> 8, (sy + 128) >> 8) through the border rule.
+ *     amp_x = amp_y = 0 is the identity, byte for byte; amp_x = 0 is the axial-only deformation (pixels stay in their A-scan).
+ *   Parameter ranges (OCT_ELASTIC_*): H, W <= 16384, S in 2..128, amp_x, amp_y in 0..8192 (32 pixels).  Then
+ *     |N| <= 36 S^6 amp <= 36 2^42 2^13 < 2^61: no intermediate leaves int64, and every source index fits an int32.  The ranges
+ *     are only visible on the device: REFUSE anything outside them on the host, before upload (common/augmentation.py
+ *     check_elastic_ops).  A kind outside 0..1, or a border, spacing or amplitude outside its range, is TREATED AS kind 0 (no
+ *     device-side flag).
+ *   labels_dev == NULL or labels_out_dev == NULL: no labels written.  Nothing depends on b, B or the launch geometry.
+ * Errors (negative, nothing launched): null x_u8_dev / ops_dev / x_out_dev, non-positive sizes, B > 65535, H or W >
+ * 16384, H*W*C >= 2^31, labels_out_dev without labels_dev, an output range overlapping an input range or the other output
+ * (the stage gathers: it cannot run in place). */
+#define OCT_ELASTIC_MAX_DIM     16384
+#define OCT_ELASTIC_MIN_SPACING 2
+#define OCT_ELASTIC_MAX_SPACING 128
+#define OCT_ELASTIC_MAX_AMP     8192     /* amp_x, amp_y: 32 pixels */
+typedef struct oct_elastic_op {  /* one per sample of the batch, 40 bytes, in DEVICE memory */
+    int kind;                    /* 0 none (the sample is copied through), 1 elastic */
+    int border;                  /* 0 replicate, 1 wrap, 2 constant (oct_warp_batch's rule) */
+    int spacing;                 /* S: control-point spacing in pixels, 2..128 */
+    int amp_x, amp_y;            /* bound of the control displacements in 1/256 pixel, 0..8192 */
+    unsigned seed_lo, seed_hi;   /* Philox key of this sample's field */
+    int fill;                    /* image value 0..255 of a tap outside the image (border 2) */
+    int fill_label;              /* label value 0..255 outside the image (border 2) */
+    int reserved;                /* 0 */
+} oct_elastic_op;
+int oct_elastic_batch(const unsigned char* x_u8_dev, const unsigned char* labels_dev, const oct_elastic_op* ops_dev,
+                      int B, int H, int W, int C,
+                      unsigned char* x_out_dev, unsigned char* labels_out_dev, oct_stream_t stream);
 
 /* ---- pad and crop on device: scans whose size is no multiple of 2^pool_layers ----
  * oct_pad_batch places a (B,H,W,ch) batch -- uint8 (is_u8) or float32 -- at (top, left) of a (B,Hp,Wp,ch) batch of the same

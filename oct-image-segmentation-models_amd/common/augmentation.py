@@ -493,3 +493,221 @@ def _warp_aug(fn, image, mask, aug_args):
         else:
             moved[outside] = fill
     return out, moved
+
+
+# ---- elastic deformation: descriptors, parameter draws and the numpy restatement of oct_elastic_batch (include/oct_unet.h) ----
+# A stage of its own in FRONT of the warps: applied with probability p to every sample, whatever list entry the sample then
+# gets.  One descriptor per sample; the layout is the C struct oct_elastic_op (40 bytes).  Integer arithmetic throughout.
+ELASTIC_OP_DTYPE = np.dtype([("kind", "<i4"), ("border", "<i4"), ("spacing", "<i4"), ("amp_x", "<i4"), ("amp_y", "<i4"),
+                             ("seed_lo", "<u4"), ("seed_hi", "<u4"), ("fill", "<i4"), ("fill_label", "<i4"), ("reserved", "<i4")])
+ELASTIC_NONE, ELASTIC_ON = range(2)
+# the ranges inside which no intermediate of the definition leaves int64 (OCT_ELASTIC_MAX_* of include/oct_unet.h)
+ELASTIC_MAX_DIM, ELASTIC_MIN_SPACING, ELASTIC_MAX_SPACING, ELASTIC_MAX_AMP = 16384, 2, 128, 8192
+ELASTIC_TAG = 0x454C4153    # "ELAS": the last counter word of a control point's Philox block
+ELASTIC_DRAWS = 3           # uniform numbers a sample takes from the generator's elastic stream, deformed or not
+
+
+def check_elastic_ops(ops, H=None, W=None) -> None:
+    """Refuse (``ValueError``) descriptors or image sizes outside the ranges ``oct_elastic_batch`` is defined for: the
+    device cannot report them."""
+    ops = np.asarray(ops)
+    if ops.dtype != ELASTIC_OP_DTYPE:
+        raise TypeError("elastic descriptors must be an ELASTIC_OP_DTYPE array")
+    for name, v in (("H", H), ("W", W)):
+        if v is not None and not 1 <= int(v) <= ELASTIC_MAX_DIM:
+            raise ValueError(f"elastic: {name} = {v} outside 1..{ELASTIC_MAX_DIM}")
+    if ops.size == 0:
+        return
+    for name, hi in (("kind", ELASTIC_ON), ("border", WARP_CONSTANT), ("fill", 255), ("fill_label", 255), ("reserved", 0)):
+        if ops[name].min() < 0 or ops[name].max() > hi:
+            raise ValueError(f"elastic: descriptor {name} outside 0..{hi}")
+    on = ops[ops["kind"] == ELASTIC_ON]
+    if on.size and (on["spacing"].min() < ELASTIC_MIN_SPACING or on["spacing"].max() > ELASTIC_MAX_SPACING):
+        raise ValueError(f"elastic: descriptor spacing outside {ELASTIC_MIN_SPACING}..{ELASTIC_MAX_SPACING}")
+    for name in ("amp_x", "amp_y"):
+        if on.size and (on[name].min() < 0 or on[name].max() > ELASTIC_MAX_AMP):
+            raise ValueError(f"elastic: descriptor {name} outside 0..{ELASTIC_MAX_AMP} (1/256 pixel)")
+
+
+def elastic_spec(args) -> dict:
+    """The validated ``elastic`` keyword of the generators and of ``TrainingParams`` as a dict: ``p`` (probability, 0..1),
+    ``spacing`` (control-point spacing in pixels, an integer in 2..128), ``amp_x`` / ``amp_y`` (``max_displacement`` in pixels,
+    one number or ``(dx, dy)``, each 0..32, as rint(256 v)), ``border`` (the warps' names, default "replicate") and ``fill`` /
+    ``fill_label``.  ``ValueError`` for anything else."""
+    if not isinstance(args, dict):
+        raise ValueError(f"elastic must be a dict of p, spacing, max_displacement[, border, fill, fill_label], got {args!r}")
+    known = {"p", "spacing", "max_displacement", "border", "fill", "fill_label"}
+    if set(args) - known:
+        raise ValueError(f"elastic: unknown keys {sorted(set(args) - known)}")
+    for key in ("p", "spacing", "max_displacement"):
+        if key not in args:
+            raise ValueError(f"elastic: {key} is required")
+    p = float(args["p"])
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"elastic: p must be within 0..1, got {args['p']!r}")
+    S = args["spacing"]
+    if isinstance(S, bool) or int(S) != S or not ELASTIC_MIN_SPACING <= int(S) <= ELASTIC_MAX_SPACING:
+        raise ValueError(f"elastic: spacing must be an integer in {ELASTIC_MIN_SPACING}..{ELASTIC_MAX_SPACING}, got {S!r}")
+    amp = args["max_displacement"]
+    dx, dy = (float(amp), float(amp)) if np.isscalar(amp) else _pair(args, "max_displacement", None)
+    px = ELASTIC_MAX_AMP / 256.0
+    if not (0.0 <= dx <= px and 0.0 <= dy <= px):
+        raise ValueError(f"elastic: max_displacement must be within 0..{px} pixels, got {amp!r}")
+    border = args.get("border", "replicate")
+    if border not in WARP_BORDERS:
+        raise ValueError(f"elastic: border must be one of {sorted(WARP_BORDERS)}, got {border!r}")
+    spec = {"p": p, "spacing": int(S), "amp_x": int(np.rint(256.0 * dx)), "amp_y": int(np.rint(256.0 * dy)),
+            "border": WARP_BORDERS[border]}
+    for key in ("fill", "fill_label"):
+        v = args.get(key, 0)
+        if int(v) != v or not 0 <= int(v) <= 255:
+            raise ValueError(f"elastic: {key} must be an integer in 0..255, got {v!r}")
+        spec[key] = int(v)
+    return spec
+
+
+def draw_elastic_ops(spec, u):
+    """The descriptors of ``len(u)`` samples from their ``ELASTIC_DRAWS`` uniform numbers ``u[i]`` in [0, 1): sample i is
+    deformed iff ``u[i, 0] < p``; its field's key is ``(floor(u[i, 1] 2^32), floor(u[i, 2] 2^32))``.  A sample that is not
+    deformed gets the all-zero descriptor.  ``spec``: what ``elastic_spec`` returns."""
+    u = np.asarray(u, dtype=np.float64).reshape(-1, ELASTIC_DRAWS)
+    ops = np.zeros(u.shape[0], dtype=ELASTIC_OP_DTYPE)
+    sel = np.flatnonzero(u[:, 0] < spec["p"])
+    ops["kind"][sel] = ELASTIC_ON
+    for name in ("border", "spacing", "amp_x", "amp_y", "fill", "fill_label"):
+        ops[name][sel] = spec[name]
+    ops["seed_lo"][sel] = np.floor(u[sel, 1] * 4294967296.0).astype(np.uint64)
+    ops["seed_hi"][sel] = np.floor(u[sel, 2] * 4294967296.0).astype(np.uint64)
+    check_elastic_ops(ops)
+    return ops
+
+
+def _elastic_kind(op):
+    ok = (int(op["kind"]) == ELASTIC_ON and 0 <= int(op["border"]) <= WARP_CONSTANT
+          and ELASTIC_MIN_SPACING <= int(op["spacing"]) <= ELASTIC_MAX_SPACING
+          and 0 <= int(op["amp_x"]) <= ELASTIC_MAX_AMP and 0 <= int(op["amp_y"]) <= ELASTIC_MAX_AMP)
+    return ELASTIC_ON if ok else ELASTIC_NONE
+
+
+def elastic_weights(n: int, S: int):
+    """``(cell, b)`` of positions 0..n-1 on one axis: the cell ``p // S`` (int64 (n,)) and the four uniform cubic B-spline
+    weight numerators over 6 S^3 at offset ``k = p % S`` (int64 (n, 4)), for control points cell..cell+3."""
+    p = np.arange(int(n), dtype=np.int64)
+    S = int(S)
+    k = p % S
+    b = np.stack([(S - k) ** 3, 3 * k ** 3 - 6 * S * k ** 2 + 4 * S ** 3, -3 * k ** 3 + 3 * S * k ** 2 + 3 * S * S * k + S ** 3,
+                  k ** 3], axis=1)
+    return p // S, b
+
+
+def elastic_control(H: int, W: int, op):
+    """The control displacements ``(dx, dy)`` of descriptor ``op`` in 1/256 pixel: int64 arrays over control points
+    i = 0..(H-1)//S + 3, j = 0..(W-1)//S + 3, uniform integers in [-amp, amp] from the point's own Philox block."""
+    S = int(op["spacing"])
+    ny, nx = (int(H) - 1) // S + 4, (int(W) - 1) // S + 4
+    ctr = np.zeros((ny, nx, 4), dtype=np.uint64)
+    ctr[..., 0], ctr[..., 1], ctr[..., 3] = np.arange(nx, dtype=np.uint64)[None, :], np.arange(ny, dtype=np.uint64)[:, None], ELASTIC_TAG
+    r = philox4x32_10(ctr, np.array([int(op["seed_lo"]), int(op["seed_hi"])], dtype=np.uint64)).astype(np.uint64)
+    ax, ay = int(op["amp_x"]), int(op["amp_y"])
+    dx = ((r[..., 0] * np.uint64(2 * ax + 1)) >> np.uint64(32)).astype(np.int64) - ax
+    dy = ((r[..., 1] * np.uint64(2 * ay + 1)) >> np.uint64(32)).astype(np.int64) - ay
+    return dx, dy
+
+
+def elastic_displacement(H: int, W: int, op, control=None):
+    """The displacement fields ``(disp_x, disp_y)`` of descriptor ``op`` in 1/256 pixel, int64 (H, W):
+    floor((N + 18 S^6) / (36 S^6)) with N the B-spline sum over the 4 x 4 control points of the pixel's cell.  ``control``:
+    a caller-given ``(dx, dy)`` pair of control grids in place of ``elastic_control`` (tests)."""
+    S = int(op["spacing"])
+    dx, dy = elastic_control(H, W, op) if control is None else (np.asarray(c, dtype=np.int64) for c in control)
+    (cx, bx), (cy, by) = elastic_weights(W, S), elastic_weights(H, S)
+    half = 18 * S ** 6
+    out = []
+    for d in (dx, dy):
+        # columns first: t[r, x] = sum_b bx[x, b] d[r, cx + b], then the rows of t
+        t = sum(bx[None, :, b] * d[:, cx + b] for b in range(4))
+        N = sum(by[:, a, None] * t[cy + a, :] for a in range(4))
+        out.append((N + half) // (2 * half))
+    return out[0], out[1]
+
+
+def elastic_label_index(H, W, op):
+    """Where every output pixel's LABEL comes from under descriptor ``op`` (a deformed one): ``(rows, cols, outside)`` as
+    ``warp_label_index``."""
+    disp_x, disp_y = elastic_displacement(H, W, op)
+    sx = 256 * np.arange(W, dtype=np.int64)[None, :] + disp_x
+    sy = 256 * np.arange(H, dtype=np.int64)[:, None] + disp_y
+    cols, ox = _border_index((sx + 128) >> 8, W, int(op["border"]))
+    rows, oy = _border_index((sy + 128) >> 8, H, int(op["border"]))
+    return rows, cols, _any_outside(ox, oy)
+
+
+def _elastic_image(img, op):
+    """One (H, W, C) uint8 image through the deformed descriptor ``op``: bilinear in 8-bit fractions, as the affine warp."""
+    border, fill = int(op["border"]), int(op["fill"]) & 255
+    H, W = img.shape[:2]
+    disp_x, disp_y = elastic_displacement(H, W, op)
+    sx = 256 * np.arange(W, dtype=np.int64)[None, :] + disp_x
+    sy = 256 * np.arange(H, dtype=np.int64)[:, None] + disp_y
+    ix, fx, iy, fy = sx >> 8, sx & 255, sy >> 8, sy & 255
+    acc = np.zeros(img.shape, dtype=np.int64)
+    for dy, wy in ((0, 256 - fy), (1, fy)):
+        rows, oy = _border_index(iy + dy, H, border)
+        for dx, wx in ((0, 256 - fx), (1, fx)):
+            cols, ox = _border_index(ix + dx, W, border)
+            tap = img[rows, cols].astype(np.int64)
+            outside = _any_outside(ox, oy)
+            if outside is not None:
+                tap[outside] = fill
+            acc += (wx * wy)[..., None] * tap
+    return ((acc + 32768) >> 16).astype(np.uint8)
+
+
+def elastic_reference(images_u8, labels_u8, ops):
+    """What ``oct_elastic_batch`` computes, by its definition in include/oct_unet.h, vectorised in int64: ``(images uint8
+    (B,H,W,C), labels uint8)`` (``labels_u8`` may be ``None``, (B,H,W) or (B,H,W,1)).  Refuses what the device entry point
+    is not defined for (``check_elastic_ops``)."""
+    images_u8 = np.asarray(images_u8)
+    if images_u8.dtype != np.uint8 or images_u8.ndim != 4:
+        raise TypeError("elastic_reference needs (B,H,W,C) uint8 images")
+    ops = np.asarray(ops)
+    B, H, W, _ = images_u8.shape
+    check_elastic_ops(ops, H, W)
+    if ops.shape != (B,):
+        raise ValueError("one descriptor per sample")
+    labels = None if labels_u8 is None else np.array(labels_u8, dtype=np.uint8)
+    if labels is not None and labels.size != B * H * W:
+        raise ValueError("labels must be (B,H,W) or (B,H,W,1)")
+    out = np.array(images_u8)
+    for b, op in enumerate(ops):
+        if _elastic_kind(op) == ELASTIC_NONE:
+            continue
+        out[b] = _elastic_image(images_u8[b], op)
+        if labels is not None:
+            rows, cols, outside = elastic_label_index(H, W, op)
+            moved = labels[b].reshape(H, W)[rows, cols]
+            if outside is not None:
+                moved[outside] = int(op["fill_label"]) & 255
+            labels[b] = moved.reshape(labels[b].shape)
+    return out, labels
+
+
+def elastic_sample(image_u8, mask, op):
+    """The host generator's side of the stage: one (H,W,C) uint8 image through ``elastic_reference`` and its mask -- (H,W),
+    (H,W,1) or one-hot (H,W,K), any dtype -- through the label rule, as ``_warp_aug`` moves a mask."""
+    op = np.asarray(op, dtype=ELASTIC_OP_DTYPE).reshape(1)
+    out = elastic_reference(np.asarray(image_u8)[None], None, op)[0][0]
+    if mask is None or _elastic_kind(op[0]) == ELASTIC_NONE:
+        return out, mask
+    m = np.asarray(mask)
+    rows, cols, outside = elastic_label_index(*out.shape[:2], op[0])
+    moved = m[rows, cols]
+    if outside is not None:
+        fill = int(op[0]["fill_label"])
+        if m.ndim == 3 and m.shape[-1] > 1:     # one-hot: the fill class's row
+            if fill >= m.shape[-1]:
+                raise ValueError(f"fill_label {fill} is not one of the mask's {m.shape[-1]} classes")
+            moved[outside] = np.eye(m.shape[-1], dtype=m.dtype)[fill]
+        else:
+            moved[outside] = fill
+    return out, moved

@@ -27,7 +27,14 @@ The geometric augmentations (``column_shift``, ``affine``) draw their per-sample
 generator, spawned from its seed: ``WARP_DRAWS`` uniform numbers per sample handed out, whatever augmentation the sample gets,
 in the order of the global sample walk (``aug_fly``), or one table entry per (image, augmentation) pair (pre-computed set).
 ``augmentation.draw_warp_ops`` turns them into integer descriptors for the host path (one sample at a time) and the device
-path (``next_batch_aug`` then returns a fourth array, one ``oct_warp_op`` per sample) alike, so both apply the same warp."""
+path (``next_batch_aug`` then returns a fourth array, one ``oct_warp_op`` per sample) alike, so both apply the same warp.
+
+``elastic`` (a dict, ``augmentation.elastic_spec``) puts the elastic deformation in FRONT of whatever the list gives a sample:
+every sample of an augmenting generator is deformed with probability ``p``.  Its ``ELASTIC_DRAWS`` numbers per sample come from
+a THIRD stream, ``SeedSequence(seed).spawn(2)[1]``, handed out like the warps' (global sample walk, or one table entry per
+pair); the other two streams do not notice.  The host path deforms the uint8 sample (``augmentation.elastic_sample``) before the
+list's function sees ``float32(u8) / 255``; ``next_batch_aug`` returns the descriptors as a fifth array (the fourth is then
+``None`` for a list without a warp)."""
 from __future__ import annotations
 
 import logging as log
@@ -43,7 +50,7 @@ from . import augmentation
 class BatchGenerator:
     def __init__(self, images: np.ndarray, labels: np.ndarray, batch_size: int, aug_fn_args: List[Tuple],
                  aug_mode: str, aug_probs: Tuple, aug_fly: bool, preprocess_input_fn: Callable,
-                 seed: Optional[int] = None, device_aug: bool = False):
+                 seed: Optional[int] = None, device_aug: bool = False, elastic: Optional[dict] = None):
         if aug_mode not in ("none", "one", "all"):
             log.error(f"Unrecognized augmentation mode: {aug_mode}. Allowed values: 'none', 'one', 'all'. Exiting...")
             exit(1)
@@ -81,6 +88,18 @@ class BatchGenerator:
             self._warp_rng = np.random.default_rng(np.random.SeedSequence(seed).spawn(1)[0])
             if aug_fly is False:    # pre-computed set: one parameter draw per (image, augmentation) pair, for good
                 self._warp_table = self._warp_rng.random((self.total_full_images, self.total_augs, augmentation.WARP_DRAWS))
+        self.elastic = None         # the validated ``elastic`` keyword: the stage in front of the list's augmentations
+        if elastic is not None:
+            if aug_mode == "none":
+                raise ValueError('elastic needs an augmentation mode: to deform otherwise un-augmented samples use aug_mode '
+                                 '"one" with a single "no_augmentation" entry')
+            if self.images_u8.dtype != np.uint8:
+                raise ValueError(f"elastic needs a uint8 image array, the dataset holds {self.images_u8.dtype}")
+            self.elastic = augmentation.elastic_spec(elastic)
+            # its parameter stream: a further child of the seed (the warps' is spawn(1)[0], the first child of the same parent)
+            self._elastic_rng = np.random.default_rng(np.random.SeedSequence(seed).spawn(2)[1])
+            if aug_fly is False:
+                self._elastic_table = self._elastic_rng.random((self.total_full_images, self.total_augs, augmentation.ELASTIC_DRAWS))
         if aug_mode != "none" and self.aug_ops is None:
             self._setup_host_aug()
         self.handle_epoch_end()
@@ -98,8 +117,19 @@ class BatchGenerator:
         for i in range(self.total_full_images):
             for j, (aug_fn, aug_arg) in enumerate(self.aug_fn_args):
                 aug_arg = self._with_warp_op(j, aug_arg, None if self.warp_ops is None else self._warp_table[i, j])
-                aug_images[i, j], aug_labels[i, j] = aug_fn(self.images[i], self.labels[i], aug_arg)
+                img, lab = self._deformed(i, None if self.elastic is None else self._elastic_table[i, j])
+                aug_images[i, j], aug_labels[i, j] = aug_fn(img, lab, aug_arg)
         return aug_images, aug_labels
+
+    def _deformed(self, ind, u):
+        """Image ``ind`` in [0, 1] and its labels as the list's function gets them: through the elastic stage where it is
+        configured and the sample's uniform numbers ``u`` say so."""
+        if self.elastic is not None:
+            op = augmentation.draw_elastic_ops(self.elastic, u)
+            if op["kind"][0]:
+                img, lab = augmentation.elastic_sample(self.images_u8[ind], self.labels[ind], op)
+                return img.astype(np.float32) / np.float32(255.0), lab
+        return self.images[ind], self.labels[ind]
 
     def _with_warp_op(self, j, aug_arg, u):
         """``aug_arg`` of augmentation ``j`` with the sample's warp descriptor, drawn from its uniform numbers ``u``, under
@@ -124,7 +154,9 @@ class BatchGenerator:
             aug_fn, aug_arg = self.aug_fn_args[j]
             if self.warp_ops is not None:       # every sample takes its numbers, whatever its augmentation
                 aug_arg = self._with_warp_op(j, aug_arg, self._warp_rng.random(augmentation.WARP_DRAWS))
-            img, lab = aug_fn(self.images[ind], self.labels[ind], aug_arg)
+            # (likewise: deformed or not, a sample takes its numbers from the elastic stream)
+            img, lab = self._deformed(ind, None if self.elastic is None else self._elastic_rng.random(augmentation.ELASTIC_DRAWS))
+            img, lab = aug_fn(img, lab, aug_arg)
         else:
             img, lab = self.aug_images[ind, j], self.aug_labels[ind, j]
         if self.full_counter == self.total_full_images:
@@ -192,7 +224,9 @@ class BatchGenerator:
         ``image_index * n_augs + j`` (the same noise for a pair in every epoch: what the pre-computed set means).  With
         ``shard = (lo, hi)`` only samples lo..hi-1 are gathered; their descriptors are those of the one-rank run.
         A list with a ``column_shift`` / ``affine`` returns a fourth array, one ``augmentation.WARP_OP_DTYPE`` descriptor per
-        sample (kind 0 for a sample that is not warped), drawn for the GLOBAL batch and sliced like the others."""
+        sample (kind 0 for a sample that is not warped), drawn for the GLOBAL batch and sliced like the others.  With
+        ``elastic`` a fifth, one ``augmentation.ELASTIC_OP_DTYPE`` descriptor per sample drawn and sliced the same way; the
+        fourth position then holds ``None`` for a list without a warp."""
         if self.aug_ops is None:
             raise TypeError("next_batch_aug needs device_aug=True, an augmentation mode and augmentations the device "
                             "implements (augmentation.aug_ops_from)")
@@ -220,9 +254,16 @@ class BatchGenerator:
         if self.warp_ops is not None:
             u = self._warp_rng.random((B, augmentation.WARP_DRAWS)) if self.aug_fly else self._warp_table[idx, j]
             wops = augmentation.draw_warp_ops(self.aug_fn_args, j, u)
+        eops = None
+        if self.elastic is not None:
+            u = self._elastic_rng.random((B, augmentation.ELASTIC_DRAWS)) if self.aug_fly else self._elastic_table[idx, j]
+            eops = augmentation.draw_elastic_ops(self.elastic, u)
         if shard is not None:
             idx, ops = idx[shard[0]:shard[1]], ops[shard[0]:shard[1]]
             wops = None if wops is None else wops[shard[0]:shard[1]]
+            eops = None if eops is None else eops[shard[0]:shard[1]]
+        if eops is not None:
+            return self.images_u8[idx], self.sparse_labels()[idx], ops, wops, eops
         if wops is not None:
             return self.images_u8[idx], self.sparse_labels()[idx], ops, wops
         return self.images_u8[idx], self.sparse_labels()[idx], ops
@@ -240,7 +281,7 @@ class DataGenerator:
 
     def __init__(self, images: np.ndarray, labels: np.ndarray, batch_size: int, aug_fn_args: List[Tuple],
                  aug_mode: str, aug_probs: Tuple, aug_fly: bool, preprocess_input_fn: Callable,
-                 seed: Optional[int] = None, device_aug: bool = False):
+                 seed: Optional[int] = None, device_aug: bool = False, elastic: Optional[dict] = None):
         # uint8 fast path (the /255 happens on the GPU) only without augmentation AND only for uint8 storage: the
         # reference divides by 255 whatever the dataset's dtype (data_generator.py:76), so any other dtype goes through
         # get_batch_list(), which computes float32(images) / 255 on the host
@@ -248,7 +289,8 @@ class DataGenerator:
         is_u8 = np.asarray(images).dtype == np.uint8
         self.batch_gen = BatchGenerator(images=images, labels=labels, batch_size=batch_size, aug_fn_args=aug_fn_args,
                                         aug_mode=aug_mode, aug_probs=aug_probs, aug_fly=aug_fly,
-                                        preprocess_input_fn=preprocess_input_fn, seed=seed, device_aug=device_aug and is_u8)
+                                        preprocess_input_fn=preprocess_input_fn, seed=seed, device_aug=device_aug and is_u8,
+                                        elastic=elastic)
         # augmentation on the device (Model.fit: uint8 upload + oct_augment_batch) where it was asked for and is possible
         self.oct_device_aug = self.batch_gen.aug_ops is not None
         if device_aug and aug_mode != "none" and not self.oct_device_aug:

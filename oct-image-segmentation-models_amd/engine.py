@@ -723,8 +723,20 @@ class UNetEngine:
                   _ptr(lab_out), self._stream())
         return x_out, lab_out
 
+    def elastic(self, x_u8: torch.Tensor, labels: Optional[torch.Tensor], ops, out=None):
+        """The elastic deformation on the device (``oct_elastic_batch``): (B,H,W,C) uint8 images, (B,H,W[,1]) uint8 labels
+        or ``None`` and one ``common.augmentation.ELASTIC_OP_DTYPE`` descriptor per sample -> ``(images uint8, labels uint8)``
+        (moved alongside; ``None`` without labels), the input of ``warp`` or ``augment``.  ``ops`` and ``out`` as for ``warp``
+        (validated with ``check_elastic_ops``; B*40 descriptor bytes).  Asynchronous on the current stream."""
+        from .common.augmentation import ELASTIC_OP_DTYPE, check_elastic_ops
+        ops, x_out, lab_out = self._stage_io("elastic", x_u8, labels, ops, "ELASTIC_OP_DTYPE", ELASTIC_OP_DTYPE, check_elastic_ops,
+                                             out, torch.uint8)
+        _hip.call("oct_elastic_batch", self.device, x_u8.data_ptr(), _ptr(labels), ops.data_ptr(), *x_u8.shape, x_out.data_ptr(),
+                  _ptr(lab_out), self._stream())
+        return x_out, lab_out
+
     def _stage_io(self, what, x_u8, labels, ops, op_name, op_dtype, check, out, x_dtype):
-        """``augment`` / ``warp`` (``what``): validates images, labels, descriptors (a numpy array: also by ``check(ops, H, W)``, then
+        """``augment`` / ``warp`` / ``elastic`` (``what``): validates images, labels, descriptors (a numpy array: also by ``check(ops, H, W)``, then
         uploaded) and ``out``, and makes what of it is missing.  Returns ``(descriptor bytes, x_out, labels_out or None)``."""
         u8 = dict(device=self.device, dtype=torch.uint8)
         _hip.expect(x_u8, f"{what}: images (B,H,W,C)", shape=(None, None, None, None), **u8)

@@ -21,7 +21,16 @@ class TrainingParams:
                  early_stopping: bool = True, restore_best_weights: bool = True, patience: int = 50,
                  seed: Union[int, None] = None, aug_device: bool = False, pad_mode: Union[str, None] = None,
                  pad_value=0, ignore_label: Union[int, None] = None, apply_class_weight: bool = False,
-                 fit_temperature: bool = False):
+                 fit_temperature: bool = False, elastic: Union[dict, None] = None):
+        # extension: elastic deformation (common.augmentation.elastic_spec: p, spacing, max_displacement[, border, fill,
+        # fill_label]) of every sample the augmentation list applies to, in front of the list's own augmentation; on the device
+        # with aug_device, on the host without.  None: no such stage, nothing changes
+        if elastic is not None:
+            aug.elastic_spec(elastic)       # (ValueError for anything outside the definition)
+            if aug_mode == "none":
+                raise ValueError('elastic needs an augmentation mode: to deform otherwise un-augmented samples use aug_mode '
+                                 '"one" with a single "no_augmentation" entry')
+        self.elastic = None if elastic is None else dict(elastic)
         # extension: after fit returns, rank 0 fits the temperature of the trained model on the un-augmented validation arrays
         # (Model.fit_temperature, with the ignore_label / pad_mode above) and writes temperature.json into the run folder
         # (evaluation.calibration.read_temperature reads it).  Off: no such file, nothing launched
