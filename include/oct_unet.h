@@ -39,6 +39,8 @@
  *   oct_warp_batch                     (none at training time; the per-column np.roll of roll_image_offset /
  *                                      flatten_image_boundary        dataset_construction.py is its dataset-preparation kin)
  *   oct_elastic_batch                  (none: the smooth random elastic deformation of the U-Net paper, a training augmentation)
+ *   oct_edge_weight_map / oct_unet_set_pixel_weights  (none: the border weight map of the U-Net paper / ReLayNet's boundary-
+ *                                      weighted cross-entropy, as a per-pixel weight of the focal / BCE term)
  *   oct_calibration_counts / oct_temperature_apply / oct_temperature_nll  (none: reliability counts, ECE / NLL / Brier and
  *                                      temperature scaling of the softmax output, Guo et al. 2017)
  *   oct_ordered_decode                 (none: the best class map per column whose class index never decreases with depth)
@@ -170,6 +172,18 @@ int oct_unet_loss_bce_dice(oct_unet* h, float smooth, float* out8_dev, oct_strea
  * A captured graph (oct_unet_graph_capture_infer) keeps the setting it was captured under.
  * The reference has no counterpart; the tests compare with a torch-fp64 masked restatement. */
 int oct_unet_set_ignore_label(oct_unet* h, int label);
+/* Per-pixel weights of the pixel term.  weights_dev: (B,H,W) f32 of the NEXT batch (caller-owned, kept alive and refilled
+ * in place between steps; e.g. oct_edge_weight_map's output), or NULL [default] = off.  With a map set, the focal term of a
+ * counted pixel is w(x) cw[y] (1 - p_y)^gamma (-log p_y) and the BCE term of a counted pixel is w(x) sum_c(...), in the
+ * forward sums and in oct_unet_backward alike; each term is multiplied by one float multiply, so a map of all 1.0f gives
+ * the bits of the off path and a map of all 2.0f doubles the focal / BCE sum exactly.
+ * NORMALISATION: the mean divides by what it divides by without a map -- B*H*W, or the counted pixels under an ignore
+ * label -- as Keras's sample_weight does.  It does NOT divide by the sum of the weights.
+ * The Dice term (plain or shaped), its five sums, the dice_coef metrics and the count of the ignore label never see the
+ * map; with a plain Dice loss selected the map is accepted and has no effect.  Workspace sizes do not change.
+ * Setting another pointer (or NULL) drops a pending forward's sums, as oct_unet_set_ignore_label does: call forward again
+ * before the loss.  The same map must be in place for the forward and the backward of a step. */
+int oct_unet_set_pixel_weights(oct_unet* h, const float* weights_dev);
 /* Shape of the Dice term: Tversky weights, focal-Tversky exponent, class weights.  Per handle; holds for the following
  * forward / loss / backward calls; every call drops a pending Dice sum (call forward again).  s = NULL, or alpha = beta = 0.5,
  * gamma = 1, weight_mode = 0, is plain Dice: the launches and results are those of a handle that never had a shape.
@@ -575,6 +589,26 @@ typedef struct oct_elastic_op {  /* one per sample of the batch, 40 bytes, in DE
 int oct_elastic_batch(const unsigned char* x_u8_dev, const unsigned char* labels_dev, const oct_elastic_op* ops_dev,
                       int B, int H, int W, int C,
                       unsigned char* x_out_dev, unsigned char* labels_out_dev, oct_stream_t stream);
+
+/* ---- edge weight map: per-pixel loss weights from the labels, on the device ----
+ * weights[b, y, x] = lut[idx] of the capped squared distance to the nearest class border of image b -- the weight map of the
+ * U-Net paper, w = 1 + w0 exp(-d^2 / 2 sigma^2), or ReLayNet's 1 + omega [x on a layer boundary], by the table the caller
+ * uploads (common/utils.py edge_weight_lut).  Defined in integers (common/utils.py edge_weight_reference restates it):
+ *   known:  label < n_cls.  The ignore label and every other byte >= n_cls are unknown.
+ *   edge:   a known pixel with a 4-neighbour INSIDE the image that is known and has another label.  Both sides of a border
+ *           are edge pixels; a border against unknown pixels (a pad frame, an unlabelled region) or the image rim is none.
+ *   d2(x):  min of dx^2 + dy^2 over the edge pixels of the same image with dx^2 + dy^2 <= R^2;
+ *           idx = d2, or R^2 + 1 ("far") where there is none; an edge pixel has idx 0.
+ *   w(x):   lut[idx] for a known pixel, 0.0f for an unknown one.
+ * lut_dev: R^2 + 2 floats.  labels_dev: (B,H,W) or (B,H,W,1) bytes; weights_dev: (B,H,W) f32.  Stand-alone: no handle, no
+ * workspace, no allocation, one asynchronous launch on `stream`, graph-capturable, no atomics; two calls give the same bytes.
+ * Errors (negative, nothing launched): null pointers, non-positive B, H or W, n_cls outside 1..255, radius outside
+ * 1..OCT_EDGE_WEIGHT_MAX_RADIUS, B > 65535, H or W > OCT_EDGE_WEIGHT_MAX_DIM, lut_dev or weights_dev not 4-byte aligned,
+ * weights_dev overlapping labels_dev. */
+#define OCT_EDGE_WEIGHT_MAX_RADIUS 32
+#define OCT_EDGE_WEIGHT_MAX_DIM    16384
+int oct_edge_weight_map(const unsigned char* labels_dev, int B, int H, int W, int n_cls, int radius, const float* lut_dev,
+                        float* weights_dev, oct_stream_t stream);
 
 /* ---- pad and crop on device: scans whose size is no multiple of 2^pool_layers ----
  * oct_pad_batch places a (B,H,W,ch) batch -- uint8 (is_u8) or float32 -- at (top, left) of a (B,Hp,Wp,ch) batch of the same

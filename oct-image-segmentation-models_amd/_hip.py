@@ -122,6 +122,7 @@ SYMBOLS = [
     ("oct_unet_set_bce_dice", C.c_int, [C.c_void_p, C.c_int]),
     ("oct_unet_loss_bce_dice", C.c_int, [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
     ("oct_unet_set_ignore_label", C.c_int, [C.c_void_p, C.c_int]),
+    ("oct_unet_set_pixel_weights", C.c_int, [C.c_void_p, C.c_void_p]),
     ("oct_unet_set_dice_shape", C.c_int, [C.c_void_p, _P(DiceShape)]),
     ("oct_unet_backward", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p]),
     ("oct_unet_set_tail_event", C.c_int, [C.c_void_p, C.c_void_p]),
@@ -159,6 +160,7 @@ SYMBOLS = [
                                  C.c_void_p]),
     ("oct_elastic_batch", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                     C.c_void_p]),
+    ("oct_edge_weight_map", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("oct_pad_batch", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                 C.c_float, C.c_void_p, C.c_void_p]),
     ("oct_crop_batch", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,

@@ -11,7 +11,13 @@ focal loss raise.
 The Dice term of all four takes a SHAPE: ``alpha`` / ``beta`` (Tversky index), ``tversky_gamma``
 (focal-Tversky exponent) and ``dice_class_weight`` (a sequence of ``num_classes`` weights, or ``"volume"`` for the
 generalized Dice loss).  A factory called with any of them tags its callable with ``oct_dice_shape``, which
-``Model.compile`` hands to ``UNetEngine.set_dice_shape``; with none of them the callables are what they were."""
+``Model.compile`` hands to ``UNetEngine.set_dice_shape``; with none of them the callables are what they were.
+
+The PIXEL term of ``focal_dice_loss`` / ``bce_dice_loss`` takes a per-pixel weight: ``edge_weight``, a
+dict ``{"radius", "weight", "profile", "sigma"}`` (``common.utils.check_edge_weight``), weights every pixel by
+``lut[squared distance to the nearest class border]`` -- the U-Net paper's weight map, ReLayNet's boundary-weighted
+cross-entropy.  The mean still divides by the number of pixels, not by the sum of the weights (Keras ``sample_weight``).  The
+factory tags its callable with ``oct_edge_weight``; the Dice factories refuse the keyword (they have no pixel term)."""
 from __future__ import annotations
 
 import numpy as np
@@ -22,6 +28,30 @@ def _one_hot(y_true, num_classes):
     if lab.ndim == 4 and lab.shape[-1] == 1:
         lab = lab[..., 0]
     return np.eye(num_classes, dtype=np.float64)[lab.astype(np.int64)]
+
+
+def _edge_weight_spec(edge_weight):
+    """The validated spec of the ``edge_weight`` keyword, or None."""
+    if edge_weight is None:
+        return None
+    from .utils import check_edge_weight
+    return check_edge_weight(edge_weight)
+
+
+def _edge_weights(spec, labels, num_classes):
+    """float64 (B,H,W) weights of ``spec`` for sparse ``labels`` (1 everywhere for ``spec = None``)."""
+    if spec is None:
+        return 1.0
+    from .utils import edge_weight_lut, edge_weight_reference
+    lab = np.asarray(labels)
+    lab = lab[..., 0] if (lab.ndim == 4 and lab.shape[-1] == 1) else lab
+    lut = edge_weight_lut(spec["radius"], spec["profile"], spec["weight"], spec["sigma"])
+    return edge_weight_reference(lab.astype(np.uint8), num_classes, spec["radius"], lut).astype(np.float64)
+
+
+def _no_edge_weight(name, kwargs):
+    if kwargs.get("edge_weight") is not None:
+        raise ValueError(f"{name}: edge_weight weights the pixel term of focal_dice_loss / bce_dice_loss; a Dice loss has none")
 
 
 DICE_CLAMP = 1e-7     # focal-Tversky: L = max(1 - TI, DICE_CLAMP) ** gamma for gamma != 1
@@ -127,6 +157,7 @@ def shaped_dice_reference(labels, probs, num_classes: int, ignore=None, *, smoot
 
 def dice_loss_micro(*, is_y_true_sparse: bool, num_classes: int, alpha: float = 0.5, beta: float = 0.5,
                     tversky_gamma: float = 1.0, dice_class_weight=None, **kwargs):
+    _no_edge_weight("dice_loss_micro", kwargs)
     shape = check_dice_shape(num_classes, alpha, beta, tversky_gamma, dice_class_weight)
 
     def _dice_loss_micro(y_true, y_pred, smooth=1e-05):
@@ -146,6 +177,7 @@ def dice_loss_micro(*, is_y_true_sparse: bool, num_classes: int, alpha: float = 
 
 def dice_loss_macro(*, is_y_true_sparse: bool, num_classes: int, alpha: float = 0.5, beta: float = 0.5,
                     tversky_gamma: float = 1.0, dice_class_weight=None, **kwargs):
+    _no_edge_weight("dice_loss_macro", kwargs)
     shape = check_dice_shape(num_classes, alpha, beta, tversky_gamma, dice_class_weight)
 
     def _dice_loss_macro(y_true, y_pred, smooth=1e-05):
@@ -171,10 +203,12 @@ FOCAL_EPS = 1e-7   # keras backend epsilon: probabilities are clipped to [eps, 1
 
 def focal_dice_loss(*, num_classes: int, gamma: float = 2, class_weight=None, focal_loss_weight: float = 0.5,
                     dice_macro: bool = True, alpha: float = 0.5, beta: float = 0.5, tversky_gamma: float = 1.0,
-                    dice_class_weight=None, **kwargs):
+                    dice_class_weight=None, edge_weight=None, **kwargs):
     """``focal_dice_loss`` / ``SparseCategoricalFocalDiceLoss`` (reference custom_losses.py:98-178), sparse labels:
     ``w * sum_px[cw[y] (1-p_y)^gamma (-log p_y)] / size(y_true) + (1 - w) * dice_loss_{macro|micro}``.  ``gamma`` and
-    ``class_weight`` belong to the focal term; ``alpha``, ``beta``, ``tversky_gamma``, ``dice_class_weight`` shape the Dice term."""
+    ``class_weight`` belong to the focal term; ``alpha``, ``beta``, ``tversky_gamma``, ``dice_class_weight`` shape the Dice term.
+    ``edge_weight`` (``check_edge_weight``'s dict) multiplies each pixel's focal term by its border weight."""
+    ew = _edge_weight_spec(edge_weight)
     cw = None if class_weight is None else np.asarray(class_weight, np.float64)
     if cw is not None and cw.shape != (num_classes,):
         raise ValueError(f"class_weight must have {num_classes} entries")
@@ -187,7 +221,7 @@ def focal_dice_loss(*, num_classes: int, gamma: float = 2, class_weight=None, fo
         lab = (lab[..., 0] if (lab.ndim == 4 and lab.shape[-1] == 1) else lab).astype(np.int64)
         p = np.asarray(y_pred, np.float64)
         py = np.clip(np.take_along_axis(p, lab[..., None], axis=-1)[..., 0], FOCAL_EPS, 1.0 - FOCAL_EPS)
-        w = 1.0 if cw is None else cw[lab]
+        w = (1.0 if cw is None else cw[lab]) * _edge_weights(ew, lab, num_classes)
         focal = np.sum(w * (1.0 - py) ** gamma * -np.log(py)) / lab.size
         return focal_loss_weight * focal + (1.0 - focal_loss_weight) * dice_fn(y_true, y_pred)
 
@@ -195,16 +229,20 @@ def focal_dice_loss(*, num_classes: int, gamma: float = 2, class_weight=None, fo
     _focal_dice_loss.oct_focal = {"gamma": float(gamma), "class_weight": None if cw is None else cw.tolist(),
                                   "focal_loss_weight": float(focal_loss_weight), "dice_macro": bool(dice_macro)}
     _focal_dice_loss.oct_dice_shape = dice_fn.oct_dice_shape
+    _focal_dice_loss.oct_edge_weight = ew
     return _focal_dice_loss
 
 
 def bce_dice_loss(*, num_classes: int, bce_inner_eps: bool = True, alpha: float = 0.5, beta: float = 0.5,
-                  tversky_gamma: float = 1.0, dice_class_weight=None, **kwargs):
+                  tversky_gamma: float = 1.0, dice_class_weight=None, edge_weight=None, **kwargs):
     """``bce_dice_loss`` (reference custom_losses.py:84-91): ``keras.losses.binary_crossentropy(y, p) + dice_loss_micro``.
     The cross-entropy restates Keras 2.9's ``backend.binary_crossentropy`` (``from_logits=False``) on the clipped
     probabilities, ``-(y ln(pc + e) + (1 - y) ln(1 - pc + e))``, averaged over the class axis and then over the batch
     (one mean over every element).  ``bce_inner_eps=False`` drops the inner ``+ e`` (engine option "bce_inner_eps").
-    Sparse ``y_true`` (labels) is accepted as well as the dense one-hot the reference feeds it."""
+    Sparse ``y_true`` (labels) is accepted as well as the dense one-hot the reference feeds it.  ``edge_weight``
+    (``check_edge_weight``'s dict) multiplies each pixel's cross-entropy by its border weight, taken from the arg-max of a
+    dense ``y_true``."""
+    ew = _edge_weight_spec(edge_weight)
     dice_fn = dice_loss_micro(is_y_true_sparse=False, num_classes=num_classes, alpha=alpha, beta=beta,
                               tversky_gamma=tversky_gamma, dice_class_weight=dice_class_weight)
     e = FOCAL_EPS if bce_inner_eps else 0.0
@@ -216,15 +254,20 @@ def bce_dice_loss(*, num_classes: int, bce_inner_eps: bool = True, alpha: float 
         pc = np.clip(p, FOCAL_EPS, 1.0 - FOCAL_EPS)
         qc = np.clip(1.0 - p, FOCAL_EPS, 1.0 - FOCAL_EPS)
         bce = -(y * np.log(pc + e) + (1.0 - y) * np.log(qc + e))
+        if ew is not None:
+            sparse = np.asarray(y_true) if np.asarray(y_true).shape != p.shape else np.argmax(y, axis=-1)
+            bce = bce * np.asarray(_edge_weights(ew, sparse, num_classes))[..., None]
         return np.mean(bce) + dice_fn(y, p)
 
     _bce_dice_loss.oct_loss = "bce_dice_loss"
     _bce_dice_loss.oct_dice_shape = dice_fn.oct_dice_shape
+    _bce_dice_loss.oct_edge_weight = ew
     return _bce_dice_loss
 
 
 def masked_loss_reference(labels, probs, num_classes: int, ignore, kind: str = "dice", *, smooth: float = 1e-05,
-                          gamma: float = 2.0, class_weight=None, focal_loss_weight: float = 0.5, bce_inner_eps: bool = True) -> dict:
+                          gamma: float = 2.0, class_weight=None, focal_loss_weight: float = 0.5, bce_inner_eps: bool = True,
+                          pixel_weight=None) -> dict:
     """The losses above and the two Dice metrics with an ignore label, as the engine defines them
     (``oct_unet_set_ignore_label``): sparse ``labels`` (B,H,W[,1]), ``probs`` (B,H,W,C), fp64.  A pixel whose label equals
     ``ignore`` (``None``: no such pixel) is dropped from every sum -- its one-hot row AND its probabilities -- and the focal
@@ -233,7 +276,9 @@ def masked_loss_reference(labels, probs, num_classes: int, ignore, kind: str = "
     ``dice_coef_macro``, ``dice_coef_micro``, ``term`` (the focal or BCE mean; 0 for ``"dice"``) and the combined
     ``loss_macro`` / ``loss_micro``: ``w term + (1 - w) dice`` for focal, ``term + dice_loss_micro`` for BCE (whose
     ``loss_macro`` is ``None``: the reference defines that loss with the micro Dice only), the Dice losses themselves for
-    ``"dice"``.  A batch without a counted pixel has ``dice_coef_micro = 0/0 = nan``, as the reference's formula gives."""
+    ``"dice"``.  ``pixel_weight`` (B,H,W), e.g. ``edge_weight_reference``'s map, multiplies each counted pixel's focal / BCE
+    term (``oct_unet_set_pixel_weights``); the divisor stays the count, and the Dice sums and metrics never see it.
+    A batch without a counted pixel has ``dice_coef_micro = 0/0 = nan``, as the reference's formula gives."""
     if kind not in ("dice", "focal", "bce"):
         raise ValueError(f"masked_loss_reference: unknown kind {kind!r}")
     lab = np.asarray(labels)
@@ -254,16 +299,21 @@ def masked_loss_reference(labels, probs, num_classes: int, ignore, kind: str = "
         out["dice_coef_micro"] = float(np.float64(2.0) * Ih.sum() / (T.sum() + Ph.sum()))
     count = int(m.sum())
     inv = 1.0 / count if count else 0.0
+    pw = None if pixel_weight is None else np.asarray(pixel_weight, np.float64).reshape(lab.shape)
     if kind == "focal":
         py = np.clip(np.take_along_axis(p, safe[..., None], axis=-1)[..., 0], FOCAL_EPS, 1.0 - FOCAL_EPS)
         cw = 1.0 if class_weight is None else np.asarray(class_weight, np.float64)[safe]
-        term, w = float(np.sum((cw * (1.0 - py) ** gamma * -np.log(py))[m]) * inv), float(focal_loss_weight)
+        px = cw * (1.0 - py) ** gamma * -np.log(py)
+        px = px if pw is None else pw * px
+        term, w = float(np.sum(px[m]) * inv), float(focal_loss_weight)
         out.update(term=term, loss_macro=w * term + (1.0 - w) * out["dice_loss_macro"],
                    loss_micro=w * term + (1.0 - w) * out["dice_loss_micro"])
     elif kind == "bce":
         e = FOCAL_EPS if bce_inner_eps else 0.0
         pc, qc = np.clip(p, FOCAL_EPS, 1.0 - FOCAL_EPS), np.clip(1.0 - p, FOCAL_EPS, 1.0 - FOCAL_EPS)
-        term = float(np.sum(-(y * np.log(pc + e) + (1.0 - y) * np.log(qc + e))[m]) * inv / num_classes)
+        px = -(y * np.log(pc + e) + (1.0 - y) * np.log(qc + e))
+        px = px if pw is None else pw[..., None] * px
+        term = float(np.sum(px[m]) * inv / num_classes)
         out.update(term=term, loss_macro=None, loss_micro=term + out["dice_loss_micro"])
     else:
         out.update(term=0.0, loss_macro=out["dice_loss_macro"], loss_micro=out["dice_loss_micro"])

@@ -514,3 +514,112 @@ def component_filter_reference(labels, root, size, n_cls: int, rule) -> Tuple[np
         cur = np.where(source[:, y], lab[:, y], cur)
     filled = np.where(above >= 0, above, np.where(below >= 0, below, fill))
     return np.where(gone, filled, lab).astype(np.uint8), removed
+
+
+# ---- edge weight maps: the table, the spec check and the numpy restatement of oct_edge_weight_map (include/oct_unet.h) ----
+EDGE_WEIGHT_MAX_RADIUS = 32
+EDGE_WEIGHT_PROFILES = ("box", "gauss", "linear")
+
+
+def check_edge_weight(spec) -> dict:
+    """The validated spec ``{"radius", "weight", "profile", "sigma"}`` of a boundary-weighted pixel loss (``edge_weight=`` of
+    ``focal_dice_loss`` / ``bce_dice_loss``): ``radius`` an integer in 1..32, ``weight`` finite and >= 0, ``profile`` one of
+    ``"box"`` [default], ``"gauss"``, ``"linear"``, ``sigma`` > 0 (``"gauss"`` only; default ``radius / 2``).  ``ValueError``
+    outside that, and for unknown keys."""
+    if not isinstance(spec, dict):
+        raise ValueError(f"edge_weight must be a dict with the keys radius, weight, profile, sigma, not {spec!r}")
+    unknown = sorted(set(spec) - {"radius", "weight", "profile", "sigma"})
+    if unknown:
+        raise ValueError(f"edge_weight: unknown keys {unknown}")
+    if "radius" not in spec or "weight" not in spec:
+        raise ValueError("edge_weight needs radius and weight")
+    radius, weight, profile, sigma = spec["radius"], spec["weight"], spec.get("profile", "box"), spec.get("sigma")
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 1 <= int(radius) <= EDGE_WEIGHT_MAX_RADIUS:
+        raise ValueError(f"edge_weight: radius must be an integer in 1..{EDGE_WEIGHT_MAX_RADIUS}, not {radius!r}")
+    try:
+        weight = float(weight)
+    except (TypeError, ValueError):
+        raise ValueError(f"edge_weight: weight must be a number, not {weight!r}") from None
+    if not (np.isfinite(weight) and weight >= 0.0):
+        raise ValueError(f"edge_weight: weight must be finite and >= 0, not {weight}")
+    if profile not in EDGE_WEIGHT_PROFILES:
+        raise ValueError(f"edge_weight: profile must be one of {EDGE_WEIGHT_PROFILES}, not {profile!r}")
+    if profile == "gauss":
+        try:
+            sigma = float(radius) / 2.0 if sigma is None else float(sigma)
+        except (TypeError, ValueError):
+            raise ValueError(f"edge_weight: sigma must be a number, not {sigma!r}") from None
+        if not (np.isfinite(sigma) and sigma > 0.0):
+            raise ValueError(f"edge_weight: sigma must be finite and > 0, not {sigma}")
+    elif sigma is not None:
+        raise ValueError(f'edge_weight: sigma belongs to profile "gauss", not {profile!r}')
+    return {"radius": int(radius), "weight": weight, "profile": profile, "sigma": sigma}
+
+
+def edge_weight_lut(radius: int, profile: str, weight: float, sigma=None) -> np.ndarray:
+    """The table of ``oct_edge_weight_map``: float32 ``[R^2 + 2]``, entry ``d2`` = the weight at squared distance ``d2`` from
+    the nearest class border, entry ``R^2 + 1`` ("far") = 1.  With ``d = sqrt(d2) <= R``:
+    ``"box"`` ``1 + weight`` (ReLayNet's ``1 + omega [x near a boundary]``); ``"gauss"`` ``1 + weight exp(-d^2 / (2 sigma^2))``
+    (the U-Net paper); ``"linear"`` ``1 + weight (1 - d / (R + 1))``.  Computed in fp64 and cast once."""
+    s = check_edge_weight({"radius": radius, "weight": weight, "profile": profile, "sigma": sigma})
+    R, w = s["radius"], s["weight"]
+    d2 = np.arange(R * R + 1, dtype=np.float64)
+    if s["profile"] == "box":
+        v = np.full_like(d2, 1.0 + w)
+    elif s["profile"] == "gauss":
+        v = 1.0 + w * np.exp(-d2 / (2.0 * s["sigma"] ** 2))
+    else:
+        v = 1.0 + w * (1.0 - np.sqrt(d2) / (R + 1.0))
+    return np.concatenate([v, [1.0]]).astype(np.float32)
+
+
+def edge_index_reference(labels, n_cls: int, radius: int) -> np.ndarray:
+    """``idx`` of ``oct_edge_weight_map`` by its definition: int64 (B,H,W), the least ``dx^2 + dy^2 <= R^2`` to an edge pixel
+    of the same image, ``R^2 + 1`` where there is none; and ``-1`` at an unknown pixel (label >= n_cls).  An edge pixel is a
+    known pixel with a known 4-neighbour inside the image of another label.  Separable, as the kernel: vertical distance per
+    column first, then the minimum over the row."""
+    lab = np.asarray(labels)
+    if lab.ndim == 4 and lab.shape[-1] == 1:
+        lab = lab[..., 0]
+    if lab.ndim != 3 or lab.dtype != np.uint8:
+        raise ValueError("edge_weight_reference: labels must be uint8 (B,H,W) or (B,H,W,1)")
+    R = int(radius)
+    if not 1 <= R <= EDGE_WEIGHT_MAX_RADIUS or not 1 <= int(n_cls) <= 255:
+        raise ValueError("edge_weight_reference: radius must be in 1..32 and n_cls in 1..255")
+    B, H, W = lab.shape
+    L = lab.astype(np.int64)
+    known = L < n_cls
+    edge = np.zeros(L.shape, bool)
+    for sl_a, sl_b in (((slice(None), slice(1, None)), (slice(None), slice(None, -1))),        # vertical neighbours
+                       ((slice(None), slice(None), slice(1, None)), (slice(None), slice(None), slice(None, -1)))):
+        diff = known[sl_a] & known[sl_b] & (L[sl_a] != L[sl_b])
+        edge[sl_a] |= diff
+        edge[sl_b] |= diff
+    none = 1 << 20
+    v = np.full(L.shape, none, np.int64)                    # vertical distance to the nearest edge pixel of the column
+    for d in range(min(R, H - 1), -1, -1):                  # (a radius beyond the image: no such neighbour)
+        near = np.zeros_like(edge)
+        near[:, d:] |= edge[:, :H - d]
+        near[:, :H - d] |= edge[:, d:]
+        v[near] = d
+    far = R * R + 1
+    best = np.full(L.shape, far, np.int64)
+    v2 = np.where(v == none, none, v * v)
+    for dx in range(-min(R, W - 1), min(R, W - 1) + 1):
+        cand = np.full(L.shape, none, np.int64)
+        if dx >= 0:
+            cand[:, :, :W - dx] = v2[:, :, dx:] + dx * dx
+        else:
+            cand[:, :, -dx:] = v2[:, :, :W + dx] + dx * dx
+        best = np.minimum(best, np.where(cand <= R * R, cand, far))
+    return np.where(known, best, -1)
+
+
+def edge_weight_reference(labels, n_cls: int, radius: int, lut) -> np.ndarray:
+    """What ``oct_edge_weight_map`` computes: float32 (B,H,W), ``lut[idx]`` at a known pixel (``edge_index_reference``),
+    ``0.0`` at an unknown one.  ``lut``: the ``R^2 + 2`` floats of ``edge_weight_lut``."""
+    lut = np.asarray(lut, np.float32)
+    if lut.shape != (int(radius) ** 2 + 2,):
+        raise ValueError(f"edge_weight_reference: lut must have radius^2 + 2 = {int(radius) ** 2 + 2} entries")
+    idx = edge_index_reference(labels, n_cls, radius)
+    return np.where(idx >= 0, lut[np.maximum(idx, 0)], np.float32(0.0)).astype(np.float32)

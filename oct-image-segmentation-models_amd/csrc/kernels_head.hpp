@@ -38,6 +38,9 @@ struct HeadFwdArgs {
     // ignore label (oct_unet_set_ignore_label): a pixel with this label byte adds nothing to the Dice sums or to slot 5*C;
     // its probs / argmax are written as ever.  -1 = off: a label byte never compares equal
     int ignore;
+    // per-pixel weights of the focal / BCE term (oct_unet_set_pixel_weights): (B,H,W) f32, or nullptr = off.  One multiply per
+    // term; the Dice sums never see it.  The mean still divides by B*H*W (or the counted pixels), NOT by the sum of the weights
+    const float* pixw;
 };
 constexpr float kFocalEps = 1e-7f;
 constexpr int kHeadClsMin = 9, kHeadClsMax = 16;     // the class-streaming family (kernels_head_cls.hpp); 16 = the columns of one dl tile
@@ -71,7 +74,7 @@ __device__ __forceinline__ void head_softmax(float (&p)[C], float mx) {
 // what a COUNTED pixel (valid, labelled, not the ignore label) adds to its thread's row of loss sums: the five Dice sums
 // per class and, at slot 5 C, the focal or the BCE sum
 template <int C, int N>
-__device__ __forceinline__ void head_loss_sums(const HeadFwdArgs& A, int lab, const float (&p)[C], float (&v)[N]) {
+__device__ __forceinline__ void head_loss_sums(const HeadFwdArgs& A, int lab, float pw, const float (&p)[C], float (&v)[N]) {
     static_assert(C * kDiceVals < N, "slot 5 C is spare");
 #pragma unroll
     for (int c = 0; c < C; ++c) {
@@ -84,7 +87,7 @@ __device__ __forceinline__ void head_loss_sums(const HeadFwdArgs& A, int lab, co
 #pragma unroll
         for (int c = 1; c < C; ++c) py = lab == c ? p[c] : py;
         const float pc = fminf(fmaxf(py, kFocalEps), 1.f - kFocalEps);
-        const float cw = A.focal_cw ? A.focal_cw[lab < C ? lab : 0] : 1.f;
+        const float cw = pw * (A.focal_cw ? A.focal_cw[lab < C ? lab : 0] : 1.f);     // the pixel's weight rides on the class weight
         v[C * kDiceVals] += cw * powf(1.f - (A.focal_clip_mod ? pc : py), A.focal_gamma) * -logf(pc);
     }
     if (A.bce_on) {
@@ -95,7 +98,7 @@ __device__ __forceinline__ void head_loss_sums(const HeadFwdArgs& A, int lab, co
             const float u = lab == c ? p[c] : q[c];        // y picks one of the two logarithms
             t -= logf(fminf(fmaxf(u, kFocalEps), 1.f - kFocalEps) + A.bce_inner);
         }
-        v[C * kDiceVals] += t;
+        v[C * kDiceVals] = fmaf(pw, t, v[C * kDiceVals]);
     }
 }
 
@@ -137,27 +140,29 @@ __device__ inline void head_load(const AT* __restrict__ zp, float (&zr)[CIN]) {
 constexpr int kHeadFwdAhead = 1, kHeadBwdAhead = 1;
 template <int CIN, int D, typename AT>
 struct HeadQueue {
-    const AT* zb; const unsigned char* lb; int HW;
-    float zq[D][CIN]; int lq[D];
-    __device__ HeadQueue(const AT* z, const unsigned char* l, int hw) : zb(z), lb(l), HW(hw) {}
+    const AT* zb; const unsigned char* lb; const float* wb; int HW;
+    float zq[D][CIN]; int lq[D]; float wq[D];       // wq: the pixel's loss weight, 1 unless a map is set (a uniform branch)
+    __device__ HeadQueue(const AT* z, const unsigned char* l, const float* w, int hw) : zb(z), lb(l), wb(w), HW(hw) {}
     __device__ __forceinline__ void request(int d, int chunk) {
         if (chunk * kBlock < HW) {
             const int px = chunk * kBlock + (int)threadIdx.x, q = px < HW ? px : 0;
             head_load<CIN, AT>(zb + (size_t)q * CIN, zq[d]);
             if (lb) lq[d] = lb[q];
+            if (wb) wq[d] = wb[q];
         }
     }
     __device__ __forceinline__ void fill(int first, int stride) {
 #pragma unroll
-        for (int d = 0; d < D; ++d) { lq[d] = 0; request(d, first + d * stride); }
+        for (int d = 0; d < D; ++d) { lq[d] = 0; wq[d] = 1.f; request(d, first + d * stride); }
     }
-    __device__ __forceinline__ int pop(float (&zr)[CIN], int next) {
+    __device__ __forceinline__ int pop(float (&zr)[CIN], float& pw, int next) {
         const int lab = lq[0];
+        pw = wq[0];
 #pragma unroll
         for (int i = 0; i < CIN; ++i) zr[i] = zq[0][i];
 #pragma unroll
         for (int d = 0; d + 1 < D; ++d) {
-            lq[d] = lq[d + 1];
+            lq[d] = lq[d + 1]; wq[d] = wq[d + 1];
 #pragma unroll
             for (int i = 0; i < CIN; ++i) zq[d][i] = zq[d + 1][i];
         }
@@ -193,14 +198,15 @@ __global__ __launch_bounds__(kBlock) void head_fwd_k(const HeadFwdArgs A) {
 #pragma unroll
     for (int i = 0; i < N; ++i) v[i] = 0.f;
     HeadQueue<CIN, kHeadFwdAhead, AT> hq(reinterpret_cast<const AT*>(A.z) + (size_t)b * A.HW * CIN,
-                                         A.labels ? A.labels + (size_t)b * A.HW : nullptr, A.HW);
+                                         A.labels ? A.labels + (size_t)b * A.HW : nullptr,
+                                         A.pixw && A.labels ? A.pixw + (size_t)b * A.HW : nullptr, A.HW);
     hq.fill(blockIdx.x, gridDim.x);
     for (int chunk = blockIdx.x; chunk * kBlock < A.HW; chunk += gridDim.x) {
         const int px = chunk * kBlock + threadIdx.x;
         const bool valid = px < A.HW;
         const size_t pix = (size_t)b * A.HW + (valid ? px : 0);
-        float y[CIN], zr[CIN], p[C];
-        const int lab = hq.pop(zr, chunk + kHeadFwdAhead * (int)gridDim.x);     // this chunk's pixel; the one kHeadFwdAhead chunks on is requested
+        float y[CIN], zr[CIN], p[C], pw;
+        const int lab = hq.pop(zr, pw, chunk + kHeadFwdAhead * (int)gridDim.x);     // this chunk's pixel; the one kHeadFwdAhead chunks on is requested
         head_logits<C, CIN>(A.ab, A.w, A.bias, y, zr, p);
         if (valid) {
             if (A.probs) {
@@ -231,7 +237,7 @@ __global__ __launch_bounds__(kBlock) void head_fwd_k(const HeadFwdArgs A) {
 #pragma unroll
                     for (int c = 1; c < C; ++c) py = lab == c ? p[c] : py;
                     const float pc = fminf(fmaxf(py, kFocalEps), 1.f - kFocalEps);
-                    const float cw = A.focal_cw ? A.focal_cw[lab < C ? lab : 0] : 1.f;
+                    const float cw = pw * (A.focal_cw ? A.focal_cw[lab < C ? lab : 0] : 1.f);     // the pixel's weight rides on the class weight
                     v[C * kDiceVals] += cw * powf(1.f - (A.focal_clip_mod ? pc : py), A.focal_gamma) * -logf(pc);
                 }
                 if (A.bce_on) {
@@ -242,7 +248,7 @@ __global__ __launch_bounds__(kBlock) void head_fwd_k(const HeadFwdArgs A) {
                         const float u = lab == c ? p[c] : q[c];        // y picks one of the two logarithms
                         t -= logf(fminf(fmaxf(u, kFocalEps), 1.f - kFocalEps) + A.bce_inner);
                     }
-                    v[C * kDiceVals] += t;
+                    v[C * kDiceVals] = fmaf(pw, t, v[C * kDiceVals]);
                 }
             }
         }
@@ -272,6 +278,8 @@ struct HeadBwdArgs {
     // and the pixel adds nothing to the statistics or the head dW / db partials.  With it set, the means' 1 / (counted
     // pixels) comes from bc[2*B*C + 2] (dice_finalize_k) and stands in for inv_count, also inside bce_scale
     int ignore;
+    // per-pixel weights (see HeadFwdArgs): multiply dp of the focal term and db of the BCE term; nullptr = off
+    const float* pixw;
     FinDesc fin;                       // BN-backward sums of the last conv block finalized by the last block (kernels_fin.hpp)
 };
 
@@ -306,14 +314,15 @@ __global__ __launch_bounds__(kBlock) void head_bwd_k(const HeadBwdArgs A) {
     const HeadMeans hm = head_means<C>(A);
     const float fscale = A.focal_w * A.loss_scale * hm.inv_count;
 
-    HeadQueue<CIN, kHeadBwdAhead, AT> hq(reinterpret_cast<const AT*>(A.z) + (size_t)b * A.HW * CIN, A.labels + (size_t)b * A.HW, A.HW);
+    HeadQueue<CIN, kHeadBwdAhead, AT> hq(reinterpret_cast<const AT*>(A.z) + (size_t)b * A.HW * CIN, A.labels + (size_t)b * A.HW,
+                                         A.pixw ? A.pixw + (size_t)b * A.HW : nullptr, A.HW);
     hq.fill(blockIdx.x, gridDim.x);
     for (int chunk = blockIdx.x; chunk * kBlock < A.HW; chunk += gridDim.x) {
         const int px = chunk * kBlock + threadIdx.x;
         const bool valid = px < A.HW;
         const size_t pix = (size_t)b * A.HW + (valid ? px : 0);
-        float y[CIN], zr[CIN], p[C];
-        const int lab = hq.pop(zr, chunk + kHeadBwdAhead * (int)gridDim.x);     // later chunks' pixels are requested before this one is used
+        float y[CIN], zr[CIN], p[C], pw;
+        const int lab = hq.pop(zr, pw, chunk + kHeadBwdAhead * (int)gridDim.x);     // later chunks' pixels are requested before this one is used
         const bool counted = valid && lab != A.ignore;  // folded into the selects that `valid` already feeds: no new branch
         head_logits<C, CIN>(A.bn, A.w, A.bias, y, zr, p);
         float dp[C], dot = 0.f;
@@ -327,7 +336,7 @@ __global__ __launch_bounds__(kBlock) void head_bwd_k(const HeadBwdArgs A) {
                 const bool inr = p[c] >= kFocalEps && p[c] <= 1.f - kFocalEps;
                 if (inr || !A.focal_clip_mod) {
                     const float pc = fminf(fmaxf(p[c], kFocalEps), 1.f - kFocalEps);
-                    const float q = 1.f - p[c], cw = A.focal_cw ? ldc(A.focal_cw + c) : 1.f, qg1 = powf(q, A.focal_gamma - 1.f);
+                    const float q = 1.f - p[c], cw = pw * (A.focal_cw ? ldc(A.focal_cw + c) : 1.f), qg1 = powf(q, A.focal_gamma - 1.f);
                     dp[c] += fscale * cw * (A.focal_gamma * qg1 * logf(pc) - (inr ? qg1 * q / pc : 0.f));
                 }
             }
@@ -346,10 +355,11 @@ __global__ __launch_bounds__(kBlock) void head_bwd_k(const HeadBwdArgs A) {
             //   dl_c = p_c ( q_c dp_c - sum_{k != c} p_k dp_k )
             float q[C], db[C];
             softmax_complement<C>(p, q);
+            const float ws = pw * hm.bce_scale;          // the pixel's weight, once for all classes
 #pragma unroll
             for (int c = 0; c < C; ++c) {
                 const bool inr = counted && p[c] >= kFocalEps && q[c] >= kFocalEps;
-                const float r = hm.bce_scale / ((lab == c ? p[c] : q[c]) + A.bce_inner);     // y picks the term
+                const float r = ws / ((lab == c ? p[c] : q[c]) + A.bce_inner);     // y picks the term
                 db[c] = inr ? (lab == c ? -r : r) : 0.f;
             }
 #pragma unroll

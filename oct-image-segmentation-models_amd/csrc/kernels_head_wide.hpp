@@ -75,8 +75,9 @@ __global__ __launch_bounds__(kBlock) void head_fwd_wide_k(const HeadFwdArgs A, c
             }
         }
         const int lab = A.labels ? A.labels[pix] : 0;
+        const float pw = A.pixw && A.labels ? A.pixw[pix] : 1.f;       // (uniform branch: see HeadQueue)
         if (valid && lab != A.ignore) {                     // the loss sums: counted pixels only (see head_fwd_k)
-            if (A.labels) head_loss_sums<C, N>(A, lab, p, v);
+            if (A.labels) head_loss_sums<C, N>(A, lab, pw, p, v);
         }
     }
     if (A.labels) head_rows_store<N>(v, red, A.dice_part + ((size_t)b * gridDim.x + blockIdx.x) * N);
@@ -111,6 +112,7 @@ __global__ __launch_bounds__(kBlock, 2) void head_bwd_wide_k(const HeadBwdArgs A
         const size_t pix = (size_t)b * A.HW + (valid ? px : 0);
         const AT* const zp = reinterpret_cast<const AT*>(A.z) + pix * CIN;
         const int lab = A.labels[pix];
+        const float pw = A.pixw ? A.pixw[pix] : 1.f;     // the pixel's loss weight: see head_bwd_k
         const bool counted = valid && lab != A.ignore;   // see head_bwd_k
         float p[C];
         head_logits_stream<C, AT>(zp, A.bn, A.w, A.bias, CIN, p);
@@ -123,7 +125,7 @@ __global__ __launch_bounds__(kBlock, 2) void head_bwd_wide_k(const HeadBwdArgs A
                 const bool inr = p[c] >= kFocalEps && p[c] <= 1.f - kFocalEps;
                 if (inr || !A.focal_clip_mod) {
                     const float pc = fminf(fmaxf(p[c], kFocalEps), 1.f - kFocalEps);
-                    const float q = 1.f - p[c], cw = A.focal_cw ? A.focal_cw[c] : 1.f, qg1 = powf(q, A.focal_gamma - 1.f);
+                    const float q = 1.f - p[c], cw = pw * (A.focal_cw ? A.focal_cw[c] : 1.f), qg1 = powf(q, A.focal_gamma - 1.f);
                     dp[c] += fscale * cw * (A.focal_gamma * qg1 * logf(pc) - (inr ? qg1 * q / pc : 0.f));
                 }
             }
@@ -135,10 +137,11 @@ __global__ __launch_bounds__(kBlock, 2) void head_bwd_wide_k(const HeadBwdArgs A
         if (A.bce_on) {                             // BCE term: see head_bwd_k
             float q[C], db[C];
             softmax_complement<C>(p, q);
+            const float ws = pw * hm.bce_scale;
 #pragma unroll
             for (int c = 0; c < C; ++c) {
                 const bool inr = counted && p[c] >= kFocalEps && q[c] >= kFocalEps;
-                const float r = hm.bce_scale / ((lab == c ? p[c] : q[c]) + A.bce_inner);
+                const float r = ws / ((lab == c ? p[c] : q[c]) + A.bce_inner);
                 db[c] = inr ? (lab == c ? -r : r) : 0.f;
             }
 #pragma unroll

@@ -259,6 +259,7 @@ struct oct_unet {
     float focal_w = 0.f, focal_gamma = 2.f; const float* focal_cw = nullptr;           // focal_dice_loss (0 = plain Dice)
     int bce_on = 0;                                                                    // bce_dice_loss (never with focal_w > 0)
     int ignore = -1;                                                                   // ignore label of the loss (-1 = none)
+    const float* pixw = nullptr;                                                       // per-pixel weights of the focal / BCE term (nullptr = off)
     // oct_unet_set_dice_shape (shape_on = 0: plain Dice, dice_finalize_k).  The folded macro and micro tables, each laid out as
     // dice_bc, and the sums table live in one device buffer the handle allocates at the first shape and frees in destroy: the
     // workspace keeps its size (tests/test_many_classes.py pins it)
@@ -560,6 +561,7 @@ int forward_head(oct_unet* h, int B, const oct_unet_io* io, hipStream_t s) {
     a.dice_part = h->dice_part; a.HW = hd.H * hd.W; a.nblk = head_nblk(a.HW, B); a.act_bf16 = h->cfg.dtype;
     a.focal_on = h->focal_w > 0.f; a.focal_gamma = h->focal_gamma; a.focal_cw = h->focal_cw; a.focal_clip_mod = h->opt.focal_clip_mod;
     a.bce_on = h->bce_on; a.bce_inner = h->opt.bce_inner_eps ? kFocalEps : 0.f; a.ignore = h->ignore;
+    a.pixw = h->pixw;
     if (int rc = launch_head_fwd(a, head_route(h->opt, h->cfg.n_cls, hd.cin), h->cfg.n_cls, hd.cin, B, s)) return rc;
     h->have_dice = a.labels != nullptr;
     return 0;
@@ -796,6 +798,7 @@ int head_backward(oct_unet* h, const unsigned char* labels, int macro, float los
     hb.HW = hd.H * hd.W; hb.nblk = head_nblk(hb.HW, B); hb.B = B; hb.macro = macro; hb.loss_scale = loss_scale; hb.act_bf16 = h->cfg.dtype;
     hb.focal_w = h->focal_w; hb.focal_gamma = h->focal_gamma; hb.focal_cw = h->focal_cw; hb.focal_clip_mod = h->opt.focal_clip_mod; hb.inv_count = 1.f / ((float)B * hb.HW);
     hb.bce_on = h->bce_on; hb.bce_inner = h->opt.bce_inner_eps ? kFocalEps : 0.f; hb.bce_scale = loss_scale * hb.inv_count / (float)h->cfg.n_cls;
+    hb.pixw = h->pixw;
     hb.ignore = h->ignore;       // >= 0: the kernels take 1 / (counted pixels) from dice_bc instead of inv_count
     // shaped Dice: the folded per-(b, c) table of this combination, read with the macro indexing (its 1 / (B C) is folded in)
     if (h->shape_on) { hb.bc = macro ? h->shape_bcm : h->shape_bcu; hb.macro = 1; }
@@ -1283,6 +1286,14 @@ int oct_unet_set_ignore_label(oct_unet* h, int label) {
         return fail(-1, "ignore label must be -1 (none) or in n_classes..255: got " + std::to_string(label));
     if (label != h->ignore) { h->have_dice = 0; h->dice_final = 0; }    // sums of a forward under the other setting are not this loss's
     h->ignore = label;
+    return 0;
+}
+
+int oct_unet_set_pixel_weights(oct_unet* h, const float* weights_dev) {
+    if (!h) return fail(-1, "null handle");
+    if ((uintptr_t)weights_dev % 4) return fail(-1, "pixel weights must be 4-byte aligned");
+    if (weights_dev != h->pixw) { h->have_dice = 0; h->dice_final = 0; }    // sums of a forward under the other setting are not this loss's
+    h->pixw = weights_dev;
     return 0;
 }
 

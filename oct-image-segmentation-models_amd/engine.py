@@ -132,6 +132,10 @@ class UNetEngine:
         self.ignore_label, self._focal_active, self._bce_active = None, False, False
         self._focal_cw, self._focal_sel, self._loss_kind = None, None, "dice"
         self.dice_shape, self._shape_cw = None, None       # set_dice_shape's validated keywords (None: plain Dice) and its device weights
+        # per-pixel loss weights: the map the library holds a pointer to (None: off), the spec select_loss last saw, and the
+        # engine's own LUTs per spec and maps per batch size (Model._run_epoch fills them)
+        self.pixel_weights, self.edge_weight = None, None
+        self._edge_luts, self._edge_maps = {}, {}
 
     def __del__(self):
         if self._h:
@@ -234,6 +238,61 @@ class UNetEngine:
         self._call("oct_unet_set_ignore_label", -1 if label is None else int(label))
         self.ignore_label = None if label is None else int(label)
 
+    def set_pixel_weights(self, w: Optional[torch.Tensor]) -> None:
+        """Per-pixel weights of the focal / BCE term for the following forward / loss / backward calls
+        (``oct_unet_set_pixel_weights``): a float32 (B,H,W[,1]) tensor of the NEXT batch, kept alive by the engine and read
+        at the forward and the backward (refill it in place between steps), or ``None`` = off.  The Dice term, the metrics
+        and the divisor of the mean (B*H*W, or the counted pixels) do not see it.  Setting another tensor drops a pending
+        forward: call ``forward`` again before the loss."""
+        if w is not None:
+            _hip.expect(w, "pixel weights (B,H,W[,1])", device=self.device, dtype=torch.float32)
+            if w.dim() not in (3, 4) or tuple(w.shape[1:3]) != (self.cfg.H, self.cfg.W) or w.numel() != w.shape[0] * self.cfg.H * self.cfg.W \
+                    or not 1 <= w.shape[0] <= self.cfg.max_batch:
+                raise OctError(f"pixel weights must be (B,{self.cfg.H},{self.cfg.W}[,1]) with B in 1..{self.cfg.max_batch}, not {tuple(w.shape)}")
+        self._call("oct_unet_set_pixel_weights", _ptr(w))
+        self.pixel_weights = w       # keep the tensor alive: the library only stores the pointer
+
+    def edge_weight_map(self, labels: torch.Tensor, radius: int, lut, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The border weight map of uint8 (B,H,W[,1]) ``labels`` on the device (``oct_edge_weight_map``;
+        ``common.utils.edge_weight_reference`` restates it): float32 (B,H,W), ``lut[capped squared distance to the nearest
+        class border]`` at a pixel whose label is a class, 0 elsewhere.  ``lut``: ``common.utils.edge_weight_lut``'s
+        ``radius^2 + 2`` floats, a numpy array (uploaded) or a float32 device tensor.  Any image size; asynchronous on the
+        current stream."""
+        _hip.expect(labels, "edge_weight_map: labels (B,H,W[,1])", device=self.device, dtype=torch.uint8)
+        if labels.dim() not in (3, 4) or (labels.dim() == 4 and labels.shape[3] != 1) or labels.numel() == 0:
+            raise OctError(f"edge_weight_map: labels must be a non-empty (B,H,W) or (B,H,W,1) tensor, not {tuple(labels.shape)}")
+        B, H, W = labels.shape[:3]
+        if int(radius) != radius or not 1 <= int(radius) <= 32:
+            raise OctError(f"edge_weight_map: radius must be an integer in 1..32, not {radius!r}")
+        if not torch.is_tensor(lut):
+            lut = torch.from_numpy(np.ascontiguousarray(lut, np.float32)).to(self.device)
+        _hip.expect(lut, "edge_weight_map: lut (radius^2 + 2 floats)", device=self.device, dtype=torch.float32, shape=(int(radius) ** 2 + 2,))
+        if out is None:
+            out = torch.empty((B, H, W), dtype=torch.float32, device=self.device)
+        else:
+            _hip.expect(out, "edge_weight_map: out", device=self.device, dtype=torch.float32, shape=(B, H, W))
+        _hip.call("oct_edge_weight_map", self.device, labels.data_ptr(), B, H, W, self.cfg.n_cls, int(radius), lut.data_ptr(),
+                  out.data_ptr(), self._stream())
+        self._keep = self._keep + [labels, lut, out]
+        return out
+
+    def edge_weight_step(self, labels: torch.Tensor, spec: dict) -> torch.Tensor:
+        """The map of ``spec`` (``check_edge_weight``'s dict) for this step's ``labels``, in the engine's buffer of that batch
+        size, and set as the pixel weights.  The LUT is uploaded once per spec, the buffer made once per batch size."""
+        from .common.utils import edge_weight_lut
+        key = (spec["radius"], spec["profile"], spec["weight"], spec["sigma"])
+        lut = self._edge_luts.get(key)
+        if lut is None:
+            lut = self._edge_luts[key] = torch.from_numpy(edge_weight_lut(*key)).to(self.device)
+        B = labels.shape[0]
+        buf = self._edge_maps.get(B)
+        if buf is None:
+            buf = self._edge_maps[B] = torch.empty((B, self.cfg.H, self.cfg.W), dtype=torch.float32, device=self.device)
+        self.edge_weight_map(labels, spec["radius"], lut, out=buf)
+        if self.pixel_weights is not buf:
+            self.set_pixel_weights(buf)
+        return buf
+
     def set_dice_shape(self, alpha=0.5, beta: float = 0.5, gamma: float = 1.0, class_weight=None) -> None:
         """Shape the Dice term of the following forward / loss / backward calls (``oct_unet_set_dice_shape``, DESIGN.md section
         32): Tversky weights ``alpha`` (false positives) and ``beta`` (false negatives), the focal-Tversky exponent ``gamma``
@@ -259,11 +318,16 @@ class UNetEngine:
         self.dice_shape = shape
 
     def select_loss(self, kind: str = "dice", focal_loss_weight=0.5, gamma=2.0, class_weight=None, ignore_label=None,
-                    dice_shape=None) -> None:
+                    dice_shape=None, edge_weight=None) -> None:
         """Put the handle into the loss state a model asks for: ``kind`` "dice", "focal" (with ``set_focal_dice``'s parameters,
         compared by value) or "bce", the ignore label and the shape of the Dice term (``set_dice_shape``'s keywords as a dict,
         None: plain Dice).  Only the ``set_*`` calls that change what the engine last had selected are issued: an engine last
-        used by a focal, BCE, masked or shaped model comes back to plain Dice over every pixel."""
+        used by a focal, BCE, masked or shaped model comes back to plain Dice over every pixel.  ``edge_weight``: the spec of
+        the model's border weights (None: none); a model without one takes the pixel weights off an engine that another
+        model left weighted (a model with one sets its map per step, ``edge_weight_step``)."""
+        if edge_weight is None and self.pixel_weights is not None:
+            self.set_pixel_weights(None)
+        self.edge_weight = edge_weight
         if self.dice_shape != dice_shape:
             self.set_dice_shape(**dice_shape) if dice_shape else self.set_dice_shape(None)
         if self.ignore_label != ignore_label:

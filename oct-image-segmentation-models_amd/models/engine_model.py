@@ -128,7 +128,7 @@ class Model:
         # label value whose pixels do not count in the loss, the Dice metrics or the gradient (compile(ignore_label=...));
         # None: every pixel counts
         self.ignore_label = None
-        self._dice_shape = None
+        self._dice_shape, self._edge_weight = None, None
         self._device = device
         self.history = None
 
@@ -259,6 +259,9 @@ class Model:
         # the shape of the Dice term (the factories' alpha / beta / tversky_gamma / dice_class_weight; None: plain Dice): every
         # engine this model steps gets it with the loss kind, per batch (select_loss), the padded-size training engine included
         self._dice_shape = getattr(loss, "oct_dice_shape", None) if loss is not None else None
+        # border weights of the pixel term (the factories' edge_weight; None: none): the map is built per batch on the device,
+        # behind the augmentations and the pad (_run_epoch)
+        self._edge_weight = getattr(loss, "oct_edge_weight", None) if loss is not None else None
         metric_name = None
         for m in metrics or []:
             metric_name = getattr(m, "oct_metric", None)
@@ -395,7 +398,12 @@ class Model:
                 # pad_value is in the units of the Sequence's batches: raw counts where the augment stage has turned them to [0, 1]
                 x, lab = self._pad_batch(eng, x, lab, at, pad_mode, pad_value / 255.0 if raw_u8 and x.dtype != torch.uint8 else pad_value,
                                          ignore)
-            eng.select_loss(kind, *focal, ignore_label=ignore, dice_shape=self._dice_shape)      # per batch: the engine may be new, or another model's last
+            eng.select_loss(kind, *focal, ignore_label=ignore, dice_shape=self._dice_shape,      # per batch: the engine may be new, or another model's last
+                            edge_weight=self._edge_weight)
+            if self._edge_weight:
+                # the border weight map of the labels as the loss sees them: deformed, flipped, padded (the frame is unknown
+                # and makes no edge), in training and validation alike; into the engine's buffer, set before the forward
+                eng.edge_weight_step(lab, self._edge_weight)
             eng.forward(x, training=training, labels=lab, want_probs=False)
             loss = eng.loss_selected()
             if training:

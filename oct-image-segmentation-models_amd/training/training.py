@@ -69,6 +69,11 @@ def save_training_params_file(save_foldername: Path, model_summary: str, model_c
     for key, val in (getattr(train_params, "loss_shape_kwargs", None) or {}).items():
         attrs["loss_param: " + key] = np.array(val, dtype="S100") if isinstance(val, str) else \
             val if np.isscalar(val) else np.asarray(val, dtype=np.float64)
+    # the border weights of the pixel term: "edge_weight_param: <key>" = each key of the validated spec, only when the
+    # keyword was given
+    for key, val in (getattr(train_params, "edge_weight_kwargs", None) or {}).items():
+        if val is not None:
+            attrs[f"edge_weight_param: {key}"] = np.array(val, dtype="S100") if isinstance(val, str) else val
     datasets = {} if class_weight is None else {"class_weight": np.asarray(class_weight)}
     h5io.save(save_foldername / Path("training_params.hdf5"), datasets, attrs)
 
@@ -139,6 +144,8 @@ def train_model(training_params: TrainingParams, mlflow_params=None):
     except NotImplementedError as e:
         log.error(e)
         exit(1)
+
+    training_params.edge_weight_kwargs = getattr(loss_fn, "oct_edge_weight", None)
 
     metric = custom_metrics.training_monitor_metric_objects.get(training_params.metric)
     if metric is None:
