@@ -39,6 +39,8 @@
  *   oct_warp_batch                     (none at training time; the per-column np.roll of roll_image_offset /
  *                                      flatten_image_boundary        dataset_construction.py is its dataset-preparation kin)
  *   oct_elastic_batch                  (none: the smooth random elastic deformation of the U-Net paper, a training augmentation)
+ *   oct_contrast_batch                 (none: CLAHE / percentile stretch of the uint8 scans in front of training, evaluation
+ *                                      and prediction)
  *   oct_edge_weight_map / oct_unet_set_pixel_weights  (none: the border weight map of the U-Net paper / ReLayNet's boundary-
  *                                      weighted cross-entropy, as a per-pixel weight of the focal / BCE term)
  *   oct_calibration_counts / oct_temperature_apply / oct_temperature_nll  (none: reliability counts, ECE / NLL / Brier and
@@ -609,6 +611,48 @@ int oct_elastic_batch(const unsigned char* x_u8_dev, const unsigned char* labels
 #define OCT_EDGE_WEIGHT_MAX_DIM    16384
 int oct_edge_weight_map(const unsigned char* labels_dev, int B, int H, int W, int n_cls, int radius, const float* lut_dev,
                         float* weights_dev, oct_stream_t stream);
+
+/* ---- contrast normalisation: CLAHE and percentile stretch of uint8 scans, on the device ----
+ * x: (B,H,W,ch) bytes, ch in 1..4, every channel on its own; out: the same shape.  Defined in integers (common/utils.py
+ * contrast_luts_reference / contrast_reference restate it and give the same bytes):
+ *   tiles:   tile row r of tiles_y covers the image rows [r H / tiles_y, (r+1) H / tiles_y) (floor), tile columns alike;
+ *            A = the tile's pixel count, h[0..255] its histogram of one channel.
+ *   LUT of a tile, OCT_CONTRAST_CLAHE:
+ *            L = A when clip_q8 = 0 (no limit), else max(1, (clip_q8 A) >> 16) in 64 bits -- clip_q8 / 256 is the limit in
+ *            units of the uniform bin height A / 256;  E = sum_i max(h[i] - L, 0);  with r = E mod 256,
+ *            h'[i] = min(h[i], L) + E / 256 + [(i+1) r / 256 > i r / 256]   (floors; one redistribution pass, the remainder
+ *            spread evenly; a bin may exceed L again);  c[i] = sum_{j<=i} h'[j], c[255] = A;  lut[i] = (255 c[i] + A / 2) / A.
+ *   LUT of a tile, OCT_CONTRAST_STRETCH:
+ *            c = cumulative sum of h;  v_lo = min{i : c[i] > lo_bp A / 10000 (floor)},  v_hi = min{i : 10000 c[i] >= hi_bp A};
+ *            the identity if v_hi <= v_lo, else lut[i] = 0 for i <= v_lo, 255 for i >= v_hi and between them
+ *            ((i - v_lo) 255 + (v_hi - v_lo) / 2) / (v_hi - v_lo).
+ *   apply:   Cy[r] = y0_r + y1_r - 1 is twice the centre of tile row r = [y0_r, y1_r).  For pixel row y:
+ *            r = clamp(#{i : Cy[i] <= 2y} - 1, 0, max(tiles_y - 2, 0)), Dy = Cy[r+1] - Cy[r], ay = clamp(2y - Cy[r], 0, Dy);
+ *            with tiles_y = 1: r = 0, ay = 0, Dy = 1 and the "next" row is row 0.  Columns alike: c, ax, Dx.  With v00, v01,
+ *            v10, v11 the LUT values of the input byte in the tiles (r,c), (r,c+1), (r+1,c), (r+1,c+1):
+ *            out = ((Dy-ay) ((Dx-ax) v00 + ax v01) + ay ((Dx-ax) v10 + ax v11) + Dy Dx / 2) / (Dy Dx)      (< 2^32 throughout).
+ * Workspace: oct_contrast_workspace_bytes; 0 = this shape or descriptor is refused.  After the call its first
+ * B * ch * tiles_y * tiles_x * 256 bytes are the LUTs in (B, ch, tiles_y, tiles_x, 256) order; what lies behind them is the
+ * implementation's (the uint32 histograms).  out_dev == x_dev is allowed: the LUTs are finished before the apply pass and
+ * one thread owns each byte.  No allocation, no host wait, asynchronous on `stream`, graph-capturable (one memset node and
+ * three kernel nodes); the histograms are merged with integer atomics only, so repeated calls give the same bytes.
+ * Errors (negative, nothing launched): null pointers; B outside 1..65535; H or W outside 1..OCT_CONTRAST_MAX_DIM; ch
+ * outside 1..4; an unknown method; tiles outside 1..OCT_CONTRAST_MAX_TILES; H / tiles_y or W / tiles_x (floor) below
+ * OCT_CONTRAST_MIN_TILE; clip_q8 neither 0 nor in 256..65535 (CLAHE); not 0 <= lo_bp < hi_bp <= 10000 (stretch); ws_bytes
+ * too small; the workspace not 4-byte aligned; out_dev overlapping x_dev without being it; the workspace overlapping
+ * x_dev or out_dev. */
+#define OCT_CONTRAST_MAX_TILES 16
+#define OCT_CONTRAST_MIN_TILE  8
+#define OCT_CONTRAST_MAX_DIM   4096
+enum { OCT_CONTRAST_CLAHE = 0, OCT_CONTRAST_STRETCH = 1 };
+typedef struct oct_contrast_desc {
+    int method, tiles_y, tiles_x;
+    unsigned clip_q8;       /* CLAHE: round(clip * 256), 0 = no limit */
+    int lo_bp, hi_bp;       /* stretch: the two percentiles in basis points */
+} oct_contrast_desc;
+size_t oct_contrast_workspace_bytes(int B, int H, int W, int ch, const oct_contrast_desc* d);
+int oct_contrast_batch(const unsigned char* x_dev, int B, int H, int W, int ch, const oct_contrast_desc* d,
+                       void* ws_dev, size_t ws_bytes, unsigned char* out_dev, oct_stream_t stream);
 
 /* ---- pad and crop on device: scans whose size is no multiple of 2^pool_layers ----
  * oct_pad_batch places a (B,H,W,ch) batch -- uint8 (is_u8) or float32 -- at (top, left) of a (B,Hp,Wp,ch) batch of the same

@@ -78,6 +78,16 @@ class ComponentRuleC(C.Structure):
     _fields_ = [("min_pixels", C.c_uint * 32), ("keep_largest", C.c_uint), ("fill_mode", C.c_int), ("fill_label", C.c_int)]
 
 
+class ContrastDesc(C.Structure):
+    """``oct_contrast_desc``: method, tile grid and clip limit / percentiles of one ``oct_contrast_batch`` call
+    (``common.utils.contrast_desc`` packs a validated spec into it)."""
+    _fields_ = [("method", C.c_int), ("tiles_y", C.c_int), ("tiles_x", C.c_int), ("clip_q8", C.c_uint), ("lo_bp", C.c_int),
+                ("hi_bp", C.c_int)]
+
+
+CONTRAST_CLAHE, CONTRAST_STRETCH = 0, 1
+
+
 class UNetIO(C.Structure):
     _fields_ = [("probs", C.c_void_p), ("argmax", C.c_void_p), ("labels", C.c_void_p)]
 
@@ -161,6 +171,9 @@ SYMBOLS = [
     ("oct_elastic_batch", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                     C.c_void_p]),
     ("oct_edge_weight_map", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("oct_contrast_workspace_bytes", C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, _P(ContrastDesc)]),
+    ("oct_contrast_batch", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _P(ContrastDesc), C.c_void_p, C.c_size_t,
+                                     C.c_void_p, C.c_void_p]),
     ("oct_pad_batch", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                 C.c_float, C.c_void_p, C.c_void_p]),
     ("oct_crop_batch", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,

@@ -623,3 +623,234 @@ def edge_weight_reference(labels, n_cls: int, radius: int, lut) -> np.ndarray:
         raise ValueError(f"edge_weight_reference: lut must have radius^2 + 2 = {int(radius) ** 2 + 2} entries")
     idx = edge_index_reference(labels, n_cls, radius)
     return np.where(idx >= 0, lut[np.maximum(idx, 0)], np.float32(0.0)).astype(np.float32)
+
+
+# ---- contrast normalisation: the spec check and the numpy restatement of oct_contrast_batch (include/oct_unet.h) ----
+CONTRAST_METHODS = ("clahe", "stretch")
+CONTRAST_MAX_TILES, CONTRAST_MIN_TILE, CONTRAST_MAX_DIM = 16, 8, 4096
+CONTRAST_FILE = "contrast.json"
+
+
+def check_contrast(spec, hw=None):
+    """The validated spec of the contrast stage (``contrast=`` of ``TrainingParams``, ``EvaluationParameters``,
+    ``PredictionParams``, ``Model.predict``): ``None`` (off) stays ``None``; else a dict ``{"method": "clahe" | "stretch",
+    "tiles": (ty, tx) [default (8, 8), each in 1..16], "clip": None | 0 (no limit) | a float in 1..255.99, in units of the
+    uniform bin height ("clahe" only), "percentiles": (lo, hi) in percent with 0 <= lo < hi <= 100 [default (1, 99)]
+    ("stretch" only)}``.  Returns a new dict with every key of its method set, ready for ``json.dumps``.  ``hw = (H, W)``
+    also checks the image size: ``H, W <= 4096`` and tiles of at least 8 x 8 pixels (``H // ty >= 8``, ``W // tx >= 8``; a
+    one-pixel tile would equalise to a constant).  ``ValueError`` outside that, and for unknown keys."""
+    if spec is None:
+        return None
+    if not isinstance(spec, dict):
+        raise ValueError(f"contrast must be None or a dict with the keys method, tiles, clip, percentiles, not {spec!r}")
+    unknown = sorted(set(spec) - {"method", "tiles", "clip", "percentiles"})
+    if unknown:
+        raise ValueError(f"contrast: unknown keys {unknown}")
+    method = spec.get("method")
+    if method not in CONTRAST_METHODS:
+        raise ValueError(f"contrast: method must be one of {CONTRAST_METHODS}, not {method!r}")
+    tiles = spec.get("tiles", (8, 8))
+    try:
+        ty, tx = tiles
+        bad = any(isinstance(t, bool) or int(t) != t for t in (ty, tx))
+    except (TypeError, ValueError):
+        bad = True
+    if bad or not (1 <= int(ty) <= CONTRAST_MAX_TILES and 1 <= int(tx) <= CONTRAST_MAX_TILES):
+        raise ValueError(f"contrast: tiles must be two integers (ty, tx) in 1..{CONTRAST_MAX_TILES}, not {tiles!r}")
+    out = {"method": method, "tiles": [int(ty), int(tx)]}
+    if method == "clahe":
+        if "percentiles" in spec:
+            raise ValueError('contrast: percentiles belong to method "stretch", not "clahe"')
+        clip = spec.get("clip")
+        if clip is not None:
+            try:
+                clip = float(clip)
+            except (TypeError, ValueError):
+                raise ValueError(f"contrast: clip must be None, 0 or a number >= 1, not {clip!r}") from None
+            if clip == 0.0:
+                clip = None
+            elif not (np.isfinite(clip) and clip >= 1.0 and round(clip * 256) <= 65535):
+                raise ValueError(f"contrast: clip must be None, 0 (no limit) or in 1..255.99 (units of the uniform bin height), not {clip}")
+        out["clip"] = clip
+    else:
+        if "clip" in spec:
+            raise ValueError('contrast: clip belongs to method "clahe", not "stretch"')
+        pct = spec.get("percentiles", (1, 99))
+        try:
+            lo, hi = (float(p) for p in pct)
+            lo_bp, hi_bp = round(lo * 100), round(hi * 100)
+        except (TypeError, ValueError, OverflowError):
+            raise ValueError(f"contrast: percentiles must be two numbers (lo, hi), not {pct!r}") from None
+        if not 0 <= lo_bp < hi_bp <= 10000:
+            raise ValueError(f"contrast: percentiles need 0 <= lo < hi <= 100 (in steps of 0.01), not {pct!r}")
+        out["percentiles"] = [lo, hi]
+    if hw is not None:
+        H, W = int(hw[0]), int(hw[1])
+        if not (1 <= H <= CONTRAST_MAX_DIM and 1 <= W <= CONTRAST_MAX_DIM):
+            raise ValueError(f"contrast: images of {H} x {W}: H and W must be in 1..{CONTRAST_MAX_DIM}")
+        if H // out["tiles"][0] < CONTRAST_MIN_TILE or W // out["tiles"][1] < CONTRAST_MIN_TILE:
+            raise ValueError(f"contrast: tiles {tuple(out['tiles'])} on {H} x {W} images leave tiles of {H // out['tiles'][0]} x "
+                             f"{W // out['tiles'][1]} pixels: need at least {CONTRAST_MIN_TILE} x {CONTRAST_MIN_TILE}")
+    return out
+
+
+def contrast_desc(spec) -> Tuple[int, int, int, int, int, int]:
+    """The integers of ``oct_contrast_desc`` for a spec: ``(method, tiles_y, tiles_x, clip_q8, lo_bp, hi_bp)`` with
+    ``clip_q8 = round(clip * 256)`` (0 = no limit) and the percentiles in basis points."""
+    s = check_contrast(spec)
+    if s is None:
+        raise ValueError("contrast_desc: the spec is None (off)")
+    ty, tx = s["tiles"]
+    if s["method"] == "clahe":
+        return 0, ty, tx, 0 if s["clip"] is None else int(round(s["clip"] * 256)), 0, 0
+    lo, hi = s["percentiles"]
+    return 1, ty, tx, 0, int(round(lo * 100)), int(round(hi * 100))
+
+
+def read_contrast_file(model_path):
+    """The spec in ``contrast.json`` beside the checkpoint ``model_path`` (written by ``train_model(contrast=)``), validated;
+    ``None`` when there is no such file."""
+    path = Path(model_path).parent / CONTRAST_FILE
+    if not path.is_file():
+        return None
+    with open(path, "r") as f:
+        return check_contrast(json.load(f))
+
+
+def resolve_contrast(contrast, model_path):
+    """What ``contrast=`` of ``EvaluationParameters`` / ``PredictionParams`` means for the checkpoint ``model_path``: a dict
+    is validated, ``"model"`` reads ``contrast.json`` beside the checkpoint (``ValueError`` if it is absent), ``None`` stays
+    off -- with one warning if the model was trained with a ``contrast.json``."""
+    if isinstance(contrast, str):
+        if contrast != "model":
+            raise ValueError(f'contrast must be None, a dict or "model", not {contrast!r}')
+        spec = read_contrast_file(model_path)
+        if spec is None:
+            raise ValueError(f'contrast="model": no {CONTRAST_FILE} beside {model_path}')
+        return spec
+    if contrast is None and model_path is not None and (Path(model_path).parent / CONTRAST_FILE).is_file():
+        log.warning(f"{Path(model_path).parent / CONTRAST_FILE} says the model was trained on contrast-normalised scans, but "
+                    'contrast is None: the scans are used as given (contrast="model" applies the file)')
+    return check_contrast(contrast)
+
+
+def _contrast_input(x, spec, what: str):
+    x = np.asarray(x)
+    if x.dtype != np.uint8 or x.ndim != 4 or not 1 <= x.shape[3] <= 4 or x.shape[0] < 1:
+        raise ValueError(f"{what}: x must be uint8 (B,H,W,ch) with ch in 1..4 and B >= 1, not {x.dtype} {x.shape}")
+    return x, check_contrast(spec, hw=x.shape[1:3]), contrast_desc(spec)
+
+
+def _contrast_axis(n: int, t: int):
+    """Cell, next cell, weight of the next cell and span of every position of an axis of ``n`` pixels in ``t`` tiles."""
+    e = (np.arange(t + 1, dtype=np.int64) * n) // t
+    if t == 1:
+        z = np.zeros(n, np.int64)
+        return z, z, z, np.ones(n, np.int64)
+    cen = e[:-1] + e[1:] - 1                                   # twice the tile centres
+    pos = 2 * np.arange(n, dtype=np.int64)
+    r = np.clip(np.searchsorted(cen, pos, side="right") - 1, 0, t - 2)
+    D = cen[r + 1] - cen[r]
+    return r, r + 1, np.clip(pos - cen[r], 0, D), D
+
+
+def contrast_luts_reference(x, spec) -> np.ndarray:
+    """The look-up tables of ``oct_contrast_batch`` by its definition (include/oct_unet.h): uint8 ``(B, ch, ty, tx, 256)``
+    for uint8 ``x`` (B,H,W,ch).  Integers only: the kernel leaves the same bytes at the head of its workspace."""
+    x, s, (method, ty, tx, clip_q8, lo_bp, hi_bp) = _contrast_input(x, spec, "contrast_luts_reference")
+    B, H, W, ch = x.shape
+    ey, ex = (np.arange(ty + 1) * H) // ty, (np.arange(tx + 1) * W) // tx
+    luts = np.empty((B, ch, ty, tx, 256), np.uint8)
+    slots = (np.arange(B * ch, dtype=np.int64) * 256)[:, None]
+    i = np.arange(256, dtype=np.int64)
+    for r in range(ty):
+        for c in range(tx):
+            tile = x[:, ey[r]:ey[r + 1], ex[c]:ex[c + 1], :]
+            A = int(tile.shape[1] * tile.shape[2])
+            flat = tile.reshape(B, A, ch).transpose(0, 2, 1).reshape(B * ch, A).astype(np.int64)
+            h = np.bincount((flat + slots).ravel(), minlength=B * ch * 256).reshape(B * ch, 256).astype(np.int64)
+            if method == 0:
+                L = A if clip_q8 == 0 else max(1, (clip_q8 * A) >> 16)
+                E = np.maximum(h - L, 0).sum(axis=1, keepdims=True)
+                rem = E % 256
+                h = np.minimum(h, L) + E // 256 + ((((i + 1) * rem) // 256) > ((i * rem) // 256))
+                lut = (np.cumsum(h, axis=1) * 255 + A // 2) // A
+            else:
+                cum = np.cumsum(h, axis=1)
+                v_lo = (cum <= (lo_bp * A) // 10000).sum(axis=1, keepdims=True)       # cum never decreases
+                v_hi = (cum * 10000 < hi_bp * A).sum(axis=1, keepdims=True)
+                span = np.maximum(v_hi - v_lo, 1)
+                lut = np.where(i <= v_lo, 0, np.where(i >= v_hi, 255, ((i - v_lo) * 255 + span // 2) // span))
+                lut = np.where(v_hi <= v_lo, i, lut)
+            luts[:, :, r, c, :] = lut.reshape(B, ch, 256).astype(np.uint8)
+    return luts
+
+
+def contrast_reference(x, spec, luts=None) -> np.ndarray:
+    """What ``oct_contrast_batch`` computes: uint8 ``x`` (B,H,W,ch) -> the same shape, every byte mapped through the
+    look-up tables of the four tiles around it (``contrast_luts_reference``; ``luts``: those, if already computed) and
+    blended bilinearly between the tile centres, in integers."""
+    x, s, (method, ty, tx, *_) = _contrast_input(x, spec, "contrast_reference")
+    B, H, W, ch = x.shape
+    r, r1, ay, Dy = (a[None, :, None, None] for a in _contrast_axis(H, ty))
+    c, c1, ax, Dx = (a[None, None, :, None] for a in _contrast_axis(W, tx))
+    ci = np.arange(ch)[None, None, None, :]
+    out = np.empty_like(x)
+    for b0 in range(0, B, 16):          # in chunks: the int64 intermediates are eight times the batch
+        xb = x[b0:b0 + 16]
+        lb = contrast_luts_reference(xb, spec) if luts is None else np.asarray(luts)[b0:b0 + 16]
+        bi = np.arange(xb.shape[0])[:, None, None, None]
+        v = xb.astype(np.int64)
+        v00, v01 = lb[bi, ci, r, c, v].astype(np.int64), lb[bi, ci, r, c1, v].astype(np.int64)
+        v10, v11 = lb[bi, ci, r1, c, v].astype(np.int64), lb[bi, ci, r1, c1, v].astype(np.int64)
+        num = (Dy - ay) * ((Dx - ax) * v00 + ax * v01) + ay * ((Dx - ax) * v10 + ax * v11) + (Dy * Dx) // 2
+        out[b0:b0 + 16] = (num // (Dy * Dx)).astype(np.uint8)
+    return out
+
+
+def contrast_images(images_u8, spec, device=None, chunk: int = 64) -> np.ndarray:
+    """A whole dataset array uint8 (N,H,W,ch) through the contrast stage -> a new array of the same shape.  With a GPU
+    (``device``: a torch device or its name; default: the current GPU if there is one) the images go through
+    ``oct_contrast_batch`` in chunks of ``chunk`` over pinned staging buffers; without one through ``contrast_reference``.
+    Both give the same bytes.  ``spec`` None returns the input."""
+    if spec is None:
+        return images_u8
+    x, s, _ = _contrast_input(images_u8, spec, "contrast_images")
+    import torch
+    if device is None and not torch.cuda.is_available():
+        return contrast_reference(x, s)
+    from .. import _hip
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if dev.type != "cuda":
+        raise ValueError(f"contrast_images: device must be a GPU or None, not {device!r}")
+    N = x.shape[0]
+    chunk = max(1, min(int(chunk), N, 65535))
+    d = _hip.ContrastDesc(*contrast_desc(s))
+    import ctypes as C
+    need = int(_hip.lib().oct_contrast_workspace_bytes(chunk, x.shape[1], x.shape[2], x.shape[3], C.byref(d)))
+    if not need:
+        raise _hip.OctError(f"contrast_images: refused: {_hip.lib().oct_last_error().decode()}")
+    out = np.empty_like(x)
+    with torch.cuda.device(dev):
+        stage = [torch.empty((chunk,) + x.shape[1:], dtype=torch.uint8).pin_memory() for _ in range(2)]
+        on_dev = [torch.empty((chunk,) + x.shape[1:], dtype=torch.uint8, device=dev) for _ in range(2)]
+        done = [None, None]
+        ws = torch.empty((need,), dtype=torch.uint8, device=dev)
+        for k, n0 in enumerate(range(0, N, chunk)):
+            n, s_ = min(chunk, N - n0), k % 2
+            if done[s_] is not None:                      # the slot's previous chunk has landed: take it out, refill
+                done[s_][0].synchronize()
+                out[done[s_][1]:done[s_][1] + done[s_][2]] = stage[s_][:done[s_][2]].numpy()
+            stage[s_][:n].copy_(torch.from_numpy(np.ascontiguousarray(x[n0:n0 + n])))
+            on_dev[s_][:n].copy_(stage[s_][:n], non_blocking=True)
+            _hip.call("oct_contrast_batch", dev, on_dev[s_].data_ptr(), n, x.shape[1], x.shape[2], x.shape[3], C.byref(d),
+                      ws.data_ptr(), ws.numel(), on_dev[s_].data_ptr(), _hip.stream_ptr(dev))
+            stage[s_][:n].copy_(on_dev[s_][:n], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            done[s_] = (ev, n0, n)
+        for s_ in (0, 1):
+            if done[s_] is not None:
+                done[s_][0].synchronize()
+                out[done[s_][1]:done[s_][1] + done[s_][2]] = stage[s_][:done[s_][2]].numpy()
+    return out

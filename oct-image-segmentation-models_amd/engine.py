@@ -859,6 +859,38 @@ class UNetEngine:
                   int(H), int(W) * k, int(top), int(left) * k, out.data_ptr(), self._stream())
         return out
 
+    # ---- contrast normalisation: CLAHE / percentile stretch of uint8 scans ---------------------------
+    def contrast(self, x_u8: torch.Tensor, spec, out=None, ws=None) -> torch.Tensor:
+        """(B,H,W,ch) uint8, ch in 1..4 -> the same shape through the contrast stage ``spec`` (``common.utils.check_contrast``'s
+        dict) on the device (``oct_contrast_batch``; ``common.utils.contrast_reference`` gives the same bytes).  Any image
+        size up to 4096 x 4096 whose tiles keep 8 x 8 pixels.  ``out``: optional tensor to write into; it may be ``x_u8``
+        itself.  ``ws``: optional uint8 workspace (``oct_contrast_workspace_bytes``), else one kept in the engine's buffer
+        set of this batch size; its first B*ch*ty*tx*256 bytes are the look-up tables after the call.  Asynchronous on the
+        current stream."""
+        from .common.utils import check_contrast, contrast_desc
+        _hip.expect(x_u8, "contrast: x (B,H,W,ch)", device=self.device, dtype=torch.uint8, shape=(None, None, None, None))
+        B, H, W, ch = x_u8.shape
+        try:
+            s = check_contrast(spec, hw=(H, W))
+            if s is None:
+                raise ValueError("contrast: the spec is None (off)")
+        except ValueError as e:
+            raise OctError(str(e)) from None
+        desc = contrast_desc(s)
+        d = _hip.ContrastDesc(*desc)
+        need = int(_hip.lib().oct_contrast_workspace_bytes(B, H, W, ch, C.byref(d)))
+        if not need:
+            raise OctError(f"contrast: unsupported shape {tuple(x_u8.shape)}: need 1 <= B <= 65535 and 1..4 channels")
+        if ws is None:
+            ws = self._buf(B, ("contrast_ws", H, W, ch) + desc[:3], (need,), torch.uint8)
+        _hip.expect(ws, "contrast: workspace", device=self.device, dtype=torch.uint8, shape=(None,))
+        if out is None:
+            out = torch.empty_like(x_u8)
+        _hip.expect(out, "contrast: out", device=self.device, dtype=torch.uint8, shape=tuple(x_u8.shape))
+        _hip.call("oct_contrast_batch", self.device, x_u8.data_ptr(), B, H, W, ch, C.byref(d), ws.data_ptr(), ws.numel(),
+                  out.data_ptr(), self._stream())
+        return out
+
     # ---- weights exchange --------------------------------------------------------------------------
     def get_weights(self) -> List[np.ndarray]:
         """Keras ``get_weights()`` order: Conv2D [kernel HWIO, bias]; BN [gamma, beta, moving_mean, moving_var]."""

@@ -16,6 +16,7 @@ are unknown: out of every Dice count, no surface element at their rim, no truth 
 ground-truth pictures; without it the value is refused and every file is what it was."""
 from __future__ import annotations
 
+import json
 import logging as log
 import os
 import time
@@ -194,7 +195,8 @@ def evaluate_model(eval_params: EvaluationParameters) -> List[EvaluationOutput]:
                       ignore_label=ignore_label, tta=getattr(eval_params, "tta", None),
                       calibration_bins=calibration_bins, temperature=temperature,
                       **({"ordered_decode": True} if ordered_decode else {}),
-                      **({"components": components} if components is not None else {})) as run:
+                      **({"components": components} if components is not None else {}),
+                      **({"contrast": eval_params.contrast} if getattr(eval_params, "contrast", None) is not None else {})) as run:
         t_prev = time.time()
         for batch in run:
             b0, b1 = lo + batch.lo, lo + batch.hi
@@ -350,6 +352,8 @@ def _save_image_evaluation_results(eval_params, eval_image, image_name, predicte
     attrs = common_utils.result_attrs(eval_params.model_path, image_name, predict_time=np.array(predict_time))
     if getattr(eval_params, "tta", None):
         attrs["tta_views"] = np.array(",".join(eval_params.tta), dtype="S1000")      # only when set: other files stay as they were
+    if getattr(eval_params, "contrast", None) is not None:
+        attrs["contrast"] = np.array(json.dumps(eval_params.contrast, sort_keys=True), dtype="S1000")      # likewise
     h5io.save(output_dir / Path(EVALUATION_RESULTS_FILENAME), ds, attrs)
 
 
@@ -435,6 +439,8 @@ def save_eval_config_file(eval_params: EvaluationParameters):
         attrs["ignore_label"] = np.array(int(eval_params.ignore_label))      # likewise
     if getattr(eval_params, "tta", None):
         attrs["tta_views"] = np.array(",".join(eval_params.tta), dtype="S1000")      # likewise
+    if getattr(eval_params, "contrast", None) is not None:
+        attrs["contrast"] = np.array(json.dumps(eval_params.contrast, sort_keys=True), dtype="S1000")      # likewise
     if getattr(eval_params, "calibration_bins", 0):
         attrs["calibration_bins"] = np.array(int(eval_params.calibration_bins))      # likewise
     if getattr(eval_params, "temperature", 1.0) != 1.0:

@@ -29,7 +29,14 @@ class EvaluationParameters:
                  gs_device_ties: str = "host", gs_workers: Optional[int] = None, metrics_device: bool = False,
                  png_plots: bool = False, pad_mode: Optional[str] = None, pad_value=0, ignore_label: Optional[int] = None,
                  tta=None, calibration_bins: int = 0, temperature: float = 1.0, ordered_decode: bool = False,
-                 components=None):
+                 components=None, contrast=None):
+        # extension: contrast normalisation of the uint8 scans in front of the prediction.  None: off; a
+        # spec of common.utils.check_contrast ({"method": "clahe" | "stretch", "tiles", "clip" | "percentiles"}); or "model": the
+        # contrast.json that train_model(contrast=) wrote beside the checkpoint -- an error if that file is absent.  Every batch
+        # is normalised on the device, at the scans' own size and in front of the pad; the result files record the spec's JSON
+        # as the attribute contrast; the pictures keep showing the scans as given.  With None and a contrast.json present: one
+        # warning, nothing changes, nothing is launched
+        self.contrast = utils.resolve_contrast(contrast, model_path)
         # extension: connected components of the arg-max class map.  A ComponentRule, or a dict of its
         # keywords (connectivity, min_pixels, keep_largest, fill): components that the rule removes -- islands below min_pixels,
         # all but the largest of a class -- are refilled on the device.  Every image gains cc_evaluation_results.hdf5

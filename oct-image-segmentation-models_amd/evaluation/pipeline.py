@@ -15,7 +15,7 @@ from typing import Iterable, Iterator, NamedTuple, Optional, Tuple
 import numpy as np
 import torch
 
-from ..common.utils import check_pad_mode, check_tta, padded_geometry
+from ..common.utils import check_contrast, check_pad_mode, check_tta, padded_geometry
 from ..min_path_processing.device_search import DeviceMinPath, LazyPool, merge_ties
 from ..min_path_processing.pool import SegmentPool, default_workers
 from .calibration import CalibrationCounts, check_bins, check_temperature
@@ -172,12 +172,18 @@ class BatchedPredictor:
     ``oct_component_filter`` run on the batch's copy of the arg-max maps -- the MEAN prediction's under ``mc_samples`` / ``tta``,
     the cropped ones under ``hw``; a ``temperature`` does not move the arg-max -- and ``Batch.components`` holds ``(clean_labels,
     stats, removed)``.  It reads neither the ground truth nor the probabilities and writes only buffers of its own: labels,
-    maps, the search and every other stage see the arg-max maps as before.  Without it nothing is launched."""
+    maps, the search and every other stage see the arg-max maps as before.  Without it nothing is launched.
+
+    With ``contrast`` (a spec of ``common.utils.check_contrast``: CLAHE or a percentile stretch) the per-batch device copy of
+    the landing buffer into the chain's fixed input becomes ``engine.contrast(landing buffer, spec, out=fixed input)``
+    (``oct_contrast_batch``): the graph, the pad in front of the forward, the TTA views and the Monte-Carlo chain see the
+    normalised batch, normalised at the true size.  Labels and maps equal those of a run on ``contrast_reference(images)``.
+    Without it the copy stays and nothing is launched."""
 
     def __init__(self, engine, batch: int, want_maps: bool = True, bg_ilm: bool = True, bg_csi: bool = False,
                  surface=None, minpath=None, confusion=None, soft_maps: bool = False, mc_samples: int = 0, mc_step0: int = 0,
                  hw=None, pad_mode: Optional[str] = None, pad_value=0, tta=None, calibration=None, temperature: float = 1.0,
-                 ordered=None, components=None):
+                 ordered=None, components=None, contrast=None):
         self.temperature = check_temperature(temperature)
         if self.temperature != 1.0 and (mc_samples or tta):
             raise ValueError("temperature != 1 with mc_samples or tta: the samples would have to be tempered before they are "
@@ -202,6 +208,7 @@ class BatchedPredictor:
                                  f"the padded size {Hp}x{Wp}")
             (H, W), self.at = (int(hw[0]), int(hw[1])), (top, left)
         self.hw = (H, W)
+        self.contrast = check_contrast(contrast, hw=self.hw)      # at the true size: normalise first, pad afterwards
         self.x_dev = torch.zeros((self.B, H, W, ic), dtype=torch.uint8, device=dev)       # the graph's fixed input (true size)
         self.x_stage = [torch.empty_like(self.x_dev) for _ in range(2)]                    # H2D landing buffers
         self.x_pin = [torch.empty((self.B, H, W, ic), dtype=torch.uint8).pin_memory() for _ in range(2)]
@@ -288,7 +295,10 @@ class BatchedPredictor:
             if i + 1 < nb:
                 upload(i + 1)                                                           # overlaps the forward of batch i
             main.wait_event(up_done[s])
-            self.x_dev.copy_(self.x_stage[s])                                           # D2D, then the staging buffer is free
+            if self.contrast is None:
+                self.x_dev.copy_(self.x_stage[s])                                       # D2D, then the staging buffer is free
+            else:                                                                       # the same move through the contrast stage
+                eng.contrast(self.x_stage[s], self.contrast, out=self.x_dev)
             x_free[s].record(main)
             if self.mc_samples:
                 self._infer(False)
@@ -359,7 +369,7 @@ class BatchedPredictor:
 def host_batches(model, images: np.ndarray, batch: int, *, gt_u8: Optional[np.ndarray] = None, surface=None,
                  minpath=None, confusion=None, soft_maps: bool = False, mc_samples: int = 0, mc_step0: int = 0,
                  pad_mode: Optional[str] = None, pad_value=0, tta=None, calibration_bins: int = 0,
-                 temperature: float = 1.0, ordered=None, components=None) -> Iterator[Batch]:
+                 temperature: float = 1.0, ordered=None, components=None, contrast=None) -> Iterator[Batch]:
     """The same records for images that are not uint8: x / 255 on the host (``Model.predict_labels``), one synchronous
     forward per batch, no overlap.  ``surface`` / ``minpath`` / ``confusion`` / ``soft_maps`` / ``mc_samples`` /
     ``mc_step0`` / ``tta`` as in ``BatchedPredictor``; each stage writes its own output buffers.  ``pad_mode`` / ``pad_value`` (in raw
@@ -367,10 +377,12 @@ def host_batches(model, images: np.ndarray, batch: int, *, gt_u8: Optional[np.nd
     here -- calibration exists for raw uint8 images only.  ``ordered`` (anything true, an ``OrderedDecode`` included):
     ``Model.predict_labels`` runs the ordered decode on the batch's probabilities while they are on the device, and
     ``Batch.ordered`` is filled as by ``BatchedPredictor``.  ``components`` (a ``Components``): a stage like the others, on the
-    uploaded class maps; ``Batch.components`` likewise."""
+    uploaded class maps; ``Batch.components`` likewise.  ``contrast``: refused here -- the contrast stage is defined on bytes."""
     if check_bins(calibration_bins) or check_temperature(temperature) != 1.0:
         raise ValueError("calibration_bins / temperature need raw uint8 images: the path for other dtypes (host_batches) has no "
                          "calibration stage")
+    if contrast is not None:
+        raise ValueError("contrast needs raw uint8 images: the path for other dtypes (host_batches) has no contrast stage")
     pad_mode, pad_value = check_pad_mode(pad_mode, pad_value)
     tta = check_tta(tta, mc_samples)
     stages = _stages(surface, confusion, minpath, have_gt=gt_u8 is not None, **({"components": components} if components is not None else {}))
@@ -451,6 +463,10 @@ class InferenceRun:
     and changes no output of ``ordered_decode``, ``gs_device``, ``confusion`` or ``calibration_bins``; the searches keep reading
     the arg-max maps.  A rule that does not fit ``num_classes`` is a ``ValueError``.
 
+    ``contrast`` (a spec of ``common.utils.check_contrast``; None: off) is passed to ``BatchedPredictor``: every batch is
+    normalised on the device, at the true size and in front of the pad, before the chain sees it.  It
+    needs raw uint8 images: for another dtype it is a ``ValueError``.  Pictures keep showing the scans as given.
+
     ``batches`` replaces the model by a ready source of records (tests of the host side: no device is touched)."""
 
     def __init__(self, model, images: np.ndarray, batch: int, num_classes: int, *, gt: Optional[np.ndarray] = None,
@@ -458,8 +474,12 @@ class InferenceRun:
                  gs_workers: Optional[int] = None, batches: Optional[Iterable[Batch]] = None, surface: bool = True,
                  confusion: bool = False, soft_maps: bool = False, mc_samples: int = 0, mc_step0: int = 0,
                  pad_mode: Optional[str] = None, pad_value=0, ignore_label: Optional[int] = None, tta=None,
-                 calibration_bins: int = 0, temperature: float = 1.0, ordered_decode: bool = False, components=None):
+                 calibration_bins: int = 0, temperature: float = 1.0, ordered_decode: bool = False, components=None,
+                 contrast=None):
         pad_mode, pad_value = check_pad_mode(pad_mode, pad_value)
+        contrast = check_contrast(contrast, hw=images.shape[1:3])
+        if images.dtype != np.uint8 and contrast is not None:
+            raise ValueError("contrast needs raw uint8 images: the path for other dtypes (host_batches) has no contrast stage")
         rule = ComponentRule.coerce(components)
         if rule is not None:
             rule.check(num_classes)
@@ -507,6 +527,8 @@ class InferenceRun:
             surface = SurfaceDistances(bs, H, W, C, dev, ignore_label=ignore_label) if gt_u8 is not None and surface else None
             confusion = ConfusionCounts(bs, H, W, C, dev, ignore_label=ignore_label) if gt_u8 is not None and confusion else None
             more = {"components": Components(bs, H, W, C, rule, dev)} if rule is not None else {}      # (only passed when set)
+            if contrast is not None:
+                more["contrast"] = contrast
             if images.dtype != np.uint8:
                 if surface is None and confusion is None:
                     gt_u8 = None

@@ -477,35 +477,53 @@ class Model:
             pad_mode, pad_value = self.pad_mode, self.pad_value
         return check_pad_mode(pad_mode, pad_value)
 
-    def _inference_batches(self, x: np.ndarray, bs: int, pad, **kind):
+    @staticmethod
+    def _contrast_option(contrast, x: np.ndarray):
+        """The validated ``contrast=`` spec of a predict call on host array ``x``: None (off), or a spec that fits the images'
+        size; only raw uint8 images have a contrast stage."""
+        from ..common.utils import check_contrast
+        if contrast is not None and x.dtype != np.uint8:
+            raise ValueError(f"contrast needs raw uint8 images, not {x.dtype}")
+        return check_contrast(contrast, hw=x.shape[1:3])
+
+    def _inference_batches(self, x: np.ndarray, bs: int, pad, contrast=None, **kind):
         """The loop of the predict methods over host array ``x`` in batches of ``bs`` under the validated ``pad`` = (pad_mode,
         pad_value): yields per batch the host slice bounds ``lo, hi``, the engine of the images' geometry and the maps of
         ``UNetEngine.infer(batch, **kind)``, of the images' size.  For a size that is no multiple of 2^pool_layers the engine is
-        that of the padded geometry and ``infer`` pads in front and crops behind."""
+        that of the padded geometry and ``infer`` pads in front and crops behind.  ``contrast`` (a validated spec): the uploaded
+        batch goes through ``UNetEngine.contrast`` in place first, at its true size."""
         n, (H, W) = x.shape[0], x.shape[1:3]
         geom, at = self._geometry((H, W), pad[0])
         eng = self._ensure_engine(min(bs, n), False, hw=geom)
         for lo in range(0, n, bs):
             xb = torch.from_numpy(np.ascontiguousarray(x[lo:lo + bs])).to(eng.device)
+            if contrast is not None:
+                eng.contrast(xb, contrast, out=xb)
             yield lo, min(lo + bs, n), eng, eng.infer(xb, pad=None if at is None else (*at, *pad), **kind)
 
     def predict(self, x, verbose=0, batch_size: Optional[int] = None, pad_mode: Optional[str] = None, pad_value=0,
-                temperature: Optional[float] = None, **kwargs) -> np.ndarray:
+                temperature: Optional[float] = None, contrast=None, **kwargs) -> np.ndarray:
         """(n,H,W,C) float input ALREADY preprocessed to [0,1] (or raw uint8) -> (n,H,W,num_classes) float32.  The engine
         follows the images' size, whatever the config records.  A size that is no multiple of 2^pool_layers needs
         ``pad_mode`` ("edge", "reflect" or "constant" with ``pad_value``, in the units of ``x``): the batch is padded on
         the device in front of the forward and the output cropped behind it (placement: ``common.utils.padded_geometry``).
         ``pad_mode=None`` takes the model's ``pad_mode`` / ``pad_value`` attributes, which are None / 0 unless set.
         ``temperature`` (a number in [1/16, 16]; None or 1.0: off): the probabilities are tempered on the device --
-        softmax(logits / temperature), formed from the probabilities themselves (``UNetEngine.temperature_apply``)."""
+        softmax(logits / temperature), formed from the probabilities themselves (``UNetEngine.temperature_apply``).
+        ``contrast`` (a spec of ``common.utils.check_contrast``; None: off; raw uint8 ``x`` only): every batch is normalised on
+        the device in front of the pad and the forward -- the output is that of ``predict(contrast_reference(x, contrast))``.
+        It is a keyword of the call and not an attribute of the model: ``train_model(contrast=)`` hands ``fit`` arrays that
+        are already normalised."""
         from ..evaluation.calibration import check_temperature
         temperature = 1.0 if temperature is None else check_temperature(temperature)
         pad = self._pad_options(pad_mode, pad_value)
         x = np.asarray(x)
         if x.dtype != np.uint8:
             x = np.ascontiguousarray(x, dtype=np.float32)   # Keras casts the float64 the reference passes to float32
+        contrast = self._contrast_option(contrast, x)
         out = np.empty(x.shape[:3] + (self.config["num_classes"],), np.float32)
-        for lo, hi, eng, maps in self._inference_batches(x, int(batch_size or min(x.shape[0], 32)), pad, want_probs=True, want_argmax=False):
+        for lo, hi, eng, maps in self._inference_batches(x, int(batch_size or min(x.shape[0], 32)), pad, contrast=contrast,
+                                                         want_probs=True, want_argmax=False):
             probs = maps["probs"]
             if temperature != 1.0:
                 eng.temperature_apply(probs, 1.0 / temperature, out=probs)
@@ -637,7 +655,7 @@ class Model:
 
     def predict_labels(self, x_u8: np.ndarray, batch_size: int = 32, want_maps: bool = False, bg_ilm: bool = True,
                        bg_csi: bool = False, soft_maps: bool = False, mc_samples: int = 0, mc_step0: int = 0,
-                       pad_mode: Optional[str] = None, pad_value=0, tta=None, ordered: bool = False):
+                       pad_mode: Optional[str] = None, pad_value=0, tta=None, ordered: bool = False, contrast=None):
         """Raw uint8 images -> uint8 arg-max class maps (n,H,W), computed on the device (1 B/px back instead of
         4*C B/px).  With ``want_maps`` also the (n, C-1, H, W) uint8 boundary maps of
         ``convert_predictions_to_maps_semantic``, computed on the device from the class maps -- or, with ``soft_maps``,
@@ -652,13 +670,16 @@ class Model:
         the boundary maps are those of the cropped tensors.
         With ``ordered`` the ordered decode (``predict_ordered``) of the same probabilities -- the mean ones under
         ``mc_samples`` / ``tta`` -- is appended as the LAST element: ``(labels (n,H,W) uint8, rows (n,C-1,W) uint16, score (n,W)
-        uint32)``."""
+        uint32)``.
+        ``contrast`` as for ``predict`` (uint8 images only): the result is that of ``predict_labels(contrast_reference(x_u8,
+        contrast))``."""
         if soft_maps and not want_maps:
             raise ValueError("soft_maps: needs want_maps=True")
         from ..common.utils import check_tta
         tta = check_tta(tta, mc_samples)
         pad_mode, pad_value = self._pad_options(pad_mode, pad_value)
         x_u8 = np.ascontiguousarray(x_u8)
+        contrast = self._contrast_option(contrast, x_u8)
         if x_u8.dtype != np.uint8:
             # the reference normalises x / 255 whatever the dtype (models/unet.py:87-91); the engine's float32 input
             # path means "already normalised", so do the division here rather than silently skipping it
@@ -672,7 +693,7 @@ class Model:
                 np.empty((x_u8.shape[0], x_u8.shape[2]), np.uint32)),) if ordered else ()
         kind = dict(mc=(mc_samples, mc_step0) if mc_samples else None, tta=tta or None, want_probs=soft_maps or bool(ordered),
                     want_argmax=True)
-        for lo, hi, eng, mc in self._inference_batches(x_u8, batch_size, (pad_mode, pad_value), **kind):
+        for lo, hi, eng, mc in self._inference_batches(x_u8, batch_size, (pad_mode, pad_value), contrast=contrast, **kind):
             probs, am = mc.get("mean_probs", mc.get("probs")), mc["argmax"]
             if dec:
                 for o, t, dt in zip(dec[0], eng.ordered_decode(probs), (np.uint8, np.uint16, np.uint32)):

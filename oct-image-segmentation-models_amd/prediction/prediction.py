@@ -5,6 +5,7 @@ without labels/metrics.  Batched device forward with device arg-max; host tail r
 device (``oct_render_rgba``, ``evaluation/render.py``); ``categorical_pred_N.png`` is out of scope."""
 from __future__ import annotations
 
+import json
 import logging as log
 import os
 import time
@@ -83,7 +84,9 @@ def predict(predict_params: PredictionParams) -> List[PredictionOutput]:
                       pad_value=getattr(predict_params, "pad_value", 0), tta=getattr(predict_params, "tta", None),
                       temperature=getattr(predict_params, "temperature", 1.0),
                       **({"ordered_decode": True} if ordered_decode else {}),
-                      **({"components": components} if components is not None else {})) as run:
+                      **({"components": components} if components is not None else {}),
+                      **({"contrast": predict_params.contrast} if getattr(predict_params, "contrast", None) is not None
+                         else {})) as run:
         t0 = time.time()
         for batch in run:
             b0, b1 = lo + batch.lo, lo + batch.hi
@@ -167,6 +170,8 @@ def save_predict_config_file(predict_params: PredictionParams):
         attrs["mc_step0"] = np.array(int(getattr(predict_params, "mc_step0", 0)))
     if getattr(predict_params, "tta", None):
         attrs["tta_views"] = np.array(",".join(predict_params.tta), dtype="S1000")      # likewise
+    if getattr(predict_params, "contrast", None) is not None:
+        attrs["contrast"] = np.array(json.dumps(predict_params.contrast, sort_keys=True), dtype="S1000")      # likewise
     if getattr(predict_params, "pad_mode", None) is not None:
         attrs["pad_mode"] = np.array(str(predict_params.pad_mode), dtype="S1000")      # likewise, with the constant
         attrs["pad_value"] = np.array(float(getattr(predict_params, "pad_value", 0)))
@@ -207,6 +212,8 @@ def save_image_prediction_results(pred_params, predict_image, image_name, predic
             attrs["mc_samples"] = np.array(int(getattr(pred_params, "mc_samples", 0)))
     if getattr(pred_params, "temperature", 1.0) != 1.0:
         attrs["temperature"] = np.array(float(pred_params.temperature))      # only when set
+    if getattr(pred_params, "contrast", None) is not None:
+        attrs["contrast"] = np.array(json.dumps(pred_params.contrast, sort_keys=True), dtype="S1000")      # only when set
     if ordered is not None:
         od_labels, od_rows = ordered[0], ordered[1]
         np.savetxt(output_dir / Path("od_boundaries.csv"), od_rows, delimiter=",", fmt="%d")

@@ -27,7 +27,14 @@ class PredictionParams:
                  gs_device_ties: str = "host", gs_workers: Union[int, None] = None, gs_labels_device: bool = False,
                  binarize: bool = True, png_plots: bool = False, mc_samples: int = 0, mc_step0: int = 0,
                  pad_mode: Union[str, None] = None, pad_value=0, tta=None, temperature: float = 1.0,
-                 ordered_decode: bool = False, components=None) -> None:
+                 ordered_decode: bool = False, components=None, contrast=None) -> None:
+        # extension: contrast normalisation of the uint8 scans in front of the prediction.  None: off; a
+        # spec of common.utils.check_contrast ({"method": "clahe" | "stretch", "tiles", "clip" | "percentiles"}); or "model": the
+        # contrast.json that train_model(contrast=) wrote beside the checkpoint -- an error if that file is absent.  Every batch
+        # is normalised on the device, at the scans' own size and in front of the pad; the result files record the spec's JSON
+        # as the attribute contrast; the pictures keep showing the scans as given.  With None and a contrast.json present: one
+        # warning, nothing changes, nothing is launched
+        self.contrast = utils.resolve_contrast(contrast, model_path)
         # extension, as EvaluationParameters.components (a ComponentRule or a dict of its keywords): prediction_info.hdf5 gains
         # cc_predicted_labels, component_count, largest_component_pixels and removed_pixels; with png_plots
         # cc_predicted_segmentation_map.png is written.  None: nothing is launched, every file as it was

@@ -114,6 +114,14 @@ def train_model(training_params: TrainingParams, mlflow_params=None):
     data = dataset_loader.open_dataset(training_dataset_path)
     train_images, train_labels = dataset_loader.load_training_data(data)
     val_images, val_labels = dataset_loader.load_validation_data(data)
+    # contrast normalisation: once, here, in front of everything that reads the images (the generators, fit_temperature)
+    contrast = getattr(training_params, "contrast", None)
+    if contrast is not None:
+        for name, arr in (("training", train_images), ("validation", val_images)):
+            if np.asarray(arr).dtype != np.uint8:
+                raise ValueError(f"contrast needs a uint8 dataset: the {name} images are {np.asarray(arr).dtype}")
+        train_images = utils.contrast_images(np.asarray(train_images), contrast)
+        val_images = utils.contrast_images(np.asarray(val_images), contrast)
 
     ignore_label = training_params.ignore_label
     num_classes = _count_classes(train_labels, ignore_label)
@@ -194,6 +202,9 @@ def train_model(training_params: TrainingParams, mlflow_params=None):
     save_foldername = training_params.results_location / Path(timestamp + "_" + model_architecture)
     if rank == 0:
         os.makedirs(save_foldername, exist_ok=True)
+        if contrast is not None:      # beside the checkpoints: the model config cannot carry it (it is UNet(**model_config))
+            with open(save_foldername / Path(utils.CONTRAST_FILE), "w") as f:
+                json.dump(contrast, f, sort_keys=True)
     parallel.barrier()
 
     savemodel = ModelCheckpoint(filepath=save_foldername / Path("model_epoch{epoch:02d}.hdf5"),

@@ -21,7 +21,14 @@ class TrainingParams:
                  early_stopping: bool = True, restore_best_weights: bool = True, patience: int = 50,
                  seed: Union[int, None] = None, aug_device: bool = False, pad_mode: Union[str, None] = None,
                  pad_value=0, ignore_label: Union[int, None] = None, apply_class_weight: bool = False,
-                 fit_temperature: bool = False, elastic: Union[dict, None] = None):
+                 fit_temperature: bool = False, elastic: Union[dict, None] = None, contrast: Union[dict, None] = None):
+        # extension: contrast normalisation (common.utils.check_contrast: {"method": "clahe" | "stretch", "tiles", "clip" |
+        # "percentiles"}).  train_model normalises the training and validation images once, directly
+        # after loading them (uint8 datasets only), so the run equals one on a dataset holding contrast_reference(images); the
+        # spec is written as contrast.json into the run folder, where EvaluationParameters / PredictionParams(contrast="model")
+        # find it.  None: nothing changes, no such file
+        from ..common.utils import check_contrast
+        self.contrast = check_contrast(contrast)
         # extension: elastic deformation (common.augmentation.elastic_spec: p, spacing, max_displacement[, border, fill,
         # fill_label]) of every sample the augmentation list applies to, in front of the list's own augmentation; on the device
         # with aug_device, on the host without.  None: no such stage, nothing changes
