@@ -39,6 +39,8 @@
  *   oct_warp_batch                     (none at training time; the per-column np.roll of roll_image_offset /
  *                                      flatten_image_boundary        dataset_construction.py is its dataset-preparation kin)
  *   oct_elastic_batch                  (none: the smooth random elastic deformation of the U-Net paper, a training augmentation)
+ *   oct_photo_batch                    (none: blur, column shadows and a gamma / brightness / contrast table, a training
+ *                                      augmentation)
  *   oct_contrast_batch                 (none: CLAHE / percentile stretch of the uint8 scans in front of training, evaluation
  *                                      and prediction)
  *   oct_edge_weight_map / oct_unet_set_pixel_weights  (none: the border weight map of the U-Net paper / ReLayNet's boundary-
@@ -591,6 +593,51 @@ typedef struct oct_elastic_op {  /* one per sample of the batch, 40 bytes, in DE
 int oct_elastic_batch(const unsigned char* x_u8_dev, const unsigned char* labels_dev, const oct_elastic_op* ops_dev,
                       int B, int H, int W, int C,
                       unsigned char* x_out_dev, unsigned char* labels_out_dev, oct_stream_t stream);
+
+/* ---- photometric augmentation on device: (B,H,W,C) u8 images -> u8 images of the same shape through a separable blur,
+ * column shadows and an intensity table (gamma, brightness, contrast), per sample.  A training augmentation; the reference
+ * has no counterpart.  A stage of its own directly BEHIND oct_elastic_batch and in front of oct_warp_batch.  Labels never
+ * change, so the call takes none.  Integer arithmetic only, and the weights and the table are INPUT: the kernel, the numpy
+ * restatement (common/augmentation.py photometric_reference) and the host generator give the same bytes whatever the host's
+ * exp and pow do.  Stand-alone: no handle, no allocation, no atomics, one asynchronous launch on `stream`, graph-capturable.
+ * Per sample b, op = ops_dev[b]; per pixel (y, x) and channel, in this order (`>>` a shift, `//` floor division):
+ *   1. blur (kind & 1), R = radius: replicate border, clamp(i) = min(max(i, 0), n - 1) on the axis
+ *        h(y, x) = sum_{k=-R..R} w[|k|] src(y, clamp(x + k))                         (<= 65280, kept exact)
+ *        v0 = (sum_{j=-R..R} w[|j|] h(clamp(y + j), x) + 32768) >> 16;     without the flag v0 = src(y, x)
+ *   2. shadows (kind & 2): g_s(x) = 256 - (strength_s max(0, hw_s - |x - cx_s|)) // hw_s for s < n_shadows;
+ *        g(y, x) = min over the s with y >= y0_s of g_s(x), 256 when there is none;  v1 = (v0 g + 128) >> 8
+ *   3. table (kind & 4): out = lut[v1];    without the flag out = v1
+ *   kind 0: the sample is copied.
+ *   Ranges (OCT_PHOTO_*): H, W <= 16384; kind 0..7; radius 0..8; w[0] + 2 sum_{k>=1} w[k] = 256 and w[k] = 0 for k > radius
+ *     (then v0 <= 255); n_shadows 0..4; cx any int16 (it may lie outside the image); hw 1..4096; y0 0..16384; strength
+ *     0..256 (then 0 <= g <= 256 and v1 <= v0); reserved 0.  The ranges are only visible on the device: REFUSE anything
+ *     outside them on the host, before upload (common/augmentation.py check_photo_ops).  A kind outside 0..7, a radius above
+ *     8, n_shadows above 4 or a live hw below 1 is TREATED AS kind 0 (no device-side flag); no other value can make the
+ *     kernel read or write outside its buffers.
+ *   Nothing depends on b, B or the launch geometry: repeated calls give identical bytes.
+ * Errors (negative, nothing launched): null x_dev / ops_dev / out_dev, ops_dev not 4-byte aligned, non-positive sizes, B >
+ * 65535, H, W or C > 16384, H*W*C >= 2^31, out_dev overlapping x_dev or ops_dev (the blur gathers: the stage cannot run in
+ * place). */
+#define OCT_PHOTO_BLUR        1
+#define OCT_PHOTO_SHADOW      2
+#define OCT_PHOTO_LUT         4
+#define OCT_PHOTO_MAX_DIM     16384
+#define OCT_PHOTO_MAX_RADIUS  8
+#define OCT_PHOTO_MAX_SHADOWS 4
+typedef struct oct_photo_op {    /* one per sample of the batch, 320 bytes, in DEVICE memory */
+    int kind;                    /* flags: 1 blur, 2 shadows, 4 table; 0: the sample is copied through */
+    int radius;                  /* R of the blur, 0..8 */
+    unsigned short w[9];         /* blur weights: w[k] at offsets +-k */
+    unsigned short n_shadows;    /* 0..4 */
+    short cx[4];                 /* shadow centre column */
+    short hw[4];                 /* shadow half-width in pixels, 1..4096 */
+    short y0[4];                 /* first shadowed row, 0..16384 */
+    unsigned short strength[4];  /* 0..256: the gain at the centre column is 256 - strength */
+    unsigned reserved;           /* 0 */
+    unsigned char lut[256];      /* the intensity table */
+} oct_photo_op;
+int oct_photo_batch(const unsigned char* x_dev, const oct_photo_op* ops_dev, int B, int H, int W, int C,
+                    unsigned char* out_dev, oct_stream_t stream);
 
 /* ---- edge weight map: per-pixel loss weights from the labels, on the device ----
  * weights[b, y, x] = lut[idx] of the capped squared distance to the nearest class border of image b -- the weight map of the

@@ -174,6 +174,7 @@ SYMBOLS = [
     ("oct_contrast_workspace_bytes", C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, _P(ContrastDesc)]),
     ("oct_contrast_batch", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _P(ContrastDesc), C.c_void_p, C.c_size_t,
                                      C.c_void_p, C.c_void_p]),
+    ("oct_photo_batch", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     ("oct_pad_batch", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                 C.c_float, C.c_void_p, C.c_void_p]),
     ("oct_crop_batch", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,

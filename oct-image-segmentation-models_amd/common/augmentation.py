@@ -711,3 +711,234 @@ def elastic_sample(image_u8, mask, op):
         else:
             moved[outside] = fill
     return out, moved
+
+
+# ---- photometric augmentation: descriptors, parameter draws and the numpy restatement of oct_photo_batch (include/oct_unet.h) ----
+# A stage of its own directly BEHIND the elastic stage and in front of the warps, on the uint8 sample: a separable integer
+# blur, column shadows and a 256-entry intensity table (gamma, brightness, contrast), in that order.  Images only: labels
+# never change.  One descriptor per sample; the layout is the C struct oct_photo_op (320 bytes).  The weights and the table
+# are INPUT of the device and of the restatement alike, so both give the same bytes whatever the host's exp and pow do.
+PHOTO_OP_DTYPE = np.dtype([("kind", "<i4"), ("radius", "<i4"), ("w", "<u2", (9,)), ("n_shadows", "<u2"), ("cx", "<i2", (4,)),
+                           ("hw", "<i2", (4,)), ("y0", "<i2", (4,)), ("strength", "<u2", (4,)), ("reserved", "<u4"),
+                           ("lut", "u1", (256,))])
+PHOTO_BLUR, PHOTO_SHADOW, PHOTO_LUT = 1, 2, 4
+PHOTO_MAX_DIM, PHOTO_MAX_RADIUS, PHOTO_MAX_SHADOWS, PHOTO_MAX_HW, PHOTO_MAX_Y0 = 16384, 8, 4, 4096, 16384
+PHOTO_DRAWS = 24            # uniform numbers a sample takes from the generator's photometric stream, whatever it draws
+
+
+def check_photo_ops(ops, H=None, W=None) -> None:
+    """Refuse (``ValueError``) descriptors or image sizes outside what ``oct_photo_batch`` is defined for: the device cannot
+    report them.  ``kind``, ``radius``, ``n_shadows`` and ``reserved`` are held to their ranges in every descriptor; the
+    weights where the BLUR flag is set (``w[0] + 2 sum_{k>=1} w[k] = 256``, ``w[k] = 0`` for k > radius); ``hw``, ``y0`` and
+    ``strength`` of shadows 0..n_shadows-1 where the SHADOW flag is set (``cx`` is any int16)."""
+    ops = np.asarray(ops)
+    if ops.dtype != PHOTO_OP_DTYPE:
+        raise TypeError("photometric descriptors must be a PHOTO_OP_DTYPE array")
+    for name, v in (("H", H), ("W", W)):
+        if v is not None and not 1 <= int(v) <= PHOTO_MAX_DIM:
+            raise ValueError(f"photometric: {name} = {v} outside 1..{PHOTO_MAX_DIM}")
+    ops = ops.reshape(-1)
+    if ops.size == 0:
+        return
+    for name, hi in (("kind", PHOTO_BLUR | PHOTO_SHADOW | PHOTO_LUT), ("radius", PHOTO_MAX_RADIUS),
+                     ("n_shadows", PHOTO_MAX_SHADOWS), ("reserved", 0)):
+        if ops[name].min() < 0 or ops[name].max() > hi:
+            raise ValueError(f"photometric: descriptor {name} outside 0..{hi}")
+    blur = ops[(ops["kind"] & PHOTO_BLUR) != 0]
+    if blur.size:
+        w = blur["w"].astype(np.int64)
+        if (w[:, 0] + 2 * w[:, 1:].sum(axis=1) != 256).any():
+            raise ValueError("photometric: descriptor w must satisfy w[0] + 2 sum(w[1:]) = 256")
+        if (w * (np.arange(9)[None, :] > blur["radius"][:, None])).any():
+            raise ValueError("photometric: descriptor w[k] must be 0 for k > radius")
+    sh = ops[(ops["kind"] & PHOTO_SHADOW) != 0]
+    if sh.size:
+        live = np.arange(PHOTO_MAX_SHADOWS)[None, :] < sh["n_shadows"][:, None]
+        for name, lo, hi in (("hw", 1, PHOTO_MAX_HW), ("y0", 0, PHOTO_MAX_Y0), ("strength", 0, 256)):
+            v = sh[name].astype(np.int64)[live]
+            if v.size and (v.min() < lo or v.max() > hi):
+                raise ValueError(f"photometric: descriptor {name} outside {lo}..{hi}")
+
+
+def blur_weights(sigma: float):
+    """``(radius, w)`` of a Gaussian blur of standard deviation ``sigma`` pixels, 0 < sigma <= 8/3: R = min(8, ceil(3 sigma)),
+    g_k = exp(-k^2 / 2 sigma^2) over -R..R normalised to sum 1, ``w[k] = rint(256 g_k)`` for k >= 1 and
+    ``w[0] = 256 - 2 sum_{k>=1} w[k]`` (uint16 (9,), zero beyond R)."""
+    sigma = float(sigma)
+    if not 0.0 < sigma <= 8.0 / 3.0:
+        raise ValueError(f"blur sigma must be within (0, 8/3], got {sigma!r}")
+    R = min(PHOTO_MAX_RADIUS, int(np.ceil(3.0 * sigma)))
+    k = np.arange(-R, R + 1, dtype=np.float64)
+    g = np.exp(-(k * k) / (2.0 * sigma * sigma))
+    g /= g.sum()
+    w = np.zeros(9, dtype=np.int64)
+    w[1:R + 1] = np.rint(256.0 * g[R + 1:])
+    w[0] = 256 - 2 * w[1:].sum()
+    return R, w.astype(np.uint16)
+
+
+def photo_lut(gamma: float = 1.0, brightness: float = 0.0, contrast: float = 1.0) -> np.ndarray:
+    """The intensity table of contrast ``c`` about mid-grey, brightness ``beta`` (units of full scale) and ``gamma``, in
+    float64: ``lut[i] = rint(255 clip((i/255 - 0.5) c + 0.5 + beta, 0, 1) ** gamma)`` (uint8 (256,))."""
+    i = np.arange(256, dtype=np.float64) / 255.0
+    v = np.clip((i - 0.5) * float(contrast) + 0.5 + float(brightness), 0.0, 1.0) ** float(gamma)
+    return np.rint(255.0 * v).astype(np.uint8)
+
+
+_IDENTITY_LUT = np.arange(256, dtype=np.uint8)
+
+
+def _prob(args, key, what):
+    p = float(args.get(key, 1.0))
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"{what}: p must be within 0..1, got {args.get(key)!r}")
+    return p
+
+
+def _range(args, key, lo, hi, what, lo_open=False):
+    if key not in args:
+        raise ValueError(f"{what}: {key} is required")
+    a, b = _pair(args, key, None)
+    if not ((lo < a if lo_open else lo <= a) and a <= b <= hi):
+        raise ValueError(f"{what}: {key} must be (lo, hi) with {lo} {'<' if lo_open else '<='} lo <= hi <= {hi}, got {args[key]!r}")
+    return a, b
+
+
+def photometric_spec(args) -> dict:
+    """The validated ``photometric`` keyword of the generators and of ``TrainingParams`` as a dict.  Every part is optional
+    and off unless given: ``p`` (probability that a sample goes through the stage, default 1), ``gamma`` (lo, hi) within
+    0.25..4, ``brightness`` b within 0..1, ``contrast`` (lo, hi) within 0.25..4, ``blur`` {``p``, ``sigma`` (lo, hi) within
+    (0, 8/3]} and ``shadows`` {``p``, ``max_count`` 1..4 (default 1), ``width`` (lo, hi) half-widths in pixels within 1..4096,
+    ``strength`` (lo, hi) within 0..1, ``top`` (lo, hi) fractions of H within 0..1 (default (0, 0))}.  ``ValueError`` for
+    anything else, unknown keys included."""
+    if not isinstance(args, dict):
+        raise ValueError(f"photometric must be a dict of p, gamma, brightness, contrast, blur, shadows, got {args!r}")
+    known = {"p", "gamma", "brightness", "contrast", "blur", "shadows"}
+    if set(args) - known:
+        raise ValueError(f"photometric: unknown keys {sorted(set(args) - known)}")
+    spec = {"p": _prob(args, "p", "photometric"), "gamma": None, "brightness": None, "contrast": None, "blur": None,
+            "shadows": None}
+    if "gamma" in args:
+        spec["gamma"] = _range(args, "gamma", 0.25, 4.0, "photometric")
+    if "brightness" in args:
+        spec["brightness"] = _nonneg(args, "brightness", 1.0)
+    if "contrast" in args:
+        spec["contrast"] = _range(args, "contrast", 0.25, 4.0, "photometric")
+    for part, keys in (("blur", {"p", "sigma"}), ("shadows", {"p", "max_count", "width", "strength", "top"})):
+        sub = args.get(part)
+        if sub is None:
+            continue
+        what = f"photometric {part}"
+        if not isinstance(sub, dict):
+            raise ValueError(f"{what} must be a dict of {sorted(keys)}, got {sub!r}")
+        if set(sub) - keys:
+            raise ValueError(f"{what}: unknown keys {sorted(set(sub) - keys)}")
+        if part == "blur":
+            spec[part] = {"p": _prob(sub, "p", what), "sigma": _range(sub, "sigma", 0.0, 8.0 / 3.0, what, lo_open=True)}
+            continue
+        n = sub.get("max_count", 1)
+        if isinstance(n, bool) or int(n) != n or not 1 <= int(n) <= PHOTO_MAX_SHADOWS:
+            raise ValueError(f"{what}: max_count must be an integer in 1..{PHOTO_MAX_SHADOWS}, got {n!r}")
+        spec[part] = {"p": _prob(sub, "p", what), "max_count": int(n), "width": _range(sub, "width", 1.0, float(PHOTO_MAX_HW), what),
+                      "strength": _range(sub, "strength", 0.0, 1.0, what),
+                      "top": _range(dict(sub, top=sub.get("top", (0.0, 0.0))), "top", 0.0, 1.0, what)}
+    return spec
+
+
+def draw_photo_ops(spec, u, H, W):
+    """The descriptors of ``len(u)`` samples of H x W pixels from their ``PHOTO_DRAWS`` uniform numbers ``u[i]`` in [0, 1);
+    float64, rounded with ``np.rint``, as ``draw_warp_ops``.  ``spec``: what ``photometric_spec`` returns.
+      u[0] < p: the sample goes through the stage; otherwise, and where it then draws nothing, its ``kind`` is 0.
+      u[1], u[2], u[3]: gamma = lo (hi/lo)^u (log-uniform), beta = b (2u - 1), contrast = lo + (hi - lo) u ->
+        ``photo_lut``; the LUT flag only where the table is not the identity.
+      u[4] < blur p: sigma = lo + (hi - lo) u[5] -> ``blur_weights``.
+      u[6] < shadows p: count = 1 + floor(u[7] max_count); shadow s from u[8 + 4s .. 11 + 4s]: cx = floor(u W),
+        hw = max(1, rint(width)), y0 = floor(H top), strength = rint(256 strength), each range drawn as lo + (hi - lo) u."""
+    H, W = int(H), int(W)
+    u = np.asarray(u, dtype=np.float64).reshape(-1, PHOTO_DRAWS)
+    ops = np.zeros(u.shape[0], dtype=PHOTO_OP_DTYPE)
+    lin = lambda r, t: r[0] + (r[1] - r[0]) * t        # noqa: E731
+    for i in np.flatnonzero(u[:, 0] < spec["p"]):
+        op, ui, kind = ops[i], u[i], 0
+        if spec["gamma"] is not None or spec["brightness"] is not None or spec["contrast"] is not None:
+            gamma = 1.0 if spec["gamma"] is None else float(np.exp(lin(np.log(spec["gamma"]), ui[1])))
+            beta = 0.0 if spec["brightness"] is None else spec["brightness"] * (2.0 * ui[2] - 1.0)
+            c = 1.0 if spec["contrast"] is None else lin(spec["contrast"], ui[3])
+            lut = photo_lut(gamma, beta, c)
+            if (lut != _IDENTITY_LUT).any():
+                kind |= PHOTO_LUT
+                op["lut"] = lut
+        if spec["blur"] is not None and ui[4] < spec["blur"]["p"]:
+            kind |= PHOTO_BLUR
+            op["radius"], op["w"] = blur_weights(lin(spec["blur"]["sigma"], ui[5]))
+        sh = spec["shadows"]
+        if sh is not None and ui[6] < sh["p"]:
+            kind |= PHOTO_SHADOW
+            n = min(sh["max_count"], 1 + int(np.floor(ui[7] * sh["max_count"])))
+            op["n_shadows"] = n
+            for s in range(n):
+                d = ui[8 + 4 * s:12 + 4 * s]
+                op["cx"][s] = min(W - 1, int(np.floor(d[0] * W)))
+                op["hw"][s] = max(1, int(np.rint(lin(sh["width"], d[1]))))
+                op["y0"][s] = int(np.floor(H * lin(sh["top"], d[2])))
+                op["strength"][s] = int(np.rint(256.0 * lin(sh["strength"], d[3])))
+        op["kind"] = kind
+        if not kind & PHOTO_LUT:
+            op["lut"] = _IDENTITY_LUT
+    check_photo_ops(ops, H, W)
+    return ops
+
+
+def shadow_gain(H: int, W: int, op) -> np.ndarray:
+    """g(y, x) of descriptor ``op``'s shadows, int64 (H, W): the minimum over the shadows with y >= y0_s of
+    ``256 - (strength_s max(0, hw_s - |x - cx_s|)) // hw_s``, 256 where there is none."""
+    g = np.full((int(H), int(W)), 256, dtype=np.int64)
+    x, y = np.arange(int(W), dtype=np.int64), np.arange(int(H), dtype=np.int64)
+    for s in range(int(op["n_shadows"])):
+        hw = int(op["hw"][s])
+        gs = 256 - (int(op["strength"][s]) * np.maximum(0, hw - np.abs(x - int(op["cx"][s])))) // hw
+        g = np.where((y >= int(op["y0"][s]))[:, None], np.minimum(g, gs[None, :]), g)
+    return g
+
+
+def _photo_image(img, op):
+    """One (H, W, C) uint8 image through descriptor ``op``: blur, shadows, table."""
+    kind, H, W = int(op["kind"]), img.shape[0], img.shape[1]
+    v = img.astype(np.int64)
+    if kind & PHOTO_BLUR:
+        R, w = int(op["radius"]), op["w"].astype(np.int64)
+        cols = np.clip(np.arange(-R, W + R), 0, W - 1)
+        rows = np.clip(np.arange(-R, H + R), 0, H - 1)
+        src = v[:, cols]
+        h = sum(w[abs(k)] * src[:, R + k:R + k + W] for k in range(-R, R + 1))       # <= 65280: exact
+        h = h[rows]
+        v = (sum(w[abs(j)] * h[R + j:R + j + H] for j in range(-R, R + 1)) + 32768) >> 16
+    if kind & PHOTO_SHADOW:
+        v = (v * shadow_gain(H, W, op)[..., None] + 128) >> 8
+    if kind & PHOTO_LUT:
+        v = op["lut"][v]
+    return v.astype(np.uint8)
+
+
+def photometric_reference(images_u8, ops):
+    """What ``oct_photo_batch`` computes, by its definition in include/oct_unet.h, vectorised in int64: (B,H,W,C) uint8 ->
+    (B,H,W,C) uint8.  Refuses what the device entry point is not defined for (``check_photo_ops``)."""
+    images_u8 = np.asarray(images_u8)
+    if images_u8.dtype != np.uint8 or images_u8.ndim != 4:
+        raise TypeError("photometric_reference needs (B,H,W,C) uint8 images")
+    ops = np.asarray(ops)
+    B, H, W, _ = images_u8.shape
+    check_photo_ops(ops, H, W)
+    if ops.shape != (B,):
+        raise ValueError("one descriptor per sample")
+    out = np.array(images_u8)
+    for b, op in enumerate(ops):
+        if op["kind"]:
+            out[b] = _photo_image(images_u8[b], op)
+    return out
+
+
+def photometric_sample(image_u8, op):
+    """The host generator's side of the stage: one (H,W,C) uint8 image through ``photometric_reference``."""
+    op = np.asarray(op, dtype=PHOTO_OP_DTYPE).reshape(1)
+    return photometric_reference(np.asarray(image_u8)[None], op)[0]

@@ -34,7 +34,13 @@ every sample of an augmenting generator is deformed with probability ``p``.  Its
 a THIRD stream, ``SeedSequence(seed).spawn(2)[1]``, handed out like the warps' (global sample walk, or one table entry per
 pair); the other two streams do not notice.  The host path deforms the uint8 sample (``augmentation.elastic_sample``) before the
 list's function sees ``float32(u8) / 255``; ``next_batch_aug`` returns the descriptors as a fifth array (the fourth is then
-``None`` for a list without a warp)."""
+``None`` for a list without a warp).
+
+``photometric`` (a dict, ``augmentation.photometric_spec``) puts blur, column shadows and a gamma / brightness / contrast
+table directly BEHIND the elastic stage and in front of the list's own augmentation, on the uint8 sample; labels never
+change.  Its ``PHOTO_DRAWS`` numbers per sample come from a FOURTH stream, ``SeedSequence(seed).spawn(3)[2]``, handed out
+like the elastic stream's; the other three do not notice.  ``next_batch_aug`` returns the descriptors as a sixth array, with
+``None`` in the unused earlier positions."""
 from __future__ import annotations
 
 import logging as log
@@ -50,7 +56,8 @@ from . import augmentation
 class BatchGenerator:
     def __init__(self, images: np.ndarray, labels: np.ndarray, batch_size: int, aug_fn_args: List[Tuple],
                  aug_mode: str, aug_probs: Tuple, aug_fly: bool, preprocess_input_fn: Callable,
-                 seed: Optional[int] = None, device_aug: bool = False, elastic: Optional[dict] = None):
+                 seed: Optional[int] = None, device_aug: bool = False, elastic: Optional[dict] = None,
+                 photometric: Optional[dict] = None):
         if aug_mode not in ("none", "one", "all"):
             log.error(f"Unrecognized augmentation mode: {aug_mode}. Allowed values: 'none', 'one', 'all'. Exiting...")
             exit(1)
@@ -100,6 +107,18 @@ class BatchGenerator:
             self._elastic_rng = np.random.default_rng(np.random.SeedSequence(seed).spawn(2)[1])
             if aug_fly is False:
                 self._elastic_table = self._elastic_rng.random((self.total_full_images, self.total_augs, augmentation.ELASTIC_DRAWS))
+        self.photometric = None     # the validated ``photometric`` keyword: the stage behind the elastic one
+        if photometric is not None:
+            if aug_mode == "none":
+                raise ValueError('photometric needs an augmentation mode: for otherwise un-augmented samples use aug_mode '
+                                 '"one" with a single "no_augmentation" entry')
+            if self.images_u8.dtype != np.uint8:
+                raise ValueError(f"photometric needs a uint8 image array, the dataset holds {self.images_u8.dtype}")
+            self.photometric = augmentation.photometric_spec(photometric)
+            # its parameter stream: the third child of the seed (the warps' is the first, the elastic stage's the second)
+            self._photo_rng = np.random.default_rng(np.random.SeedSequence(seed).spawn(3)[2])
+            if aug_fly is False:
+                self._photo_table = self._photo_rng.random((self.total_full_images, self.total_augs, augmentation.PHOTO_DRAWS))
         if aug_mode != "none" and self.aug_ops is None:
             self._setup_host_aug()
         self.handle_epoch_end()
@@ -117,19 +136,26 @@ class BatchGenerator:
         for i in range(self.total_full_images):
             for j, (aug_fn, aug_arg) in enumerate(self.aug_fn_args):
                 aug_arg = self._with_warp_op(j, aug_arg, None if self.warp_ops is None else self._warp_table[i, j])
-                img, lab = self._deformed(i, None if self.elastic is None else self._elastic_table[i, j])
+                img, lab = self._deformed(i, None if self.elastic is None else self._elastic_table[i, j],
+                                          None if self.photometric is None else self._photo_table[i, j])
                 aug_images[i, j], aug_labels[i, j] = aug_fn(img, lab, aug_arg)
         return aug_images, aug_labels
 
-    def _deformed(self, ind, u):
+    def _deformed(self, ind, u, pu=None):
         """Image ``ind`` in [0, 1] and its labels as the list's function gets them: through the elastic stage where it is
-        configured and the sample's uniform numbers ``u`` say so."""
+        configured and the sample's uniform numbers ``u`` say so, then through the photometric stage likewise (``pu``)."""
+        img8, lab = None, self.labels[ind]
         if self.elastic is not None:
             op = augmentation.draw_elastic_ops(self.elastic, u)
             if op["kind"][0]:
-                img, lab = augmentation.elastic_sample(self.images_u8[ind], self.labels[ind], op)
-                return img.astype(np.float32) / np.float32(255.0), lab
-        return self.images[ind], self.labels[ind]
+                img8, lab = augmentation.elastic_sample(self.images_u8[ind], lab, op)
+        if self.photometric is not None:
+            op = augmentation.draw_photo_ops(self.photometric, pu, self.image_height, self.image_width)
+            if op["kind"][0]:
+                img8 = augmentation.photometric_sample(self.images_u8[ind] if img8 is None else img8, op)
+        if img8 is None:
+            return self.images[ind], lab
+        return img8.astype(np.float32) / np.float32(255.0), lab
 
     def _with_warp_op(self, j, aug_arg, u):
         """``aug_arg`` of augmentation ``j`` with the sample's warp descriptor, drawn from its uniform numbers ``u``, under
@@ -155,7 +181,8 @@ class BatchGenerator:
             if self.warp_ops is not None:       # every sample takes its numbers, whatever its augmentation
                 aug_arg = self._with_warp_op(j, aug_arg, self._warp_rng.random(augmentation.WARP_DRAWS))
             # (likewise: deformed or not, a sample takes its numbers from the elastic stream)
-            img, lab = self._deformed(ind, None if self.elastic is None else self._elastic_rng.random(augmentation.ELASTIC_DRAWS))
+            img, lab = self._deformed(ind, None if self.elastic is None else self._elastic_rng.random(augmentation.ELASTIC_DRAWS),
+                                      None if self.photometric is None else self._photo_rng.random(augmentation.PHOTO_DRAWS))
             img, lab = aug_fn(img, lab, aug_arg)
         else:
             img, lab = self.aug_images[ind, j], self.aug_labels[ind, j]
@@ -226,7 +253,8 @@ class BatchGenerator:
         A list with a ``column_shift`` / ``affine`` returns a fourth array, one ``augmentation.WARP_OP_DTYPE`` descriptor per
         sample (kind 0 for a sample that is not warped), drawn for the GLOBAL batch and sliced like the others.  With
         ``elastic`` a fifth, one ``augmentation.ELASTIC_OP_DTYPE`` descriptor per sample drawn and sliced the same way; the
-        fourth position then holds ``None`` for a list without a warp."""
+        fourth position then holds ``None`` for a list without a warp.  With ``photometric`` a sixth, one
+        ``augmentation.PHOTO_OP_DTYPE`` descriptor per sample, likewise; unused earlier positions hold ``None``."""
         if self.aug_ops is None:
             raise TypeError("next_batch_aug needs device_aug=True, an augmentation mode and augmentations the device "
                             "implements (augmentation.aug_ops_from)")
@@ -258,10 +286,17 @@ class BatchGenerator:
         if self.elastic is not None:
             u = self._elastic_rng.random((B, augmentation.ELASTIC_DRAWS)) if self.aug_fly else self._elastic_table[idx, j]
             eops = augmentation.draw_elastic_ops(self.elastic, u)
+        pops = None
+        if self.photometric is not None:
+            u = self._photo_rng.random((B, augmentation.PHOTO_DRAWS)) if self.aug_fly else self._photo_table[idx, j]
+            pops = augmentation.draw_photo_ops(self.photometric, u, self.image_height, self.image_width)
         if shard is not None:
             idx, ops = idx[shard[0]:shard[1]], ops[shard[0]:shard[1]]
             wops = None if wops is None else wops[shard[0]:shard[1]]
             eops = None if eops is None else eops[shard[0]:shard[1]]
+            pops = None if pops is None else pops[shard[0]:shard[1]]
+        if pops is not None:
+            return self.images_u8[idx], self.sparse_labels()[idx], ops, wops, eops, pops
         if eops is not None:
             return self.images_u8[idx], self.sparse_labels()[idx], ops, wops, eops
         if wops is not None:
@@ -281,7 +316,8 @@ class DataGenerator:
 
     def __init__(self, images: np.ndarray, labels: np.ndarray, batch_size: int, aug_fn_args: List[Tuple],
                  aug_mode: str, aug_probs: Tuple, aug_fly: bool, preprocess_input_fn: Callable,
-                 seed: Optional[int] = None, device_aug: bool = False, elastic: Optional[dict] = None):
+                 seed: Optional[int] = None, device_aug: bool = False, elastic: Optional[dict] = None,
+                 photometric: Optional[dict] = None):
         # uint8 fast path (the /255 happens on the GPU) only without augmentation AND only for uint8 storage: the
         # reference divides by 255 whatever the dataset's dtype (data_generator.py:76), so any other dtype goes through
         # get_batch_list(), which computes float32(images) / 255 on the host
@@ -290,7 +326,7 @@ class DataGenerator:
         self.batch_gen = BatchGenerator(images=images, labels=labels, batch_size=batch_size, aug_fn_args=aug_fn_args,
                                         aug_mode=aug_mode, aug_probs=aug_probs, aug_fly=aug_fly,
                                         preprocess_input_fn=preprocess_input_fn, seed=seed, device_aug=device_aug and is_u8,
-                                        elastic=elastic)
+                                        elastic=elastic, photometric=photometric)
         # augmentation on the device (Model.fit: uint8 upload + oct_augment_batch) where it was asked for and is possible
         self.oct_device_aug = self.batch_gen.aug_ops is not None
         if device_aug and aug_mode != "none" and not self.oct_device_aug:

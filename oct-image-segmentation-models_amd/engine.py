@@ -799,8 +799,21 @@ class UNetEngine:
                   _ptr(lab_out), self._stream())
         return x_out, lab_out
 
+    def photometric(self, x_u8: torch.Tensor, ops, out=None) -> torch.Tensor:
+        """The photometric augmentation on the device (``oct_photo_batch``): (B,H,W,C) uint8 images and one
+        ``common.augmentation.PHOTO_OP_DTYPE`` descriptor per sample -> uint8 images of the same shape through each sample's
+        blur, shadows and intensity table; labels never change, so the call takes none.  ``ops``: a numpy descriptor array
+        (validated with ``check_photo_ops``, then uploaded) or a uint8 device tensor of B*320 bytes that already holds
+        validated descriptors.  ``out``: optional tensor to write into, never ``x_u8`` itself (the blur gathers).
+        Asynchronous on the current stream."""
+        from .common.augmentation import PHOTO_OP_DTYPE, check_photo_ops
+        ops, x_out, _ = self._stage_io("photometric", x_u8, None, ops, "PHOTO_OP_DTYPE", PHOTO_OP_DTYPE, check_photo_ops,
+                                       None if out is None else (out, None), torch.uint8)
+        _hip.call("oct_photo_batch", self.device, x_u8.data_ptr(), ops.data_ptr(), *x_u8.shape, x_out.data_ptr(), self._stream())
+        return x_out
+
     def _stage_io(self, what, x_u8, labels, ops, op_name, op_dtype, check, out, x_dtype):
-        """``augment`` / ``warp`` / ``elastic`` (``what``): validates images, labels, descriptors (a numpy array: also by ``check(ops, H, W)``, then
+        """``augment`` / ``warp`` / ``elastic`` / ``photometric`` (``what``): validates images, labels, descriptors (a numpy array: also by ``check(ops, H, W)``, then
         uploaded) and ``out``, and makes what of it is missing.  Returns ``(descriptor bytes, x_out, labels_out or None)``."""
         u8 = dict(device=self.device, dtype=torch.uint8)
         _hip.expect(x_u8, f"{what}: images (B,H,W,C)", shape=(None, None, None, None), **u8)

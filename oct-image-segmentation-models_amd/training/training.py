@@ -62,6 +62,10 @@ def save_training_params_file(save_foldername: Path, model_summary: str, model_c
     for key, val in (getattr(train_params, "elastic", None) or {}).items():
         attrs[f"elastic_param: {key}"] = (np.array(val, dtype="S100") if isinstance(val, str) else
                                           val if np.isscalar(val) else np.asarray(val, dtype=np.float64))
+    # the photometric stage likewise: "photometric_param: <key>"; a part that is itself a dict as its repr
+    for key, val in (getattr(train_params, "photometric", None) or {}).items():
+        attrs[f"photometric_param: {key}"] = (np.array(str(val), dtype="S200") if isinstance(val, (str, dict)) else
+                                              val if np.isscalar(val) else np.asarray(val, dtype=np.float64))
     for key, val in opt.get_config().items():
         attrs["opt_param: " + key] = np.bytes_(str(val)) if isinstance(val, (dict, str)) else val
     # the shape of the Dice term: only the keys that were given (loss_fn_kwargs, or apply_class_weight's), so that a run
@@ -227,17 +231,20 @@ def train_model(training_params: TrainingParams, mlflow_params=None):
     # run gets one OS-entropy seed from rank 0, not one per rank
     seed = parallel.shared_seed(training_params.seed) if parallel.world_size() > 1 else training_params.seed
     elastic = getattr(training_params, "elastic", None)      # the stage goes wherever the list's augmentations go
+    photometric = getattr(training_params, "photometric", None)      # (likewise)
     train_gen = data_gen.DataGenerator(train_images, train_labels, batch_size, training_params.aug_fn_args, training_params.aug_mode,
                                        training_params.aug_probs, training_params.aug_fly,
                                        model_container.get_preprocess_input_fn(), seed=seed,
-                                       device_aug=training_params.aug_device, elastic=elastic)
+                                       device_aug=training_params.aug_device, elastic=elastic,
+                                       photometric=photometric)
     val_gen = data_gen.DataGenerator(val_images, val_labels, batch_size,
                                      training_params.aug_fn_args if aug_val_mode != "none" else [], aug_val_mode,
                                      training_params.aug_probs if aug_val_mode != "none" else (),
                                      training_params.aug_fly if aug_val_mode != "none" else False,
                                      model_container.get_preprocess_input_fn(),
                                      seed=None if seed is None else seed + 1, device_aug=training_params.aug_device,
-                                     elastic=elastic if aug_val_mode != "none" else None)
+                                     elastic=elastic if aug_val_mode != "none" else None,
+                                     photometric=photometric if aug_val_mode != "none" else None)
 
     for name, gen in (("training", train_gen), ("validation", val_gen)):
         if batch_size > gen.get_total_samples():

@@ -21,7 +21,17 @@ class TrainingParams:
                  early_stopping: bool = True, restore_best_weights: bool = True, patience: int = 50,
                  seed: Union[int, None] = None, aug_device: bool = False, pad_mode: Union[str, None] = None,
                  pad_value=0, ignore_label: Union[int, None] = None, apply_class_weight: bool = False,
-                 fit_temperature: bool = False, elastic: Union[dict, None] = None, contrast: Union[dict, None] = None):
+                 fit_temperature: bool = False, elastic: Union[dict, None] = None, contrast: Union[dict, None] = None,
+                 photometric: Union[dict, None] = None):
+        # extension: photometric augmentation (common.augmentation.photometric_spec: p, gamma, brightness, contrast, blur,
+        # shadows) of every sample the augmentation list applies to, directly behind the elastic stage; on the device with
+        # aug_device, on the host without.  None: no such stage, nothing changes
+        if photometric is not None:
+            aug.photometric_spec(photometric)       # (ValueError for anything outside the definition)
+            if aug_mode == "none":
+                raise ValueError('photometric needs an augmentation mode: for otherwise un-augmented samples use aug_mode '
+                                 '"one" with a single "no_augmentation" entry')
+        self.photometric = None if photometric is None else dict(photometric)
         # extension: contrast normalisation (common.utils.check_contrast: {"method": "clahe" | "stretch", "tiles", "clip" |
         # "percentiles"}).  train_model normalises the training and validation images once, directly
         # after loading them (uint8 datasets only), so the run equals one on a dataset holding contrast_reference(images); the
